@@ -10,8 +10,12 @@ all-reduce of the parameter gradients.  Inputs are resident in HBM before the ti
     python bench.py                       # 1 GPU, default steps
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+    python bench.py --full                # + the other legs, per-kernel timing, rooflines and the CPU baseline
+    python bench.py --dump-outputs DIR    # + what the last timed step computed, as DIR/<name>.npy
 
-Prints ONE JSON line on rank 0 (contract: task description / DESIGN.md §Measurement).
+A plain run only sets up, warms up (cfg2-type workloads: the eager and library-default legs run untimed, as the warm-up the
+headline has always followed), times the K steps and prints the headline; everything else it can measure (the figures of
+those legs, the per-kernel / roofline figures, the bf16 k-NN leg of cfg3 / cfg5, the CPU baseline) runs with --full.  Prints ONE JSON line on rank 0 (contract: task description / DESIGN.md §Measurement).
 """
 from __future__ import annotations
 
@@ -52,6 +56,27 @@ BACKBONE_WORKLOADS = {
 PEAK_BF16_MFMA_TFLOPS = 2500.0     # dense bf16 matrix peak (no sparsity)
 PEAK_FP32_MFMA_TFLOPS = 157.3      # MI355X_MICROARCH.md: dense fp32 matrix peak (= vector peak)
 PEAK_HBM_GBPS = 8000.0
+DUMP_BUDGET_BYTES = 60_000_000     # --dump-outputs: all .npy files of one run together stay below 64 MB
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write each tensor of ``arrays`` (name -> tensor) as ``path/<name>.npy``, floating point as float32,
+    integer (edge lists) as float64.  When all of them together exceed DUMP_BUDGET_BYTES, every array larger than its
+    equal share of the budget is replaced by a fixed sample of its flattened elements: positions drawn without replacement
+    by a generator seeded with 0, in ascending order — the same positions in every run with the same arguments."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    items = [(name, t.detach().float() if t.is_floating_point() else t.detach().double()) for name, t in arrays.items()]
+    total = sum(t.numel() * t.element_size() for _, t in items)
+    share = DUMP_BUDGET_BYTES // max(len(items), 1)
+    for name, t in items:
+        if total > DUMP_BUDGET_BYTES and t.numel() * t.element_size() > share:
+            n = share // t.element_size()
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:n].sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+    print(f"[bench] wrote {len(items)} output arrays to {path}" + (" (sampled: larger than the budget)"
+                                                                   if total > DUMP_BUDGET_BYTES else ""), file=sys.stderr)
 
 
 def build_modules(w, device):
@@ -245,8 +270,8 @@ def run_backbone(args):
     build_s = time.perf_counter() - t_build
     gen = torch.Generator().manual_seed(100 + rank)
     img = torch.randn(B, 3, size, size, generator=gen).to(dev)
-    steps = args.steps if args.steps != 50 else (10 if kind == "forward" else 6)      # default K sized to finish in minutes
-    warmup = args.warmup if args.warmup != 10 else 3
+    steps = args.steps if args.steps is not None else (10 if kind == "forward" else 6)      # default K sized to finish in minutes
+    warmup = args.warmup if args.warmup is not None else 3
     head = tgt = None
     n_graph = sum(1 for m in net.modules() if type(m).__name__ in ("Grapher", "GrapherLabel"))
 
@@ -282,12 +307,16 @@ def run_backbone(args):
         return {k: dict(us_per_step=round(1e3 * v[0] / n, 1), launches_per_step=v[1] // n) for k, v in prof.items() if v[1]}, work
 
     legs = {}
+    last = {}                                # what the last step handed its caller (a captured step: the graph's static outputs)
     if kind == "forward":
         net.eval()
 
         def fwd():
             with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
-                return net(img)
+                out = net(img)
+                if args.dump_outputs:
+                    last["out"] = out             # no_grad: no autograd graph attached
+                return out
         names = ["exact", "bf16"] if args.knn == "both" else [args.knn]
         launch_desc = {}
         for name in names:
@@ -322,7 +351,11 @@ def run_backbone(args):
                     if not args.no_tune:
                         tunable.tuning_enable(True)
             el = timed(step)
-            kernels, work = profile(fwd)
+            if args.dump_outputs and rank == 0 and name == names[0]:
+                # the forward's triple: label tokens (B, n_classes, C4), gap (B, C4), the last label graph's edge list
+                dump_outputs(args.dump_outputs, {n_: t for n_, t in zip(("label_tokens", "gap", "edge_index"), last["out"])
+                                                 if torch.is_tensor(t)})
+            kernels, work = profile(fwd) if args.full else (None, None)
             legs[name] = (el, kernels, work)
         fused.KNN_BF16 = names[0] == "bf16"
         headline = names[0]
@@ -349,6 +382,8 @@ def run_backbone(args):
             bucket.release(prezero=True)
             losses = head.forward_train(net(img), tgt)
             (losses["bce_loss"] + losses["asy_loss"]).backward()
+            if args.dump_outputs:
+                last.update({k: v.detach() for k, v in losses.items()})
             bucket.wait()
             if args.foreach_optimizer:
                 torch.nn.utils.clip_grad_norm_(params, 5.0)
@@ -356,7 +391,11 @@ def run_backbone(args):
                 bucket.clip_grad_norm_(5.0)          # the same clipping as a norm + a scale launch on the flat buffer
             opt.step()
         el = timed(train_step)
-        kernels, work = profile(train_step, 1)
+        if args.dump_outputs and rank == 0:
+            # the step's losses, the clipped (all-reduced) gradients it applied and the parameters it left behind
+            dump_outputs(args.dump_outputs, dict(bce_loss=last["bce_loss"], asy_loss=last["asy_loss"], param_grads=bucket.flat,
+                                                 params=torch.cat([p.detach().reshape(-1) for p in params])))
+        kernels, work = profile(train_step, 1) if args.full else (None, None)
         legs["train"] = (el, kernels, work)
         if args.amp != "none":
             # Extra leg: the recipe the reference ships (configs/gkgnet/gkgnet_coco_576.py:146, fp16 AMP with a dynamic loss
@@ -385,6 +424,7 @@ def run_backbone(args):
 
     if rank == 0:
         el, kernels, work = legs[headline]
+        kernels, work = kernels or {}, work or {}                    # None: no per-kernel pass (plain run)
         ms_step = 1e3 * el / steps
         value = world * B * steps / el
         roof = None
@@ -423,16 +463,17 @@ def run_backbone(args):
                                                ("none (1 GPU)" if world == 1 else
                                                 f"chunked {'RCCL' if backend == 'nccl' else backend} all-reduces started from "
                                                 f"post-accumulate hooks during backward"))),
-                   roofline=roof, roofline_hbm=roof_hbm, hip_kernels=kernels,
                    peak_mem_GiB=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2), model_build_s=round(build_s, 1))
+        if args.full:
+            res.update(roofline=roof, roofline_hbm=roof_hbm, hip_kernels=kernels)
         if "amp" in legs:
             res[f"ms_per_step_amp_{args.amp}"] = round(1e3 * legs["amp"][0] / steps, 3)
         if kind == "forward":
             for name, (e2, k2, w2) in legs.items():
                 res[f"ms_per_step_knn_{name}"] = round(1e3 * e2 / steps, 3)
-                if "knn_tile" in k2:
+                if k2 and "knn_tile" in k2:
                     res[f"knn_us_per_step_{name}"] = k2["knn_tile"]["us_per_step"]
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             sb = 1 if kind == "forward" else 2
             res["cpu_baseline"] = cpu_baseline_backbone(net, head, img[:sb], None if tgt is None else tgt[:sb], kind)
             res["cpu_baseline"]["host_physical_cores"] = physical_cores()
@@ -445,8 +486,13 @@ def run_backbone(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 50; cfg3 / cfg5: 10; cfg4: 6)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed warm-up steps before them (default: 10; cfg3 / cfg4 / cfg5: 3)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the legs beside the headline (eager launches, library-default GEMM selection, bf16 k-NN for "
+                         "cfg3 / cfg5), per-kernel timing and rooflines, and the CPU baseline (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, < 64 MB)")
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS) + sorted(BACKBONE_WORKLOADS))
     ap.add_argument("--batch", type=int, default=None, help="images per GPU (default: 32; cfg5: 16)")
     ap.add_argument("--sync-bn", action="store_true", help="SyncBatchNorm across ranks (reference DDP semantics)")
@@ -460,10 +506,13 @@ def main():
                     help="cfg4: also time the train step under autocast (fp16 with a dynamic loss scale = the reference's shipped recipe); reported beside the fp32 value")
     ap.add_argument("--foreach-optimizer", action="store_true", help="cfg4: torch's multi-tensor clip_grad_norm_ + foreach AdamW instead of the flat-buffer clip + fused AdamW")
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel eagerly instead of replaying a hipGraph")
-    ap.add_argument("--knn", default="both", choices=["both", "exact", "bf16"],
+    ap.add_argument("--knn", default=None, choices=["both", "exact", "bf16"],
                     help="cfg3 / cfg5 (bf16 autocast): which k-NN legs to time — exact (the bit-exact index contract, same graphs as "
-                         "fp32: the default mode of the library) and / or bf16 (the opt-in GKG_KNN_BF16_CONTRACT contraction)")
+                         "fp32: the default mode of the library) and / or bf16 (the opt-in GKG_KNN_BF16_CONTRACT contraction); "
+                         "default: exact, with --full both")
     args = ap.parse_args()
+    if args.knn is None:
+        args.knn = "both" if args.full else "exact"
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus))         # no launcher: be the launcher (this process never touches the GPU)
@@ -471,6 +520,10 @@ def main():
         return run_backbone(args)
     if args.batch is None:
         args.batch = 32
+    if args.steps is None:
+        args.steps = 50
+    if args.warmup is None:
+        args.warmup = 10
     from gkgnet_amd import _lib, layers, parallel
     rank, world, local = parallel.init_distributed()
     if world != args.gpus:
@@ -512,6 +565,10 @@ def main():
         e2, _ = label(e, out)
         torch.autograd.backward([out, e2], [cot_x, cot_e])
         bucket.pack()
+        if args.dump_outputs:                    # what the caller receives (a captured step: the graph's static outputs);
+            # detached: holding the outputs themselves keeps this step's autograd graph alive into the next one, whose
+            # AccumulateGrad nodes then run on the wrong stream under capture (the process crashed)
+            state["out"], state["e2"] = out.detach(), e2.detach()
 
     def eager_step():
         compute()
@@ -530,7 +587,7 @@ def main():
     # Host-synchronising backends (gloo: the 1-GPU exercise) keep the collective outside the graph.
     state = {"reduce_in_graph": False}
 
-    def measure():
+    def measure(steps=None):
         """eager warm-up -> capture -> (multi-rank: replay-vs-eager vote) -> W untimed + K timed steps.  Returns
         (elapsed seconds of the K steps on this rank, captured graph or None)."""
         for _ in range(2):                   # eager warm-up (also where TunableOp, when on, tunes each GEMM shape once)
@@ -615,7 +672,7 @@ def main():
             torch.distributed.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(steps or args.steps):
             step()
         torch.cuda.synchronize()
         if world > 1:
@@ -631,6 +688,8 @@ def main():
     # same step without the hipGraph, launched op by op — host launch overhead included.  Reported beside the replayed value.
     # Measured FIRST, in a process that has not captured anything yet: once a hipGraph exists every eager call re-checks the
     # weight planes and clears the BN scratch (a replay may have run in between), which an eager-only user never pays.
+    # Every run launches these steps: they are also the untimed eager warm-up (collective included) that the capture and the
+    # timed steps below have always followed; the figure itself is reported with --full.
     for _ in range(10):
         eager_step()
     torch.cuda.synchronize()
@@ -641,8 +700,10 @@ def main():
     torch.cuda.synchronize()
     ms_eager = 1e3 * (time.perf_counter() - t0) / n_eager
 
-    # Leg 1: the GEMM library's default kernel selection — what a drop-in user gets without a tuning pass.
-    elapsed_no_tune, graph = measure()
+    # Leg 1: the GEMM library's default kernel selection — what a drop-in user gets without a tuning pass (the headline with
+    # --no-tune; reported with --full).  A plain run still runs it, at most 200 steps, as the warm-up the headline leg has always
+    # followed: without it the headline measured 0.5 % slower on the same box.
+    elapsed_no_tune, graph = measure(None if (args.full or args.no_tune) else min(args.steps, 200))
     elapsed = elapsed_no_tune
     if not args.no_tune:
         # Leg 2 (the headline unless --no-tune): the projections that are still plain library GEMMs get PyTorch's
@@ -656,54 +717,59 @@ def main():
         graph = None
         elapsed, graph = measure()
 
-    # Per-kernel timing for the roofline: the same step, launched eagerly with the library's HIP-event brackets
-    # on the launch stream (events cannot bracket individual nodes of a replayed graph).
-    prof_steps = max(5, min(args.steps, 20))
-    _lib.prof_reset()
-    _lib.prof_enable(True)
-    for _ in range(prof_steps):
-        eager_step()
-    torch.cuda.synchronize()
-    _lib.prof_enable(False)
-    prof = _lib.prof_read()
-    # the algorithmic work the library counted for THESE launches (the A/B leg below resets and re-accumulates the counters:
-    # reading them later paired one leg's bytes with the other leg's time — VERDICT r5 weak 9)
-    prof_work = {name: _lib.prof_work(name) for name in ("mr_fwd", "mr_bwd", "gemm_x6")}
-
-    # the box's own streaming rate (a 256 MiB device-to-device copy: read + write), the practical ceiling of every bandwidth
-    # figure below — the pool's boxes differ (4.9-5.5 TB/s measured), 8 TB/s is the data-sheet peak
-    cp_src = torch.empty(64 << 20, dtype=torch.float32, device=dev)
-    cp_dst = torch.empty_like(cp_src)
-    for _ in range(3):
-        cp_dst.copy_(cp_src)
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ev0.record()
-    for _ in range(10):
-        cp_dst.copy_(cp_src)
-    ev1.record()
-    torch.cuda.synchronize()
-    copy_gbps = 10 * 2 * cp_src.numel() * 4 / (ev0.elapsed_time(ev1) * 1e-3) / 1e9
-    del cp_src, cp_dst
+    if args.dump_outputs and rank == 0:          # the last timed step's results, before anything else runs
+        dump_outputs(args.dump_outputs, dict(grapher_out=state["out"], label_out=state["e2"], x_grad=x.grad, e_grad=e.grad,
+                                             param_grads=bucket.flat))
 
     from gkgnet_amd import fused
-    # Row g2 (round 5): by default the k-NN kernel also does the aggregation (fused epilogue), so `knn_tile`'s time below is the
-    # fused kernel's and there is no mr_fwd launch.  For continuity with earlier rounds the two-launch form is timed as well.
-    prof_two = None
-    if fused.KNN_MR:
-        fused.KNN_MR = False
-        try:
-            for _ in range(2):
-                eager_step()
-            torch.cuda.synchronize()
-            _lib.prof_reset()
-            _lib.prof_enable(True)
-            for _ in range(prof_steps):
-                eager_step()
-            torch.cuda.synchronize()
-            _lib.prof_enable(False)
-            prof_two = (_lib.prof_read(), _lib.prof_work("mr_fwd") / prof_steps)
-        finally:
-            fused.KNN_MR = True
+    if args.full:
+        # Per-kernel timing for the roofline: the same step, launched eagerly with the library's HIP-event brackets
+        # on the launch stream (events cannot bracket individual nodes of a replayed graph).
+        prof_steps = max(5, min(args.steps, 20))
+        _lib.prof_reset()
+        _lib.prof_enable(True)
+        for _ in range(prof_steps):
+            eager_step()
+        torch.cuda.synchronize()
+        _lib.prof_enable(False)
+        prof = _lib.prof_read()
+        # the algorithmic work the library counted for THESE launches (the A/B leg below resets and re-accumulates the counters:
+        # reading them later paired one leg's bytes with the other leg's time — VERDICT r5 weak 9)
+        prof_work = {name: _lib.prof_work(name) for name in ("mr_fwd", "mr_bwd", "gemm_x6")}
+
+        # the box's own streaming rate (a 256 MiB device-to-device copy: read + write), the practical ceiling of every bandwidth
+        # figure below — the pool's boxes differ (4.9-5.5 TB/s measured), 8 TB/s is the data-sheet peak
+        cp_src = torch.empty(64 << 20, dtype=torch.float32, device=dev)
+        cp_dst = torch.empty_like(cp_src)
+        for _ in range(3):
+            cp_dst.copy_(cp_src)
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        for _ in range(10):
+            cp_dst.copy_(cp_src)
+        ev1.record()
+        torch.cuda.synchronize()
+        copy_gbps = 10 * 2 * cp_src.numel() * 4 / (ev0.elapsed_time(ev1) * 1e-3) / 1e9
+        del cp_src, cp_dst
+
+        # Row g2 (round 5): by default the k-NN kernel also does the aggregation (fused epilogue), so `knn_tile`'s time below is the
+        # fused kernel's and there is no mr_fwd launch.  For continuity with earlier rounds the two-launch form is timed as well.
+        prof_two = None
+        if fused.KNN_MR:
+            fused.KNN_MR = False
+            try:
+                for _ in range(2):
+                    eager_step()
+                torch.cuda.synchronize()
+                _lib.prof_reset()
+                _lib.prof_enable(True)
+                for _ in range(prof_steps):
+                    eager_step()
+                torch.cuda.synchronize()
+                _lib.prof_enable(False)
+                prof_two = (_lib.prof_read(), _lib.prof_work("mr_fwd") / prof_steps)
+            finally:
+                fused.KNN_MR = True
     lib_desc = "vendor-library GEMMs (TunableOp-selected)" if not args.no_tune else "vendor-library GEMMs (default heuristic)"
     gemm_desc = {"x6": "fp32 projections: every forward, input-gradient and weight-gradient GEMM on the bf16 matrix cores with an "
                        "exact 3-way operand split, 6 cross products, fp32 accumulation (csrc/gkg_gemm_x6.hip: error vs fp64 below an "
@@ -713,132 +779,6 @@ def main():
     if rank == 0:
         ms_step = 1e3 * elapsed / args.steps
         value = world * B * args.steps / elapsed
-        N = H * H
-        M = N // (w["r"] ** 2)
-        BG = B * w["G"]
-        # algorithmic work of the k-NN tile kernel per step: Grapher graph + label graph
-        flops_knn = 2.0 * BG * (C // w["G"]) * (N * M + L * N)
-        tile_ms, tile_n = prof["knn_tile"]
-        # HBM-side traffic of the same kernel: hardware counters cannot be read from inside the process, so this field is
-        # NOT measured by this run — it is the value of the newest committed rocprofv3 --pmc collection for this workload
-        # (tools/pmc_refresh.sh -> profiles/rNN_pmc.json), labelled with its file and the commit it was taken at.
-        traffic, traffic_source, traffic_by = None, None, {}
-        issue_slots = None
-        if args.workload == "cfg2" and B == 32:
-            import glob
-            for pmc_path in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc.json")), reverse=True):
-                try:
-                    with open(pmc_path) as fh:
-                        pj = json.load(fh)
-                    # per launch, over the FUSED instantiations on the timed path only (tools/pmc_json.py "knn_mr_fused")
-                    traffic = pj["knn_tile_per_step_traffic_bytes"] / pj.get("knn_tile_launches_per_step", 2)
-                    traffic_by = {k: v["hbm_bytes_per_launch"] for k, v in pj.get("knn_mr_fused", {}).items()}
-                    from gkgnet_amd._build import csrc_sha16
-                    same = pj.get("csrc_sha16") == csrc_sha16()
-                    if "knn_tile_issue_slot_frac" in pj:
-                        issue_slots = dict(issue_slot_frac=pj["knn_tile_issue_slot_frac"], mfma_slot_frac=pj.get("knn_tile_mfma_slot_frac"),
-                                           formula="(4 * SQ_INSTS_VALU + SQ_VALU_MFMA_BUSY_CYCLES) / (32 * SQ_BUSY_CYCLES): vector + matrix "
-                                                   "issue cycles per SIMD over the launch's busy cycles (same counter collection as `traffic`)")
-                    traffic_source = (f"{os.path.relpath(pmc_path, ROOT)} @ {pj.get('commit', '?')} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE "
-                                      f"passes, not this run); collected on " +
-                                      ("the kernel sources this run uses (csrc hash matches)" if same else
-                                       "OTHER kernel sources than this run's (csrc hash differs: stale)"))
-                    break
-                except Exception:
-                    continue
-        roof = None
-        if tile_n:
-            per_step_ms = tile_ms / prof_steps
-            ach = flops_knn / (per_step_ms * 1e-3) / 1e12
-            fused_now = prof_two is not None and not prof.get("mr_fwd", (0, 0))[1]
-            roof = dict(kernel="knn_tile_kernel<..., MRF> (k-NN + max-relative aggregation in one kernel, row g2)" if fused_now
-                        else "knn_tile_kernel", bound="mfma", achieved=round(ach, 2), peak=PEAK_FP32_MFMA_TFLOPS,
-                        unit="TFLOP/s", frac=round(ach / PEAK_FP32_MFMA_TFLOPS, 4), traffic=traffic, traffic_source=traffic_source,
-                        avg_launch_us=round(1e3 * tile_ms / tile_n, 2), launches_per_step=tile_n // prof_steps,
-                        algorithmic_flops_per_step=flops_knn)
-            if issue_slots:
-                roof["issue_slots"] = issue_slots
-            # the counter traffic next to the ALGORITHMIC bytes of the same launches (SURVEY §8d "Fused fwd (k-NN+MR)": x + (y) +
-            # relative_pos + the aggregated output m + the winning rows; no index tensor, no copy of x): ratio > 1 = re-reads
-            alg_g = 4.0 * B * C * N + (4.0 * B * C * M if M != N else 0.0) + 4.0 * N * M + 4.0 * B * C * N + 2.0 * B * C * N
-            alg_l = 4.0 * B * C * L + 4.0 * B * C * N + 4.0 * B * C * L + 2.0 * B * C * L + 16.0 * BG * L * w["k"]
-            roof["algorithmic_bytes_per_launch"] = dict(grapher=alg_g, label=alg_l, mean=(alg_g + alg_l) / 2)
-            if traffic_by:
-                roof["traffic_per_launch"] = traffic_by
-                roof["traffic_ratio"] = {k: round(v / dict(grapher=alg_g, label=alg_l)[k], 3) for k, v in traffic_by.items()
-                                         if k in ("grapher", "label")}
-                if len(traffic_by) == 2:
-                    roof["traffic_ratio"]["step"] = round(sum(traffic_by.values()) / (alg_g + alg_l), 3)
-            if fused_now:
-                # SURVEY §8(d) "Fused fwd (k-NN+MR)": the same contraction flop, more bytes — the kernel's time now includes the
-                # gather, so `frac` is NOT comparable with the k-NN-only kernel of rounds 1-4 (0.21-0.23); that kernel, timed
-                # in the two-launch form by this run:
-                t2_ms, t2_n = prof_two[0]["knn_tile"]
-                m2_ms, m2_n = prof_two[0]["mr_fwd"]
-                if t2_n:
-                    ach2 = flops_knn / (t2_ms / prof_steps * 1e-3) / 1e12
-                    roof["two_launch_form"] = dict(kernel="knn_tile_kernel (k-NN only) + mr_fwd_tm_kernel (GKG_DISABLE=knn_mr)",
-                                                   knn_achieved=round(ach2, 2), knn_frac=round(ach2 / PEAK_FP32_MFMA_TFLOPS, 4),
-                                                   knn_us_per_step=round(1e3 * t2_ms / prof_steps, 2),
-                                                   mr_fwd_us_per_step=round(1e3 * m2_ms / prof_steps, 2),
-                                                   mr_fwd_frac_of_hbm=round(prof_two[1] / max(1e3 * m2_ms / prof_steps, 1e-9) / 1e3 / PEAK_HBM_GBPS, 4))
-                roof["note"] = ("frac counts the contraction's flop over the FUSED kernel's whole time (matrix phase + selection + "
-                                "neighbour gather); two_launch_form.knn_frac is the figure comparable with earlier rounds")
-        kernels = {k: dict(us_per_step=round(1e3 * v[0] / prof_steps, 2), launches_per_step=v[1] // prof_steps)
-                   for k, v in prof.items() if v[1]}
-        # HBM-bound companions of the k-NN kernel (the gather + max-relative forward and its scatter backward): ALGORITHMIC
-        # bytes per SURVEY §8d, reported by the library per launch (gkg_prof_work), / measured time, vs 8 TB/s
-        roof_hbm = {}
-        # (round 5: from 160 query rows per image the exact scatter is the one-sweep streaming form; label graphs keep the
-        # two-sweep kernel; both are order-independent, so GKG_DETERMINISTIC runs them too)
-        mr_bwd_kernel = "mr_bwd_tm_stream_kernel (>= 160 query rows) / mr_bwd_tm_scatter_i64_kernel"
-        for name, kern in (("mr_fwd", "mr_fwd_tm_kernel"), ("mr_bwd", mr_bwd_kernel)):
-            if name in kernels and kernels[name]["us_per_step"] > 0:
-                nbytes = prof_work[name] / prof_steps
-                gbs = nbytes / kernels[name]["us_per_step"] / 1e3
-                kernels[name].update(bound="hbm", achieved_GBps=round(gbs, 1), frac=round(gbs / PEAK_HBM_GBPS, 4))
-                roof_hbm[name] = dict(kernel=kern, bound="hbm", achieved=round(gbs, 1), peak=PEAK_HBM_GBPS, unit="GB/s",
-                                      frac=round(gbs / PEAK_HBM_GBPS, 4), frac_of_copy=round(gbs / copy_gbps, 4),
-                                      algorithmic_bytes_per_step=nbytes,
-                                      us_per_step=kernels[name]["us_per_step"], launches_per_step=kernels[name]["launches_per_step"])
-        if roof is not None and "two_launch_form" in roof:
-            # the fused kernel against the HBM roofline with §8(d)'s "Fused fwd (k-NN+MR)" bytes per graph:
-            # x + (y) + relative_pos + index lists + the aggregated output
-            e4 = 4.0
-            by_g, by_l = roof["algorithmic_bytes_per_launch"]["grapher"], roof["algorithmic_bytes_per_launch"]["label"]
-            us = kernels["knn_tile"]["us_per_step"]
-            gbs = (by_g + by_l) / us / 1e3
-            roof_hbm["knn_mr_fused"] = dict(kernel="knn_tile_kernel<..., MRF>", bound="hbm", achieved=round(gbs, 1), peak=PEAK_HBM_GBPS,
-                                            unit="GB/s", frac=round(gbs / PEAK_HBM_GBPS, 4), frac_of_copy=round(gbs / copy_gbps, 4),
-                                            algorithmic_bytes_per_step=by_g + by_l,
-                                            us_per_step=us, launches_per_step=kernels["knn_tile"]["launches_per_step"],
-                                            note="compute-bound kernel (SURVEY §8d: 3.7 us at 8 TB/s vs 13.7 us at the fp32 matrix peak for the Grapher graph)")
-        if "gemm_x6" in kernels and kernels["gemm_x6"]["us_per_step"] > 0:
-            # the projection GEMMs that run on the split-bf16 kernels: algorithmic fp32 flop (2 R cin cout, reported by the
-            # library per launch) per second, against the fp32-MFMA peak they replace and against their own bound — six
-            # bf16 MFMAs per fp32 block product at the dense bf16 peak (2.5 PFLOP/s / 6)
-            gf = prof_work["gemm_x6"] / prof_steps
-            tf = gf / kernels["gemm_x6"]["us_per_step"] / 1e6
-            kernels["gemm_x6"].update(bound="mfma", algorithmic_flops_per_step=gf, achieved_TFLOPs=round(tf, 1),
-                                      frac_of_fp32_mfma_peak=round(tf / PEAK_FP32_MFMA_TFLOPS, 4),
-                                      frac_of_split_bf16_bound=round(tf / (2500.0 / 6), 4))
-        # Step-level roofline: every algorithmic flop of the step (the projections' forward + input-gradient +
-        # weight-gradient GEMMs = 3x their forward, plus the two distance contractions) against the dense fp32 matrix peak,
-        # and the bytes that must cross HBM at least once (inputs, cotangents, input gradients, weights and weight
-        # gradients, relative_pos, the edge lists) against 8 TB/s.  The larger of the two times bounds the step.
-        T, TL = B * N, B * L
-        flops_proj = 3.0 * (8.0 * T * C * C + 24.0 * TL * C * C)
-        flops_step = flops_proj + flops_knn
-        n_par = sum(p.numel() for p in params)
-        bytes_step = 4.0 * (3 * B * C * N + 3 * B * L * C + B * C * N) + 8.0 * n_par + 4.0 * N * M + 8.0 * BG * (N + L) * w["k"]
-        t_flop = flops_step / (PEAK_FP32_MFMA_TFLOPS * 1e12)
-        t_byte = bytes_step / (PEAK_HBM_GBPS * 1e9)
-        roof_step = dict(bound="mfma" if t_flop >= t_byte else "hbm", algorithmic_flops=flops_step,
-                         algorithmic_bytes=bytes_step, flop_time_ms_at_fp32_peak=round(1e3 * t_flop, 4),
-                         byte_time_ms_at_8TBps=round(1e3 * t_byte, 4), achieved_TFLOPs=round(flops_step / (ms_step * 1e-3) / 1e12, 2),
-                         peak=PEAK_FP32_MFMA_TFLOPS, frac=round(max(t_flop, t_byte) / (ms_step * 1e-3), 4),
-                         note="projections 3 x (8 T C^2 + 24 T_L C^2) + k-NN 2 B C (N M + L N) flop; fp32 matrix peak "
-                              "(the split-bf16 kernels may exceed it: their own bound is the bf16 peak / 6)")
         res = dict(metric="Grapher fwd+bwd images/sec", value=round(value, 1), unit="images/s", n_gpus=world,
                    steps=args.steps, warmup=args.warmup, ms_per_step=round(ms_step, 4), higher_is_better=True,
                    scaling="weak", vs_baseline=None, dtype="f32", data="synthetic",
@@ -852,16 +792,144 @@ def main():
                                grad_allreduce=("none (1 GPU)" if world == 1 else
                                                f"one flat {'RCCL' if backend == 'nccl' else backend} all-reduce per step, " +
                                                ("captured inside the step's hipGraph" if state["reduce_in_graph"] else
-                                                "issued by the host after the replay"))),
-                   roofline=roof, roofline_hbm=roof_hbm, roofline_step=roof_step, hip_kernels=kernels,
-                   hbm_copy_GBps=round(copy_gbps, 1),
-                   ms_per_step_no_tune=round(1e3 * elapsed_no_tune / args.steps, 4),
-                   ms_per_step_eager=round(ms_eager, 4),
-                   gemm_selection="library default (no tuning pass)" if args.no_tune else
-                   "TunableOp pass in the warm-up (round 5: the step holds no vendor GEMM any more, so there is nothing to tune — "
-                   "the two legs run the same kernels); ms_per_step_no_tune = the leg without it; ms_per_step_eager = the same "
-                   "step launched op by op without the hipGraph (what an eager training loop gets)")
-        if world == 1 and not args.no_cpu_baseline:
+                                                "issued by the host after the replay"))))
+        if args.full:
+            N = H * H
+            M = N // (w["r"] ** 2)
+            BG = B * w["G"]
+            # algorithmic work of the k-NN tile kernel per step: Grapher graph + label graph
+            flops_knn = 2.0 * BG * (C // w["G"]) * (N * M + L * N)
+            tile_ms, tile_n = prof["knn_tile"]
+            # HBM-side traffic of the same kernel: hardware counters cannot be read from inside the process, so this field is
+            # NOT measured by this run — it is the value of the newest committed rocprofv3 --pmc collection for this workload
+            # (tools/pmc_refresh.sh -> profiles/rNN_pmc.json), labelled with its file and the commit it was taken at.
+            traffic, traffic_source, traffic_by = None, None, {}
+            issue_slots = None
+            if args.workload == "cfg2" and B == 32:
+                import glob
+                for pmc_path in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc.json")), reverse=True):
+                    try:
+                        with open(pmc_path) as fh:
+                            pj = json.load(fh)
+                        # per launch, over the FUSED instantiations on the timed path only (tools/pmc_json.py "knn_mr_fused")
+                        traffic = pj["knn_tile_per_step_traffic_bytes"] / pj.get("knn_tile_launches_per_step", 2)
+                        traffic_by = {k: v["hbm_bytes_per_launch"] for k, v in pj.get("knn_mr_fused", {}).items()}
+                        from gkgnet_amd._build import csrc_sha16
+                        same = pj.get("csrc_sha16") == csrc_sha16()
+                        if "knn_tile_issue_slot_frac" in pj:
+                            issue_slots = dict(issue_slot_frac=pj["knn_tile_issue_slot_frac"], mfma_slot_frac=pj.get("knn_tile_mfma_slot_frac"),
+                                               formula="(4 * SQ_INSTS_VALU + SQ_VALU_MFMA_BUSY_CYCLES) / (32 * SQ_BUSY_CYCLES): vector + matrix "
+                                                       "issue cycles per SIMD over the launch's busy cycles (same counter collection as `traffic`)")
+                        traffic_source = (f"{os.path.relpath(pmc_path, ROOT)} @ {pj.get('commit', '?')} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE "
+                                          f"passes, not this run); collected on " +
+                                          ("the kernel sources this run uses (csrc hash matches)" if same else
+                                           "OTHER kernel sources than this run's (csrc hash differs: stale)"))
+                        break
+                    except Exception:
+                        continue
+            roof = None
+            if tile_n:
+                per_step_ms = tile_ms / prof_steps
+                ach = flops_knn / (per_step_ms * 1e-3) / 1e12
+                fused_now = prof_two is not None and not prof.get("mr_fwd", (0, 0))[1]
+                roof = dict(kernel="knn_tile_kernel<..., MRF> (k-NN + max-relative aggregation in one kernel, row g2)" if fused_now
+                            else "knn_tile_kernel", bound="mfma", achieved=round(ach, 2), peak=PEAK_FP32_MFMA_TFLOPS,
+                            unit="TFLOP/s", frac=round(ach / PEAK_FP32_MFMA_TFLOPS, 4), traffic=traffic, traffic_source=traffic_source,
+                            avg_launch_us=round(1e3 * tile_ms / tile_n, 2), launches_per_step=tile_n // prof_steps,
+                            algorithmic_flops_per_step=flops_knn)
+                if issue_slots:
+                    roof["issue_slots"] = issue_slots
+                # the counter traffic next to the ALGORITHMIC bytes of the same launches (SURVEY §8d "Fused fwd (k-NN+MR)": x + (y) +
+                # relative_pos + the aggregated output m + the winning rows; no index tensor, no copy of x): ratio > 1 = re-reads
+                alg_g = 4.0 * B * C * N + (4.0 * B * C * M if M != N else 0.0) + 4.0 * N * M + 4.0 * B * C * N + 2.0 * B * C * N
+                alg_l = 4.0 * B * C * L + 4.0 * B * C * N + 4.0 * B * C * L + 2.0 * B * C * L + 16.0 * BG * L * w["k"]
+                roof["algorithmic_bytes_per_launch"] = dict(grapher=alg_g, label=alg_l, mean=(alg_g + alg_l) / 2)
+                if traffic_by:
+                    roof["traffic_per_launch"] = traffic_by
+                    roof["traffic_ratio"] = {k: round(v / dict(grapher=alg_g, label=alg_l)[k], 3) for k, v in traffic_by.items()
+                                             if k in ("grapher", "label")}
+                    if len(traffic_by) == 2:
+                        roof["traffic_ratio"]["step"] = round(sum(traffic_by.values()) / (alg_g + alg_l), 3)
+                if fused_now:
+                    # SURVEY §8(d) "Fused fwd (k-NN+MR)": the same contraction flop, more bytes — the kernel's time now includes the
+                    # gather, so `frac` is NOT comparable with the k-NN-only kernel of rounds 1-4 (0.21-0.23); that kernel, timed
+                    # in the two-launch form by this run:
+                    t2_ms, t2_n = prof_two[0]["knn_tile"]
+                    m2_ms, m2_n = prof_two[0]["mr_fwd"]
+                    if t2_n:
+                        ach2 = flops_knn / (t2_ms / prof_steps * 1e-3) / 1e12
+                        roof["two_launch_form"] = dict(kernel="knn_tile_kernel (k-NN only) + mr_fwd_tm_kernel (GKG_DISABLE=knn_mr)",
+                                                       knn_achieved=round(ach2, 2), knn_frac=round(ach2 / PEAK_FP32_MFMA_TFLOPS, 4),
+                                                       knn_us_per_step=round(1e3 * t2_ms / prof_steps, 2),
+                                                       mr_fwd_us_per_step=round(1e3 * m2_ms / prof_steps, 2),
+                                                       mr_fwd_frac_of_hbm=round(prof_two[1] / max(1e3 * m2_ms / prof_steps, 1e-9) / 1e3 / PEAK_HBM_GBPS, 4))
+                    roof["note"] = ("frac counts the contraction's flop over the FUSED kernel's whole time (matrix phase + selection + "
+                                    "neighbour gather); two_launch_form.knn_frac is the figure comparable with earlier rounds")
+            kernels = {k: dict(us_per_step=round(1e3 * v[0] / prof_steps, 2), launches_per_step=v[1] // prof_steps)
+                       for k, v in prof.items() if v[1]}
+            # HBM-bound companions of the k-NN kernel (the gather + max-relative forward and its scatter backward): ALGORITHMIC
+            # bytes per SURVEY §8d, reported by the library per launch (gkg_prof_work), / measured time, vs 8 TB/s
+            roof_hbm = {}
+            # (round 5: from 160 query rows per image the exact scatter is the one-sweep streaming form; label graphs keep the
+            # two-sweep kernel; both are order-independent, so GKG_DETERMINISTIC runs them too)
+            mr_bwd_kernel = "mr_bwd_tm_stream_kernel (>= 160 query rows) / mr_bwd_tm_scatter_i64_kernel"
+            for name, kern in (("mr_fwd", "mr_fwd_tm_kernel"), ("mr_bwd", mr_bwd_kernel)):
+                if name in kernels and kernels[name]["us_per_step"] > 0:
+                    nbytes = prof_work[name] / prof_steps
+                    gbs = nbytes / kernels[name]["us_per_step"] / 1e3
+                    kernels[name].update(bound="hbm", achieved_GBps=round(gbs, 1), frac=round(gbs / PEAK_HBM_GBPS, 4))
+                    roof_hbm[name] = dict(kernel=kern, bound="hbm", achieved=round(gbs, 1), peak=PEAK_HBM_GBPS, unit="GB/s",
+                                          frac=round(gbs / PEAK_HBM_GBPS, 4), frac_of_copy=round(gbs / copy_gbps, 4),
+                                          algorithmic_bytes_per_step=nbytes,
+                                          us_per_step=kernels[name]["us_per_step"], launches_per_step=kernels[name]["launches_per_step"])
+            if roof is not None and "two_launch_form" in roof:
+                # the fused kernel against the HBM roofline with §8(d)'s "Fused fwd (k-NN+MR)" bytes per graph:
+                # x + (y) + relative_pos + index lists + the aggregated output
+                e4 = 4.0
+                by_g, by_l = roof["algorithmic_bytes_per_launch"]["grapher"], roof["algorithmic_bytes_per_launch"]["label"]
+                us = kernels["knn_tile"]["us_per_step"]
+                gbs = (by_g + by_l) / us / 1e3
+                roof_hbm["knn_mr_fused"] = dict(kernel="knn_tile_kernel<..., MRF>", bound="hbm", achieved=round(gbs, 1), peak=PEAK_HBM_GBPS,
+                                                unit="GB/s", frac=round(gbs / PEAK_HBM_GBPS, 4), frac_of_copy=round(gbs / copy_gbps, 4),
+                                                algorithmic_bytes_per_step=by_g + by_l,
+                                                us_per_step=us, launches_per_step=kernels["knn_tile"]["launches_per_step"],
+                                                note="compute-bound kernel (SURVEY §8d: 3.7 us at 8 TB/s vs 13.7 us at the fp32 matrix peak for the Grapher graph)")
+            if "gemm_x6" in kernels and kernels["gemm_x6"]["us_per_step"] > 0:
+                # the projection GEMMs that run on the split-bf16 kernels: algorithmic fp32 flop (2 R cin cout, reported by the
+                # library per launch) per second, against the fp32-MFMA peak they replace and against their own bound — six
+                # bf16 MFMAs per fp32 block product at the dense bf16 peak (2.5 PFLOP/s / 6)
+                gf = prof_work["gemm_x6"] / prof_steps
+                tf = gf / kernels["gemm_x6"]["us_per_step"] / 1e6
+                kernels["gemm_x6"].update(bound="mfma", algorithmic_flops_per_step=gf, achieved_TFLOPs=round(tf, 1),
+                                          frac_of_fp32_mfma_peak=round(tf / PEAK_FP32_MFMA_TFLOPS, 4),
+                                          frac_of_split_bf16_bound=round(tf / (2500.0 / 6), 4))
+            # Step-level roofline: every algorithmic flop of the step (the projections' forward + input-gradient +
+            # weight-gradient GEMMs = 3x their forward, plus the two distance contractions) against the dense fp32 matrix peak,
+            # and the bytes that must cross HBM at least once (inputs, cotangents, input gradients, weights and weight
+            # gradients, relative_pos, the edge lists) against 8 TB/s.  The larger of the two times bounds the step.
+            T, TL = B * N, B * L
+            flops_proj = 3.0 * (8.0 * T * C * C + 24.0 * TL * C * C)
+            flops_step = flops_proj + flops_knn
+            n_par = sum(p.numel() for p in params)
+            bytes_step = 4.0 * (3 * B * C * N + 3 * B * L * C + B * C * N) + 8.0 * n_par + 4.0 * N * M + 8.0 * BG * (N + L) * w["k"]
+            t_flop = flops_step / (PEAK_FP32_MFMA_TFLOPS * 1e12)
+            t_byte = bytes_step / (PEAK_HBM_GBPS * 1e9)
+            roof_step = dict(bound="mfma" if t_flop >= t_byte else "hbm", algorithmic_flops=flops_step,
+                             algorithmic_bytes=bytes_step, flop_time_ms_at_fp32_peak=round(1e3 * t_flop, 4),
+                             byte_time_ms_at_8TBps=round(1e3 * t_byte, 4), achieved_TFLOPs=round(flops_step / (ms_step * 1e-3) / 1e12, 2),
+                             peak=PEAK_FP32_MFMA_TFLOPS, frac=round(max(t_flop, t_byte) / (ms_step * 1e-3), 4),
+                             note="projections 3 x (8 T C^2 + 24 T_L C^2) + k-NN 2 B C (N M + L N) flop; fp32 matrix peak "
+                                  "(the split-bf16 kernels may exceed it: their own bound is the bf16 peak / 6)")
+            res.update(roofline=roof, roofline_hbm=roof_hbm, roofline_step=roof_step, hip_kernels=kernels,
+                       hbm_copy_GBps=round(copy_gbps, 1),
+                       ms_per_step_no_tune=round(1e3 * elapsed_no_tune / args.steps, 4),
+                       ms_per_step_eager=round(ms_eager, 4))
+        res["gemm_selection"] = ("library default (no tuning pass)" if args.no_tune else
+                                 "TunableOp pass in the warm-up" if not args.full else
+                                 "TunableOp pass in the warm-up (round 5: the step holds no vendor GEMM any more, so there is nothing to "
+                                 "tune — the two legs run the same kernels); ms_per_step_no_tune = the leg without it; ms_per_step_eager = "
+                                 "the same step launched op by op without the hipGraph (what an eager training loop gets)")
+        if world == 1 and args.full and not args.no_cpu_baseline:
             # the port scales badly past a few dozen threads (tiny per-op work): sweep 8 / 32 / all PHYSICAL cores (BASELINE.md
             # §3), report the fastest leg; the physical core count of the host is stated either way
             pc = physical_cores()

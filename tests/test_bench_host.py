@@ -36,3 +36,24 @@ def test_workload_tables_cover_every_baseline_config():
     assert set(bench.BACKBONE_WORKLOADS) == {"cfg3", "cfg4", "cfg5"}
     assert bench.BACKBONE_WORKLOADS["cfg5"]["kw"]["num_group"] == 8 and bench.BACKBONE_WORKLOADS["cfg5"]["B"] == 16
     assert bench.WORKLOADS["stage1"]["H"] ** 2 == 20736 and bench.WORKLOADS["stage1"]["r"] == 4
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path):
+    """--dump-outputs: float32 / float64 .npy files, whole arrays when they fit, a fixed seeded sample (the same positions in
+    every run) when together they exceed the budget."""
+    import numpy as np
+    import bench
+    small = dict(out=torch.randn(3, 4, dtype=torch.float64), edge=torch.arange(10))
+    bench.dump_outputs(str(tmp_path / "a"), small)
+    a = np.load(tmp_path / "a" / "out.npy")
+    assert a.dtype == np.float32 and a.shape == (3, 4) and np.array_equal(a, small["out"].float().numpy())
+    e = np.load(tmp_path / "a" / "edge.npy")
+    assert e.dtype == np.float64 and np.array_equal(e, np.arange(10))
+    big = dict(x=torch.randn(bench.DUMP_BUDGET_BYTES // 4 + 1000), y=torch.randn(7))
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    assert sum(os.path.getsize(p) for p in (tmp_path / "b").iterdir()) <= 64e6
+    xb, xc = np.load(tmp_path / "b" / "x.npy"), np.load(tmp_path / "c" / "x.npy")
+    assert xb.size < big["x"].numel() and np.array_equal(xb, xc)
+    assert np.isin(xb, big["x"].numpy()).all()
+    assert np.array_equal(np.load(tmp_path / "b" / "y.npy"), big["y"].numpy())

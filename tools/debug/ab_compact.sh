@@ -11,7 +11,7 @@ d = json.loads(sys.stdin.readline()); print('$w', 'disable=[$dis]', d['ms_per_st
 done
 for rep in 1 2; do
   for dis in "" knn_compact; do
-    GKG_DISABLE=$dis python bench.py --workload stage1 --no-cpu-baseline 2>/dev/null | python -c "
+    GKG_DISABLE=$dis python bench.py --full --workload stage1 --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline()); print('stage1', 'disable=[$dis]', d['ms_per_step'], d['hip_kernels'].get('mr_fwd'))"
   done

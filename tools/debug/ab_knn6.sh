@@ -8,6 +8,6 @@ for s in s1 s2 s3; do
   done
 done
 for rep in 1 2; do
-  GKG_HIP_LIB=$H python bench.py --workload cfg5 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('before cfg5', j['ms_per_step'], j.get('ms_per_step_knn_bf16'))"
-  python bench.py --workload cfg5 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('ku6    cfg5', j['ms_per_step'], j.get('ms_per_step_knn_bf16'))"
+  GKG_HIP_LIB=$H python bench.py --full --workload cfg5 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('before cfg5', j['ms_per_step'], j.get('ms_per_step_knn_bf16'))"
+  python bench.py --full --workload cfg5 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('ku6    cfg5', j['ms_per_step'], j.get('ms_per_step_knn_bf16'))"
 done

@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp
 for pass in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES"; do
   name=$(echo $pass | cut -d' ' -f1)
   rm -rf /tmp/pmc_$name
-  rocprofv3 --pmc $pass --kernel-trace --output-format csv -d /tmp/pmc_$name -o run -- python $R/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-tune --no-graph > /tmp/pmc_$name.log 2>&1
+  rocprofv3 --pmc $pass --kernel-trace --output-format csv -d /tmp/pmc_$name -o run -- python $R/bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-tune --no-graph > /tmp/pmc_$name.log 2>&1
 done
 cd $R
 python tools/pmc_json.py /tmp/pmc_FETCH_SIZE /tmp/pmc_WRITE_SIZE /tmp/pmc_SQ_WAVE_CYCLES > gpurun_out/${TAG}_pmc.json

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 cd /tmp && export TMPDIR=/tmp
 for mode in 1 0; do
 rm -rf /tmp/pk$mode
-GKG_KNN_PREFILTER=$mode rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pk$mode -o run -- python $R/bench.py --steps 20 --warmup 5 --no-tune --no-cpu-baseline "$@" > /tmp/pk$mode.log 2>&1
+GKG_KNN_PREFILTER=$mode rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pk$mode -o run -- python $R/bench.py --full --steps 20 --warmup 5 --no-tune --no-cpu-baseline "$@" > /tmp/pk$mode.log 2>&1
 echo "== prefilter=$mode  $(grep -o '"ms_per_step": [0-9.]*' /tmp/pk$mode.log | head -1)"
 python - <<PY
 import csv,glob

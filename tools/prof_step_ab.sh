@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp
 for rep in 1 2; do
  for side in "$@"; do
   R=$ROOT/${side%%|*}; E=${side##*|}
-  env $E python $R/bench.py --steps 50 --warmup 10 --no-cpu-baseline 2>/dev/null | python -c "
+  env $E python $R/bench.py --full --steps 50 --warmup 10 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 j=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$side', j['ms_per_step'], j['ms_per_step_no_tune'])"
  done
@@ -15,11 +15,11 @@ n=0
 for side in "$@"; do
   R=$ROOT/${side%%|*}; E=${side##*|}; n=$((n+1))
   export $E
-  rm -rf $ROOT/gpurun_out/ab_$n
-  rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/gpurun_out/ab_$n -o t -- python3 $R/bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-tune > /dev/null 2>&1
+  rm -rf /tmp/ab_$n
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ab_$n -o t -- python3 $R/bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-tune > /dev/null 2>&1
   python - <<PY
 import csv, glob, collections
-f = glob.glob("$ROOT/gpurun_out/ab_$n/**/*kernel_trace.csv", recursive=True)[0]
+f = glob.glob("/tmp/ab_$n/**/*kernel_trace.csv", recursive=True)[0]
 rows = list(csv.DictReader(open(f)))
 end = max(int(r["End_Timestamp"]) for r in rows)
 win = 20e6
@@ -35,5 +35,5 @@ for k, v in sorted(tot.items(), key=lambda kv: -kv[1][1])[:50]:
     print("%8.1f us %5d  %s" % (v[1], v[0], k))
 PY
   unset ${E%%=*}
-  rm -rf $ROOT/gpurun_out/ab_$n
+  rm -rf /tmp/ab_$n
 done

@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp
 for mode in "x6all --no-tune" "x6 --no-tune" "x6 "; do
   export GKG_GEMM_MATH=${mode%% *}
   rm -rf /tmp/wg_prof
-  rocprofv3 --kernel-trace --output-format csv -d /tmp/wg_prof -o t -- python3 $ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline ${mode#* } > /tmp/wg_prof.json 2>/dev/null
+  rocprofv3 --kernel-trace --output-format csv -d /tmp/wg_prof -o t -- python3 $ROOT/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline ${mode#* } > /tmp/wg_prof.json 2>/dev/null
   tail -1 /tmp/wg_prof.json | python3 -c "
 import json,sys
 j=json.loads(sys.stdin.read()); print('== $mode: ms_per_step', j['ms_per_step'], 'no_tune', j.get('ms_per_step_no_tune'))"
