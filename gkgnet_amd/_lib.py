@@ -84,7 +84,8 @@ EXPORTS = ("gkg_version", "gkg_last_error_string", "gkg_knn_workspace_bytes", "g
            "gkg_tm_affine_to_nchw_dual", "gkg_nchw_to_tm_add", "gkg_bn_apply_train_dual",
            "gkg_knn_mr_fused_supported", "gkg_knn_mr_fwd_tm", "gkg_x6_prep_weights_zero",
            "gkg_knn_fwd_tm16", "gkg_mr_fwd_tm16", "gkg_mr_linear_bf16_nn16",
-           "gkg_grapher_fwd", "gkg_grapher_bwd", "gkg_grapher_label_fwd", "gkg_grapher_label_bwd")
+           "gkg_grapher_fwd", "gkg_grapher_bwd", "gkg_grapher_label_fwd", "gkg_grapher_label_bwd",
+           "gkg_gconv_workspace_bytes", "gkg_gin_fwd", "gkg_gin_bwd", "gkg_gat_fwd", "gkg_gat_bwd")
 PROF_KERNELS = ("token_prep", "knn_tile", "knn_merge", "mr_fwd", "mr_bwd", "gemm_x6")
 
 _lib = None
@@ -195,6 +196,16 @@ def load():
     lib.gkg_edge_bwd_stats.argtypes = [V] * 10 + [I, I, I, I, I, I, V]
     lib.gkg_edge_bwd.restype = I
     lib.gkg_edge_bwd.argtypes = [V] * 13 + [I, I, I, I, I, I, V]
+    lib.gkg_gconv_workspace_bytes.restype = Z
+    lib.gkg_gconv_workspace_bytes.argtypes = [I] * 5
+    lib.gkg_gin_fwd.restype = I
+    lib.gkg_gin_fwd.argtypes = [V] * 5 + [I] * 5 + [V]
+    lib.gkg_gin_bwd.restype = I
+    lib.gkg_gin_bwd.argtypes = [V] * 7 + [I] * 5 + [V, Z, V]
+    lib.gkg_gat_fwd.restype = I
+    lib.gkg_gat_fwd.argtypes = [V] * 7 + [I] * 5 + [V, Z, V]
+    lib.gkg_gat_bwd.restype = I
+    lib.gkg_gat_bwd.argtypes = [V] * 10 + [I] * 5 + [V, Z, V]
     lib.gkg_stream_capture_id.restype = C.c_ulonglong
     lib.gkg_stream_capture_id.argtypes = [V]
     lib.gkg_x6_planes_bytes.restype = Z

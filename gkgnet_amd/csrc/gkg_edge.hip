@@ -13,6 +13,8 @@
 //                       the BN backward
 //   gkg_edge_bwd        dz[n][k] = a ( g [k == argmax] - mg - zhat[n][k] mgz ) for EVERY edge (train-mode BN spreads the
 //                       gradient over the batch): dQ[idx] += dz (atomics, dQ zero on entry), dQc[n] = - sum_k dz
+// qc == NULL means Qc = 0: z = Q[j] + bias, GraphSAGE's nn1 on the gathered neighbours (reference torch_vertex.py:116-131);
+// dqc is then optional (written when given).
 // Layout: channel-major (B, O, N) / (B, O, M) fp32, nn_idx (B, N, k) int64.  act: 0 none, 1 GELU (erf), 2 ReLU.
 #include "gkg_common.h"
 
@@ -51,7 +53,7 @@ __global__ __launch_bounds__(256) void edge_stats_kernel(const float* __restrict
   double s1 = 0.0, s2 = 0.0;
   if (n < N) {
     const float* q = qs + ((size_t)b * O + o) * M;
-    const float c0 = qc[((size_t)b * O + o) * N + n];
+    const float c0 = qc ? qc[((size_t)b * O + o) * N + n] : 0.f;
     const int64_t* ip = idx + ((size_t)b * N + n) * k;
     for (int kk = 0; kk < k; ++kk) {
       const double v = (double)(q[edge_idx(ip[kk], M)] - c0);
@@ -74,7 +76,7 @@ __global__ __launch_bounds__(256) void edge_fwd_kernel(const float* __restrict__
   if (n >= N) return;
   const float* q = qs + ((size_t)b * O + o) * M;
   const size_t at = ((size_t)b * O + o) * N + n;
-  const float c0 = qc[at], av = a[o], cv = c[o];
+  const float c0 = qc ? qc[at] : 0.f, av = a[o], cv = c[o];
   const int64_t* ip = idx + ((size_t)b * N + n) * k;
   float best = 0.f;
   int bk = 0;
@@ -97,7 +99,7 @@ __global__ __launch_bounds__(256) void edge_bwd_stats_kernel(const float* __rest
   double t1 = 0.0, t2 = 0.0;
   if (n < N) {
     const size_t at = ((size_t)b * O + o) * N + n;
-    const float z = qs[((size_t)b * O + o) * M + edge_idx(idx[((size_t)b * N + n) * k + argmax[at]], M)] - qc[at];
+    const float z = qs[((size_t)b * O + o) * M + edge_idx(idx[((size_t)b * N + n) * k + argmax[at]], M)] - (qc ? qc[at] : 0.f);
     const float gv = g[at] * edge_act_grad(__builtin_fmaf(a[o], z, c[o]), act);
     t1 = gv;
     t2 = (double)gv * (double)((z - mean0[o]) * invstd[o]);
@@ -124,13 +126,13 @@ __global__ __launch_bounds__(256) void edge_bwd_kernel(const float* __restrict__
   const float* q = qs + row * M;
   float* dq = dqs + row * M;
   const int64_t* ip = idx + ((size_t)b * N + n) * k;
-  const float c0 = qc[at], av = a[o], cv = c[o];
+  const float c0 = qc ? qc[at] : 0.f, av = a[o], cv = c[o];
   const int ka = argmax[at];
   if (!DENSE) {                                   // no batch statistics in the way: only the winning edge carries gradient
     const int j = edge_idx(ip[ka], M);
     const float dz = av * g[at] * edge_act_grad(__builtin_fmaf(av, q[j] - c0, cv), act);
     atomicAdd(dq + j, dz);
-    dqc[at] = -dz;
+    if (dqc) dqc[at] = -dz;
     return;
   }
   const float m0 = mean0[o], is = invstd[o], gm = mg[o], gz = mgz[o];
@@ -143,11 +145,13 @@ __global__ __launch_bounds__(256) void edge_bwd_kernel(const float* __restrict__
     atomicAdd(dq + j, dz);
     acc += dz;
   }
-  dqc[at] = -acc;
+  if (dqc) dqc[at] = -acc;
 }
 
+// qc (p1) may be NULL: the centre projection is then zero (GraphSAGE's nn1, z = Q[j]), and dqc may be NULL too
 static int edge_check(const void* p0, const void* p1, const void* p2, int B, int O, int N, int M, int k, const char* who) {
-  if (!p0 || !p1 || !p2) return gkg_fail(GKG_ERR_NULL, who);
+  (void)p1;
+  if (!p0 || !p2) return gkg_fail(GKG_ERR_NULL, who);
   if (B <= 0 || O <= 0 || N <= 0 || M <= 0 || k <= 0 || k > 255 || O > 65535 || B > 65535) return gkg_fail(GKG_ERR_SHAPE, who);
   return 0;
 }
@@ -190,7 +194,7 @@ extern "C" int gkg_edge_bwd(const float* g, const float* qs, const float* qc, co
                             const float* a, const float* c, const float* mean0, const float* invstd, const float* mg,
                             const float* mgz, float* dqs, float* dqc, int B, int O, int N, int M, int k, int act, void* stream) {
   if (int rc = edge_check(qs, qc, nn_idx, B, O, N, M, k, "gkg_edge_bwd: bad pointer / size")) return rc;
-  if (!g || !argmax || !a || !c || !dqs || !dqc) return gkg_fail(GKG_ERR_NULL, "gkg_edge_bwd: null pointer");
+  if (!g || !argmax || !a || !c || !dqs || (qc && !dqc)) return gkg_fail(GKG_ERR_NULL, "gkg_edge_bwd: null pointer");
   const bool dense = mg != nullptr;
   if (dense && (!mgz || !mean0 || !invstd)) return gkg_fail(GKG_ERR_NULL, "gkg_edge_bwd: batch-statistics backward needs mean0, invstd, mg, mgz");
   dim3 grid((N + 255) / 256, O, B);

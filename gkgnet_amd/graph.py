@@ -9,6 +9,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import ops
+from .dense import pointwise_conv
 from .layers import BasicConv
 
 
@@ -26,6 +27,42 @@ class DenseDilatedKnnGraph(nn.Module):
             pick = torch.randperm(self.k * self.dilation, device=full.device)[: self.k]
             return full[:, :, :, pick]
         return ops.knn_graph(x, y, relative_pos, self.k, self.dilation)
+
+
+def _fp32_cuda(x):
+    return x.is_cuda and x.dtype == torch.float32 and not torch.is_autocast_enabled()
+
+
+def _basic_conv_plan(seq):
+    """(conv, bn or None, act code) when a BasicConv can run beside the HIP aggregations: grouped 1x1 conv (groups = 4)
+    [+ BatchNorm with a fixed momentum, statistics local to this process] [+ GELU (erf) / ReLU], no dropout; else None."""
+    mods = list(seq)
+    conv = mods[0]
+    if not isinstance(conv, nn.Conv2d) or conv.groups != 4 or conv.out_channels % 4 or conv.in_channels % 4:
+        return None
+    bn, act = None, ops.ACT_NONE
+    for m in mods[1:]:
+        if isinstance(m, nn.modules.batchnorm._BatchNorm):
+            if m.momentum is None or not m.affine or (m.training and torch.distributed.is_available()
+                                                      and torch.distributed.is_initialized()
+                                                      and torch.distributed.get_world_size() > 1
+                                                      and isinstance(m, nn.SyncBatchNorm)):
+                return None
+            bn = m
+        elif isinstance(m, nn.GELU) and getattr(m, "approximate", "none") == "none":
+            act = ops.ACT_GELU
+        elif isinstance(m, nn.ReLU):
+            act = ops.ACT_RELU
+        else:
+            return None
+    return conv, bn, act
+
+
+def _batched_index_select(x, idx):
+    """(B, C, M[, 1]) gathered at idx (B, N, k) -> (B, C, N, k) (reference torch_nn.py:84-105)."""
+    b, c = x.shape[:2]
+    n, k = idx.shape[1:]
+    return torch.gather(x.reshape(b, c, -1), 2, idx.reshape(b, 1, n * k).expand(b, c, n * k)).reshape(b, c, n, k)
 
 
 def _interleave(x, m, full_c):
@@ -63,29 +100,9 @@ class EdgeConv2d(nn.Module):
     def _hip_plan(self, x):
         """(conv, bn or None, act code) when the HIP aggregation applies: fp32 CUDA tensors, BasicConv = grouped 1x1 conv
         [+ BatchNorm with a fixed momentum, statistics local to this process] [+ GELU / ReLU], no dropout."""
-        from . import ops
-        if not (x.is_cuda and x.dtype == torch.float32 and not torch.is_autocast_enabled()):
+        if not _fp32_cuda(x):
             return None
-        mods = list(self.nn)
-        conv = mods[0]
-        if not isinstance(conv, nn.Conv2d) or conv.groups != 4 or conv.out_channels % 4 or conv.in_channels % 4:
-            return None
-        bn, act = None, ops.ACT_NONE
-        for m in mods[1:]:
-            if isinstance(m, nn.modules.batchnorm._BatchNorm):
-                if m.momentum is None or not m.affine or (m.training and torch.distributed.is_available()
-                                                          and torch.distributed.is_initialized()
-                                                          and torch.distributed.get_world_size() > 1
-                                                          and isinstance(m, nn.SyncBatchNorm)):
-                    return None
-                bn = m
-            elif isinstance(m, nn.GELU) and getattr(m, "approximate", "none") == "none":
-                act = ops.ACT_GELU
-            elif isinstance(m, nn.ReLU):
-                act = ops.ACT_RELU
-            else:
-                return None
-        return conv, bn, act
+        return _basic_conv_plan(self.nn)
 
     def forward(self, x, edge_index, y=None):
         bg, c = x.shape[:2]
@@ -147,6 +164,118 @@ class EdgeConv2d(nn.Module):
         return torch.cat([zA, zB], dim=1).unsqueeze(-1)
 
 
+# The three aggregations below, like MRConv2d and EdgeConv2d, are secondary in GKGNet (its configs select 'mr').  Each runs
+# a HIP aggregation (gkgnet_amd.ops, csrc/gkg_gconv.hip / gkg_edge.hip) when ``_hip_plan`` applies and otherwise the
+# reference's literal formula in torch (CPU tensors, autocast, other norms / activations, dropout, ...).  Like the reference
+# they are single-group modules: with use_multi_group=True they receive C/G channels, the plan's channel check fails and
+# the literal form raises in its convolution, as the reference does.  The HIP paths take the centre of every edge to be the
+# query itself (edge_index[1][b][n][k] == n, what the k-NN produces) and do not read edge_index[1]; the literal GAT form
+# does, as the reference.
+
+
+class GraphAtten(nn.Module):
+    """Graph attention (reference torch_vertex.py:16-37): p = softmax_k(a(cat[x_i, x_j])), nn(interleave[x, sum_k p x_j]).
+    ``leakyrelu`` holds no state and is never applied, as in the reference."""
+
+    def __init__(self, in_channels, out_channels, act="relu", norm=None, bias=True, alpha=0.1):
+        super().__init__()
+        self.in_channels = in_channels
+        self.leakyrelu = nn.LeakyReLU(alpha)
+        self.nn = BasicConv([in_channels * 2, out_channels], act, norm, bias)
+        self.a = nn.Conv2d(in_channels * 2, 1, 1, bias=bias)
+
+    def _hip_plan(self, x):
+        """nn's plan when the HIP attention applies: additionally x carries this module's C channels, N >= 2 (checked in
+        forward, with k >= 2: at k == 1 the reference's squeeze() turns the softmax into one over nodes) and ``a`` is a
+        plain fp32 1x1 convolution."""
+        a = self.a
+        if not _fp32_cuda(x) or x.shape[1] * 2 != a.in_channels or a.weight.dtype != torch.float32 or not a.weight.is_cuda \
+                or a.kernel_size != (1, 1) or a.groups != 1:
+            return None
+        return _basic_conv_plan(self.nn)
+
+    def forward(self, x, edge_index, y=None):
+        idx = edge_index[0]
+        n, k = idx.shape[1:]
+        if k >= 2 and n >= 2 and self._hip_plan(x) is not None:
+            bg, c = x.shape[:2]
+            xt = x.reshape(bg, c, -1)
+            agg = ops.gat_aggregate(xt, idx, self.a.weight, self.a.bias, None if y is None else y.reshape(bg, c, -1))
+            return self.nn(_interleave(xt, agg, self.in_channels))
+        x_i = _batched_index_select(x, edge_index[1])
+        x_j = _batched_index_select(x if y is None else y, idx)
+        e = self.a(torch.cat([x_i, x_j], dim=1)).squeeze()
+        atten = F.softmax(e, -1)
+        x_j = (atten.unsqueeze(-1) * x_j.permute(0, 2, 3, 1)).sum(2).transpose(1, 2).unsqueeze(-1)
+        b, c, n, _ = x.shape
+        x = torch.cat([x.unsqueeze(2), x_j.unsqueeze(2)], dim=2).reshape(b, 2 * c, n, _)
+        return self.nn(x)
+
+
+class GraphSAGE(nn.Module):
+    """GraphSAGE (reference torch_vertex.py:116-131): nn2(cat[x, max_k nn1(x_j)]) — a plain concatenation, not interleaved."""
+
+    def __init__(self, in_channels, out_channels, act="relu", norm=None, bias=True):
+        super().__init__()
+        self.nn1 = BasicConv([in_channels, in_channels], act, norm, bias)
+        self.nn2 = BasicConv([in_channels * 2, out_channels], act, norm, bias)
+
+    def _hip_plan(self, x):
+        """nn1's plan when the gathered half runs on the edge kernels: fp32 CUDA x with nn1's input channels."""
+        if not _fp32_cuda(x) or x.shape[1] != self.nn1[0].in_channels:
+            return None
+        return _basic_conv_plan(self.nn1)
+
+    def forward(self, x, edge_index, y=None):
+        idx = edge_index[0]
+        plan = self._hip_plan(x)
+        if plan is not None and idx.shape[2] <= 255:
+            return self.nn2(torch.cat([x, self._nn1_max_hip(x, idx, y, *plan)], dim=1))
+        x_j = _batched_index_select(x if y is None else y, idx)
+        x_j = self.nn1(x_j).max(dim=-1, keepdim=True).values
+        return self.nn2(torch.cat([x, x_j], dim=1))
+
+    @staticmethod
+    def _nn1_max_hip(x, idx, y, conv, bn, act):
+        """max_k nn1(x_j) without the (B, C, N, k) tensors: nn1's 1x1 convolution is per-position linear, so
+        z = (W src + bias)[j] — one per-node projection, then the edge kernels with a zero centre projection (qc = None),
+        BN statistics over (B, N, k) included."""
+        bg, c = x.shape[:2]
+        src = (x if y is None else y).reshape(bg, c, -1)
+        qs = pointwise_conv(src, conv.weight, None, conv.groups)
+        O = conv.out_channels
+        if bn is not None and bn.training and bn.track_running_stats:
+            bn.num_batches_tracked += 1                    # the running statistics themselves are updated by edge_aggregate
+        m = ops.edge_aggregate(qs, None, idx, conv.bias, None if bn is None else bn.weight, None if bn is None else bn.bias,
+                               bn, slice(0, O), act)
+        return m.unsqueeze(-1)
+
+
+class GINConv2d(nn.Module):
+    """GIN (reference torch_vertex.py:134-150): nn((1 + eps) x + sum_k x_j), eps a learnable (1,) parameter (init 0)."""
+
+    def __init__(self, in_channels, out_channels, act="relu", norm=None, bias=True):
+        super().__init__()
+        self.nn = BasicConv([in_channels, out_channels], act, norm, bias)
+        eps_init = 0.0
+        self.eps = nn.Parameter(torch.Tensor([eps_init]))
+
+    def _hip_plan(self, x):
+        """nn's plan when the HIP sum applies: fp32 CUDA x with nn's input channels, eps an fp32 device tensor."""
+        if not _fp32_cuda(x) or x.shape[1] != self.nn[0].in_channels or not self.eps.is_cuda or self.eps.dtype != torch.float32:
+            return None
+        return _basic_conv_plan(self.nn)
+
+    def forward(self, x, edge_index, y=None):
+        if self._hip_plan(x) is not None:
+            bg, c = x.shape[:2]
+            h = ops.gin_aggregate(x.reshape(bg, c, -1), edge_index[0], self.eps, None if y is None else y.reshape(bg, c, -1))
+            return self.nn(h.reshape(x.shape))
+        x_j = _batched_index_select(x if y is None else y, edge_index[0])
+        x_j = torch.sum(x_j, -1, keepdim=True)
+        return self.nn((1 + self.eps) * x + x_j)
+
+
 class GraphConv2d(nn.Module):
     """Static graph convolution dispatcher (reference torch_vertex.py:153-173)."""
 
@@ -154,8 +283,14 @@ class GraphConv2d(nn.Module):
         super().__init__()
         if conv == "edge":
             self.gconv = EdgeConv2d(in_channels, out_channels, act, norm, bias)
+        elif conv == "gat":
+            self.gconv = GraphAtten(in_channels, out_channels, act, norm, bias)
         elif conv == "mr":
             self.gconv = MRConv2d(in_channels, out_channels, act, norm, bias)
+        elif conv == "sage":
+            self.gconv = GraphSAGE(in_channels, out_channels, act, norm, bias)
+        elif conv == "gin":
+            self.gconv = GINConv2d(in_channels, out_channels, act, norm, bias)
         else:
             raise NotImplementedError("conv:{} is not supported".format(conv))
 

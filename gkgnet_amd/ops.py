@@ -2,6 +2,9 @@
 
     knn_graph(x, y, relative_pos, k, dilation)  ==  DenseDilatedKnnGraph.forward   (reference torch_edge.py:164-176)
     max_relative(x, nn_idx, y)                  ==  max_k(gather(y|x, idx) - x)    (reference torch_vertex.py:49-54)
+    edge_aggregate(...)                         ==  EdgeConv2d / GraphSAGE.nn1's max over neighbours  (:82-131)
+    gin_aggregate(x, nn_idx, eps, y)            ==  (1 + eps) x + sum_k gather(y|x, idx)   (reference torch_vertex.py:134-150)
+    gat_aggregate(x, nn_idx, w, b, y)           ==  GraphAtten's attention-weighted sum    (reference torch_vertex.py:16-37)
 
 Tensors keep the reference layout (B*G, c, N, 1) / (B*G, c, N).  torch is used only for device
 memory and the current HIP stream; all arithmetic runs in the library.  There is no CPU path:
@@ -143,7 +146,8 @@ class _EdgeAggregate(torch.autograd.Function):
         _need_cuda(qs, qc, nn_idx)
         B, O, M = qs.shape
         N, k = nn_idx.shape[1:]
-        qs, qc, nn_idx = qs.contiguous(), qc.contiguous(), nn_idx.contiguous()
+        qs, nn_idx = qs.contiguous(), nn_idx.contiguous()
+        qc = None if qc is None else qc.contiguous()
         dev = qs.device
         cnt = B * N * k
         bias_v = torch.zeros(O, dtype=torch.float32, device=dev) if bias is None else bias.detach().float()
@@ -198,15 +202,129 @@ class _EdgeAggregate(torch.autograd.Function):
             elif has_bias:
                 dbias = a * dbeta                                     # eval: u = a (z + bias - running_mean) + beta
         dqs = torch.zeros_like(qs)
-        dqc = torch.empty_like(qc)
+        # qc None (Qc = 0): dqc is only needed for the bias gradient without normalisation
+        dqc = torch.empty_like(qc) if qc is not None else \
+            (torch.empty((B, O, N), dtype=torch.float32, device=dev) if not has_bn and has_bias else None)
         _lib.check(lib.gkg_edge_bwd(_ptr(g), _ptr(qs), _ptr(qc), _ptr(nn_idx), _ptr(arg), _ptr(a), _ptr(c), _ptr(mean0), _ptr(invstd),
                                     _ptr(mg), _ptr(mgz), _ptr(dqs), _ptr(dqc), B, O, N, M, k, act, _stream()), "gkg_edge_bwd")
         if not has_bn and has_bias:
             dbias = -dqc.sum(dim=(0, 2))                              # sum of the winning-edge gradients
         if has_bn and train_stats and has_bias:
             dbias = torch.zeros(O, dtype=torch.float32, device=dev)   # exactly zero: BN removes the mean
-        return dqs, dqc, None, dbias, dgamma, dbeta, None, None, None
+        return dqs, (dqc if qc is not None else None), None, dbias, dgamma, dbeta, None, None, None
 
 
 def edge_aggregate(qs, qc, nn_idx, bias, gamma, beta, bn, sl, act):
+    """``qc`` None means a zero centre projection: out = max_k act(norm(Q[idx] + bias)), GraphSAGE's nn1 on the gathered
+    neighbours (reference torch_vertex.py:116-131)."""
     return _EdgeAggregate.apply(qs, qc, nn_idx, bias, gamma, beta, bn, sl, act)
+
+
+# ------------------------------------------------------------------------------------------- GIN / graph-attention
+def _gconv_ws(lib, B, C, N, M, k, dev):
+    nbytes = int(lib.gkg_gconv_workspace_bytes(B, C, N, M, k))
+    return torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+
+
+def _gconv_args(x, nn_idx, src):
+    _need_cuda(x, nn_idx, src)
+    xs = _tokens(x)
+    ss = None if src is None else _tokens(src)
+    if xs.dtype != torch.float32 or (ss is not None and (ss.dtype != torch.float32 or ss.shape[:2] != xs.shape[:2])):
+        raise _lib.GkgError("x / y must be fp32 with the same batch and channels")
+    idx = nn_idx.contiguous()
+    if idx.dtype != torch.int64 or idx.dim() != 3 or tuple(idx.shape[:2]) != (xs.shape[0], xs.shape[2]):
+        raise _lib.GkgError(f"nn_idx must be int64 (B,N,k); got {idx.dtype} {tuple(idx.shape)}")
+    return xs, ss, idx
+
+
+class _GinAggregate(torch.autograd.Function):
+    """h = (1 + eps) x + sum_k src[idx] (csrc/gkg_gconv.hip; reference torch_vertex.py:134-150)."""
+
+    @staticmethod
+    def forward(ctx, x, src, nn_idx, eps):
+        lib = _lib.load()
+        B, C, N = x.shape
+        M = N if src is None else src.shape[2]
+        k = nn_idx.shape[2]
+        e = eps.detach().contiguous()
+        h = torch.empty_like(x)
+        _lib.check(lib.gkg_gin_fwd(_ptr(x), _ptr(src), _ptr(nn_idx), _ptr(e), _ptr(h), B, C, N, M, k, _stream()), "gkg_gin_fwd")
+        ctx.save_for_backward(x, nn_idx, e)
+        ctx.dims = (B, C, N, M, k, src is not None)
+        return h
+
+    @staticmethod
+    def backward(ctx, gh):
+        lib = _lib.load()
+        x, nn_idx, e = ctx.saved_tensors
+        B, C, N, M, k, has_src = ctx.dims
+        gh = gh.contiguous().float()
+        gx = torch.empty((B, C, N), dtype=torch.float32, device=gh.device)
+        gsrc = torch.empty((B, C, M), dtype=torch.float32, device=gh.device) if has_src else None
+        geps = torch.empty(1, dtype=torch.float64, device=gh.device) if ctx.needs_input_grad[3] else None
+        ws = _gconv_ws(lib, B, C, N, M, k, gh.device)
+        _lib.check(lib.gkg_gin_bwd(_ptr(gh), _ptr(x), _ptr(e), _ptr(nn_idx), _ptr(gx), _ptr(gsrc), _ptr(geps), B, C, N, M, k,
+                                   _ptr(ws), ws.numel(), _stream()), "gkg_gin_bwd")
+        return gx, gsrc, None, None if geps is None else geps.float().view_as(e)
+
+
+def gin_aggregate(x: torch.Tensor, nn_idx: torch.Tensor, eps: torch.Tensor, y: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """h[b,c,n] = (1 + eps) x[b,c,n] + sum_k src[b,c,nn_idx[b,n,k]], src = y if given else x; fp32 (B,C,N[,1]) -> (B,C,N).
+    Differentiable w.r.t. x, y and eps (a 1-element fp32 tensor on the device; read there, no host sync)."""
+    xs, ys, idx = _gconv_args(x, nn_idx, y)
+    _need_cuda(eps)
+    if eps.numel() != 1 or eps.dtype != torch.float32:
+        raise _lib.GkgError("eps must be a 1-element fp32 tensor")
+    return _GinAggregate.apply(xs, ys, idx, eps)
+
+
+class _GatAggregate(torch.autograd.Function):
+    """agg = sum_k softmax_k(a[:C].x_i + a[C:].src_j + bias) src_j (csrc/gkg_gconv.hip; reference torch_vertex.py:16-37)."""
+
+    @staticmethod
+    def forward(ctx, x, src, nn_idx, w, bias):
+        lib = _lib.load()
+        B, C, N = x.shape
+        M = N if src is None else src.shape[2]
+        k = nn_idx.shape[2]
+        wv = w.detach().contiguous()
+        bv = None if bias is None else bias.detach().contiguous()
+        agg = torch.empty_like(x)
+        p = torch.empty((B, N, k), dtype=torch.float32, device=x.device)
+        ws = _gconv_ws(lib, B, C, N, M, k, x.device)
+        _lib.check(lib.gkg_gat_fwd(_ptr(x), _ptr(src), _ptr(nn_idx), _ptr(wv), _ptr(bv), _ptr(agg), _ptr(p), B, C, N, M, k,
+                                   _ptr(ws), ws.numel(), _stream()), "gkg_gat_fwd")
+        ctx.save_for_backward(x, src, nn_idx, wv, p)
+        ctx.dims = (B, C, N, M, k, bias is not None)
+        return agg
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        x, src, nn_idx, wv, p = ctx.saved_tensors
+        B, C, N, M, k, has_bias = ctx.dims
+        g = g.contiguous().float()
+        dev = g.device
+        gx = torch.empty((B, C, N), dtype=torch.float32, device=dev)
+        gsrc = torch.empty((B, C, M), dtype=torch.float32, device=dev) if src is not None else None
+        da = torch.empty(2 * C, dtype=torch.float64, device=dev) if ctx.needs_input_grad[3] else None
+        db = torch.empty(1, dtype=torch.float64, device=dev) if has_bias and ctx.needs_input_grad[4] else None
+        ws = _gconv_ws(lib, B, C, N, M, k, dev)
+        _lib.check(lib.gkg_gat_bwd(_ptr(g), _ptr(x), _ptr(src), _ptr(nn_idx), _ptr(wv), _ptr(p), _ptr(gx), _ptr(gsrc), _ptr(da),
+                                   _ptr(db), B, C, N, M, k, _ptr(ws), ws.numel(), _stream()), "gkg_gat_bwd")
+        return gx, gsrc, None, None if da is None else da.float(), None if db is None else db.float()
+
+
+def gat_aggregate(x: torch.Tensor, nn_idx: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                  y: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Graph-attention aggregation: e[b,n,k] = weight[:C].x[b,:,n] + weight[C:].src[b,:,j] + bias (j = nn_idx[b,n,k]),
+    p = softmax over k, agg[b,c,n] = sum_k p src[b,c,j]; src = y if given else x; fp32 (B,C,N[,1]) -> (B,C,N).
+    ``weight``: the 2C weights of GraphAtten.a (any shape), ``bias``: its 1-element bias or None.  The centre of every edge
+    is the query n itself.  Differentiable w.r.t. x, y, weight and bias."""
+    xs, ys, idx = _gconv_args(x, nn_idx, y)
+    _need_cuda(weight, bias)
+    C = xs.shape[1]
+    if weight.numel() != 2 * C or weight.dtype != torch.float32 or (bias is not None and (bias.numel() != 1 or bias.dtype != torch.float32)):
+        raise _lib.GkgError(f"weight must hold 2C = {2 * C} fp32 values, bias one (or None)")
+    return _GatAggregate.apply(xs, ys, idx, weight.reshape(-1), None if bias is None else bias.reshape(-1))

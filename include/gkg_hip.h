@@ -139,7 +139,10 @@ int gkg_mr_bwd(const void* g, const int64_t* nn_idx, const uint8_t* argmax, void
  *                       (z - mean0) invstd: dbeta, dgamma and (divided by B N k) the two means of the BN backward.
  *   gkg_edge_bwd        dz[n][k] = a (g' [k == argmax] - mg - zhat[n][k] mgz) for every edge; dqs[nn_idx] += dz (atomics; dqs
  *                       zero on entry), dqc[n] = -sum_k dz.  mg == NULL: statistics are constants, only the winning edge
- *                       carries gradient. */
+ *                       carries gradient.
+ *   qc == NULL (all four): Qc is zero, z = Q[nn_idx] + bias — GraphSAGE's nn1 applied to the gathered neighbours
+ *                       (Grapher(conv='sage'); reference torch_vertex.py:116-131).  dqc may then be NULL (it is written
+ *                       when given).  A non-NULL qc computes exactly what it did before. */
 int gkg_edge_stats(const float* qs, const float* qc, const int64_t* nn_idx, double* sums, int B, int O, int N, int M, int k,
                    void* stream);
 int gkg_edge_fwd(const float* qs, const float* qc, const int64_t* nn_idx, const float* a, const float* c, float* out,
@@ -150,6 +153,34 @@ int gkg_edge_bwd_stats(const float* g, const float* qs, const float* qc, const i
 int gkg_edge_bwd(const float* g, const float* qs, const float* qc, const int64_t* nn_idx, const uint8_t* argmax,
                  const float* a, const float* c, const float* mean0, const float* invstd, const float* mg, const float* mgz,
                  float* dqs, float* dqc, int B, int O, int N, int M, int k, int act, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * GIN and graph-attention aggregations (Grapher(conv='gin' / 'gat'); reference torch_vertex.py:134-150 GINConv2d and
+ * :16-37 GraphAtten).  Channel-major fp32 x (B, C, N), src (B, C, M) or NULL (self graph: src = x, M == N), nn_idx (B, N, k)
+ * int64 (== edge_index[0]; out-of-range entries are clamped into [0, M)).  The centre of every edge is the query itself
+ * (edge_index[1][b][n][k] == n, as the k-NN produces it), so edge_index[1] is not an argument.  No (B, C, N, k) tensor is
+ * formed, and every backward is bit-identical from run to run: the source gradients are gathers over the transposed graph
+ * (built in the workspace, each key's edges in edge order), the parameter gradients fixed-order fp64 reductions.
+ *   gkg_gconv_workspace_bytes  workspace the calls below need (0: invalid sizes).
+ *   gkg_gin_fwd   h[b][c][n] = (1 + eps[0]) x[b][c][n] + sum_k src[b][c][nn_idx[b][n][k]]   (eps: 1 float in device memory)
+ *   gkg_gin_bwd   gx = (1 + eps) gh; gsrc[j] += gh[n] over every edge (gsrc == NULL: into gx, self graph); geps (optional,
+ *                 1 double) = sum gh x.  gx, gsrc, geps are fully overwritten.
+ *   gkg_gat_fwd   a: 2C floats (the Conv2d(2C, 1, 1) weight), bias: 1 float or NULL.  t[n] = a[:C] . x[n] + bias,
+ *                 s[m] = a[C:] . src[m], p[b][n][k] = softmax_k(t[n] + s[nn_idx]) (max-subtracted; (B, N, k) out, the
+ *                 backward's input), agg[b][c][n] = sum_k p src[c][nn_idx].
+ *   gkg_gat_bwd   g = d agg.  dp = g[n] . src[j], de = p (dp - sum_k p dp); gsrc[j] += p g[n] + de a[C:] (src and gsrc both
+ *                 NULL: self graph, into gx); gx[n] += (sum_k de) a[:C]; da (optional, 2C doubles) = [sum (sum_k de) x[n],
+ *                 sum de src[j]]; dbias (optional, 1 double) = sum de.  All outputs fully overwritten. */
+size_t gkg_gconv_workspace_bytes(int B, int C, int N, int M, int k);
+int gkg_gin_fwd(const float* x, const float* src, const int64_t* nn_idx, const float* eps, float* h, int B, int C, int N, int M,
+                int k, void* stream);
+int gkg_gin_bwd(const float* gh, const float* x, const float* eps, const int64_t* nn_idx, float* gx, float* gsrc, double* geps,
+                int B, int C, int N, int M, int k, void* ws, size_t ws_bytes, void* stream);
+int gkg_gat_fwd(const float* x, const float* src, const int64_t* nn_idx, const float* a, const float* bias, float* agg, float* p,
+                int B, int C, int N, int M, int k, void* ws, size_t ws_bytes, void* stream);
+int gkg_gat_bwd(const float* g, const float* x, const float* src, const int64_t* nn_idx, const float* a, const float* p, float* gx,
+                float* gsrc, double* da, double* dbias, int B, int C, int N, int M, int k, void* ws, size_t ws_bytes,
+                void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Token-major variants used inside the fused Grapher block (activations (B, N, C), C = G*c, fp32).
