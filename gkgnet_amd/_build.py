@@ -12,8 +12,7 @@ INCLUDE = os.path.join(os.path.dirname(PKG), "include")
 LIB = os.path.join(PKG, "libgkg_hip.so")
 SOURCES = ["gkg_api.hip", "gkg_knn.hip", "gkg_knn_f32.hip", "gkg_knn_f32_norp.hip", "gkg_knn_f32_mr.hip", "gkg_knn_f32_mr_norp.hip", "gkg_knn_bf.hip", "gkg_knn_bf_norp.hip", "gkg_knn_pf.hip", "gkg_knn_pf_norp.hip", "gkg_mr.hip", "gkg_dense.hip", "gkg_gemm_x6.hip", "gkg_edge.hip", "gkg_mrgemm.hip", "gkg_stem.hip", "gkg_block.hip", "gkg_gconv.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
-         "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wno-pass-failed", "-I" + INCLUDE, "-I" + CSRC] + \
-        os.environ.get("GKG_BUILD_FLAGS", "").split()          # measurement builds (-D switches of the ablation tools)
+         "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wno-pass-failed", "-I" + INCLUDE, "-I" + CSRC]
 
 
 def csrc_sha16() -> str:
@@ -48,8 +47,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     objdir = os.path.join(PKG, "build")
     os.makedirs(objdir, exist_ok=True)
     hipcc = _hipcc()
-    # objects are only as good as the flags they were compiled with (GKG_BUILD_FLAGS adds -D ablation switches: no stores, no
-    # loads ...): a stamp of the flag list sits beside them, and a different list rebuilds everything
+    # objects are only as good as the flags they were compiled with: a stamp of the flag list sits beside them, and a different
+    # list (an edit of FLAGS) rebuilds everything
     stamp = os.path.join(objdir, ".flags")
     flags_now = " ".join(FLAGS)
     try:
@@ -57,7 +56,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     except OSError:
         flags_then = None
     if flags_then != flags_now:
-        force = force or flags_then is not None or bool(os.environ.get("GKG_BUILD_FLAGS", "").split())
+        force = force or flags_then is not None
         with open(stamp, "w") as fh:
             fh.write(flags_now)
     jobs = []

@@ -48,10 +48,6 @@ __device__ __forceinline__ unsigned x6_cvt2(float a, float b) {
 
 // two floats -> packed (hi, mid, lo) bf16 pairs; the residuals are exact fp32 differences
 __device__ __forceinline__ void x6_split2(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
-#ifdef X6_ABLATE_NOSPLIT
-  h = x6_cvt2(x0, x1); m = x6_cvt2(x1, x0); l = h ^ 0x00010001u;
-  return;
-#endif
   h = x6_cvt2(x0, x1);
   const float r0 = x0 - __uint_as_float(h << 16), r1 = x1 - __uint_as_float(h & 0xffff0000u);
   m = x6_cvt2(r0, r1);
@@ -189,18 +185,6 @@ __device__ __forceinline__ void x6_dma16(const void* sbase, unsigned voff, unsig
                : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
 }
 
-// -DX6_TIMELINE (tools/ubench/x6_timeline.py only): phase timestamps (s_memtime) of every 16th workgroup's first wave
-#ifdef X6_TIMELINE
-__device__ long long* x6_tl_buf;
-#define X6_TL(p)                                                                                                      \
-  do {                                                                                                                \
-    if (x6_tl_buf && tid == 0 && (blockIdx.x & 15) == 0 && (blockIdx.x >> 4) < 4096)                                 \
-      x6_tl_buf[(blockIdx.x >> 4) * 8 + (p)] = (long long)__builtin_readcyclecounter();                               \
-  } while (0)
-#else
-#define X6_TL(p) do {} while (0)
-#endif
-
 // BN: columns per tile — 32 NI, or 80 with NI = 3 (the last 32-column block is half used).  Every GKGNet width is a multiple of
 // 80, so 80-column tiles cover 80 / 160 outputs with one / two workgroups per row block where 64-column tiles need two / three:
 // at the short-K stage-1 / stage-2 shapes the launch time follows the number of requests (A is fetched once per column tile,
@@ -222,7 +206,6 @@ __global__ __launch_bounds__(256) void gemm_x6_kernel(X6Args g) {
   const int per_row = g.ntiles * g.ksplit, inner = slot % per_row;
   const int tn = inner % g.ntiles, ks = inner / g.ntiles, tm = (slot / per_row) * 8 + xcd;
   if (tm >= g.mtiles) return;
-  X6_TL(0);
   const int m0 = tm * BM, n0 = tn * BN;
   const int M = g.M, N = g.N;
   const int K = g.ksplit > 1 ? min(g.K - ks * g.kper * BK, g.kper * BK) : g.K;       // this workgroup's share of the contraction
@@ -308,9 +291,6 @@ __global__ __launch_bounds__(256) void gemm_x6_kernel(X6Args g) {
   auto op = [&](int i) {
     const int p = i & 3, o = i >> 2;
     float& x0 = f[2 * p]; float& x1 = f[2 * p + 1];
-#ifdef X6_ABLATE_NOSPLIT          // tools/ubench/x6_nosplit.py: what the kernels cost without the operand split (3 of 11 steps kept)
-    if (o != 0 && o != 5 && o != 10) return;
-#endif
     if (o == 0) asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(sh_[p]) : "v"(x0), "v"(x1));
     if (o == 1) asm volatile("v_lshlrev_b32 %0, 16, %1" : "=v"(t0_[p]) : "v"(sh_[p]));
     if (o == 2) asm volatile("v_and_b32 %0, 0xffff0000, %1" : "=v"(t1_[p]) : "v"(sh_[p]));
@@ -368,12 +348,10 @@ __global__ __launch_bounds__(256) void gemm_x6_kernel(X6Args g) {
   dma_a(0); dma_b(0);
   if (nk > 1) { dma_a(1); dma_b(1); }
   if (nk > 2) dma_a(2);
-  X6_TL(1);
   if (nk > 2) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(8 + BI_MIN) : "memory");
   else if (nk > 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(4 + BI_MIN) : "memory");
   else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
-  X6_TL(2);
   read_raw(0, 0); read_b(0, 0, 0);
 #pragma unroll
   for (int i = 0; i < 44; ++i) op(i);
@@ -389,7 +367,6 @@ __global__ __launch_bounds__(256) void gemm_x6_kernel(X6Args g) {
   }
   half(0, true, nk - 1, 1);
   half(1, false, 0, 0);
-  X6_TL(3);
 
   // X6_BNBWD: the producer's y values of this lane's 16 rows x NI columns are fetched NOW, ahead of the tile's stores and the
   // barrier, so that their latency is off the workgroup's tail
@@ -472,11 +449,6 @@ __global__ __launch_bounds__(256) void gemm_x6_kernel(X6Args g) {
       }
     }
   }
-  X6_TL(4);
-#ifdef X6_TIMELINE
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  X6_TL(5);
-#endif
   if (EPI == X6_BNBWD) {
     // Backward statistics of the PRODUCER's BN (see X6Args): per lane the 16 rows of its column, y read with the same
     // 128-byte row segments the tile was stored with; the two half-waves and the four waves are combined through LDS in
@@ -873,9 +845,6 @@ __device__ __forceinline__ void x6w_op(float (&raw)[4][8], X6WFrag& fn, unsigned
   constexpr int blk = I / 44, u = I % 44, p = u & 3, o = u >> 2;
   float& x0 = raw[blk][2 * p]; float& x1 = raw[blk][2 * p + 1];
   unsigned w;
-#ifdef X6_ABLATE_NOSPLIT
-  if constexpr (o != 0 && o != 5 && o != 10) return;
-#endif
   if constexpr (o == 0) { asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(w) : "v"(x0), "v"(x1)); fn[blk][0][p] = w; }
   if constexpr (o == 1) asm volatile("v_lshlrev_b32 %0, 16, %1" : "=v"(t0[p]) : "v"(fn[blk][0][p]));
   if constexpr (o == 2) asm volatile("v_and_b32 %0, 0xffff0000, %1" : "=v"(t1[p]) : "v"(fn[blk][0][p]));
@@ -1348,19 +1317,8 @@ __global__ __launch_bounds__(256) void wgrad_x6_batch_kernel(X6WgradBatch b) {
   const int local = bid - b.begin[i], gx = b.gridx[i];
   const int z = local / gx, lin = local - z * gx;
   const X6WgradArgs g = b.p[i];
-#ifdef X6_TIMELINE      // tools/ubench/wgrad_batch_timeline.py: every workgroup's start / end / placement / problem
-  if (x6_tl_buf && threadIdx.x == 0 && bid < 4096) {
-    long long* t = x6_tl_buf + 4096 * 8 + bid * 4;
-    t[0] = (long long)__builtin_readcyclecounter();
-    t[2] = ((long long)__builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11)) << 8) | (__builtin_amdgcn_s_getreg((20) | (0 << 6) | (31 << 11)) & 0xf);
-    t[3] = i * 2 + (b.wide[i] ? 1 : 0);
-  }
-#endif
   if (b.wide[i]) wgrad_x6_wide_body(g, lin, z);
   else wgrad_x6_dma_body(g, lin, z);
-#ifdef X6_TIMELINE
-  if (x6_tl_buf && threadIdx.x == 0 && bid < 4096) x6_tl_buf[4096 * 8 + bid * 4 + 1] = (long long)__builtin_readcyclecounter();
-#endif
 }
 
 inline bool x6_bad_dim(int v) { return v <= 0 || (v & 3) != 0; }
@@ -1370,12 +1328,6 @@ inline size_t x6_plane_units(int n, int k, int nb) {       // uint4 units of one
 
 }  // namespace gkg
 using namespace gkg;
-
-#ifdef X6_TIMELINE
-extern "C" int gkg_debug_set_x6_timeline(void* buf) {
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(x6_tl_buf), &buf, sizeof(buf));
-}
-#endif
 
 namespace gkg {
 // Train-mode BN parameters from the fp64 column sums of Y (which EXCLUDES the conv bias, folded here); re-zeroes the sums

@@ -4,12 +4,6 @@
 #include "gkg_knn_common.h"
 #include "gkg_topk_merge.h"
 
-// -DPF_ABL=<bits> (tools/ubench/pf_ablate.py only; results wrong, timing valid): 1 no candidate appends (tested, never stored),
-// 2 no MFMAs, 4 no relative_pos loads, 8 no selection at all (the accumulators are summed into a sink), 16 no key-operand loads
-#ifndef PF_ABL
-#define PF_ABL 0
-#endif
-
 namespace gkg {
 
 // ------------------------------------------------------------------------------------------ prefilter + exact re-rank
@@ -74,7 +68,6 @@ __global__ __launch_bounds__(256, KDW <= 16 ? 3 : 2) void knn_pf_kernel(KnnArgs 
   const int lin = blockIdx.x;
   int bg, qt;
   if (!knn_map(a, lin, bg, qt)) return;              // XCD-aware map shared with knn_tile_kernel (gkg_knn_common.h)
-  KNN_TL(0);
   const int n0 = qt * QT;
   const int N = a.N, M = a.M, cpad = a.cpad, cp16 = a.cp16, S16 = cp16 >> 4;
   const int lane_n = n0 + lane;
@@ -152,7 +145,6 @@ __global__ __launch_bounds__(256, KDW <= 16 ? 3 : 2) void knn_pf_kernel(KnnArgs 
   }
   if (PBUF > 0) reinterpret_cast<float*>(xq_lo + QT * qpitch + (size_t)PBUF * 256 * 8)[tid] = INFINITY;   // shared admission bounds (see flush)
   __syncthreads();
-  KNN_TL(2);
 
   const float* sqy = a.sqy + (size_t)bg * M;
   const bool two_blocks = n0 + 32 < N;               // wave-uniform
@@ -176,16 +168,6 @@ __global__ __launch_bounds__(256, KDW <= 16 ? 3 : 2) void knn_pf_kernel(KnnArgs 
     unsigned cw_now = cw;
     asm volatile("" : "+v"(cw_now));
     int bcnt = (int)((cw_now - cw0) / (256 * 8));
-#if PF_ABL & 64
-    {                                               // tools/ubench/pf_ablate.py counters: flushes, entries, insert rounds (max over lanes)
-      unsigned long long* ctr = reinterpret_cast<unsigned long long*>(a.part_v);
-      if (lane == 0) atomicAdd(&ctr[0], 1ull);
-      atomicAdd(&ctr[1], (unsigned long long)bcnt);
-      int mx = bcnt;
-      for (int m_ = 1; m_ < 64; m_ <<= 1) mx = max(mx, __shfl_xor(mx, m_, 64));
-      if (lane == 0) atomicAdd(&ctr[2], (unsigned long long)mx);
-    }
-#endif
     if constexpr (PBUF >= 12 && KDW >= 16) {
       if (__builtin_amdgcn_ballot_w64(bcnt > 3) != 0ull) {
         double b[16];
@@ -238,12 +220,6 @@ __global__ __launch_bounds__(256, KDW <= 16 ? 3 : 2) void knn_pf_kernel(KnnArgs 
   // stage 3).  With 12-entry lists they cost the third wave per SIMD and the kernel loses (stage 1 2230 -> 2450 us).
   constexpr bool AHEAD = KDW > 16 || SB;
   float4 rq0[4], rq1[4];
-#if PF_ABL & 4
-  for (int g_ = 0; g_ < 4; ++g_) { rq0[g_] = make_float4(0.f, 0.f, 0.f, 0.f); rq1[g_] = make_float4(0.f, 0.f, 0.f, 0.f); }
-#endif
-#if PF_ABL & (1 | 8)
-  float abl_sink = INFINITY;
-#endif
   const size_t rp_row0 = (size_t)min(n0, N - 1) * M;
   const size_t rp_left = ((size_t)N * M - rp_row0) * sizeof(float);
   const __amdgpu_buffer_rsrc_t rp_rsrc = __builtin_amdgcn_make_buffer_rsrc(
@@ -252,7 +228,7 @@ __global__ __launch_bounds__(256, KDW <= 16 ? 3 : 2) void knn_pf_kernel(KnnArgs 
   const unsigned rp_o1 = (unsigned)(((size_t)(32 + l31) * M + 4 * kk) * sizeof(float));
   auto fetch_side = [&](int tt) __attribute__((always_inline)) {
     const int mm0 = tt * KT;
-    if (HAS_RP && !(PF_ABL & 4)) {
+    if (HAS_RP) {
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         rq0[g] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rp_rsrc, (int)(rp_o0 + 32 * g), mm0 * 4, 0));
@@ -297,10 +273,6 @@ __global__ __launch_bounds__(256, KDW <= 16 ? 3 : 2) void knn_pf_kernel(KnnArgs 
             const bf16x8_t kl = __builtin_bit_cast(bf16x8_t, bl_[u]);
             const bf16x8_t qh0 = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(xh0 + 32 * u));
             const bf16x8_t ql0 = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(xl0 + 32 * u));
-#if PF_ABL & 2
-            acc0[u] += __uint_as_float(bh_[u].x ^ bl_[u].y) + __builtin_bit_cast(float, (unsigned)(qh0[0] != ql0[1]));
-            acc1[u] += __uint_as_float(bh_[u].z ^ bl_[u].w);
-#else
             if (two_blocks) {
               const bf16x8_t qh1 = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(xh1 + 32 * u));
               const bf16x8_t ql1 = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(xl1 + 32 * u));
@@ -315,17 +287,14 @@ __global__ __launch_bounds__(256, KDW <= 16 ? 3 : 2) void knn_pf_kernel(KnnArgs 
               acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kh, ql0, acc0, 0, 0, 0);
               acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kh, qh0, acc0, 0, 0, 0);
             }
-#endif
           }
         }
         __builtin_amdgcn_sched_barrier(0);                        // the next tile's batch: behind the MFMAs that read this one
-#if !(PF_ABL & 16)
 #pragma unroll
         for (int u = 0; u < KB; ++u) {
           bh_[u] = u < S16 ? ynh[(size_t)(2 * u) * MR] : make_uint4(0, 0, 0, 0);
           bl_[u] = u < S16 ? ynl[(size_t)(2 * u) * MR] : make_uint4(0, 0, 0, 0);
         }
-#endif
       } else
       for (int s0 = 0; s0 < S16; s0 += KB) {
         const bool last = s0 + KB >= S16;                         // uniform: prefetch the NEXT tile's first batch
@@ -364,14 +333,9 @@ __global__ __launch_bounds__(256, KDW <= 16 ? 3 : 2) void knn_pf_kernel(KnnArgs 
         }
       }
     }
-    if (iv / NW < 10) KNN_TL(3 + 2 * (iv / NW));
     if (AHEAD && iv + NW < ktiles) fetch_side(t_next); // in flight during the selection below
     // ---- lane l <- all 32 keys of query n0 + l (permlane swap as in knn_tile_kernel); approximate distance (without the
     //      query's own |x|^2, a per-query constant) = acc + |y|^2, keys past M masked by MASKED_SQ
-#if PF_ABL & 8
-    for (int r_ = 0; r_ < 16; ++r_) abl_sink = fminf(abl_sink, acc0[r_] + acc1[r_]);
-    if (iv + NW >= ktiles) top.template insert<false>(abl_sink, 0);
-#else
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       float lo[4], hi[4];
@@ -389,14 +353,10 @@ __global__ __launch_bounds__(256, KDW <= 16 ? 3 : 2) void knn_pf_kernel(KnnArgs 
           const int row = 8 * g + 4 * hh + j;
           const float d = hh ? hi[j] : lo[j];     // |y|^2 is already inside (channels pf_c, pf_c + 1 of the contraction)
           if constexpr (PBUF > 0) {
-#if PF_ABL & 1
-            abl_sink = fminf(abl_sink, d <= thr ? d : abl_sink);
-#else
             if (d <= thr) {                       // '<=': the tiles are not visited in index order (NaN fails)
               *(lds_v2u_t*)(size_t)cw = v2u_t{__float_as_uint(d), (unsigned)(m0 + row)};
               asm volatile("v_add_u32_e32 %0, %1, %0" : "+v"(cw) : "i"(256 * 8) : "memory");
             }
-#endif
           } else {
             top.template insert<KDW >= 18>(d, m0 + row);
           }
@@ -404,19 +364,12 @@ __global__ __launch_bounds__(256, KDW <= 16 ? 3 : 2) void knn_pf_kernel(KnnArgs 
       }
       if (PBUF > 0 && ((g == 3 && iv + NW >= ktiles) || __builtin_amdgcn_ballot_w64(cw > cw_lim) != 0ull)) flush();
     }
-#if PF_ABL & 1
-    if (iv + NW >= ktiles) top.template insert<false>(abl_sink, 0);
-#endif
-#endif
-    if (iv / NW < 10) KNN_TL(4 + 2 * (iv / NW));
   }
 
   // ---- the 4 per-wave lists -> LDS; wave 0 merges them per query and collects the survivors.  (A rank-counting merge on all
   //      four waves, as in knn_tile_kernel, measured the same launch time here: it trades wave 0's LDS latency, which the
   //      CU's other workgroups fill, for vector work — and vector issue is what this kernel is short of.)
-  KNN_TL(28);
   __syncthreads();                       // everyone is done with the staged queries
-  KNN_TL(29);
   float* lv = smem;                      // [NW][KDW][64]
   int* li = reinterpret_cast<int*>(smem + NW * KDW * 64);
   int* sidx = li + NW * KDW * 64;        // [SMAX][64] survivor key indices (ascending prefilter distance)
@@ -499,9 +452,7 @@ __global__ __launch_bounds__(256, KDW <= 16 ? 3 : 2) void knn_pf_kernel(KnnArgs 
       }
     }
   }
-  KNN_TL(30);
   __syncthreads();
-  KNN_TL(25);
 
   // ---- exact contract distance of the pairs that need it: one thread per pair, dense over the workgroup
   const float* xcb = a.xh + (size_t)bg * cpad * N;
@@ -518,9 +469,7 @@ __global__ __launch_bounds__(256, KDW <= 16 ? 3 : 2) void knn_pf_kernel(KnnArgs 
       keys[sv * 64 + q] = d == d && d < INFINITY ? pack_key(d, m) : (double)INFINITY;   // NaN / +inf never enter a list
     }
   }
-  KNN_TL(26);
   __syncthreads();
-  KNN_TL(27);
   if (w != 0) return;
 
   // ---- wave 0: rank the survivors by their keys (a flagged tile writes nothing: the clean-up launch owns it)
@@ -549,7 +498,6 @@ __global__ __launch_bounds__(256, KDW <= 16 ? 3 : 2) void knn_pf_kernel(KnnArgs 
       }
     }
   }
-  KNN_TL(31);
 }
 
 }  // namespace gkg

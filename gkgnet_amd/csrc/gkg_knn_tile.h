@@ -64,7 +64,6 @@ __global__ __launch_bounds__(64 * NWV, (BF && HAS_RP) ? (KD <= 18 ? 3 : 2) : (KD
   // congruent mod 8 (same XCD) and adjacent in dispatch order: the keys are then fetched into one L2 once instead
   // of once per query tile (measured: FETCH_SIZE 53 -> see profiles/).  Placement only affects speed.
   const int lin = blockIdx.x;
-  KNN_TL(0);
   if (a.wg_flags && a.wg_flags[lin] == 0) return;   // clean-up pass behind knn_pf_kernel: only the tiles it flagged
   // the map (gkg_knn_common.h): problem-major, bias-major (pvig_m stage 1, bf16 form: 43.5 GB of relative_pos per launch from
   // the MALL -> 0.34 GB, against 5.4 GB of keys that now re-enter per query tile) or interleaved
@@ -193,9 +192,7 @@ __global__ __launch_bounds__(64 * NWV, (BF && HAS_RP) ? (KD <= 18 ? 3 : 2) : (KD
   // floats of the staged query tile (bf16 form: 64 rows of cp16 + 8 bf16), behind which the candidate buffer lives
   const size_t qfloats = BF ? (size_t)QT * (a.cp16 + 8) / 2 : (size_t)cpad * QT;
   if (BUF > 0) smem[qfloats + (size_t)BUF * 2 * TH + tid] = INFINITY;   // ths (see below)
-  KNN_TL(1);
   __syncthreads();
-  KNN_TL(2);
 
   const int n = lane_n;
   const float* sqy = a.sqy + (size_t)bg * M;
@@ -253,19 +250,6 @@ __global__ __launch_bounds__(64 * NWV, (BF && HAS_RP) ? (KD <= 18 ? 3 : 2) : (KD
     unsigned cw_now = cw;
     asm volatile("" : "+v"(cw_now));
     int bcnt = (int)((cw_now - cw0) / (TH * 8));
-#if defined(KNN_ABLATE) && KNN_ABLATE == 3
-    unsigned long long* gkg_knn_ablate_counters = reinterpret_cast<unsigned long long*>(a.part_v);
-    if (lane == 0) {                               // tools/ubench/knn_ablate.py: flushes, batches through the network
-      atomicAdd(&gkg_knn_ablate_counters[0], 1ull);
-      if (__builtin_amdgcn_ballot_w64(bcnt > 3) != 0ull) atomicAdd(&gkg_knn_ablate_counters[1], 1ull);
-    }
-    atomicAdd(&gkg_knn_ablate_counters[2], (unsigned long long)bcnt);
-    {
-      int mx = bcnt;
-      for (int m_ = 1; m_ < 64; m_ <<= 1) mx = max(mx, __shfl_xor(mx, m_, 64));
-      if (lane == 0) atomicAdd(&gkg_knn_ablate_counters[3], (unsigned long long)mx);
-    }
-#endif
     if constexpr (NET) {
       if (__builtin_amdgcn_ballot_w64(bcnt > 3) != 0ull) {
         double b[16];
@@ -295,13 +279,7 @@ __global__ __launch_bounds__(64 * NWV, (BF && HAS_RP) ? (KD <= 18 ? 3 : 2) : (KD
       refresh_shared();
       thr = fminf(thr, next_up(sh));               // strict '<' against own KD-th entry, '<=' against the shared bound
     }
-#if defined(KNN_ABLATE) && KNN_ABLATE == 1
-    thr = -INFINITY;                               // tools/ubench/knn_ablate.py: every candidate tested, none admitted after the first flush
-#endif
   };
-#if defined(KNN_ABLATE) && KNN_ABLATE == 2
-  float abl_sink = INFINITY;
-#endif
 
   const int ktiles = (M + KT - 1) / KT;
   const int t_end = min(t_begin + a.tiles_per_split, ktiles);
@@ -483,7 +461,6 @@ __global__ __launch_bounds__(64 * NWV, (BF && HAS_RP) ? (KD <= 18 ? 3 : 2) : (KD
         asm volatile("" : "=v"(acc1));
       }
     }
-    KNN_TL(3 + 2 * (iv / NWV));
     // next tile's relative_pos rows and |y|^2: in flight during this tile's selection phase (bf16 form; sy32 was copied)
     if (BF && iv + NWV < TV) fetch_side(t_next);
     // ---- lane l needs all 32 keys of ITS query: v_permlane32_swap exchanges the 32-lane halves of the two
@@ -520,28 +497,19 @@ __global__ __launch_bounds__(64 * NWV, (BF && HAS_RP) ? (KD <= 18 ? 3 : 2) : (KD
             if (HAS_RP) dist = dist + rp[row];
           }
           if (BUF > 0) {
-#if defined(KNN_ABLATE) && KNN_ABLATE == 2
-            abl_sink = fminf(abl_sink, dist);       // tools/ubench/knn_ablate.py: the contraction + distance adds alone
-#else
             if (HAS_RP ? dist <= thr : dist < thr) { // NaN fails; '<=' where the tiles are not visited in index order
               *(lds_v2u_t*)(size_t)cw = v2u_t{__float_as_uint(dist), (unsigned)(m0 + row)};
               // in place, behind the store (left to the compiler the add lands in a temporary in front of it, plus a copy back)
               asm volatile("v_add_u32_e32 %0, %1, %0" : "+v"(cw) : "i"(TH * 8) : "memory");
             }
-#endif
           } else {
             top.template insert<GUARD>(dist, m0 + row);
           }
         }
       }
       // room for the next 8 candidates?  (the stream's last group flushes unconditionally)
-#if defined(KNN_ABLATE) && KNN_ABLATE == 2
-      if (BUF > 0 && g == 3 && iv + NWV >= TV) { top.template insert<false>(abl_sink, 0); }
-#else
       if (BUF > 0 && ((g == 3 && iv + NWV >= TV) || __builtin_amdgcn_ballot_w64(cw > cw_lim) != 0ull)) flush();
-#endif
     }
-    KNN_TL(4 + 2 * (iv / NWV));
   }
 
   const int kd = a.kd;
@@ -575,7 +543,6 @@ __global__ __launch_bounds__(64 * NWV, (BF && HAS_RP) ? (KD <= 18 ? 3 : 2) : (KD
         }
       }
     }
-    KNN_TL(31);
     return;
   }
   // ---- merge the per-wave lists of each query: EVERY wave ranks its own entries among all lists (rank = own position +
@@ -586,9 +553,7 @@ __global__ __launch_bounds__(64 * NWV, (BF && HAS_RP) ? (KD <= 18 ? 3 : 2) : (KD
   //      trips per rank) after the other waves had exited: 19 k of a cfg2 workgroup's 87 k cycles; this form takes 5 k, for
   //      any number of waves.  The launch time at cfg2 did not move (the CU's other two workgroups filled the idle SIMDs:
   //      tools/ubench/knn_timeline.py, profiles/r04_knn_timeline.txt).
-  KNN_TL(28);
   __syncthreads();                       // everyone is done with xs / dmat
-  KNN_TL(29);
   double* lk = reinterpret_cast<double*>(smem);      // [NWV][KD][64]
 #pragma unroll
   for (int j = 0; j < KD; ++j) lk[(w * KD + j) * 64 + lane] = top.key[j];
@@ -597,7 +562,6 @@ __global__ __launch_bounds__(64 * NWV, (BF && HAS_RP) ? (KD <= 18 ? 3 : 2) : (KD
     for (int i = tid; i < a.k * 64; i += TH) nbr[i] = 0;               // ranks no finite candidate claims (non-finite inputs)
   }
   __syncthreads();
-  KNN_TL(30);
   const int dil = a.dilation;
   const unsigned magic = dil > 1 ? 0xffffffffu / (unsigned)dil + 1u : 0u;      // r / dil for r < 2^16 (r <= KD * NWV)
   constexpr int JC = 9;                  // own entries ranked per pass (bounds the registers the ranks take next to the list)
@@ -741,7 +705,6 @@ __global__ __launch_bounds__(64 * NWV, (BF && HAS_RP) ? (KD <= 18 ? 3 : 2) : (KD
     if (KD <= 9 || k <= 9) pass(std::integral_constant<int, 9>{});          // a 9-entry list holds k <= 9 neighbours
     else if constexpr (KD > 9) pass(std::integral_constant<int, 18>{});
   }
-  KNN_TL(31);
 }
 
 constexpr int KNN_BUF = 16;        // buffered selection: entries per lane (8 bytes each: 32 KB per workgroup)

@@ -16,23 +16,6 @@
 
 #include "gkg_common.h"
 
-// measurement builds only (tools/ubench/mr_fwd_ablate.py).  MR_ABL bits: 1 gathers from 4 fixed rows, 2 synthetic indices (no
-// index loads), 4 no out stores, 8 no argmax stores.  MR_TL: wave-level s_memtime stamps of every 1009th workgroup, written
-// behind the argmax tensor (the tool allocates the room).
-#ifndef MR_ABL
-#define MR_ABL 0
-#endif
-#ifdef MR_TL
-#define MR_STAMP(p)                                                                                                     \
-  do {                                                                                                                  \
-    if ((threadIdx.x & 63) == 0 && blockIdx.x % 1009 == 0 && blockIdx.x / 1009 < 512)                                   \
-      reinterpret_cast<unsigned long long*>(argmax + 2 * T * C)[((blockIdx.x / 1009) * 4 + (threadIdx.x >> 6)) * 8 + (p)] = \
-          __builtin_readcyclecounter();                                                                                 \
-  } while (0)
-#else
-#define MR_STAMP(p) do {} while (0)
-#endif
-
 namespace gkg {
 
 constexpr int MR_LDS_BUDGET = 96 * 1024;   // bytes of LDS for source rows / accumulators
@@ -280,7 +263,6 @@ __global__ __launch_bounds__(256) void mr_fwd_tm_kernel(const float* __restrict_
   const float* xb = x + t * (size_t)ldx + xm_col(ch, xchunk);
   float4 xi[QP], best[QP];
   int ai[QP][4];                                                  // winner per channel: neighbour slot j (AK == 0) / row index (AK == 1)
-  MR_STAMP(0);
 #pragma unroll
   for (int q = 0; q < QP; ++q) xi[q] = *reinterpret_cast<const float4*>(xb + 4 * q);
   // `takes` (first maximum wins, a NaN is the maximum and sticks) costs 3 compares + 2 scalar mask operations + exec-masked
@@ -318,26 +300,12 @@ __global__ __launch_bounds__(256) void mr_fwd_tm_kernel(const float* __restrict_
   if (KS > 0) {
     int id[KS > 0 ? KS : 1];
 #pragma unroll
-#if MR_ABL & 2
-    for (int j = 0; j < KS; ++j) id[j] = (int)(((unsigned)n * 7u + (unsigned)j * 131u) % (unsigned)M);
-#else
     for (int j = 0; j < KS; ++j) id[j] = clamp_idx(ip[j], M);
-#endif
 #pragma unroll
     for (int q = 0; q < QP; ++q) {
       float4 v[KS > 0 ? KS : 1];
 #pragma unroll
-#if MR_ABL & 1
-      for (int j = 0; j < KS; ++j) v[j] = *reinterpret_cast<const float4*>(sb + (size_t)(id[j] & 3) * lds_ + 4 * q);
-#else
       for (int j = 0; j < KS; ++j) v[j] = *reinterpret_cast<const float4*>(sb + (size_t)id[j] * lds_ + 4 * q);
-#endif
-#ifdef MR_TL
-      if (v[0].x == 1.25e-33f || id[8] == -7) MR_STAMP(7);      // (forces the index loads to have arrived)
-      MR_STAMP(1);
-      if (v[8].y == 1.25e-33f && v[3].z == 1.5e-33f) MR_STAMP(7);
-      MR_STAMP(2);
-#endif
       const float chk = chain(std::false_type{}, q, v, id, KS);
       if (__builtin_amdgcn_ballot_w64(chk != chk) != 0ull) (void)chain(std::true_type{}, q, v, id, KS);
     }
@@ -361,13 +329,12 @@ __global__ __launch_bounds__(256) void mr_fwd_tm_kernel(const float* __restrict_
 #pragma unroll
   for (int q = 0; q < QP; ++q) {
     const int chq = ch + 4 * q;
-    if (argmax && (!(MR_ABL & 8) || best[q].x == 1.2345e-30f)) {
+    if (argmax) {
       if (AK == 1) *reinterpret_cast<uint2*>(argmax + 2 * (t * C + chq)) =
           make_uint2((uint32_t)ai[q][0] | ((uint32_t)ai[q][1] << 16), (uint32_t)ai[q][2] | ((uint32_t)ai[q][3] << 16));
       else *reinterpret_cast<uint32_t*>(argmax + t * C + chq) =
           (uint32_t)ai[q][0] | ((uint32_t)ai[q][1] << 8) | ((uint32_t)ai[q][2] << 16) | ((uint32_t)ai[q][3] << 24);
     }
-    if ((MR_ABL & 4) && best[q].y != 1.2345e-30f) continue;
     if (mode == 0) {
       stf4(out + t * C + chq, best[q]);
     } else {
@@ -377,11 +344,6 @@ __global__ __launch_bounds__(256) void mr_fwd_tm_kernel(const float* __restrict_
       stf4(o + Cq, best[q]);
     }
   }
-#ifdef MR_TL
-  MR_STAMP(3);
-  __builtin_amdgcn_s_waitcnt(0);                                 // stores acknowledged
-  MR_STAMP(4);
-#endif
 }
 
 // Backward, pass 1: gx[t][ch] = direct[t][ch] - gm[t][ch]   (mode 1: direct / gm are the x / m chunks of dXM)

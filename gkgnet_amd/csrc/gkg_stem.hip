@@ -10,10 +10,6 @@
 // output, which is what the next (library) convolution and the blocks' token-major kernels want — go out as 16-byte stores.
 #include "gkg_common.h"
 
-#ifndef STEM_ABL
-#define STEM_ABL 0     // measurement builds only (tools/ubench/stem_ablate.py): 1 no loads, 2 no stores, 4 one FMA group per tap
-#endif
-
 namespace gkg {
 
 typedef float st_f2 __attribute__((ext_vector_type(2)));
@@ -59,18 +55,14 @@ __global__ __launch_bounds__(256, 2) void stem_conv3x3s2_kernel(const float* __r
 #pragma unroll
     for (int j = 0; j < NC; ++j) {
       const int wi = wi0 + j;
-#if STEM_ABL & 1
-      col[j] = (float)(wi + cr);
-#else
       col[j] = (rowok && wi >= 0 && wi < W) ? xr[wi] : 0.f;
-#endif
     }
     if (++dy == 3) { dy = 0; ++c; }
 #pragma unroll
     for (int dx = 0; dx < 3; ++dx) {
       const float4* wt = reinterpret_cast<const float4*>(wl + (cr * 3 + dx) * COUT);
 #pragma unroll
-      for (int k = 0; k < ((STEM_ABL & 4) ? 1 : COUT / 4); ++k) {
+      for (int k = 0; k < COUT / 4; ++k) {
         const float4 w4 = wt[k];
         const st_f2 w01 = st_f2{w4.x, w4.y}, w23 = st_f2{w4.z, w4.w};
 #pragma unroll
@@ -97,11 +89,7 @@ __global__ __launch_bounds__(256, 2) void stem_conv3x3s2_kernel(const float* __r
           r.z = __builtin_fmaf(a[4 * k + 2], r.z, cs[4 * k + 2]); r.w = __builtin_fmaf(a[4 * k + 3], r.w, cs[4 * k + 3]);
         }
         if (act == 1) { r.x = gelu_f(r.x); r.y = gelu_f(r.y); r.z = gelu_f(r.z); r.w = gelu_f(r.w); }
-#if STEM_ABL & 2
-        if (r.x == 1.2345e-30f) stf4(o + 4 * k, r);
-#else
         stf4(o + 4 * k, r);
-#endif
       }
     }
   }
