@@ -85,7 +85,8 @@ EXPORTS = ("gkg_version", "gkg_last_error_string", "gkg_knn_workspace_bytes", "g
            "gkg_knn_mr_fused_supported", "gkg_knn_mr_fwd_tm", "gkg_x6_prep_weights_zero",
            "gkg_knn_fwd_tm16", "gkg_mr_fwd_tm16", "gkg_mr_linear_bf16_nn16",
            "gkg_grapher_fwd", "gkg_grapher_bwd", "gkg_grapher_label_fwd", "gkg_grapher_label_bwd",
-           "gkg_gconv_workspace_bytes", "gkg_gin_fwd", "gkg_gin_bwd", "gkg_gat_fwd", "gkg_gat_bwd")
+           "gkg_gconv_workspace_bytes", "gkg_gin_fwd", "gkg_gin_bwd", "gkg_gat_fwd", "gkg_gat_bwd",
+           "gkg_bn_eval_bwd")
 PROF_KERNELS = ("token_prep", "knn_tile", "knn_merge", "mr_fwd", "mr_bwd", "gemm_x6")
 
 _lib = None
@@ -170,6 +171,8 @@ def load():
     lib.gkg_bn_bwd_atomic.argtypes = [V] * 9 + [I, I, I, I, Z, I, V, V, Z, V]
     lib.gkg_bn_bwd_atomic_scaled.restype = I
     lib.gkg_bn_bwd_atomic_scaled.argtypes = [V] * 9 + [I, I, I, I, Z, I, V, V, Z, V, I, V]
+    lib.gkg_bn_eval_bwd.restype = I
+    lib.gkg_bn_eval_bwd.argtypes = [V] * 5 + [I, I, I, I, Z, I, V, I, V, V, V, F, V, V, V, V, V, Z, V, Z, V]
     lib.gkg_bn_bwd_apply_from_sums.restype = I
     lib.gkg_bn_bwd_apply_from_sums.argtypes = [V] * 9 + [I, I, I, I, Z, I, V, V, Z, V]
     lib.gkg_linear_dgrad_x6_bnbwd.restype = I

@@ -133,9 +133,10 @@ class GKGNet(nn.Module):
 
     def __init__(self, choice="s", k=9, k_label_gcn=9, use_multi_group=True, backbone_multi_group=True, num_group=2,
                  drop_path=0.0, n_classes=1000, out_indices=(3,), size=576, num_gcn=1, pretrain_path=None,
-                 init_cfg=None):
+                 init_cfg=None, norm_eval=False):
         super().__init__()
         self.init_cfg = init_cfg
+        self.norm_eval = bool(norm_eval)          # mmcls convention: BatchNorm layers stay in eval mode while the model trains
         opt = self.arch_settings[choice]
         act, norm, bias = opt["act"], opt["norm"], opt["bias"]
         epsilon, stochastic, conv = opt["epsilon"], opt["use_stochastic"], opt["conv"]
@@ -196,6 +197,15 @@ class GKGNet(nn.Module):
         """Checkpoint loading is left to the caller (mmcv's ``init_cfg=dict(type='Pretrained', ...)`` or
         ``load_state_dict``); keys match the reference's."""
         return None
+
+    def train(self, mode: bool = True):
+        """``norm_eval``: every BatchNorm is put back in eval mode (running statistics, no update) after the switch."""
+        super().train(mode)
+        if mode and self.norm_eval:
+            for m in self.modules():
+                if isinstance(m, nn.modules.batchnorm._BatchNorm):
+                    m.eval()
+        return self
 
     def forward(self, inputs):
         # (B, n_classes, C1) label queries: label_input is arange(n_classes), so the embedding lookup of the reference

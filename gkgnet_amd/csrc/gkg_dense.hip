@@ -577,6 +577,130 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* dout, co
   }
 }
 
+// ------------------------------------------------------------------------------------------ eval-mode BN backward
+// out = act(a*y + c) with (a, c) folded from the RUNNING statistics (bn_eval_affine_kernel): no batch statistic stands between
+// dout and dy, so ONE sweep does what the train-mode backward needs a statistics and an apply pass for:
+//   dz = dout * row_scale[row / rows_per_scale] * act'(a*y + c),   dy = a * dz
+// and, with SUMS, the two column sums the parameter gradients are made of:  S0 = sum dz,  S1 = sum dz * y.  Same decomposition
+// as bn_bwd_stats_kernel (row chunk x 64-channel tile x nb).  The sums are carried in fp64 from the first addition on (a lane's
+// run is up to rows_per_block / 16 terms and S1 + (bias - rm) * S0 cancels when the running mean is close to the batch's),
+// reduced over the workgroup's 16 row lanes through LDS and then either added to `asums` with fp64 atomics or written, rounded
+// to fp32, as this workgroup's partial row of `part` (deterministic form: bn_eval_bwd_finish_kernel adds the partials in a
+// fixed order).  SUMS == false: a pure elementwise pass over the flat matrix, no LDS, no atomics; dy has the same bits either way.
+template <int ACT, bool SUMS>
+__global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const float* dout, const float* __restrict__ y,
+                                                          const float* __restrict__ a, const float* __restrict__ cs, float* dy,
+                                                          float* __restrict__ part, double* __restrict__ asums, int R, int C,
+                                                          int rows_per_block, int ldg, size_t g_bstride,
+                                                          const float* __restrict__ row_scale, int rows_per_scale) {
+  __shared__ double red[SUMS ? 2 : 1][SUMS ? ST_RL : 1][SUMS ? 4 * ST_CG : 1];
+  const int tid = threadIdx.x;
+  const int cg = tid & (ST_CG - 1), rl = tid >> 4;
+  const int cgi = blockIdx.y * ST_CG + cg;
+  const int q = blockIdx.z;
+  y += (size_t)q * R * C; dy += (size_t)q * R * C; dout += (size_t)q * g_bstride;
+  a += (size_t)q * C; cs += (size_t)q * C;
+  const int r0 = blockIdx.x * rows_per_block;
+  const int r1 = min(R, r0 + rows_per_block);
+  if (!SUMS) {
+    // no reduction -> no reason for the column-tile decomposition (at C = 80 its second tile keeps 4 of 16 column groups busy):
+    // the workgroups of one q walk the matrix as a flat list of float4, fully coalesced
+    const int C4 = C >> 2;
+    const size_t total4 = (size_t)R * C4;
+    const size_t nthreads = (size_t)gridDim.x * gridDim.y * 256;
+    for (size_t i = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 256 + tid; i < total4; i += nthreads) {
+      const size_t r = i / C4;
+      const int g4 = (int)(i - r * C4);
+      const float4 g = *reinterpret_cast<const float4*>(dout + r * (size_t)ldg + 4 * g4);
+      const float4 v = *reinterpret_cast<const float4*>(y + 4 * i);
+      const float4 a4 = *reinterpret_cast<const float4*>(a + 4 * g4);
+      const float4 c4 = *reinterpret_cast<const float4*>(cs + 4 * g4);
+      float4 dz = g;
+      if (row_scale) {
+        const float sc = row_scale[r / (size_t)rows_per_scale];
+        dz.x *= sc; dz.y *= sc; dz.z *= sc; dz.w *= sc;
+      }
+      if (ACT == 1) {
+        dz.x *= gelu_grad_f(__builtin_fmaf(a4.x, v.x, c4.x)); dz.y *= gelu_grad_f(__builtin_fmaf(a4.y, v.y, c4.y));
+        dz.z *= gelu_grad_f(__builtin_fmaf(a4.z, v.z, c4.z)); dz.w *= gelu_grad_f(__builtin_fmaf(a4.w, v.w, c4.w));
+      }
+      *reinterpret_cast<float4*>(dy + 4 * i) = make_float4(a4.x * dz.x, a4.y * dz.y, a4.z * dz.z, a4.w * dz.w);
+    }
+    return;
+  }
+  double s[4] = {0.0, 0.0, 0.0, 0.0}, sq[4] = {0.0, 0.0, 0.0, 0.0};
+  if (cgi < (C >> 2)) {
+    const float4 a4 = *reinterpret_cast<const float4*>(a + 4 * cgi);
+    const float4 c4 = *reinterpret_cast<const float4*>(cs + 4 * cgi);
+#pragma unroll 4
+    for (int r = r0 + rl; r < r1; r += ST_RL) {
+      const float4 g = *reinterpret_cast<const float4*>(dout + (size_t)r * ldg + 4 * cgi);
+      const float4 v = *reinterpret_cast<const float4*>(y + (size_t)r * C + 4 * cgi);
+      float4 dz = g;
+      if (row_scale) {                                // DropPath: the branch output was scaled per image, so is its gradient
+        const float sc = row_scale[r / rows_per_scale];
+        dz.x *= sc; dz.y *= sc; dz.z *= sc; dz.w *= sc;
+      }
+      if (ACT == 1) {
+        dz.x *= gelu_grad_f(__builtin_fmaf(a4.x, v.x, c4.x)); dz.y *= gelu_grad_f(__builtin_fmaf(a4.y, v.y, c4.y));
+        dz.z *= gelu_grad_f(__builtin_fmaf(a4.z, v.z, c4.z)); dz.w *= gelu_grad_f(__builtin_fmaf(a4.w, v.w, c4.w));
+      }
+      *reinterpret_cast<float4*>(dy + (size_t)r * C + 4 * cgi) = make_float4(a4.x * dz.x, a4.y * dz.y, a4.z * dz.z, a4.w * dz.w);
+      s[0] += (double)dz.x; s[1] += (double)dz.y; s[2] += (double)dz.z; s[3] += (double)dz.w;
+      sq[0] += (double)dz.x * (double)v.x; sq[1] += (double)dz.y * (double)v.y;
+      sq[2] += (double)dz.z * (double)v.z; sq[3] += (double)dz.w * (double)v.w;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { red[0][rl][4 * cg + j] = s[j]; red[1][rl][4 * cg + j] = sq[j]; }
+  __syncthreads();
+  if (tid < 8 * ST_CG) {
+    const int which = tid >> 6, col = tid & 63;
+    double acc = 0.0;
+#pragma unroll
+    for (int l = 0; l < ST_RL; ++l) acc += red[which][l][col];
+    const int ch = blockIdx.y * 4 * ST_CG + col;
+    if (ch < C) {
+      if (asums) __hip_atomic_fetch_add(asums + ((size_t)q * 2 + which) * C + ch, acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      else part[(((size_t)q * gridDim.x + blockIdx.x) * 2 + which) * C + ch] = (float)acc;
+    }
+  }
+}
+
+// The parameter gradients of the eval-mode BN from S0 = sum dz, S1 = sum dz*y (y EXCLUDES the conv bias):
+//   dbeta = S0,  dgamma = (S1 + (bias - rm) * S0) / sqrt(rv + eps),  dbias(conv) = a * S0      (each optional)
+// The sums come from `dsums` (fp64 atomics of the sweep) or, when that is NULL, from the fixed-order fp64 sum of the sweep's
+// `nblk` partial rows (deterministic form).  Also clears `zero_buf` (the OTHER scratch buffer, see gkg_bn_bwd_atomic).
+__global__ __launch_bounds__(256) void bn_eval_bwd_finish_kernel(const double* __restrict__ dsums, const float* __restrict__ part,
+                                                                 int nblk, const float* __restrict__ a,
+                                                                 const float* __restrict__ running_mean,
+                                                                 const float* __restrict__ running_var,
+                                                                 const float* __restrict__ bias, float eps, int C,
+                                                                 float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                                 float* __restrict__ dbias, double* __restrict__ zero_buf,
+                                                                 size_t zero_doubles) {
+  const int q = blockIdx.y;
+  if (blockIdx.x == 0 && q == 0)
+    for (size_t i = threadIdx.x; i < zero_doubles; i += 256) zero_buf[i] = 0.0;
+  const int ch = blockIdx.x * 256 + threadIdx.x;
+  if (ch >= C) return;
+  double S0 = 0.0, S1 = 0.0;
+  if (dsums) {
+    S0 = dsums[(size_t)q * 2 * C + ch];
+    S1 = dsums[(size_t)q * 2 * C + C + ch];
+  } else {
+    const float* p = part + (size_t)q * nblk * 2 * C + ch;
+    for (int b = 0; b < nblk; ++b) { S0 += (double)p[(size_t)b * 2 * C]; S1 += (double)p[(size_t)b * 2 * C + C]; }
+  }
+  const size_t o = (size_t)q * C + ch;
+  if (dbeta) dbeta[o] = (float)S0;
+  if (dgamma) {
+    const double sh = (bias ? (double)bias[o] : 0.0) - (double)running_mean[o];
+    dgamma[o] = (float)((S1 + sh * S0) / sqrt((double)running_var[o] + (double)eps));
+  }
+  if (dbias) dbias[o] = (float)((double)a[o] * S0);
+}
+
 }  // namespace gkg
 
 using namespace gkg;
@@ -836,6 +960,45 @@ extern "C" int gkg_bn_bwd_apply_from_sums(const float* dout, const float* y, con
     return gkg_fail(GKG_ERR_SHAPE, "gkg_bn_bwd_apply_from_sums: bad sizes");
   return bn_bwd_atomic_impl(dout, y, a, c, mean, invstd, dy, dgamma, dbeta, R, C, nb, ldg, dout_bstride, act,
                             const_cast<double*>(sums), zero_buf, zero_doubles, stream, false);
+}
+
+// Backward of out = act(BN_eval(y)) (running statistics; (a, c) from gkg_bn_eval_affine): dy in ONE sweep, plus — only when at
+// least one of dgamma / dbeta / dbias is asked for — the column sums and a small finishing launch.  `sums` != NULL: the sweep
+// adds to it with fp64 atomics (2 * nb * C doubles, ZERO on entry) and the finishing launch clears `zero_buf` (the protocol of
+// gkg_bn_bwd_atomic); `sums` == NULL: the two-stage deterministic form through `workspace` (gkg_bn_workspace_bytes).
+extern "C" int gkg_bn_eval_bwd(const float* dout, const float* y, const float* a, const float* c, float* dy, int R, int C, int nb,
+                               int ldg, size_t dout_bstride, int act, const float* row_scale, int rows_per_scale,
+                               const float* running_mean, const float* running_var, const float* bias, float eps, float* dgamma,
+                               float* dbeta, float* dbias, double* sums, double* zero_buf, size_t zero_doubles, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+  if (!dout || !y || !a || !c || !dy) return gkg_fail(GKG_ERR_NULL, "gkg_bn_eval_bwd: null pointer");
+  if (R <= 0 || bad_c(C) || nb <= 0 || nb > 64 || ldg < C || (ldg & 3) || (dout_bstride & 3) || (act != 0 && act != 1) ||
+      (zero_doubles && !zero_buf) || (row_scale && rows_per_scale <= 0))
+    return gkg_fail(GKG_ERR_SHAPE, "gkg_bn_eval_bwd: bad sizes");
+  const bool want = dgamma || dbeta || dbias;
+  if (dgamma && (!running_mean || !running_var)) return gkg_fail(GKG_ERR_NULL, "gkg_bn_eval_bwd: dgamma needs the running statistics");
+  if (!want && (sums || zero_doubles)) return gkg_fail(GKG_ERR_SHAPE, "gkg_bn_eval_bwd: scratch given but no parameter gradient asked for");
+  int rpb;
+  const int nblk = stats_blocks(R, C, nb, &rpb);
+  float* part = nullptr;
+  if (want && !sums) {
+    if (!workspace) return gkg_fail(GKG_ERR_NULL, "gkg_bn_eval_bwd: neither sums nor workspace");
+    if (workspace_bytes < (size_t)nb * nblk * 2 * C * sizeof(float)) return gkg_fail(GKG_ERR_WORKSPACE, "gkg_bn_eval_bwd: workspace too small");
+    if (zero_doubles) return gkg_fail(GKG_ERR_SHAPE, "gkg_bn_eval_bwd: zero_buf belongs to the atomic form");
+    part = (float*)workspace;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(nblk, stats_tiles(C), nb);
+#define GKG_EVAL_BWD(ACT, SUMS) hipLaunchKernelGGL((bn_eval_bwd_kernel<ACT, SUMS>), grid, dim3(256), 0, st, dout, y, a, c, dy, part, sums, \
+                                                   R, C, rpb, ldg, dout_bstride, row_scale, rows_per_scale)
+  if (want) { if (act == 1) GKG_EVAL_BWD(1, true); else GKG_EVAL_BWD(0, true); }
+  else { if (act == 1) GKG_EVAL_BWD(1, false); else GKG_EVAL_BWD(0, false); }
+#undef GKG_EVAL_BWD
+  if (want)
+    hipLaunchKernelGGL(bn_eval_bwd_finish_kernel, dim3((C + 255) / 256, nb), dim3(256), 0, st, (const double*)sums, (const float*)part, nblk,
+                       a, running_mean, running_var, bias, eps, C, dgamma, dbeta, dbias, zero_buf, zero_doubles);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : gkg_fail_hip(e, "bn_eval_bwd");
 }
 
 

@@ -792,6 +792,31 @@ def _bn_backward(lib, g, Y, a, c, mean, invstd, dY, dgamma, dbeta, R, C, nb, ldg
                "gkg_bn_bwd_apply")
 
 
+def _bn_eval_backward(lib, g, Y, a, c, dY, bn, bias, dgamma, dbeta, dbias, R, C, nb, ldg, g_bstride, act, row_scale=None,
+                      rows_per_scale=0):
+    """dY of out = act(BN_eval(Y)) (running statistics: a frozen BN, or a module in eval() with gradients) in ONE sweep
+    (gkg_bn_eval_bwd); ``dgamma`` / ``dbeta`` / ``dbias``: output tensors for the gradients that are wanted (None: not wanted) —
+    with any of them the sweep also takes the two column sums (fp64 atomics into the alternating scratch pair, or the two-stage
+    workspace form under DETERMINISTIC) and a small second launch finishes them; with none (a fully frozen affine) the pass is
+    purely elementwise.  ``dbias`` is the gradient of the conv bias in front of the BN: real here, exactly zero in train mode."""
+    rs, rps = (_ptr(row_scale), rows_per_scale) if row_scale is not None else (None, 0)
+    tail = (_ptr(bn.running_mean), _ptr(bn.running_var), _ptr(bias), float(bn.eps), _ptr(dgamma), _ptr(dbeta), _ptr(dbias))
+    head = (_ptr(g), _ptr(Y), _ptr(a), _ptr(c), _ptr(dY), R, C, nb, ldg, g_bstride, act, rs, rps)
+    if dgamma is None and dbeta is None and dbias is None:
+        _lib.check(lib.gkg_bn_eval_bwd(*head, *tail, None, None, 0, None, 0, _stream()), "gkg_bn_eval_bwd")
+    elif not DETERMINISTIC and 2 * nb * C <= _BnBwdScratch.DOUBLES:
+        scratch = _BnBwdScratch.of(Y.device)
+        cur, other, zero = scratch.acquire(lib, 2 * nb * C)
+        try:
+            _lib.check(lib.gkg_bn_eval_bwd(*head, *tail, _ptr(cur), _ptr(other), zero, None, 0, _stream()), "gkg_bn_eval_bwd")
+        except Exception:
+            scratch.poison()
+            raise
+    else:
+        ws = _ws(lib.gkg_bn_workspace_bytes(R, C, nb), Y.device)
+        _lib.check(lib.gkg_bn_eval_bwd(*head, *tail, None, None, 0, _ptr(ws), ws.numel(), _stream()), "gkg_bn_eval_bwd")
+
+
 class _LinearBNAct(torch.autograd.Function):
     """out = act(BN(x @ W^T + b)) (+ residual), token-major.  ``nchw``: write the result (and read the
     residual) in (B, C, N) layout — the block's last layer."""
@@ -871,6 +896,7 @@ class _LinearBNAct(torch.autograd.Function):
             _lib.check(lib.gkg_tm_affine_to_nchw(_ptr(Y), _ptr(a), _ptr(c), _ptr(res), _ptr(out), nchw[0], cout,
                                                  R // nchw[0], _ptr(scale), _stream()), "gkg_tm_affine_to_nchw")
         ctx.save_for_backward(x, weight, Y, a, c, mean, invstd)
+        ctx.bn_eval = (bn, bias) if mean is None else None       # eval-mode BN: the backward reads the running statistics
         ctx.dual = dual
         ctx.meta = (act, nchw, residual is not None, bias is not None)
         ctx.scale = (scale, rows_per_scale)
@@ -930,21 +956,28 @@ class _LinearBNAct(torch.autograd.Function):
             dout_c = dout.contiguous()           # named: the copy must outlive the launch that reads it
             _lib.check(lib.gkg_nchw_to_tm(_ptr(dout_c), _ptr(g), nchw[0], cout, R // nchw[0], _lib.F32,
                                           _ptr(ctx.scale[0]), _stream()), "gkg_nchw_to_tm")      # DropPath: g * mask / keep
-        elif ctx.scale[0] is not None and _bn_scale_in_kernel(ctx.sync, 1, cout) and (ctx.link is None or ctx.link.ready is None):
+        elif (ctx.scale[0] is not None and (mean is None or _bn_scale_in_kernel(ctx.sync, 1, cout))
+              and (ctx.link is None or ctx.link.ready is None)):
             g = dout.contiguous()                # DropPath: the BN-backward kernels scale the gradient per image themselves
             row_scale = (ctx.scale[0].contiguous().float(), ctx.scale[1])
         elif ctx.scale[0] is not None:
             g = (dout.view(-1, ctx.scale[1], cout) * ctx.scale[0].view(-1, 1, 1)).view(R, cout)
         else:
             g = dout.contiguous()                # (an xm output's gradient arrives (B, N, 4, cout / 4): the same memory as (R, cout))
-        if mean is None:
-            raise _lib.GkgError("backward through eval-mode BN is only supported on the composable path")
         # a conv bias in front of train-mode BN has exactly zero gradient (BN removes the mean): not materialised
         dbias = None
         dY = torch.empty_like(Y)
         dWv, dgamma, dbeta = _grad_outs(ctx.gparams, (cout, cin), cout, Y.device)
-        _bn_backward(lib, g, Y, a, c, mean, invstd, dY, dgamma, dbeta, R, cout, 1, cout, 0, act, ctx.sync, ctx.link,
-                     *(row_scale if row_scale is not None else (None, 0)))
+        if mean is None:                         # eval-mode BN (running statistics): one sweep, and the conv bias HAS a gradient
+            bn, bias = ctx.bn_eval
+            dgamma, dbeta = (dgamma if ctx.needs_input_grad[3] else None), (dbeta if ctx.needs_input_grad[4] else None)
+            if has_bias and ctx.needs_input_grad[2]:
+                dbias = torch.empty(cout, dtype=_F32, device=Y.device)
+            _bn_eval_backward(lib, g, Y, a, c, dY, bn, bias, dgamma, dbeta, dbias, R, cout, 1, cout, 0, act,
+                              *(row_scale if row_scale is not None else (None, 0)))
+        else:
+            _bn_backward(lib, g, Y, a, c, mean, invstd, dY, dgamma, dbeta, R, cout, 1, cout, 0, act, ctx.sync, ctx.link,
+                         *(row_scale if row_scale is not None else (None, 0)))
         W = weight.view(cout, cin)
         if not ctx.needs_input_grad[0]:
             dx = None
@@ -1011,6 +1044,7 @@ class _GroupedLinearBNAct(torch.autograd.Function):
             _lib.check(lib.gkg_affine_act(_ptr(Y), _ptr(a), _ptr(c), None, _ptr(out), R, co, nb, cout, co, 0, act,
                                           code, None, 0, _stream()), "gkg_affine_act")
         ctx.save_for_backward(XM, weight, Y, a, c, mean, invstd)
+        ctx.bn_eval = (bn, bias) if mean is None else None
         ctx.meta = (act, bias is not None)
         ctx.gparams = (weight, gamma, beta)
         ctx.sync = sync
@@ -1028,11 +1062,17 @@ class _GroupedLinearBNAct(torch.autograd.Function):
         cout = weight.shape[0]
         co = cout // nb
         g = dout.contiguous()
-        if mean is None:
-            raise _lib.GkgError("backward through eval-mode BN is only supported on the composable path")
+        dbias = None                                                # train-mode BN: == 0 exactly (see _LinearBNAct)
         dY = torch.empty_like(Y)
         dWv, dgamma, dbeta = _grad_outs(ctx.gparams, (nb, co, ci), cout, Y.device)
-        _bn_backward(lib, g, Y, a, c, mean, invstd, dY, dgamma, dbeta, R, co, nb, cout, co, act, ctx.sync, ctx.link)
+        if mean is None:                                            # eval-mode BN: see _LinearBNAct.backward
+            bn, bias = ctx.bn_eval
+            dgamma, dbeta = (dgamma if ctx.needs_input_grad[3] else None), (dbeta if ctx.needs_input_grad[4] else None)
+            if has_bias and ctx.needs_input_grad[2]:
+                dbias = torch.empty(cout, dtype=_F32, device=Y.device)
+            _bn_eval_backward(lib, g, Y, a, c, dY, bn, bias, dgamma, dbeta, dbias, R, co, nb, cout, co, act)
+        else:
+            _bn_backward(lib, g, Y, a, c, mean, invstd, dY, dgamma, dbeta, R, co, nb, cout, co, act, ctx.sync, ctx.link)
         Wg = weight.view(nb, co, ci)
         if not ctx.needs_input_grad[0]:
             dXM = None
@@ -1042,7 +1082,7 @@ class _GroupedLinearBNAct(torch.autograd.Function):
         else:
             dXM = torch.bmm(dY, _kperm_weight(Wg)).permute(1, 0, 2).reshape(R, nb * ci)
         dW = _wgrad_grouped(dY, XM.view(R, nb, ci).permute(1, 0, 2), dWv, kperm=1).view_as(weight)
-        return dXM, dW, None, dgamma, dbeta, None, None, None, None      # dbias == 0 exactly (see _LinearBNAct)
+        return dXM, dW, dbias, dgamma, dbeta, None, None, None, None
 
 
 # ----------------------------------------------------------------------------------------------- BN (+ act) behind a library conv
@@ -1066,14 +1106,13 @@ class _BNActTM(torch.autograd.Function):
                    "gkg_affine_act")
         ctx.save_for_backward(Y, a, c, mean, invstd)
         ctx.act, ctx.sync, ctx.gparams = act, sync, (gamma, beta)
+        ctx.bn_eval = bn if mean is None else None
         return out
 
     @staticmethod
     def backward(ctx, dout):
         lib = _lib.load()
         Y, a, c, mean, invstd = ctx.saved_tensors
-        if mean is None:
-            raise _lib.GkgError("backward through eval-mode BN is only supported on the composable path")
         R, C = Y.shape
         g = dout.contiguous()
         dY = torch.empty_like(Y)
@@ -1084,21 +1123,23 @@ class _BNActTM(torch.autograd.Function):
             dgamma = torch.empty(C, dtype=_F32, device=Y.device)
         if dbeta is None:
             dbeta = torch.empty(C, dtype=_F32, device=Y.device)
-        _bn_backward(lib, g, Y, a, c, mean, invstd, dY, dgamma, dbeta, R, C, 1, C, 0, ctx.act, ctx.sync)
+        if mean is None:                         # eval-mode BN: one sweep (see _LinearBNAct.backward); the conv in front owns its bias
+            dgamma, dbeta = (dgamma if ctx.needs_input_grad[1] else None), (dbeta if ctx.needs_input_grad[2] else None)
+            _bn_eval_backward(lib, g, Y, a, c, dY, ctx.bn_eval, None, dgamma, dbeta, None, R, C, 1, C, 0, ctx.act)
+        else:
+            _bn_backward(lib, g, Y, a, c, mean, invstd, dY, dgamma, dbeta, R, C, 1, C, 0, ctx.act, ctx.sync)
         return dY, dgamma, dbeta, None, None
 
 
 def bn_act_supported(bn, x, act_mod) -> bool:
     """fp32 CUDA activations in channels-last memory (what a channels-last convolution returns), affine BN, GELU or no
-    activation, channel count a multiple of 4; gradients through eval-mode BN stay on the composable path."""
+    activation, channel count a multiple of 4.  Train-mode and eval-mode (frozen) BN alike, with or without gradients."""
     if not (ENABLED and STEM_BN and x.is_cuda and x.dim() == 4 and x.dtype == _F32 and _bn_ok(bn)):
         return False
     if act_mod is not None and not isinstance(act_mod, torch.nn.GELU):
         return False
     C = x.shape[1]
     if C % 4 or C > 4096 or not x.permute(0, 2, 3, 1).is_contiguous():
-        return False
-    if torch.is_grad_enabled() and not bn.training and (x.requires_grad or bn.weight.requires_grad):
         return False
     return True
 
@@ -1559,8 +1600,9 @@ def _bn_ok(bn) -> bool:
 
 def fused_supported(mod, x, groups: int) -> bool:
     """Fused path preconditions: fp32 CUDA input (any dtype under autocast), 'mr' aggregation with GELU+BN, channel
-    counts that keep float4 / group boundaries aligned, inactive DropPath.  BatchNorm and SyncBatchNorm (statistics
-    all-reduced inside the path) are both handled."""
+    counts that keep float4 / group boundaries aligned.  BatchNorm and SyncBatchNorm (statistics all-reduced inside the
+    path) are both handled, each layer in train mode or in eval mode (frozen: running statistics, gkg_bn_eval_bwd in the
+    backward) independently of the module's own mode."""
     from .graph import MRConv2d
     gc = mod.graph_conv
     C = mod.channels
@@ -1579,8 +1621,6 @@ def fused_supported(mod, x, groups: int) -> bool:
             return False
     if not all(_bn_ok(b) for b in bns):
         return False
-    if torch.is_grad_enabled() and not mod.training and (x.requires_grad or any(p.requires_grad for p in mod.parameters())):
-        return False            # gradients through eval-mode BN: composable path
     return ENABLED
 
 
@@ -1771,8 +1811,6 @@ def ffn_supported(mod, x) -> bool:
     if not isinstance(mod.act, torch.nn.GELU) or not (_bn_ok(mod.fc1[1]) and _bn_ok(mod.fc2[1])):
         return False
     if any(conv.weight.shape[0] % 4 or conv.weight.shape[1] % 4 for conv in (mod.fc1[0], mod.fc2[0])):
-        return False
-    if torch.is_grad_enabled() and not mod.training and (x.requires_grad or any(p.requires_grad for p in mod.parameters())):
         return False
     return True
 

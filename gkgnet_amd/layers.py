@@ -75,6 +75,29 @@ def build_norm(num_features: int) -> nn.Module:
     return layer
 
 
+def _frozen_train(self, mode: bool = True):
+    """``train`` of a BatchNorm frozen by freeze_batchnorm: stays in eval mode whatever the parent asks for."""
+    return type(self).train(self, False)
+
+
+def freeze_batchnorm(module: nn.Module, affine: bool = False) -> nn.Module:
+    """Freeze every BatchNorm under ``module`` for fine-tuning at a small batch: the layers normalise with their running
+    statistics and do not update them, and they stay that way through later ``module.train()`` calls.  ``affine=False`` also
+    stops training their scale and shift (``requires_grad = False``); ``affine=True`` leaves them trainable.  Parameters,
+    buffers and state_dict keys are unchanged.  On the fused path such layers run the eval-mode kernels in both directions
+    (forward: folded affine; backward: gkg_bn_eval_bwd), and a conv bias in front of one has a real gradient.  Returns
+    ``module``."""
+    import types
+    for m in module.modules():
+        if isinstance(m, nn.modules.batchnorm._BatchNorm):
+            m.train = types.MethodType(_frozen_train, m)
+            m.train(False)
+            if not affine and m.affine:
+                m.weight.requires_grad_(False)
+                m.bias.requires_grad_(False)
+    return module
+
+
 def act_layer(act: str, inplace: bool = False, neg_slope: float = 0.2, n_prelu: int = 1) -> nn.Module:
     act = act.lower()
     table = {

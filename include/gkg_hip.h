@@ -397,6 +397,25 @@ int gkg_bn_bwd_atomic_scaled(const float* dout, const float* y, const float* a, 
                              const float* invstd, float* dy, float* dgamma, float* dbeta, int R, int C, int nb, int ldg,
                              size_t dout_bstride, int act, double* sums, double* zero_buf, size_t zero_doubles,
                              const float* row_scale, int rows_per_scale, void* stream);
+/* Backward of out = act(a*y + c) for an EVAL-mode BN (running statistics; a, c from gkg_bn_eval_affine, y excludes the conv
+ * bias): frozen-BatchNorm fine-tuning, input gradients of a model in eval().  No batch statistic stands between dout and dy,
+ * so one sweep writes
+ *   dy = a * dz,   dz = dout * row_scale[row / rows_per_scale] * act'(a*y + c)      (row_scale NULL: no scale; act 0 | 1 = GELU)
+ * Operand forms as gkg_bn_bwd_atomic_scaled (y, dy (nb, R, C); dout with row pitch ldg and batch stride; C % 4 == 0).
+ * dgamma / dbeta / dbias ([nb][C] each, any of them NULL = not wanted): the sweep also takes S0 = sum dz, S1 = sum dz*y per
+ * column (fp64 from the first addition on) and a second, small launch finishes
+ *   dbeta = S0,   dgamma = (S1 + (bias - running_mean) * S0) / sqrt(running_var + eps),   dbias = a * S0
+ * (dbias: the gradient of the conv bias in front of the BN — not zero as in train mode).  All three NULL: ONE launch, a pure
+ * elementwise pass (no atomics, no scratch; sums / workspace NULL); dy has the same bits in every form.
+ * `sums` != NULL: fp64 atomics into it (2 * nb * C doubles, ZERO on entry), the finishing launch clears `zero_buf`
+ * (`zero_doubles` doubles) — the alternating-pair protocol of gkg_bn_bwd_atomic; run-dependent in the last fp64 bits.
+ * `sums` == NULL: bit-reproducible two-stage form through `workspace` (gkg_bn_workspace_bytes(R, C, nb)).
+ * No host synchronisation (capturable). */
+int gkg_bn_eval_bwd(const float* dout, const float* y, const float* a, const float* c, float* dy, int R, int C, int nb,
+                    int ldg, size_t dout_bstride, int act, const float* row_scale, int rows_per_scale,
+                    const float* running_mean, const float* running_var, const float* bias, float eps, float* dgamma,
+                    float* dbeta, float* dbias, double* sums, double* zero_buf, size_t zero_doubles, void* workspace,
+                    size_t workspace_bytes, void* stream);
 /* Cross-rank batch statistics (the reference's SyncBatchNorm under DDP, torch_nn.py:37 / mmcv build_norm_layer):
  * gkg_bn_train_stats and gkg_bn_bwd split where the ranks exchange statistics.  Forward: gkg_bn_stats_sums ->
  * caller all-reduces `sums` [nb][2][C] (column sum, sum of squares) and the row count over the ranks ->

@@ -475,6 +475,76 @@ def amp_fp16_case(ref, name, *, C, k, d, hw, G, L, B=2, seed=0, loss_scale=128.0
 
 
 # ----------------------------------------------------------------------------- train-step case
+def frozen_bn_case(ref, name, *, C, k, d, hw, G, L, B=3, seed=0):
+    """F22: fine-tuning with FROZEN BatchNorm — the reference's Grapher -> GrapherLabel chain with the modules in train()
+    and every BatchNorm in eval() (running statistics, not updated), forward + backward in fp32.  In this mode the conv
+    biases in front of a BN have real gradients (train-mode BN removes them exactly), so ``grad/`` holds EVERY parameter
+    of both modules.  Running statistics, affines and conv biases are non-trivial (randomize_norm_ / keyed_fill_)."""
+    torch.manual_seed(seed)
+    gen = torch.Generator().manual_seed(seed + 1)
+    n = hw * hw
+    g = ref.vig.Grapher(C, k, d, "mr", "gelu", "batch", True, False, 0.2, 1, n=n, drop_path=0.0, relative_pos=True,
+                        use_multi_group=True, num_group=G)
+    gl = ref.vig.GrapherLabel(C, k, 1, "mr", "gelu", "batch", True, False, 0.2, 1, n=n, drop_path=0.0,
+                              relative_pos=False, num_nodes=L, use_multi_group=True, num_group=G)
+    for mod, sub in ((g, 22), (gl, 23)):
+        sd = mod.state_dict()
+        with torch.no_grad():
+            keyed_fill_({k_: v for k_, v in sd.items() if k_.endswith(".0.bias")}, seed=seed + sub)     # conv biases
+        randomize_norm_(mod, gen)
+    x = torch.randn(B, C, hw, hw, generator=gen)
+    e = torch.randn(B, L, C, generator=gen)
+    cot_out = torch.randn(B, C, hw, hw, generator=gen)
+    cot_e = torch.randn(B, L, C, generator=gen)
+    # inputs and cotangents on the bf16 grid (fp32 tensors whose low 16 bits are zero, like F7's input): they deflate to about
+    # half, which keeps the file below 1 MiB with every parameter gradient of both modules in it
+    x, e, cot_out, cot_e = (t.to(torch.bfloat16).to(torch.float32) for t in (x, e, cot_out, cot_e))
+    g.train(); gl.train()
+    for mod in (g, gl):
+        for m in mod.modules():
+            if isinstance(m, torch.nn.modules.batchnorm._BatchNorm):
+                m.eval()
+    sd_g, sd_gl = np_state(g), np_state(gl)
+    cap = {}
+    h1 = g.graph_conv.register_forward_hook(lambda m, i, o: cap.update(g_in=i[0].detach().clone(), edge=o[1].detach().clone()))
+    h2 = gl.graph_conv.register_forward_hook(lambda m, i, o: cap.update(l_in=i[0].detach().clone(), l_y=i[2].detach().clone()
+                                                                        if len(i) > 2 and i[2] is not None else None))
+    xg = x.clone().requires_grad_(True)
+    eg = e.clone().requires_grad_(True)
+    out = g(xg)
+    e2, idx = gl(eg, out)
+    ((out * cot_out).sum() + (e2 * cot_e).sum()).backward()
+    h1.remove(); h2.remove()
+    for mod, before in ((g, sd_g), (gl, sd_gl)):                     # frozen: the statistics must not have moved
+        for k_, v in np_state(mod).items():
+            assert np.array_equal(v, before[k_]), k_
+    xq = cap["g_in"].reshape(B * G, C // G, n, 1)
+    topd, topi = ref_top_distances(ref, xq, None, g.relative_pos, k * d)
+    lq = cap["l_in"].reshape(B * G, C // G, L, 1)
+    lk = out.detach().reshape(B * G, C // G, n, 1)
+    ltopd, ltopi = ref_top_distances(ref, lq, lk, None, k)
+    arrays = dict(x=x.numpy(), e=e.numpy(), cot_out=cot_out.numpy(), cot_e=cot_e.numpy(), out=out.detach().numpy(),
+                  e2=e2.detach().numpy(), edge_index=cap["edge"].numpy().astype(np.int32), topd=topd,
+                  topi=topi.astype(np.int32), nn_idx=idx.numpy().astype(np.int32), label_topd=ltopd,
+                  label_topi=ltopi.astype(np.int32), dx=xg.grad.numpy(), de=eg.grad.numpy())
+    # (relative_pos is a function of (C, n) alone, pinned by f9_relpos: the consumer keeps its own — the file stays below 1 MiB)
+    arrays.update({"g/" + k_: v for k_, v in sd_g.items() if not k_.endswith("relative_pos")})
+    arrays.update({"gl/" + k_: v for k_, v in sd_gl.items()})
+    for pre, mod in (("g/", g), ("gl/", gl)):
+        for pn, p in mod.named_parameters():
+            if p.requires_grad:
+                assert p.grad is not None, pn
+                arrays[pre + "grad/" + pn] = p.grad.numpy()
+    # tie-free at fp32: the graphs recomputed in fp64 from the same k-NN inputs are identical
+    for q, y, rp, kd, got, dil in ((xq, None, g.relative_pos, k * d, cap["edge"][0], d), (lq, lk, None, k, idx if idx.dim() == 3 else idx[0], 1)):
+        _, i64 = ref_top_distances(ref, q.double(), None if y is None else y.double(), None if rp is None else rp.double(), kd)
+        assert i64[..., :kd:dil].shape == tuple(got.shape) and np.array_equal(i64[..., :kd:dil], got.numpy()), \
+            "F22 is not tie-free at fp32: pick another seed"
+    meta = dict(kind="frozen_bn", C=C, k=k, dilation=d, r=1, hw=hw, n=n, G=G, L=L, B=B, use_multi_group=True, conv="mr",
+                ref="torch_vertex.py:278-403, modules in train(), every BatchNorm in eval(), fp32 forward + backward")
+    save(name, meta, **arrays)
+
+
 def paramwise_groups(modules, weight_decay):
     """The reference's paramwise_cfg (configs/gkgnet/gkgnet_coco_576.py:110-117: norm_decay_mult=0, bias_decay_mult=0)
     as mmcv's DefaultOptimizerConstructor applies it: every parameter of a norm layer and every 'bias' decays with 0."""
@@ -562,6 +632,8 @@ def main():
             train_step_case(ref, 'f15_train_step')
         if 'f17' in only:
             amp_fp16_case(ref, 'f17_amp_fp16', C=64, k=9, d=2, hw=12, G=2, L=20, seed=17)
+        if 'f22' in only:
+            frozen_bn_case(ref, 'f22_frozen_bn', C=64, k=9, d=2, hw=12, G=2, L=20, seed=22)
         return
     grapher_case(ref, "f1_grapher_cfg1", C=64, k=9, d=1, r=1, hw=14, G=1, multi=False)
     grapher_case(ref, "f2_grapher_g4", C=64, k=9, d=1, r=1, hw=8, G=4, multi=True, seed=2)
@@ -584,6 +656,7 @@ def main():
     autocast_case(ref, 'f14_autocast_bf16', C=64, k=9, d=2, hw=12, G=2, L=20, seed=14)
     train_step_case(ref, 'f15_train_step')
     amp_fp16_case(ref, 'f17_amp_fp16', C=64, k=9, d=2, hw=12, G=2, L=20, seed=17)
+    frozen_bn_case(ref, 'f22_frozen_bn', C=64, k=9, d=2, hw=12, G=2, L=20, seed=22)
     coco_case('f16_coco')
     map_case("f13_map")
 
