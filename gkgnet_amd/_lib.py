@@ -10,7 +10,7 @@ import os
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GKG_HIP_LIB") or os.path.join(PKG, "libgkg_hip.so")   # GKG_HIP_LIB: same-box A/B of two builds (tools)
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 F32, BF16, F16 = 0, 1, 2
 KNN_NORMALIZE = 1
 KNN_BF16_CONTRACT = 2
@@ -69,6 +69,8 @@ def knn_select_flags() -> int:
 MR_DETERMINISTIC = 1
 MR_FP32_ATOMICS = 2
 X6_NO_KS, X6_FORCE_KS = 1, 2
+ERR_UNSUPPORTED = -3
+BLOCK_NO_BWD_FUSE = 1
 
 EXPORTS = ("gkg_version", "gkg_last_error_string", "gkg_knn_workspace_bytes", "gkg_knn_fwd", "gkg_mr_fwd",
            "gkg_mr_bwd", "gkg_prof_enable", "gkg_prof_reset", "gkg_prof_read", "gkg_prof_work", "gkg_knn_fwd_tm", "gkg_mr_fwd_tm",
@@ -86,7 +88,8 @@ EXPORTS = ("gkg_version", "gkg_last_error_string", "gkg_knn_workspace_bytes", "g
            "gkg_knn_fwd_tm16", "gkg_mr_fwd_tm16", "gkg_mr_linear_bf16_nn16",
            "gkg_grapher_fwd", "gkg_grapher_bwd", "gkg_grapher_label_fwd", "gkg_grapher_label_bwd",
            "gkg_gconv_workspace_bytes", "gkg_gin_fwd", "gkg_gin_bwd", "gkg_gat_fwd", "gkg_gat_bwd",
-           "gkg_bn_eval_bwd")
+           "gkg_bn_eval_bwd", "gkg_nchw_to_tm_add_bnstats", "gkg_mr_bwd_tm_bnstats", "gkg_linear_dgrad_x6_nchw",
+           "gkg_mr_bwd_tm_bnstats_supported")
 PROF_KERNELS = ("token_prep", "knn_tile", "knn_merge", "mr_fwd", "mr_bwd", "gemm_x6")
 
 _lib = None
@@ -153,6 +156,14 @@ def load():
     lib.gkg_tm_affine_to_nchw_dual.argtypes = [V] * 6 + [I, I, I, V]
     lib.gkg_nchw_to_tm_add.restype = I
     lib.gkg_nchw_to_tm_add.argtypes = [V, V, V, I, I, I, V]
+    lib.gkg_nchw_to_tm_add_bnstats.restype = I
+    lib.gkg_nchw_to_tm_add_bnstats.argtypes = [V] * 7 + [I, I, I, V]
+    lib.gkg_mr_bwd_tm_bnstats.restype = I
+    lib.gkg_mr_bwd_tm_bnstats.argtypes = [V] * 5 + [I] * 8 + [C.c_uint] + [V] * 5
+    lib.gkg_mr_bwd_tm_bnstats_supported.restype = I
+    lib.gkg_mr_bwd_tm_bnstats_supported.argtypes = [I] * 9 + [C.c_uint]
+    lib.gkg_linear_dgrad_x6_nchw.restype = I
+    lib.gkg_linear_dgrad_x6_nchw.argtypes = [V, I, V, V, V, I, I, I, V, I, I, V, Z, C.c_uint, V]
     lib.gkg_bn_apply_train_dual.restype = I
     lib.gkg_bn_apply_train_dual.argtypes = [V] * 15 + [I, I, I, F, F, V, Z, V]
     lib.gkg_bn_workspace_bytes.restype = Z

@@ -38,14 +38,14 @@ class GrapherBlock(C.Structure):
                 ("fc1", ProjBN), ("conv", ProjBN), ("fc2", ProjBN), ("graph", GraphOp), ("sk_ws", V), ("sk_bytes", Z),
                 ("keys_G", I), ("keys_L", I), ("keys_k", I), ("keys_d", I), ("keys_fused_mr", I), ("keys_flags", U), ("keys_ws", V),
                 ("keys_ws_bytes", Z), ("dout", V), ("dout_tm", V), ("dx", V), ("g3", V), ("dY3", V), ("dA2", V), ("dY2", V), ("dXM", V),
-                ("gx1", V), ("dY1", V), ("dxt", V)]
+                ("gx1", V), ("dY1", V), ("dxt", V), ("bwd_flags", U)]
 
 
 class LabelBlock(C.Structure):
     _fields_ = [("B", I), ("C", I), ("L", I), ("M", I), ("e", V), ("ft", V), ("out", V), ("XM", V), ("A2", V), ("h2", V), ("f1", V),
                 ("fc1", ProjBN), ("conv", ProjBN), ("fc2", ProjBN), ("ffn1", ProjBN), ("ffn2", ProjBN), ("graph", GraphOp), ("sk_ws", V),
                 ("sk_bytes", Z), ("dout", V), ("de", V), ("dft", V), ("dY5", V), ("df1", V), ("dY4", V), ("dh2", V), ("dY3", V),
-                ("dA2", V), ("dY2", V), ("dXM", V), ("gx1", V), ("dY1", V)]
+                ("dA2", V), ("dY2", V), ("dXM", V), ("gx1", V), ("dY1", V), ("bwd_flags", U)]
 
 
 ENABLED = "block_driver" not in fused._DISABLED
@@ -439,6 +439,7 @@ class _GrapherBlockFn(torch.autograd.Function):
         dout_c = dout.contiguous()
         dtm_c = None if dtm is None else dtm.contiguous()
         d.dout, d.dout_tm, d.dx = dout_c.data_ptr(), _ptr(dtm_c), dx.data_ptr()
+        d.bwd_flags = 0 if fused.BWD_FUSE else _lib.BLOCK_NO_BWD_FUSE
         scratch = fused._BnBwdScratch.of(dev)
         wq = (_lib.WgradProblem * 3)()
         p1, pc, p2 = plan.projs
@@ -547,6 +548,7 @@ class _LabelBlockFn(torch.autograd.Function):
         dft = torch.empty((B, M, Cc), dtype=_F32, device=dev)
         dout_c = dout.contiguous()
         d.dout, d.de, d.dft = dout_c.data_ptr(), de.data_ptr(), dft.data_ptr()
+        d.bwd_flags = 0 if fused.BWD_FUSE else _lib.BLOCK_NO_BWD_FUSE
         scratch = fused._BnBwdScratch.of(dev)
         wq = (_lib.WgradProblem * 5)()
         p1, pc, p3, p4, p5 = plan.projs

@@ -40,6 +40,31 @@ int proj_bwd(const GkgProjBN& p, const float* g, int ldg, size_t gbs, int R, int
   return gkg_linear_dgrad_x6_sk(dY, p.cout, (size_t)R * p.cout, p.planes_dgrad, dx, R, p.cin, p.cout, p.nb, residual, sk_ws, sk_bytes, ldx,
                                 x_bstride, 0, st);
 }
+// The BN half of proj_bwd with the statistics ALREADY in p.bsum — left there by the kernel that produced g
+// (gkg_nchw_to_tm_add_bnstats, gkg_mr_bwd_tm_bnstats; un-grouped layer, act == 0): the apply pass only.
+int proj_bwd_apply(const GkgProjBN& p, const float* g, int R, float* dY, void* st) {
+  const int n = p.cout;
+  return gkg_bn_bwd_apply_from_sums(g, p.Y, p.bn, p.bn + n, p.bn + 2 * n, p.bn + 3 * n, dY, p.dgamma, p.dbeta, R, p.cout, 1, p.cout, 0, 0,
+                                    p.bsum, p.bzero, p.bzero_n, st);
+}
+int proj_dgrad(const GkgProjBN& p, const float* dY, int R, const float* residual, float* dx, void* sk_ws, size_t sk_bytes, void* st) {
+  return gkg_linear_dgrad_x6_sk(dY, p.cout, (size_t)R * p.cout, p.planes_dgrad, dx, R, p.cin, p.cout, p.nb, residual, sk_ws, sk_bytes, 0, 0, 0, st);
+}
+// gkg_mr_bwd_tm with fc1's BN backward statistics taken inside the scatter (then only the apply pass follows), or — bwd_fuse off,
+// or a shape whose scatter form carries none — the plain call and the two-launch BN backward
+int mr_bwd_bn(const GkgProjBN& p, const GkgGraphOp& g, bool fuse, const float* dXM, float* gx1, float* gsrc, int B, int C, int N, int M,
+              float* dY, void* st) {
+  const uint8_t* arg = reinterpret_cast<const uint8_t*>(g.arg);
+  const int T = B * N;
+  if (fuse) {
+    const int rc = gkg_mr_bwd_tm_bnstats(dXM, nullptr, arg, gx1, gsrc, B, g.G, C / g.G, N, M, g.k, 1, 1, g.mr_flags, p.Y, p.bn + 2 * p.cout,
+                                         p.bn + 3 * p.cout, p.bsum, st);
+    if (rc == 0) return proj_bwd_apply(p, gx1, T, dY, st);
+    if (rc != GKG_ERR_UNSUPPORTED) return rc;
+  }
+  GKG_TRY(gkg_mr_bwd_tm(dXM, nullptr, arg, gx1, gsrc, B, g.G, C / g.G, N, M, g.k, 1, 1, g.mr_flags, st));
+  return proj_bwd(p, gx1, p.cout, 0, T, 0, dY, nullptr, nullptr, 0, 0, nullptr, 0, st);
+}
 void wgrad_entry(GkgWgradProblem& q, const GkgProjBN& p, const float* dY, const float* x, int ldx, size_t x_bstride, int R, int kperm) {
   q.dy = dY; q.x = x; q.dw = p.dw;
   q.g_bstride = (size_t)R * p.cout; q.x_bstride = x_bstride;
@@ -114,17 +139,28 @@ extern "C" int gkg_grapher_bwd(const GkgGrapherBlock* b, GkgWgradProblem* wq, vo
     return gkg_fail(GKG_ERR_NULL, "gkg_grapher_bwd: null pointer");
   const int B = b->B, C = b->C, N = b->H * b->W, T = B * N;
   // the output's gradient(s) token-major; it is also the residual branch's gradient
-  if (b->dout_tm) GKG_TRY(gkg_nchw_to_tm_add(b->dout, b->dout_tm, b->g3, B, C, N, st));
-  else GKG_TRY(gkg_nchw_to_tm(b->dout, b->g3, B, C, N, GKG_F32, nullptr, st));
-  GKG_TRY(proj_bwd(b->fc2, b->g3, C, 0, T, 0, b->dY3, nullptr, b->dA2, 0, 0, b->sk_ws, b->sk_bytes, st));
+  // (round 8, unless GKG_BLOCK_NO_BWD_FUSE: the re-layout pass takes fc2's BN backward statistics, the scatter takes fc1's, and
+  // fc1's input-gradient GEMM stores dx channel-major — four launches fewer)
+  const bool fuse = !(b->bwd_flags & GKG_BLOCK_NO_BWD_FUSE);
+  if (fuse) {
+    GKG_TRY(gkg_nchw_to_tm_add_bnstats(b->dout, b->dout_tm, b->g3, b->fc2.Y, b->fc2.bn + 2 * C, b->fc2.bn + 3 * C, b->fc2.bsum, B, C, N, st));
+    GKG_TRY(proj_bwd_apply(b->fc2, b->g3, T, b->dY3, st));
+    GKG_TRY(proj_dgrad(b->fc2, b->dY3, T, nullptr, b->dA2, b->sk_ws, b->sk_bytes, st));
+  } else {
+    if (b->dout_tm) GKG_TRY(gkg_nchw_to_tm_add(b->dout, b->dout_tm, b->g3, B, C, N, st));
+    else GKG_TRY(gkg_nchw_to_tm(b->dout, b->g3, B, C, N, GKG_F32, nullptr, st));
+    GKG_TRY(proj_bwd(b->fc2, b->g3, C, 0, T, 0, b->dY3, nullptr, b->dA2, 0, 0, b->sk_ws, b->sk_bytes, st));
+  }
   wgrad_entry(wq[0], b->fc2, b->dY3, b->A2, 2 * C, (size_t)T * 2 * C, T, 0);
   GKG_TRY(proj_bwd(b->conv, b->dA2, 2 * C, (size_t)(C / 2), T, 1, b->dY2, nullptr, b->dXM, 2 * C, (size_t)(C / 2), b->sk_ws, b->sk_bytes, st));
   wgrad_entry(wq[1], b->conv, b->dY2, b->XM, 2 * C, (size_t)(C / 2), T, 1);
   const GkgGraphOp& g = b->graph;
-  GKG_TRY(gkg_mr_bwd_tm(b->dXM, nullptr, reinterpret_cast<const uint8_t*>(g.arg), b->gx1, nullptr, B, g.G, C / g.G, N, N, g.k, 1, 1, g.mr_flags, st));
-  // fc1: its input gradient + the residual branch's (g3), then back to NCHW
-  GKG_TRY(proj_bwd(b->fc1, b->gx1, C, 0, T, 0, b->dY1, b->g3, b->dxt, 0, 0, b->sk_ws, b->sk_bytes, st));
+  GKG_TRY(mr_bwd_bn(b->fc1, g, fuse, b->dXM, b->gx1, nullptr, B, C, N, N, b->dY1, st));
+  // fc1: its input gradient + the residual branch's (g3), channel-major (NCHW)
   wgrad_entry(wq[2], b->fc1, b->dY1, b->xt, C, (size_t)T * C, T, 0);
+  if (fuse)
+    return gkg_linear_dgrad_x6_nchw(b->dY1, C, b->fc1.planes_dgrad, b->dx, b->dxt, T, C, C, b->g3, B, N, b->sk_ws, b->sk_bytes, 0, st);
+  GKG_TRY(proj_dgrad(b->fc1, b->dY1, T, b->g3, b->dxt, b->sk_ws, b->sk_bytes, st));
   return gkg_tm_affine_to_nchw(b->dxt, nullptr, nullptr, nullptr, b->dx, B, C, N, nullptr, st);
 }
 
@@ -176,8 +212,8 @@ extern "C" int gkg_grapher_label_bwd(const GkgLabelBlock* b, GkgWgradProblem* wq
   wgrad_entry(wq[2], b->fc2, b->dY3, b->A2, 2 * C, (size_t)T * 2 * C, T, 0);
   GKG_TRY(proj_bwd(b->conv, b->dA2, 2 * C, (size_t)(C / 2), T, 1, b->dY2, nullptr, b->dXM, 2 * C, (size_t)(C / 2), b->sk_ws, b->sk_bytes, st));
   wgrad_entry(wq[3], b->conv, b->dY2, b->XM, 2 * C, (size_t)(C / 2), T, 1);
-  GKG_TRY(gkg_mr_bwd_tm(b->dXM, nullptr, reinterpret_cast<const uint8_t*>(g.arg), b->gx1, b->dft, B, g.G, C / g.G, L, M, g.k, 1, 1, g.mr_flags, st));
-  GKG_TRY(proj_bwd(b->fc1, b->gx1, C, 0, T, 0, b->dY1, b->dh2, b->de, 0, 0, b->sk_ws, b->sk_bytes, st));           // + the block residual's gradient
+  GKG_TRY(mr_bwd_bn(b->fc1, g, !(b->bwd_flags & GKG_BLOCK_NO_BWD_FUSE), b->dXM, b->gx1, b->dft, B, C, L, M, b->dY1, st));
+  GKG_TRY(proj_dgrad(b->fc1, b->dY1, T, b->dh2, b->de, b->sk_ws, b->sk_bytes, st));                                // + the block residual's gradient
   wgrad_entry(wq[4], b->fc1, b->dY1, b->e, C, (size_t)T * C, T, 0);
   return 0;
 }

@@ -18,28 +18,72 @@ namespace gkg {
 
 // ------------------------------------------------------------------------------------------ layout
 // (B, C, N) channel-major -> (B*N, C) token-major through a padded 32x32 LDS tile (coalesced both sides).
-template <typename OutT>
+// STATS (round 8, the upstream gradient of a block's last layer, gkg_nchw_to_tm_add_bnstats): the pass that writes g = out is
+// also the statistics pass of that layer's BN backward (act == 0: dz = g) — next to every store it reads y[t][ch] at the same
+// coalesced address and accumulates  sum g, sum g * yhat  per channel; the workgroup's eight row groups are combined through LDS
+// in fp64 and leave ONE fp64 atomic pair per channel in `asums` ([2][C], zero on entry, as for bn_bwd_stats_kernel).  That
+// instantiation takes four 32-token tiles per workgroup, so that the launch issues no more atomics than the pass it replaces.
+template <typename OutT, bool STATS = false>
 __global__ __launch_bounds__(256) void nchw_to_tm_kernel(const float* __restrict__ x, OutT* __restrict__ out,
                                                          int C, int N, const float* __restrict__ img_scale,
-                                                         const float* __restrict__ add_tm = nullptr) {
-  __shared__ float tile[32][33];
-  const int b = blockIdx.z, c0 = blockIdx.y * 32, n0 = blockIdx.x * 32;
+                                                         const float* __restrict__ add_tm = nullptr,
+                                                         const float* __restrict__ y = nullptr, const float* __restrict__ mean = nullptr,
+                                                         const float* __restrict__ invstd = nullptr, double* __restrict__ asums = nullptr) {
+  constexpr int TS = STATS ? 4 : 1;                       // 32-token tiles per workgroup
+  __shared__ float tile[TS][32][33];
+  const int b = blockIdx.z, c0 = blockIdx.y * 32, n0 = blockIdx.x * 32 * TS;
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;      // 32 x 8
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int ch = c0 + ty + 8 * i, n = n0 + tx;
-    tile[ty + 8 * i][tx] = (ch < C && n < N) ? x[((size_t)b * C + ch) * N + n] : 0.f;
-  }
+  for (int s = 0; s < TS; ++s)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int ch = c0 + ty + 8 * i, n = n0 + 32 * s + tx;
+      tile[s][ty + 8 * i][tx] = (ch < C && n < N) ? x[((size_t)b * C + ch) * N + n] : 0.f;
+    }
   const float sc = img_scale ? img_scale[b] : 1.0f;       // stochastic depth: per-image keep / (1 - p) factor
+  float mv = 0.f, iv = 0.f, s0 = 0.f, s1 = 0.f;
+  float av[TS][4], yv[TS][4];                             // STATS: the addend and y of this thread's 16 outputs, requested with
+  if constexpr (STATS) {                                  // the tile's loads — nothing waits for memory behind the barrier
+    if (c0 + tx < C) { mv = mean[c0 + tx]; iv = invstd[c0 + tx]; }
+#pragma unroll
+    for (int s = 0; s < TS; ++s)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int n = n0 + 32 * s + ty + 8 * i, ch = c0 + tx;
+        const bool ok = ch < C && n < N;
+        const size_t o = ((size_t)b * N + n) * C + ch;
+        av[s][i] = (ok && add_tm) ? add_tm[o] : 0.f;
+        yv[s][i] = ok ? y[o] : 0.f;
+      }
+  }
   __syncthreads();
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int n = n0 + ty + 8 * i, ch = c0 + tx;
-    if (ch < C && n < N) {
-      const size_t o = ((size_t)b * N + n) * C + ch;
-      float v = tile[tx][ty + 8 * i];
-      if (add_tm) v += add_tm[o];                 // a second gradient of the same tensor that arrives token-major
-      stf(out + o, img_scale ? v * sc : v);
+  for (int s = 0; s < TS; ++s)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int n = n0 + 32 * s + ty + 8 * i, ch = c0 + tx;
+      if (ch < C && n < N) {
+        const size_t o = ((size_t)b * N + n) * C + ch;
+        float v = tile[s][tx][ty + 8 * i];
+        if (add_tm) v += STATS ? av[s][i] : add_tm[o];      // a second gradient of the same tensor that arrives token-major
+        stf(out + o, img_scale ? v * sc : v);
+        if (STATS) {
+          s0 += v;
+          s1 += v * ((yv[s][i] - mv) * iv);
+        }
+      }
+    }
+  if constexpr (STATS) {
+    __shared__ double red[2][8][32];
+    red[0][ty][tx] = (double)s0;
+    red[1][ty][tx] = (double)s1;
+    __syncthreads();
+    if (threadIdx.x < 64) {
+      const int which = threadIdx.x >> 5;
+      double acc = 0.0;
+#pragma unroll
+      for (int l = 0; l < 8; ++l) acc += red[which][l][tx];
+      if (c0 + tx < C) __hip_atomic_fetch_add(asums + (size_t)which * C + c0 + tx, acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
 }
@@ -751,6 +795,21 @@ extern "C" int gkg_nchw_to_tm_add(const float* x, const float* add_tm, float* ou
   hipLaunchKernelGGL(nchw_to_tm_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, x, out, C, N, (const float*)nullptr, add_tm);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : gkg_fail_hip(e, "nchw_to_tm_kernel (add)");
+}
+
+// gkg_nchw_to_tm_add (add_tm may be NULL: a plain re-layout) that is ALSO the statistics pass of the BN backward whose upstream
+// gradient it writes (act == 0, nb == 1): y (B*N, C) is that layer's pre-BN output, `sums` ([2][C] fp64, ZERO on entry) receives
+// sum g and sum g * yhat with atomics, exactly what gkg_bn_bwd_atomic's first launch would leave there.  The caller follows it
+// with gkg_bn_bwd_apply_from_sums.  `out` has the bits gkg_nchw_to_tm_add / gkg_nchw_to_tm give.
+extern "C" int gkg_nchw_to_tm_add_bnstats(const float* x, const float* add_tm, float* out, const float* y, const float* mean,
+                                          const float* invstd, double* sums, int B, int C, int N, void* stream) {
+  if (!x || !out || !y || !mean || !invstd || !sums) return gkg_fail(GKG_ERR_NULL, "gkg_nchw_to_tm_add_bnstats: null pointer");
+  if (B <= 0 || C <= 0 || N <= 0 || B > 65535) return gkg_fail(GKG_ERR_SHAPE, "gkg_nchw_to_tm_add_bnstats: bad sizes");
+  dim3 grid((N + 127) / 128, (C + 31) / 32, B);
+  hipLaunchKernelGGL((nchw_to_tm_kernel<float, true>), grid, dim3(256), 0, (hipStream_t)stream, x, out, C, N, (const float*)nullptr, add_tm,
+                     y, mean, invstd, sums);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : gkg_fail_hip(e, "nchw_to_tm_kernel (add + BN backward statistics)");
 }
 
 // gkg_tm_affine_to_nchw with the residual given token-major and the result written in both layouts.

@@ -163,9 +163,12 @@ struct X6Args {
   int ksplit, kper;
   float* part;  unsigned* cnt;
   const float* add;                                     // X6_STORE: C = A B^T + add (same shape and pitch as C), or null
+  // X6_STORE_NCHW: the tile goes out channel-major, C (M / nchw_n, nchw_c == N, nchw_n) — row m is token m % nchw_n of image
+  // m / nchw_n — while `add` stays token-major (row pitch ldc).  nchw_n % 4 == 0 and M == images * nchw_n.
+  int nchw_n, nchw_c;
 };
 
-enum { X6_STORE = 0, X6_BNSTATS = 1, X6_BNBWD = 2 };
+enum { X6_STORE = 0, X6_BNSTATS = 1, X6_BNBWD = 2, X6_STORE_NCHW = 3 };
 
 __device__ __forceinline__ void x6_chan_merge(double& n, double& mean, double& m2, double nb, double mb, double m2b) {
   if (nb <= 0.0) return;
@@ -434,6 +437,30 @@ __global__ __launch_bounds__(256) void gemm_x6_kernel(X6Args g) {
 #pragma unroll
         for (int q = 0; q < 16; ++q) acc[j][q] += __hip_atomic_load(ps + (j * 16 + q) * 256, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+  }
+  if constexpr (EPI == X6_STORE_NCHW) {
+    // registers 4 qg .. 4 qg + 3 of a block are four consecutive tokens of ONE channel: 16 contiguous bytes of the (image,
+    // channel, token) tensor.  Tokens per image and M are multiples of 4, so a group never crosses an image and is stored or
+    // skipped as a whole.  Same values as X6_STORE (the residual is read token-major and added in the same order).
+#pragma unroll
+    for (int j = 0; j < NI; ++j) {
+      const int n = n0 + j * 32 + r;
+      const bool mine = n < N && (!PARTIAL || j * 32 + r < BN);
+#pragma unroll
+      for (int qg = 0; qg < 4; ++qg) {
+        const int m = m0 + 32 * w + 8 * qg + 4 * h;
+        if (m < M && mine) {
+          float4 v = make_float4(acc[j][4 * qg], acc[j][4 * qg + 1], acc[j][4 * qg + 2], acc[j][4 * qg + 3]);
+          if (g.add) {
+            const float* ap = g.add + (size_t)z * g.c_bstride + (size_t)m * g.ldc + n;
+            v.x += ap[0]; v.y += ap[g.ldc]; v.z += ap[2 * (size_t)g.ldc]; v.w += ap[3 * (size_t)g.ldc];
+          }
+          const int img = m / g.nchw_n, tok = m - img * g.nchw_n;
+          *reinterpret_cast<float4*>(C + ((size_t)img * g.nchw_c + n) * g.nchw_n + tok) = v;
+        }
+      }
+    }
+    return;
   }
 #pragma unroll
   for (int j = 0; j < NI; ++j) {
@@ -778,7 +805,7 @@ static hipError_t x6_launch(X6Args a, int nb, hipStream_t st, void* sk_ws = null
   // where every 32-row workgroup re-reads a wide B (320 -> 1280: 30.0 vs 22.4, its transpose 27.3 vs 21.3: 196 MB of plane
   // traffic) and on the grouped 4 x (160 -> 160) products (15.5 vs 13.5).  Rule: un-grouped, at most 640 output columns.
   // The caller's `flags` (GKG_X6_NO_KS / GKG_X6_FORCE_KS: measurement, tests) override the rule per call.
-  if constexpr (EPI != X6_BNBWD) {
+  if constexpr (EPI != X6_BNBWD && EPI != X6_STORE_NCHW) {
     if (sk_ws && !(flags & GKG_X6_NO_KS) && a.M <= 4096 && (long long)((a.M + 31) / 32) * ((a.N + 63) / 64) * nb <= 65535 * 8 &&
         ((flags & GKG_X6_FORCE_KS) || (nb == 1 && a.N <= 640))) {
       // (64-row tiles — half the plane traffic, one wave per SIMD — measured no better on the long contractions they were built
@@ -803,7 +830,7 @@ static hipError_t x6_launch(X6Args a, int nb, hipStream_t st, void* sk_ws = null
   // 64-column tile — 663 552 rows: 80 -> 80 171 -> 133 us, + statistics 208 -> 161, 320 -> 80 345 -> 279, dgrad 320 <- 80
   // 351 -> 279.  Wider outputs measured equal or slower on 80-column tiles (160: +-3 %, 320 / 400 / 640: 3-8 % slower:
   // profiles/r04_x6_80_column_tiles_ab.txt); the BN-backward epilogue's registers do not fit two waves per SIMD there.
-  if constexpr (EPI != X6_BNBWD) {
+  if constexpr (EPI != X6_BNBWD && EPI != X6_STORE_NCHW) {
     if (a.N == 80 && ni == 2) return x6_launch_ni<3, EPI, 80>(a, nb, st);
   }
   if (ni == 1) return x6_launch_ni<1, EPI>(a, nb, st);
@@ -1544,6 +1571,43 @@ extern "C" int gkg_linear_dgrad_x6_sk(const float* dy, int ldg, size_t g_bstride
   if (splitk_ws && (splitk_bytes < X6_SK_BYTES || ((size_t)splitk_ws & 15)))
     return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_dgrad_x6_sk: need a 16-byte aligned workspace of gkg_x6_splitk_workspace_bytes() bytes (or NULL: no split)");
   return x6_dgrad_impl(dy, ldg, g_bstride, planes_dgrad, dx, R, cin, cout, nb, residual, splitk_ws, splitk_bytes, stream, ldx, x_bstride, flags);
+}
+
+// The un-grouped input gradient (+ token-major residual) stored CHANNEL-MAJOR: dx (B, cin, N) = (dy w + residual)^T per image,
+// R == B * N rows — a block's first layer, whose input gradient leaves the block as an NCHW tensor (round 8: the re-layout pass
+// behind gkg_linear_dgrad_x6_sk and its kernel boundary are gone).  The 128-row tile kernel stores so itself (X6_STORE_NCHW) when
+// N % 4 == 0 and the shape takes that kernel; otherwise (the short-matrix body, 80-column tiles, N % 4 != 0) the two launches
+// run as before: gkg_linear_dgrad_x6_sk into `dx_tm` (R, cin; scratch, required) and gkg_tm_affine_to_nchw.  Either way dx
+// has the bits of that two-launch form.
+extern "C" int gkg_linear_dgrad_x6_nchw(const float* dy, int ldg, const void* planes_dgrad, float* dx, float* dx_tm, int R, int cin,
+                                        int cout, const float* residual, int B, int N, void* splitk_ws, size_t splitk_bytes,
+                                        unsigned flags, void* stream) {
+  if (!dy || !planes_dgrad || !dx || !dx_tm) return gkg_fail(GKG_ERR_NULL, "gkg_linear_dgrad_x6_nchw: null pointer");
+  if (B <= 0 || N <= 0 || (long long)B * N != R) return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_dgrad_x6_nchw: R == B * N");
+  if (splitk_ws && (splitk_bytes < X6_SK_BYTES || ((size_t)splitk_ws & 15)))
+    return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_dgrad_x6_nchw: need a 16-byte aligned workspace of gkg_x6_splitk_workspace_bytes() bytes (or NULL: no split)");
+  // x6_launch's rule for the short-matrix body (which has no channel-major store)
+  const bool ks_form = splitk_ws && !(flags & GKG_X6_NO_KS) && R <= 4096 && (long long)((R + 31) / 32) * ((cin + 63) / 64) <= 65535 * 8 &&
+                       ((flags & GKG_X6_FORCE_KS) || cin <= 640);
+  const bool tile80 = cin == 80 && (long long)((R + 127) / 128) * ((cin + 63) / 64) >= 160;
+  if ((N & 3) || ks_form || tile80 || ((size_t)dx & 15)) {
+    const int rc = x6_dgrad_impl(dy, ldg, (size_t)R * cout, planes_dgrad, dx_tm, R, cin, cout, 1, residual, splitk_ws, splitk_bytes, stream, 0, 0, flags);
+    if (rc != 0) return rc;
+    return gkg_tm_affine_to_nchw(dx_tm, nullptr, nullptr, nullptr, dx, B, cin, N, nullptr, stream);
+  }
+  if (R <= 0 || x6_bad_dim(cin) || x6_bad_dim(cout) || ldg < cout || (ldg & 3) || ((size_t)dy & 15))
+    return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_dgrad_x6_nchw: need R > 0, cin % 4 == 0, cout % 4 == 0, 16-byte aligned rows");
+  if ((size_t)R * ldg * 4 > 0xffffffffull) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_dgrad_x6_nchw: operand larger than 4 GiB");
+  X6Args a{};
+  a.A = dy; a.a_bstride = 0; a.lda = ldg;
+  a.NP = (cin + X6_NPAD - 1) / X6_NPAD * X6_NPAD; a.KC = (cout + 31) / 32 * 4;
+  a.P = (const uint4*)planes_dgrad; a.p_bstride = (size_t)3 * a.KC * a.NP;
+  a.C = dx; a.c_bstride = (size_t)R * cin; a.ldc = cin;
+  a.M = R; a.N = cin; a.K = cout;
+  a.add = residual;
+  a.nchw_n = N; a.nchw_c = cin;
+  hipError_t e = x6_launch<X6_STORE_NCHW>(a, 1, (hipStream_t)stream, splitk_ws, splitk_bytes, flags);
+  return e == hipSuccess ? 0 : gkg_fail_hip(e, "gemm_x6_kernel (dgrad, channel-major store)");
 }
 
 // The same input gradient with the BACKWARD statistics of the producer's BN in the epilogue (X6_BNBWD): dx is the upstream

@@ -15,6 +15,7 @@
 #include <type_traits>
 
 #include "gkg_common.h"
+#include <optional>
 
 namespace gkg {
 
@@ -498,11 +499,70 @@ __device__ __forceinline__ float mr_from_fixed(long long a, int emax, int shmax)
   return (float)__builtin_ldexp((double)a, emax - 150 - shmax);
 }
 
-template <bool SELF, int MODE, int AK>
+// ---- BN backward statistics in the scatter (round 8, gkg_mr_bwd_tm_bnstats) ------------------------------------------------
+// gx is the upstream gradient of the layer  x = BN(y)  in front of the aggregation (a Grapher's fc1, act == 0).  A STATS
+// instantiation reads y next to every FINAL gx value it stores (the store phase of the self graph, the first sweep of the
+// bipartite one) and keeps  sum g, sum g * yhat  (yhat = (y - mean) * invstd) for the thread's four channels; at its exit the
+// workgroup (one image x one channel chunk x all rows) combines its row lanes — across the lanes of a wave by shuffles, across
+// the waves through LDS, in fp64 — and adds ONE fp64 atomic pair per channel to `sums` ([2][C], zero on entry): what
+// bn_bwd_stats_kernel<0> would have left there after a pass of its own over gx and y.  gx / gsrc are untouched.
+struct MrBnArgs { const float* y; const float* mean; const float* invstd; double* sums; };
+
+template <bool ON> struct MrStat {};
+template <> struct MrStat<true> {
+  const float* y;
+  float4 m4, i4, s, q;
+  __device__ __forceinline__ void init(const MrBnArgs& a, int ch) {
+    y = a.y;
+    m4 = *reinterpret_cast<const float4*>(a.mean + ch);
+    i4 = *reinterpret_cast<const float4*>(a.invstd + ch);
+    s = make_float4(0.f, 0.f, 0.f, 0.f);
+    q = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  // g: the four gx values stored at element offset `off` of the (T, C) gradient — y has the same shape
+  __device__ __forceinline__ float4 ld(size_t off) const { return *reinterpret_cast<const float4*>(y + off); }
+  __device__ __forceinline__ void add(const float4& g, size_t off) { acc(g, ld(off)); }
+  // (ld early — with the iteration's other loads — and acc once g is known keeps y's latency off the store loops)
+  __device__ __forceinline__ void acc(const float4& g, const float4& v) {
+    s.x += g.x; s.y += g.y; s.z += g.z; s.w += g.w;
+    q.x += g.x * ((v.x - m4.x) * i4.x); q.y += g.y * ((v.y - m4.y) * i4.y);
+    q.z += g.z * ((v.z - m4.z) * i4.z); q.w += g.w * ((v.w - m4.w) * i4.w);
+  }
+  // every thread of the workgroup, from uniform control flow; `lds`: the accumulator image (free after the barrier), at least
+  // (NT / 64) * 2 * CW doubles.  CW is 4, 8 or 16: the lanes of a wave that share a channel quad are lane % (CW / 4).
+  template <int NT>
+  __device__ __forceinline__ void flush(void* lds, double* __restrict__ sums, int C, int ch0, int CW) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, cw4 = CW >> 2;
+    double d[8] = {(double)s.x, (double)s.y, (double)s.z, (double)s.w, (double)q.x, (double)q.y, (double)q.z, (double)q.w};
+    for (int o = 32; o >= cw4; o >>= 1) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) d[i] += __shfl_xor(d[i], o);
+    }
+    __syncthreads();
+    double* red = reinterpret_cast<double*>(lds);       // [wave][2][CW]
+    if (lane < cw4) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        red[(wave * 2 + 0) * CW + 4 * lane + i] = d[i];
+        red[(wave * 2 + 1) * CW + 4 * lane + i] = d[4 + i];
+      }
+    }
+    __syncthreads();
+    if (tid < 2 * CW) {
+      const int which = tid / CW, col = tid - which * CW;
+      double a = 0.0;
+#pragma unroll
+      for (int w = 0; w < NT / 64; ++w) a += red[(w * 2 + which) * CW + col];
+      __hip_atomic_fetch_add(sums + (size_t)which * C + ch0 + col, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+};
+
+template <bool SELF, int MODE, int AK, bool STATS = false>
 __device__ __forceinline__ void mr_scatter_f32_body(float* acc, const float* __restrict__ gin, const int64_t* __restrict__ nn_idx,
                                                     const uint8_t* __restrict__ argmax, float* __restrict__ gx,
                                                     float* __restrict__ gsrc, int b, int G, int c, int N, int M, int k, int CW,
-                                                    int ch0, size_t T, bool write_gx) {
+                                                    int ch0, size_t T, bool write_gx, MrStat<STATS>* stat = nullptr) {
   const int C = G * c;
   const int cw4 = CW >> 2;
   const int tid = threadIdx.x;
@@ -529,8 +589,11 @@ __device__ __forceinline__ void mr_scatter_f32_body(float* acc, const float* __r
       mr_targets<AK>(argmax, AK, t * C + ch, ip, k, M, j);
       float4 direct, gm;
       load_grad<MODE>(gin, T, t, C, ch, MODE, direct, gm);
-      if (!SELF && write_gx)
-        *reinterpret_cast<float4*>(gx + t * C + ch) = make_float4(direct.x - gm.x, direct.y - gm.y, direct.z - gm.z, direct.w - gm.w);
+      if (!SELF && write_gx) {
+        const float4 o = make_float4(direct.x - gm.x, direct.y - gm.y, direct.z - gm.z, direct.w - gm.w);
+        if constexpr (STATS) stat->add(o, t * C + ch);
+        *reinterpret_cast<float4*>(gx + t * C + ch) = o;
+      }
       atomicAdd(acc + (size_t)j[0] * CW + 4 * qd + 0, gm.x);
       atomicAdd(acc + (size_t)j[1] * CW + 4 * qd + 1, gm.y);
       atomicAdd(acc + (size_t)j[2] * CW + 4 * qd + 2, gm.z);
@@ -540,16 +603,19 @@ __device__ __forceinline__ void mr_scatter_f32_body(float* acc, const float* __r
   __syncthreads();
   if (tl < TL) {
     float* db = (SELF ? gx : gsrc) + (size_t)b * M * C + ch0;
-    for (int m = tl; m < M; m += TL)
-      *reinterpret_cast<float4*>(db + (size_t)m * C + 4 * qd) = *reinterpret_cast<const float4*>(acc + (size_t)m * CW + 4 * qd);
+    for (int m = tl; m < M; m += TL) {
+      const float4 o = *reinterpret_cast<const float4*>(acc + (size_t)m * CW + 4 * qd);
+      if constexpr (STATS && SELF) stat->add(o, ((size_t)b * M + m) * C + ch);
+      *reinterpret_cast<float4*>(db + (size_t)m * C + 4 * qd) = o;
+    }
   }
 }
 
-template <bool SELF, int MODE, int AK>
+template <bool SELF, int MODE, int AK, bool STATS = false>
 __global__ __launch_bounds__(256) void mr_bwd_tm_scatter_i64_kernel(const float* __restrict__ gin, const int64_t* __restrict__ nn_idx,
                                                                     const uint8_t* __restrict__ argmax, float* __restrict__ gx,
                                                                     float* __restrict__ gsrc, int B, int G, int c, int N, int M,
-                                                                    int k, int CW, int shmax) {
+                                                                    int k, int CW, int shmax, MrBnArgs bn = MrBnArgs{}) {
   extern __shared__ long long acc64[];            // [M][CW] + control words
   const int C = G * c;
   const int nchunk = C / CW;
@@ -569,13 +635,19 @@ __global__ __launch_bounds__(256) void mr_bwd_tm_scatter_i64_kernel(const float*
   __syncthreads();
   // ---- sweep 1: gx of the bipartite graph, and the chunk's largest |gm| bit pattern
   unsigned mx = 0;
+  MrStat<STATS> stat;
+  if constexpr (STATS) stat.init(bn, ch);
   if (tl < TL) {
     for (int n = tl; n < N; n += TL) {
       const size_t t = (size_t)b * N + n;
-      float4 direct, gm;
+      float4 direct, gm, yv;
+      if constexpr (STATS && !SELF) yv = stat.ld(t * C + ch);
       load_grad<MODE>(gin, T, t, C, ch, MODE, direct, gm);
-      if (!SELF)
-        *reinterpret_cast<float4*>(gx + t * C + ch) = make_float4(direct.x - gm.x, direct.y - gm.y, direct.z - gm.z, direct.w - gm.w);
+      if (!SELF) {
+        const float4 o = make_float4(direct.x - gm.x, direct.y - gm.y, direct.z - gm.z, direct.w - gm.w);
+        if constexpr (STATS) stat.acc(o, yv);
+        *reinterpret_cast<float4*>(gx + t * C + ch) = o;
+      }
       mx = max(max(mx, __float_as_uint(gm.x) & 0x7fffffffu), max(__float_as_uint(gm.y) & 0x7fffffffu,
                max(__float_as_uint(gm.z) & 0x7fffffffu, __float_as_uint(gm.w) & 0x7fffffffu)));
     }
@@ -588,8 +660,9 @@ __global__ __launch_bounds__(256) void mr_bwd_tm_scatter_i64_kernel(const float*
   const int emax = (int)(mx >> 23);
   if (emax == 255) {                              // inf / NaN somewhere in this chunk: the fp32-atomic form propagates them
     __syncthreads();
-    mr_scatter_f32_body<SELF, MODE, AK>(reinterpret_cast<float*>(acc64), gin, nn_idx, argmax, gx, gsrc, b, G, c, N, M, k, CW, ch0, T,
-                                        false);
+    mr_scatter_f32_body<SELF, MODE, AK, STATS>(reinterpret_cast<float*>(acc64), gin, nn_idx, argmax, gx, gsrc, b, G, c, N, M, k, CW, ch0,
+                                               T, false, &stat);
+    if constexpr (STATS) stat.template flush<256>(acc64, bn.sums, C, ch0, CW);
     return;
   }
   // ---- sweep 2: exact accumulation
@@ -623,9 +696,11 @@ __global__ __launch_bounds__(256) void mr_bwd_tm_scatter_i64_kernel(const float*
         load_grad<MODE>(gin, T, (size_t)b * N + m, C, ch, MODE, direct, gm);
         o = make_float4(o.x + (direct.x - gm.x), o.y + (direct.y - gm.y), o.z + (direct.z - gm.z), o.w + (direct.w - gm.w));
       }
+      if constexpr (STATS && SELF) stat.add(o, ((size_t)b * M + m) * C + ch);
       *reinterpret_cast<float4*>(db + (size_t)m * C + 4 * qd) = o;
     }
   }
+  if constexpr (STATS) stat.template flush<256>(acc64, bn.sums, C, ch0, CW);
 }
 
 // ---- streaming form of the exact scatter (round 5) ----------------------------------------------------------------------
@@ -645,11 +720,12 @@ __global__ __launch_bounds__(256) void mr_bwd_tm_scatter_i64_kernel(const float*
 //     (the scale sits HEAD orders above the sampled maximum: values more than 2^-(SHMAX - HEAD) below THAT lose low bits —
 //     17 binary orders at N = 20 736).
 // ACC == 1 (measurement): fp64 LDS atomics (ds_add_f64) instead of fixed point — no scale at all, not order-independent.
-template <int NT, bool SELF, int MODE, int AK>
+template <int NT, bool SELF, int MODE, int AK, bool STATS = false>
 __device__ __forceinline__ void mr_i64_two_sweep_body(long long* acc64, unsigned* ctl, const float* __restrict__ gin,
                                                       const int64_t* __restrict__ nn_idx, const uint8_t* __restrict__ argmax,
                                                       float* __restrict__ gx, float* __restrict__ gsrc, int b, int G, int c, int N,
-                                                      int M, int k, int CW, int ch0, size_t T, int shmax, bool write_gx) {
+                                                      int M, int k, int CW, int ch0, size_t T, int shmax, bool write_gx,
+                                                      MrStat<STATS>* stat = nullptr) {
   const int C = G * c;
   const int cw4 = CW >> 2;
   const int tid = threadIdx.x;
@@ -661,8 +737,11 @@ __device__ __forceinline__ void mr_i64_two_sweep_body(long long* acc64, unsigned
       const size_t t = (size_t)b * N + n;
       float4 direct, gm;
       load_grad<MODE>(gin, T, t, C, ch, MODE, direct, gm);
-      if (!SELF && write_gx)
-        *reinterpret_cast<float4*>(gx + t * C + ch) = make_float4(direct.x - gm.x, direct.y - gm.y, direct.z - gm.z, direct.w - gm.w);
+      if (!SELF && write_gx) {
+        const float4 o = make_float4(direct.x - gm.x, direct.y - gm.y, direct.z - gm.z, direct.w - gm.w);
+        if constexpr (STATS) stat->add(o, t * C + ch);
+        *reinterpret_cast<float4*>(gx + t * C + ch) = o;
+      }
       mx = max(max(mx, __float_as_uint(gm.x) & 0x7fffffffu), max(__float_as_uint(gm.y) & 0x7fffffffu,
                max(__float_as_uint(gm.z) & 0x7fffffffu, __float_as_uint(gm.w) & 0x7fffffffu)));
     }
@@ -706,8 +785,11 @@ __device__ __forceinline__ void mr_i64_two_sweep_body(long long* acc64, unsigned
     __syncthreads();
     if (tl < TL) {
       float* db = (SELF ? gx : gsrc) + (size_t)b * M * C + ch0;
-      for (int m = tl; m < M; m += TL)
-        *reinterpret_cast<float4*>(db + (size_t)m * C + 4 * qd) = *reinterpret_cast<const float4*>(acc + (size_t)m * CW + 4 * qd);
+      for (int m = tl; m < M; m += TL) {
+        const float4 o = *reinterpret_cast<const float4*>(acc + (size_t)m * CW + 4 * qd);
+        if constexpr (STATS && SELF) stat->add(o, ((size_t)b * M + m) * C + ch);
+        *reinterpret_cast<float4*>(db + (size_t)m * C + 4 * qd) = o;
+      }
     }
     return;
   }
@@ -740,6 +822,7 @@ __device__ __forceinline__ void mr_i64_two_sweep_body(long long* acc64, unsigned
         load_grad<MODE>(gin, T, (size_t)b * N + m, C, ch, MODE, direct, gm);
         o = make_float4(o.x + (direct.x - gm.x), o.y + (direct.y - gm.y), o.z + (direct.z - gm.z), o.w + (direct.w - gm.w));
       }
+      if constexpr (STATS && SELF) stat->add(o, ((size_t)b * M + m) * C + ch);
       *reinterpret_cast<float4*>(db + (size_t)m * C + 4 * qd) = o;
     }
   }
@@ -747,11 +830,11 @@ __device__ __forceinline__ void mr_i64_two_sweep_body(long long* acc64, unsigned
 
 constexpr int MR_STREAM_HEAD = 6;       // binary orders of headroom above the sampled maximum
 
-template <int NT, bool SELF, int MODE, int AK, int ACC, int U>     // U: rows in flight per thread
+template <int NT, bool SELF, int MODE, int AK, int ACC, int U, bool STATS = false>     // U: rows in flight per thread
 __global__ __launch_bounds__(NT) void mr_bwd_tm_stream_kernel(const float* __restrict__ gin, const int64_t* __restrict__ nn_idx,
                                                                const uint8_t* __restrict__ argmax, float* __restrict__ gx,
                                                                float* __restrict__ gsrc, int B, int G, int c, int N, int M,
-                                                               int k, int CW, int shmax, int arg_planes) {
+                                                               int k, int CW, int shmax, int arg_planes, MrBnArgs bn = MrBnArgs{}) {
   extern __shared__ long long acc64[];            // [M][CW] (fixed point, or the bits of doubles) + control words
   const int C = G * c;
   const int nchunk = C / CW;
@@ -820,15 +903,19 @@ __global__ __launch_bounds__(NT) void mr_bwd_tm_stream_kernel(const float* __res
     lim = (unsigned)(em + 1) << 23;               // |bits| >= lim: beyond the scale (inf / NaN always are)
   }
   bool over = false;
+  MrStat<STATS> stat;
+  if constexpr (STATS) stat.init(bn, ch);
   auto process_rows = [&](int n0) __attribute__((always_inline)) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int n = n0 + u * TL;
       if (n < N) {
         const size_t t = (size_t)b * N + n;
-        if (!SELF)
-          *reinterpret_cast<float4*>(gx + t * C + ch) =
-              make_float4(direct[u].x - gm[u].x, direct[u].y - gm[u].y, direct[u].z - gm[u].z, direct[u].w - gm[u].w);
+        if (!SELF) {
+          const float4 o = make_float4(direct[u].x - gm[u].x, direct[u].y - gm[u].y, direct[u].z - gm[u].z, direct[u].w - gm[u].w);
+          if constexpr (STATS) stat.add(o, t * C + ch);
+          *reinterpret_cast<float4*>(gx + t * C + ch) = o;
+        }
         if (ACC == 0) {
           over |= absmax4(gm[u]) >= lim;
           atomicAdd(reinterpret_cast<unsigned long long*>(acc64 + (size_t)j[u][0] * CW + 4 * qd + 0), (unsigned long long)mr_to_fixed(gm[u].x, em, shmax));
@@ -859,7 +946,9 @@ __global__ __launch_bounds__(NT) void mr_bwd_tm_stream_kernel(const float* __res
       for (int i = tid; i < M * CW; i += NT) acc64[i] = 0;
       if (tid == 0) ctl[0] = 0;
       __syncthreads();
-      mr_i64_two_sweep_body<NT, SELF, MODE, AK>(acc64, ctl, gin, nn_idx, argmax, gx, gsrc, b, G, c, N, M, k, CW, ch0, T, shmax, false);
+      mr_i64_two_sweep_body<NT, SELF, MODE, AK, STATS>(acc64, ctl, gin, nn_idx, argmax, gx, gsrc, b, G, c, N, M, k, CW, ch0, T, shmax, false,
+                                                       &stat);
+      if constexpr (STATS) stat.template flush<NT>(acc64, bn.sums, C, ch0, CW);
       return;
     }
   } else {
@@ -870,7 +959,8 @@ __global__ __launch_bounds__(NT) void mr_bwd_tm_stream_kernel(const float* __res
     float* db = (SELF ? gx : gsrc) + (size_t)b * M * C + ch0;
     for (int m = tl; m < M; m += TL) {
       const long long* a = acc64 + (size_t)m * CW + 4 * qd;
-      float4 o;
+      float4 o, yv;
+      if constexpr (STATS && SELF) yv = stat.ld(((size_t)b * M + m) * C + ch);
       if (ACC == 0) {
         o = make_float4(mr_from_fixed(a[0], em, shmax), mr_from_fixed(a[1], em, shmax), mr_from_fixed(a[2], em, shmax),
                         mr_from_fixed(a[3], em, shmax));
@@ -883,9 +973,11 @@ __global__ __launch_bounds__(NT) void mr_bwd_tm_stream_kernel(const float* __res
         load_grad<MODE>(gin, T, (size_t)b * N + m, C, ch, MODE, direct1, gm1);
         o = make_float4(o.x + (direct1.x - gm1.x), o.y + (direct1.y - gm1.y), o.z + (direct1.z - gm1.z), o.w + (direct1.w - gm1.w));
       }
+      if constexpr (STATS && SELF) stat.acc(o, yv);
       *reinterpret_cast<float4*>(db + (size_t)m * C + 4 * qd) = o;
     }
   }
+  if constexpr (STATS) stat.template flush<NT>(acc64, bn.sums, C, ch0, CW);
 }
 
 // Deterministic scatter (GKG_MR_DETERMINISTIC): the LDS-atomic kernel above adds the fan-in of a key in whatever order
@@ -1236,12 +1328,28 @@ static void launch_tm_stream_nt(bool self, int mode, int ak, dim3 grid, size_t l
 #undef GKG_TMS_CASE
 }
 
-extern "C" int gkg_mr_bwd_tm(const float* gin, const int64_t* nn_idx, const uint8_t* argmax, float* gx, float* gsrc,
-                             int B, int G, int c, int N, int M, int k, int mode, int arg_kind, unsigned flags, void* stream) {
+// The two scatter forms with the BN backward statistics of gx (MrStat): the XM gradient layout (mode 1), chunk widths 4 / 8 / 16,
+// the 512-thread / 4-rows-in-flight streaming form or the two-sweep form.
+template <bool SELF, int AK>
+static void launch_tm_stream_stats(dim3 grid, size_t lds, hipStream_t st, const float* gin, const int64_t* nn_idx, const uint8_t* argmax,
+                                   float* gx, float* gsrc, int B, int G, int c, int N, int M, int k, int CW, int shmax, const MrBnArgs& bn) {
+  if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mr_bwd_tm_stream_kernel<512, SELF, 1, AK, 0, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL((mr_bwd_tm_stream_kernel<512, SELF, 1, AK, 0, 4, true>), grid, dim3(512), lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, CW, shmax, 0, bn);
+}
+template <bool SELF, int AK>
+static void launch_tm_i64_stats(dim3 grid, size_t lds, hipStream_t st, const float* gin, const int64_t* nn_idx, const uint8_t* argmax,
+                                float* gx, float* gsrc, int B, int G, int c, int N, int M, int k, int CW, int shmax, const MrBnArgs& bn) {
+  if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mr_bwd_tm_scatter_i64_kernel<SELF, 1, AK, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL((mr_bwd_tm_scatter_i64_kernel<SELF, 1, AK, true>), grid, dim3(256), lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, CW, shmax, bn);
+}
+
+static int mr_bwd_tm_impl(const float* gin, const int64_t* nn_idx, const uint8_t* argmax, float* gx, float* gsrc, int B, int G, int c,
+                          int N, int M, int k, int mode, int arg_kind, unsigned flags, void* stream, const MrBnArgs* bn,
+                          bool dry = false) {
   if (arg_kind != 0 && arg_kind != 1) return gkg_fail(GKG_ERR_SHAPE, "gkg_mr_bwd_tm: arg_kind is 0 or 1");
   // arg_kind 1: the saved winning ROWS are the scatter targets — the index tensor is not read and may be null (the fused
   // k-NN + aggregation forward, gkg_knn_mr_fwd_tm, never materialises one)
-  if (!gin || (!nn_idx && arg_kind != 1) || !argmax || !gx) return gkg_fail(GKG_ERR_NULL, "gkg_mr_bwd_tm: gin, argmax, gx (and nn_idx unless arg_kind == 1) must be non-null");
+  if (!dry && (!gin || (!nn_idx && arg_kind != 1) || !argmax || !gx)) return gkg_fail(GKG_ERR_NULL, "gkg_mr_bwd_tm: gin, argmax, gx (and nn_idx unless arg_kind == 1) must be non-null");
   if (B <= 0 || G <= 0 || c <= 0 || N <= 0 || M <= 0 || k <= 0 || k > 255 || (c & 3)) return gkg_fail(GKG_ERR_SHAPE, "gkg_mr_bwd_tm: bad sizes");
   if (mode != 0 && mode != 1) return gkg_fail(GKG_ERR_SHAPE, "gkg_mr_bwd_tm: mode is 0 or 1");
   if (mode == 1 && ((G * c) & 15)) return gkg_fail(GKG_ERR_SHAPE, "gkg_mr_bwd_tm: mode 1 needs C % 16 == 0");
@@ -1250,7 +1358,8 @@ extern "C" int gkg_mr_bwd_tm(const float* gin, const int64_t* nn_idx, const uint
   // algorithmic bytes (SURVEY §8d "MR bwd"): g + int64 indices + argmax + gx (+ gsrc); arg_kind 1: u16 winning rows, no indices
   const double work = 4.0 * B * (double)G * c * N + (arg_kind == 1 ? 0.0 : 8.0 * B * (double)G * N * k) + (arg_kind == 1 ? 2.0 : 1.0) * B * (double)G * c * N
                       + 4.0 * B * (double)G * c * N + (gsrc ? 4.0 * B * (double)G * c * M : 0.0);
-  GkgProfScope prof(GKG_PROF_MR_BWD, st, work);
+  std::optional<GkgProfScope> prof;
+  if (!dry) prof.emplace(GKG_PROF_MR_BWD, st, work);       // (a dry run — gkg_mr_bwd_tm_bnstats_supported — launches nothing)
   const int C = G * c;
   const size_t T = (size_t)B * N;
   const size_t total = T * (C / 4);
@@ -1273,6 +1382,9 @@ extern "C" int gkg_mr_bwd_tm(const float* gin, const int64_t* nn_idx, const uint
   // flight), 2 = its fp64-atomic variant (ds_add_f64: 45-98 cycles per wave instruction against 170-183 for ds_add_f32 —
   // tools/ubench/lds_atomic_rate.hip), 3 = the two-sweep kernel wherever it fits.
   const int sv = (int)((flags >> 16) & 3);
+  // with statistics: only the library's own choice among the two exact forms (no measurement overrides), XM gradient layout
+  if (bn && (mode != 1 || sv || ((flags >> 8) & 0xff) || (flags & GKG_MR_FP32_ATOMICS)))
+    return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_mr_bwd_tm_bnstats: mode 1 and the default scatter form only");
   if (N < (1 << 24) && (sv == 1 || sv == 2 || (sv == 0 && !(flags & GKG_MR_FP32_ATOMICS) && N >= 160))) {
     int CW = (int)((flags >> 8) & 0xff);
     auto sfits = [&](int cw) { return (size_t)M * cw * 8 + 16 <= (size_t)MR_LDS_BUDGET && C % cw == 0 && c % cw == 0; };
@@ -1284,11 +1396,22 @@ extern "C" int gkg_mr_bwd_tm(const float* gin, const int64_t* nn_idx, const uint
       const bool long_sweep = M > 512 && (long)N >= 4L * M;
       const bool nt256 = sv ? ((flags >> 20) & 3) == 2 : long_sweep;
       const bool u8 = sv ? ((flags >> 22) & 1) != 0 : (M > 512 && !long_sweep);       // 8 rows in flight
-      const size_t lds = (size_t)M * CW * 8 + 16;
+      size_t lds = (size_t)M * CW * 8 + 16;
       int bitsN = 0;
       while ((1 << bitsN) <= N) ++bitsN;
       const dim3 grid((C / CW) * ((B + 7) / 8) * 8);
       const bool self = gsrc == nullptr;
+      if (bn) {
+        if (nt256 || u8) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_mr_bwd_tm_bnstats: long-sweep streaming forms carry no statistics");
+        if (lds < (size_t)(512 / 64) * 2 * CW * 8) lds = (size_t)(512 / 64) * 2 * CW * 8;       // room for MrStat::flush
+        if (dry) return 0;
+        if (self) { if (arg_kind) launch_tm_stream_stats<true, 1>(grid, lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, CW, 38 - bitsN, *bn);
+                    else launch_tm_stream_stats<true, 0>(grid, lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, CW, 38 - bitsN, *bn); }
+        else { if (arg_kind) launch_tm_stream_stats<false, 1>(grid, lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, CW, 38 - bitsN, *bn);
+               else launch_tm_stream_stats<false, 0>(grid, lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, CW, 38 - bitsN, *bn); }
+        hipError_t eb = hipGetLastError();
+        return eb == hipSuccess ? 0 : gkg_fail_hip(eb, "mr_bwd_tm_stream_kernel (BN backward statistics)");
+      }
       const int planes_bit = (sv && ((flags >> 23) & 1) && arg_kind == 1) ? (1 << 16) : 0;      // measurement: 8-channel planes of winning rows
       if (sv == 2) launch_tm_stream_nt<512, 1, 4>(self, mode, arg_kind, grid, lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, CW, (38 - bitsN) | planes_bit);
       else if (nt256 && u8) launch_tm_stream_nt<256, 0, 8>(self, mode, arg_kind, grid, lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, CW, (38 - bitsN) | planes_bit);
@@ -1309,12 +1432,25 @@ extern "C" int gkg_mr_bwd_tm(const float* gin, const int64_t* nn_idx, const uint
     if (fits(CW, (size_t)MR_LDS_BUDGET) && (long)(C / CW) * (B + 7) < 0x7fffffffL) {
       int bitsN = 0;
       while ((1 << bitsN) <= N) ++bitsN;                  // N < 2^bitsN
+      if (bn) {
+        size_t lds = (size_t)M * CW * 8 + 16;
+        if (lds < (size_t)(256 / 64) * 2 * CW * 8) lds = (size_t)(256 / 64) * 2 * CW * 8;       // room for MrStat::flush
+        if (dry) return 0;
+        const dim3 grid((C / CW) * ((B + 7) / 8) * 8);
+        if (!gsrc) { if (arg_kind) launch_tm_i64_stats<true, 1>(grid, lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, CW, 38 - bitsN, *bn);
+                     else launch_tm_i64_stats<true, 0>(grid, lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, CW, 38 - bitsN, *bn); }
+        else { if (arg_kind) launch_tm_i64_stats<false, 1>(grid, lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, CW, 38 - bitsN, *bn);
+               else launch_tm_i64_stats<false, 0>(grid, lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, CW, 38 - bitsN, *bn); }
+        hipError_t eb = hipGetLastError();
+        return eb == hipSuccess ? 0 : gkg_fail_hip(eb, "mr_bwd_tm_scatter_i64_kernel (BN backward statistics)");
+      }
       launch_tm_i64(gsrc == nullptr, mode, arg_kind, dim3((C / CW) * ((B + 7) / 8) * 8), (size_t)M * CW * 8 + 16, st, gin, nn_idx,
                     argmax, gx, gsrc, B, G, c, N, M, k, CW, 38 - bitsN);
       hipError_t ei = hipGetLastError();
       return ei == hipSuccess ? 0 : gkg_fail_hip(ei, "mr_bwd_tm_scatter_i64_kernel");
     }
   }
+  if (bn) return dry ? GKG_ERR_UNSUPPORTED : gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_mr_bwd_tm_bnstats: this shape takes a scatter form without statistics");
   if (flags & GKG_MR_DETERMINISTIC) {
     if (B > 65535) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_mr_bwd_tm: B <= 65535");
     long TL = (long)(144 * 1024) / ((long)M * 16);
@@ -1350,4 +1486,36 @@ extern "C" int gkg_mr_bwd_tm(const float* gin, const int64_t* nn_idx, const uint
   }
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : gkg_fail_hip(e, "mr_bwd_tm");
+}
+
+extern "C" int gkg_mr_bwd_tm(const float* gin, const int64_t* nn_idx, const uint8_t* argmax, float* gx, float* gsrc,
+                             int B, int G, int c, int N, int M, int k, int mode, int arg_kind, unsigned flags, void* stream) {
+  return mr_bwd_tm_impl(gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, mode, arg_kind, flags, stream, nullptr);
+}
+
+// gkg_mr_bwd_tm that is ALSO the statistics pass of the BN backward whose upstream gradient gx is (the layer x = BN(y) in front
+// of the aggregation: nb == 1, act == 0): y (B*N, C), mean / invstd [C], `sums` [2][C] fp64, ZERO on entry, receives sum gx and
+// sum gx * yhat with atomics — what gkg_bn_bwd_atomic's first launch would leave there; follow it with
+// gkg_bn_bwd_apply_from_sums.  gx / gsrc have the bits of gkg_mr_bwd_tm.  GKG_ERR_UNSUPPORTED (nothing launched, nothing
+// written) when the shape or the flags select a scatter form that carries no statistics: run the plain call and
+// gkg_bn_bwd_atomic then.
+extern "C" int gkg_mr_bwd_tm_bnstats(const float* gin, const int64_t* nn_idx, const uint8_t* argmax, float* gx, float* gsrc,
+                                     int B, int G, int c, int N, int M, int k, int mode, int arg_kind, unsigned flags,
+                                     const float* y, const float* mean, const float* invstd, double* sums, void* stream) {
+  if (!y || !mean || !invstd || !sums) return gkg_fail(GKG_ERR_NULL, "gkg_mr_bwd_tm_bnstats: null pointer");
+  const MrBnArgs bn{y, mean, invstd, sums};
+  return mr_bwd_tm_impl(gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, mode, arg_kind, flags, stream, &bn);
+}
+
+// 1 when gkg_mr_bwd_tm_bnstats would run for these sizes and flags (0: GKG_ERR_UNSUPPORTED or bad sizes); pure host code, for
+// callers that must book their scratch buffer before the call.
+extern "C" int gkg_mr_bwd_tm_bnstats_supported(int B, int G, int c, int N, int M, int k, int mode, int arg_kind, int self_graph,
+                                               unsigned flags) {
+  if (B <= 0 || G <= 0 || c <= 0 || N <= 0 || M <= 0 || k <= 0 || k > 255 || (c & 3) || (mode != 0 && mode != 1) ||
+      (arg_kind != 0 && arg_kind != 1) || (self_graph && M != N))
+    return 0;
+  const MrBnArgs bn{};
+  float dummy;
+  return mr_bwd_tm_impl(nullptr, nullptr, nullptr, nullptr, self_graph ? nullptr : &dummy, B, G, c, N, M, k, mode, arg_kind, flags, nullptr,
+                        &bn, true) == 0;
 }

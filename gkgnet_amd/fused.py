@@ -67,6 +67,8 @@ DETERMINISTIC = os.environ.get("GKG_DETERMINISTIC", "0") != "0"
 #   mr_gemm        bf16 inference: aggregation as the grouped projection's operand producer (row g1)
 #   channels_last  blocks take / return channels-last tensors as views of their token-major matrices
 #   fold_epilogue  bf16 inference: eval-mode BN folded into the weights, bias (+ GELU) in the library GEMM's epilogue
+#   bwd_fuse       backward: BN statistics taken by the kernel that produces the gradient (re-layout pass, aggregation scatter),
+#                  a Grapher's dx stored channel-major by its input-gradient GEMM (BWD_FUSE below)
 _DISABLED = _env_list("GKG_DISABLE")
 _ENABLED = _env_list("GKG_ENABLE")
 KNN_BF16 = "knn_bf16" in _ENABLED
@@ -689,6 +691,60 @@ BN_EPILOGUE = True
 BN_EPILOGUE_MIN_ROWS = 32768
 
 
+# Backward passes folded into their producers (round 8).  Where the upstream gradient g of a train-mode BN layer (no activation)
+# is written by a streaming kernel that holds every value in registers, that kernel also reads Y and takes  sum g, sum g yhat
+# — gkg_nchw_to_tm_add_bnstats for a block's last layer (the NCHW -> token-major re-layout of the block output's gradient),
+# gkg_mr_bwd_tm_bnstats for a Grapher's / GrapherLabel's fc1 (the aggregation's scatter) — and the BN backward runs its apply
+# pass only (gkg_bn_bwd_apply_from_sums); the block driver additionally stores a Grapher's dx channel-major from the GEMM
+# (gkg_linear_dgrad_x6_nchw).  Off (the stand-alone statistics launch) under GKG_DETERMINISTIC, SyncBN, frozen / eval-mode BN, an
+# active DropPath scale, 2 nb C beyond the scratch, and GKG_DISABLE=bwd_fuse.  The statistics' fp32 partial sums follow the
+# producer's partition of the rows: results agree with the two-pass form to rounding (tests/test_hip_bwd_pass_fusion.py).
+BWD_FUSE = "bwd_fuse" not in _DISABLED
+
+
+def _bwd_fuse_ok(mean, sync, scale, nb, co) -> bool:
+    return (BWD_FUSE and mean is not None and sync is None and scale is None and not DETERMINISTIC and nb == 1
+            and 2 * co <= _BnBwdScratch.DOUBLES)
+
+
+_MR_BN_OK = {}
+
+
+def _mr_bn_supported(lib, B, G, c, N, M, k, mode, ak, self_graph, flags) -> bool:
+    key = (B, G, c, N, M, k, mode, ak, self_graph, flags)
+    ok = _MR_BN_OK.get(key)
+    if ok is None:
+        ok = _MR_BN_OK[key] = bool(lib.gkg_mr_bwd_tm_bnstats_supported(B, G, c, N, M, k, mode, ak, 1 if self_graph else 0, flags))
+    return ok
+
+
+def _mr_bwd(lib, g, nn_idx, arg, B, G, C, N, M, k, mode, ak, has_src, xshape, link):
+    """The aggregation's backward -> (gx viewed as ``xshape``, gsrc).  ``link``: the _BnLink of the layer that produced the
+    aggregation's input (found on that tensor in the forward) — the scatter then also takes that layer's BN backward statistics
+    and leaves them on the link, exactly like _dgrad_x6_with_link."""
+    gx = torch.empty((B, N, C), dtype=_F32, device=g.device)
+    gsrc = torch.empty((B, M, C), dtype=_F32, device=g.device) if has_src else None
+    flags = _mr_bwd_flags()
+    if (link is not None and BWD_FUSE and not DETERMINISTIC and link.nb == 1 and link.act == 0 and link.co == C and link.R == B * N
+            and _mr_bn_supported(lib, B, G, C // G, N, M, k, mode, ak, not has_src, flags)):
+        scratch = _BnBwdScratch.of(g.device)
+        cur, other, zero = scratch.acquire(lib, 2 * C)
+        try:
+            _lib.check(lib.gkg_mr_bwd_tm_bnstats(_ptr(g), _ptr(nn_idx), _ptr(arg), _ptr(gx), _ptr(gsrc), B, G, C // G, N, M, k, mode, ak,
+                                                 flags, _ptr(link.Y), _ptr(link.mean), _ptr(link.invstd), _ptr(cur), _stream()),
+                       "gkg_mr_bwd_tm_bnstats")
+        except Exception:
+            scratch.poison()
+            raise
+        gxv = gx.view(xshape)
+        link.ready = (gxv, gxv._version, cur, other, zero)
+        scratch.pending = link
+        return gxv, gsrc
+    _lib.check(lib.gkg_mr_bwd_tm(_ptr(g), _ptr(nn_idx), _ptr(arg), _ptr(gx), _ptr(gsrc), B, G, C // G, N, M, k, mode, ak, flags, _stream()),
+               "gkg_mr_bwd_tm")
+    return gx.view(xshape), gsrc
+
+
 class _BnLink:
     __slots__ = ("Y", "a", "c", "mean", "invstd", "act", "nb", "co", "R", "ready", "__weakref__")
 
@@ -705,6 +761,23 @@ def _bn_link(out, Y, a, c, mean, invstd, act, nb, co, R, bn, sync, scale):
         out._gkg_bn_link = link
         return link
     return None
+
+
+def _relayout_bnstats(lib, dout_c, dtm_c, g, Y, mean, invstd, a, c, B, cout, R):
+    """g (R, cout) = dout_c (B, cout, N)^T (+ dtm_c) with the BN backward statistics of  out = BN(Y)  taken in the same pass
+    (gkg_nchw_to_tm_add_bnstats) -> a _BnLink that carries them to _bn_backward, which then runs the apply pass only."""
+    scratch = _BnBwdScratch.of(g.device)
+    cur, other, zero = scratch.acquire(lib, 2 * cout)
+    try:
+        _lib.check(lib.gkg_nchw_to_tm_add_bnstats(_ptr(dout_c), _ptr(dtm_c), _ptr(g), _ptr(Y), _ptr(mean), _ptr(invstd), _ptr(cur),
+                                                  B, cout, R // B, _stream()), "gkg_nchw_to_tm_add_bnstats")
+    except Exception:
+        scratch.poison()
+        raise
+    link = _BnLink(Y, a, c, mean, invstd, 0, 1, cout, R)
+    link.ready = (g, g._version, cur, other, zero)
+    scratch.pending = link
+    return link
 
 
 def _dgrad_x6_with_link(lib, dY, pd, R, cin, cout, link):
@@ -907,6 +980,9 @@ class _LinearBNAct(torch.autograd.Function):
         ctx.link = _bn_link(out, Y, a, c, mean, invstd, act, 1, cout, R, bn, sync, scale) if (nchw is None and xm is None) else None
         if xm is not None:
             out = _xm_xview(out, xm[0], xm[1], cout)
+            if act == 0 and out.dtype == _F32 and _bwd_fuse_ok(mean, sync, scale, 1, cout):
+                # the aggregation behind this layer takes its BN backward statistics in its scatter (_mr_bwd)
+                ctx.link = out._gkg_mr_bn_link = _BnLink(Y, a, c, mean, invstd, act, 1, cout, R)
             if knn is not None and fused_apply and getattr(knn, "ws", None) is not None:
                 out._gkg_knn = knn               # the queries' prepared copies are in knn.ws (see _knn_prepared)
         if alias:
@@ -935,10 +1011,20 @@ class _LinearBNAct(torch.autograd.Function):
         cout = weight.shape[0]
         dres = dout if has_res else None
         row_scale = None
+        link = ctx.link
         if ctx.dual:
             # the output went out in both layouts: its two upstream gradients are summed while the NCHW one is re-laid out, and
             # the (token-major) residual's gradient is that very sum
-            if dout is None:
+            fuse_stats = _bwd_fuse_ok(mean, ctx.sync, ctx.scale[0], 1, cout)
+            if fuse_stats:
+                # the re-layout pass is also this BN's backward statistics pass (BWD_FUSE); like the block driver it takes a
+                # missing NCHW gradient as zeros, so that both issue the same launches
+                if dout is None:
+                    dout = torch.zeros(nchw, dtype=_F32, device=dtm.device)
+                g = torch.empty((R, cout), dtype=_F32, device=dout.device)
+                dout_c, dtm_c = dout.contiguous(), (None if dtm is None else dtm.contiguous())
+                link = _relayout_bnstats(lib, dout_c, dtm_c, g, Y, mean, invstd, a, c, nchw[0], cout, R)
+            elif dout is None:
                 g = dtm.contiguous()
             elif dtm is None:
                 g = torch.empty((R, cout), dtype=_F32, device=dout.device)
@@ -951,6 +1037,10 @@ class _LinearBNAct(torch.autograd.Function):
                 _lib.check(lib.gkg_nchw_to_tm_add(_ptr(dout_c), _ptr(dtm_c), _ptr(g), nchw[0], cout, R // nchw[0], _stream()),
                            "gkg_nchw_to_tm_add")
             dres = g
+        elif nchw is not None and _bwd_fuse_ok(mean, ctx.sync, ctx.scale[0], 1, cout):
+            g = torch.empty((R, cout), dtype=_F32, device=dout.device)
+            dout_c = dout.contiguous()
+            link = _relayout_bnstats(lib, dout_c, None, g, Y, mean, invstd, a, c, nchw[0], cout, R)
         elif nchw is not None:
             g = torch.empty((R, cout), dtype=_F32, device=dout.device)
             dout_c = dout.contiguous()           # named: the copy must outlive the launch that reads it
@@ -976,7 +1066,7 @@ class _LinearBNAct(torch.autograd.Function):
             _bn_eval_backward(lib, g, Y, a, c, dY, bn, bias, dgamma, dbeta, dbias, R, cout, 1, cout, 0, act,
                               *(row_scale if row_scale is not None else (None, 0)))
         else:
-            _bn_backward(lib, g, Y, a, c, mean, invstd, dY, dgamma, dbeta, R, cout, 1, cout, 0, act, ctx.sync, ctx.link,
+            _bn_backward(lib, g, Y, a, c, mean, invstd, dY, dgamma, dbeta, R, cout, 1, cout, 0, act, ctx.sync, link,
                          *(row_scale if row_scale is not None else (None, 0)))
         W = weight.view(cout, cin)
         if not ctx.needs_input_grad[0]:
@@ -1435,6 +1525,7 @@ class _MaxRelativeTM(torch.autograd.Function):
                                          mode, code, ak, _stream()), "gkg_mr_fwd_tm")
         ctx.save_for_backward(nn_idx, arg)
         ctx.meta = (B, G, C, N, M, k, mode, src is not None, ak, tuple(x.shape))
+        ctx.bn_link = getattr(x, "_gkg_mr_bn_link", None) if (need and mode == 1) else None      # see _mr_bwd
         return out
 
     @staticmethod
@@ -1443,11 +1534,8 @@ class _MaxRelativeTM(torch.autograd.Function):
         nn_idx, arg = ctx.saved_tensors
         B, G, C, N, M, k, mode, has_src, ak, xshape = ctx.meta
         g = g.contiguous()
-        gx = torch.empty((B, N, C), dtype=_F32, device=g.device)
-        gsrc = torch.empty((B, M, C), dtype=_F32, device=g.device) if has_src else None
-        _lib.check(lib.gkg_mr_bwd_tm(_ptr(g), _ptr(nn_idx), _ptr(arg), _ptr(gx), _ptr(gsrc), B, G, C // G, N, M, k, mode, ak,
-                                     _mr_bwd_flags(), _stream()), "gkg_mr_bwd_tm")
-        return gx.view(xshape), gsrc, None, None, None, None
+        gxv, gsrc = _mr_bwd(lib, g, nn_idx, arg, B, G, C, N, M, k, mode, ak, has_src, xshape, ctx.bn_link)
+        return gxv, gsrc, None, None, None, None
 
 
 # ----------------------------------------------------------------------------------------------- row g2: k-NN + aggregation
@@ -1486,6 +1574,7 @@ class _KnnMaxRelativeTM(torch.autograd.Function):
                                          N, M, k, d, flags, _ptr(ws), ws.numel(), _stream()), "gkg_knn_mr_fwd_tm")
         ctx.save_for_backward(arg)
         ctx.meta = (B, G, C, N, M, k, src is not None, tuple(x.shape))
+        ctx.bn_link = getattr(x, "_gkg_mr_bn_link", None)                  # see _mr_bwd
         ctx.mark_non_differentiable(edge)
         ctx.set_materialize_grads(False)          # (no zero-filled int64 "gradient" of the graph output: 4.8 us per step)
         return XM, edge
@@ -1498,11 +1587,8 @@ class _KnnMaxRelativeTM(torch.autograd.Function):
         if g is None:
             return (None,) * 7
         g = g.contiguous()
-        gx = torch.empty((B, N, C), dtype=_F32, device=g.device)
-        gsrc = torch.empty((B, M, C), dtype=_F32, device=g.device) if has_src else None
-        _lib.check(lib.gkg_mr_bwd_tm(_ptr(g), None, _ptr(arg), _ptr(gx), _ptr(gsrc), B, G, C // G, N, M, k, 1, 1, _mr_bwd_flags(),
-                                     _stream()), "gkg_mr_bwd_tm")
-        return gx.view(xshape), gsrc, None, None, None, None, None
+        gxv, gsrc = _mr_bwd(lib, g, None, arg, B, G, C, N, M, k, 1, 1, has_src, xshape, ctx.bn_link)
+        return gxv, gsrc, None, None, None, None, None
 
 
 def _knn_mr_shapes_ok(B, N, C, M, has_src, relative_pos, k, d, G, nn_, lp) -> bool:

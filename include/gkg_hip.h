@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define GKG_ABI_VERSION 9
+#define GKG_ABI_VERSION 10
 
 /* dtype codes */
 #define GKG_F32 0
@@ -287,6 +287,18 @@ int gkg_mr_fwd_tm(const float* x, int ldx, int xchunk, const float* src, const i
 #define GKG_MR_FP32_ATOMICS 2u  /* keep the fp32 LDS-atomic scatter instead of the exact integer accumulation (measurement, tests) */
 int gkg_mr_bwd_tm(const float* gin, const int64_t* nn_idx, const uint8_t* argmax, float* gx, float* gsrc,
                   int B, int G, int c, int N, int M, int k, int mode, int arg_kind, unsigned flags, void* stream);
+/* gkg_mr_bwd_tm that is also the STATISTICS pass of the BN backward whose upstream gradient gx is (the layer x = BN(y) in front of
+ * the aggregation; un-grouped, no activation): y (B*N, C), mean / invstd [C]; sums [2][C] fp64, ZERO on entry, receives sum gx
+ * and sum gx * yhat with atomics, what gkg_bn_bwd_atomic's first launch would leave there — follow it with
+ * gkg_bn_bwd_apply_from_sums.  gx / gsrc: the bits of gkg_mr_bwd_tm.  Returns GKG_ERR_UNSUPPORTED, with nothing launched, when
+ * the shape or the flags select a scatter form that carries no statistics (mode 0, forced forms, fp32 atomics, destination images
+ * beyond the LDS forms): run gkg_mr_bwd_tm and gkg_bn_bwd_atomic then. */
+int gkg_mr_bwd_tm_bnstats(const float* gin, const int64_t* nn_idx, const uint8_t* argmax, float* gx, float* gsrc,
+                          int B, int G, int c, int N, int M, int k, int mode, int arg_kind, unsigned flags,
+                          const float* y, const float* mean, const float* invstd, double* sums, void* stream);
+/* 1 when gkg_mr_bwd_tm_bnstats would run for these sizes and flags, 0 when it would return GKG_ERR_UNSUPPORTED (pure host code:
+ * for callers that book their scratch buffer before the call). */
+int gkg_mr_bwd_tm_bnstats_supported(int B, int G, int c, int N, int M, int k, int mode, int arg_kind, int self_graph, unsigned flags);
 
 /* ------------------------------------------------------------------------------------------------
  * SURVEY §8 row g1, inference: the aggregation as the OPERAND PRODUCER of the grouped 1x1 projection.
@@ -330,6 +342,12 @@ int gkg_tm_affine_to_nchw(const float* y, const float* a, const float* c, const 
 int gkg_tm_affine_to_nchw_dual(const float* y, const float* a, const float* c, const float* res_tm, float* out, float* out_tm,
                                int B, int C, int N, void* stream);
 int gkg_nchw_to_tm_add(const float* x, const float* add_tm, float* out, int B, int C, int N, void* stream);
+/* The same pass (add_tm may be NULL: gkg_nchw_to_tm's fp32 form) as the STATISTICS pass of the BN backward whose upstream
+ * gradient it writes (un-grouped layer, no activation): y (B*N, C) that layer's pre-BN output, mean / invstd [C]; sums [2][C]
+ * fp64, ZERO on entry, receives sum out and sum out * yhat with atomics — follow it with gkg_bn_bwd_apply_from_sums.  `out` has
+ * the bits of gkg_nchw_to_tm_add / gkg_nchw_to_tm. */
+int gkg_nchw_to_tm_add_bnstats(const float* x, const float* add_tm, float* out, const float* y, const float* mean,
+                               const float* invstd, double* sums, int B, int C, int N, void* stream);
 size_t gkg_bn_workspace_bytes(int R, int C, int nb);
 /* Train-mode batch statistics of y (R,C) (conv bias NOT included in y; it is folded: it cancels in the output and
  * is added to running_mean).  Writes scale a, shift c (out = a*y + c), saved mean / invstd; updates running stats
@@ -508,6 +526,13 @@ int gkg_linear_bn_fwd_x6_sk(const float* x, int ldx, size_t x_bstride, const voi
 int gkg_linear_dgrad_x6_sk(const float* dy, int ldg, size_t g_bstride, const void* planes_dgrad, float* dx, int R, int cin,
                            int cout, int nb, const float* residual, void* splitk_ws, size_t splitk_bytes, int ldx,
                            size_t x_bstride, unsigned flags, void* stream);
+/* The un-grouped input gradient stored CHANNEL-MAJOR: dx (B, cin, N) = per image (dy w + residual)^T, R == B * N rows, residual
+ * (R, cin) token-major or NULL — the bits of gkg_linear_dgrad_x6_sk + gkg_tm_affine_to_nchw in one launch.  The 128-row tile
+ * kernel stores so itself when N % 4 == 0; a shape that takes another body (few rows with a split-K workspace, 80 columns,
+ * N % 4 != 0) runs those two launches through dx_tm (R, cin; scratch, always required). */
+int gkg_linear_dgrad_x6_nchw(const float* dy, int ldg, const void* planes_dgrad, float* dx, float* dx_tm, int R, int cin, int cout,
+                             const float* residual, int B, int N, void* splitk_ws, size_t splitk_bytes, unsigned flags,
+                             void* stream);
 /* dw (nb, cout, cin) += dy^T x over the R rows (both operands split in registers; no LDS staging, each wave streams its own
  * rows).  dw must be ZERO on entry: slabs of rows are added with fp32 atomics (run-dependent summation order, like a
  * split-K GEMM).  x (nb, R, cin) with row pitch ldx / batch stride x_bstride (floats).  Any cin, cout >= 1. */
@@ -570,6 +595,10 @@ int gkg_bn_bwd_apply_from_sums(const float* dout, const float* y, const float* a
  * Weight gradients: the backward calls FILL wq[] (3 / 5 problems, in backward order) for gkg_linear_wgrad_x6_batch; the caller
  * launches them at once or queues them with the rest of its backward pass (operands: dY buffers and saved activations must stay
  * valid until then). */
+/* bwd_flags: the backward calls take the BN backward statistics of fc2 (Grapher) and fc1 inside the kernels that produce those
+ * layers' upstream gradients (gkg_nchw_to_tm_add_bnstats, gkg_mr_bwd_tm_bnstats) and store a Grapher's dx from the GEMM
+ * (gkg_linear_dgrad_x6_nchw); GKG_BLOCK_NO_BWD_FUSE keeps the stand-alone statistics and re-layout launches. */
+#define GKG_BLOCK_NO_BWD_FUSE 1u
 typedef struct GkgProjBN {
   const void* planes_fwd; const void* planes_dgrad;
   const float* gamma; const float* beta; const float* bias;
@@ -599,6 +628,7 @@ typedef struct GkgGrapherBlock {
   /* backward */
   const float* dout; const float* dout_tm; float* dx;
   float* g3; float* dY3; float* dA2; float* dY2; float* dXM; float* gx1; float* dY1; float* dxt;
+  unsigned bwd_flags;                                         /* GKG_BLOCK_* */
 } GkgGrapherBlock;
 typedef struct GkgLabelBlock {
   int B, C, L, M;
@@ -610,6 +640,7 @@ typedef struct GkgLabelBlock {
   /* backward */
   const float* dout; float* de; float* dft;
   float* dY5; float* df1; float* dY4; float* dh2; float* dY3; float* dA2; float* dY2; float* dXM; float* gx1; float* dY1;
+  unsigned bwd_flags;                                         /* GKG_BLOCK_* */
 } GkgLabelBlock;
 int gkg_grapher_fwd(const GkgGrapherBlock* b, void* stream);
 int gkg_grapher_bwd(const GkgGrapherBlock* b, GkgWgradProblem* wq /* [3] */, void* stream);
