@@ -10,7 +10,7 @@ import os
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GKG_HIP_LIB") or os.path.join(PKG, "libgkg_hip.so")   # GKG_HIP_LIB: same-box A/B of two builds (tools)
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 F32, BF16, F16 = 0, 1, 2
 KNN_NORMALIZE = 1
 KNN_BF16_CONTRACT = 2
@@ -70,7 +70,7 @@ MR_DETERMINISTIC = 1
 MR_FP32_ATOMICS = 2
 X6_NO_KS, X6_FORCE_KS = 1, 2
 ERR_UNSUPPORTED = -3
-BLOCK_NO_BWD_FUSE = 1
+BLOCK_NO_BWD_FUSE, BLOCK_NO_DGRAD_STATS = 1, 2
 
 EXPORTS = ("gkg_version", "gkg_last_error_string", "gkg_knn_workspace_bytes", "gkg_knn_fwd", "gkg_mr_fwd",
            "gkg_mr_bwd", "gkg_prof_enable", "gkg_prof_reset", "gkg_prof_read", "gkg_prof_work", "gkg_knn_fwd_tm", "gkg_mr_fwd_tm",
@@ -89,7 +89,7 @@ EXPORTS = ("gkg_version", "gkg_last_error_string", "gkg_knn_workspace_bytes", "g
            "gkg_grapher_fwd", "gkg_grapher_bwd", "gkg_grapher_label_fwd", "gkg_grapher_label_bwd",
            "gkg_gconv_workspace_bytes", "gkg_gin_fwd", "gkg_gin_bwd", "gkg_gat_fwd", "gkg_gat_bwd",
            "gkg_bn_eval_bwd", "gkg_nchw_to_tm_add_bnstats", "gkg_mr_bwd_tm_bnstats", "gkg_linear_dgrad_x6_nchw",
-           "gkg_mr_bwd_tm_bnstats_supported")
+           "gkg_mr_bwd_tm_bnstats_supported", "gkg_linear_dgrad_x6_bnbwd_sk", "gkg_linear_dgrad_x6_bnbwd_sk_supported")
 PROF_KERNELS = ("token_prep", "knn_tile", "knn_merge", "mr_fwd", "mr_bwd", "gemm_x6")
 
 _lib = None
@@ -242,6 +242,10 @@ def load():
     lib.gkg_x6_splitk_workspace_bytes.argtypes = []
     lib.gkg_linear_bn_fwd_x6_sk.restype = I
     lib.gkg_linear_bn_fwd_x6_sk.argtypes = [V, I, Z, V, V, I, I, I, I, I] + [V] * 10 + [F, F, V, V, Z, C.c_uint, V]
+    lib.gkg_linear_dgrad_x6_bnbwd_sk.restype = I
+    lib.gkg_linear_dgrad_x6_bnbwd_sk.argtypes = [V, I, V, V, I, I, I, V] + [V] * 6 + [I, I, I, V, Z, C.c_uint, V]
+    lib.gkg_linear_dgrad_x6_bnbwd_sk_supported.restype = I
+    lib.gkg_linear_dgrad_x6_bnbwd_sk_supported.argtypes = [I, I, I, I, C.c_uint]
     lib.gkg_linear_dgrad_x6_sk.restype = I
     lib.gkg_linear_dgrad_x6_sk.argtypes = [V, I, Z, V, V, I, I, I, I, V, V, Z, I, Z, C.c_uint, V]
     lib.gkg_linear_wgrad_x6_batch.restype = I

@@ -439,7 +439,7 @@ class _GrapherBlockFn(torch.autograd.Function):
         dout_c = dout.contiguous()
         dtm_c = None if dtm is None else dtm.contiguous()
         d.dout, d.dout_tm, d.dx = dout_c.data_ptr(), _ptr(dtm_c), dx.data_ptr()
-        d.bwd_flags = 0 if fused.BWD_FUSE else _lib.BLOCK_NO_BWD_FUSE
+        d.bwd_flags = fused._block_flags()
         scratch = fused._BnBwdScratch.of(dev)
         wq = (_lib.WgradProblem * 3)()
         p1, pc, p2 = plan.projs
@@ -548,7 +548,7 @@ class _LabelBlockFn(torch.autograd.Function):
         dft = torch.empty((B, M, Cc), dtype=_F32, device=dev)
         dout_c = dout.contiguous()
         d.dout, d.de, d.dft = dout_c.data_ptr(), de.data_ptr(), dft.data_ptr()
-        d.bwd_flags = 0 if fused.BWD_FUSE else _lib.BLOCK_NO_BWD_FUSE
+        d.bwd_flags = fused._block_flags()
         scratch = fused._BnBwdScratch.of(dev)
         wq = (_lib.WgradProblem * 5)()
         p1, pc, p3, p4, p5 = plan.projs

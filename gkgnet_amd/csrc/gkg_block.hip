@@ -47,6 +47,37 @@ int proj_bwd_apply(const GkgProjBN& p, const float* g, int R, float* dY, void* s
   return gkg_bn_bwd_apply_from_sums(g, p.Y, p.bn, p.bn + n, p.bn + 2 * n, p.bn + 3 * n, dY, p.dgamma, p.dbeta, R, p.cout, 1, p.cout, 0, 0,
                                     p.bsum, p.bzero, p.bzero_n, st);
 }
+// Round 9.  proj_dgrad with the backward statistics of the layer q IN FRONT (q's output, act(BN(q.Y)), is this projection's input,
+// so dx is q's upstream gradient) taken in the GEMM's epilogue into q.bsum, and the BN half of proj_bwd for such a layer: the
+// apply pass only, in the layout proj_bwd gives it (grouped: row pitch ldg, batch stride gbs).
+int proj_dgrad_stats(const GkgProjBN& p, const GkgProjBN& q, int qact, const float* dY, int R, const float* residual, float* dx,
+                     void* sk_ws, size_t sk_bytes, void* st) {
+  const int n = q.nb * q.cout;
+  return gkg_linear_dgrad_x6_bnbwd_sk(dY, p.cout, p.planes_dgrad, dx, R, p.cin, p.cout, residual, q.Y, q.bn, q.bn + n, q.bn + 2 * n,
+                                      q.bn + 3 * n, q.bsum, q.nb, q.cout, qact, sk_ws, sk_bytes, 0, st);
+}
+bool dgrad_stats_ok(const GkgProjBN& p, unsigned bwd_flags, int R, bool residual, const void* sk_ws) {
+  return !(bwd_flags & (GKG_BLOCK_NO_BWD_FUSE | GKG_BLOCK_NO_DGRAD_STATS)) && p.nb == 1 &&
+         gkg_linear_dgrad_x6_bnbwd_sk_supported(R, p.cin, residual ? 1 : 0, sk_ws ? 1 : 0, 0);
+}
+int proj_bwd_apply_at(const GkgProjBN& p, const float* g, int ldg, size_t gbs, int R, int act, float* dY, void* st) {
+  const int n = p.nb * p.cout;
+  return gkg_bn_bwd_apply_from_sums(g, p.Y, p.bn, p.bn + n, p.bn + 2 * n, p.bn + 3 * n, dY, p.dgamma, p.dbeta, R, p.cout, p.nb, ldg, gbs,
+                                    act, p.bsum, p.bzero, p.bzero_n, st);
+}
+// proj_bwd of layer p whose statistics came with its upstream gradient (`have`) and whose own input gradient takes those of the
+// layer q in front (`give`; q == nullptr: none)
+int proj_bwd_chain(const GkgProjBN& p, bool have, const GkgProjBN* q, bool give, int qact, const float* g, int ldg, size_t gbs, int R,
+                   int act, float* dY, const float* residual, float* dx, int ldx, size_t x_bstride, void* sk_ws, size_t sk_bytes,
+                   void* st) {
+  const int n = p.nb * p.cout;
+  if (have) GKG_TRY(proj_bwd_apply_at(p, g, ldg, gbs, R, act, dY, st));
+  else GKG_TRY(gkg_bn_bwd_atomic(g, p.Y, p.bn, p.bn + n, p.bn + 2 * n, p.bn + 3 * n, dY, p.dgamma, p.dbeta, R, p.cout, p.nb, ldg, gbs, act,
+                                 p.bsum, p.bzero, p.bzero_n, st));
+  if (give && q) return proj_dgrad_stats(p, *q, qact, dY, R, residual, dx, sk_ws, sk_bytes, st);
+  return gkg_linear_dgrad_x6_sk(dY, p.cout, (size_t)R * p.cout, p.planes_dgrad, dx, R, p.cin, p.cout, p.nb, residual, sk_ws, sk_bytes, ldx,
+                                x_bstride, 0, st);
+}
 int proj_dgrad(const GkgProjBN& p, const float* dY, int R, const float* residual, float* dx, void* sk_ws, size_t sk_bytes, void* st) {
   return gkg_linear_dgrad_x6_sk(dY, p.cout, (size_t)R * p.cout, p.planes_dgrad, dx, R, p.cin, p.cout, p.nb, residual, sk_ws, sk_bytes, 0, 0, 0, st);
 }
@@ -141,18 +172,22 @@ extern "C" int gkg_grapher_bwd(const GkgGrapherBlock* b, GkgWgradProblem* wq, vo
   // the output's gradient(s) token-major; it is also the residual branch's gradient
   // (round 8, unless GKG_BLOCK_NO_BWD_FUSE: the re-layout pass takes fc2's BN backward statistics, the scatter takes fc1's, and
   // fc1's input-gradient GEMM stores dx channel-major — four launches fewer)
+  // (round 9, unless GKG_BLOCK_NO_DGRAD_STATS: fc2's input-gradient GEMM takes the grouped projection's — one launch fewer)
   const bool fuse = !(b->bwd_flags & GKG_BLOCK_NO_BWD_FUSE);
+  const bool conv_stats = dgrad_stats_ok(b->fc2, b->bwd_flags, T, false, b->sk_ws);
   if (fuse) {
     GKG_TRY(gkg_nchw_to_tm_add_bnstats(b->dout, b->dout_tm, b->g3, b->fc2.Y, b->fc2.bn + 2 * C, b->fc2.bn + 3 * C, b->fc2.bsum, B, C, N, st));
     GKG_TRY(proj_bwd_apply(b->fc2, b->g3, T, b->dY3, st));
-    GKG_TRY(proj_dgrad(b->fc2, b->dY3, T, nullptr, b->dA2, b->sk_ws, b->sk_bytes, st));
+    if (conv_stats) GKG_TRY(proj_dgrad_stats(b->fc2, b->conv, 1, b->dY3, T, nullptr, b->dA2, b->sk_ws, b->sk_bytes, st));
+    else GKG_TRY(proj_dgrad(b->fc2, b->dY3, T, nullptr, b->dA2, b->sk_ws, b->sk_bytes, st));
   } else {
     if (b->dout_tm) GKG_TRY(gkg_nchw_to_tm_add(b->dout, b->dout_tm, b->g3, B, C, N, st));
     else GKG_TRY(gkg_nchw_to_tm(b->dout, b->g3, B, C, N, GKG_F32, nullptr, st));
     GKG_TRY(proj_bwd(b->fc2, b->g3, C, 0, T, 0, b->dY3, nullptr, b->dA2, 0, 0, b->sk_ws, b->sk_bytes, st));
   }
   wgrad_entry(wq[0], b->fc2, b->dY3, b->A2, 2 * C, (size_t)T * 2 * C, T, 0);
-  GKG_TRY(proj_bwd(b->conv, b->dA2, 2 * C, (size_t)(C / 2), T, 1, b->dY2, nullptr, b->dXM, 2 * C, (size_t)(C / 2), b->sk_ws, b->sk_bytes, st));
+  GKG_TRY(proj_bwd_chain(b->conv, conv_stats, nullptr, false, 0, b->dA2, 2 * C, (size_t)(C / 2), T, 1, b->dY2, nullptr, b->dXM, 2 * C,
+                         (size_t)(C / 2), b->sk_ws, b->sk_bytes, st));
   wgrad_entry(wq[1], b->conv, b->dY2, b->XM, 2 * C, (size_t)(C / 2), T, 1);
   const GkgGraphOp& g = b->graph;
   GKG_TRY(mr_bwd_bn(b->fc1, g, fuse, b->dXM, b->gx1, nullptr, B, C, N, N, b->dY1, st));
@@ -204,13 +239,19 @@ extern "C" int gkg_grapher_label_bwd(const GkgLabelBlock* b, GkgWgradProblem* wq
     return gkg_fail(GKG_ERR_NULL, "gkg_grapher_label_bwd: null pointer");
   const int B = b->B, C = b->C, L = b->L, M = b->M, T = B * L, Cf = b->ffn1.cout;
   const GkgGraphOp& g = b->graph;
-  GKG_TRY(proj_bwd(b->ffn2, b->dout, C, 0, T, 0, b->dY5, nullptr, b->df1, 0, 0, b->sk_ws, b->sk_bytes, st));
+  // (round 9, unless GKG_BLOCK_NO_DGRAD_STATS: each input-gradient GEMM of the chain ffn2 -> ffn1 -> fc2 -> conv takes the backward
+  // statistics of the layer in front of it, whose BN backward is then its apply pass — three launches fewer)
+  const bool s4 = dgrad_stats_ok(b->ffn2, b->bwd_flags, T, false, b->sk_ws), s3 = dgrad_stats_ok(b->ffn1, b->bwd_flags, T, true, b->sk_ws),
+             s2 = dgrad_stats_ok(b->fc2, b->bwd_flags, T, false, b->sk_ws);
+  GKG_TRY(proj_bwd_chain(b->ffn2, false, &b->ffn1, s4, 1, b->dout, C, 0, T, 0, b->dY5, nullptr, b->df1, 0, 0, b->sk_ws, b->sk_bytes, st));
   wgrad_entry(wq[0], b->ffn2, b->dY5, b->f1, Cf, (size_t)T * Cf, T, 0);
-  GKG_TRY(proj_bwd(b->ffn1, b->df1, Cf, 0, T, 1, b->dY4, b->dout, b->dh2, 0, 0, b->sk_ws, b->sk_bytes, st));      // + the FFN residual's gradient
+  GKG_TRY(proj_bwd_chain(b->ffn1, s4, &b->fc2, s3, 0, b->df1, Cf, 0, T, 1, b->dY4, b->dout, b->dh2, 0, 0, b->sk_ws, b->sk_bytes,
+                         st));                                                                                     // + the FFN residual's gradient
   wgrad_entry(wq[1], b->ffn1, b->dY4, b->h2, C, (size_t)T * C, T, 0);
-  GKG_TRY(proj_bwd(b->fc2, b->dh2, C, 0, T, 0, b->dY3, nullptr, b->dA2, 0, 0, b->sk_ws, b->sk_bytes, st));
+  GKG_TRY(proj_bwd_chain(b->fc2, s3, &b->conv, s2, 1, b->dh2, C, 0, T, 0, b->dY3, nullptr, b->dA2, 0, 0, b->sk_ws, b->sk_bytes, st));
   wgrad_entry(wq[2], b->fc2, b->dY3, b->A2, 2 * C, (size_t)T * 2 * C, T, 0);
-  GKG_TRY(proj_bwd(b->conv, b->dA2, 2 * C, (size_t)(C / 2), T, 1, b->dY2, nullptr, b->dXM, 2 * C, (size_t)(C / 2), b->sk_ws, b->sk_bytes, st));
+  GKG_TRY(proj_bwd_chain(b->conv, s2, nullptr, false, 0, b->dA2, 2 * C, (size_t)(C / 2), T, 1, b->dY2, nullptr, b->dXM, 2 * C, (size_t)(C / 2),
+                         b->sk_ws, b->sk_bytes, st));
   wgrad_entry(wq[3], b->conv, b->dY2, b->XM, 2 * C, (size_t)(C / 2), T, 1);
   GKG_TRY(mr_bwd_bn(b->fc1, g, !(b->bwd_flags & GKG_BLOCK_NO_BWD_FUSE), b->dXM, b->gx1, b->dft, B, C, L, M, b->dY1, st));
   GKG_TRY(proj_dgrad(b->fc1, b->dY1, T, b->dh2, b->de, b->sk_ws, b->sk_bytes, st));                                // + the block residual's gradient

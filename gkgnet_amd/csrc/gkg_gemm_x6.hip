@@ -726,6 +726,23 @@ __global__ __launch_bounds__(256, MI == 1 ? 2 : 1) void gemm_x6_ks_kernel(X6Args
         const int row = 32 * mi + (q & 3) + 8 * (q >> 2) + 4 * h;
         red[(w * BM + row) * BN + j * 32 + r] = acc[mi][j][q] + accs[mi][j][q];
       }
+  // X6_BNBWD (see X6Args): thread tid sums column tid & 63 over rows (tid >> 6) + 4 u below; the producer's y values at those
+  // places are fetched ahead of the barrier, so that their latency overlaps the other waves' arrival
+  float yv[EPI == X6_BNBWD ? 8 * MI : 1];
+  float pav = 0.f, pcv = 0.f, pmv = 0.f, piv = 0.f, s0 = 0.f, s1 = 0.f;
+  if constexpr (EPI == X6_BNBWD) {
+    const int n = n0 + (tid & 63);
+#pragma unroll
+    for (int u = 0; u < 8 * MI; ++u) yv[u] = 0.f;
+    if (n < N) {
+      const int pq = n / g.pco, pi = n - pq * g.pco;
+      pav = g.pa[n]; pcv = g.pc[n]; pmv = g.pmean[n]; piv = g.pinvstd[n];
+      const float* yp = g.py + ((size_t)pq * M + m0 + (tid >> 6)) * (size_t)g.pco + pi;
+#pragma unroll
+      for (int u = 0; u < 8 * MI; ++u)
+        if (m0 + (tid >> 6) + 4 * u < M) yv[u] = yp[(size_t)(4 * u) * g.pco];
+    }
+  }
   __syncthreads();
   float* C = g.C + (size_t)z * g.c_bstride;
   float v[8 * MI];
@@ -736,9 +753,33 @@ __global__ __launch_bounds__(256, MI == 1 ? 2 : 1) void gemm_x6_ks_kernel(X6Args
     const int m = m0 + row, n = n0 + col;
     if (m < M && n < N) {
       float o = v[u];
-      if (EPI == X6_STORE && g.add) o += g.add[(size_t)z * g.c_bstride + (size_t)m * g.ldc + n];
+      if ((EPI == X6_STORE || EPI == X6_BNBWD) && g.add) o += g.add[(size_t)z * g.c_bstride + (size_t)m * g.ldc + n];
       C[(size_t)m * g.ldc + n] = o;
+      if constexpr (EPI == X6_BNBWD) {                 // the BN's upstream gradient is the stored value, residual included
+        float dz = o;
+        if (g.pact == 1) dz *= gelu_grad_f(__builtin_fmaf(pav, yv[u], pcv));
+        s0 += dz;
+        s1 += dz * ((yv[u] - pmv) * piv);
+      }
     }
+  }
+  if constexpr (EPI == X6_BNBWD) {
+    // the four waves' partial column sums (8 rows each) meet in LDS and are added in fp64: ONE atomic pair per column and
+    // workgroup, like the statistics below
+    __syncthreads();                                   // every thread has read its partials
+    red[((tid >> 6) * BN + (tid & 63)) * 2] = s0;
+    red[((tid >> 6) * BN + (tid & 63)) * 2 + 1] = s1;
+    __syncthreads();
+    if (tid < BN && n0 + tid < N) {
+      double t0 = 0.0, t1 = 0.0;
+#pragma unroll
+      for (int rg = 0; rg < 4; ++rg) { t0 += (double)red[(rg * BN + tid) * 2]; t1 += (double)red[(rg * BN + tid) * 2 + 1]; }
+      const int n = n0 + tid, pq = n / g.pco, pi = n - pq * g.pco;
+      double* sz = g.psums + (size_t)pq * 2 * g.pco + pi;
+      __hip_atomic_fetch_add(sz, t0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_fetch_add(sz + g.pco, t1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    return;
   }
   if (EPI != X6_BNSTATS) return;
   // train-mode BN statistics of the tile's columns: the summed tile back into LDS, one thread per column takes the centred
@@ -787,6 +828,13 @@ static hipError_t x6_launch_ks(X6Args a, int nb, hipStream_t st) {
 constexpr size_t X6_SK_CNT_BYTES = 4096, X6_SK_MAX_WG = 512;
 constexpr size_t X6_SK_BYTES = X6_SK_CNT_BYTES + X6_SK_MAX_WG * (size_t)(2 * 16 * 256 * 4);
 
+// The rule for the short-matrix body (gemm_x6_ks_kernel; measured in x6_launch's comment below) — ONE predicate for the launch and
+// for the entry points that must know beforehand which body a shape takes.
+static bool x6_ks_form(int M, int N, int nb, bool has_ws, unsigned flags) {
+  return has_ws && !(flags & GKG_X6_NO_KS) && M <= 4096 && (long long)((M + 31) / 32) * ((N + 63) / 64) * nb <= 65535 * 8 &&
+         ((flags & GKG_X6_FORCE_KS) || (nb == 1 && N <= 640));
+}
+
 template <int EPI>
 static hipError_t x6_launch(X6Args a, int nb, hipStream_t st, void* sk_ws = nullptr, size_t sk_bytes = 0, unsigned flags = 0) {
   GkgProfScope prof(GKG_PROF_GEMM_X6, st, 2.0 * a.M * a.N * a.K * nb);
@@ -805,15 +853,16 @@ static hipError_t x6_launch(X6Args a, int nb, hipStream_t st, void* sk_ws = null
   // where every 32-row workgroup re-reads a wide B (320 -> 1280: 30.0 vs 22.4, its transpose 27.3 vs 21.3: 196 MB of plane
   // traffic) and on the grouped 4 x (160 -> 160) products (15.5 vs 13.5).  Rule: un-grouped, at most 640 output columns.
   // The caller's `flags` (GKG_X6_NO_KS / GKG_X6_FORCE_KS: measurement, tests) override the rule per call.
-  if constexpr (EPI != X6_BNBWD && EPI != X6_STORE_NCHW) {
-    if (sk_ws && !(flags & GKG_X6_NO_KS) && a.M <= 4096 && (long long)((a.M + 31) / 32) * ((a.N + 63) / 64) * nb <= 65535 * 8 &&
-        ((flags & GKG_X6_FORCE_KS) || (nb == 1 && a.N <= 640))) {
+  // (X6_BNBWD comes here with a workspace only from gkg_linear_dgrad_x6_bnbwd_sk, which wants the body — and so the bits of dx —
+  // that X6_STORE takes for the same shape)
+  if constexpr (EPI != X6_STORE_NCHW) {
+    if (x6_ks_form(a.M, a.N, nb, sk_ws != nullptr, flags)) {
       // (64-row tiles — half the plane traffic, one wave per SIMD — measured no better on the long contractions they were built
       // for: 2 560 x 1280 -> 320 26.8 vs 24.3 us; what bounds those launches is the wave-serial K loop, not the B planes)
       return x6_launch_ks<EPI, 1>(a, nb, st);
     }
   }
-  if (sk_ws && sk_bytes >= X6_SK_BYTES && base2 < 320 && base2 <= 1024 && nk_total >= 8 && EPI != X6_BNBWD) {
+  if (sk_ws && sk_bytes >= X6_SK_BYTES && base2 < 320 && base2 <= 1024 && nk_total >= 8) {
     int ks = (int)(X6_SK_MAX_WG / base2);
     if (ks > nk_total / 4) ks = nk_total / 4;
     if (ks > 8) ks = 8;
@@ -825,11 +874,16 @@ static hipError_t x6_launch(X6Args a, int nb, hipStream_t st, void* sk_ws = null
       return x6_launch_ni<2, EPI>(a, nb, st);
     }
   }
+  if constexpr (EPI == X6_BNBWD) {
+    if (a.add) return hipErrorInvalidValue;              // the tile body's statistics epilogue takes no residual (never dropped silently)
+  }
   int ni = base2 < 160 ? 1 : 2;
   // 80 output columns on many rows (GKGNet-576 stage 1): ONE 80-column tile per row block instead of a full and a quarter
   // 64-column tile — 663 552 rows: 80 -> 80 171 -> 133 us, + statistics 208 -> 161, 320 -> 80 345 -> 279, dgrad 320 <- 80
   // 351 -> 279.  Wider outputs measured equal or slower on 80-column tiles (160: +-3 %, 320 / 400 / 640: 3-8 % slower:
   // profiles/r04_x6_80_column_tiles_ab.txt); the BN-backward epilogue's registers do not fit two waves per SIMD there.
+  // Round 9 tried them for the grouped 4 x (160 -> 160) products of cfg2 (10 368 rows: 648 workgroups instead of 972, fewer
+  // rounds of 512): the replayed step got 3-4 us SLOWER (profiles/r09_dgrad_stats_ab.txt) — not taken.
   if constexpr (EPI != X6_BNBWD && EPI != X6_STORE_NCHW) {
     if (a.N == 80 && ni == 2) return x6_launch_ni<3, EPI, 80>(a, nb, st);
   }
@@ -1587,8 +1641,7 @@ extern "C" int gkg_linear_dgrad_x6_nchw(const float* dy, int ldg, const void* pl
   if (splitk_ws && (splitk_bytes < X6_SK_BYTES || ((size_t)splitk_ws & 15)))
     return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_dgrad_x6_nchw: need a 16-byte aligned workspace of gkg_x6_splitk_workspace_bytes() bytes (or NULL: no split)");
   // x6_launch's rule for the short-matrix body (which has no channel-major store)
-  const bool ks_form = splitk_ws && !(flags & GKG_X6_NO_KS) && R <= 4096 && (long long)((R + 31) / 32) * ((cin + 63) / 64) <= 65535 * 8 &&
-                       ((flags & GKG_X6_FORCE_KS) || cin <= 640);
+  const bool ks_form = x6_ks_form(R, cin, 1, splitk_ws != nullptr, flags);
   const bool tile80 = cin == 80 && (long long)((R + 127) / 128) * ((cin + 63) / 64) >= 160;
   if ((N & 3) || ks_form || tile80 || ((size_t)dx & 15)) {
     const int rc = x6_dgrad_impl(dy, ldg, (size_t)R * cout, planes_dgrad, dx_tm, R, cin, cout, 1, residual, splitk_ws, splitk_bytes, stream, 0, 0, flags);
@@ -1614,24 +1667,51 @@ extern "C" int gkg_linear_dgrad_x6_nchw(const float* dy, int ldg, const void* pl
 // gradient of the layer  h = act(BN(py))  that made this projection's input; psums [pnb][2][pco] fp64 receives (atomics)
 // sum dz and sum dz * yhat per channel — what gkg_bn_bwd_atomic's statistics pass would compute from dx and py.  Un-grouped
 // projections only (nb == 1): dx (R, cin), cin == pnb * pco, py (pnb, R, pco).
+extern "C" int gkg_linear_dgrad_x6_bnbwd_sk(const float* dy, int ldg, const void* planes_dgrad, float* dx, int R, int cin, int cout,
+                                            const float* residual, const float* py, const float* pa, const float* pc,
+                                            const float* pmean, const float* pinvstd, double* psums, int pnb, int pco, int pact,
+                                            void* splitk_ws, size_t splitk_bytes, unsigned flags, void* stream);
 extern "C" int gkg_linear_dgrad_x6_bnbwd(const float* dy, int ldg, const void* planes_dgrad, float* dx, int R, int cin, int cout,
                                          const float* py, const float* pa, const float* pc, const float* pmean,
                                          const float* pinvstd, double* psums, int pnb, int pco, int pact, void* stream) {
+  // no workspace, no residual: always the 128-row tile body
+  return gkg_linear_dgrad_x6_bnbwd_sk(dy, ldg, planes_dgrad, dx, R, cin, cout, nullptr, py, pa, pc, pmean, pinvstd, psums, pnb, pco, pact,
+                                      nullptr, 0, 0, stream);
+}
+
+// gkg_linear_dgrad_x6_bnbwd with gkg_linear_dgrad_x6_sk's choice of kernel body (round 9): given the split-K workspace the launch
+// takes the short-matrix body / the cross-workgroup split exactly where gkg_linear_dgrad_x6_sk does for the same shape and flags,
+// so dx has that call's bits, and `residual` (R, cin; or NULL) is added in front of the statistics (the BN's upstream gradient is
+// the sum).  The 128-row tile body takes no residual here: gkg_linear_dgrad_x6_bnbwd_sk_supported() tells, and an unsupported
+// call returns GKG_ERR_UNSUPPORTED with nothing launched.
+extern "C" int gkg_linear_dgrad_x6_bnbwd_sk_supported(int R, int cin, int has_residual, int has_ws, unsigned flags) {
+  return (!has_residual || x6_ks_form(R, cin, 1, has_ws != 0, flags)) ? 1 : 0;
+}
+
+extern "C" int gkg_linear_dgrad_x6_bnbwd_sk(const float* dy, int ldg, const void* planes_dgrad, float* dx, int R, int cin, int cout,
+                                            const float* residual, const float* py, const float* pa, const float* pc,
+                                            const float* pmean, const float* pinvstd, double* psums, int pnb, int pco, int pact,
+                                            void* splitk_ws, size_t splitk_bytes, unsigned flags, void* stream) {
   if (!dy || !planes_dgrad || !dx || !py || !pa || !pc || !pmean || !pinvstd || !psums)
-    return gkg_fail(GKG_ERR_NULL, "gkg_linear_dgrad_x6_bnbwd: null pointer");
+    return gkg_fail(GKG_ERR_NULL, "gkg_linear_dgrad_x6_bnbwd_sk: null pointer");
+  if (splitk_ws && (splitk_bytes < X6_SK_BYTES || ((size_t)splitk_ws & 15)))
+    return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_dgrad_x6_bnbwd_sk: need a 16-byte aligned workspace of gkg_x6_splitk_workspace_bytes() bytes (or NULL: no split)");
   if (R <= 0 || x6_bad_dim(cin) || x6_bad_dim(cout) || ldg < cout || (ldg & 3) || ((size_t)dy & 15) || pnb <= 0 || pco <= 0 ||
       (long long)pnb * pco != cin || (pact != 0 && pact != 1))
-    return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_dgrad_x6_bnbwd: need R > 0, cin % 4 == 0, cout % 4 == 0, cin == pnb * pco, 16-byte aligned rows");
-  if ((size_t)R * ldg * 4 > 0xffffffffull) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_dgrad_x6_bnbwd: operand larger than 4 GiB");
+    return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_dgrad_x6_bnbwd_sk: need R > 0, cin % 4 == 0, cout % 4 == 0, cin == pnb * pco, 16-byte aligned rows");
+  if ((size_t)R * ldg * 4 > 0xffffffffull) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_dgrad_x6_bnbwd_sk: operand larger than 4 GiB");
+  if (residual && !x6_ks_form(R, cin, 1, splitk_ws != nullptr, flags))
+    return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_dgrad_x6_bnbwd_sk: a residual needs the short-matrix body");
   X6Args a{};
   a.A = dy; a.a_bstride = 0; a.lda = ldg;
   a.NP = (cin + X6_NPAD - 1) / X6_NPAD * X6_NPAD; a.KC = (cout + 31) / 32 * 4;
   a.P = (const uint4*)planes_dgrad; a.p_bstride = (size_t)3 * a.KC * a.NP;
   a.C = dx; a.c_bstride = (size_t)R * cin; a.ldc = cin;
   a.M = R; a.N = cin; a.K = cout;
+  a.add = residual;
   a.py = py; a.pa = pa; a.pc = pc; a.pmean = pmean; a.pinvstd = pinvstd; a.psums = psums; a.pco = pco; a.pact = pact;
-  hipError_t e = x6_launch<X6_BNBWD>(a, 1, (hipStream_t)stream);
-  return e == hipSuccess ? 0 : gkg_fail_hip(e, "gemm_x6_kernel (dgrad + BN backward statistics)");
+  hipError_t e = x6_launch<X6_BNBWD>(a, 1, (hipStream_t)stream, splitk_ws, splitk_bytes, flags);
+  return e == hipSuccess ? 0 : gkg_fail_hip(e, "gemm_x6 (dgrad + BN backward statistics)");
 }
 
 // dw (nb, cout, cin) += dy^T x over the R rows; dw must be ZERO on entry (the slabs of rows are added with fp32 atomics).

@@ -69,6 +69,8 @@ DETERMINISTIC = os.environ.get("GKG_DETERMINISTIC", "0") != "0"
 #   fold_epilogue  bf16 inference: eval-mode BN folded into the weights, bias (+ GELU) in the library GEMM's epilogue
 #   bwd_fuse       backward: BN statistics taken by the kernel that produces the gradient (re-layout pass, aggregation scatter),
 #                  a Grapher's dx stored channel-major by its input-gradient GEMM (BWD_FUSE below)
+#   dgrad_stats    backward: BN statistics taken by the input-gradient GEMM that writes the layer's upstream gradient, at every
+#                  size (DGRAD_STATS below; bwd_fuse off switches it off too)
 _DISABLED = _env_list("GKG_DISABLE")
 _ENABLED = _env_list("GKG_ENABLE")
 KNN_BF16 = "knn_bf16" in _ENABLED
@@ -702,6 +704,22 @@ BN_EPILOGUE_MIN_ROWS = 32768
 BWD_FUSE = "bwd_fuse" not in _DISABLED
 
 
+# Round 9: the same trade for the layers whose upstream gradient an input-gradient GEMM writes — the BN_EPILOGUE link above,
+# attached at EVERY size and served by gkg_linear_dgrad_x6_bnbwd_sk (the short-matrix body's epilogue carries the statistics too,
+# a residual is added in front of them, dx keeps the bits of the plain call): a block's grouped projection (from fc2's input
+# gradient) and a label block's FFN fc1 / fc2 (from the FFN fc2 / FFN fc1 input gradients, the latter with the FFN's residual).
+# Four stand-alone statistics launches fewer per cfg2 step; off with bwd_fuse, under GKG_DETERMINISTIC, SyncBN, frozen BN, a
+# DropPath scale and sums beyond the scratch (the conditions of _bn_link), and with GKG_DISABLE=dgrad_stats — BN_EPILOGUE_MIN_ROWS
+# then decides alone, as before.  The block driver folds the same four (GKG_BLOCK_NO_DGRAD_STATS: off).
+DGRAD_STATS = BWD_FUSE and "dgrad_stats" not in _DISABLED
+
+
+def _block_flags() -> int:
+    """GkgGrapherBlock / GkgLabelBlock.bwd_flags from the module switches."""
+    return ((0 if BWD_FUSE else _lib.BLOCK_NO_BWD_FUSE)
+            | (0 if (BWD_FUSE and DGRAD_STATS and BN_EPILOGUE) else _lib.BLOCK_NO_DGRAD_STATS))
+
+
 def _bwd_fuse_ok(mean, sync, scale, nb, co) -> bool:
     return (BWD_FUSE and mean is not None and sync is None and scale is None and not DETERMINISTIC and nb == 1
             and 2 * co <= _BnBwdScratch.DOUBLES)
@@ -755,8 +773,8 @@ class _BnLink:
 
 def _bn_link(out, Y, a, c, mean, invstd, act, nb, co, R, bn, sync, scale):
     """Hang a _BnLink on a token-major fp32 layer output (train-mode, rank-local statistics, atomics allowed)."""
-    if (BN_EPILOGUE and R >= BN_EPILOGUE_MIN_ROWS and mean is not None and sync is None and scale is None and not DETERMINISTIC
-            and out.dtype == _F32 and 2 * nb * co <= _BnBwdScratch.DOUBLES):
+    if (BN_EPILOGUE and (R >= BN_EPILOGUE_MIN_ROWS or (BWD_FUSE and DGRAD_STATS)) and mean is not None and sync is None
+            and scale is None and not DETERMINISTIC and out.dtype == _F32 and 2 * nb * co <= _BnBwdScratch.DOUBLES):
         link = _BnLink(Y, a, c, mean, invstd, act, nb, co, R)
         out._gkg_bn_link = link
         return link
@@ -780,15 +798,23 @@ def _relayout_bnstats(lib, dout_c, dtm_c, g, Y, mean, invstd, a, c, B, cout, R):
     return link
 
 
-def _dgrad_x6_with_link(lib, dY, pd, R, cin, cout, link):
-    """dx = dY W on the x6 kernel with the producer's BN backward statistics in the epilogue -> dx; leaves the sums on the link."""
+def _dgrad_with_link_ok(lib, R, cin, has_res) -> bool:
+    """Whether the statistics-carrying input gradient takes this call (a residual needs the short-matrix body)."""
+    return bool(lib.gkg_linear_dgrad_x6_bnbwd_sk_supported(R, cin, 1 if has_res else 0, 1, 0))
+
+
+def _dgrad_x6_with_link(lib, dY, pd, R, cin, cout, link, residual=None):
+    """dx = dY W (+ residual) on the x6 kernel with the producer's BN backward statistics in the epilogue -> dx (the bits of
+    _dgrad_x6); leaves the sums on the link."""
     scratch = _BnBwdScratch.of(dY.device)
     cur, other, zero = scratch.acquire(lib, 2 * link.nb * link.co)
     dx = torch.empty((R, cin), dtype=_F32, device=dY.device)
+    ws = _sk_ws(dY.device)
     try:
-        _lib.check(lib.gkg_linear_dgrad_x6_bnbwd(_ptr(dY), cout, _ptr(pd), _ptr(dx), R, cin, cout, _ptr(link.Y), _ptr(link.a),
-                                                 _ptr(link.c), _ptr(link.mean), _ptr(link.invstd), _ptr(cur), link.nb, link.co,
-                                                 link.act, _stream()), "gkg_linear_dgrad_x6_bnbwd")
+        _lib.check(lib.gkg_linear_dgrad_x6_bnbwd_sk(_ptr(dY), cout, _ptr(pd), _ptr(dx), R, cin, cout, _ptr(residual), _ptr(link.Y),
+                                                    _ptr(link.a), _ptr(link.c), _ptr(link.mean), _ptr(link.invstd), _ptr(cur),
+                                                    link.nb, link.co, link.act, _ptr(ws), ws.numel(), 0, _stream()),
+                   "gkg_linear_dgrad_x6_bnbwd_sk")
     except Exception:
         scratch.poison()
         raise
@@ -912,7 +938,8 @@ class _LinearBNAct(torch.autograd.Function):
         R, cin = x.shape
         cout = weight.shape[0]
         W = weight.view(cout, cin)
-        prev = None if alias else getattr(x, "_gkg_bn_link", None)       # the layer that produced x (see _BnLink)
+        # the layer that produced x (see _BnLink); with ``alias`` the input gradient carries the alias's too (DGRAD_STATS)
+        prev = None if (alias and not (BWD_FUSE and DGRAD_STATS)) else getattr(x, "_gkg_bn_link", None)
         x6f, x6d = _x6(x, weight, bn, 1, "fwd"), _x6(x, weight, bn, 1, "dgrad")
         own = x6f
         pf, pd = _planes(lib, weight, 1, cout, cin, x6f, x6d) if x6f or x6d else (None, None)
@@ -1073,6 +1100,14 @@ class _LinearBNAct(torch.autograd.Function):
             dx = None
         elif ctx.prev is not None and dalias is None:
             dx = _dgrad_x6_with_link(lib, dY, ctx.pd, R, cin, cout, ctx.prev)      # + the producer's BN backward statistics
+        # (with the skip gradient only where the short-matrix body runs, i.e. up to 4 096 rows and 640 columns: the tile body's
+        # statistics epilogue takes no residual.  Above that this branch is EXPECTED to miss: the plain input gradient below adds
+        # the residual, link.ready stays None and the producer runs its own statistics pass — as the block driver's
+        # dgrad_stats_ok does for the same shapes)
+        elif (ctx.prev is not None and dalias.dtype == _F32 and dalias.shape == (R, cin)
+              and _dgrad_with_link_ok(lib, R, cin, True)):
+            dx = _dgrad_x6_with_link(lib, dY, ctx.pd, R, cin, cout, ctx.prev, dalias.contiguous())      # + the skip gradient in front
+            dalias = None
         elif ctx.pd is not None:
             dx = torch.empty((R, cin), dtype=_F32, device=dY.device)
             res = dalias.contiguous() if (dalias is not None and dalias.dtype == _F32 and dalias.shape == dx.shape) else None

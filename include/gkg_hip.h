@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define GKG_ABI_VERSION 10
+#define GKG_ABI_VERSION 11
 
 /* dtype codes */
 #define GKG_F32 0
@@ -571,6 +571,17 @@ int gkg_linear_wgrad_x6_batch(const GkgWgradProblem* problems, int n, int units_
 int gkg_linear_dgrad_x6_bnbwd(const float* dy, int ldg, const void* planes_dgrad, float* dx, int R, int cin, int cout,
                               const float* py, const float* pa, const float* pc, const float* pmean, const float* pinvstd,
                               double* psums, int pnb, int pco, int pact, void* stream);
+/* The same with gkg_linear_dgrad_x6_sk's choice of kernel body (round 9): with the split-K workspace the launch takes the
+ * short-matrix body (whose epilogue then carries the statistics: one fp64 atomic pair per column and 32-row workgroup) or the
+ * cross-workgroup split exactly where gkg_linear_dgrad_x6_sk does for the same shape and flags, so dx has that call's bits;
+ * `residual` (R, cin) or NULL is added to dx in front of the statistics (the BN's upstream gradient is the sum).  The 128-row
+ * body takes no residual here: gkg_linear_dgrad_x6_bnbwd_sk_supported() -> 1 / 0 tells beforehand, and an unsupported call
+ * returns GKG_ERR_UNSUPPORTED with nothing launched. */
+int gkg_linear_dgrad_x6_bnbwd_sk_supported(int R, int cin, int has_residual, int has_ws, unsigned flags);
+int gkg_linear_dgrad_x6_bnbwd_sk(const float* dy, int ldg, const void* planes_dgrad, float* dx, int R, int cin, int cout,
+                                 const float* residual, const float* py, const float* pa, const float* pc, const float* pmean,
+                                 const float* pinvstd, double* psums, int pnb, int pco, int pact, void* splitk_ws,
+                                 size_t splitk_bytes, unsigned flags, void* stream);
 int gkg_bn_bwd_apply_from_sums(const float* dout, const float* y, const float* a, const float* c, const float* mean,
                                const float* invstd, float* dy, float* dgamma, float* dbeta, int R, int C, int nb, int ldg,
                                size_t dout_bstride, int act, const double* sums, double* zero_buf, size_t zero_doubles,
@@ -599,6 +610,11 @@ int gkg_bn_bwd_apply_from_sums(const float* dout, const float* y, const float* a
  * layers' upstream gradients (gkg_nchw_to_tm_add_bnstats, gkg_mr_bwd_tm_bnstats) and store a Grapher's dx from the GEMM
  * (gkg_linear_dgrad_x6_nchw); GKG_BLOCK_NO_BWD_FUSE keeps the stand-alone statistics and re-layout launches. */
 #define GKG_BLOCK_NO_BWD_FUSE 1u
+/* Round 9: the backward statistics of a layer whose upstream gradient an input-gradient GEMM writes — a block's grouped
+ * projection (from fc2's input gradient) and a label block's FFN fc1 and fc2 (from the FFN fc2 / FFN fc1 input gradients) — are
+ * taken in that GEMM's epilogue (gkg_linear_dgrad_x6_bnbwd_sk) and the layer runs its apply pass only: four launches fewer per
+ * block pair.  GKG_BLOCK_NO_DGRAD_STATS keeps the stand-alone statistics launches (GKG_BLOCK_NO_BWD_FUSE implies it). */
+#define GKG_BLOCK_NO_DGRAD_STATS 2u
 typedef struct GkgProjBN {
   const void* planes_fwd; const void* planes_dgrad;
   const float* gamma; const float* beta; const float* bias;
