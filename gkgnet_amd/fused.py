@@ -206,17 +206,28 @@ def _wq_open(task, device):
     return q
 
 
+def _wq_launch(q):
+    """Launch what is queued now (a cap was reached): the launch is stream-ordered behind the operands' producers and ahead of
+    their reuse, so the keep-alive references can go with it."""
+    items, q.items = q.items, []
+    if items:
+        _launch_wgrads(q, items)
+    q.keep, q.bytes = [], 0
+
+
 def _wq_push(q, problem, out, keep, nbytes):
+    """One problem into the queue; q.keep[i] is what keeps q.items[i]'s operands alive (the two lists have the same length)."""
     q.items.append(problem)
     q.keep.append(keep)
     owner = getattr(out, "_gkg_owner", None)
     if owner is not None:
         owner._gkg_deferred = True       # the slot, not p.grad, holds this gradient until the batch has run (GradBucket._resident)
     q.bytes += nbytes
+
+
+def _wq_cap(q):
     if len(q.items) >= q.MAX or q.bytes > q.MAX_BYTES:
-        items, q.items = q.items, []
-        _launch_wgrads(q, items)
-        q.keep, q.bytes = [], 0
+        _wq_launch(q)
 
 
 def _wgrad_defer(dY, x, out, R, cin, cout, nb, ldg, g_bs, ldx, x_bs, kperm=0) -> bool:
@@ -239,6 +250,7 @@ def _wgrad_defer(dY, x, out, R, cin, cout, nb, ldg, g_bs, ldx, x_bs, kperm=0) ->
         out.zero_()
     _wq_push(q, _lib.WgradProblem(dY.data_ptr(), x.data_ptr(), out.data_ptr(), g_bs, x_bs, ldg, ldx, R, cin, cout, nb, kperm), out,
              (dY, x), (dY.numel() + x.numel()) * 4)
+    _wq_cap(q)
     return True
 
 
@@ -252,8 +264,17 @@ def _wgrad_defer_block(problems, n, outs, keep, device) -> bool:
     if task < 0:
         return False
     q = _wq_open(task, device)
+    # The block's problems read ONE set of arenas (``keep``), so they enter the queue together: a launch forced by the cap happens
+    # before the first or after the last of them, never in between (it clears q.keep — the rest of the block would stay queued
+    # with nothing holding its operands), and every entry carries the keep tuple.
+    if q.items and len(q.items) + n > q.MAX:
+        _wq_launch(q)
     for i in range(n):
-        _wq_push(q, _lib.WgradProblem.from_buffer_copy(problems[i]), outs[i], keep if i == 0 else None, 0)
+        p = _lib.WgradProblem.from_buffer_copy(problems[i])
+        # operand bytes: this problem's (dY, x) pair, as _wgrad_defer counts it.  (The arenas in ``keep`` hold more than the
+        # operands, and problems of one block may share an x: the sum errs on the early side of MAX_BYTES, never the late one.)
+        _wq_push(q, p, outs[i], keep, 4 * p.nb * p.R * (p.cin + p.cout))
+    _wq_cap(q)
     return True
 
 

@@ -129,6 +129,36 @@ def test_b_relayout_pass_takes_the_bn_backward_statistics(B, C, N, with_add):
         assert _close(u, v), name
 
 
+@pytest.mark.parametrize("B,C,N", [(32, 320, 324), (5, 64, 129)])
+def test_b_the_two_pass_side_of_the_comparison_ends_at_fp64(B, C, N):
+    """Part B compares the fused form with gkg_nchw_to_tm_add + gkg_bn_bwd_atomic: kernel against kernel.  Here that two-launch side
+    is held to the fp64 reference (tests/dense_ref.py) under the bar of tests/test_hip_dense_fp64.py, and so is the fused side."""
+    from dense_ref import nchw_to_tm
+    from test_hip_dense_fp64 import Bars, check_bn_bwd
+    from gkgnet_amd import _lib
+    from gkgnet_amd.ops import _ptr, _stream
+    lib = _lib.load()
+    R = B * N
+    gen = torch.Generator(device="cuda").manual_seed(7 * R + C)
+    x = torch.randn(B, C, N, device="cuda", generator=gen)
+    add = torch.randn(R, C, device="cuda", generator=gen)
+    Y, mean, invstd, a, c = _bn_case(R, C, gen)
+    g = torch.full((R, C), float("nan"), device="cuda")
+    _lib.check(lib.gkg_nchw_to_tm_add(_ptr(x), _ptr(add), _ptr(g), B, C, N, _stream()), "gkg_nchw_to_tm_add")
+    two = _two_pass(lib, g, Y, a, c, mean, invstd, R, C)
+    g1 = torch.full((R, C), float("nan"), device="cuda")
+    sums = torch.zeros(2 * C, dtype=torch.float64, device="cuda")
+    _lib.check(lib.gkg_nchw_to_tm_add_bnstats(_ptr(x), _ptr(add), _ptr(g1), _ptr(Y), _ptr(mean), _ptr(invstd), _ptr(sums), B, C, N,
+                                              _stream()), "gkg_nchw_to_tm_add_bnstats")
+    fused_ = _apply_only(lib, g1, Y, a, c, mean, invstd, R, C, sums)
+    torch.cuda.synchronize()
+    assert torch.equal(g, nchw_to_tm(x, None, add))                    # a permutation and one fp32 add: correctly rounded on both sides
+    for side, (dY, dgamma, dbeta) in (("two-pass", two), ("fused", fused_)):
+        bars = Bars(f"pass_fusion B {side} B{B} C{C} N{N}")
+        check_bn_bwd(bars, g[None], Y[None], a[None], c[None], mean[None], invstd[None], 0, dY, dgamma, dbeta)
+        bars.done()
+
+
 # ---------------------------------------------------------------------------------------------------------------- C
 def _mr_case(B, G, c, N, M, gen, inf_at=None):
     C = G * c

@@ -107,6 +107,49 @@ def test_dgrad_epilogue_statistics_match_the_stand_alone_pass(R, cin, cout, pnb,
         assert _rel(u, v) <= TOL, name
 
 
+@pytest.mark.parametrize("R,cin,cout,pnb,act,with_res", [(2571, 160, 64, 4, 1, True), (10368, 640, 320, 4, 1, False), (1003, 320, 96, 1, 0, True)])
+def test_the_stand_alone_pass_of_the_comparison_ends_at_fp64(R, cin, cout, pnb, act, with_res):
+    """The test above compares the epilogue statistics with the two-launch gkg_bn_bwd_atomic: kernel against kernel.  Here both
+    sides' dY / dgamma / dbeta are held to the fp64 reference (tests/dense_ref.py) of the BN backward of the gradient dx the GEMM
+    wrote, under the bar of tests/test_hip_dense_fp64.py."""
+    from test_hip_dense_fp64 import Bars, check_bn_bwd
+    from gkgnet_amd import _lib, fused
+    from gkgnet_amd.ops import _ptr, _stream
+    lib = _lib.load()
+    pco = cin // pnb
+    gen = torch.Generator(device="cuda").manual_seed(R + 3 * cin + cout)
+    w = torch.randn(1, cout, cin, device="cuda", generator=gen) / cout ** 0.5
+    dy = torch.randn(R, cout, device="cuda", generator=gen)
+    res = torch.randn(R, cin, device="cuda", generator=gen) if with_res else None
+    Y, mean, invstd, a, c = _bn_case(R, pnb, pco, gen)
+    _, pd = _planes(lib, w, 1, cout, cin)
+    sk = fused._sk_ws(dy.device)
+    gbs = pco if pnb > 1 else 0
+    dx = torch.full((R, cin), float("nan"), device="cuda")
+    sums1 = torch.zeros(2 * cin, dtype=torch.float64, device="cuda")
+    _lib.check(lib.gkg_linear_dgrad_x6_bnbwd_sk(_ptr(dy), cout, _ptr(pd), _ptr(dx), R, cin, cout, _ptr(res), _ptr(Y), _ptr(a), _ptr(c),
+                                                _ptr(mean), _ptr(invstd), _ptr(sums1), pnb, pco, act, _ptr(sk), sk.numel(), 0, _stream()),
+               "gkg_linear_dgrad_x6_bnbwd_sk")
+    sides = {}
+    for side in ("two-pass", "epilogue"):
+        out = torch.full_like(Y, float("nan")), torch.full((cin,), float("nan"), device="cuda"), torch.full((cin,), float("nan"), device="cuda")
+        if side == "two-pass":
+            sums0 = torch.zeros(2 * cin, dtype=torch.float64, device="cuda")
+            _lib.check(lib.gkg_bn_bwd_atomic(_ptr(dx), _ptr(Y), _ptr(a), _ptr(c), _ptr(mean), _ptr(invstd), *[_ptr(t) for t in out],
+                                             R, pco, pnb, cin, gbs, act, _ptr(sums0), None, 0, _stream()), "gkg_bn_bwd_atomic")
+        else:
+            _lib.check(lib.gkg_bn_bwd_apply_from_sums(_ptr(dx), _ptr(Y), _ptr(a), _ptr(c), _ptr(mean), _ptr(invstd), *[_ptr(t) for t in out],
+                                                      R, pco, pnb, cin, gbs, act, _ptr(sums1), None, 0, _stream()), "gkg_bn_bwd_apply_from_sums")
+        sides[side] = out
+    torch.cuda.synchronize()
+    g = dx.view(R, pnb, pco).permute(1, 0, 2).contiguous()                # dout[q] = columns [q * pco, (q + 1) * pco) of dx
+    per = lambda t: t.view(pnb, pco)      # noqa: E731
+    for side, (dY, dgamma, dbeta) in sides.items():
+        bars = Bars(f"dgrad_stats {side} R{R} cin{cin} pnb{pnb} act{act}")
+        check_bn_bwd(bars, g, Y, per(a), per(c), per(mean), per(invstd), act, dY, per(dgamma), per(dbeta))
+        bars.done()
+
+
 def test_the_round_4_entry_point_is_the_sk_form_without_a_workspace():
     """gkg_linear_dgrad_x6_bnbwd (no workspace, no residual: the 128-row tile body whatever the shape) against
     gkg_linear_dgrad_x6_bnbwd_sk with a NULL workspace: the same dx bits, and the statistics to the bound above."""

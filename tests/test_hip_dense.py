@@ -282,6 +282,12 @@ def test_affine_act_dual_writes_both_copies(act):
     _lib.check(lib.gkg_affine_act_dual(Y.data_ptr(), a.data_ptr(), c.data_ptr(), res.data_ptr(), o2.data_ptr(), o16.data_ptr(),
                                        R, C, act, scale.data_ptr(), 59, None), "gkg_affine_act_dual")
     assert torch.equal(o1, o2) and torch.equal(o16, o1.bfloat16())
+    # ... and both are the same kernel template: the values themselves against the fp64 reference (tests/test_hip_dense_fp64.py)
+    from test_hip_dense_fp64 import Bars, check_affine_act_dual
+    torch.cuda.synchronize()
+    bars = Bars(f"test_hip_dense affine_act_dual act{act}")
+    check_affine_act_dual(bars, Y, a, c, res, act, scale, 59, o2, o16)
+    bars.done()
 
 
 @pytest.mark.parametrize("train", [True, False])

@@ -165,3 +165,121 @@ def test_backward_on_a_side_stream_launches_the_batch_there(monkeypatch):
     for n, v in want.items():
         assert float((got[n] - v).abs().max()) <= 2e-5 * float(v.abs().max()) + 5e-5, n
     torch.cuda.synchronize()
+
+
+# ---------------------------------------------------------------------------------------------------------------- queue overflow
+# A cap reached while a block's problems enter the queue: the block driver hands fused._wgrad_defer_block its 3 (Grapher) or
+# 5 (GrapherLabel) problems with ONE keep-alive tuple (the arenas every one of them reads).  A launch forced by _WgradQueue.MAX /
+# MAX_BYTES clears q.keep, so it must come before the first or after the last problem of a block, never in between.
+def _three_blocks(monkeypatch, max_items=None, max_bytes=None, batch=True, record=None):
+    """Two Graphers and a GrapherLabel through the block driver with bucket slots; one fwd + bwd step.  Backward order: the label
+    block (5 problems), then the two Graphers (3 + 3).  T = 32 * 144 = 4608 rows (36 units of 128 rows: two slabs per weight
+    gradient, so their fp32 atomic accumulation into the zeroed slot is order-independent and dW reproducible bit for bit), label
+    rows 32 * 16 = 512.  -> (flat gradients, dx, de)."""
+    from gkgnet_amd import block, fused, parallel
+    from gkgnet_amd.grapher import Grapher, GrapherLabel
+    monkeypatch.setattr(block, "ENABLED", True)
+    monkeypatch.setattr(fused, "WGRAD_BATCH", batch)
+    if max_items is not None:
+        monkeypatch.setattr(fused._WgradQueue, "MAX", max_items)
+    if max_bytes is not None:
+        monkeypatch.setattr(fused._WgradQueue, "MAX_BYTES", max_bytes)
+    block._PLANS.clear()
+    torch.manual_seed(13)
+    C, H, L, B, G = 64, 12, 16, 32, 2
+    mk = lambda: Grapher(C, 9, 1, "mr", "gelu", "batch", True, False, 0.2, 1, n=H * H, relative_pos=True, use_multi_group=True,      # noqa: E731
+                         num_group=G).cuda().train()
+    g1, g2 = mk(), mk()
+    gl = GrapherLabel(C, 9, 1, "mr", "gelu", "batch", True, False, 0.2, 1, n=H * H, relative_pos=False, num_nodes=L,
+                      use_multi_group=True, num_group=G).cuda().train()
+    params = list(g1.parameters()) + list(g2.parameters()) + list(gl.parameters())
+    bucket = parallel.GradBucket(params)
+    gen = torch.Generator(device="cuda").manual_seed(4)
+    x = torch.randn(B, C, H, H, device="cuda", generator=gen).requires_grad_(True)
+    e = torch.randn(B, L, C, device="cuda", generator=gen).requires_grad_(True)
+    cx, ce = torch.randn(B, C, H, H, device="cuda", generator=gen), torch.randn(B, L, C, device="cuda", generator=gen)
+    bucket.release(prezero=True)
+    if record is not None:
+        real_defer, real_launch = fused._wgrad_defer_block, fused._launch_wgrads
+
+        def op_bytes(p):
+            return 4 * p.nb * p.R * (p.cin + p.cout)                       # the (dY, x) pair of one problem, fp32
+
+        def launch(q, items):
+            record["launches"].append((len(items), q.bytes, sum(op_bytes(p) for p in items)))
+            return real_launch(q, items)
+
+        def defer(problems, n, outs, keep, device):
+            q = fused._WQ
+            taken = real_defer(problems, n, outs, keep, device)
+            mine = {problems[i].dw for i in range(n)}
+            record["blocks"].append(dict(taken=taken, n=n, items=len(q.items), keeps=len(q.keep), bytes=q.bytes,
+                                         want_bytes=sum(op_bytes(p) for p in q.items),
+                                         held=all(kp is not None and all(any(t is u for u in kp) for t in keep)
+                                                  for p, kp in zip(q.items, q.keep) if p.dw in mine)))
+            return taken
+        monkeypatch.setattr(fused, "_launch_wgrads", launch)
+        monkeypatch.setattr(fused, "_wgrad_defer_block", defer)
+    out = g2(g1(x))
+    e2, _ = gl(e, out)
+    torch.autograd.backward([out, e2], [cx, ce])
+    bucket.pack()
+    torch.cuda.synchronize()
+    assert not fused._WQ.items and not fused._WQ.keep and fused._WQ.bytes == 0
+    return bucket.flat.clone(), x.grad.clone(), e.grad.clone()
+
+
+def test_a_cap_reached_inside_a_block_keeps_the_blocks_operands_alive(monkeypatch):
+    """MAX = 4: the label block's five problems overflow the queue on their own, and the second Grapher's three do not fit behind
+    the first one's.  After every block: one keep entry per queued problem, every queued problem of the block holds the block's
+    keep tuple, and q.bytes is the real operand byte count of what is queued (it was 0 for blocks: MAX_BYTES never saw them)."""
+    rec = {"blocks": [], "launches": []}
+    _three_blocks(monkeypatch, max_items=4, record=rec)
+    assert [b["n"] for b in rec["blocks"]] == [5, 3, 3] and all(b["taken"] for b in rec["blocks"])      # the driver, with bucket slots
+    for b in rec["blocks"]:
+        assert b["keeps"] == b["items"], b
+        assert b["held"], b
+        assert b["bytes"] == b["want_bytes"], b
+    assert [b["items"] for b in rec["blocks"]] == [0, 3, 3]                # 5 >= MAX: launched whole; 3; 3 + 3 > MAX: launched, then 3
+    assert [n for n, _, _ in rec["launches"]] == [5, 3, 3]                 # never a part of a block
+    assert all(have == want and want > 0 for _, have, want in rec["launches"])
+
+
+@pytest.mark.parametrize("cap", [dict(max_items=4), dict(max_bytes=1 << 20)], ids=["MAX", "MAX_BYTES"])
+def test_gradients_under_overflow_are_those_of_the_default_queue(cap, monkeypatch):
+    """Every gradient bit for bit as with the default caps: where the queue is cut changes which launch computes a dW, not its
+    value.  (The BN column sums of the forward are accumulated with fp64 atomics and a mean on an fp32 rounding tie can differ
+    between two runs of the SAME configuration — tests/test_hip_block_driver.py — so a pair that differs is repeated; a real
+    difference shows in every pair.)  And to rounding as the per-layer launches (GKG_DISABLE=wgrad_batch), at this file's tolerance."""
+    TIE = 2e-5                    # what a BN mean one ulp apart moves any gradient by, at most (the bound this file uses throughout)
+    same = False
+    for attempt in range(4):
+        small = _three_blocks(monkeypatch, **cap)
+        monkeypatch.undo()
+        default = _three_blocks(monkeypatch)
+        monkeypatch.undo()
+        # EVERY pair, agreeing bit for bit or not, agrees to rounding: a dW computed from a released arena is wrong by far more than
+        # a tie is, and is not repeated away
+        for u, v in zip(small, default):
+            assert torch.isfinite(u).all()
+            scale = float(v.abs().max())
+            assert float((u - v).abs().max()) <= TIE * scale, (attempt, float((u - v).abs().max()) / scale)
+        same = all(torch.equal(u, v) for u, v in zip(small, default))
+        if same:
+            break
+    assert same
+    per_layer = _three_blocks(monkeypatch, batch=False)
+    for u, w in zip(small, per_layer):
+        scale = float(w.abs().max())
+        assert float((u - w).abs().max()) <= 2e-5 * scale, float((u - w).abs().max()) / scale
+
+
+def test_a_block_that_exactly_fills_the_queue_leaves_nothing_dangling(monkeypatch):
+    """MAX = 6: the label block (5) stays queued, the first Grapher (5 + 3 > 6) sends it out and queues 3, the second one makes
+    len(items) + n == MAX: all six go out together and the queue is empty, keep list included."""
+    rec = {"blocks": [], "launches": []}
+    _three_blocks(monkeypatch, max_items=6, record=rec)
+    assert [b["items"] for b in rec["blocks"]] == [5, 3, 0]
+    assert [b["keeps"] for b in rec["blocks"]] == [5, 3, 0] and all(b["held"] for b in rec["blocks"])
+    assert [b["bytes"] for b in rec["blocks"]] == [b["want_bytes"] for b in rec["blocks"]] and rec["blocks"][2]["bytes"] == 0
+    assert [n for n, _, _ in rec["launches"]] == [5, 6]
