@@ -376,7 +376,7 @@ class _GrapherBlockFn(torch.autograd.Function):
         x = x.contiguous()
         d = GrapherBlock.from_buffer_copy(plan.tmpl)
         keep = []
-        scratch = fused._BnFwdScratch.of(dev)
+        scratch = fused._BnScratch.of(dev)
         buf = torch.empty(plan.fwd_total, dtype=_F32, device=dev)
         base = buf.data_ptr()
         oxt, oXM, oA2, oY1, oY2, oY3, ob1, ob2, ob3, oarg = [base + 4 * o for o in plan.fwd_offs]
@@ -386,8 +386,7 @@ class _GrapherBlockFn(torch.autograd.Function):
         d.x, d.out, d.out_tm = x.data_ptr(), out.data_ptr(), _ptr(out_tm)
         d.xt, d.XM, d.A2 = oxt, oXM, oA2
         p1, pc, p2 = plan.projs
-        scratch.hold = 1                 # every layer's buffers are handed out before the first launch (bn_scratch.one_call)
-        try:
+        with scratch.one_call():
             _proj_fwd(lib, d.fc1, p1, scratch, keep, oY1, ob1)
             _proj_fwd(lib, d.conv, pc, scratch, keep, oY2, ob2)
             _proj_fwd(lib, d.fc2, p2, scratch, keep, oY3, ob3)
@@ -405,11 +404,6 @@ class _GrapherBlockFn(torch.autograd.Function):
                     d.keys_G, d.keys_L, d.keys_k, d.keys_d, d.keys_fused_mr, d.keys_flags = G2, L2, k2, d2, int(fm2), kk.flags
                     d.keys_ws, d.keys_ws_bytes = kk.ws.data_ptr(), kk.ws.numel()
             _lib.check(lib.gkg_grapher_fwd(C.byref(d), _stream()), "gkg_grapher_fwd")
-        except Exception:
-            scratch.poison()
-            raise
-        finally:
-            scratch.hold = 0
         if kk is not None:
             out_tm._gkg_knn_keys = kk
         ctx.save_for_backward(buf, w1, wc, w2)
@@ -440,20 +434,14 @@ class _GrapherBlockFn(torch.autograd.Function):
         dtm_c = None if dtm is None else dtm.contiguous()
         d.dout, d.dout_tm, d.dx = dout_c.data_ptr(), _ptr(dtm_c), dx.data_ptr()
         d.bwd_flags = fused._block_flags()
-        scratch = fused._BnBwdScratch.of(dev)
+        scratch = fused._BnScratch.of(dev)
         wq = (_lib.WgradProblem * 3)()
         p1, pc, p2 = plan.projs
-        scratch.hold = 1                 # every layer's buffers are handed out before the first launch (bn_scratch.one_call)
-        try:
+        with scratch.one_call():
             o2 = _proj_bwd(lib, d.fc2, p2, scratch, dev)
             oc = _proj_bwd(lib, d.conv, pc, scratch, dev)
             o1 = _proj_bwd(lib, d.fc1, p1, scratch, dev)
             _lib.check(lib.gkg_grapher_bwd(C.byref(d), wq, _stream()), "gkg_grapher_bwd")
-        except Exception:
-            scratch.poison()
-            raise
-        finally:
-            scratch.hold = 0
         _issue_wgrads(lib, wq, 3, (o2[0], oc[0], o1[0]), (buf, tbuf, dout_c, dtm_c), dev)
         return (dx, o1[0].view_as(w1), o1[1], o1[2], oc[0].view_as(wc), oc[1], oc[2], o2[0].view_as(w2), o2[1], o2[2], None, None, None, None)
 
@@ -497,7 +485,7 @@ class _LabelBlockFn(torch.autograd.Function):
         groups = plan.groups
         d = LabelBlock.from_buffer_copy(plan.tmpl)
         keep = []
-        scratch = fused._BnFwdScratch.of(dev)
+        scratch = fused._BnScratch.of(dev)
         buf = torch.empty(plan.fwd_total, dtype=_F32, device=dev)
         base = buf.data_ptr()
         oXM, oA2, oh2, of1, oY1, oY2, oY3, oY4, oY5, ob1, ob2, ob3, ob4, ob5, oarg = [base + 4 * o for o in plan.fwd_offs]
@@ -505,8 +493,7 @@ class _LabelBlockFn(torch.autograd.Function):
         d.B, d.C, d.L, d.M = B, Cc, L, M
         d.e, d.ft, d.out = e2.data_ptr(), ft.data_ptr(), out.data_ptr()
         d.XM, d.A2, d.h2, d.f1 = oXM, oA2, oh2, of1
-        scratch.hold = 1                 # every layer's buffers are handed out before the first launch (bn_scratch.one_call)
-        try:
+        with scratch.one_call():
             for p, pr, oy, ob in zip((d.fc1, d.conv, d.fc2, d.ffn1, d.ffn2), plan.projs, (oY1, oY2, oY3, oY4, oY5), (ob1, ob2, ob3, ob4, ob5)):
                 _proj_fwd(lib, p, pr, scratch, keep, oy, ob)
             key, edge = _graph_op(lib, plan, d.graph, B, groups, Cc // groups, L, M, None, True, True, dev, keys_key, keep)
@@ -514,11 +501,6 @@ class _LabelBlockFn(torch.autograd.Function):
             sk = fused._sk_ws(dev)
             d.sk_ws, d.sk_bytes = sk.data_ptr(), sk.numel()
             _lib.check(lib.gkg_grapher_label_fwd(C.byref(d), _stream()), "gkg_grapher_label_fwd")
-        except Exception:
-            scratch.poison()
-            raise
-        finally:
-            scratch.hold = 0
         if producer is not None and fused.KNN_PREP:
             lk = (groups, L, plan.k, plan.d, key.fused_mr)                 # the Grapher in front prepares this graph's keys
             if producer.__dict__.get("_gkg_label_knn") != lk:              # from its next call on (fused.grapher_label_forward)
@@ -549,22 +531,16 @@ class _LabelBlockFn(torch.autograd.Function):
         dout_c = dout.contiguous()
         d.dout, d.de, d.dft = dout_c.data_ptr(), de.data_ptr(), dft.data_ptr()
         d.bwd_flags = fused._block_flags()
-        scratch = fused._BnBwdScratch.of(dev)
+        scratch = fused._BnScratch.of(dev)
         wq = (_lib.WgradProblem * 5)()
         p1, pc, p3, p4, p5 = plan.projs
-        scratch.hold = 1                 # every layer's buffers are handed out before the first launch (bn_scratch.one_call)
-        try:
+        with scratch.one_call():
             o5 = _proj_bwd(lib, d.ffn2, p5, scratch, dev)
             o4 = _proj_bwd(lib, d.ffn1, p4, scratch, dev)
             o3 = _proj_bwd(lib, d.fc2, p3, scratch, dev)
             oc = _proj_bwd(lib, d.conv, pc, scratch, dev)
             o1 = _proj_bwd(lib, d.fc1, p1, scratch, dev)
             _lib.check(lib.gkg_grapher_label_bwd(C.byref(d), wq, _stream()), "gkg_grapher_label_bwd")
-        except Exception:
-            scratch.poison()
-            raise
-        finally:
-            scratch.hold = 0
         _issue_wgrads(lib, wq, 5, (o5[0], o4[0], o3[0], oc[0], o1[0]), (buf, tbuf, e2, dout_c), dev)
         return (de, dft, o1[0].view_as(w1), o1[1], o1[2], oc[0].view_as(wc), oc[1], oc[2], o3[0].view_as(w2), o3[1], o3[2],
                 o4[0].view_as(w4), o4[1], o4[2], o5[0].view_as(w5), o5[1], o5[2], None, None, None)

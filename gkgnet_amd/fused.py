@@ -394,14 +394,14 @@ def _dgrad_x6(lib, dY, ldg, g_bs, pd, dx, R, cin, cout, nb, residual=None, ldx=0
 
 def _grad_outs(gparams, wshape, nch, dev):
     """Output tensors for (dW, dgamma, dbeta): the parameters' slots in the gradient bucket when they have one and the
-    step is not accumulating (parallel.grad_view), else fresh tensors."""
+    step is not accumulating (parallel.grad_view), else fresh tensors.  ``wshape`` None: a BN without a projection, no dW."""
     w = g = b = None
     if gparams is not None:
         wp, gp, bp = gparams
-        w = grad_view(wp, wshape) if wp.dtype == _F32 else None
+        w = grad_view(wp, wshape) if (wshape is not None and wp.dtype == _F32) else None
         g = grad_view(gp, (nch,)) if gp.dtype == _F32 else None
         b = grad_view(bp, (nch,)) if bp.dtype == _F32 else None
-    if w is None:
+    if w is None and wshape is not None:
         w = torch.empty(wshape, dtype=_F32, device=dev)
     if g is None:
         g = torch.empty(nch, dtype=_F32, device=dev)
@@ -632,7 +632,7 @@ def _bn_forward_params(lib, Y, bn, bias, R, C, nb):
     return a, c, None, None, None
 
 
-from .bn_scratch import _BnBwdScratch, _BnFwdScratch      # noqa: E402  (fp64 column-sum scratch of the two-launch BN passes)
+from .bn_scratch import _BnLink, _BnScratch      # noqa: E402  (fp64 column-sum scratch of the two-launch BN passes)
 
 
 def _train_apply_from_sums(lib, x, W, bias, bn, R, cin, cout, nb, planes, res, out, ldo, obs, act, nchw_B, scale, rows_per_scale,
@@ -641,9 +641,7 @@ def _train_apply_from_sums(lib, x, W, bias, bn, R, cin, cout, nb, planes, res, o
     Returns (Y, a, c, mean, invstd).  ``launch(Y, sums) -> rc``: a caller-supplied producer of Y and its column sums (the
     fused aggregation + projection kernel) instead of the plain projection of ``x``."""
     dev = x.device
-    scratch = _BnFwdScratch.of(dev)
-    cur, other, zero = scratch.acquire(lib, 2 * nb * cout)
-    try:
+    with _BnScratch.of(dev).scoped(lib, 2 * nb * cout) as (cur, other, zero):
         Y = torch.empty((nb, R, cout) if nb > 1 else (R, cout), dtype=_F32, device=dev)
         none10 = [None] * 10
         if launch is not None:
@@ -685,9 +683,6 @@ def _train_apply_from_sums(lib, x, W, bias, bn, R, cin, cout, nb, planes, res, o
                                               _ptr(res), _ptr(out), R, cout, nb, ldo, obs, ochunk, act, nchw_B, _ptr(scale), rows_per_scale,
                                               float(bn.momentum), float(bn.eps), _ptr(other), zero, _stream()),
                        "gkg_bn_apply_train")
-    except Exception:
-        scratch.poison()                 # sums may sit in a buffer the bookkeeping calls clean: cleared at the next acquire
-        raise
     return Y, a, c, mean, invstd
 
 
@@ -695,7 +690,7 @@ def _derive_ok(bn, nb, cout, code, want16) -> bool:
     """Train-mode statistics local to the rank, fp32 output: the BN-apply pass derives its coefficients from the projection
     kernel's sums (no finalize launch)."""
     return ((bn.training or not bn.track_running_stats) and _sync_group(bn) is None
-            and code == _lib.F32 and not want16 and 2 * nb * cout <= _BnBwdScratch.DOUBLES)
+            and code == _lib.F32 and not want16 and _BnScratch.fits(2 * nb * cout))
 
 
 # BN backward statistics in the epilogue of the NEXT projection's input-gradient GEMM (round 4, csrc/gkg_gemm_x6.hip X6_BNBWD).
@@ -743,7 +738,7 @@ def _block_flags() -> int:
 
 def _bwd_fuse_ok(mean, sync, scale, nb, co) -> bool:
     return (BWD_FUSE and mean is not None and sync is None and scale is None and not DETERMINISTIC and nb == 1
-            and 2 * co <= _BnBwdScratch.DOUBLES)
+            and _BnScratch.fits(2 * co))
 
 
 _MR_BN_OK = {}
@@ -766,36 +761,23 @@ def _mr_bwd(lib, g, nn_idx, arg, B, G, C, N, M, k, mode, ak, has_src, xshape, li
     flags = _mr_bwd_flags()
     if (link is not None and BWD_FUSE and not DETERMINISTIC and link.nb == 1 and link.act == 0 and link.co == C and link.R == B * N
             and _mr_bn_supported(lib, B, G, C // G, N, M, k, mode, ak, not has_src, flags)):
-        scratch = _BnBwdScratch.of(g.device)
-        cur, other, zero = scratch.acquire(lib, 2 * C)
-        try:
+        scratch = _BnScratch.of(g.device)
+        with scratch.scoped(lib, 2 * C) as (cur, other, zero):
             _lib.check(lib.gkg_mr_bwd_tm_bnstats(_ptr(g), _ptr(nn_idx), _ptr(arg), _ptr(gx), _ptr(gsrc), B, G, C // G, N, M, k, mode, ak,
                                                  flags, _ptr(link.Y), _ptr(link.mean), _ptr(link.invstd), _ptr(cur), _stream()),
                        "gkg_mr_bwd_tm_bnstats")
-        except Exception:
-            scratch.poison()
-            raise
         gxv = gx.view(xshape)
-        link.ready = (gxv, gxv._version, cur, other, zero)
-        scratch.pending = link
+        scratch.hand_off(link, gxv, cur, other, zero)
         return gxv, gsrc
     _lib.check(lib.gkg_mr_bwd_tm(_ptr(g), _ptr(nn_idx), _ptr(arg), _ptr(gx), _ptr(gsrc), B, G, C // G, N, M, k, mode, ak, flags, _stream()),
                "gkg_mr_bwd_tm")
     return gx.view(xshape), gsrc
 
 
-class _BnLink:
-    __slots__ = ("Y", "a", "c", "mean", "invstd", "act", "nb", "co", "R", "ready", "__weakref__")
-
-    def __init__(self, Y, a, c, mean, invstd, act, nb, co, R):
-        self.Y, self.a, self.c, self.mean, self.invstd, self.act, self.nb, self.co, self.R = Y, a, c, mean, invstd, act, nb, co, R
-        self.ready = None             # (the gradient tensor the sums belong to, its version, cur, other, zero)
-
-
 def _bn_link(out, Y, a, c, mean, invstd, act, nb, co, R, bn, sync, scale):
     """Hang a _BnLink on a token-major fp32 layer output (train-mode, rank-local statistics, atomics allowed)."""
     if (BN_EPILOGUE and (R >= BN_EPILOGUE_MIN_ROWS or (BWD_FUSE and DGRAD_STATS)) and mean is not None and sync is None
-            and scale is None and not DETERMINISTIC and out.dtype == _F32 and 2 * nb * co <= _BnBwdScratch.DOUBLES):
+            and scale is None and not DETERMINISTIC and out.dtype == _F32 and _BnScratch.fits(2 * nb * co)):
         link = _BnLink(Y, a, c, mean, invstd, act, nb, co, R)
         out._gkg_bn_link = link
         return link
@@ -805,17 +787,12 @@ def _bn_link(out, Y, a, c, mean, invstd, act, nb, co, R, bn, sync, scale):
 def _relayout_bnstats(lib, dout_c, dtm_c, g, Y, mean, invstd, a, c, B, cout, R):
     """g (R, cout) = dout_c (B, cout, N)^T (+ dtm_c) with the BN backward statistics of  out = BN(Y)  taken in the same pass
     (gkg_nchw_to_tm_add_bnstats) -> a _BnLink that carries them to _bn_backward, which then runs the apply pass only."""
-    scratch = _BnBwdScratch.of(g.device)
-    cur, other, zero = scratch.acquire(lib, 2 * cout)
-    try:
+    scratch = _BnScratch.of(g.device)
+    with scratch.scoped(lib, 2 * cout) as (cur, other, zero):
         _lib.check(lib.gkg_nchw_to_tm_add_bnstats(_ptr(dout_c), _ptr(dtm_c), _ptr(g), _ptr(Y), _ptr(mean), _ptr(invstd), _ptr(cur),
                                                   B, cout, R // B, _stream()), "gkg_nchw_to_tm_add_bnstats")
-    except Exception:
-        scratch.poison()
-        raise
     link = _BnLink(Y, a, c, mean, invstd, 0, 1, cout, R)
-    link.ready = (g, g._version, cur, other, zero)
-    scratch.pending = link
+    scratch.hand_off(link, g, cur, other, zero)
     return link
 
 
@@ -827,30 +804,22 @@ def _dgrad_with_link_ok(lib, R, cin, has_res) -> bool:
 def _dgrad_x6_with_link(lib, dY, pd, R, cin, cout, link, residual=None):
     """dx = dY W (+ residual) on the x6 kernel with the producer's BN backward statistics in the epilogue -> dx (the bits of
     _dgrad_x6); leaves the sums on the link."""
-    scratch = _BnBwdScratch.of(dY.device)
-    cur, other, zero = scratch.acquire(lib, 2 * link.nb * link.co)
-    dx = torch.empty((R, cin), dtype=_F32, device=dY.device)
-    ws = _sk_ws(dY.device)
-    try:
+    scratch = _BnScratch.of(dY.device)
+    with scratch.scoped(lib, 2 * link.nb * link.co) as (cur, other, zero):
+        dx = torch.empty((R, cin), dtype=_F32, device=dY.device)
+        ws = _sk_ws(dY.device)
         _lib.check(lib.gkg_linear_dgrad_x6_bnbwd_sk(_ptr(dY), cout, _ptr(pd), _ptr(dx), R, cin, cout, _ptr(residual), _ptr(link.Y),
                                                     _ptr(link.a), _ptr(link.c), _ptr(link.mean), _ptr(link.invstd), _ptr(cur),
                                                     link.nb, link.co, link.act, _ptr(ws), ws.numel(), 0, _stream()),
                    "gkg_linear_dgrad_x6_bnbwd_sk")
-    except Exception:
-        scratch.poison()
-        raise
-    # the tensor ITSELF and its version (ADVICE r4): holding it keeps autograd from accumulating another consumer's gradient
-    # into it in place (use_count > 1 -> a fresh sum is allocated), and a changed version or another object means the sums on
-    # the link do not describe the gradient the producer receives
-    link.ready = (dx, dx._version, cur, other, zero)
-    scratch.pending = link               # the other buffer's clear is deferred to the producer's apply pass (bn_scratch.acquire)
+    scratch.hand_off(link, dx, cur, other, zero)      # the other buffer's clear is deferred to the producer's apply pass
     return dx
 
 
 def _bn_scale_in_kernel(sync, nb, C) -> bool:
     """Whether _bn_backward will take the two-launch fp64-atomic form, whose kernels can apply a per-image gradient scale
     (DropPath) themselves instead of a separate elementwise launch in front of them (22 launches, 0.6 ms of the cfg4 step)."""
-    return sync is None and not DETERMINISTIC and 2 * nb * C <= _BnBwdScratch.DOUBLES
+    return sync is None and not DETERMINISTIC and _BnScratch.fits(2 * nb * C)
 
 
 def _bn_backward(lib, g, Y, a, c, mean, invstd, dY, dgamma, dbeta, R, C, nb, ldg, g_bstride, act, sync, link=None, row_scale=None,
@@ -859,30 +828,20 @@ def _bn_backward(lib, g, Y, a, c, mean, invstd, dY, dgamma, dbeta, R, C, nb, ldg
     input gradient needs are all-reduced over the ranks (dgamma/dbeta stay local, like torch's SyncBatchNorm: the
     data-parallel gradient exchange averages them).  ``link``: this layer's _BnLink — when the consumer's dgrad epilogue has
     left the statistics of exactly this gradient tensor on it, only the apply pass runs."""
-    if link is not None and link.ready is not None:
-        dxr, ver, cur, other, zero = link.ready
-        link.ready = None
-        scr = _BnBwdScratch.of(Y.device)
-        if scr.pending is link:
-            scr.pending = None
-        if g is dxr and g._version == ver and g_bstride == (C if nb > 1 else 0) and ldg == nb * C:
-            try:
+    if link is not None and link.holds_sums():
+        scratch = _BnScratch.of(Y.device)
+        sums = scratch.take(link, g, g_bstride == (C if nb > 1 else 0) and ldg == nb * C)
+        if sums is not None:
+            cur, other, zero = sums
+            with scratch:
                 _lib.check(lib.gkg_bn_bwd_apply_from_sums(_ptr(g), _ptr(Y), _ptr(a), _ptr(c), _ptr(mean), _ptr(invstd), _ptr(dY),
                                                           _ptr(dgamma), _ptr(dbeta), R, C, nb, ldg, g_bstride, act, _ptr(cur),
                                                           _ptr(other), zero, _stream()), "gkg_bn_bwd_apply_from_sums")
-            except Exception:
-                _BnBwdScratch.of(Y.device).poison()
-                raise
             return
-        # the gradient that arrived is not the tensor the sums were taken from (autograd added another contribution):
-        # the buffer bookkeeping is off by one acquire -> start clean
-        _BnBwdScratch.of(Y.device).poison()
-    if sync is None and not DETERMINISTIC and 2 * nb * C <= _BnBwdScratch.DOUBLES:
+    if _bn_scale_in_kernel(sync, nb, C):
         # two launches: statistics with fp64 atomics into one of two alternating scratch buffers, apply (which also clears
         # what the previous call left in the other buffer) — no partial rows, no second-stage reduction launch
-        scratch = _BnBwdScratch.of(Y.device)
-        cur, other, zero = scratch.acquire(lib, 2 * nb * C)
-        try:
+        with _BnScratch.of(Y.device).scoped(lib, 2 * nb * C) as (cur, other, zero):
             if row_scale is not None:
                 _lib.check(lib.gkg_bn_bwd_atomic_scaled(_ptr(g), _ptr(Y), _ptr(a), _ptr(c), _ptr(mean), _ptr(invstd), _ptr(dY),
                                                         _ptr(dgamma), _ptr(dbeta), R, C, nb, ldg, g_bstride, act, _ptr(cur), _ptr(other),
@@ -891,9 +850,6 @@ def _bn_backward(lib, g, Y, a, c, mean, invstd, dY, dgamma, dbeta, R, C, nb, ldg
                 _lib.check(lib.gkg_bn_bwd_atomic(_ptr(g), _ptr(Y), _ptr(a), _ptr(c), _ptr(mean), _ptr(invstd), _ptr(dY), _ptr(dgamma),
                                                  _ptr(dbeta), R, C, nb, ldg, g_bstride, act, _ptr(cur), _ptr(other), zero, _stream()),
                            "gkg_bn_bwd_atomic")
-        except Exception:
-            scratch.poison()
-            raise
         return
     ws = _ws(lib.gkg_bn_workspace_bytes(R, C, nb), Y.device)
     if sync is None:
@@ -924,17 +880,29 @@ def _bn_eval_backward(lib, g, Y, a, c, dY, bn, bias, dgamma, dbeta, dbias, R, C,
     head = (_ptr(g), _ptr(Y), _ptr(a), _ptr(c), _ptr(dY), R, C, nb, ldg, g_bstride, act, rs, rps)
     if dgamma is None and dbeta is None and dbias is None:
         _lib.check(lib.gkg_bn_eval_bwd(*head, *tail, None, None, 0, None, 0, _stream()), "gkg_bn_eval_bwd")
-    elif not DETERMINISTIC and 2 * nb * C <= _BnBwdScratch.DOUBLES:
-        scratch = _BnBwdScratch.of(Y.device)
-        cur, other, zero = scratch.acquire(lib, 2 * nb * C)
-        try:
+    elif not DETERMINISTIC and _BnScratch.fits(2 * nb * C):
+        with _BnScratch.of(Y.device).scoped(lib, 2 * nb * C) as (cur, other, zero):
             _lib.check(lib.gkg_bn_eval_bwd(*head, *tail, _ptr(cur), _ptr(other), zero, None, 0, _stream()), "gkg_bn_eval_bwd")
-        except Exception:
-            scratch.poison()
-            raise
     else:
         ws = _ws(lib.gkg_bn_workspace_bytes(R, C, nb), Y.device)
         _lib.check(lib.gkg_bn_eval_bwd(*head, *tail, None, None, 0, _ptr(ws), ws.numel(), _stream()), "gkg_bn_eval_bwd")
+
+
+def _bn_backward_any(lib, ctx, want, g, Y, a, c, mean, invstd, dY, dgamma, dbeta, R, C, nb, ldg, g_bstride, act, link=None,
+                     row_scale=None, rows_per_scale=0):
+    """The BN backward of a layer's autograd node, train or eval mode -> (dbias, dgamma, dbeta) to return.  ``want``: whether the
+    conv bias, gamma and beta need a gradient (eval mode computes only those); ``ctx.bn_eval``: (bn, conv bias) of an eval-mode
+    layer.  A conv bias in front of train-mode BN has exactly zero gradient (BN removes the mean): not materialised."""
+    if mean is not None:
+        _bn_backward(lib, g, Y, a, c, mean, invstd, dY, dgamma, dbeta, R, C, nb, ldg, g_bstride, act, ctx.sync, link, row_scale,
+                     rows_per_scale)
+        return None, dgamma, dbeta
+    # running statistics: one sweep, and the conv bias HAS a gradient
+    bn, bias = ctx.bn_eval
+    dbias = torch.empty(nb * C, dtype=_F32, device=Y.device) if (bias is not None and want[0]) else None
+    dgamma, dbeta = (dgamma if want[1] else None), (dbeta if want[2] else None)
+    _bn_eval_backward(lib, g, Y, a, c, dY, bn, bias, dgamma, dbeta, dbias, R, C, nb, ldg, g_bstride, act, row_scale, rows_per_scale)
+    return dbias, dgamma, dbeta
 
 
 class _LinearBNAct(torch.autograd.Function):
@@ -1019,7 +987,7 @@ class _LinearBNAct(torch.autograd.Function):
         ctx.save_for_backward(x, weight, Y, a, c, mean, invstd)
         ctx.bn_eval = (bn, bias) if mean is None else None       # eval-mode BN: the backward reads the running statistics
         ctx.dual = dual
-        ctx.meta = (act, nchw, residual is not None, bias is not None)
+        ctx.meta = (act, nchw, residual is not None)
         ctx.scale = (scale, rows_per_scale)
         ctx.gparams = (weight, gamma, beta)
         ctx.sync = sync
@@ -1047,7 +1015,7 @@ class _LinearBNAct(torch.autograd.Function):
     def backward(ctx, dout, dalias=None):
         lib = _lib.load()
         x, weight, Y, a, c, mean, invstd = ctx.saved_tensors
-        act, nchw, has_res, has_bias = ctx.meta
+        act, nchw, has_res = ctx.meta
         dtm = None
         if ctx.dual:
             dtm, dalias = dalias, None
@@ -1095,27 +1063,17 @@ class _LinearBNAct(torch.autograd.Function):
             _lib.check(lib.gkg_nchw_to_tm(_ptr(dout_c), _ptr(g), nchw[0], cout, R // nchw[0], _lib.F32,
                                           _ptr(ctx.scale[0]), _stream()), "gkg_nchw_to_tm")      # DropPath: g * mask / keep
         elif (ctx.scale[0] is not None and (mean is None or _bn_scale_in_kernel(ctx.sync, 1, cout))
-              and (ctx.link is None or ctx.link.ready is None)):
+              and (ctx.link is None or not ctx.link.holds_sums())):
             g = dout.contiguous()                # DropPath: the BN-backward kernels scale the gradient per image themselves
             row_scale = (ctx.scale[0].contiguous().float(), ctx.scale[1])
         elif ctx.scale[0] is not None:
             g = (dout.view(-1, ctx.scale[1], cout) * ctx.scale[0].view(-1, 1, 1)).view(R, cout)
         else:
             g = dout.contiguous()                # (an xm output's gradient arrives (B, N, 4, cout / 4): the same memory as (R, cout))
-        # a conv bias in front of train-mode BN has exactly zero gradient (BN removes the mean): not materialised
-        dbias = None
         dY = torch.empty_like(Y)
         dWv, dgamma, dbeta = _grad_outs(ctx.gparams, (cout, cin), cout, Y.device)
-        if mean is None:                         # eval-mode BN (running statistics): one sweep, and the conv bias HAS a gradient
-            bn, bias = ctx.bn_eval
-            dgamma, dbeta = (dgamma if ctx.needs_input_grad[3] else None), (dbeta if ctx.needs_input_grad[4] else None)
-            if has_bias and ctx.needs_input_grad[2]:
-                dbias = torch.empty(cout, dtype=_F32, device=Y.device)
-            _bn_eval_backward(lib, g, Y, a, c, dY, bn, bias, dgamma, dbeta, dbias, R, cout, 1, cout, 0, act,
-                              *(row_scale if row_scale is not None else (None, 0)))
-        else:
-            _bn_backward(lib, g, Y, a, c, mean, invstd, dY, dgamma, dbeta, R, cout, 1, cout, 0, act, ctx.sync, link,
-                         *(row_scale if row_scale is not None else (None, 0)))
+        dbias, dgamma, dbeta = _bn_backward_any(lib, ctx, ctx.needs_input_grad[2:5], g, Y, a, c, mean, invstd, dY, dgamma, dbeta,
+                                                R, cout, 1, cout, 0, act, link, *(row_scale if row_scale is not None else (None, 0)))
         W = weight.view(cout, cin)
         if not ctx.needs_input_grad[0]:
             dx = None
@@ -1123,7 +1081,7 @@ class _LinearBNAct(torch.autograd.Function):
             dx = _dgrad_x6_with_link(lib, dY, ctx.pd, R, cin, cout, ctx.prev)      # + the producer's BN backward statistics
         # (with the skip gradient only where the short-matrix body runs, i.e. up to 4 096 rows and 640 columns: the tile body's
         # statistics epilogue takes no residual.  Above that this branch is EXPECTED to miss: the plain input gradient below adds
-        # the residual, link.ready stays None and the producer runs its own statistics pass — as the block driver's
+        # the residual, the link stays empty and the producer runs its own statistics pass — as the block driver's
         # dgrad_stats_ok does for the same shapes)
         elif (ctx.prev is not None and dalias.dtype == _F32 and dalias.shape == (R, cin)
               and _dgrad_with_link_ok(lib, R, cin, True)):
@@ -1191,7 +1149,7 @@ class _GroupedLinearBNAct(torch.autograd.Function):
                                           code, None, 0, _stream()), "gkg_affine_act")
         ctx.save_for_backward(XM, weight, Y, a, c, mean, invstd)
         ctx.bn_eval = (bn, bias) if mean is None else None
-        ctx.meta = (act, bias is not None)
+        ctx.act = act
         ctx.gparams = (weight, gamma, beta)
         ctx.sync = sync
         ctx.pd = pd
@@ -1202,23 +1160,16 @@ class _GroupedLinearBNAct(torch.autograd.Function):
     def backward(ctx, dout):
         lib = _lib.load()
         XM, weight, Y, a, c, mean, invstd = ctx.saved_tensors
-        act, has_bias = ctx.meta
+        act = ctx.act
         nb = 4
         R, ci = XM.shape[0], XM.shape[1] // nb
         cout = weight.shape[0]
         co = cout // nb
         g = dout.contiguous()
-        dbias = None                                                # train-mode BN: == 0 exactly (see _LinearBNAct)
         dY = torch.empty_like(Y)
         dWv, dgamma, dbeta = _grad_outs(ctx.gparams, (nb, co, ci), cout, Y.device)
-        if mean is None:                                            # eval-mode BN: see _LinearBNAct.backward
-            bn, bias = ctx.bn_eval
-            dgamma, dbeta = (dgamma if ctx.needs_input_grad[3] else None), (dbeta if ctx.needs_input_grad[4] else None)
-            if has_bias and ctx.needs_input_grad[2]:
-                dbias = torch.empty(cout, dtype=_F32, device=Y.device)
-            _bn_eval_backward(lib, g, Y, a, c, dY, bn, bias, dgamma, dbeta, dbias, R, co, nb, cout, co, act)
-        else:
-            _bn_backward(lib, g, Y, a, c, mean, invstd, dY, dgamma, dbeta, R, co, nb, cout, co, act, ctx.sync, ctx.link)
+        dbias, dgamma, dbeta = _bn_backward_any(lib, ctx, ctx.needs_input_grad[2:5], g, Y, a, c, mean, invstd, dY, dgamma, dbeta,
+                                                R, co, nb, cout, co, act, ctx.link)
         Wg = weight.view(nb, co, ci)
         if not ctx.needs_input_grad[0]:
             dXM = None
@@ -1251,8 +1202,8 @@ class _BNActTM(torch.autograd.Function):
         _lib.check(lib.gkg_affine_act(_ptr(Y), _ptr(a), _ptr(c), None, _ptr(out), R, C, 1, C, 0, 0, act, _lib.F32, None, 0, _stream()),
                    "gkg_affine_act")
         ctx.save_for_backward(Y, a, c, mean, invstd)
-        ctx.act, ctx.sync, ctx.gparams = act, sync, (gamma, beta)
-        ctx.bn_eval = bn if mean is None else None
+        ctx.act, ctx.sync, ctx.gparams = act, sync, (None, gamma, beta)
+        ctx.bn_eval = (bn, None) if mean is None else None
         return out
 
     @staticmethod
@@ -1262,18 +1213,9 @@ class _BNActTM(torch.autograd.Function):
         R, C = Y.shape
         g = dout.contiguous()
         dY = torch.empty_like(Y)
-        gp, bp = ctx.gparams
-        dgamma = grad_view(gp, (C,)) if gp.dtype == _F32 else None
-        dbeta = grad_view(bp, (C,)) if bp.dtype == _F32 else None
-        if dgamma is None:
-            dgamma = torch.empty(C, dtype=_F32, device=Y.device)
-        if dbeta is None:
-            dbeta = torch.empty(C, dtype=_F32, device=Y.device)
-        if mean is None:                         # eval-mode BN: one sweep (see _LinearBNAct.backward); the conv in front owns its bias
-            dgamma, dbeta = (dgamma if ctx.needs_input_grad[1] else None), (dbeta if ctx.needs_input_grad[2] else None)
-            _bn_eval_backward(lib, g, Y, a, c, dY, ctx.bn_eval, None, dgamma, dbeta, None, R, C, 1, C, 0, ctx.act)
-        else:
-            _bn_backward(lib, g, Y, a, c, mean, invstd, dY, dgamma, dbeta, R, C, 1, C, 0, ctx.act, ctx.sync)
+        _, dgamma, dbeta = _grad_outs(ctx.gparams, None, C, Y.device)
+        _, dgamma, dbeta = _bn_backward_any(lib, ctx, (False,) + ctx.needs_input_grad[1:3], g, Y, a, c, mean, invstd, dY, dgamma,
+                                            dbeta, R, C, 1, C, 0, ctx.act)            # (the conv in front owns its bias)
         return dY, dgamma, dbeta, None, None
 
 

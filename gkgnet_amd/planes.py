@@ -171,8 +171,8 @@ class _WeightPlanes:
                     else:
                         t.zero_()
                 if ZERO_FOLD:
-                    from .bn_scratch import _BnBwdScratch
-                    scr = _BnBwdScratch._inst.get((self.device.type, self.device.index))
+                    from .bn_scratch import _BnScratch
+                    scr = _BnScratch.existing(self.device)
                     if scr is not None:
                         zero.append(scr.fold_reset(cap))
                 self.refresh(lib, zero)

@@ -350,6 +350,103 @@ def test_bn_scratch_protocol_under_capture_replay_and_eager_interleaving():
             check(step(), f"eager {it}.{j}")
 
 
+def _fail_once_after(monkeypatch, name, nth):
+    """_lib.check raises a GkgError once, AFTER the real check of the ``nth`` call reported as ``name`` (the launch has been
+    issued and has succeeded: a Python exception, no GPU fault) -> a list that holds True once it has fired."""
+    from gkgnet_amd import _lib
+    real, seen, fired = _lib.check, [0], []
+
+    def check(rc, what):
+        real(rc, what)
+        if what == name:
+            seen[0] += 1
+            if seen[0] == nth:
+                fired.append(True)
+                raise _lib.GkgError(f"{what} failed (injected after the launch)")
+    monkeypatch.setattr(_lib, "check", check)
+    return fired
+
+
+def test_bn_scratch_recovers_after_a_failed_pass(monkeypatch):
+    """A BN pass that raises between its acquire and the end of its launches leaves the scratch pair in a state the bookkeeping
+    cannot vouch for: the exception reaches the caller and the next step computes what an undisturbed one does.  The chain of
+    the test above (three layers: both buffers hold sums when the middle layer fails), a fresh scratch instance so that no
+    earlier capture makes every eager call clear the pair anyway.  Failures injected, one step each:
+      * the middle layer's gkg_bn_bwd_atomic (with the statistics hand-off of the input-gradient GEMMs switched off, every layer
+        runs that pass itself);
+      * the middle layer's apply pass on sums its consumer handed over (what the default switches run there);
+      * the middle layer's forward between its statistics GEMM and its apply pass: sums of the first layer then still sit in
+        the buffer the bookkeeping calls clean, and only the clear owed after a failure removes them."""
+    from gkgnet_amd import _lib, bn_scratch, fused
+    monkeypatch.setattr(bn_scratch._BnScratch, "_inst", {})
+    torch.manual_seed(13)
+    R, C = 640, 64
+    convs = [torch.nn.Conv2d(C, C, 1).cuda() for _ in range(3)]
+    bns = [torch.nn.BatchNorm2d(C).cuda().train() for _ in range(3)]
+    x = torch.randn(R, C, device="cuda", requires_grad=True)
+    params = [p for m in convs + bns for p in m.parameters()]
+
+    def step():
+        h = x
+        for conv, bn in zip(convs, bns):
+            h = fused._LinearBNAct.apply(h, conv.weight, conv.bias, bn.weight, bn.bias, None, bn, 1, None)
+        grads = torch.autograd.grad(h.square().mean(), [x] + params, allow_unused=True)
+        torch.cuda.synchronize()
+        return [h.detach().clone()] + [g.clone() for g in grads if g is not None]
+
+    ref = step()
+    for switches, name, nth in [({"DGRAD_STATS": False}, "gkg_bn_bwd_atomic", 2),
+                                ({}, "gkg_bn_bwd_apply_from_sums", 1),
+                                ({}, "gkg_linear_bn_fwd_x6 (statistics only)", 2)]:
+        with monkeypatch.context() as m:
+            for k, v in switches.items():
+                m.setattr(fused, k, v)
+            fired = _fail_once_after(m, name, nth)
+            with pytest.raises(_lib.GkgError, match="injected after the launch"):
+                step()
+            assert fired, (name, "was never called", nth, "times")
+        torch.cuda.synchronize()
+        for i, (a, b) in enumerate(zip(step(), ref)):
+            assert torch.allclose(a, b, rtol=1e-4, atol=1e-6), (name, i, float((a - b).abs().max()))
+
+
+def test_bn_scratch_recovers_after_a_failed_block_driver_call(monkeypatch):
+    """The same through the block driver (bn_scratch.one_call), at the smallest Grapher of tests/test_hip_block_driver.py: the
+    driver's backward call raises after it has issued its launches; the next step equals an undisturbed one to rounding (that
+    file's bounds for two runs of one path: BN statistics and weight gradients are accumulated with atomics)."""
+    from gkgnet_amd import _lib, block, bn_scratch
+    from gkgnet_amd.grapher import Grapher
+    monkeypatch.setattr(bn_scratch._BnScratch, "_inst", {})
+    monkeypatch.setattr(block, "ENABLED", True)
+    torch.manual_seed(0)
+    x = torch.randn(4, 64, 12, 12, device="cuda", requires_grad=True)
+    g = Grapher(64, 9, 1, "mr", "gelu", "batch", True, False, 0.2, 1, n=144, relative_pos=True, use_multi_group=True, num_group=2).cuda().train()
+    params = [p for p in g.parameters() if p.requires_grad]
+    cx = torch.randn(4, 64, 12, 12, device="cuda")
+
+    def step():
+        out = g(x)
+        grads = torch.autograd.grad(out, [x] + params, cx, allow_unused=True)      # conv biases: folded, no gradient
+        torch.cuda.synchronize()
+        return [out.detach().clone()] + [t.clone() for t in grads if t is not None]
+
+    ref = step()
+    with monkeypatch.context() as m:
+        fired = _fail_once_after(m, "gkg_grapher_bwd", 1)
+        with pytest.raises(_lib.GkgError, match="injected after the launch"):
+            step()
+        assert fired, "the block driver did not run"
+    torch.cuda.synchronize()
+    for i, (a, b) in enumerate(zip(step(), ref)):
+        top = float(b.abs().max())
+        if i < 2:                                            # the output and the input gradient
+            assert float((a - b).abs().max()) <= 2e-5 * top + 1e-6, (i, float((a - b).abs().max()), top)
+        elif a.dim() >= 2:                                   # weight gradients: slabs added with fp32 atomics
+            assert torch.allclose(a, b, rtol=1e-4, atol=1e-3 * top + 1e-6), (i, float((a - b).abs().max()), top)
+        else:                                                # BN gammas / betas: plain stores of fp64-accumulated sums
+            assert torch.allclose(a, b, rtol=1e-5, atol=1e-5 * top + 1e-7), (i, float((a - b).abs().max()), top)
+
+
 def test_random_shapes_forward_dgrad_wgrad():
     """Seeded sweep over ragged shapes (rows / channels not multiples of the tile sizes, K tails, batches)."""
     from gkgnet_amd import _lib

@@ -32,8 +32,8 @@ def run(bucket, steps=3, with_label=True, prep=True, driver=False, dual_ok=True)
         else:
             for p in params: p.grad = None
         if SCR:
-            from gkgnet_amd.bn_scratch import _BnBwdScratch
-            sc = _BnBwdScratch.of(x.device)
+            from gkgnet_amd.bn_scratch import _BnScratch
+            sc = _BnScratch.of(x.device)
             torch.cuda.synchronize()
             for i in (0, 1):
                 tail = sc.store[i][sc.dirty[i]:]
@@ -60,8 +60,8 @@ _chk = fused._lib.check
 def _check(rc, msg=''):
     _chk(rc, msg)
     if 'statistics only' in msg:
-        from gkgnet_amd.bn_scratch import _BnBwdScratch
-        sc = _BnBwdScratch.of(torch.device('cuda', 0))
+        from gkgnet_amd.bn_scratch import _BnScratch
+        sc = _BnScratch.of(torch.device('cuda', 0))
         torch.cuda.synchronize()
         SUMS.append((sc.cur ^ 1, sc.bufs[sc.cur ^ 1][:512].clone(), sc.bufs[sc.cur][:512].clone()))
 fused._lib.check = _check
