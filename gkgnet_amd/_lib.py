@@ -10,7 +10,7 @@ import os
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GKG_HIP_LIB") or os.path.join(PKG, "libgkg_hip.so")   # GKG_HIP_LIB: same-box A/B of two builds (tools)
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 F32, BF16, F16 = 0, 1, 2
 KNN_NORMALIZE = 1
 KNN_BF16_CONTRACT = 2
@@ -89,7 +89,8 @@ EXPORTS = ("gkg_version", "gkg_last_error_string", "gkg_knn_workspace_bytes", "g
            "gkg_grapher_fwd", "gkg_grapher_bwd", "gkg_grapher_label_fwd", "gkg_grapher_label_bwd",
            "gkg_gconv_workspace_bytes", "gkg_gin_fwd", "gkg_gin_bwd", "gkg_gat_fwd", "gkg_gat_bwd",
            "gkg_bn_eval_bwd", "gkg_nchw_to_tm_add_bnstats", "gkg_mr_bwd_tm_bnstats", "gkg_linear_dgrad_x6_nchw",
-           "gkg_mr_bwd_tm_bnstats_supported", "gkg_linear_dgrad_x6_bnbwd_sk", "gkg_linear_dgrad_x6_bnbwd_sk_supported")
+           "gkg_mr_bwd_tm_bnstats_supported", "gkg_linear_dgrad_x6_bnbwd_sk", "gkg_linear_dgrad_x6_bnbwd_sk_supported",
+           "gkg_affine_knn_prep")
 PROF_KERNELS = ("token_prep", "knn_tile", "knn_merge", "mr_fwd", "mr_bwd", "gemm_x6")
 
 _lib = None
@@ -142,6 +143,8 @@ def load():
     lib.gkg_mr_fwd_tm16.argtypes = [V, I, I] + [V] * 4 + [I] * 9 + [V]
     lib.gkg_bn_apply_knn_prep.restype = I
     lib.gkg_bn_apply_knn_prep.argtypes = [V] * 13 + [I] * 11 + [C.c_uint, I, I, V, V, V, Z, F, F, V, Z, V]
+    lib.gkg_affine_knn_prep.restype = I
+    lib.gkg_affine_knn_prep.argtypes = [V] * 4 + [I] * 11 + [C.c_uint, I, I, V, V, V, Z, V]
     lib.gkg_avgpool_tm.restype = I
     lib.gkg_avgpool_tm.argtypes = [V, I, I, V, I, I, I, I, I, V]
     lib.gkg_knn_fwd_tm16.restype = I

@@ -7,7 +7,10 @@ one by one.  Here the host allocates two arenas (what the forward saves, what th
 and sizes and makes one call; the C side issues the same launches with the same arguments, so the results are bit-identical to the
 composition (tests/test_hip_block_driver.py).  Taken automatically for the form the metric is quoted on — fp32, train-mode
 BatchNorm with rank-local statistics, no DropPath scaling, un-pooled keys, every projection on the split-bf16 kernels, blocks
-below the BN-epilogue row count; everything else keeps the composition.  GKG_DISABLE=block_driver: off."""
+below the BN-epilogue row count — and for the same block with EVERY BatchNorm frozen (eval mode with running statistics:
+``layers.freeze_batchnorm``, ``norm_eval``, ``eval()`` with gradients; a frozen SyncBatchNorm too): the descriptor's ``bn_frozen``
+form, which writes no statistics and returns the conv biases' gradients (tests/test_hip_frozen_block_driver.py).  A block with
+some layers frozen and some not, and everything else, keeps the composition.  GKG_DISABLE=block_driver: off."""
 from __future__ import annotations
 
 import ctypes as C
@@ -25,7 +28,7 @@ V, I, Z, F, U = C.c_void_p, C.c_int, C.c_size_t, C.c_float, C.c_uint
 class ProjBN(C.Structure):
     _fields_ = [("planes_fwd", V), ("planes_dgrad", V), ("gamma", V), ("beta", V), ("bias", V), ("running_mean", V), ("running_var", V),
                 ("nbt", V), ("momentum", F), ("eps", F), ("cin", I), ("cout", I), ("nb", I), ("fsum", V), ("fzero", V), ("fzero_n", Z),
-                ("bsum", V), ("bzero", V), ("bzero_n", Z), ("Y", V), ("bn", V), ("dw", V), ("dgamma", V), ("dbeta", V)]
+                ("bsum", V), ("bzero", V), ("bzero_n", Z), ("Y", V), ("bn", V), ("dw", V), ("dgamma", V), ("dbeta", V), ("dbias", V)]
 
 
 class GraphOp(C.Structure):
@@ -38,14 +41,14 @@ class GrapherBlock(C.Structure):
                 ("fc1", ProjBN), ("conv", ProjBN), ("fc2", ProjBN), ("graph", GraphOp), ("sk_ws", V), ("sk_bytes", Z),
                 ("keys_G", I), ("keys_L", I), ("keys_k", I), ("keys_d", I), ("keys_fused_mr", I), ("keys_flags", U), ("keys_ws", V),
                 ("keys_ws_bytes", Z), ("dout", V), ("dout_tm", V), ("dx", V), ("g3", V), ("dY3", V), ("dA2", V), ("dY2", V), ("dXM", V),
-                ("gx1", V), ("dY1", V), ("dxt", V), ("bwd_flags", U)]
+                ("gx1", V), ("dY1", V), ("dxt", V), ("bwd_flags", U), ("bn_frozen", I)]
 
 
 class LabelBlock(C.Structure):
     _fields_ = [("B", I), ("C", I), ("L", I), ("M", I), ("e", V), ("ft", V), ("out", V), ("XM", V), ("A2", V), ("h2", V), ("f1", V),
                 ("fc1", ProjBN), ("conv", ProjBN), ("fc2", ProjBN), ("ffn1", ProjBN), ("ffn2", ProjBN), ("graph", GraphOp), ("sk_ws", V),
                 ("sk_bytes", Z), ("dout", V), ("de", V), ("dft", V), ("dY5", V), ("df1", V), ("dY4", V), ("dh2", V), ("dY3", V),
-                ("dA2", V), ("dY2", V), ("dXM", V), ("gx1", V), ("dY1", V), ("bwd_flags", U)]
+                ("dA2", V), ("dY2", V), ("dXM", V), ("gx1", V), ("dY1", V), ("bwd_flags", U), ("bn_frozen", I)]
 
 
 ENABLED = "block_driver" not in fused._DISABLED
@@ -68,12 +71,29 @@ def _bind(lib):
 
 
 # ----------------------------------------------------------------------------------------------- eligibility
-def _proj_ok(seq, R, cin, cout, nb) -> bool:
+def _frozen(bn) -> bool:
+    """A BatchNorm that normalises with its running statistics and does not update them (eval mode, statistics present)."""
+    return (not bn.training and bool(bn.track_running_stats) and bn.running_mean is not None and bn.running_var is not None)
+
+
+def _proj_ok(seq, R, cin, cout, nb, frozen=False) -> bool:
+    """One projection + BN in the driver's scope, in train mode or (``frozen``) on its running statistics."""
     conv, bn = seq[0], seq[1]
-    return (conv.weight.dtype == _F32 and bn.weight.dtype == _F32 and bn.training and fused._bn_ok(bn) and fused._sync_group(bn) is None
-            and isinstance(bn, torch.nn.modules.batchnorm._BatchNorm)
-            and fused._x6_rule(R, cin, cout, nb, "fwd") and fused._derive_ok(bn, nb, cout, _lib.F32, False)
-            and (conv.bias is None or conv.bias.dtype == _F32))
+    if not (conv.weight.dtype == _F32 and bn.weight.dtype == _F32 and fused._bn_ok(bn) and fused._sync_group(bn) is None
+            and isinstance(bn, torch.nn.modules.batchnorm._BatchNorm) and fused._x6_rule(R, cin, cout, nb, "fwd")
+            and (conv.bias is None or conv.bias.dtype == _F32)):
+        return False
+    if frozen:
+        return (_frozen(bn) and bn.running_mean.dtype == _F32 and bn.running_var.dtype == _F32
+                and fused._BnScratch.fits(2 * nb * cout))
+    return bn.training and fused._derive_ok(bn, nb, cout, _lib.F32, False)
+
+
+def _block_mode(bn):
+    """The mode every projection of a block must share, read off its first BN: True frozen, False train, None neither."""
+    if bn.training:
+        return False
+    return True if _frozen(bn) else None
 
 
 def _common_ok(x) -> bool:
@@ -100,7 +120,9 @@ def grapher_ok(mod, x, relative_pos, groups, want_edge, dual) -> bool:
     if (gc.r != 1 or Cc % 16 or (Cc // groups) % 4 or T >= fused.BN_EPILOGUE_MIN_ROWS or len(nn_) != 3
             or _drops(mod.drop_path) or H * W > 65536):
         return False
-    if not (_proj_ok(mod.fc1, T, Cc, Cc, 1) and _proj_ok(nn_, T, Cc // 2, Cc // 2, 4) and _proj_ok(mod.fc2, T, 2 * Cc, Cc, 1)):
+    fz = _block_mode(mod.fc1[1])
+    if fz is None or not (_proj_ok(mod.fc1, T, Cc, Cc, 1, fz) and _proj_ok(nn_, T, Cc // 2, Cc // 2, 4, fz)
+                          and _proj_ok(mod.fc2, T, 2 * Cc, Cc, 1, fz)):
         return False
     if nn_[0].groups != 4 or tuple(nn_[0].weight.shape[:2]) != (2 * Cc, Cc // 2) or not isinstance(nn_[2], torch.nn.GELU):
         return False
@@ -123,8 +145,10 @@ def label_ok(mod, e, ft, groups) -> bool:
         return False
     if nn_[0].groups != 4 or tuple(nn_[0].weight.shape[:2]) != (2 * Cc, Cc // 2):
         return False
-    return (_proj_ok(mod.fc1, T, Cc, Cc, 1) and _proj_ok(nn_, T, Cc // 2, Cc // 2, 4) and _proj_ok(mod.fc2, T, 2 * Cc, Cc, 1)
-            and _proj_ok(mod.ffn.fc1, T, Cc, Cf, 1) and _proj_ok(mod.ffn.fc2, T, Cf, Cc, 1))
+    fz = _block_mode(mod.fc1[1])
+    return (fz is not None and _proj_ok(mod.fc1, T, Cc, Cc, 1, fz) and _proj_ok(nn_, T, Cc // 2, Cc // 2, 4, fz)
+            and _proj_ok(mod.fc2, T, 2 * Cc, Cc, 1, fz) and _proj_ok(mod.ffn.fc1, T, Cc, Cf, 1, fz)
+            and _proj_ok(mod.ffn.fc2, T, Cf, Cc, 1, fz))
 
 
 # ----------------------------------------------------------------------------------------------- plans
@@ -183,16 +207,20 @@ def _layout(sizes):
 
 class _Plan:
     __slots__ = ("kind", "projs", "ident", "tensors", "ptrs", "tmpl", "fwd_offs", "fwd_total", "bwd_offs", "bwd_total", "drops",
-                 "sync", "gc", "nn_", "k", "d", "groups", "dims", "rp", "rp_view", "fast", "params", "fm", "has_bucket", "__weakref__")
+                 "sync", "gc", "nn_", "k", "d", "groups", "dims", "rp", "rp_view", "fast", "params", "fm", "has_bucket", "frozen",
+                 "gelus", "__weakref__")
 
     def valid(self) -> bool:
         for dct, key, obj in self.ident:
             if dct.get(key) is not obj:
                 return False
+        frozen = self.frozen
         for p in self.projs:
             bn = p.bn
-            if (not bn.training or bn.track_running_stats != p.trs or bn.momentum != p.mom or bn.eps != p.eps
-                    or p.W.shape != p.wreal or p.W.dtype != _F32):
+            # (the recorded mode: a BN switched in either direction drops the plan; the tensors behind a frozen layer's running
+            # statistics are among self.ident / self.tensors)
+            if (bn.training == frozen or bn.track_running_stats != p.trs or bn.momentum != p.mom or bn.eps != p.eps
+                    or not bn.affine or p.W.shape != p.wreal or p.W.dtype != _F32):
                 return False
         if self.ptrs != [t.data_ptr() for t in self.tensors]:
             return False
@@ -200,8 +228,13 @@ class _Plan:
             if _drops(dp):
                 return False
         gc = self.gc
-        if gc.k != self.k or gc.d != self.d:
+        if gc.k != self.k or gc.d != self.d or gc.r != 1 or getattr(gc.dilated_knn_graph, "stochastic", False):
             return False
+        if self.nn_[0].groups != 4:
+            return False
+        for m in self.gelus():
+            if not isinstance(m, torch.nn.GELU):
+                return False
         if self.sync:
             for p in self.projs:
                 if fused._sync_group(p.bn) is not None:
@@ -212,20 +245,25 @@ class _Plan:
 def _finish_plan(plan, mod, cls, projs, ident, drops, gc, nn_, groups, dims, relative_pos, fwd_sizes, bwd_sizes):
     plan.projs, plan.ident, plan.drops, plan.gc, plan.nn_, plan.groups, plan.dims = projs, ident, drops, gc, nn_, groups, dims
     plan.k, plan.d = gc.k, gc.d
+    plan.frozen = not projs[0].bn.training                 # (grapher_ok / label_ok: every projection in the same mode)
+    ffn = mod._modules.get("ffn")
+    plan.gelus = (lambda: (nn_[2],)) if ffn is None else (lambda: (nn_[2], ffn.act))
     plan.tensors = [t for p in projs for t in p.baked()]
     plan.ptrs = [t.data_ptr() for t in plan.tensors]
     plan.sync = any(isinstance(p.bn, torch.nn.SyncBatchNorm) for p in projs)
     plan.fwd_offs, plan.fwd_total = _layout(fwd_sizes)
     plan.bwd_offs, plan.bwd_total = _layout(bwd_sizes)
-    plan.params = tuple(t for p in projs for t in (p.W, p.gamma, p.beta))
+    # the autograd inputs: a conv bias in front of a frozen BN has a real gradient (in train mode it is exactly zero: no input)
+    plan.params = tuple(t for p in projs for t in ((p.W, p.gamma, p.beta, p.bias) if plan.frozen else (p.W, p.gamma, p.beta)))
     plan.fm = {}
     own = mod._parameters.get("relative_pos", mod.__dict__.get("relative_pos"))
-    plan.rp = relative_pos
     plan.fast = relative_pos is None or relative_pos is own        # a re-interpolated bias is a new tensor every call: slow path
+    plan.rp = relative_pos if plan.fast else None                  # (a slow plan must not keep that call's tensor alive)
     plan.rp_view = None
     if relative_pos is not None and plan.fast:
         ident.append((mod._parameters, "relative_pos", relative_pos))
     d = cls()
+    d.bn_frozen = int(plan.frozen)
     names = [f[0] for f in cls._fields_ if f[1] is ProjBN]
     for nm, p in zip(names, projs):
         p.static(getattr(d, nm))
@@ -293,14 +331,15 @@ def _proj_fwd(lib, p: ProjBN, pr: _Proj, scratch, keep, y_ptr, bn_ptr):
     """The per-call half of a projection's forward descriptor: weight planes (refreshed when the weight moved), the BN pass's
     scratch buffers, where Y and the BN coefficients go."""
     pf, pd = fused._planes(lib, pr.W, pr.nb, pr.cout, pr.cin, True, True, kperm=pr.kperm)
-    if pr.trs:
-        ep = pr.bn.__dict__.get("_gkg_epoch")
-        if ep is not None:
-            pr.bn.__dict__["_gkg_epoch"] = ep + 1             # fused._touch_stats: the kernels update the running statistics
-    cur, other, zero = scratch.acquire(lib, 2 * pr.nch)
     p.planes_fwd, p.planes_dgrad = pf.data_ptr(), pd.data_ptr()
-    p.fsum, p.fzero, p.fzero_n = cur.data_ptr(), other.data_ptr(), zero
     p.Y, p.bn = y_ptr, bn_ptr
+    if scratch is not None:                                   # (None: a frozen layer — no statistics pass, nothing written back)
+        if pr.trs:
+            ep = pr.bn.__dict__.get("_gkg_epoch")
+            if ep is not None:
+                pr.bn.__dict__["_gkg_epoch"] = ep + 1         # fused._touch_stats: the kernels update the running statistics
+        cur, other, zero = scratch.acquire(lib, 2 * pr.nch)
+        p.fsum, p.fzero, p.fzero_n = cur.data_ptr(), other.data_ptr(), zero
     keep.append(pf)
     keep.append(pd)
 
@@ -314,6 +353,51 @@ def _proj_bwd(lib, p: ProjBN, pr: _Proj, scratch, dev):
     p.bsum, p.bzero, p.bzero_n = cur.data_ptr(), other.data_ptr(), zero
     p.dw, p.dgamma, p.dbeta = dWv.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr()
     return dWv, dgamma, dbeta
+
+
+class _NoScratch:
+    """Stands in for the BN scratch pair where a frozen block uses none (no statistics pass in the forward, no parameter gradient
+    wanted in the backward): nothing is created, acquired or marked."""
+    def __enter__(self):
+        return None
+
+    def __exit__(self, et, ev, tb):
+        return False
+
+
+_NO_SCRATCH = _NoScratch()
+
+
+def _want_1d(need, projs) -> bool:
+    """Whether a frozen block's backward computes any gamma / beta / conv-bias gradient (``need``: the needs_input_grad slice of
+    its parameters, four per projection)."""
+    return any(need[4 * i + 1] or need[4 * i + 2] or (need[4 * i + 3] and pr.bias is not None) for i, pr in enumerate(projs))
+
+
+def _slot(param, n, dev):
+    """Where a 1-D parameter gradient goes: the parameter's gradient-bucket slot, else a fresh tensor."""
+    v = fused.grad_view(param, (n,)) if param.dtype == _F32 else None
+    return torch.empty(n, dtype=_F32, device=dev) if v is None else v
+
+
+def _proj_bwd_frozen(lib, p: ProjBN, pr: _Proj, scratch, dev, want):
+    """Backward half of a frozen layer -> (dW, dgamma, dbeta, dbias).  ``want``: ctx.needs_input_grad of (W, gamma, beta, bias);
+    only the wanted 1-D gradients get a pointer (gkg_bn_eval_bwd computes those and nothing else), and the scratch pair is
+    acquired only when there is one.  The weight gradient is always computed, like the composition's."""
+    wv = fused.grad_view(pr.W, pr.wshape) if pr.W.dtype == _F32 else None
+    dWv = torch.empty(pr.wshape, dtype=_F32, device=dev) if wv is None else wv
+    if not getattr(dWv, "_gkg_zero", False):
+        dWv.zero_()                                      # the weight-gradient kernels ADD into dw
+    dgamma = _slot(pr.gamma, pr.nch, dev) if want[1] else None
+    dbeta = _slot(pr.beta, pr.nch, dev) if want[2] else None
+    dbias = _slot(pr.bias, pr.nch, dev) if (want[3] and pr.bias is not None) else None
+    if dgamma is not None or dbeta is not None or dbias is not None:
+        cur, other, zero = scratch.acquire(lib, 2 * pr.nch)
+        p.bsum, p.bzero, p.bzero_n = cur.data_ptr(), other.data_ptr(), zero
+    else:
+        p.bsum, p.bzero, p.bzero_n = None, None, 0
+    p.dw, p.dgamma, p.dbeta, p.dbias = dWv.data_ptr(), _ptr(dgamma), _ptr(dbeta), _ptr(dbias)
+    return dWv, dgamma, dbeta, dbias
 
 
 def _graph_op(lib, plan, g: GraphOp, B, G, c, N, M, relative_pos, has_y, want_edge, dev, keys_key, keep):
@@ -367,7 +451,8 @@ def _issue_wgrads(lib, wq, n, outs, keep, device):
 # ----------------------------------------------------------------------------------------------- Grapher
 class _GrapherBlockFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w1, g1, b1, wc, gc_, bc, w2, g2, b2, plan, relative_pos, label_knn, dual):
+    def forward(ctx, x, plan, relative_pos, label_knn, dual, *params):
+        # params: (W, gamma, beta) of fc1, the grouped projection and fc2 — with the conv bias as a fourth for a frozen block
         lib = _lib.load()
         _bind(lib)
         B, Cc, H, W = plan.dims
@@ -376,7 +461,7 @@ class _GrapherBlockFn(torch.autograd.Function):
         x = x.contiguous()
         d = GrapherBlock.from_buffer_copy(plan.tmpl)
         keep = []
-        scratch = fused._BnScratch.of(dev)
+        scratch = None if plan.frozen else fused._BnScratch.of(dev)
         buf = torch.empty(plan.fwd_total, dtype=_F32, device=dev)
         base = buf.data_ptr()
         oxt, oXM, oA2, oY1, oY2, oY3, ob1, ob2, ob3, oarg = [base + 4 * o for o in plan.fwd_offs]
@@ -386,7 +471,7 @@ class _GrapherBlockFn(torch.autograd.Function):
         d.x, d.out, d.out_tm = x.data_ptr(), out.data_ptr(), _ptr(out_tm)
         d.xt, d.XM, d.A2 = oxt, oXM, oA2
         p1, pc, p2 = plan.projs
-        with scratch.one_call():
+        with (_NO_SCRATCH if scratch is None else scratch.one_call()):
             _proj_fwd(lib, d.fc1, p1, scratch, keep, oY1, ob1)
             _proj_fwd(lib, d.conv, pc, scratch, keep, oY2, ob2)
             _proj_fwd(lib, d.fc2, p2, scratch, keep, oY3, ob3)
@@ -406,7 +491,8 @@ class _GrapherBlockFn(torch.autograd.Function):
             _lib.check(lib.gkg_grapher_fwd(C.byref(d), _stream()), "gkg_grapher_fwd")
         if kk is not None:
             out_tm._gkg_knn_keys = kk
-        ctx.save_for_backward(buf, w1, wc, w2)
+        st = 4 if plan.frozen else 3
+        ctx.save_for_backward(buf, params[0], params[st], params[2 * st])
         ctx.desc = d
         ctx.plan = plan
         if dual:
@@ -420,7 +506,7 @@ class _GrapherBlockFn(torch.autograd.Function):
         plan = ctx.plan
         B, Cc, H, W = plan.dims
         if dout is None and dtm is None:
-            return (None,) * 14
+            return (None,) * (5 + (12 if plan.frozen else 9))
         buf, w1, wc, w2 = ctx.saved_tensors
         T, dev = B * H * W, buf.device
         d = ctx.desc
@@ -434,20 +520,26 @@ class _GrapherBlockFn(torch.autograd.Function):
         dtm_c = None if dtm is None else dtm.contiguous()
         d.dout, d.dout_tm, d.dx = dout_c.data_ptr(), _ptr(dtm_c), dx.data_ptr()
         d.bwd_flags = fused._block_flags()
-        scratch = fused._BnScratch.of(dev)
+        need = ctx.needs_input_grad
+        scratch = fused._BnScratch.of(dev) if (not plan.frozen or _want_1d(need[5:], plan.projs)) else None
         wq = (_lib.WgradProblem * 3)()
         p1, pc, p2 = plan.projs
-        with scratch.one_call():
-            o2 = _proj_bwd(lib, d.fc2, p2, scratch, dev)
-            oc = _proj_bwd(lib, d.conv, pc, scratch, dev)
-            o1 = _proj_bwd(lib, d.fc1, p1, scratch, dev)
+        with (_NO_SCRATCH if scratch is None else scratch.one_call()):
+            if plan.frozen:
+                o2 = _proj_bwd_frozen(lib, d.fc2, p2, scratch, dev, need[13:17])
+                oc = _proj_bwd_frozen(lib, d.conv, pc, scratch, dev, need[9:13])
+                o1 = _proj_bwd_frozen(lib, d.fc1, p1, scratch, dev, need[5:9])
+            else:
+                o2 = _proj_bwd(lib, d.fc2, p2, scratch, dev)
+                oc = _proj_bwd(lib, d.conv, pc, scratch, dev)
+                o1 = _proj_bwd(lib, d.fc1, p1, scratch, dev)
             _lib.check(lib.gkg_grapher_bwd(C.byref(d), wq, _stream()), "gkg_grapher_bwd")
         _issue_wgrads(lib, wq, 3, (o2[0], oc[0], o1[0]), (buf, tbuf, dout_c, dtm_c), dev)
-        return (dx, o1[0].view_as(w1), o1[1], o1[2], oc[0].view_as(wc), oc[1], oc[2], o2[0].view_as(w2), o2[1], o2[2], None, None, None, None)
+        return (dx, None, None, None, None, o1[0].view_as(w1), *o1[1:], oc[0].view_as(wc), *oc[1:], o2[0].view_as(w2), *o2[1:])
 
 
 def _run_grapher(plan, mod, x, relative_pos, dual):
-    res = _GrapherBlockFn.apply(x, *plan.params, plan, relative_pos, mod.__dict__.get("_gkg_label_knn"), dual)
+    res = _GrapherBlockFn.apply(x, plan, relative_pos, mod.__dict__.get("_gkg_label_knn"), dual, *plan.params)
     out = res[0] if dual else res
     if dual:
         out._gkg_tm = (out._version, res[1])
@@ -477,7 +569,8 @@ def try_grapher(mod, x):
 # ----------------------------------------------------------------------------------------------- GrapherLabel
 class _LabelBlockFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, e2, ft, w1, g1, b1, wc, gc_, bc, w2, g2, b2, w4, g4, b4, w5, g5, b5, plan, keys_key, producer):
+    def forward(ctx, e2, ft, plan, keys_key, producer, *params):
+        # params: (W, gamma, beta) of fc1, the grouped projection, fc2, FFN fc1 and FFN fc2 — + the conv bias for a frozen block
         lib = _lib.load()
         _bind(lib)
         B, Cc, L, M, Cf = plan.dims
@@ -485,7 +578,7 @@ class _LabelBlockFn(torch.autograd.Function):
         groups = plan.groups
         d = LabelBlock.from_buffer_copy(plan.tmpl)
         keep = []
-        scratch = fused._BnScratch.of(dev)
+        scratch = None if plan.frozen else fused._BnScratch.of(dev)
         buf = torch.empty(plan.fwd_total, dtype=_F32, device=dev)
         base = buf.data_ptr()
         oXM, oA2, oh2, of1, oY1, oY2, oY3, oY4, oY5, ob1, ob2, ob3, ob4, ob5, oarg = [base + 4 * o for o in plan.fwd_offs]
@@ -493,7 +586,7 @@ class _LabelBlockFn(torch.autograd.Function):
         d.B, d.C, d.L, d.M = B, Cc, L, M
         d.e, d.ft, d.out = e2.data_ptr(), ft.data_ptr(), out.data_ptr()
         d.XM, d.A2, d.h2, d.f1 = oXM, oA2, oh2, of1
-        with scratch.one_call():
+        with (_NO_SCRATCH if scratch is None else scratch.one_call()):
             for p, pr, oy, ob in zip((d.fc1, d.conv, d.fc2, d.ffn1, d.ffn2), plan.projs, (oY1, oY2, oY3, oY4, oY5), (ob1, ob2, ob3, ob4, ob5)):
                 _proj_fwd(lib, p, pr, scratch, keep, oy, ob)
             key, edge = _graph_op(lib, plan, d.graph, B, groups, Cc // groups, L, M, None, True, True, dev, keys_key, keep)
@@ -505,7 +598,7 @@ class _LabelBlockFn(torch.autograd.Function):
             lk = (groups, L, plan.k, plan.d, key.fused_mr)                 # the Grapher in front prepares this graph's keys
             if producer.__dict__.get("_gkg_label_knn") != lk:              # from its next call on (fused.grapher_label_forward)
                 producer._gkg_label_knn = lk
-        ctx.save_for_backward(buf, e2, ft, w1, wc, w2, w4, w5)
+        ctx.save_for_backward(buf, e2, ft, *params[::4 if plan.frozen else 3])
         ctx.desc = d
         ctx.plan = plan
         ctx.mark_non_differentiable(edge)
@@ -515,9 +608,9 @@ class _LabelBlockFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout, _gedge=None):
         lib = _lib.load()
-        if dout is None:
-            return (None,) * 20
         plan = ctx.plan
+        if dout is None:
+            return (None,) * (5 + (20 if plan.frozen else 15))
         B, Cc, L, M, Cf = plan.dims
         T = B * L
         buf, e2, ft, w1, wc, w2, w4, w5 = ctx.saved_tensors
@@ -531,25 +624,33 @@ class _LabelBlockFn(torch.autograd.Function):
         dout_c = dout.contiguous()
         d.dout, d.de, d.dft = dout_c.data_ptr(), de.data_ptr(), dft.data_ptr()
         d.bwd_flags = fused._block_flags()
-        scratch = fused._BnScratch.of(dev)
+        need = ctx.needs_input_grad
+        scratch = fused._BnScratch.of(dev) if (not plan.frozen or _want_1d(need[5:], plan.projs)) else None
         wq = (_lib.WgradProblem * 5)()
         p1, pc, p3, p4, p5 = plan.projs
-        with scratch.one_call():
-            o5 = _proj_bwd(lib, d.ffn2, p5, scratch, dev)
-            o4 = _proj_bwd(lib, d.ffn1, p4, scratch, dev)
-            o3 = _proj_bwd(lib, d.fc2, p3, scratch, dev)
-            oc = _proj_bwd(lib, d.conv, pc, scratch, dev)
-            o1 = _proj_bwd(lib, d.fc1, p1, scratch, dev)
+        with (_NO_SCRATCH if scratch is None else scratch.one_call()):
+            if plan.frozen:
+                o5 = _proj_bwd_frozen(lib, d.ffn2, p5, scratch, dev, need[21:25])
+                o4 = _proj_bwd_frozen(lib, d.ffn1, p4, scratch, dev, need[17:21])
+                o3 = _proj_bwd_frozen(lib, d.fc2, p3, scratch, dev, need[13:17])
+                oc = _proj_bwd_frozen(lib, d.conv, pc, scratch, dev, need[9:13])
+                o1 = _proj_bwd_frozen(lib, d.fc1, p1, scratch, dev, need[5:9])
+            else:
+                o5 = _proj_bwd(lib, d.ffn2, p5, scratch, dev)
+                o4 = _proj_bwd(lib, d.ffn1, p4, scratch, dev)
+                o3 = _proj_bwd(lib, d.fc2, p3, scratch, dev)
+                oc = _proj_bwd(lib, d.conv, pc, scratch, dev)
+                o1 = _proj_bwd(lib, d.fc1, p1, scratch, dev)
             _lib.check(lib.gkg_grapher_label_bwd(C.byref(d), wq, _stream()), "gkg_grapher_label_bwd")
         _issue_wgrads(lib, wq, 5, (o5[0], o4[0], o3[0], oc[0], o1[0]), (buf, tbuf, e2, dout_c), dev)
-        return (de, dft, o1[0].view_as(w1), o1[1], o1[2], oc[0].view_as(wc), oc[1], oc[2], o3[0].view_as(w2), o3[1], o3[2],
-                o4[0].view_as(w4), o4[1], o4[2], o5[0].view_as(w5), o5[1], o5[2], None, None, None)
+        return (de, dft, None, None, None, o1[0].view_as(w1), *o1[1:], oc[0].view_as(wc), *oc[1:], o3[0].view_as(w2), *o3[1:],
+                o4[0].view_as(w4), *o4[1:], o5[0].view_as(w5), *o5[1:])
 
 
 def label_forward(mod, e2, ft, groups, keys_key, producer=None):
     """After label_ok(): the block through the driver (fused.grapher_label_forward; builds the plan the next calls go through)."""
     plan = _plan_label(mod, e2, ft, groups)
-    return _LabelBlockFn.apply(e2, ft, *plan.params, plan, keys_key, producer)
+    return _LabelBlockFn.apply(e2, ft, plan, keys_key, producer, *plan.params)
 
 
 def try_label(mod, e, features):
@@ -567,5 +668,5 @@ def try_label(mod, e, features):
     if plan is None or not plan.valid():
         return None
     ft, keys_key, producer = fused._label_features(features, B, Cc)
-    out, edge = _LabelBlockFn.apply(e.view(B * L, Cc), ft, *plan.params, plan, keys_key, producer)
+    out, edge = _LabelBlockFn.apply(e.view(B * L, Cc), ft, plan, keys_key, producer, *plan.params)
     return out.view(B, L, Cc), edge

@@ -4,7 +4,9 @@
 // (include/gkg_hip.h), called in the order and with the arguments the Python composition (gkgnet_amd/fused.py) uses for the same
 // block — so the results are bit-identical to that composition (tests/test_hip_block_driver.py) — and the host side shrinks to
 // "allocate, fill a descriptor, call".  Scope: the fp32 training form (train-mode BatchNorm with rank-local statistics, no
-// DropPath scaling, un-pooled keys r == 1, every projection on the split-bf16 kernels); everything else keeps the composition.
+// DropPath scaling, un-pooled keys r == 1, every projection on the split-bf16 kernels) and its all-frozen form (bn_frozen: every
+// BatchNorm of the block in eval mode — running statistics, nothing but gradients written back); everything else keeps the
+// composition.
 // The library still allocates nothing and keeps no state: the descriptor carries every buffer, including the fp64 column-sum
 // scratch pair the caller alternates between BN passes.
 #include "gkg_common.h"
@@ -96,6 +98,102 @@ int mr_bwd_bn(const GkgProjBN& p, const GkgGraphOp& g, bool fuse, const float* d
   GKG_TRY(gkg_mr_bwd_tm(dXM, nullptr, arg, gx1, gsrc, B, g.G, C / g.G, N, M, g.k, 1, 1, g.mr_flags, st));
   return proj_bwd(p, gx1, p.cout, 0, T, 0, dY, nullptr, nullptr, 0, 0, nullptr, 0, st);
 }
+// ---- frozen (eval-mode) BatchNorm: the launches fused.py issues for a layer whose BN uses its running statistics ----------------
+// y = x W^T without statistics, then (a, c) folded from the running statistics and the conv bias into p.bn's a | c slots
+int proj_fwd_frozen(const GkgProjBN& p, const float* x, int ldx, size_t x_bstride, int R, void* sk_ws, size_t sk_bytes, void* st) {
+  GKG_TRY(gkg_linear_bn_fwd_x6_sk(x, ldx, x_bstride, p.planes_fwd, p.Y, R, p.cin, p.cout, p.nb, 0, nullptr, nullptr, nullptr, nullptr,
+                                  nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, nullptr, sk_ws, sk_bytes, 0, st));
+  const int n = p.nb * p.cout;
+  return gkg_bn_eval_affine(p.gamma, p.beta, p.bias, p.running_mean, p.running_var, p.bn, p.bn + n, n, p.eps, st);
+}
+int proj_apply_frozen(const GkgProjBN& p, int R, const float* res, float* out, int ldo, size_t obs, int ochunk, int act, void* st) {
+  return gkg_affine_act(p.Y, p.bn, p.bn + p.nb * p.cout, res, out, R, p.cout, p.nb, ldo, obs, ochunk, act, GKG_F32, nullptr, 0, st);
+}
+// fc1's apply: also the k-NN's token preparation when the graph op asks for prepared queries
+int fc1_apply_frozen(const GkgProjBN& p, const GkgGraphOp& g, float* XM, int B, int C, int N, int M, int has_y, void* st) {
+  if (g.knn_flags & GKG_KNN_X_PREPARED)
+    return gkg_affine_knn_prep(p.Y, p.bn, p.bn + C, XM, 2 * C, C / 4, B, g.G, C / g.G, N, M, g.k, g.d, has_y, g.relpos ? 1 : 0,
+                               g.knn_flags & ~(GKG_KNN_X_PREPARED | GKG_KNN_Y_PREPARED), g.fused_mr, 0, nullptr, nullptr, g.knn_ws,
+                               g.knn_ws_bytes, st);
+  return proj_apply_frozen(p, B * N, nullptr, XM, 2 * C, 0, C / 4, 0, st);
+}
+// dY of out = act(BN_eval(Y)): one sweep; with a parameter gradient wanted the sweep takes two column sums into p.bsum and a
+// small second launch finishes dgamma / dbeta / dbias (and clears p.bzero)
+int bn_bwd_frozen(const GkgProjBN& p, const float* g, int ldg, size_t gbs, int R, int act, float* dY, void* st) {
+  const bool want = p.dgamma || p.dbeta || p.dbias;
+  return gkg_bn_eval_bwd(g, p.Y, p.bn, p.bn + p.nb * p.cout, dY, R, p.cout, p.nb, ldg, gbs, act, nullptr, 0, p.running_mean,
+                         p.running_var, p.bias, p.eps, p.dgamma, p.dbeta, p.dbias, want ? p.bsum : nullptr, want ? p.bzero : nullptr,
+                         want ? p.bzero_n : 0, nullptr, 0, st);
+}
+int proj_bwd_frozen(const GkgProjBN& p, const float* g, int ldg, size_t gbs, int R, int act, float* dY, const float* residual, float* dx,
+                    int ldx, size_t x_bstride, void* sk_ws, size_t sk_bytes, void* st) {
+  GKG_TRY(bn_bwd_frozen(p, g, ldg, gbs, R, act, dY, st));
+  return gkg_linear_dgrad_x6_sk(dY, p.cout, (size_t)R * p.cout, p.planes_dgrad, dx, R, p.cin, p.cout, p.nb, residual, sk_ws, sk_bytes, ldx,
+                                x_bstride, 0, st);
+}
+
+// ---- descriptor validation, shared by the four entry points (before any launch) ---------------------------------------------------
+int check_proj(const GkgProjBN& p, bool frozen, bool bwd, const char* who) {
+  if (!p.planes_fwd || !p.planes_dgrad || !p.gamma || !p.beta || !p.Y || !p.bn) return gkg_fail(GKG_ERR_NULL, who);
+  if (frozen ? (!p.running_mean || !p.running_var) : (!p.fsum || (bwd && !p.bsum))) return gkg_fail(GKG_ERR_NULL, who);
+  if (bwd) {
+    if (!p.dw) return gkg_fail(GKG_ERR_NULL, who);
+    if (!frozen && (!p.dgamma || !p.dbeta)) return gkg_fail(GKG_ERR_NULL, who);
+    if (frozen && (p.dgamma || p.dbeta || p.dbias) && !p.bsum) return gkg_fail(GKG_ERR_NULL, who);
+    if (p.dbias && (!frozen || !p.bias)) return gkg_fail(GKG_ERR_SHAPE, who);
+  }
+  return 0;
+}
+int check_graph(const GkgGraphOp& g, int C, const char* who_null, const char* who_shape) {
+  if (g.G <= 0 || C % g.G || g.k <= 0 || g.d <= 0) return gkg_fail(GKG_ERR_SHAPE, who_shape);
+  if (!g.arg || !g.knn_ws) return gkg_fail(GKG_ERR_NULL, who_null);
+  return 0;
+}
+int check_grapher(const GkgGrapherBlock* b, const GkgWgradProblem* wq, bool bwd) {
+  const char* nul = bwd ? "gkg_grapher_bwd: null pointer" : "gkg_grapher_fwd: null pointer";
+  const char* shp = bwd ? "gkg_grapher_bwd: C % 16 == 0, G > 0, C % G == 0; fc1 C -> C, conv 4 x (C/2 -> C/2), fc2 2C -> C"
+                        : "gkg_grapher_fwd: C % 16 == 0, G > 0, C % G == 0; fc1 C -> C, conv 4 x (C/2 -> C/2), fc2 2C -> C";
+  if (!b || (bwd && !wq)) return gkg_fail(GKG_ERR_NULL, nul);
+  const int C = b->C;
+  if (b->B <= 0 || b->H <= 0 || b->W <= 0 || C <= 0 || (C & 15) || b->fc1.nb != 1 || b->conv.nb != 4 || b->fc2.nb != 1 || b->fc1.cin != C ||
+      b->fc1.cout != C || b->conv.cin != C / 2 || b->conv.cout != C / 2 || b->fc2.cin != 2 * C || b->fc2.cout != C)
+    return gkg_fail(GKG_ERR_SHAPE, shp);
+  GKG_TRY(check_graph(b->graph, C, nul, shp));
+  if (b->keys_ws && (b->keys_G <= 0 || C % b->keys_G)) return gkg_fail(GKG_ERR_SHAPE, shp);
+  // what the forward writes and the backward reads: the block's input, the saved activations, the projections
+  if (!b->x || !b->xt || !b->XM || !b->A2) return gkg_fail(GKG_ERR_NULL, nul);
+  const bool frozen = b->bn_frozen != 0;
+  GKG_TRY(check_proj(b->fc1, frozen, bwd, nul));
+  GKG_TRY(check_proj(b->conv, frozen, bwd, nul));
+  GKG_TRY(check_proj(b->fc2, frozen, bwd, nul));
+  if (!bwd) return b->out ? 0 : gkg_fail(GKG_ERR_NULL, nul);
+  if (!b->dout || !b->dx || !b->g3 || !b->dY3 || !b->dA2 || !b->dY2 || !b->dXM || !b->gx1 || !b->dY1 || !b->dxt) return gkg_fail(GKG_ERR_NULL, nul);
+  return 0;
+}
+int check_label(const GkgLabelBlock* b, const GkgWgradProblem* wq, bool bwd) {
+  const char* nul = bwd ? "gkg_grapher_label_bwd: null pointer" : "gkg_grapher_label_fwd: null pointer";
+  const char* shp = bwd ? "gkg_grapher_label_bwd: bad projection shapes (C % 16 == 0, G > 0, C % G == 0)"
+                        : "gkg_grapher_label_fwd: bad projection shapes (C % 16 == 0, G > 0, C % G == 0)";
+  if (!b || (bwd && !wq)) return gkg_fail(GKG_ERR_NULL, nul);
+  const int C = b->C;
+  if (b->B <= 0 || b->L <= 0 || b->M <= 0 || C <= 0 || (C & 15) || b->fc1.nb != 1 || b->conv.nb != 4 || b->fc2.nb != 1 || b->ffn1.nb != 1 ||
+      b->ffn2.nb != 1 || b->fc1.cin != C || b->fc1.cout != C || b->conv.cin != C / 2 || b->conv.cout != C / 2 || b->fc2.cin != 2 * C ||
+      b->fc2.cout != C || b->ffn1.cin != C || b->ffn1.cout <= 0 || b->ffn2.cout != C || b->ffn2.cin != b->ffn1.cout)
+    return gkg_fail(GKG_ERR_SHAPE, shp);
+  GKG_TRY(check_graph(b->graph, C, nul, shp));
+  if (!b->e || !b->ft || !b->XM || !b->A2 || !b->h2 || !b->f1) return gkg_fail(GKG_ERR_NULL, nul);
+  const bool frozen = b->bn_frozen != 0;
+  GKG_TRY(check_proj(b->fc1, frozen, bwd, nul));
+  GKG_TRY(check_proj(b->conv, frozen, bwd, nul));
+  GKG_TRY(check_proj(b->fc2, frozen, bwd, nul));
+  GKG_TRY(check_proj(b->ffn1, frozen, bwd, nul));
+  GKG_TRY(check_proj(b->ffn2, frozen, bwd, nul));
+  if (!bwd) return b->out ? 0 : gkg_fail(GKG_ERR_NULL, nul);
+  if (!b->dout || !b->de || !b->dft || !b->dY5 || !b->df1 || !b->dY4 || !b->dh2 || !b->dY3 || !b->dA2 || !b->dY2 || !b->dXM || !b->gx1 || !b->dY1)
+    return gkg_fail(GKG_ERR_NULL, nul);
+  return 0;
+}
+
 void wgrad_entry(GkgWgradProblem& q, const GkgProjBN& p, const float* dY, const float* x, int ldx, size_t x_bstride, int R, int kperm) {
   q.dy = dY; q.x = x; q.dw = p.dw;
   q.g_bstride = (size_t)R * p.cout; q.x_bstride = x_bstride;
@@ -122,13 +220,26 @@ int graph_fwd(const GkgGraphOp& g, float* XM, const float* y, int B, int C, int 
 
 // ---- Grapher (reference torch_vertex.py:325-333): x (B, C, H, W) -> out (B, C, H, W) [+ out_tm (B N, C)] ----------------------
 extern "C" int gkg_grapher_fwd(const GkgGrapherBlock* b, void* st) {
-  if (!b || !b->x || !b->out || !b->xt || !b->XM || !b->A2 || !b->graph.arg) return gkg_fail(GKG_ERR_NULL, "gkg_grapher_fwd: null pointer");
+  GKG_TRY(check_grapher(b, nullptr, false));
   const int B = b->B, C = b->C, N = b->H * b->W, T = B * N;
-  if (B <= 0 || N <= 0 || C <= 0 || (C & 15) || b->fc1.nb != 1 || b->conv.nb != 4 || b->fc2.nb != 1 || b->fc1.cin != C || b->fc1.cout != C ||
-      b->conv.cin != C / 2 || b->conv.cout != C / 2 || b->fc2.cin != 2 * C || b->fc2.cout != C)
-    return gkg_fail(GKG_ERR_SHAPE, "gkg_grapher_fwd: C % 16 == 0; fc1 C -> C, conv 4 x (C/2 -> C/2), fc2 2C -> C");
   // block entry: NCHW -> token-major
   GKG_TRY(gkg_nchw_to_tm(b->x, b->xt, B, C, N, GKG_F32, nullptr, st));
+  if (b->bn_frozen) {
+    // every BatchNorm on its running statistics: projection without statistics, folded affine, apply — nothing else is written
+    const GkgGraphOp& g = b->graph;
+    GKG_TRY(proj_fwd_frozen(b->fc1, b->xt, C, (size_t)T * C, T, b->sk_ws, b->sk_bytes, st));
+    GKG_TRY(fc1_apply_frozen(b->fc1, g, b->XM, B, C, N, N, 0, st));
+    GKG_TRY(graph_fwd(g, b->XM, nullptr, B, C, N, N, st));
+    GKG_TRY(proj_fwd_frozen(b->conv, b->XM, 2 * C, (size_t)(C / 2), T, b->sk_ws, b->sk_bytes, st));
+    GKG_TRY(proj_apply_frozen(b->conv, T, nullptr, b->A2, 2 * C, (size_t)(C / 2), 0, 1, st));
+    GKG_TRY(proj_fwd_frozen(b->fc2, b->A2, 2 * C, (size_t)T * 2 * C, T, b->sk_ws, b->sk_bytes, st));
+    const GkgProjBN& p = b->fc2;
+    if (b->out_tm && b->keys_ws)
+      return gkg_affine_knn_prep(p.Y, p.bn, p.bn + C, b->out_tm, 0, 0, B, b->keys_G, C / b->keys_G, b->keys_L, N, b->keys_k, b->keys_d, 1, 0,
+                                 b->keys_flags, b->keys_fused_mr, 1, b->xt, b->out, b->keys_ws, b->keys_ws_bytes, st);
+    if (b->out_tm) return gkg_tm_affine_to_nchw_dual(p.Y, p.bn, p.bn + C, b->xt, b->out, b->out_tm, B, C, N, st);
+    return gkg_tm_affine_to_nchw(p.Y, p.bn, p.bn + C, b->x, b->out, B, C, N, nullptr, st);
+  }
   // fc1 + BN: x into the x half of the operand buffer; the same pass prepares the k-NN's queries when the graph op asks for it
   GKG_TRY(proj_fwd(b->fc1, b->xt, C, (size_t)T * C, T, b->sk_ws, b->sk_bytes, st));
   const GkgGraphOp& g = b->graph;
@@ -166,9 +277,28 @@ extern "C" int gkg_grapher_fwd(const GkgGrapherBlock* b, void* st) {
 // them now or queues them with the rest of the backward pass).  Temporaries: g3, dY3 (T, C), dA2 (T, 2C), dY2 (4, T, C/2),
 // dXM (T, 2C), gx1, dY1, dxt (T, C) — caller-owned; dY3 / dY2 / dY1 must stay valid until the weight gradients have run.
 extern "C" int gkg_grapher_bwd(const GkgGrapherBlock* b, GkgWgradProblem* wq, void* st) {
-  if (!b || !wq || !b->dout || !b->dx || !b->g3 || !b->dY3 || !b->dA2 || !b->dY2 || !b->dXM || !b->gx1 || !b->dY1 || !b->dxt)
-    return gkg_fail(GKG_ERR_NULL, "gkg_grapher_bwd: null pointer");
+  GKG_TRY(check_grapher(b, wq, true));
   const int B = b->B, C = b->C, N = b->H * b->W, T = B * N;
+  if (b->bn_frozen) {
+    // running statistics: each BN backward is gkg_bn_eval_bwd (one sweep, + a finishing launch when a parameter gradient is
+    // wanted) in front of the plain input-gradient GEMM; no statistics ride in another kernel
+    if (b->dout_tm) GKG_TRY(gkg_nchw_to_tm_add(b->dout, b->dout_tm, b->g3, B, C, N, st));
+    else GKG_TRY(gkg_nchw_to_tm(b->dout, b->g3, B, C, N, GKG_F32, nullptr, st));
+    GKG_TRY(proj_bwd_frozen(b->fc2, b->g3, C, 0, T, 0, b->dY3, nullptr, b->dA2, 0, 0, b->sk_ws, b->sk_bytes, st));
+    wgrad_entry(wq[0], b->fc2, b->dY3, b->A2, 2 * C, (size_t)T * 2 * C, T, 0);
+    GKG_TRY(proj_bwd_frozen(b->conv, b->dA2, 2 * C, (size_t)(C / 2), T, 1, b->dY2, nullptr, b->dXM, 2 * C, (size_t)(C / 2), b->sk_ws,
+                            b->sk_bytes, st));
+    wgrad_entry(wq[1], b->conv, b->dY2, b->XM, 2 * C, (size_t)(C / 2), T, 1);
+    const GkgGraphOp& g = b->graph;
+    GKG_TRY(gkg_mr_bwd_tm(b->dXM, nullptr, reinterpret_cast<const uint8_t*>(g.arg), b->gx1, nullptr, B, g.G, C / g.G, N, N, g.k, 1, 1,
+                          g.mr_flags, st));
+    GKG_TRY(bn_bwd_frozen(b->fc1, b->gx1, C, 0, T, 0, b->dY1, st));
+    wgrad_entry(wq[2], b->fc1, b->dY1, b->xt, C, (size_t)T * C, T, 0);
+    if (!(b->bwd_flags & GKG_BLOCK_NO_BWD_FUSE))
+      return gkg_linear_dgrad_x6_nchw(b->dY1, C, b->fc1.planes_dgrad, b->dx, b->dxt, T, C, C, b->g3, B, N, b->sk_ws, b->sk_bytes, 0, st);
+    GKG_TRY(proj_dgrad(b->fc1, b->dY1, T, b->g3, b->dxt, b->sk_ws, b->sk_bytes, st));
+    return gkg_tm_affine_to_nchw(b->dxt, nullptr, nullptr, nullptr, b->dx, B, C, N, nullptr, st);
+  }
   // the output's gradient(s) token-major; it is also the residual branch's gradient
   // (round 8, unless GKG_BLOCK_NO_BWD_FUSE: the re-layout pass takes fc2's BN backward statistics, the scatter takes fc1's, and
   // fc1's input-gradient GEMM stores dx channel-major — four launches fewer)
@@ -201,14 +331,23 @@ extern "C" int gkg_grapher_bwd(const GkgGrapherBlock* b, GkgWgradProblem* wq, vo
 
 // ---- GrapherLabel (reference torch_vertex.py:392-403 + FFNLabel :334-360): e (B L, C), keys / values ft (B, M, C) -> E' (B L, C) -----
 extern "C" int gkg_grapher_label_fwd(const GkgLabelBlock* b, void* st) {
-  if (!b || !b->e || !b->ft || !b->out || !b->XM || !b->A2 || !b->h2 || !b->f1 || !b->graph.arg)
-    return gkg_fail(GKG_ERR_NULL, "gkg_grapher_label_fwd: null pointer");
+  GKG_TRY(check_label(b, nullptr, false));
   const int B = b->B, C = b->C, L = b->L, M = b->M, T = B * L;
-  if (B <= 0 || L <= 0 || M <= 0 || (C & 15) || b->fc1.nb != 1 || b->conv.nb != 4 || b->fc2.nb != 1 || b->ffn1.nb != 1 || b->ffn2.nb != 1 ||
-      b->fc1.cin != C || b->fc1.cout != C || b->conv.cin != C / 2 || b->conv.cout != C / 2 || b->fc2.cin != 2 * C || b->fc2.cout != C ||
-      b->ffn1.cin != C || b->ffn2.cout != C || b->ffn2.cin != b->ffn1.cout)
-    return gkg_fail(GKG_ERR_SHAPE, "gkg_grapher_label_fwd: bad projection shapes");
   const GkgGraphOp& g = b->graph;
+  if (b->bn_frozen) {
+    const int Cf = b->ffn1.cout;
+    GKG_TRY(proj_fwd_frozen(b->fc1, b->e, C, (size_t)T * C, T, b->sk_ws, b->sk_bytes, st));
+    GKG_TRY(fc1_apply_frozen(b->fc1, g, b->XM, B, C, L, M, 1, st));
+    GKG_TRY(graph_fwd(g, b->XM, b->ft, B, C, L, M, st));
+    GKG_TRY(proj_fwd_frozen(b->conv, b->XM, 2 * C, (size_t)(C / 2), T, b->sk_ws, b->sk_bytes, st));
+    GKG_TRY(proj_apply_frozen(b->conv, T, nullptr, b->A2, 2 * C, (size_t)(C / 2), 0, 1, st));
+    GKG_TRY(proj_fwd_frozen(b->fc2, b->A2, 2 * C, (size_t)T * 2 * C, T, b->sk_ws, b->sk_bytes, st));
+    GKG_TRY(proj_apply_frozen(b->fc2, T, b->e, b->h2, C, 0, 0, 0, st));
+    GKG_TRY(proj_fwd_frozen(b->ffn1, b->h2, C, (size_t)T * C, T, b->sk_ws, b->sk_bytes, st));
+    GKG_TRY(proj_apply_frozen(b->ffn1, T, nullptr, b->f1, Cf, 0, 0, 1, st));
+    GKG_TRY(proj_fwd_frozen(b->ffn2, b->f1, Cf, (size_t)T * Cf, T, b->sk_ws, b->sk_bytes, st));
+    return proj_apply_frozen(b->ffn2, T, b->h2, b->out, C, 0, 0, 0, st);
+  }
   GKG_TRY(proj_fwd(b->fc1, b->e, C, (size_t)T * C, T, b->sk_ws, b->sk_bytes, st));
   if (g.knn_flags & GKG_KNN_X_PREPARED) {
     const GkgProjBN& p = b->fc1;
@@ -234,11 +373,26 @@ extern "C" int gkg_grapher_label_fwd(const GkgLabelBlock* b, void* st) {
 // Backward: dout (B L, C) -> de (B L, C), dft (B, M, C) (the keys' / values' gradient), BN parameter gradients, wq[0..4].
 // Temporaries: dY5 (T, C), df1 (T, Cf), dY4 (T, Cf), dh2 (T, C), dY3 (T, C), dA2 (T, 2C), dY2 (4, T, C/2), dXM (T, 2C), gx1, dY1 (T, C).
 extern "C" int gkg_grapher_label_bwd(const GkgLabelBlock* b, GkgWgradProblem* wq, void* st) {
-  if (!b || !wq || !b->dout || !b->de || !b->dft || !b->dY5 || !b->df1 || !b->dY4 || !b->dh2 || !b->dY3 || !b->dA2 || !b->dY2 || !b->dXM ||
-      !b->gx1 || !b->dY1)
-    return gkg_fail(GKG_ERR_NULL, "gkg_grapher_label_bwd: null pointer");
+  GKG_TRY(check_label(b, wq, true));
   const int B = b->B, C = b->C, L = b->L, M = b->M, T = B * L, Cf = b->ffn1.cout;
   const GkgGraphOp& g = b->graph;
+  if (b->bn_frozen) {
+    GKG_TRY(proj_bwd_frozen(b->ffn2, b->dout, C, 0, T, 0, b->dY5, nullptr, b->df1, 0, 0, b->sk_ws, b->sk_bytes, st));
+    wgrad_entry(wq[0], b->ffn2, b->dY5, b->f1, Cf, (size_t)T * Cf, T, 0);
+    GKG_TRY(proj_bwd_frozen(b->ffn1, b->df1, Cf, 0, T, 1, b->dY4, b->dout, b->dh2, 0, 0, b->sk_ws, b->sk_bytes, st));   // + the FFN residual's gradient
+    wgrad_entry(wq[1], b->ffn1, b->dY4, b->h2, C, (size_t)T * C, T, 0);
+    GKG_TRY(proj_bwd_frozen(b->fc2, b->dh2, C, 0, T, 0, b->dY3, nullptr, b->dA2, 0, 0, b->sk_ws, b->sk_bytes, st));
+    wgrad_entry(wq[2], b->fc2, b->dY3, b->A2, 2 * C, (size_t)T * 2 * C, T, 0);
+    GKG_TRY(proj_bwd_frozen(b->conv, b->dA2, 2 * C, (size_t)(C / 2), T, 1, b->dY2, nullptr, b->dXM, 2 * C, (size_t)(C / 2), b->sk_ws,
+                            b->sk_bytes, st));
+    wgrad_entry(wq[3], b->conv, b->dY2, b->XM, 2 * C, (size_t)(C / 2), T, 1);
+    GKG_TRY(gkg_mr_bwd_tm(b->dXM, nullptr, reinterpret_cast<const uint8_t*>(g.arg), b->gx1, b->dft, B, g.G, C / g.G, L, M, g.k, 1, 1,
+                          g.mr_flags, st));
+    GKG_TRY(bn_bwd_frozen(b->fc1, b->gx1, C, 0, T, 0, b->dY1, st));
+    GKG_TRY(proj_dgrad(b->fc1, b->dY1, T, b->dh2, b->de, b->sk_ws, b->sk_bytes, st));                                 // + the block residual's gradient
+    wgrad_entry(wq[4], b->fc1, b->dY1, b->e, C, (size_t)T * C, T, 0);
+    return 0;
+  }
   // (round 9, unless GKG_BLOCK_NO_DGRAD_STATS: each input-gradient GEMM of the chain ffn2 -> ffn1 -> fc2 -> conv takes the backward
   // statistics of the layer in front of it, whose BN backward is then its apply pass — three launches fewer)
   const bool s4 = dgrad_stats_ok(b->ffn2, b->bwd_flags, T, false, b->sk_ws), s3 = dgrad_stats_ok(b->ffn1, b->bwd_flags, T, true, b->sk_ws),

@@ -897,3 +897,29 @@ extern "C" int gkg_bn_apply_knn_prep(const float* y, const double* sums, const f
   return knn_fwd_impl(y, has_y ? &dummy : nullptr, has_relpos ? &dummy : nullptr, nullptr, nullptr, B * G, c, N, M, k, dilation, GKG_F32,
                       knn_flags, knn_workspace, knn_workspace_bytes, stream, G, fused_mr ? &mr_dummy : nullptr, false, nullptr, 0, 0, &prod);
 }
+
+// The same pass behind an eval-mode (frozen) BatchNorm: the caller passes the folded scale / shift (gkg_bn_eval_affine) instead of
+// column sums — out = a y + c (+ res_tm) with the arithmetic of gkg_affine_act / gkg_tm_affine_to_nchw_dual, then the k-NN's own
+// preparation from the same registers.  Nothing but out, out_nchw and the workspace is written: no saved statistics, no running
+// statistics, no scratch buffer to clear (BnDerive::sums == null keeps prep_affine_table away from all of them).
+extern "C" int gkg_affine_knn_prep(const float* y, const float* a, const float* c_in, float* out, int ldo, int ochunk, int B, int G,
+                                   int c, int N, int M, int k, int dilation, int has_y, int has_relpos, unsigned knn_flags,
+                                   int fused_mr, int as_keys, const float* res_tm, float* out_nchw, void* knn_workspace,
+                                   size_t knn_workspace_bytes, void* stream) {
+  if (!y || !a || !c_in || !out || !knn_workspace) return gkg_fail(GKG_ERR_NULL, "gkg_affine_knn_prep: null pointer");
+  if (!as_keys && (res_tm || out_nchw)) return gkg_fail(GKG_ERR_SHAPE, "gkg_affine_knn_prep: res_tm / out_nchw belong to a keys producer");
+  if (as_keys && (!has_y || ochunk != 0 || ((size_t)res_tm & 15))) return gkg_fail(GKG_ERR_SHAPE, "gkg_affine_knn_prep: a keys producer writes plain rows for a problem with keys");
+  if (B <= 0 || G <= 0 || c <= 0 || (c & 3) || N <= 0) return gkg_fail(GKG_ERR_SHAPE, "gkg_affine_knn_prep: bad sizes (c % 4 == 0)");
+  const int C = G * c;
+  if (ldo == 0) ldo = C;
+  if (ldo < C || (ldo & 3) || ochunk < 0 || (ochunk & 3) || (ochunk > 0 && (C % ochunk || ldo < 2 * C)) || ((size_t)out & 15) || ((size_t)y & 15))
+    return gkg_fail(GKG_ERR_SHAPE, "gkg_affine_knn_prep: bad output view");
+  KnnProducer prod{};                              // aff.d.sums == null: the table is copied from a / c
+  prod.aff.a = a; prod.aff.c = c_in;
+  prod.raw = out; prod.raw_ld = ldo; prod.raw_chunk = ochunk;
+  prod.as_keys = as_keys ? 1 : 0; prod.res_tm = res_tm; prod.nchw = out_nchw;
+  static const float dummy = 0.f;
+  static KnnMrFuse mr_dummy{nullptr, nullptr, nullptr};
+  return knn_fwd_impl(y, has_y ? &dummy : nullptr, has_relpos ? &dummy : nullptr, nullptr, nullptr, B * G, c, N, M, k, dilation, GKG_F32,
+                      knn_flags, knn_workspace, knn_workspace_bytes, stream, G, fused_mr ? &mr_dummy : nullptr, false, nullptr, 0, 0, &prod);
+}

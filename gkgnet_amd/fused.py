@@ -967,8 +967,23 @@ class _LinearBNAct(torch.autograd.Function):
         else:
             Y = _mm_t(x, W, w16)
             a, c, mean, invstd, sync = _bn_forward_params(lib, Y, bn, bias, R, cout, 1)
+        # a frozen (eval-mode) layer in the place where a train-mode one takes gkg_bn_apply_knn_prep: the folded affine is also the
+        # k-NN's token preparation (gkg_affine_knn_prep) — fc1's queries into the XM buffer, or a Grapher's last layer as the
+        # producer of the label graph's keys
+        eval_prep = (knn if (own and not fused_apply and mean is None and act == 0 and scale is None and code == _lib.F32
+                             and not want16 and ((xm is not None and not knn.as_keys) or (dual and knn.as_keys))) else None) \
+            if knn is not None else None
         if fused_apply:
             pass
+        elif eval_prep is not None:
+            kp = eval_prep
+            if kp.ws is None:
+                kp.ws = _ws(lib.gkg_knn_workspace_bytes(kp.B * kp.G, kp.c, kp.N, kp.M, kp.k, kp.d, _lib.F32, _lib.KNN_NORMALIZE), x.device)
+            _lib.check(lib.gkg_affine_knn_prep(_ptr(Y), _ptr(a), _ptr(c), _ptr(out_tm if kp.as_keys else out), 0 if kp.as_keys else ldo,
+                                               0 if kp.as_keys else ochunk, kp.B, kp.G, kp.c, kp.N, kp.M, kp.k, kp.d, kp.has_y,
+                                               kp.has_rp, kp.flags, kp.fused_mr, kp.as_keys, _ptr(res) if kp.as_keys else None,
+                                               _ptr(out) if kp.as_keys else None, _ptr(kp.ws), kp.ws.numel(), _stream()),
+                       "gkg_affine_knn_prep")
         elif nchw is None and want16 and code == _lib.F32:
             # bf16 inference, channels-last chain: also emit the bf16 rounding the next block's first GEMM reads
             out16 = torch.empty((R, cout), dtype=torch.bfloat16, device=x.device)
@@ -999,14 +1014,14 @@ class _LinearBNAct(torch.autograd.Function):
             if act == 0 and out.dtype == _F32 and _bwd_fuse_ok(mean, sync, scale, 1, cout):
                 # the aggregation behind this layer takes its BN backward statistics in its scatter (_mr_bwd)
                 ctx.link = out._gkg_mr_bn_link = _BnLink(Y, a, c, mean, invstd, act, 1, cout, R)
-            if knn is not None and fused_apply and getattr(knn, "ws", None) is not None:
+            if knn is not None and (fused_apply or eval_prep is not None) and getattr(knn, "ws", None) is not None:
                 out._gkg_knn = knn               # the queries' prepared copies are in knn.ws (see _knn_prepared)
         if alias:
             ctx.set_materialize_grads(False)
             return out, x.view_as(x)
         if dual:
             ctx.set_materialize_grads(False)
-            if knn is not None and knn.as_keys and fused_apply and knn.ws is not None:
+            if knn is not None and knn.as_keys and (fused_apply or eval_prep is not None) and knn.ws is not None:
                 out_tm._gkg_knn_keys = knn       # the label graph's keys are prepared in knn.ws (grapher_label_forward)
             return out, out_tm
         return out

@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define GKG_ABI_VERSION 11
+#define GKG_ABI_VERSION 12
 
 /* dtype codes */
 #define GKG_F32 0
@@ -244,6 +244,15 @@ int gkg_bn_apply_knn_prep(const float* y, const double* sums, const float* gamma
                           int dilation, int has_y, int has_relpos, unsigned knn_flags, int fused_mr, int as_keys, const float* res_tm,
                           float* out_nchw, void* knn_workspace, size_t knn_workspace_bytes, float momentum, float eps, double* zero_buf,
                           size_t zero_doubles, void* stream);
+/* The eval-mode (frozen BatchNorm) counterpart of gkg_bn_apply_knn_prep: the caller passes the folded scale / shift a, c
+ * (C = G c each; gkg_bn_eval_affine) instead of column sums.  out = fmaf(a, y, c) (+ res_tm for a keys producer) — the bits of
+ * gkg_affine_act (queries: out / ldo / ochunk as above) or gkg_tm_affine_to_nchw_dual (as_keys: out (B M, C) plain, out_nchw
+ * (B, C, M)) — and, from the same registers, the k-NN call's own token preparation into `knn_workspace`; the k-NN call with the
+ * same problem follows with GKG_KNN_X_PREPARED (GKG_KNN_Y_PREPARED for as_keys).  Writes nothing but out, out_nchw and the
+ * workspace: no saved statistics, no running statistics, no scratch buffer.  Every other argument as gkg_bn_apply_knn_prep. */
+int gkg_affine_knn_prep(const float* y, const float* a, const float* c_in, float* out, int ldo, int ochunk, int B, int G, int c,
+                        int N, int M, int k, int dilation, int has_y, int has_relpos, unsigned knn_flags, int fused_mr, int as_keys,
+                        const float* res_tm, float* out_nchw, void* knn_workspace, size_t knn_workspace_bytes, void* stream);
 /* Pooled key set of a Grapher with r > 1 (reference torch_vertex.py:194-196, F.avg_pool2d(x, r, r)) from a token-major map
  * x (B, H, W, C) given as a view -> out (B, H/r, W/r, C) plain fp32 (floor mode; window sum in (h, w) order, one division). */
 int gkg_avgpool_tm(const float* x, int ldx, int xchunk, float* out, int B, int H, int W, int C, int r, void* stream);
@@ -591,14 +600,25 @@ int gkg_bn_bwd_apply_from_sums(const float* dout, const float* y, const float* a
  * Block-level entry points (round 6; csrc/gkg_block.hip): ONE call runs the whole launch sequence of a Grapher / GrapherLabel
  * block's forward or backward (reference torch_vertex.py:325-333, :392-403 + FFNLabel :334-360) from a descriptor — the host side
  * allocates, fills the descriptor and calls.  Every launch inside is one of the entry points above, in the order and with the
- * arguments of the per-layer composition: bit-identical results.  Scope: fp32, train-mode BatchNorm with rank-local statistics,
- * no DropPath scaling, un-pooled keys (r == 1), C % 16 == 0, every projection on the split-bf16 kernels.  The library allocates
+ * arguments of the per-layer composition: bit-identical results.  Scope: fp32, train-mode BatchNorm with rank-local statistics
+ * — or, with bn_frozen != 0, EVERY BatchNorm of the block in eval mode (running statistics) —, no DropPath scaling, un-pooled
+ * keys (r == 1), C % 16 == 0, every projection on the split-bf16 kernels.
+ * bn_frozen: per projection the forward is the GEMM without statistics (gkg_linear_bn_fwd_x6_sk, train == 0), gkg_bn_eval_affine
+ * into the a | c slots of `bn`, and the apply (gkg_affine_act; gkg_affine_knn_prep where the train-mode form takes
+ * gkg_bn_apply_knn_prep; gkg_tm_affine_to_nchw[_dual] for a Grapher's last layer); the backward is gkg_bn_eval_bwd (one launch
+ * when dgamma, dbeta and dbias are all NULL, two otherwise — only then bsum / bzero are used) and the plain input-gradient
+ * GEMMs.  running_mean / running_var are read, never written; nbt, momentum, fsum / fzero and the mean | invstd slots of `bn`
+ * are unused; dgamma / dbeta / dbias may each be NULL (not wanted).
+ * Every entry point validates the descriptor before its first launch: GKG_ERR_SHAPE for bad sizes (C % 16, the projections'
+ * shapes, graph.G <= 0 or C % G != 0, keys_G likewise when keys_ws is set), GKG_ERR_NULL for a missing pointer (the saved
+ * activations and projection buffers the backward reads included).  The library allocates
  * nothing and keeps no state: all buffers — including, per BN pass, the fp64 column-sum buffer to accumulate into and the region
  * of the OTHER buffer to clear (the caller's alternating pair, see gkg_bn_bwd_atomic) — come in the descriptor.
  *   GkgProjBN   one 1x1 projection + BatchNorm: weight as x6 planes (gkg_x6_prep_weights; the grouped projection behind the
  *               aggregation with kperm), BN parameters, what the forward saves for the backward (Y: pre-BN output (nb, R, cout);
- *               bn: [4][nb cout] = a, c, mean, invstd), the backward's outputs (dgamma, dbeta; dw: where the weight-gradient
- *               problem it emits will add — zero on entry).
+ *               bn: [4][nb cout] = a, c, mean, invstd), the backward's outputs (dgamma, dbeta, with bn_frozen also dbias: the
+ *               gradient of the conv bias, which is exactly zero in train mode; dw: where the weight-gradient problem it
+ *               emits will add — zero on entry).
  *   GkgGraphOp  the k-NN + aggregation of the block: flags as gkg_knn_fwd (GKG_KNN_X_PREPARED: fc1's BN-apply prepares the
  *               queries — gkg_bn_apply_knn_prep; GKG_KNN_Y_PREPARED: the keys are already in knn_ws); fused_mr: one kernel
  *               (gkg_knn_mr_fused_supported), else k-NN + aggregation with u16 lists (nn16) or — a caller that returns the
@@ -625,6 +645,7 @@ typedef struct GkgProjBN {
   double* bsum; double* bzero; size_t bzero_n;      /* backward BN pass */
   float* Y; float* bn;
   float* dw; float* dgamma; float* dbeta;
+  float* dbias;                                     /* bn_frozen only, may be NULL: the conv bias's gradient */
 } GkgProjBN;
 typedef struct GkgGraphOp {
   int G, k, d, fused_mr;
@@ -645,6 +666,7 @@ typedef struct GkgGrapherBlock {
   const float* dout; const float* dout_tm; float* dx;
   float* g3; float* dY3; float* dA2; float* dY2; float* dXM; float* gx1; float* dY1; float* dxt;
   unsigned bwd_flags;                                         /* GKG_BLOCK_* */
+  int bn_frozen;                                              /* != 0: every BatchNorm in eval mode (see above); 0: train mode */
 } GkgGrapherBlock;
 typedef struct GkgLabelBlock {
   int B, C, L, M;
@@ -657,6 +679,7 @@ typedef struct GkgLabelBlock {
   const float* dout; float* de; float* dft;
   float* dY5; float* df1; float* dY4; float* dh2; float* dY3; float* dA2; float* dY2; float* dXM; float* gx1; float* dY1;
   unsigned bwd_flags;                                         /* GKG_BLOCK_* */
+  int bn_frozen;
 } GkgLabelBlock;
 int gkg_grapher_fwd(const GkgGrapherBlock* b, void* stream);
 int gkg_grapher_bwd(const GkgGrapherBlock* b, GkgWgradProblem* wq /* [3] */, void* stream);

@@ -5,6 +5,7 @@
     python tools/bench_frozen_bn.py --mode eval              # whole modules in eval(), gradients on
     python tools/bench_frozen_bn.py --mode train             # train-mode BN (the ordinary step), for scale
     python tools/bench_frozen_bn.py --mode kernel            # gkg_bn_eval_bwd vs bn_bwd_stats + bn_bwd_apply_d, bytes / s
+    python tools/bench_frozen_bn.py --mode frozen --bucket --graph    # gradients in a GradBucket; eager, then replayed from a hipGraph
 
 Step: Grapher(C=320, G=4, k=9, d=1, 18x18, relative_pos) -> GrapherLabel(L=80), B=32, fp32, forward + backward of fixed
 cotangents, eager launches, device events around all timed steps of a repeat.  ``--root DIR`` imports gkgnet_amd from another
@@ -27,6 +28,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--no-fused", action="store_true", help="force the composable path")
+    ap.add_argument("--bucket", action="store_true", help="parameter gradients in a parallel.GradBucket (release / pack per step)")
+    ap.add_argument("--graph", action="store_true", help="with --bucket: also time the step replayed from a hipGraph (GraphedStep)")
     ap.add_argument("--label", default=None)
     args = ap.parse_args()
     sys.path.insert(0, os.path.abspath(args.root))
@@ -87,16 +90,39 @@ def step_bench(args, torch, fused):
         return real(*a, **kw)
     fused.grapher_forward = spy
 
+    bucket = None
+    if args.bucket:
+        from gkgnet_amd import parallel
+        bucket = parallel.GradBucket(params)
+    drv = [0]
+    try:                                                 # calls of the block driver (absent or train-mode only in older checkouts)
+        from gkgnet_amd import block
+        fwd = block._GrapherBlockFn.forward
+        block._GrapherBlockFn.forward = staticmethod(lambda *a: (drv.__setitem__(0, drv[0] + 1), fwd(*a))[1])
+    except ImportError:
+        pass
+
     def step():
-        for p in params:
-            p.grad = None
+        if bucket is not None:
+            bucket.release(prezero=True)
+        else:
+            for p in params:
+                p.grad = None
         x.grad = e.grad = None
         out = g(x)
         e2, _ = gl(e, out)
         torch.autograd.backward([out, e2], [cx, ce])
+        if bucket is not None:
+            bucket.pack()
     ms = timed(torch, step, args.steps, args.warmup, args.repeats)
-    return dict(ms_per_step=[round(v, 4) for v in ms], median_ms=round(statistics.median(ms), 4), fused_path=calls[0] > 0,
-                bias_grad=g.fc1[0].bias.grad is not None)
+    res = dict(ms_per_step=[round(v, 4) for v in ms], median_ms=round(statistics.median(ms), 4), fused_path=calls[0] > 0,
+               block_driver=drv[0] > 0, bias_grad=g.fc1[0].bias.grad is not None, bucket=bucket is not None)
+    if args.graph and bucket is not None:
+        from gkgnet_amd.graphed import GraphedStep
+        gs = GraphedStep(step, warmup=3)
+        rp = timed(torch, gs.replay, args.steps, args.warmup, args.repeats)
+        res.update(captured=gs.captured, replay_ms_per_step=[round(v, 4) for v in rp], replay_median_ms=round(statistics.median(rp), 4))
+    return res
 
 
 def kernel_bench(args, torch):
