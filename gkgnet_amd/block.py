@@ -10,11 +10,19 @@ BatchNorm with rank-local statistics, no DropPath scaling, un-pooled keys, every
 below the BN-epilogue row count — and for the same block with EVERY BatchNorm frozen (eval mode with running statistics:
 ``layers.freeze_batchnorm``, ``norm_eval``, ``eval()`` with gradients; a frozen SyncBatchNorm too): the descriptor's ``bn_frozen``
 form, which writes no statistics and returns the conv biases' gradients (tests/test_hip_frozen_block_driver.py).  A block with
-some layers frozen and some not, and everything else, keeps the composition.  GKG_DISABLE=block_driver: off."""
+some layers frozen and some not, and everything else, keeps the composition.  GKG_DISABLE=block_driver: off.
+
+Structure: a per-module ``_Plan`` holds what is the same on every step — the projections, the static half of the descriptor, and
+the two arena layouts, which are data (``_ARENAS``: descriptor field -> size) resolved to (field, offset) pairs when the plan is
+built.  The two autograd Functions keep what is their own (inputs, outputs, the Grapher's keys handshake and dual output, the label
+block's announcement to its producer); everything a call shares lives once, in ``_forward`` and ``_backward``, which treat the
+projections as a list in the plan's order (train: three autograd inputs each, frozen: four) — one ``_proj_fwd`` / ``_proj_bwd`` per
+projection, whatever the mode."""
 from __future__ import annotations
 
 import ctypes as C
 import weakref
+from contextlib import nullcontext
 
 import torch
 
@@ -196,17 +204,45 @@ class _Proj:
         return [t for t in (self.gamma, self.beta, self.bias) + ((self.rm, self.rv, self.nbt) if self.trs else ()) if t is not None]
 
 
-def _layout(sizes):
-    """Arena layout: element offsets of 16-byte aligned fp32 pieces -> (offsets, total elements)."""
-    offs, o = [], 0
-    for n in sizes:
-        offs.append(o)
-        o += (n + 3) & ~3
-    return offs, o
+# The two arenas of a block call — what the forward saves, what the backward needs — as data: per block kind the descriptor fields
+# that point into the arena, in arena order, each with its size in fp32 elements as rows x columns (T tokens, C channels, Cf the
+# FFN's width; `fc1.Y` is field Y of the projection fc1; a BN's `bn` holds a, c, mean, invstd per channel — the grouped projection
+# has 4 x C/2 channels —, `graph.arg` the u16 winning rows).  A piece starts 16-byte aligned.
+_ARENAS = {
+    "g": ((("xt", "T", "C"), ("XM", "T", "2C"), ("A2", "T", "2C"), ("fc1.Y", "T", "C"), ("conv.Y", "T", "2C"), ("fc2.Y", "T", "C"),
+           ("fc1.bn", "4", "C"), ("conv.bn", "4", "2C"), ("fc2.bn", "4", "C"), ("graph.arg", "T", "C/2")),
+          (("g3", "T", "C"), ("dY3", "T", "C"), ("gx1", "T", "C"), ("dY1", "T", "C"), ("dxt", "T", "C"), ("dA2", "T", "2C"),
+           ("dY2", "T", "2C"), ("dXM", "T", "2C"))),
+    "l": ((("XM", "T", "2C"), ("A2", "T", "2C"), ("h2", "T", "C"), ("f1", "T", "Cf"), ("fc1.Y", "T", "C"), ("conv.Y", "T", "2C"),
+           ("fc2.Y", "T", "C"), ("ffn1.Y", "T", "Cf"), ("ffn2.Y", "T", "C"), ("fc1.bn", "4", "C"), ("conv.bn", "4", "2C"),
+           ("fc2.bn", "4", "C"), ("ffn1.bn", "4", "Cf"), ("ffn2.bn", "4", "C"), ("graph.arg", "T", "C/2")),
+          (("dY5", "T", "C"), ("dh2", "T", "C"), ("dY3", "T", "C"), ("gx1", "T", "C"), ("dY1", "T", "C"), ("df1", "T", "Cf"),
+           ("dY4", "T", "Cf"), ("dA2", "T", "2C"), ("dY2", "T", "2C"), ("dXM", "T", "2C"))),
+}
+
+
+def _layout(table, T, Cc, Cf):
+    """One arena of _ARENAS for these sizes -> (((sub-structure | None, ((field, byte offset), ...)), ...), total elements): the
+    names resolved here, once per plan, so that a call only stores pointers (_point)."""
+    dim = {"T": T, "4": 4, "C": Cc, "2C": 2 * Cc, "C/2": Cc // 2, "Cf": Cf}
+    owners, o = {}, 0
+    for path, rows, cols in table:
+        owner, _, field = path.rpartition(".")
+        owners.setdefault(owner or None, []).append((field, 4 * o))
+        o += (dim[rows] * dim[cols] + 3) & ~3
+    return tuple((owner, tuple(fields)) for owner, fields in owners.items()), o
+
+
+def _point(d, arena, base):
+    """Point the descriptor's fields of one arena (_layout) into the buffer at ``base``."""
+    for owner, fields in arena:
+        obj = d if owner is None else getattr(d, owner)
+        for field, off in fields:
+            setattr(obj, field, base + off)
 
 
 class _Plan:
-    __slots__ = ("kind", "projs", "ident", "tensors", "ptrs", "tmpl", "fwd_offs", "fwd_total", "bwd_offs", "bwd_total", "drops",
+    __slots__ = ("kind", "projs", "ident", "tensors", "ptrs", "tmpl", "names", "stride", "fwd", "fwd_total", "bwd", "bwd_total", "drops",
                  "sync", "gc", "nn_", "k", "d", "groups", "dims", "rp", "rp_view", "fast", "params", "fm", "has_bucket", "frozen",
                  "gelus", "__weakref__")
 
@@ -242,7 +278,7 @@ class _Plan:
         return True
 
 
-def _finish_plan(plan, mod, cls, projs, ident, drops, gc, nn_, groups, dims, relative_pos, fwd_sizes, bwd_sizes):
+def _finish_plan(plan, mod, cls, projs, ident, drops, gc, nn_, groups, dims, relative_pos, T, Cc, Cf):
     plan.projs, plan.ident, plan.drops, plan.gc, plan.nn_, plan.groups, plan.dims = projs, ident, drops, gc, nn_, groups, dims
     plan.k, plan.d = gc.k, gc.d
     plan.frozen = not projs[0].bn.training                 # (grapher_ok / label_ok: every projection in the same mode)
@@ -251,10 +287,13 @@ def _finish_plan(plan, mod, cls, projs, ident, drops, gc, nn_, groups, dims, rel
     plan.tensors = [t for p in projs for t in p.baked()]
     plan.ptrs = [t.data_ptr() for t in plan.tensors]
     plan.sync = any(isinstance(p.bn, torch.nn.SyncBatchNorm) for p in projs)
-    plan.fwd_offs, plan.fwd_total = _layout(fwd_sizes)
-    plan.bwd_offs, plan.bwd_total = _layout(bwd_sizes)
-    # the autograd inputs: a conv bias in front of a frozen BN has a real gradient (in train mode it is exactly zero: no input)
-    plan.params = tuple(t for p in projs for t in ((p.W, p.gamma, p.beta, p.bias) if plan.frozen else (p.W, p.gamma, p.beta)))
+    fwd, bwd = _ARENAS[plan.kind]
+    plan.fwd, plan.fwd_total = _layout(fwd, T, Cc, Cf)
+    plan.bwd, plan.bwd_total = _layout(bwd, T, Cc, Cf)
+    # the autograd inputs, `stride` per projection: a conv bias in front of a frozen BN has a real gradient (in train mode it is
+    # exactly zero: no input)
+    plan.stride = 4 if plan.frozen else 3
+    plan.params = tuple(t for p in projs for t in (p.W, p.gamma, p.beta, p.bias)[:plan.stride])
     plan.fm = {}
     own = mod._parameters.get("relative_pos", mod.__dict__.get("relative_pos"))
     plan.fast = relative_pos is None or relative_pos is own        # a re-interpolated bias is a new tensor every call: slow path
@@ -264,8 +303,8 @@ def _finish_plan(plan, mod, cls, projs, ident, drops, gc, nn_, groups, dims, rel
         ident.append((mod._parameters, "relative_pos", relative_pos))
     d = cls()
     d.bn_frozen = int(plan.frozen)
-    names = [f[0] for f in cls._fields_ if f[1] is ProjBN]
-    for nm, p in zip(names, projs):
+    plan.names = tuple(f[0] for f in cls._fields_ if f[1] is ProjBN)          # the projections' descriptor fields, in forward order
+    for nm, p in zip(plan.names, projs):
         p.static(getattr(d, nm))
     plan.tmpl = bytes(d)
     return plan
@@ -287,10 +326,7 @@ def _plan_grapher(mod, x, relative_pos, groups):
              _Proj(mod.fc2, 1, 2 * Cc, Cc, 0, (Cc, 2 * Cc), ident)]
     plan = _Plan()
     plan.kind = "g"
-    # forward arena: xt, XM, A2, Y1, Y2, Y3, bn1, bn2, bn3, winning rows (u16)   backward: g3, dY3, gx1, dY1, dxt, dA2, dY2, dXM
-    fwd = [T * Cc, T * 2 * Cc, T * 2 * Cc, T * Cc, 4 * T * (Cc // 2), T * Cc, 4 * Cc, 8 * Cc, 4 * Cc, T * (Cc // 2)]
-    bwd = [T * Cc] * 5 + [T * 2 * Cc] * 3
-    _finish_plan(plan, mod, GrapherBlock, projs, ident, [mod.drop_path], gc, nn_, groups, (B, Cc, H, W), relative_pos, fwd, bwd)
+    _finish_plan(plan, mod, GrapherBlock, projs, ident, [mod.drop_path], gc, nn_, groups, (B, Cc, H, W), relative_pos, T, Cc, 0)
     plans[key] = plan
     return plan
 
@@ -317,22 +353,17 @@ def _plan_label(mod, e2, ft, groups):
              _Proj(ffn.fc2, 1, Cf, Cc, 0, (Cc, Cf), ident)]
     plan = _Plan()
     plan.kind = "l"
-    # forward arena: XM, A2, h2, f1, Y1..Y5, bn1..bn5, winning rows      backward: dY5, dh2, dY3, gx1, dY1, df1, dY4, dA2, dY2, dXM
-    fwd = [T * 2 * Cc, T * 2 * Cc, T * Cc, T * Cf, T * Cc, 4 * T * (Cc // 2), T * Cc, T * Cf, T * Cc, 4 * Cc, 8 * Cc, 4 * Cc, 4 * Cf,
-           4 * Cc, T * (Cc // 2)]
-    bwd = [T * Cc] * 5 + [T * Cf] * 2 + [T * 2 * Cc] * 3
-    _finish_plan(plan, mod, LabelBlock, projs, ident, [mod.drop_path, ffn.drop_path], gc, nn_, groups, (B, Cc, L, M, Cf), None, fwd, bwd)
+    _finish_plan(plan, mod, LabelBlock, projs, ident, [mod.drop_path, ffn.drop_path], gc, nn_, groups, (B, Cc, L, M, Cf), None, T, Cc, Cf)
     plans[key] = plan
     return plan
 
 
 # ----------------------------------------------------------------------------------------------- descriptor pieces
-def _proj_fwd(lib, p: ProjBN, pr: _Proj, scratch, keep, y_ptr, bn_ptr):
-    """The per-call half of a projection's forward descriptor: weight planes (refreshed when the weight moved), the BN pass's
-    scratch buffers, where Y and the BN coefficients go."""
+def _proj_fwd(lib, p: ProjBN, pr: _Proj, scratch, keep):
+    """The per-call half of a projection's forward descriptor: weight planes (refreshed when the weight moved) and the BN pass's
+    scratch buffers (Y and the BN coefficients live in the forward arena)."""
     pf, pd = fused._planes(lib, pr.W, pr.nb, pr.cout, pr.cin, True, True, kperm=pr.kperm)
     p.planes_fwd, p.planes_dgrad = pf.data_ptr(), pd.data_ptr()
-    p.Y, p.bn = y_ptr, bn_ptr
     if scratch is not None:                                   # (None: a frozen layer — no statistics pass, nothing written back)
         if pr.trs:
             ep = pr.bn.__dict__.get("_gkg_epoch")
@@ -342,30 +373,6 @@ def _proj_fwd(lib, p: ProjBN, pr: _Proj, scratch, keep, y_ptr, bn_ptr):
         p.fsum, p.fzero, p.fzero_n = cur.data_ptr(), other.data_ptr(), zero
     keep.append(pf)
     keep.append(pd)
-
-
-def _proj_bwd(lib, p: ProjBN, pr: _Proj, scratch, dev):
-    """Backward half: the BN pass's scratch buffers and the gradient outputs (bucket slots when the parameters have them)."""
-    dWv, dgamma, dbeta = fused._grad_outs((pr.W, pr.gamma, pr.beta), pr.wshape, pr.nch, dev)
-    if not getattr(dWv, "_gkg_zero", False):
-        dWv.zero_()                                      # the weight-gradient kernels ADD into dw
-    cur, other, zero = scratch.acquire(lib, 2 * pr.nch)
-    p.bsum, p.bzero, p.bzero_n = cur.data_ptr(), other.data_ptr(), zero
-    p.dw, p.dgamma, p.dbeta = dWv.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr()
-    return dWv, dgamma, dbeta
-
-
-class _NoScratch:
-    """Stands in for the BN scratch pair where a frozen block uses none (no statistics pass in the forward, no parameter gradient
-    wanted in the backward): nothing is created, acquired or marked."""
-    def __enter__(self):
-        return None
-
-    def __exit__(self, et, ev, tb):
-        return False
-
-
-_NO_SCRATCH = _NoScratch()
 
 
 def _want_1d(need, projs) -> bool:
@@ -380,18 +387,24 @@ def _slot(param, n, dev):
     return torch.empty(n, dtype=_F32, device=dev) if v is None else v
 
 
-def _proj_bwd_frozen(lib, p: ProjBN, pr: _Proj, scratch, dev, want):
-    """Backward half of a frozen layer -> (dW, dgamma, dbeta, dbias).  ``want``: ctx.needs_input_grad of (W, gamma, beta, bias);
-    only the wanted 1-D gradients get a pointer (gkg_bn_eval_bwd computes those and nothing else), and the scratch pair is
-    acquired only when there is one.  The weight gradient is always computed, like the composition's."""
-    wv = fused.grad_view(pr.W, pr.wshape) if pr.W.dtype == _F32 else None
-    dWv = torch.empty(pr.wshape, dtype=_F32, device=dev) if wv is None else wv
+def _proj_bwd(lib, p: ProjBN, pr: _Proj, scratch, dev, want):
+    """Backward half of a projection's descriptor -> (dW, dgamma, dbeta, dbias): the gradient outputs (bucket slots when the
+    parameters have them) and the BN pass's scratch buffers.  ``want`` None: train mode — gamma's and beta's gradients are always
+    written, the conv bias has none, the scratch pair is always used.  A frozen layer passes ctx.needs_input_grad of (W, gamma,
+    beta, bias): only the wanted 1-D gradients get a pointer (gkg_bn_eval_bwd computes those and nothing else), and the scratch
+    pair is acquired only when there is one.  The weight gradient is always computed, like the composition's."""
+    if want is None:
+        dWv, dgamma, dbeta = fused._grad_outs((pr.W, pr.gamma, pr.beta), pr.wshape, pr.nch, dev)
+        dbias = None
+    else:
+        wv = fused.grad_view(pr.W, pr.wshape) if pr.W.dtype == _F32 else None
+        dWv = torch.empty(pr.wshape, dtype=_F32, device=dev) if wv is None else wv
+        dgamma = _slot(pr.gamma, pr.nch, dev) if want[1] else None
+        dbeta = _slot(pr.beta, pr.nch, dev) if want[2] else None
+        dbias = _slot(pr.bias, pr.nch, dev) if (want[3] and pr.bias is not None) else None
     if not getattr(dWv, "_gkg_zero", False):
         dWv.zero_()                                      # the weight-gradient kernels ADD into dw
-    dgamma = _slot(pr.gamma, pr.nch, dev) if want[1] else None
-    dbeta = _slot(pr.beta, pr.nch, dev) if want[2] else None
-    dbias = _slot(pr.bias, pr.nch, dev) if (want[3] and pr.bias is not None) else None
-    if dgamma is not None or dbeta is not None or dbias is not None:
+    if want is None or dgamma is not None or dbeta is not None or dbias is not None:
         cur, other, zero = scratch.acquire(lib, 2 * pr.nch)
         p.bsum, p.bzero, p.bzero_n = cur.data_ptr(), other.data_ptr(), zero
     else:
@@ -448,6 +461,54 @@ def _issue_wgrads(lib, wq, n, outs, keep, device):
     _lib.check(lib.gkg_linear_wgrad_x6_batch(wq, n, fused.WGRAD_UNITS, _stream()), "gkg_linear_wgrad_x6_batch (block)")
 
 
+# ----------------------------------------------------------------------------------------------- the two Functions' common part
+def _forward(lib, plan, d, dev, N, M, relative_pos, has_y, want_edge, keys_key, entry):
+    """A block's forward call on the descriptor ``d`` (a copy of the plan's template with the block's own inputs and outputs set):
+    BN scratch (none for a frozen block: no statistics pass), forward arena, the projections, the graph op, the split-K workspace,
+    the call -> (arena, key object of the k-NN problem, edge tensor | None)."""
+    keep = []
+    scratch = None if plan.frozen else fused._BnScratch.of(dev)
+    buf = torch.empty(plan.fwd_total, dtype=_F32, device=dev)
+    _point(d, plan.fwd, buf.data_ptr())
+    B, Cc, groups = plan.dims[0], plan.dims[1], plan.groups
+    with (nullcontext() if scratch is None else scratch.one_call()):
+        for nm, pr in zip(plan.names, plan.projs):
+            _proj_fwd(lib, getattr(d, nm), pr, scratch, keep)
+        key, edge = _graph_op(lib, plan, d.graph, B, groups, Cc // groups, N, M, relative_pos, has_y, want_edge, dev, keys_key, keep)
+        sk = fused._sk_ws(dev)
+        d.sk_ws, d.sk_bytes = sk.data_ptr(), sk.numel()
+        _lib.check(getattr(lib, entry)(C.byref(d), _stream()), entry)
+    return buf, key, edge
+
+
+def _backward(ctx, buf, weights, lead, keep, entry):
+    """A block's backward call on ctx.desc (the block's own gradient inputs and outputs set): backward arena, flags, BN scratch
+    (none for a frozen block that wants no 1-D gradient), the projections in backward order — the order of wq[] —, the call, the
+    weight gradients -> ``lead`` (the gradients of the inputs in front of the parameters) + per projection, in forward order,
+    (dW, dgamma, dbeta[, dbias])."""
+    lib = _lib.load()
+    plan, d, dev = ctx.plan, ctx.desc, buf.device
+    tbuf = torch.empty(plan.bwd_total, dtype=_F32, device=dev)
+    _point(d, plan.bwd, tbuf.data_ptr())
+    d.bwd_flags = fused._block_flags()
+    n, st = len(plan.projs), plan.stride
+    need = ctx.needs_input_grad[len(lead):]
+    scratch = fused._BnScratch.of(dev) if (not plan.frozen or _want_1d(need, plan.projs)) else None
+    wq = (_lib.WgradProblem * n)()
+    outs = [None] * n
+    with (nullcontext() if scratch is None else scratch.one_call()):
+        for i in reversed(range(n)):
+            outs[i] = _proj_bwd(lib, getattr(d, plan.names[i]), plan.projs[i], scratch, dev,
+                                need[st * i:st * (i + 1)] if plan.frozen else None)
+        _lib.check(getattr(lib, entry)(C.byref(d), wq, _stream()), entry)
+    _issue_wgrads(lib, wq, n, tuple(o[0] for o in reversed(outs)), (buf, tbuf) + keep, dev)
+    grads = list(lead)
+    for o, w in zip(outs, weights):
+        grads.append(o[0].view_as(w))
+        grads += o[1:st]
+    return tuple(grads)
+
+
 # ----------------------------------------------------------------------------------------------- Grapher
 class _GrapherBlockFn(torch.autograd.Function):
     @staticmethod
@@ -457,42 +518,25 @@ class _GrapherBlockFn(torch.autograd.Function):
         _bind(lib)
         B, Cc, H, W = plan.dims
         N, T, dev = H * W, B * H * W, x.device
-        groups = plan.groups
         x = x.contiguous()
         d = GrapherBlock.from_buffer_copy(plan.tmpl)
-        keep = []
-        scratch = None if plan.frozen else fused._BnScratch.of(dev)
-        buf = torch.empty(plan.fwd_total, dtype=_F32, device=dev)
-        base = buf.data_ptr()
-        oxt, oXM, oA2, oY1, oY2, oY3, ob1, ob2, ob3, oarg = [base + 4 * o for o in plan.fwd_offs]
         out = torch.empty((B, Cc, H, W), dtype=_F32, device=dev)
         out_tm = torch.empty((T, Cc), dtype=_F32, device=dev) if dual else None
         d.B, d.C, d.H, d.W = B, Cc, H, W
         d.x, d.out, d.out_tm = x.data_ptr(), out.data_ptr(), _ptr(out_tm)
-        d.xt, d.XM, d.A2 = oxt, oXM, oA2
-        p1, pc, p2 = plan.projs
-        with (_NO_SCRATCH if scratch is None else scratch.one_call()):
-            _proj_fwd(lib, d.fc1, p1, scratch, keep, oY1, ob1)
-            _proj_fwd(lib, d.conv, pc, scratch, keep, oY2, ob2)
-            _proj_fwd(lib, d.fc2, p2, scratch, keep, oY3, ob3)
-            _graph_op(lib, plan, d.graph, B, groups, Cc // groups, N, N, relative_pos, False, False, dev, None, keep)
-            d.graph.arg = oarg
-            sk = fused._sk_ws(dev)
-            d.sk_ws, d.sk_bytes = sk.data_ptr(), sk.numel()
-            kk = None
-            if label_knn is not None and dual and fused.KNN_PREP:
-                G2, L2, k2, d2, fm2 = label_knn
-                if Cc % G2 == 0 and (Cc // G2) % 4 == 0:
-                    kk = fused._KnnKey(B, G2, Cc // G2, L2, N, k2, d2, True, None, fm2)
-                    kk.as_keys = 1
-                    kk.ws = fused._ws(lib.gkg_knn_workspace_bytes(B * G2, Cc // G2, L2, N, k2, d2, _lib.F32, _lib.KNN_NORMALIZE), dev)
-                    d.keys_G, d.keys_L, d.keys_k, d.keys_d, d.keys_fused_mr, d.keys_flags = G2, L2, k2, d2, int(fm2), kk.flags
-                    d.keys_ws, d.keys_ws_bytes = kk.ws.data_ptr(), kk.ws.numel()
-            _lib.check(lib.gkg_grapher_fwd(C.byref(d), _stream()), "gkg_grapher_fwd")
+        kk = None
+        if label_knn is not None and dual and fused.KNN_PREP:     # the label block behind announced its graph: prepare its keys
+            G2, L2, k2, d2, fm2 = label_knn
+            if Cc % G2 == 0 and (Cc // G2) % 4 == 0:
+                kk = fused._KnnKey(B, G2, Cc // G2, L2, N, k2, d2, True, None, fm2)
+                kk.as_keys = 1
+                kk.ws = fused._ws(lib.gkg_knn_workspace_bytes(B * G2, Cc // G2, L2, N, k2, d2, _lib.F32, _lib.KNN_NORMALIZE), dev)
+                d.keys_G, d.keys_L, d.keys_k, d.keys_d, d.keys_fused_mr, d.keys_flags = G2, L2, k2, d2, int(fm2), kk.flags
+                d.keys_ws, d.keys_ws_bytes = kk.ws.data_ptr(), kk.ws.numel()
+        buf, _, _ = _forward(lib, plan, d, dev, N, N, relative_pos, False, False, None, "gkg_grapher_fwd")
         if kk is not None:
             out_tm._gkg_knn_keys = kk
-        st = 4 if plan.frozen else 3
-        ctx.save_for_backward(buf, params[0], params[st], params[2 * st])
+        ctx.save_for_backward(buf, *params[::plan.stride])
         ctx.desc = d
         ctx.plan = plan
         if dual:
@@ -502,40 +546,19 @@ class _GrapherBlockFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout, dtm=None):
-        lib = _lib.load()
         plan = ctx.plan
         B, Cc, H, W = plan.dims
         if dout is None and dtm is None:
-            return (None,) * (5 + (12 if plan.frozen else 9))
-        buf, w1, wc, w2 = ctx.saved_tensors
-        T, dev = B * H * W, buf.device
-        d = ctx.desc
-        tbuf = torch.empty(plan.bwd_total, dtype=_F32, device=dev)
-        base = tbuf.data_ptr()
-        d.g3, d.dY3, d.gx1, d.dY1, d.dxt, d.dA2, d.dY2, d.dXM = [base + 4 * o for o in plan.bwd_offs]
+            return (None,) * (5 + len(plan.params))
+        buf, *weights = ctx.saved_tensors
+        dev, d = buf.device, ctx.desc
         dx = torch.empty((B, Cc, H, W), dtype=_F32, device=dev)
         if dout is None:                                          # only the token-major companion was used downstream
             dout = torch.zeros((B, Cc, H, W), dtype=_F32, device=dev)
         dout_c = dout.contiguous()
         dtm_c = None if dtm is None else dtm.contiguous()
         d.dout, d.dout_tm, d.dx = dout_c.data_ptr(), _ptr(dtm_c), dx.data_ptr()
-        d.bwd_flags = fused._block_flags()
-        need = ctx.needs_input_grad
-        scratch = fused._BnScratch.of(dev) if (not plan.frozen or _want_1d(need[5:], plan.projs)) else None
-        wq = (_lib.WgradProblem * 3)()
-        p1, pc, p2 = plan.projs
-        with (_NO_SCRATCH if scratch is None else scratch.one_call()):
-            if plan.frozen:
-                o2 = _proj_bwd_frozen(lib, d.fc2, p2, scratch, dev, need[13:17])
-                oc = _proj_bwd_frozen(lib, d.conv, pc, scratch, dev, need[9:13])
-                o1 = _proj_bwd_frozen(lib, d.fc1, p1, scratch, dev, need[5:9])
-            else:
-                o2 = _proj_bwd(lib, d.fc2, p2, scratch, dev)
-                oc = _proj_bwd(lib, d.conv, pc, scratch, dev)
-                o1 = _proj_bwd(lib, d.fc1, p1, scratch, dev)
-            _lib.check(lib.gkg_grapher_bwd(C.byref(d), wq, _stream()), "gkg_grapher_bwd")
-        _issue_wgrads(lib, wq, 3, (o2[0], oc[0], o1[0]), (buf, tbuf, dout_c, dtm_c), dev)
-        return (dx, None, None, None, None, o1[0].view_as(w1), *o1[1:], oc[0].view_as(wc), *oc[1:], o2[0].view_as(w2), *o2[1:])
+        return _backward(ctx, buf, weights, (dx, None, None, None, None), (dout_c, dtm_c), "gkg_grapher_bwd")
 
 
 def _run_grapher(plan, mod, x, relative_pos, dual):
@@ -575,30 +598,16 @@ class _LabelBlockFn(torch.autograd.Function):
         _bind(lib)
         B, Cc, L, M, Cf = plan.dims
         T, dev = B * L, e2.device
-        groups = plan.groups
         d = LabelBlock.from_buffer_copy(plan.tmpl)
-        keep = []
-        scratch = None if plan.frozen else fused._BnScratch.of(dev)
-        buf = torch.empty(plan.fwd_total, dtype=_F32, device=dev)
-        base = buf.data_ptr()
-        oXM, oA2, oh2, of1, oY1, oY2, oY3, oY4, oY5, ob1, ob2, ob3, ob4, ob5, oarg = [base + 4 * o for o in plan.fwd_offs]
         out = torch.empty((T, Cc), dtype=_F32, device=dev)
         d.B, d.C, d.L, d.M = B, Cc, L, M
         d.e, d.ft, d.out = e2.data_ptr(), ft.data_ptr(), out.data_ptr()
-        d.XM, d.A2, d.h2, d.f1 = oXM, oA2, oh2, of1
-        with (_NO_SCRATCH if scratch is None else scratch.one_call()):
-            for p, pr, oy, ob in zip((d.fc1, d.conv, d.fc2, d.ffn1, d.ffn2), plan.projs, (oY1, oY2, oY3, oY4, oY5), (ob1, ob2, ob3, ob4, ob5)):
-                _proj_fwd(lib, p, pr, scratch, keep, oy, ob)
-            key, edge = _graph_op(lib, plan, d.graph, B, groups, Cc // groups, L, M, None, True, True, dev, keys_key, keep)
-            d.graph.arg = oarg
-            sk = fused._sk_ws(dev)
-            d.sk_ws, d.sk_bytes = sk.data_ptr(), sk.numel()
-            _lib.check(lib.gkg_grapher_label_fwd(C.byref(d), _stream()), "gkg_grapher_label_fwd")
+        buf, key, edge = _forward(lib, plan, d, dev, L, M, None, True, True, keys_key, "gkg_grapher_label_fwd")
         if producer is not None and fused.KNN_PREP:
-            lk = (groups, L, plan.k, plan.d, key.fused_mr)                 # the Grapher in front prepares this graph's keys
+            lk = (plan.groups, L, plan.k, plan.d, key.fused_mr)            # the Grapher in front prepares this graph's keys
             if producer.__dict__.get("_gkg_label_knn") != lk:              # from its next call on (fused.grapher_label_forward)
                 producer._gkg_label_knn = lk
-        ctx.save_for_backward(buf, e2, ft, *params[::4 if plan.frozen else 3])
+        ctx.save_for_backward(buf, e2, ft, *params[::plan.stride])
         ctx.desc = d
         ctx.plan = plan
         ctx.mark_non_differentiable(edge)
@@ -607,44 +616,17 @@ class _LabelBlockFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout, _gedge=None):
-        lib = _lib.load()
         plan = ctx.plan
         if dout is None:
-            return (None,) * (5 + (20 if plan.frozen else 15))
+            return (None,) * (5 + len(plan.params))
         B, Cc, L, M, Cf = plan.dims
-        T = B * L
-        buf, e2, ft, w1, wc, w2, w4, w5 = ctx.saved_tensors
-        dev = buf.device
-        d = ctx.desc
-        tbuf = torch.empty(plan.bwd_total, dtype=_F32, device=dev)
-        base = tbuf.data_ptr()
-        d.dY5, d.dh2, d.dY3, d.gx1, d.dY1, d.df1, d.dY4, d.dA2, d.dY2, d.dXM = [base + 4 * o for o in plan.bwd_offs]
-        de = torch.empty((T, Cc), dtype=_F32, device=dev)
+        buf, e2, ft, *weights = ctx.saved_tensors
+        dev, d = buf.device, ctx.desc
+        de = torch.empty((B * L, Cc), dtype=_F32, device=dev)
         dft = torch.empty((B, M, Cc), dtype=_F32, device=dev)
         dout_c = dout.contiguous()
         d.dout, d.de, d.dft = dout_c.data_ptr(), de.data_ptr(), dft.data_ptr()
-        d.bwd_flags = fused._block_flags()
-        need = ctx.needs_input_grad
-        scratch = fused._BnScratch.of(dev) if (not plan.frozen or _want_1d(need[5:], plan.projs)) else None
-        wq = (_lib.WgradProblem * 5)()
-        p1, pc, p3, p4, p5 = plan.projs
-        with (_NO_SCRATCH if scratch is None else scratch.one_call()):
-            if plan.frozen:
-                o5 = _proj_bwd_frozen(lib, d.ffn2, p5, scratch, dev, need[21:25])
-                o4 = _proj_bwd_frozen(lib, d.ffn1, p4, scratch, dev, need[17:21])
-                o3 = _proj_bwd_frozen(lib, d.fc2, p3, scratch, dev, need[13:17])
-                oc = _proj_bwd_frozen(lib, d.conv, pc, scratch, dev, need[9:13])
-                o1 = _proj_bwd_frozen(lib, d.fc1, p1, scratch, dev, need[5:9])
-            else:
-                o5 = _proj_bwd(lib, d.ffn2, p5, scratch, dev)
-                o4 = _proj_bwd(lib, d.ffn1, p4, scratch, dev)
-                o3 = _proj_bwd(lib, d.fc2, p3, scratch, dev)
-                oc = _proj_bwd(lib, d.conv, pc, scratch, dev)
-                o1 = _proj_bwd(lib, d.fc1, p1, scratch, dev)
-            _lib.check(lib.gkg_grapher_label_bwd(C.byref(d), wq, _stream()), "gkg_grapher_label_bwd")
-        _issue_wgrads(lib, wq, 5, (o5[0], o4[0], o3[0], oc[0], o1[0]), (buf, tbuf, e2, dout_c), dev)
-        return (de, dft, None, None, None, o1[0].view_as(w1), *o1[1:], oc[0].view_as(wc), *oc[1:], o3[0].view_as(w2), *o3[1:],
-                o4[0].view_as(w4), *o4[1:], o5[0].view_as(w5), *o5[1:])
+        return _backward(ctx, buf, weights, (de, dft, None, None, None), (e2, dout_c), "gkg_grapher_label_bwd")
 
 
 def label_forward(mod, e2, ft, groups, keys_key, producer=None):

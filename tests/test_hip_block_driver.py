@@ -83,6 +83,10 @@ def test_block_driver_is_bit_identical_to_the_composition(bucket, plans, shape, 
     the run-dependent order of the atomics decides the last bit of the saved mean (measured with tools/debug/dbg_block.py: two
     runs of the SAME path differ that way, DESIGN.md section 5).  A pair of runs that hits such a tie differently is repeated;
     a difference between the driver and the composition would show in every pair."""
+    _assert_bit_identical(monkeypatch, bucket, plans, shape)
+
+
+def _assert_bit_identical(monkeypatch, bucket, plans, shape):
     diff = None
     for attempt in range(4):
         c1, on = _run(True, monkeypatch, bucket=bucket, plans=plans, **shape)
@@ -102,6 +106,21 @@ def test_block_driver_is_bit_identical_to_the_composition(bucket, plans, shape, 
         assert float((a["edge"] == b["edge"]).float().mean()) >= 0.998, (step, "edge", diff)
     warnings.warn(f"driver and composition were never bit-identical in 4 pairs of runs (first difference {diff}); they agree to "
                   f"rounding - a BN mean on an fp32 rounding tie (DESIGN.md section 4)")
+
+
+SWITCHES = ["KNN_PREP", "KNN_MR", "BWD_FUSE", "DGRAD_STATS"]
+
+
+@pytest.mark.parametrize("switch", SWITCHES)
+def test_block_driver_matches_the_composition_with_a_switch_off(switch, monkeypatch):
+    """The driver's other branches, each against the composition under the same switch: KNN_PREP off takes fc1's plain apply pass
+    (un-prepared queries), KNN_MR off the two-launch graph (u16 lists in the Grapher, int64 lists in the label block), BWD_FUSE
+    off the stand-alone statistics / re-layout tail, DGRAD_STATS off the plain input-gradient GEMMs.  Same protocol and bounds as
+    test_block_driver_is_bit_identical_to_the_composition, at the shape with 80-column tiles, four groups and ragged 81-token
+    images."""
+    from gkgnet_amd import fused
+    monkeypatch.setattr(fused, switch, False)
+    _assert_bit_identical(monkeypatch, False, True, dict(C=80, H=9, L=7, B=5, G=4, d=1))
 
 
 def test_ineligible_calls_keep_the_composition(monkeypatch):

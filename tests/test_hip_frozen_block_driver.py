@@ -12,7 +12,7 @@ import ctypes
 import pytest
 import torch
 
-from test_hip_block_driver import _first_difference
+from test_hip_block_driver import SWITCHES, _first_difference
 
 pytestmark = pytest.mark.gpu
 
@@ -274,6 +274,18 @@ def test_frozen_blocks_through_the_driver_match_the_composition(shape, variant, 
                 assert (gr is None) == fz, name            # every trainable parameter (conv biases included) got a gradient, no other
     # (the Grapher's relative_pos is never trained; affine=False freezes the 2 x 8 BN scales and shifts as well)
     assert sum(on[0]["frozen"]) == (1 + 16 if variant in ("frozen", "sync") else 1)
+
+
+@pytest.mark.parametrize("switch", SWITCHES)
+def test_frozen_blocks_through_the_driver_match_the_composition_with_a_switch_off(switch, monkeypatch):
+    """The frozen form of the driver's other branches (test_hip_block_driver.py: un-prepared queries, the two-launch graph, the
+    un-fused backward tail; DGRAD_STATS has nothing to switch in a frozen block and must change nothing): bit equality at once."""
+    from gkgnet_amd import fused
+    monkeypatch.setattr(fused, switch, False)
+    c1, on, _ = _run(True, "frozen_affine", monkeypatch, bucket=False, **SHAPES[1])
+    c0, off, _ = _run(False, "frozen_affine", monkeypatch, bucket=False, **SHAPES[1])
+    assert c1 == {"g": 3, "l": 3} and c0 == {"g": 0, "l": 0}, (c1, c0)
+    assert _first_difference(on, off) is None, _first_difference(on, off)
 
 
 # ------------------------------------------------------------------------------------------------ (3) scope
