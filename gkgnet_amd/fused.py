@@ -116,165 +116,63 @@ def _x6_wgrad_ok(dY, x, nb=1) -> bool:
 
 
 # ---- batched weight gradients (round 5) ---------------------------------------------------------------------------------
-# Nothing downstream of a backward pass reads a weight gradient, so the projections' dW launches are taken OFF the chain of
-# dependent launches: while the backward runs they are only queued (operands kept alive), and ONE launch at the end of the
-# backward pass (an autograd engine callback) computes all of them (csrc/gkg_gemm_x6.hip wgrad_x6_batch_kernel).  At the cfg2
-# shapes the ten weight gradients were ten launches of 50-400 workgroups on 256 CUs, 12-40 us each (195 of 981 us, six of them
-# vendor kernels); together they fill the chip.  Queued only when the gradient has a slot in a GradBucket (the kernel writes
-# there; autograd adopts the returned view as ``p.grad``) — a caller without a bucket gets its dW from this node's own launch,
-# as before, because autograd consumes the returned tensor at once.  GradBucket flushes the queue before it reads a gradient
-# (all_reduce / chunk all-reduce / clip / pack).  GKG_DISABLE=wgrad_batch: every weight gradient in its own launch.
+# wgrad_queue.py owns the queue and its protocol; here is the policy, what goes into it.  Queued only when the gradient has a slot
+# in a GradBucket (the kernel writes there; autograd adopts the returned view as ``p.grad``; GradBucket flushes the queue before
+# it reads a gradient) — without a bucket autograd consumes the returned tensor at once, so the node launches its own dW, as
+# before.  GKG_DISABLE=wgrad_batch: every weight gradient in its own launch.
 WGRAD_BATCH = "wgrad_batch" not in _DISABLED
 WGRAD_UNITS = 0          # rows per workgroup of the batched launch / 128 (0: the library's default, 20)
 
-
-class _WgradQueue:
-    MAX = 192
-    # Operand bytes the queue may keep alive: deferring holds every layer's (dY, x) pair until the batch runs —
-    # GKGNet-576's train step peaked at 30.7 GiB against 24.2 before the batching.  Problems that fill the chip on their own gain
-    # nothing from the batch (see _wgrad_defer) and are launched at once; what is left is flushed early past this cap.
-    MAX_BYTES = 1 << 30
-
-    def __init__(self):
-        self.items, self.keep, self.task = [], [], -1
-        self.bytes = 0
-        self.stream, self.device = None, None        # where the queued operands are produced: the batch is launched THERE
-
-
-_WQ = _WgradQueue()
+from . import parallel as _parallel      # noqa: E402
+from . import planes as _planes_mod      # noqa: E402
+from .wgrad_queue import QUEUE as _WQ    # noqa: E402
+_parallel._ZERO_DEFER[:] = [_planes_mod.defer_zero, _planes_mod.flush_deferred_zero]
 
 
 def flush_wgrads():
     """Launch every queued weight gradient (no-op when the queue is empty)."""
-    q = _WQ
-    if not q.items:
-        q.keep, q.task, q.bytes = [], -1, 0
-        return
-    items, q.items, q.task = q.items, [], -1
-    try:
-        _launch_wgrads(q, items)
-        # the engine runs this callback in the thread that called backward(), whose current stream need not be the nodes'
-        # (ADVICE r5): whatever that stream does next with the gradients (pack, clip, the optimiser) is ordered behind the batch
-        cur = torch.cuda.current_stream(q.device)
-        if q.stream is not None and cur.cuda_stream != q.stream:
-            ev = torch.cuda.Event()
-            with torch.cuda.device(q.device):
-                ev.record(torch.cuda.ExternalStream(q.stream, device=q.device) if q.stream else torch.cuda.default_stream(q.device))
-            cur.wait_event(ev)
-    finally:
-        q.keep, q.bytes = [], 0          # the launch is stream-ordered behind the operands' producers and ahead of their reuse
+    _WQ.flush()
 
 
-def _launch_wgrads(q, items):
-    """One batched launch on the stream (and device) the operands were produced on — the engine callback that flushes the queue
-    runs in the thread that called backward(), whose current stream need not be the backward nodes'."""
-    arr = (_lib.WgradProblem * len(items))(*items)
-    with torch.cuda.device(q.device):
-        _lib.check(_lib.load().gkg_linear_wgrad_x6_batch(arr, len(items), WGRAD_UNITS, q.stream), "gkg_linear_wgrad_x6_batch")
-
-
-from . import parallel as _parallel      # noqa: E402
-from . import planes as _planes_mod      # noqa: E402
-_parallel._FLUSH.append(flush_wgrads)
-_parallel._ZERO_DEFER[:] = [_planes_mod.defer_zero, _planes_mod.flush_deferred_zero]
-
-
-def _wq_task() -> int:
-    """Id of the backward pass this thread is executing (-1: none — nobody would flush a queue —, or one that builds a graph:
-    create_graph makes autograd clone what a node returns, so a slot filled later would never reach p.grad)."""
-    task_id = getattr(torch._C, "_current_graph_task_id", None)
-    task = task_id() if task_id is not None else -1
-    return -1 if torch.is_grad_enabled() else task
-
-
-def _wq_open(task, device):
-    """The queue of backward pass ``task`` on the current stream: registers the flush callback on first use, launches what another
-    pass / stream / device left behind."""
-    q = _WQ
-    st = _stream()
-    if q.task != task:
-        if q.items:                      # another backward pass is still queued (a nested / re-entrant backward, or one that raised
-            items, q.items = q.items, []     # before its callback): its operands are alive — launch, do not drop (ADVICE r5)
-            _launch_wgrads(q, items)
-        q.keep, q.bytes = [], 0
-        q.task = task
-        torch.autograd.Variable._execution_engine.queue_callback(flush_wgrads)
-    elif q.items and (q.stream != st or q.device != device):
-        items, q.items = q.items, []     # another stream / device: what is queued goes out where it was produced
-        _launch_wgrads(q, items)
-    q.stream, q.device = st, device
-    return q
-
-
-def _wq_launch(q):
-    """Launch what is queued now (a cap was reached): the launch is stream-ordered behind the operands' producers and ahead of
-    their reuse, so the keep-alive references can go with it."""
-    items, q.items = q.items, []
-    if items:
-        _launch_wgrads(q, items)
-    q.keep, q.bytes = [], 0
-
-
-def _wq_push(q, problem, out, keep, nbytes):
-    """One problem into the queue; q.keep[i] is what keeps q.items[i]'s operands alive (the two lists have the same length)."""
-    q.items.append(problem)
-    q.keep.append(keep)
-    owner = getattr(out, "_gkg_owner", None)
-    if owner is not None:
-        owner._gkg_deferred = True       # the slot, not p.grad, holds this gradient until the batch has run (GradBucket._resident)
-    q.bytes += nbytes
-
-
-def _wq_cap(q):
-    if len(q.items) >= q.MAX or q.bytes > q.MAX_BYTES:
-        _wq_launch(q)
+def _wgrad_queue(device):
+    """The queue to defer a weight gradient into right now (opened for the running backward pass on the current stream), or None:
+    batching switched off, or no backward pass that would flush it."""
+    if not (WGRAD_BATCH and not DETERMINISTIC and GEMM_MATH == "x6"):
+        return None
+    task = _WQ.task_id()
+    return _WQ.open(task, device, WGRAD_UNITS) if task >= 0 else None
 
 
 def _wgrad_defer(dY, x, out, R, cin, cout, nb, ldg, g_bs, ldx, x_bs, kperm=0) -> bool:
     """Queue dW = dY^T x for the batched launch.  True: queued (``out`` will hold the gradient when the backward pass ends)."""
-    if not (WGRAD_BATCH and not DETERMINISTIC and GEMM_MATH == "x6"
-            and out is not None and getattr(out, "_gkg_slot", False) and dY.dtype == _F32 and x.dtype == _F32
+    if not (out is not None and getattr(out, "_gkg_slot", False) and dY.dtype == _F32 and x.dtype == _F32
             and R % 128 == 0 and cin % 4 == 0 and cout % 4 == 0 and ldg % 4 == 0 and ldx % 4 == 0 and g_bs % 4 == 0 and x_bs % 4 == 0
             and dY.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0 and R * max(ldg, ldx) * 4 < 0xffffffff and nb <= 64):
-        return False
-    task = _wq_task()
-    if task < 0:
         return False
     # a problem that fills the chip on its own (GKGNet-576's stage-1 / stage-2 layers: thousands of 128-row units) keeps its
     # stand-alone slabs inside a batch anyway (csrc x6_wgrad_plan): launching it from the node costs nothing and frees its operands
     tiles = nb * ((cout + 63) // 64) * ((cin + 63) // 64)
     if tiles * min(R // 128, 64) >= 2048 and R >= 32768:
         return False
-    q = _wq_open(task, dY.device)
+    q = _wgrad_queue(dY.device)
+    if q is None:
+        return False
     if not getattr(out, "_gkg_zero", False):
         out.zero_()
-    _wq_push(q, _lib.WgradProblem(dY.data_ptr(), x.data_ptr(), out.data_ptr(), g_bs, x_bs, ldg, ldx, R, cin, cout, nb, kperm), out,
-             (dY, x), (dY.numel() + x.numel()) * 4)
-    _wq_cap(q)
+    q.push((_lib.WgradProblem(dY.data_ptr(), x.data_ptr(), out.data_ptr(), g_bs, x_bs, ldg, ldx, R, cin, cout, nb, kperm),), (out,),
+           (dY, x))
     return True
 
 
 def _wgrad_defer_block(problems, n, outs, keep, device) -> bool:
     """The block driver's weight-gradient problems (prebuilt GkgWgradProblem array, dW slots already zero): all of them into the
     backward pass's batched launch, or none (False: the caller launches them now)."""
-    if not (WGRAD_BATCH and not DETERMINISTIC and GEMM_MATH == "x6" and all(getattr(o, "_gkg_slot", False) for o in outs)
-            and all(problems[i].R % 128 == 0 for i in range(n))):
+    if not (all(getattr(o, "_gkg_slot", False) for o in outs) and all(problems[i].R % 128 == 0 for i in range(n))):
         return False
-    task = _wq_task()
-    if task < 0:
+    q = _wgrad_queue(device)
+    if q is None:
         return False
-    q = _wq_open(task, device)
-    # The block's problems read ONE set of arenas (``keep``), so they enter the queue together: a launch forced by the cap happens
-    # before the first or after the last of them, never in between (it clears q.keep — the rest of the block would stay queued
-    # with nothing holding its operands, ADVICE r6), and every entry carries the keep tuple.
-    if q.items and len(q.items) + n > q.MAX:
-        _wq_launch(q)
-    for i in range(n):
-        p = _lib.WgradProblem.from_buffer_copy(problems[i])
-        # operand bytes: this problem's (dY, x) pair, as _wgrad_defer counts it.  (The arenas in ``keep`` hold more than the
-        # operands, and problems of one block may share an x: the sum errs on the early side of MAX_BYTES, never the late one.)
-        _wq_push(q, p, outs[i], keep, 4 * p.nb * p.R * (p.cin + p.cout))
-    _wq_cap(q)
+    q.push([_lib.WgradProblem.from_buffer_copy(problems[i]) for i in range(n)], outs, keep)
     return True
 
 

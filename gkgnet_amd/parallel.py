@@ -36,7 +36,7 @@ def init_distributed(backend: Optional[str] = None) -> tuple:
 
 
 _ZERO_DEFER = []     # [defer(t) -> bool, flush()]: fused registers planes.defer_zero / planes.flush_deferred_zero
-_FLUSH = []          # callables that complete gradients still queued for a batched launch (fused.flush_wgrads registers itself)
+_FLUSH = []          # callables that complete gradients still queued for a batched launch (wgrad_queue registers its flush)
 
 
 def flush_pending_grads():
@@ -289,7 +289,7 @@ def grad_view(p: torch.nn.Parameter, shape=None):
     v = flat[o:o + p.numel()]
     v = v.view(p.shape if shape is None else shape)
     v._gkg_slot = True                            # a bucket slot: kernels may fill it after the backward node has returned it
-    v._gkg_owner = p                              # (fused._wgrad_defer marks the parameter: see GradBucket._resident)
+    v._gkg_owner = p                              # (WgradQueue.push marks the parameter: see GradBucket._resident)
     if getattr(p, "_gkg_clean", False):           # zeroed by release(prezero=True) and not written since
         p._gkg_clean = False
         v._gkg_zero = True

@@ -69,6 +69,7 @@ def _block_grads(batch: bool, graph: bool, monkeypatch):
     """Parameter gradients of one Grapher -> GrapherLabel fwd+bwd step with a GradBucket."""
     from gkgnet_amd import fused, parallel
     from gkgnet_amd.grapher import Grapher, GrapherLabel
+    from gkgnet_amd.wgrad_queue import QUEUE
     monkeypatch.setattr(fused, "WGRAD_BATCH", batch)
     torch.manual_seed(3)
     C, H, L, B = 64, 16, 24, 8                      # T = 2048 rows (whole units), label rows 192 (ragged: own launches)
@@ -106,7 +107,7 @@ def _block_grads(batch: bool, graph: bool, monkeypatch):
         gr.replay()
         gr.replay()
     torch.cuda.synchronize()
-    assert not fused._WQ.items and not fused._WQ.keep
+    assert not QUEUE.items and not QUEUE.keep
     return bucket.flat.clone(), x.grad.clone(), e.grad.clone()
 
 
@@ -123,13 +124,14 @@ def test_deferred_queue_gives_the_per_layer_gradients(graph, monkeypatch):
 def test_without_a_bucket_nothing_is_queued(monkeypatch):
     from gkgnet_amd import fused
     from gkgnet_amd.grapher import Grapher
+    from gkgnet_amd.wgrad_queue import QUEUE
     monkeypatch.setattr(fused, "WGRAD_BATCH", True)
     torch.manual_seed(0)
     g = Grapher(32, 9, 1, "mr", "gelu", "batch", True, False, 0.2, 1, n=256, relative_pos=True, use_multi_group=True,
                 num_group=2).cuda().train()
     x = torch.randn(8, 32, 16, 16, device="cuda").requires_grad_(True)
     g(x).sum().backward()
-    assert not fused._WQ.items and not fused._WQ.keep
+    assert not QUEUE.items and not QUEUE.keep
     assert all(p.grad is not None and torch.isfinite(p.grad).all() for p in g.parameters() if p.requires_grad and p.dim() > 1)
 
 
@@ -169,7 +171,7 @@ def test_backward_on_a_side_stream_launches_the_batch_there(monkeypatch):
 
 # ---------------------------------------------------------------------------------------------------------------- queue overflow
 # A cap reached while a block's problems enter the queue: the block driver hands fused._wgrad_defer_block its 3 (Grapher) or
-# 5 (GrapherLabel) problems with ONE keep-alive tuple (the arenas every one of them reads).  A launch forced by _WgradQueue.MAX /
+# 5 (GrapherLabel) problems with ONE keep-alive tuple (the arenas every one of them reads).  A launch forced by WgradQueue.MAX /
 # MAX_BYTES clears q.keep, so it must come before the first or after the last problem of a block, never in between.
 def _three_blocks(monkeypatch, max_items=None, max_bytes=None, batch=True, record=None):
     """Two Graphers and a GrapherLabel through the block driver with bucket slots; one fwd + bwd step.  Backward order: the label
@@ -178,12 +180,13 @@ def _three_blocks(monkeypatch, max_items=None, max_bytes=None, batch=True, recor
     rows 32 * 16 = 512.  -> (flat gradients, dx, de)."""
     from gkgnet_amd import block, fused, parallel
     from gkgnet_amd.grapher import Grapher, GrapherLabel
+    from gkgnet_amd.wgrad_queue import QUEUE, WgradQueue
     monkeypatch.setattr(block, "ENABLED", True)
     monkeypatch.setattr(fused, "WGRAD_BATCH", batch)
     if max_items is not None:
-        monkeypatch.setattr(fused._WgradQueue, "MAX", max_items)
+        monkeypatch.setattr(WgradQueue, "MAX", max_items)
     if max_bytes is not None:
-        monkeypatch.setattr(fused._WgradQueue, "MAX_BYTES", max_bytes)
+        monkeypatch.setattr(WgradQueue, "MAX_BYTES", max_bytes)
     block._PLANS.clear()
     torch.manual_seed(13)
     C, H, L, B, G = 64, 12, 16, 32, 2
@@ -200,17 +203,17 @@ def _three_blocks(monkeypatch, max_items=None, max_bytes=None, batch=True, recor
     cx, ce = torch.randn(B, C, H, H, device="cuda", generator=gen), torch.randn(B, L, C, device="cuda", generator=gen)
     bucket.release(prezero=True)
     if record is not None:
-        real_defer, real_launch = fused._wgrad_defer_block, fused._launch_wgrads
+        real_defer, real_launch = fused._wgrad_defer_block, WgradQueue._launch_batch
 
         def op_bytes(p):
             return 4 * p.nb * p.R * (p.cin + p.cout)                       # the (dY, x) pair of one problem, fp32
 
-        def launch(q, items):
-            record["launches"].append((len(items), q.bytes, sum(op_bytes(p) for p in items)))
-            return real_launch(q, items)
+        def launch(q, arr, n):
+            record["launches"].append((n, q.bytes, sum(op_bytes(arr[i]) for i in range(n))))
+            return real_launch(q, arr, n)
 
         def defer(problems, n, outs, keep, device):
-            q = fused._WQ
+            q = QUEUE
             taken = real_defer(problems, n, outs, keep, device)
             mine = {problems[i].dw for i in range(n)}
             record["blocks"].append(dict(taken=taken, n=n, items=len(q.items), keeps=len(q.keep), bytes=q.bytes,
@@ -218,14 +221,14 @@ def _three_blocks(monkeypatch, max_items=None, max_bytes=None, batch=True, recor
                                          held=all(kp is not None and all(any(t is u for u in kp) for t in keep)
                                                   for p, kp in zip(q.items, q.keep) if p.dw in mine)))
             return taken
-        monkeypatch.setattr(fused, "_launch_wgrads", launch)
+        monkeypatch.setattr(WgradQueue, "_launch_batch", launch)
         monkeypatch.setattr(fused, "_wgrad_defer_block", defer)
     out = g2(g1(x))
     e2, _ = gl(e, out)
     torch.autograd.backward([out, e2], [cx, ce])
     bucket.pack()
     torch.cuda.synchronize()
-    assert not fused._WQ.items and not fused._WQ.keep and fused._WQ.bytes == 0
+    assert not QUEUE.items and not QUEUE.keep and QUEUE.bytes == 0
     return bucket.flat.clone(), x.grad.clone(), e.grad.clone()
 
 

@@ -56,7 +56,7 @@ def main():
     print(f"eager: {1e3 * t_all / args.steps:.4f} ms/step wall ({1e3 * t_issue / args.steps:.4f} ms/step to issue)")
     # own timers around the four block calls (forward: this thread; backward: the autograd engine's thread, which cProfile
     # does not see) and around the C entry points inside them
-    from gkgnet_amd import _lib, block, fused
+    from gkgnet_amd import _lib, block, fused, wgrad_queue
     lib = _lib.load()
     acc = {}
 
@@ -75,7 +75,8 @@ def main():
     for cls, nm in ((block._GrapherBlockFn, "grapher"), (block._LabelBlockFn, "label")):
         cls.forward = staticmethod(timed(f"py {nm}.forward (incl. C)", cls.forward))
         cls.backward = staticmethod(timed(f"py {nm}.backward (incl. C)", cls.backward))
-    fused.flush_wgrads = timed("py flush_wgrads (incl. C)", fused.flush_wgrads)
+    wgrad_queue.QUEUE.flush = timed("py flush_wgrads (incl. C)", wgrad_queue.QUEUE.flush)       # what fused.flush_wgrads, the engine
+                                                                                              # callback and GradBucket all call
     for nm in ("_proj_fwd", "_proj_bwd", "_graph_op", "_issue_wgrads", "try_grapher", "try_label", "_run_grapher"):
         setattr(block, nm, timed("  block." + nm, getattr(block, nm)))
     block._Plan.valid = timed("  block._Plan.valid", block._Plan.valid)
