@@ -26,56 +26,15 @@ from contextlib import nullcontext
 
 import torch
 
-from . import _lib, fused
+from . import _abi, _lib, fused
 from .ops import _ptr, _stream
 
 _F32 = torch.float32
-V, I, Z, F, U = C.c_void_p, C.c_int, C.c_size_t, C.c_float, C.c_uint
-
-
-class ProjBN(C.Structure):
-    _fields_ = [("planes_fwd", V), ("planes_dgrad", V), ("gamma", V), ("beta", V), ("bias", V), ("running_mean", V), ("running_var", V),
-                ("nbt", V), ("momentum", F), ("eps", F), ("cin", I), ("cout", I), ("nb", I), ("fsum", V), ("fzero", V), ("fzero_n", Z),
-                ("bsum", V), ("bzero", V), ("bzero_n", Z), ("Y", V), ("bn", V), ("dw", V), ("dgamma", V), ("dbeta", V), ("dbias", V)]
-
-
-class GraphOp(C.Structure):
-    _fields_ = [("G", I), ("k", I), ("d", I), ("fused_mr", I), ("relpos", V), ("knn_flags", U), ("mr_flags", U), ("knn_ws", V),
-                ("knn_ws_bytes", Z), ("arg", V), ("nn16", V), ("nn_idx", V), ("center", V)]
-
-
-class GrapherBlock(C.Structure):
-    _fields_ = [("B", I), ("C", I), ("H", I), ("W", I), ("x", V), ("out", V), ("out_tm", V), ("xt", V), ("XM", V), ("A2", V),
-                ("fc1", ProjBN), ("conv", ProjBN), ("fc2", ProjBN), ("graph", GraphOp), ("sk_ws", V), ("sk_bytes", Z),
-                ("keys_G", I), ("keys_L", I), ("keys_k", I), ("keys_d", I), ("keys_fused_mr", I), ("keys_flags", U), ("keys_ws", V),
-                ("keys_ws_bytes", Z), ("dout", V), ("dout_tm", V), ("dx", V), ("g3", V), ("dY3", V), ("dA2", V), ("dY2", V), ("dXM", V),
-                ("gx1", V), ("dY1", V), ("dxt", V), ("bwd_flags", U), ("bn_frozen", I)]
-
-
-class LabelBlock(C.Structure):
-    _fields_ = [("B", I), ("C", I), ("L", I), ("M", I), ("e", V), ("ft", V), ("out", V), ("XM", V), ("A2", V), ("h2", V), ("f1", V),
-                ("fc1", ProjBN), ("conv", ProjBN), ("fc2", ProjBN), ("ffn1", ProjBN), ("ffn2", ProjBN), ("graph", GraphOp), ("sk_ws", V),
-                ("sk_bytes", Z), ("dout", V), ("de", V), ("dft", V), ("dY5", V), ("df1", V), ("dY4", V), ("dh2", V), ("dY3", V),
-                ("dA2", V), ("dY2", V), ("dXM", V), ("gx1", V), ("dY1", V), ("bwd_flags", U), ("bn_frozen", I)]
-
+# The block entry points' descriptors: include/gkg_hip.h's structs as _abi.py derives them (fields in declaration order).
+_S = _abi.header().structs
+ProjBN, GraphOp, GrapherBlock, LabelBlock = _S["GkgProjBN"], _S["GkgGraphOp"], _S["GkgGrapherBlock"], _S["GkgLabelBlock"]
 
 ENABLED = "block_driver" not in fused._DISABLED
-_BOUND = False
-
-
-def _bind(lib):
-    global _BOUND
-    if _BOUND:
-        return
-    lib.gkg_grapher_fwd.restype = I
-    lib.gkg_grapher_fwd.argtypes = [C.POINTER(GrapherBlock), V]
-    lib.gkg_grapher_bwd.restype = I
-    lib.gkg_grapher_bwd.argtypes = [C.POINTER(GrapherBlock), C.POINTER(_lib.WgradProblem), V]
-    lib.gkg_grapher_label_fwd.restype = I
-    lib.gkg_grapher_label_fwd.argtypes = [C.POINTER(LabelBlock), V]
-    lib.gkg_grapher_label_bwd.restype = I
-    lib.gkg_grapher_label_bwd.argtypes = [C.POINTER(LabelBlock), C.POINTER(_lib.WgradProblem), V]
-    _BOUND = True
 
 
 # ----------------------------------------------------------------------------------------------- eligibility
@@ -515,7 +474,6 @@ class _GrapherBlockFn(torch.autograd.Function):
     def forward(ctx, x, plan, relative_pos, label_knn, dual, *params):
         # params: (W, gamma, beta) of fc1, the grouped projection and fc2 — with the conv bias as a fourth for a frozen block
         lib = _lib.load()
-        _bind(lib)
         B, Cc, H, W = plan.dims
         N, T, dev = H * W, B * H * W, x.device
         x = x.contiguous()
@@ -595,7 +553,6 @@ class _LabelBlockFn(torch.autograd.Function):
     def forward(ctx, e2, ft, plan, keys_key, producer, *params):
         # params: (W, gamma, beta) of fc1, the grouped projection, fc2, FFN fc1 and FFN fc2 — + the conv bias for a frozen block
         lib = _lib.load()
-        _bind(lib)
         B, Cc, L, M, Cf = plan.dims
         T, dev = B * L, e2.device
         d = LabelBlock.from_buffer_copy(plan.tmpl)

@@ -19,10 +19,17 @@ def test_header_symbols_exported():
     lib = ctypes.CDLL(so)
     names = _declared()
     assert set(names) == set(_lib.EXPORTS), (names, _lib.EXPORTS)
+    assert len(names) == len(_lib.EXPORTS) >= 80
     for n in names:
         assert hasattr(lib, n), f"{n} declared in gkg_hip.h but not exported"
     lib.gkg_version.restype = ctypes.c_int
     assert lib.gkg_version() == _lib.ABI_VERSION
+    # ... and bound: after load() every declared entry point carries the header's signature (a function ctypes has not been told
+    # about has argtypes None and would take anything)
+    assert lib.gkg_version.argtypes is None
+    bound = _lib.load()
+    for n in names:
+        assert getattr(bound, n).argtypes is not None, f"{n} declared in gkg_hip.h but left unbound by load()"
 
 
 def test_workspace_query_is_pure_host_code():

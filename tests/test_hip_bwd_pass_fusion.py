@@ -310,7 +310,6 @@ def test_blocks_bwd_fuse_on_matches_off(driver, monkeypatch):
     so a pair that differs is repeated, as there; a real difference would show in every pair.)"""
     from gkgnet_amd import _lib, block, fused
     lib = _lib.load()
-    block._bind(lib)
     n = _count(monkeypatch, lib, fused)
     for attempt in range(4):
         for key in n:

@@ -274,7 +274,6 @@ def test_driver_and_composition_are_bit_identical_with_the_part_on(monkeypatch):
     tests/test_hip_block_driver.py — so a pair that differs is repeated; a real difference shows in every pair.)"""
     from gkgnet_amd import _lib, block
     lib = _lib.load()
-    block._bind(lib)
     n = _count(monkeypatch, lib)
     diff = None
     for attempt in range(4):
@@ -292,7 +291,6 @@ def test_driver_and_composition_are_bit_identical_with_the_part_on(monkeypatch):
 def test_blocks_part_on_matches_off(driver, monkeypatch):
     from gkgnet_amd import _lib, block
     lib = _lib.load()
-    block._bind(lib)
     n = _count(monkeypatch, lib)
     for attempt in range(4):
         on, n_on = _run_pair(monkeypatch, driver, True, n)

@@ -424,7 +424,6 @@ def test_entry_points_validate_the_descriptor_before_any_launch(frozen):
     before the first launch (every pointer is a live 4 KB buffer all the same)."""
     from gkgnet_amd import _lib, block
     lib = _lib.load()
-    block._bind(lib)
     ERR_NULL, ERR_SHAPE = -1, -2
     live = torch.zeros(1024, device="cuda")
     C = 64
