@@ -26,7 +26,7 @@ __device__ __forceinline__ int edge_idx(int64_t v, int M) { return (int)(v < 0 ?
 
 __device__ __forceinline__ float edge_act(float u, int act) {
   if (act == 1) return 0.5f * u * (1.0f + erff(u * 0.70710678118654752440f));
-  if (act == 2) return u > 0.f ? u : 0.f;
+  if (act == 2) return u <= 0.f ? 0.f : u;                                            // NaN stays NaN, like torch.relu
   return u;
 }
 __device__ __forceinline__ float edge_act_grad(float u, int act) {
@@ -171,7 +171,8 @@ extern "C" int gkg_edge_stats(const float* qs, const float* qc, const int64_t* n
 extern "C" int gkg_edge_fwd(const float* qs, const float* qc, const int64_t* nn_idx, const float* a, const float* c,
                             float* out, uint8_t* argmax, int B, int O, int N, int M, int k, int act, void* stream) {
   if (int rc = edge_check(qs, qc, nn_idx, B, O, N, M, k, "gkg_edge_fwd: bad pointer / size")) return rc;
-  if (!a || !c || !out || act < 0 || act > 2) return gkg_fail(GKG_ERR_NULL, "gkg_edge_fwd: a, c, out required; act in 0..2");
+  if (!a || !c || !out) return gkg_fail(GKG_ERR_NULL, "gkg_edge_fwd: a, c, out required");
+  if (act < 0 || act > 2) return gkg_fail(GKG_ERR_SHAPE, "gkg_edge_fwd: act in 0..2");
   hipLaunchKernelGGL(edge_fwd_kernel, dim3((N + 255) / 256, O, B), dim3(256), 0, (hipStream_t)stream, qs, qc, nn_idx, a, c, out,
                      argmax, O, N, M, k, act);
   hipError_t e = hipGetLastError();
@@ -183,6 +184,7 @@ extern "C" int gkg_edge_bwd_stats(const float* g, const float* qs, const float* 
                                   const float* invstd, double* sums, int B, int O, int N, int M, int k, int act, void* stream) {
   if (int rc = edge_check(qs, qc, nn_idx, B, O, N, M, k, "gkg_edge_bwd_stats: bad pointer / size")) return rc;
   if (!g || !argmax || !a || !c || !mean0 || !invstd || !sums) return gkg_fail(GKG_ERR_NULL, "gkg_edge_bwd_stats: null pointer");
+  if (act < 0 || act > 2) return gkg_fail(GKG_ERR_SHAPE, "gkg_edge_bwd_stats: act in 0..2");
   hipLaunchKernelGGL(edge_bwd_stats_kernel, dim3((N + 255) / 256, O, B), dim3(256), 0, (hipStream_t)stream, g, qs, qc, nn_idx, argmax,
                      a, c, mean0, invstd, sums, O, N, M, k, act);
   hipError_t e = hipGetLastError();
@@ -195,6 +197,7 @@ extern "C" int gkg_edge_bwd(const float* g, const float* qs, const float* qc, co
                             const float* mgz, float* dqs, float* dqc, int B, int O, int N, int M, int k, int act, void* stream) {
   if (int rc = edge_check(qs, qc, nn_idx, B, O, N, M, k, "gkg_edge_bwd: bad pointer / size")) return rc;
   if (!g || !argmax || !a || !c || !dqs || (qc && !dqc)) return gkg_fail(GKG_ERR_NULL, "gkg_edge_bwd: null pointer");
+  if (act < 0 || act > 2) return gkg_fail(GKG_ERR_SHAPE, "gkg_edge_bwd: act in 0..2");
   const bool dense = mg != nullptr;
   if (dense && (!mgz || !mean0 || !invstd)) return gkg_fail(GKG_ERR_NULL, "gkg_edge_bwd: batch-statistics backward needs mean0, invstd, mg, mgz");
   dim3 grid((N + 255) / 256, O, B);

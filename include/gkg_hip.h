@@ -130,7 +130,8 @@ int gkg_mr_bwd(const void* g, const int64_t* nn_idx, const uint8_t* argmax, void
  * tensor.  With the hard-coded groups = 4 the output channels of groups 2 and 3 depend on (x_j - x_i) only, and the
  * convolution is linear, so for them z[b][o][n][k] = Q[b][o][nn_idx[b][n][k]] - Qc[b][o][n] + bias[o] with the per-node
  * projections Q = W src, Qc = W x (ordinary GEMMs in the caller: k times less work, no (B, 2C, N, k) tensor).  These four
- * entry points are the gather side; channel-major fp32 (B, O, N) / (B, O, M), nn_idx (B, N, k), k <= 255.
+ * entry points are the gather side; channel-major fp32 (B, O, N) / (B, O, M), nn_idx (B, N, k) int64, k <= 255.  Out-of-range
+ * nn_idx entries are clamped into [0, M) (all four: never an out-of-bounds read or atomic).
  *   gkg_edge_stats      sums[o] += sum (Q[j] - Qc), sums[O + o] += sum (Q[j] - Qc)^2 over all (b, n, k): the batch statistics
  *                       of train-mode BN (the bias shifts the mean only).  sums: 2*O doubles, zero on entry.
  *   gkg_edge_fwd        out = max_k act(a[o] (Q[j] - Qc) + c[o]); argmax (optional) = first maximising k.  The caller folds
