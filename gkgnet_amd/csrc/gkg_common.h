@@ -78,21 +78,27 @@ struct BnDerive {
   float* a_out; float* c_out; float* mean_out; float* invstd_out;
   int R; float momentum, eps;
   double* zero_buf; size_t zero_doubles;
+  // cross-rank statistics (the _sync entry points): `sums` were added up over the ranks and *count, a device scalar that went
+  // through the same exchange, is the number of rows over all of them — it takes R's place.  count_out (optional): the count as
+  // fp32 for the backward, stored by the thread that derives channel 0's saved statistics.  Null: rank-local statistics, R.
+  const double* count = nullptr; float* count_out = nullptr;
 };
 
 __device__ __forceinline__ void bn_derive_channel(const BnDerive& d, size_t o, double S, double Q, bool side, float& av, float& cv) {
-  const double m = S / d.R;
-  double var = Q / d.R - m * m;
+  const double n = d.count ? *d.count : (double)d.R;           // rows behind S and Q (the local form: R converted, as S / R did)
+  const double m = S / n;
+  double var = Q / n - m * m;
   if (var < 0.0) var = 0.0;
   const float is = (float)(1.0 / sqrt(var + (double)d.eps));
   av = d.gamma[o] * is;
   cv = d.beta[o] - av * (float)m;
   if (side) {
     d.a_out[o] = av; d.c_out[o] = cv; d.mean_out[o] = (float)m; d.invstd_out[o] = is;
+    if (o == 0 && d.count_out) *d.count_out = (float)n;
     if (d.running_mean) {
       const float bv = d.bias ? d.bias[o] : 0.f;
       d.running_mean[o] = (1.f - d.momentum) * d.running_mean[o] + d.momentum * ((float)m + bv);
-      const double unb = d.R > 1 ? var * (double)d.R / (double)(d.R - 1) : var;
+      const double unb = n > 1.0 ? var * n / (n - 1.0) : var;
       d.running_var[o] = (1.f - d.momentum) * d.running_var[o] + d.momentum * (float)unb;
     }
   }

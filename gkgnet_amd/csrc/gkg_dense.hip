@@ -539,9 +539,13 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_d_kernel(const float* dout, 
                                                              size_t total4, int C, int R, int ldg, size_t g_bstride,
                                                              float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                              double* __restrict__ zero_buf, size_t zero_doubles,
-                                                             const float* __restrict__ row_scale = nullptr, int rows_per_scale = 1) {
+                                                             const float* __restrict__ row_scale = nullptr, int rows_per_scale = 1,
+                                                             const double* __restrict__ gsums = nullptr,
+                                                             const float* __restrict__ count = nullptr) {
+  // gsums / count (gkg_bn_bwd_apply_sync): the sums added up over the ranks and the rows over all of them — dy is made of those,
+  // dgamma / dbeta of this rank's own `dsums`
   const int C4 = C >> 2;
-  const float invR = 1.0f / (float)R;
+  const float invR = 1.0f / (count ? count[0] : (float)R);
   const int q = blockIdx.y;
   y += (size_t)q * total4 * 4; dy += (size_t)q * total4 * 4; dout += (size_t)q * g_bstride;
   a += (size_t)q * C; cs += (size_t)q * C; mean += (size_t)q * C; invstd += (size_t)q * C; dsums += (size_t)q * 2 * C;
@@ -553,6 +557,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_d_kernel(const float* dout, 
     if (q == 0)
       for (size_t i = threadIdx.x; i < zero_doubles; i += 256) zero_buf[i] = 0.0;
   }
+  if (gsums) dsums = gsums + (size_t)q * 2 * C;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (size_t)gridDim.x * 256) {
     const size_t r = i / C4;
     const int cg = (int)(i - r * C4);
@@ -977,7 +982,8 @@ extern "C" int gkg_bn_bwd(const float* dout, const float* y, const float* a, con
 static int bn_bwd_atomic_impl(const float* dout, const float* y, const float* a, const float* c, const float* mean,
                               const float* invstd, float* dy, float* dgamma, float* dbeta, int R, int C, int nb, int ldg,
                               size_t dout_bstride, int act, double* sums, double* zero_buf, size_t zero_doubles, void* stream,
-                              bool stats_pass, const float* row_scale = nullptr, int rows_per_scale = 1);
+                              bool stats_pass, const float* row_scale = nullptr, int rows_per_scale = 1, bool apply_pass = true,
+                              const double* gsums = nullptr, const float* count = nullptr);
 
 extern "C" int gkg_bn_bwd_atomic(const float* dout, const float* y, const float* a, const float* c, const float* mean,
                                  const float* invstd, float* dy, float* dgamma, float* dbeta, int R, int C, int nb, int ldg,
@@ -1064,7 +1070,8 @@ extern "C" int gkg_bn_eval_bwd(const float* dout, const float* y, const float* a
 static int bn_bwd_atomic_impl(const float* dout, const float* y, const float* a, const float* c, const float* mean,
                               const float* invstd, float* dy, float* dgamma, float* dbeta, int R, int C, int nb, int ldg,
                               size_t dout_bstride, int act, double* sums, double* zero_buf, size_t zero_doubles, void* stream,
-                              bool stats_pass, const float* row_scale, int rows_per_scale) {
+                              bool stats_pass, const float* row_scale, int rows_per_scale, bool apply_pass, const double* gsums,
+                              const float* count) {
   // (A one-launch form with a grid barrier was built and measured in round 5 — a barrier of a few hundred workgroups costs
   // more than the kernel boundary it replaces, EXPERIMENTS.md — and removed in round 6.)
   int rpb;
@@ -1074,12 +1081,47 @@ static int bn_bwd_atomic_impl(const float* dout, const float* y, const float* a,
     if (act == 1) hipLaunchKernelGGL((bn_bwd_stats_kernel<1>), dim3(nblk, stats_tiles(C), nb), dim3(256), 0, st, dout, y, a, c, mean, invstd, (float*)nullptr, R, C, rpb, ldg, dout_bstride, (float*)nullptr, sums, row_scale, rows_per_scale);
     else hipLaunchKernelGGL((bn_bwd_stats_kernel<0>), dim3(nblk, stats_tiles(C), nb), dim3(256), 0, st, dout, y, a, c, mean, invstd, (float*)nullptr, R, C, rpb, ldg, dout_bstride, (float*)nullptr, sums, row_scale, rows_per_scale);
   }
-  const size_t total4 = (size_t)R * (C >> 2);
-  const int blocks = (int)((total4 + 255) / 256 > 2048 ? 2048 : (total4 + 255) / 256);
-  if (act == 1) hipLaunchKernelGGL((bn_bwd_apply_d_kernel<1>), dim3(blocks, nb), dim3(256), 0, st, dout, y, a, c, mean, invstd, sums, dy, total4, C, R, ldg, dout_bstride, dgamma, dbeta, zero_buf, zero_doubles, row_scale, rows_per_scale);
-  else hipLaunchKernelGGL((bn_bwd_apply_d_kernel<0>), dim3(blocks, nb), dim3(256), 0, st, dout, y, a, c, mean, invstd, sums, dy, total4, C, R, ldg, dout_bstride, dgamma, dbeta, zero_buf, zero_doubles, row_scale, rows_per_scale);
+  if (apply_pass) {
+    const size_t total4 = (size_t)R * (C >> 2);
+    const int blocks = (int)((total4 + 255) / 256 > 2048 ? 2048 : (total4 + 255) / 256);
+    if (act == 1) hipLaunchKernelGGL((bn_bwd_apply_d_kernel<1>), dim3(blocks, nb), dim3(256), 0, st, dout, y, a, c, mean, invstd, sums, dy, total4, C, R, ldg, dout_bstride, dgamma, dbeta, zero_buf, zero_doubles, row_scale, rows_per_scale, gsums, count);
+    else hipLaunchKernelGGL((bn_bwd_apply_d_kernel<0>), dim3(blocks, nb), dim3(256), 0, st, dout, y, a, c, mean, invstd, sums, dy, total4, C, R, ldg, dout_bstride, dgamma, dbeta, zero_buf, zero_doubles, row_scale, rows_per_scale, gsums, count);
+  }
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : gkg_fail_hip(e, "bn_bwd_atomic");
+}
+
+// gkg_bn_bwd_atomic split where the ranks of a SyncBatchNorm group exchange statistics.  gkg_bn_bwd_stats_f64 is its statistics
+// pass alone: sum dz, sum dz * yhat added to `sums` [nb][2][C] (fp64, ZERO on entry) with atomics, nothing else written.  The
+// caller keeps a copy (this rank's sums: its dgamma / dbeta, as in torch.nn.SyncBatchNorm and gkg_bn_bwd_sums), all-reduces
+// the buffer and calls gkg_bn_bwd_apply_sync.
+extern "C" int gkg_bn_bwd_stats_f64(const float* dout, const float* y, const float* a, const float* c, const float* mean,
+                                    const float* invstd, int R, int C, int nb, int ldg, size_t dout_bstride, int act, double* sums,
+                                    const float* row_scale, int rows_per_scale, void* stream) {
+  if (!dout || !y || !a || !c || !mean || !invstd || !sums) return gkg_fail(GKG_ERR_NULL, "gkg_bn_bwd_stats_f64: null pointer");
+  if (R <= 0 || bad_c(C) || nb <= 0 || nb > 64 || ldg < C || (ldg & 3) || (dout_bstride & 3) || (act != 0 && act != 1) ||
+      (row_scale && rows_per_scale <= 0))
+    return gkg_fail(GKG_ERR_SHAPE, "gkg_bn_bwd_stats_f64: bad sizes");
+  return bn_bwd_atomic_impl(dout, y, a, c, mean, invstd, nullptr, nullptr, nullptr, R, C, nb, ldg, dout_bstride, act, sums, nullptr, 0,
+                            stream, true, row_scale, row_scale ? rows_per_scale : 1, false);
+}
+
+// The apply pass behind it: dy from `sums_global` (the all-reduced sums) and `count` (device scalar: rows over all ranks, what
+// gkg_bn_apply_train_sync left in count_out), dgamma / dbeta from `sums_local`; clears `zero_buf` (the alternating-pair
+// protocol of gkg_bn_bwd_atomic).
+extern "C" int gkg_bn_bwd_apply_sync(const float* dout, const float* y, const float* a, const float* c, const float* mean,
+                                     const float* invstd, float* dy, float* dgamma, float* dbeta, int R, int C, int nb, int ldg,
+                                     size_t dout_bstride, int act, const double* sums_local, const double* sums_global,
+                                     const float* count, double* zero_buf, size_t zero_doubles, const float* row_scale,
+                                     int rows_per_scale, void* stream) {
+  if (!dout || !y || !a || !c || !mean || !invstd || !dy || !dgamma || !dbeta || !sums_local || !sums_global || !count)
+    return gkg_fail(GKG_ERR_NULL, "gkg_bn_bwd_apply_sync: null pointer");
+  if (R <= 0 || bad_c(C) || nb <= 0 || nb > 64 || ldg < C || (ldg & 3) || (dout_bstride & 3) || (act != 0 && act != 1) ||
+      (zero_doubles && !zero_buf) || (row_scale && rows_per_scale <= 0) || (((size_t)sums_local | (size_t)sums_global) & 15))
+    return gkg_fail(GKG_ERR_SHAPE, "gkg_bn_bwd_apply_sync: bad sizes");
+  return bn_bwd_atomic_impl(dout, y, a, c, mean, invstd, dy, dgamma, dbeta, R, C, nb, ldg, dout_bstride, act,
+                            const_cast<double*>(sums_local), zero_buf, zero_doubles, stream, false, row_scale,
+                            row_scale ? rows_per_scale : 1, true, sums_global, count);
 }
 
 // Train-mode BN-apply straight from the projection's fp64 column sums (gkg_linear_bn_fwd / _x6 with train == 2): replaces
@@ -1089,18 +1131,19 @@ static int bn_bwd_atomic_impl(const float* dout, const float* y, const float* a,
 //   nchw_B == 0: out (nb, R, ...) token-major like gkg_affine_act (fp32 out; act, res, row_scale as there)
 //   nchw_B  > 0: out / res are (nchw_B, C, R / nchw_B) channel-major like gkg_tm_affine_to_nchw (nb == 1, act == 0,
 //                row_scale = one factor per image)
-extern "C" int gkg_bn_apply_train(const float* y, const double* sums, const float* gamma, const float* beta, const float* bias,
-                                  float* running_mean, float* running_var, long long* num_batches_tracked, float* a, float* c,
-                                  float* mean, float* invstd, const float* res, float* out, int R, int C, int nb, int ldo,
-                                  size_t out_bstride, int ochunk, int act, int nchw_B, const float* row_scale, int rows_per_scale,
-                                  float momentum, float eps, double* zero_buf, size_t zero_doubles, void* stream) {
+static int bn_apply_train_impl(const float* y, const double* sums, const float* gamma, const float* beta, const float* bias,
+                               float* running_mean, float* running_var, long long* num_batches_tracked, float* a, float* c,
+                               float* mean, float* invstd, const float* res, float* out, int R, int C, int nb, int ldo,
+                               size_t out_bstride, int ochunk, int act, int nchw_B, const float* row_scale, int rows_per_scale,
+                               float momentum, float eps, double* zero_buf, size_t zero_doubles, void* stream,
+                               const double* count, float* count_out) {
   if (!y || !sums || !gamma || !beta || !a || !c || !mean || !invstd || !out)
     return gkg_fail(GKG_ERR_NULL, "gkg_bn_apply_train: null pointer");
   if ((running_mean == nullptr) != (running_var == nullptr)) return gkg_fail(GKG_ERR_NULL, "gkg_bn_apply_train: running stats come in pairs");
   if (R <= 0 || bad_c(C) || nb <= 0 || nb > 64 || (act != 0 && act != 1) || (zero_doubles && !zero_buf) || nchw_B < 0)
     return gkg_fail(GKG_ERR_SHAPE, "gkg_bn_apply_train: bad sizes");
   BnDerive d{sums, gamma, beta, bias, running_mean, running_var, num_batches_tracked, a, c, mean, invstd, R, momentum, eps,
-             zero_buf, zero_doubles};
+             zero_buf, zero_doubles, count, count_out};
   hipStream_t st = (hipStream_t)stream;
   if (nchw_B > 0) {
     if (nb != 1 || act != 0 || R % nchw_B) return gkg_fail(GKG_ERR_SHAPE, "gkg_bn_apply_train: channel-major output needs nb == 1, act == 0, R % B == 0");
@@ -1124,24 +1167,72 @@ extern "C" int gkg_bn_apply_train(const float* y, const double* sums, const floa
   return e == hipSuccess ? 0 : gkg_fail_hip(e, "bn_apply_train");
 }
 
+extern "C" int gkg_bn_apply_train(const float* y, const double* sums, const float* gamma, const float* beta, const float* bias,
+                                  float* running_mean, float* running_var, long long* num_batches_tracked, float* a, float* c,
+                                  float* mean, float* invstd, const float* res, float* out, int R, int C, int nb, int ldo,
+                                  size_t out_bstride, int ochunk, int act, int nchw_B, const float* row_scale, int rows_per_scale,
+                                  float momentum, float eps, double* zero_buf, size_t zero_doubles, void* stream) {
+  return bn_apply_train_impl(y, sums, gamma, beta, bias, running_mean, running_var, num_batches_tracked, a, c, mean, invstd, res, out,
+                             R, C, nb, ldo, out_bstride, ochunk, act, nchw_B, row_scale, rows_per_scale, momentum, eps, zero_buf,
+                             zero_doubles, stream, nullptr, nullptr);
+}
+
+// gkg_bn_apply_train behind a cross-rank exchange (SyncBatchNorm): `sums` are the column sums added up over the ranks and
+// `count` — a device scalar, normally the double behind them in the all-reduced buffer — the rows over all ranks: mean, biased
+// variance and the unbiased factor of running_var use it where the local form uses R (this rank's rows: the extent of y / out
+// only).  count_out (may be NULL): the count as fp32, stored by the first workgroup for gkg_bn_bwd_apply_sync — the scratch
+// buffer `count` lives in is cleared by a later pass.  Every output form of gkg_bn_apply_train.
+extern "C" int gkg_bn_apply_train_sync(const float* y, const double* sums, const float* gamma, const float* beta, const float* bias,
+                                       float* running_mean, float* running_var, long long* num_batches_tracked, float* a, float* c,
+                                       float* mean, float* invstd, const float* res, float* out, int R, int C, int nb, int ldo,
+                                       size_t out_bstride, int ochunk, int act, int nchw_B, const float* row_scale,
+                                       int rows_per_scale, float momentum, float eps, double* zero_buf, size_t zero_doubles,
+                                       const double* count, float* count_out, void* stream) {
+  if (!count) return gkg_fail(GKG_ERR_NULL, "gkg_bn_apply_train_sync: null count");
+  return bn_apply_train_impl(y, sums, gamma, beta, bias, running_mean, running_var, num_batches_tracked, a, c, mean, invstd, res, out,
+                             R, C, nb, ldo, out_bstride, ochunk, act, nchw_B, row_scale, rows_per_scale, momentum, eps, zero_buf,
+                             zero_doubles, stream, count, count_out);
+}
+
 // gkg_bn_apply_train's channel-major form with the residual given token-major and the result written in both layouts
 // (gkg_tm_affine_to_nchw_dual with the coefficients derived from the projection's column sums).
-extern "C" int gkg_bn_apply_train_dual(const float* y, const double* sums, const float* gamma, const float* beta, const float* bias,
-                                       float* running_mean, float* running_var, long long* num_batches_tracked, float* a,
-                                       float* c, float* mean, float* invstd, const float* res_tm, float* out, float* out_tm,
-                                       int B, int C, int N, float momentum, float eps, double* zero_buf, size_t zero_doubles,
-                                       void* stream) {
+static int bn_apply_train_dual_impl(const float* y, const double* sums, const float* gamma, const float* beta, const float* bias,
+                                    float* running_mean, float* running_var, long long* num_batches_tracked, float* a,
+                                    float* c, float* mean, float* invstd, const float* res_tm, float* out, float* out_tm,
+                                    int B, int C, int N, float momentum, float eps, double* zero_buf, size_t zero_doubles,
+                                    void* stream, const double* count, float* count_out) {
   if (!y || !sums || !gamma || !beta || !a || !c || !mean || !invstd || !out || !res_tm || !out_tm)
     return gkg_fail(GKG_ERR_NULL, "gkg_bn_apply_train_dual: null pointer");
   if ((running_mean == nullptr) != (running_var == nullptr)) return gkg_fail(GKG_ERR_NULL, "gkg_bn_apply_train_dual: running stats come in pairs");
   if (B <= 0 || B > 65535 || N <= 0 || bad_c(C) || (zero_doubles && !zero_buf)) return gkg_fail(GKG_ERR_SHAPE, "gkg_bn_apply_train_dual: bad sizes");
   BnDerive d{sums, gamma, beta, bias, running_mean, running_var, num_batches_tracked, a, c, mean, invstd, B * N, momentum, eps,
-             zero_buf, zero_doubles};
+             zero_buf, zero_doubles, count, count_out};
   dim3 grid((N + 31) / 32, (C + 31) / 32, B);
   hipLaunchKernelGGL(tm_affine_to_nchw_kernel, grid, dim3(256), 0, (hipStream_t)stream, y, (const float*)nullptr, (const float*)nullptr,
                      (const float*)nullptr, out, C, N, (const float*)nullptr, d, res_tm, out_tm);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : gkg_fail_hip(e, "bn_apply_train (dual)");
+}
+
+extern "C" int gkg_bn_apply_train_dual(const float* y, const double* sums, const float* gamma, const float* beta, const float* bias,
+                                       float* running_mean, float* running_var, long long* num_batches_tracked, float* a,
+                                       float* c, float* mean, float* invstd, const float* res_tm, float* out, float* out_tm,
+                                       int B, int C, int N, float momentum, float eps, double* zero_buf, size_t zero_doubles,
+                                       void* stream) {
+  return bn_apply_train_dual_impl(y, sums, gamma, beta, bias, running_mean, running_var, num_batches_tracked, a, c, mean, invstd,
+                                  res_tm, out, out_tm, B, C, N, momentum, eps, zero_buf, zero_doubles, stream, nullptr, nullptr);
+}
+
+// gkg_bn_apply_train_dual with gkg_bn_apply_train_sync's `count` / `count_out` (B: this rank's images).
+extern "C" int gkg_bn_apply_train_dual_sync(const float* y, const double* sums, const float* gamma, const float* beta,
+                                            const float* bias, float* running_mean, float* running_var,
+                                            long long* num_batches_tracked, float* a, float* c, float* mean, float* invstd,
+                                            const float* res_tm, float* out, float* out_tm, int B, int C, int N, float momentum,
+                                            float eps, double* zero_buf, size_t zero_doubles, const double* count, float* count_out,
+                                            void* stream) {
+  if (!count) return gkg_fail(GKG_ERR_NULL, "gkg_bn_apply_train_dual_sync: null count");
+  return bn_apply_train_dual_impl(y, sums, gamma, beta, bias, running_mean, running_var, num_batches_tracked, a, c, mean, invstd,
+                                  res_tm, out, out_tm, B, C, N, momentum, eps, zero_buf, zero_doubles, stream, count, count_out);
 }
 
 // ------------------------------------------------------------------------------------------ cross-rank (SyncBN) halves

@@ -869,13 +869,13 @@ extern "C" int gkg_knn_mr_fwd_tm(const float* x, int ldx, int xchunk, const floa
 //   k-NN call (gkg_knn_fwd_tm / _tm16 / gkg_knn_mr_fwd_tm) with the SAME (B, G, c, N, M, k, dilation, y / relative_pos presence,
 //   flags) that follows with GKG_KNN_X_PREPARED set and x = `out`: it then launches no preparation for the queries (none at all
 //   for a self graph).  fused_mr != 0: that call is gkg_knn_mr_fwd_tm.  Same arithmetic, same bits as apply + token_prep.
-extern "C" int gkg_bn_apply_knn_prep(const float* y, const double* sums, const float* gamma, const float* beta, const float* bias,
-                                     float* running_mean, float* running_var, long long* num_batches_tracked, float* a, float* c_out,
-                                     float* mean, float* invstd, float* out, int ldo, int ochunk, int B, int G, int c, int N, int M,
-                                     int k, int dilation, int has_y, int has_relpos, unsigned knn_flags, int fused_mr,
-                                     int as_keys, const float* res_tm, float* out_nchw,
-                                     void* knn_workspace, size_t knn_workspace_bytes, float momentum, float eps, double* zero_buf,
-                                     size_t zero_doubles, void* stream) {
+static int bn_apply_knn_prep_impl(const float* y, const double* sums, const float* gamma, const float* beta, const float* bias,
+                                  float* running_mean, float* running_var, long long* num_batches_tracked, float* a, float* c_out,
+                                  float* mean, float* invstd, float* out, int ldo, int ochunk, int B, int G, int c, int N, int M,
+                                  int k, int dilation, int has_y, int has_relpos, unsigned knn_flags, int fused_mr,
+                                  int as_keys, const float* res_tm, float* out_nchw,
+                                  void* knn_workspace, size_t knn_workspace_bytes, float momentum, float eps, double* zero_buf,
+                                  size_t zero_doubles, void* stream, const double* count, float* count_out) {
   if (!y || !sums || !gamma || !beta || !a || !c_out || !mean || !invstd || !out || !knn_workspace)
     return gkg_fail(GKG_ERR_NULL, "gkg_bn_apply_knn_prep: null pointer");
   if (!as_keys && (res_tm || out_nchw)) return gkg_fail(GKG_ERR_SHAPE, "gkg_bn_apply_knn_prep: res_tm / out_nchw belong to a keys producer");
@@ -889,13 +889,42 @@ extern "C" int gkg_bn_apply_knn_prep(const float* y, const double* sums, const f
     return gkg_fail(GKG_ERR_SHAPE, "gkg_bn_apply_knn_prep: bad output view");
   KnnProducer prod{};
   prod.aff.d = BnDerive{sums, gamma, beta, bias, running_mean, running_var, num_batches_tracked, a, c_out, mean, invstd,
-                        B * (as_keys ? M : N), momentum, eps, zero_buf, zero_doubles};
+                        B * (as_keys ? M : N), momentum, eps, zero_buf, zero_doubles, count, count_out};
   prod.raw = out; prod.raw_ld = ldo; prod.raw_chunk = ochunk;
   prod.as_keys = as_keys ? 1 : 0; prod.res_tm = res_tm; prod.nchw = out_nchw;
   static const float dummy = 0.f;
   static KnnMrFuse mr_dummy{nullptr, nullptr, nullptr};
   return knn_fwd_impl(y, has_y ? &dummy : nullptr, has_relpos ? &dummy : nullptr, nullptr, nullptr, B * G, c, N, M, k, dilation, GKG_F32,
                       knn_flags, knn_workspace, knn_workspace_bytes, stream, G, fused_mr ? &mr_dummy : nullptr, false, nullptr, 0, 0, &prod);
+}
+
+extern "C" int gkg_bn_apply_knn_prep(const float* y, const double* sums, const float* gamma, const float* beta, const float* bias,
+                                     float* running_mean, float* running_var, long long* num_batches_tracked, float* a, float* c_out,
+                                     float* mean, float* invstd, float* out, int ldo, int ochunk, int B, int G, int c, int N, int M,
+                                     int k, int dilation, int has_y, int has_relpos, unsigned knn_flags, int fused_mr,
+                                     int as_keys, const float* res_tm, float* out_nchw,
+                                     void* knn_workspace, size_t knn_workspace_bytes, float momentum, float eps, double* zero_buf,
+                                     size_t zero_doubles, void* stream) {
+  return bn_apply_knn_prep_impl(y, sums, gamma, beta, bias, running_mean, running_var, num_batches_tracked, a, c_out, mean, invstd, out,
+                                ldo, ochunk, B, G, c, N, M, k, dilation, has_y, has_relpos, knn_flags, fused_mr, as_keys, res_tm,
+                                out_nchw, knn_workspace, knn_workspace_bytes, momentum, eps, zero_buf, zero_doubles, stream, nullptr,
+                                nullptr);
+}
+
+// gkg_bn_apply_knn_prep behind a cross-rank exchange of the statistics: `sums` added up over the ranks, `count` / `count_out` as
+// in gkg_bn_apply_train_sync (B: this rank's images).
+extern "C" int gkg_bn_apply_knn_prep_sync(const float* y, const double* sums, const float* gamma, const float* beta, const float* bias,
+                                          float* running_mean, float* running_var, long long* num_batches_tracked, float* a,
+                                          float* c_out, float* mean, float* invstd, float* out, int ldo, int ochunk, int B, int G,
+                                          int c, int N, int M, int k, int dilation, int has_y, int has_relpos, unsigned knn_flags,
+                                          int fused_mr, int as_keys, const float* res_tm, float* out_nchw, void* knn_workspace,
+                                          size_t knn_workspace_bytes, float momentum, float eps, double* zero_buf,
+                                          size_t zero_doubles, const double* count, float* count_out, void* stream) {
+  if (!count) return gkg_fail(GKG_ERR_NULL, "gkg_bn_apply_knn_prep_sync: null count");
+  return bn_apply_knn_prep_impl(y, sums, gamma, beta, bias, running_mean, running_var, num_batches_tracked, a, c_out, mean, invstd, out,
+                                ldo, ochunk, B, G, c, N, M, k, dilation, has_y, has_relpos, knn_flags, fused_mr, as_keys, res_tm,
+                                out_nchw, knn_workspace, knn_workspace_bytes, momentum, eps, zero_buf, zero_doubles, stream, count,
+                                count_out);
 }
 
 // The same pass behind an eval-mode (frozen) BatchNorm: the caller passes the folded scale / shift (gkg_bn_eval_affine) instead of

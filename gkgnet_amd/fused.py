@@ -45,7 +45,7 @@ def _env_list(name):
 #                   accumulation (csrc/gkg_gemm_x6.hip: error vs fp64 3-4x below an fp32 fma chain) for every forward, input-
 #                   gradient and weight-gradient GEMM of the blocks (split-K forms for the label branch's short matrices, the
 #                   weight gradients of a backward pass batched into one launch) — no vendor GEMM in the step;
-#   "vendor"        vendor GEMM library + stand-alone BN passes everywhere (what autocast and SyncBN callers get anyway).
+#   "vendor"        vendor GEMM library + stand-alone BN passes everywhere (what autocast callers get anyway).
 GEMM_MATH = os.environ.get("GKG_GEMM_MATH", "x6")
 if GEMM_MATH not in ("x6", "vendor"):
     raise ValueError(f"GKG_GEMM_MATH={GEMM_MATH!r}: expected x6 | vendor")
@@ -82,10 +82,11 @@ from .planes import (_WeightPlanes, _PLANES, _planes, refresh_weight_planes, par
 
 def _x6(x, weight, bn, nb=1, kind="fwd") -> bool:
     """This projection GEMM (kind "fwd": y = x W^T, "dgrad": dx = dy W) runs on the x6 kernels.  Eligible: fp32 operands
-    outside autocast, batch statistics local to the rank, 16-byte aligned rows, the C entry points' size limits (_x6_rule)."""
+    outside autocast, batch statistics local to the rank or exchanged in fp64 (_sync_x6_ok), 16-byte aligned rows, the C entry
+    points' size limits (_x6_rule)."""
     if GEMM_MATH != "x6":
         return False
-    if not (x.dtype == _F32 and weight.dtype == _F32 and not torch.is_autocast_enabled() and _sync_group(bn) is None
+    if not (x.dtype == _F32 and weight.dtype == _F32 and not torch.is_autocast_enabled() and _sync_x6_ok(_sync_group(bn))
             and x.shape[-1] % 4 == 0 and weight.shape[0] % 4 == 0):
         return False
     return _x6_rule(x.shape[-2], x.shape[-1], weight.shape[0] // nb, nb, kind)
@@ -466,6 +467,13 @@ def _sync_group(bn):
     return group if dist.get_world_size(group) > 1 else None
 
 
+def _sync_x6_ok(group) -> bool:
+    """Whether a layer with this statistics group (None: rank-local) may take the x6 projection kernels and the two-launch fp64
+    BN passes.  Across ranks the fp64 column sums themselves are all-reduced (gkg_bn_apply_train_sync / gkg_bn_bwd_apply_sync);
+    GKG_DETERMINISTIC keeps such a layer on the two-stage fp32 exchange (the fp64 atomics are run-dependent in their last bits)."""
+    return group is None or (GEMM_MATH == "x6" and not DETERMINISTIC)
+
+
 def _touch_stats(bn, track):
     """The kernels about to run update bn's running statistics through raw pointers: invalidate what was derived from them."""
     if track and hasattr(bn, "_gkg_epoch"):
@@ -536,10 +544,15 @@ from .bn_scratch import _BnLink, _BnScratch      # noqa: E402  (fp64 column-sum 
 def _train_apply_from_sums(lib, x, W, bias, bn, R, cin, cout, nb, planes, res, out, ldo, obs, act, nchw_B, scale, rows_per_scale,
                            launch=None, out_tm=None, xld=None, xbs=None, ochunk=0, knn_prep=None):
     """Projection (statistics in its epilogue) -> BN-apply straight from the fp64 sums: two launches, no finalize kernel.
-    Returns (Y, a, c, mean, invstd).  ``launch(Y, sums) -> rc``: a caller-supplied producer of Y and its column sums (the
-    fused aggregation + projection kernel) instead of the plain projection of ``x``."""
+    Returns (Y, a, c, mean, invstd, sync).  ``launch(Y, sums) -> rc``: a caller-supplied producer of Y and its column sums (the
+    fused aggregation + projection kernel) instead of the plain projection of ``x``.
+    A SyncBatchNorm in a multi-rank group: the same two launches with ONE fp64 all-reduce between them — the sums and, in the
+    double behind them, the row count — and the _sync form of the apply pass, which divides by the exchanged count;
+    ``sync`` = (group, count as an fp32 device scalar) for the backward, else None."""
     dev = x.device
-    with _BnScratch.of(dev).scoped(lib, 2 * nb * cout) as (cur, other, zero):
+    group = _sync_group(bn)
+    n = 2 * nb * cout
+    with _BnScratch.of(dev).scoped(lib, n + (group is not None)) as (cur, other, zero):
         Y = torch.empty((nb, R, cout) if nb > 1 else (R, cout), dtype=_F32, device=dev)
         none10 = [None] * 10
         if launch is not None:
@@ -553,11 +566,17 @@ def _train_apply_from_sums(lib, x, W, bias, bn, R, cin, cout, nb, planes, res, o
         a, c, mean, invstd = torch.empty((4, nb * cout), dtype=_F32, device=dev).unbind(0)     # one allocation
         track = bn.training and bn.track_running_stats
         _touch_stats(bn, track)
+        sfx, tail, sync = "", (_stream(),), None
+        if group is not None:
+            cur[n:n + 1].fill_(float(R))
+            dist.all_reduce(cur[:n + 1], group=group)
+            count = torch.empty(1, dtype=_F32, device=dev)
+            sfx, tail, sync = "_sync", (cur.data_ptr() + 8 * n, _ptr(count), _stream()), (group, count)
         if knn_prep is not None:         # the apply pass is also the k-NN's token preparation (gkg_bn_apply_knn_prep): knn_prep = _KnnKey
             kp = knn_prep
             if kp.ws is None:            # (a label block's fc1 prepares its queries into the workspace the keys already live in)
                 kp.ws = _ws(lib.gkg_knn_workspace_bytes(kp.B * kp.G, kp.c, kp.N, kp.M, kp.k, kp.d, _lib.F32, _lib.KNN_NORMALIZE), dev)
-            _lib.check(lib.gkg_bn_apply_knn_prep(_ptr(Y), _ptr(cur), _ptr(bn.weight), _ptr(bn.bias), _ptr(bias),
+            _lib.check(getattr(lib, "gkg_bn_apply_knn_prep" + sfx)(_ptr(Y), _ptr(cur), _ptr(bn.weight), _ptr(bn.bias), _ptr(bias),
                                                  _ptr(bn.running_mean) if track else None, _ptr(bn.running_var) if track else None,
                                                  _ptr(bn.num_batches_tracked) if track else None, _ptr(a), _ptr(c), _ptr(mean),
                                                  _ptr(invstd), _ptr(out_tm if kp.as_keys else out), 0 if kp.as_keys else ldo,
@@ -565,30 +584,31 @@ def _train_apply_from_sums(lib, x, W, bias, bn, R, cin, cout, nb, planes, res, o
                                                  kp.has_rp, kp.flags, kp.fused_mr, kp.as_keys,
                                                  _ptr(res) if kp.as_keys else None, _ptr(out) if kp.as_keys else None,
                                                  _ptr(kp.ws), kp.ws.numel(),
-                                                 float(bn.momentum), float(bn.eps), _ptr(other), zero, _stream()),
-                       "gkg_bn_apply_knn_prep")
+                                                 float(bn.momentum), float(bn.eps), _ptr(other), zero, *tail),
+                       "gkg_bn_apply_knn_prep" + sfx)
         elif out_tm is not None:         # channel-major AND token-major result, residual token-major (gkg_bn_apply_train_dual)
-            _lib.check(lib.gkg_bn_apply_train_dual(_ptr(Y), _ptr(cur), _ptr(bn.weight), _ptr(bn.bias), _ptr(bias),
+            _lib.check(getattr(lib, "gkg_bn_apply_train_dual" + sfx)(_ptr(Y), _ptr(cur), _ptr(bn.weight), _ptr(bn.bias), _ptr(bias),
                                                    _ptr(bn.running_mean) if track else None, _ptr(bn.running_var) if track else None,
                                                    _ptr(bn.num_batches_tracked) if track else None, _ptr(a), _ptr(c), _ptr(mean),
                                                    _ptr(invstd), _ptr(res), _ptr(out), _ptr(out_tm), nchw_B, cout, R // nchw_B,
-                                                   float(bn.momentum), float(bn.eps), _ptr(other), zero, _stream()),
-                       "gkg_bn_apply_train_dual")
+                                                   float(bn.momentum), float(bn.eps), _ptr(other), zero, *tail),
+                       "gkg_bn_apply_train_dual" + sfx)
         else:
-            _lib.check(lib.gkg_bn_apply_train(_ptr(Y), _ptr(cur), _ptr(bn.weight), _ptr(bn.bias), _ptr(bias),
+            _lib.check(getattr(lib, "gkg_bn_apply_train" + sfx)(_ptr(Y), _ptr(cur), _ptr(bn.weight), _ptr(bn.bias), _ptr(bias),
                                               _ptr(bn.running_mean) if track else None, _ptr(bn.running_var) if track else None,
                                               _ptr(bn.num_batches_tracked) if track else None, _ptr(a), _ptr(c), _ptr(mean), _ptr(invstd),
                                               _ptr(res), _ptr(out), R, cout, nb, ldo, obs, ochunk, act, nchw_B, _ptr(scale), rows_per_scale,
-                                              float(bn.momentum), float(bn.eps), _ptr(other), zero, _stream()),
-                       "gkg_bn_apply_train")
-    return Y, a, c, mean, invstd
+                                              float(bn.momentum), float(bn.eps), _ptr(other), zero, *tail),
+                       "gkg_bn_apply_train" + sfx)
+    return Y, a, c, mean, invstd, sync
 
 
 def _derive_ok(bn, nb, cout, code, want16) -> bool:
-    """Train-mode statistics local to the rank, fp32 output: the BN-apply pass derives its coefficients from the projection
-    kernel's sums (no finalize launch)."""
-    return ((bn.training or not bn.track_running_stats) and _sync_group(bn) is None
-            and code == _lib.F32 and not want16 and _BnScratch.fits(2 * nb * cout))
+    """Train-mode statistics (local to the rank, or exchanged as fp64 sums: _sync_x6_ok), fp32 output: the BN-apply pass
+    derives its coefficients from the projection kernel's sums (no finalize launch)."""
+    group = _sync_group(bn)
+    return ((bn.training or not bn.track_running_stats) and _sync_x6_ok(group)
+            and code == _lib.F32 and not want16 and _BnScratch.fits(2 * nb * cout + (group is not None)))
 
 
 # BN backward statistics in the epilogue of the NEXT projection's input-gradient GEMM (round 4, csrc/gkg_gemm_x6.hip X6_BNBWD).
@@ -717,14 +737,16 @@ def _dgrad_x6_with_link(lib, dY, pd, R, cin, cout, link, residual=None):
 def _bn_scale_in_kernel(sync, nb, C) -> bool:
     """Whether _bn_backward will take the two-launch fp64-atomic form, whose kernels can apply a per-image gradient scale
     (DropPath) themselves instead of a separate elementwise launch in front of them (22 launches, 0.6 ms of the cfg4 step)."""
-    return sync is None and not DETERMINISTIC and _BnScratch.fits(2 * nb * C)
+    return (sync is None or GEMM_MATH == "x6") and not DETERMINISTIC and _BnScratch.fits(2 * nb * C)
 
 
 def _bn_backward(lib, g, Y, a, c, mean, invstd, dY, dgamma, dbeta, R, C, nb, ldg, g_bstride, act, sync, link=None, row_scale=None,
                  rows_per_scale=0):
     """dY, dgamma, dbeta of out = act(BN_train(Y)) from the upstream gradient g; with ``sync`` the two column sums the
     input gradient needs are all-reduced over the ranks (dgamma/dbeta stay local, like torch's SyncBatchNorm: the
-    data-parallel gradient exchange averages them).  ``link``: this layer's _BnLink — when the consumer's dgrad epilogue has
+    data-parallel gradient exchange averages them) — as fp64, between the two launches of the atomic form
+    (gkg_bn_bwd_stats_f64 / gkg_bn_bwd_apply_sync), or as fp32 between the two-stage halves under GKG_DETERMINISTIC and
+    GKG_GEMM_MATH=vendor.  ``link``: this layer's _BnLink — when the consumer's dgrad epilogue has
     left the statistics of exactly this gradient tensor on it, only the apply pass runs."""
     if link is not None and link.holds_sums():
         scratch = _BnScratch.of(Y.device)
@@ -740,7 +762,19 @@ def _bn_backward(lib, g, Y, a, c, mean, invstd, dY, dgamma, dbeta, R, C, nb, ldg
         # two launches: statistics with fp64 atomics into one of two alternating scratch buffers, apply (which also clears
         # what the previous call left in the other buffer) — no partial rows, no second-stage reduction launch
         with _BnScratch.of(Y.device).scoped(lib, 2 * nb * C) as (cur, other, zero):
-            if row_scale is not None:
+            if sync is not None:
+                # the same two launches with the exchange in the middle: this rank's sums are kept (dgamma / dbeta), the fp64
+                # buffer itself is all-reduced, the apply pass divides by the exchanged row count
+                group, count = sync
+                rs, rps = (_ptr(row_scale), rows_per_scale) if row_scale is not None else (None, 0)
+                _lib.check(lib.gkg_bn_bwd_stats_f64(_ptr(g), _ptr(Y), _ptr(a), _ptr(c), _ptr(mean), _ptr(invstd), R, C, nb, ldg,
+                                                    g_bstride, act, _ptr(cur), rs, rps, _stream()), "gkg_bn_bwd_stats_f64")
+                local = cur[:2 * nb * C].clone()
+                dist.all_reduce(cur[:2 * nb * C], group=group)
+                _lib.check(lib.gkg_bn_bwd_apply_sync(_ptr(g), _ptr(Y), _ptr(a), _ptr(c), _ptr(mean), _ptr(invstd), _ptr(dY),
+                                                     _ptr(dgamma), _ptr(dbeta), R, C, nb, ldg, g_bstride, act, _ptr(local), _ptr(cur),
+                                                     _ptr(count), _ptr(other), zero, rs, rps, _stream()), "gkg_bn_bwd_apply_sync")
+            elif row_scale is not None:
                 _lib.check(lib.gkg_bn_bwd_atomic_scaled(_ptr(g), _ptr(Y), _ptr(a), _ptr(c), _ptr(mean), _ptr(invstd), _ptr(dY),
                                                         _ptr(dgamma), _ptr(dbeta), R, C, nb, ldg, g_bstride, act, _ptr(cur), _ptr(other),
                                                         zero, _ptr(row_scale), rows_per_scale, _stream()), "gkg_bn_bwd_atomic_scaled")
@@ -853,8 +887,10 @@ class _LinearBNAct(torch.autograd.Function):
             assert nchw is not None and scale is None and res is not None and res.shape == (R, cout) and res.dtype == _F32
             out_tm = torch.empty((R, cout), dtype=_F32, device=x.device)
         fused_apply = own and _derive_ok(bn, 1, cout, code, want16)
+        if own and not fused_apply and _sync_group(bn) is not None:
+            own = False                               # exchanged statistics reach the x6 forward through the derive form only
         if fused_apply:                               # projection (statistics epilogue) -> apply from the sums: 2 launches
-            Y, a, c, mean, invstd = _train_apply_from_sums(lib, x, W.contiguous(), bias, bn, R, cin, cout, 1, pf, res, out,
+            Y, a, c, mean, invstd, sync = _train_apply_from_sums(lib, x, W.contiguous(), bias, bn, R, cin, cout, 1, pf, res, out,
                                                            ldo, 0, act, 0 if nchw is None else nchw[0], scale, rows_per_scale,
                                                            out_tm=out_tm, ochunk=ochunk,
                                                            knn_prep=knn if (act == 0 and scale is None and
@@ -1043,8 +1079,10 @@ class _GroupedLinearBNAct(torch.autograd.Function):
         out = torch.empty((R, cout), dtype=dt, device=XM.device)
         sync = None
         fused_apply = own and _derive_ok(bn, nb, co, code, False)
+        if own and not fused_apply and _sync_group(bn) is not None:
+            own = False
         if fused_apply:
-            Y, a, c, mean, invstd = _train_apply_from_sums(lib, XM, None, bias, bn, R, ci, co, nb, pf, None, out,
+            Y, a, c, mean, invstd, sync = _train_apply_from_sums(lib, XM, None, bias, bn, R, ci, co, nb, pf, None, out,
                                                            cout, co, act, 0, None, 0, xld=nb * ci, xbs=ci)
         elif own:
             Y, a, c, mean, invstd = _linear_fwd_own(lib, XM, None, bias, bn, R, ci, co, nb, planes=pf, xld=nb * ci, xbs=ci)

@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define GKG_ABI_VERSION 12
+#define GKG_ABI_VERSION 13
 
 /* dtype codes */
 #define GKG_F32 0
@@ -245,6 +245,14 @@ int gkg_bn_apply_knn_prep(const float* y, const double* sums, const float* gamma
                           int dilation, int has_y, int has_relpos, unsigned knn_flags, int fused_mr, int as_keys, const float* res_tm,
                           float* out_nchw, void* knn_workspace, size_t knn_workspace_bytes, float momentum, float eps, double* zero_buf,
                           size_t zero_doubles, void* stream);
+/* gkg_bn_apply_knn_prep behind a cross-rank exchange of the statistics (SyncBatchNorm): `sums` added up over the ranks, `count` /
+ * `count_out` as in gkg_bn_apply_train_sync (B: this rank's images). */
+int gkg_bn_apply_knn_prep_sync(const float* y, const double* sums, const float* gamma, const float* beta, const float* bias,
+                               float* running_mean, float* running_var, long long* num_batches_tracked, float* a, float* c_out,
+                               float* mean, float* invstd, float* out, int ldo, int ochunk, int B, int G, int c, int N, int M, int k,
+                               int dilation, int has_y, int has_relpos, unsigned knn_flags, int fused_mr, int as_keys,
+                               const float* res_tm, float* out_nchw, void* knn_workspace, size_t knn_workspace_bytes, float momentum,
+                               float eps, double* zero_buf, size_t zero_doubles, const double* count, float* count_out, void* stream);
 /* The eval-mode (frozen BatchNorm) counterpart of gkg_bn_apply_knn_prep: the caller passes the folded scale / shift a, c
  * (C = G c each; gkg_bn_eval_affine) instead of column sums.  out = fmaf(a, y, c) (+ res_tm for a keys producer) — the bits of
  * gkg_affine_act (queries: out / ldo / ochunk as above) or gkg_tm_affine_to_nchw_dual (as_keys: out (B M, C) plain, out_nchw
@@ -461,6 +469,38 @@ int gkg_bn_bwd_sums(const float* dout, const float* y, const float* a, const flo
 int gkg_bn_bwd_apply(const float* dout, const float* y, const float* a, const float* c, const float* mean,
                      const float* invstd, const float* sums, const float* count, float* dy, int R, int C, int nb,
                      int ldg, size_t dout_bstride, int act, void* stream);
+/* The same exchange for the layers whose statistics come out of the projection kernel as fp64 column sums (gkg_bn_apply_train /
+ * gkg_bn_bwd_atomic): ONE fp64 all-reduce per direction, nothing rounded to fp32 before the derive.
+ * Forward: the projection (train == 2) accumulates into `sums` [nb][2][C]; the caller stores its row count in a double behind
+ * them and all-reduces the 2 nb C + 1 doubles; the _sync apply forms below are their local siblings with two more arguments:
+ *   count      device scalar (never NULL): rows over ALL ranks.  Mean, biased variance and the unbiased factor of running_var use
+ *              it where the sibling uses its host-side row count; R / B keep describing this rank's y and out.
+ *   count_out  may be NULL: the first workgroup stores (float)*count there for gkg_bn_bwd_apply_sync (the scratch buffer `count`
+ *              lives in is cleared by a later pass of the alternating-pair protocol).
+ * Backward: gkg_bn_bwd_stats_f64 is gkg_bn_bwd_atomic[_scaled]'s statistics pass alone (sum dz, sum dz * yhat added to the
+ * ZEROED `sums` with fp64 atomics; row_scale NULL: no scale; no apply pass, nothing else written); the caller keeps a copy of
+ * this rank's sums, all-reduces the buffer and calls gkg_bn_bwd_apply_sync: dy from `sums_global` and `count`, dgamma / dbeta
+ * from `sums_local` (like torch.nn.SyncBatchNorm and gkg_bn_bwd_sums: the data-parallel gradient exchange averages them), and
+ * `zero_buf` cleared as by gkg_bn_bwd_atomic.  Both sums pointers 16-byte aligned.  Validation as the siblings': GKG_ERR_* and
+ * nothing launched. */
+int gkg_bn_apply_train_sync(const float* y, const double* sums, const float* gamma, const float* beta, const float* bias,
+                            float* running_mean, float* running_var, long long* num_batches_tracked, float* a, float* c,
+                            float* mean, float* invstd, const float* res, float* out, int R, int C, int nb, int ldo,
+                            size_t out_bstride, int ochunk, int act, int nchw_B, const float* row_scale, int rows_per_scale,
+                            float momentum, float eps, double* zero_buf, size_t zero_doubles, const double* count,
+                            float* count_out, void* stream);
+int gkg_bn_apply_train_dual_sync(const float* y, const double* sums, const float* gamma, const float* beta, const float* bias,
+                                 float* running_mean, float* running_var, long long* num_batches_tracked, float* a, float* c,
+                                 float* mean, float* invstd, const float* res_tm, float* out, float* out_tm, int B, int C, int N,
+                                 float momentum, float eps, double* zero_buf, size_t zero_doubles, const double* count,
+                                 float* count_out, void* stream);
+int gkg_bn_bwd_stats_f64(const float* dout, const float* y, const float* a, const float* c, const float* mean,
+                         const float* invstd, int R, int C, int nb, int ldg, size_t dout_bstride, int act, double* sums,
+                         const float* row_scale, int rows_per_scale, void* stream);
+int gkg_bn_bwd_apply_sync(const float* dout, const float* y, const float* a, const float* c, const float* mean,
+                          const float* invstd, float* dy, float* dgamma, float* dbeta, int R, int C, int nb, int ldg,
+                          size_t dout_bstride, int act, const double* sums_local, const double* sums_global, const float* count,
+                          double* zero_buf, size_t zero_doubles, const float* row_scale, int rows_per_scale, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * The dense 1x1 projections (reference torch_vertex.py:290-306 fc1 / fc2 = Conv2d(1x1) + BN, torch_nn.py:57-69 BasicConv =
