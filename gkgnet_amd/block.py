@@ -17,7 +17,7 @@ the two arena layouts, which are data (``_ARENAS``: descriptor field -> size) re
 built.  The two autograd Functions keep what is their own (inputs, outputs, the Grapher's keys handshake and dual output, the label
 block's announcement to its producer); everything a call shares lives once, in ``_forward`` and ``_backward``, which treat the
 projections as a list in the plan's order (train: three autograd inputs each, frozen: four) — one ``_proj_fwd`` / ``_proj_bwd`` per
-projection, whatever the mode."""
+projection, whatever the mode.  The prepared-token handshake with the k-NN (problem, workspace, marks) is ``knn_prep.py``'s."""
 from __future__ import annotations
 
 import ctypes as C
@@ -26,7 +26,7 @@ from contextlib import nullcontext
 
 import torch
 
-from . import _abi, _lib, fused
+from . import _abi, _lib, fused, knn_prep
 from .ops import _ptr, _stream
 
 _F32 = torch.float32
@@ -376,19 +376,17 @@ def _graph_op(lib, plan, g: GraphOp, B, G, c, N, M, relative_pos, has_y, want_ed
     """The block's k-NN + aggregation: kernel form, flags, workspace (shared with a keys producer when the Grapher in front prepared
     this graph's keys).  -> (key object of this k-NN problem, edge tensor | None)."""
     k, d = plan.k, plan.d
-    flags0 = _lib.KNN_NORMALIZE | _lib.knn_select_flags() | _lib.relpos_flags(relative_pos)
+    flags0 = knn_prep.problem_flags(relative_pos)            # (once per call: the kernel choice below is cached per flag word)
     fm = plan.fm.get(flags0)
     if fm is None:
         fm = plan.fm[flags0] = bool(fused._knn_mr_shapes_ok(B, N, G * c, M, has_y, relative_pos, k, d, G, plan.nn_, False))
-    key = fused._KnnKey(B, G, c, N, M, k, d, has_y, relative_pos, fm, flags0)
+    key = knn_prep.KnnProblem(B, G, c, N, M, k, d, has_y, relative_pos, fm, flags0)
     flags = flags0
     if fused.KNN_PREP:
-        flags |= _lib.KNN_X_PREPARED
-        if keys_key is not None and keys_key.ws is not None and keys_key.tuple() == key.tuple():
-            key.ws, key.y_ready = keys_key.ws, True
+        flags |= _lib.KNN_X_PREPARED                         # no tuple to match: this call's own fc1 step is the queries' producer
+        if key.adopt_keys(keys_key):
             flags |= _lib.KNN_Y_PREPARED
-    if key.ws is None:
-        key.ws = fused._ws(lib.gkg_knn_workspace_bytes(B * G, c, N, M, k, d, _lib.F32, _lib.KNN_NORMALIZE), dev)
+    key.workspace(lib, dev)
     rp = None
     if relative_pos is not None:
         rp = plan.rp_view if relative_pos is plan.rp else None
@@ -482,18 +480,15 @@ class _GrapherBlockFn(torch.autograd.Function):
         out_tm = torch.empty((T, Cc), dtype=_F32, device=dev) if dual else None
         d.B, d.C, d.H, d.W = B, Cc, H, W
         d.x, d.out, d.out_tm = x.data_ptr(), out.data_ptr(), _ptr(out_tm)
-        kk = None
-        if label_knn is not None and dual and fused.KNN_PREP:     # the label block behind announced its graph: prepare its keys
-            G2, L2, k2, d2, fm2 = label_knn
-            if Cc % G2 == 0 and (Cc // G2) % 4 == 0:
-                kk = fused._KnnKey(B, G2, Cc // G2, L2, N, k2, d2, True, None, fm2)
-                kk.as_keys = 1
-                kk.ws = fused._ws(lib.gkg_knn_workspace_bytes(B * G2, Cc // G2, L2, N, k2, d2, _lib.F32, _lib.KNN_NORMALIZE), dev)
-                d.keys_G, d.keys_L, d.keys_k, d.keys_d, d.keys_fused_mr, d.keys_flags = G2, L2, k2, d2, int(fm2), kk.flags
-                d.keys_ws, d.keys_ws_bytes = kk.ws.data_ptr(), kk.ws.numel()
+        # the label block behind announced its graph: prepare its keys
+        kk = knn_prep.KnnProblem.keys_for_label(B, Cc, N, label_knn) if (dual and fused.KNN_PREP) else None
+        if kk is not None:
+            ws = kk.workspace(lib, dev)                           # up front: the producer runs inside the call below
+            d.keys_G, d.keys_L, d.keys_k, d.keys_d, d.keys_fused_mr, d.keys_flags = kk.G, kk.N, kk.k, kk.d, kk.fused_mr, kk.flags
+            d.keys_ws, d.keys_ws_bytes = ws.data_ptr(), ws.numel()
         buf, _, _ = _forward(lib, plan, d, dev, N, N, relative_pos, False, False, None, "gkg_grapher_fwd")
         if kk is not None:
-            out_tm._gkg_knn_keys = kk
+            kk.mark(out_tm)
         ctx.save_for_backward(buf, *params[::plan.stride])
         ctx.desc = d
         ctx.plan = plan
@@ -520,7 +515,7 @@ class _GrapherBlockFn(torch.autograd.Function):
 
 
 def _run_grapher(plan, mod, x, relative_pos, dual):
-    res = _GrapherBlockFn.apply(x, plan, relative_pos, mod.__dict__.get("_gkg_label_knn"), dual, *plan.params)
+    res = _GrapherBlockFn.apply(x, plan, relative_pos, knn_prep.announced(mod), dual, *plan.params)
     out = res[0] if dual else res
     if dual:
         out._gkg_tm = (out._version, res[1])
@@ -560,10 +555,8 @@ class _LabelBlockFn(torch.autograd.Function):
         d.B, d.C, d.L, d.M = B, Cc, L, M
         d.e, d.ft, d.out = e2.data_ptr(), ft.data_ptr(), out.data_ptr()
         buf, key, edge = _forward(lib, plan, d, dev, L, M, None, True, True, keys_key, "gkg_grapher_label_fwd")
-        if producer is not None and fused.KNN_PREP:
-            lk = (plan.groups, L, plan.k, plan.d, key.fused_mr)            # the Grapher in front prepares this graph's keys
-            if producer.__dict__.get("_gkg_label_knn") != lk:              # from its next call on (fused.grapher_label_forward)
-                producer._gkg_label_knn = lk
+        if fused.KNN_PREP:
+            key.announce(producer, plan.groups, L)       # the Grapher in front prepares this graph's keys from its next call on
         ctx.save_for_backward(buf, e2, ft, *params[::plan.stride])
         ctx.desc = d
         ctx.plan = plan

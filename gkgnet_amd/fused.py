@@ -15,7 +15,8 @@ torch_vertex.py:278-403), restructured for MI355X:
 
 Autograd sees four custom Functions (layout, linear+BN+act, grouped linear+BN+act, max-relative) with
 hand-written backward passes.  Used automatically by ``Grapher`` / ``GrapherLabel`` when supported
-(``fused_supported``); everything else takes the composable path.
+(``fused_supported``); everything else takes the composable path.  The handshake by which a BN-apply pass prepares the
+tokens of the k-NN call behind it (round 6) lives in ``knn_prep.py``; here are its policy switches and its two kinds of call.
 """
 from __future__ import annotations
 
@@ -542,7 +543,7 @@ from .bn_scratch import _BnLink, _BnScratch      # noqa: E402  (fp64 column-sum 
 
 
 def _train_apply_from_sums(lib, x, W, bias, bn, R, cin, cout, nb, planes, res, out, ldo, obs, act, nchw_B, scale, rows_per_scale,
-                           launch=None, out_tm=None, xld=None, xbs=None, ochunk=0, knn_prep=None):
+                           launch=None, out_tm=None, xld=None, xbs=None, ochunk=0, prep=None):
     """Projection (statistics in its epilogue) -> BN-apply straight from the fp64 sums: two launches, no finalize kernel.
     Returns (Y, a, c, mean, invstd, sync).  ``launch(Y, sums) -> rc``: a caller-supplied producer of Y and its column sums (the
     fused aggregation + projection kernel) instead of the plain projection of ``x``.
@@ -572,18 +573,12 @@ def _train_apply_from_sums(lib, x, W, bias, bn, R, cin, cout, nb, planes, res, o
             dist.all_reduce(cur[:n + 1], group=group)
             count = torch.empty(1, dtype=_F32, device=dev)
             sfx, tail, sync = "_sync", (cur.data_ptr() + 8 * n, _ptr(count), _stream()), (group, count)
-        if knn_prep is not None:         # the apply pass is also the k-NN's token preparation (gkg_bn_apply_knn_prep): knn_prep = _KnnKey
-            kp = knn_prep
-            if kp.ws is None:            # (a label block's fc1 prepares its queries into the workspace the keys already live in)
-                kp.ws = _ws(lib.gkg_knn_workspace_bytes(kp.B * kp.G, kp.c, kp.N, kp.M, kp.k, kp.d, _lib.F32, _lib.KNN_NORMALIZE), dev)
+        if prep is not None:             # the apply pass is also the k-NN's token preparation: prep = the KnnProblem, whose
+            # workspace is allocated now, by the call that is a producer (a label block's fc1 finds the one its keys already live in)
             _lib.check(getattr(lib, "gkg_bn_apply_knn_prep" + sfx)(_ptr(Y), _ptr(cur), _ptr(bn.weight), _ptr(bn.bias), _ptr(bias),
                                                  _ptr(bn.running_mean) if track else None, _ptr(bn.running_var) if track else None,
                                                  _ptr(bn.num_batches_tracked) if track else None, _ptr(a), _ptr(c), _ptr(mean),
-                                                 _ptr(invstd), _ptr(out_tm if kp.as_keys else out), 0 if kp.as_keys else ldo,
-                                                 0 if kp.as_keys else ochunk, kp.B, kp.G, kp.c, kp.N, kp.M, kp.k, kp.d, kp.has_y,
-                                                 kp.has_rp, kp.flags, kp.fused_mr, kp.as_keys,
-                                                 _ptr(res) if kp.as_keys else None, _ptr(out) if kp.as_keys else None,
-                                                 _ptr(kp.ws), kp.ws.numel(),
+                                                 _ptr(invstd), *prep.producer_args(lib, out, out_tm, res, ldo, ochunk),
                                                  float(bn.momentum), float(bn.eps), _ptr(other), zero, *tail),
                        "gkg_bn_apply_knn_prep" + sfx)
         elif out_tm is not None:         # channel-major AND token-major result, residual token-major (gkg_bn_apply_train_dual)
@@ -852,9 +847,10 @@ class _LinearBNAct(torch.autograd.Function):
         returned in both layouts, ``(out (B, C, H, W), out_tm (R, cout))`` — see DUAL_LAYOUT below.
         ``xm`` = (B, N) (fp32 token-major output, no residual): the result is written into the x half of a fresh XM operand
         buffer (R, 2 cout) and returned as its (B, N, 4, cout / 4) view (see _xm_xview) — a Grapher's fc1, whose output the
-        aggregation and the grouped projection read in place.  ``knn`` (a _KnnKey, with ``xm``): the k-NN problem whose queries
+        aggregation and the grouped projection read in place.  ``knn`` (a KnnProblem, with ``xm``): the k-NN problem whose queries
         this output is — the BN-apply pass then also leaves the queries' normalised copies in that call's workspace
-        (gkg_bn_apply_knn_prep) and the returned view carries the key (``_gkg_knn``): no token-preparation launch downstream."""
+        (gkg_bn_apply_knn_prep) and the returned view carries the problem (KnnProblem.mark): no token-preparation launch
+        downstream."""
         lib = _lib.load()
         R, cin = x.shape
         cout = weight.shape[0]
@@ -889,35 +885,26 @@ class _LinearBNAct(torch.autograd.Function):
         fused_apply = own and _derive_ok(bn, 1, cout, code, want16)
         if own and not fused_apply and _sync_group(bn) is not None:
             own = False                               # exchanged statistics reach the x6 forward through the derive form only
+        # this call's apply pass is also the producer of ``knn``'s prepared tokens (knn_prep.py): fc1's queries into the XM buffer, or
+        # a Grapher's last layer as the producer of the label graph's keys
+        prep = knn if (knn is not None and act == 0 and scale is None
+                       and ((xm is not None and not knn.as_keys) or (dual and knn.as_keys))) else None
         if fused_apply:                               # projection (statistics epilogue) -> apply from the sums: 2 launches
             Y, a, c, mean, invstd, sync = _train_apply_from_sums(lib, x, W.contiguous(), bias, bn, R, cin, cout, 1, pf, res, out,
                                                            ldo, 0, act, 0 if nchw is None else nchw[0], scale, rows_per_scale,
-                                                           out_tm=out_tm, ochunk=ochunk,
-                                                           knn_prep=knn if (act == 0 and scale is None and
-                                                                            ((xm is not None and not knn.as_keys) or (dual and knn.as_keys))
-                                                                            if knn is not None else False) else None)
+                                                           out_tm=out_tm, ochunk=ochunk, prep=prep)
         elif own:                                     # projection kernel with the BN statistics in its epilogue
             Y, a, c, mean, invstd = _linear_fwd_own(lib, x, W.contiguous(), bias, bn, R, cin, cout, 1, planes=pf)
         else:
             Y = _mm_t(x, W, w16)
             a, c, mean, invstd, sync = _bn_forward_params(lib, Y, bn, bias, R, cout, 1)
-        # a frozen (eval-mode) layer in the place where a train-mode one takes gkg_bn_apply_knn_prep: the folded affine is also the
-        # k-NN's token preparation (gkg_affine_knn_prep) — fc1's queries into the XM buffer, or a Grapher's last layer as the
-        # producer of the label graph's keys
-        eval_prep = (knn if (own and not fused_apply and mean is None and act == 0 and scale is None and code == _lib.F32
-                             and not want16 and ((xm is not None and not knn.as_keys) or (dual and knn.as_keys))) else None) \
-            if knn is not None else None
+        if not fused_apply and not (own and mean is None and code == _lib.F32 and not want16):
+            prep = None      # besides the train-mode pass only a frozen layer's affine behind the x6 projection, fp32 out, prepares
         if fused_apply:
             pass
-        elif eval_prep is not None:
-            kp = eval_prep
-            if kp.ws is None:
-                kp.ws = _ws(lib.gkg_knn_workspace_bytes(kp.B * kp.G, kp.c, kp.N, kp.M, kp.k, kp.d, _lib.F32, _lib.KNN_NORMALIZE), x.device)
-            _lib.check(lib.gkg_affine_knn_prep(_ptr(Y), _ptr(a), _ptr(c), _ptr(out_tm if kp.as_keys else out), 0 if kp.as_keys else ldo,
-                                               0 if kp.as_keys else ochunk, kp.B, kp.G, kp.c, kp.N, kp.M, kp.k, kp.d, kp.has_y,
-                                               kp.has_rp, kp.flags, kp.fused_mr, kp.as_keys, _ptr(res) if kp.as_keys else None,
-                                               _ptr(out) if kp.as_keys else None, _ptr(kp.ws), kp.ws.numel(), _stream()),
-                       "gkg_affine_knn_prep")
+        elif prep is not None:                        # the folded affine is also the k-NN's token preparation
+            _lib.check(lib.gkg_affine_knn_prep(_ptr(Y), _ptr(a), _ptr(c), *prep.producer_args(lib, out, out_tm, res, ldo, ochunk),
+                                               _stream()), "gkg_affine_knn_prep")
         elif nchw is None and want16 and code == _lib.F32:
             # bf16 inference, channels-last chain: also emit the bf16 rounding the next block's first GEMM reads
             out16 = torch.empty((R, cout), dtype=torch.bfloat16, device=x.device)
@@ -948,15 +935,15 @@ class _LinearBNAct(torch.autograd.Function):
             if act == 0 and out.dtype == _F32 and _bwd_fuse_ok(mean, sync, scale, 1, cout):
                 # the aggregation behind this layer takes its BN backward statistics in its scatter (_mr_bwd)
                 ctx.link = out._gkg_mr_bn_link = _BnLink(Y, a, c, mean, invstd, act, 1, cout, R)
-            if knn is not None and (fused_apply or eval_prep is not None) and getattr(knn, "ws", None) is not None:
-                out._gkg_knn = knn               # the queries' prepared copies are in knn.ws (see _knn_prepared)
+            if prep is not None:
+                prep.mark(out)                        # the queries' prepared copies are in prep.ws (knn_prep.consumer_ws_flags)
         if alias:
             ctx.set_materialize_grads(False)
             return out, x.view_as(x)
         if dual:
             ctx.set_materialize_grads(False)
-            if knn is not None and knn.as_keys and (fused_apply or eval_prep is not None) and knn.ws is not None:
-                out_tm._gkg_knn_keys = knn       # the label graph's keys are prepared in knn.ws (grapher_label_forward)
+            if prep is not None:
+                prep.mark(out_tm)                     # the label graph's keys are prepared in prep.ws (grapher_label_forward)
             return out, out_tm
         return out
 
@@ -1351,34 +1338,7 @@ def _as_tokens(x):
     return x if _is_xm_half(x) else x.contiguous()
 
 
-class _KnnKey:
-    """One k-NN problem as the C entry points see it: what gkg_bn_apply_knn_prep (the producer of the queries) and the k-NN call
-    must agree on for the prepared queries in ``ws`` to be THAT call's (same workspace plan, same kernel choice)."""
-    __slots__ = ("B", "G", "c", "N", "M", "k", "d", "has_y", "has_rp", "flags", "fused_mr", "ws", "as_keys", "y_ready")
-
-    def __init__(self, B, G, c, N, M, k, d, has_y, relative_pos, fused_mr, flags=None):
-        self.B, self.G, self.c, self.N, self.M, self.k, self.d = B, G, c, N, M, k, d
-        self.has_y, self.has_rp, self.fused_mr = int(bool(has_y)), int(relative_pos is not None), int(bool(fused_mr))
-        self.flags = (_lib.KNN_NORMALIZE | _lib.knn_select_flags() | _lib.relpos_flags(relative_pos)) if flags is None else flags
-        self.ws = None
-        self.as_keys = 0         # 1: this producer call prepares the problem's KEYS (a Grapher's fc2 in front of a GrapherLabel)
-        self.y_ready = False     # the keys' copies are already in ``ws`` (the k-NN call then sets GKG_KNN_Y_PREPARED)
-
-    def tuple(self):
-        return (self.B, self.G, self.c, self.N, self.M, self.k, self.d, self.has_y, self.has_rp, self.flags, self.fused_mr)
-
-    def same(self, B, G, c, N, M, k, d, has_y, has_rp, flags, fused_mr) -> bool:
-        return ((self.B, self.G, self.c, self.N, self.M, self.k, self.d, self.has_y, self.has_rp, self.flags, self.fused_mr)
-                == (B, G, c, N, M, k, d, int(bool(has_y)), int(bool(has_rp)), flags, int(bool(fused_mr))))
-
-
-def _knn_prepared(x, B, G, c, N, M, k, d, has_y, has_rp, flags, fused_mr):
-    """(workspace, flags) for a k-NN call on queries ``x``: the producer's workspace + GKG_KNN_X_PREPARED when x carries prepared
-    copies for exactly this problem (fc1's BN-apply left them: _LinearBNAct ``knn``), else a fresh workspace."""
-    key = getattr(x, "_gkg_knn", None)
-    if key is not None and key.ws is not None and key.same(B, G, c, N, M, k, d, has_y, has_rp, flags, fused_mr) and not (flags & _lib.KNN_BF16_CONTRACT):
-        return key.ws, flags | _lib.KNN_X_PREPARED | (_lib.KNN_Y_PREPARED if key.y_ready else 0)
-    return _ws(_lib.load().gkg_knn_workspace_bytes(B * G, c, N, M, k, d, _lib.F32, _lib.KNN_NORMALIZE), x.device), flags
+from . import knn_prep                          # noqa: E402  (the prepared-token handshake between a BN-apply pass and the k-NN)
 
 
 def _rp_arg(relative_pos, N, M):
@@ -1389,26 +1349,32 @@ def _rp_arg(relative_pos, N, M):
 
 
 @torch.no_grad()
-def knn_graph_tm(x, y, relative_pos, k, dilation, G):
-    """x (B,N,C) [or the x half of an XM buffer], y (B,M,C)|None token-major -> edge_index (2, B*G, N, k) int64."""
+def _knn_graph(x, y, relative_pos, k, dilation, G, compact):
+    """knn_graph_tm / knn_graph_tm16: the same problem, flags and workspace; ``compact`` chooses the output and the entry point."""
     lib = _lib.load()
     B, N, C, ldx, xchunk = _tm_view(x)
     x = _as_tokens(x)
     c = C // G
     M = N if y is None else y.shape[1]
-    flags = _lib.KNN_NORMALIZE | _lib.knn_select_flags()
-    if KNN_BF16 and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16:
-        flags |= _lib.KNN_BF16_CONTRACT          # the reference's own x.y^T runs in bf16 here (and rounds the result to bf16)
-    rp = None
-    if relative_pos is not None:
-        rp = _rp_arg(relative_pos, N, M)
-        flags |= _lib.relpos_flags(relative_pos)
-    edge = torch.empty((2, B * G, N, k), dtype=torch.int64, device=x.device)
-    ws, flags = _knn_prepared(x, B, G, c, N, M, k, dilation, y is not None, rp is not None, flags, False)
-    rc = lib.gkg_knn_fwd_tm(_ptr(x), ldx, xchunk, _ptr(y), _ptr(rp), edge[0].data_ptr(), edge[1].data_ptr(), B, G, c, N, M, k,
-                            dilation, _lib.F32, flags, _ptr(ws), ws.numel(), _stream())
-    _lib.check(rc, "gkg_knn_fwd_tm")
-    return edge
+    rp = None if relative_pos is None else _rp_arg(relative_pos, N, M)
+    # (under opt-in bf16 autocast the reference's own x.y^T runs in bf16, and rounds the result to bf16)
+    flags = knn_prep.problem_flags(relative_pos, KNN_BF16 and torch.is_autocast_enabled()
+                                   and torch.get_autocast_dtype("cuda") == torch.bfloat16)
+    if compact:
+        out, entry = torch.empty((B * G, N, k), dtype=torch.int16, device=x.device), "gkg_knn_fwd_tm16"
+        outs = (_ptr(out),)
+    else:
+        out, entry = torch.empty((2, B * G, N, k), dtype=torch.int64, device=x.device), "gkg_knn_fwd_tm"
+        outs = (out[0].data_ptr(), out[1].data_ptr())
+    ws, flags = knn_prep.consumer_ws_flags(lib, x, B, G, c, N, M, k, dilation, y is not None, rp is not None, flags, False)
+    _lib.check(getattr(lib, entry)(_ptr(x), ldx, xchunk, _ptr(y), _ptr(rp), *outs, B, G, c, N, M, k, dilation, _lib.F32, flags,
+                                   _ptr(ws), ws.numel(), _stream()), entry)
+    return out
+
+
+def knn_graph_tm(x, y, relative_pos, k, dilation, G):
+    """x (B,N,C) [or the x half of an XM buffer], y (B,M,C)|None token-major -> edge_index (2, B*G, N, k) int64."""
+    return _knn_graph(x, y, relative_pos, k, dilation, G, False)
 
 
 _KNN_GRAPH_TM = knn_graph_tm             # the library's own function (tests patch ``fused.knn_graph_tm`` to record / force graphs)
@@ -1421,26 +1387,9 @@ _KNN_GRAPH_TM = knn_graph_tm             # the library's own function (tests pat
 KNN_COMPACT = "knn_compact" not in _DISABLED
 
 
-@torch.no_grad()
 def knn_graph_tm16(x, y, relative_pos, k, dilation, G):
     """x (B,N,C) [or the x half of an XM buffer], y (B,M,C)|None token-major -> neighbour lists (B*G, N, k) int16 (the bits of u16 rows)."""
-    lib = _lib.load()
-    B, N, C, ldx, xchunk = _tm_view(x)
-    x = _as_tokens(x)
-    c = C // G
-    M = N if y is None else y.shape[1]
-    flags = _lib.KNN_NORMALIZE | _lib.knn_select_flags()
-    if KNN_BF16 and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16:
-        flags |= _lib.KNN_BF16_CONTRACT
-    rp = None
-    if relative_pos is not None:
-        rp = _rp_arg(relative_pos, N, M)
-        flags |= _lib.relpos_flags(relative_pos)
-    nn16 = torch.empty((B * G, N, k), dtype=torch.int16, device=x.device)
-    ws, flags = _knn_prepared(x, B, G, c, N, M, k, dilation, y is not None, rp is not None, flags, False)
-    _lib.check(lib.gkg_knn_fwd_tm16(_ptr(x), ldx, xchunk, _ptr(y), _ptr(rp), _ptr(nn16), B, G, c, N, M, k, dilation, _lib.F32, flags,
-                                    _ptr(ws), ws.numel(), _stream()), "gkg_knn_fwd_tm16")
-    return nn16
+    return _knn_graph(x, y, relative_pos, k, dilation, G, True)
 
 
 def _xm_out(x, B, N, C, dt):
@@ -1508,16 +1457,13 @@ class _KnnMaxRelativeTM(torch.autograd.Function):
         x = _as_tokens(x)
         M = N if src is None else src.shape[1]
         c = C // G
-        flags = _lib.KNN_NORMALIZE | _lib.knn_select_flags()
-        rp = None
-        if relative_pos is not None:
-            rp = _rp_arg(relative_pos, N, M)
-            flags |= _lib.relpos_flags(relative_pos)
+        rp = None if relative_pos is None else _rp_arg(relative_pos, N, M)
+        flags = knn_prep.problem_flags(relative_pos)
         XM = _xm_out(x, B, N, C, _F32)
         arg = torch.empty((B, N, C), dtype=torch.int16, device=x.device)
         # the (2, B*G, N, k) int64 edge_index only for callers that return the graph (GrapherLabel / tests): written by the kernel
         edge = torch.empty((2, B * G, N, k) if want_nn else (0,), dtype=torch.int64, device=x.device)
-        ws, flags = _knn_prepared(x, B, G, c, N, M, k, d, src is not None, rp is not None, flags, True)
+        ws, flags = knn_prep.consumer_ws_flags(lib, x, B, G, c, N, M, k, d, src is not None, rp is not None, flags, True)
         _lib.check(lib.gkg_knn_mr_fwd_tm(_ptr(x), ldx, xchunk, _ptr(src), _ptr(rp), _ptr(XM), _ptr(arg), None,
                                          edge[0].data_ptr() if want_nn else None, edge[1].data_ptr() if want_nn else None, B, G, c,
                                          N, M, k, d, flags, _ptr(ws), ws.numel(), _stream()), "gkg_knn_mr_fwd_tm")
@@ -1540,15 +1486,20 @@ class _KnnMaxRelativeTM(torch.autograd.Function):
         return gxv, gsrc, None, None, None, None, None
 
 
+def _knn_ahead_ok() -> bool:
+    """The k-NN problem of a call can be told before its tokens exist (the fused kernel chosen, the tokens prepared by their
+    producer): not with the bf16 contraction, nor with a patched ``knn_graph_tm`` (tests that record or force graphs)."""
+    return knn_graph_tm is _KNN_GRAPH_TM and not (KNN_BF16 and torch.is_autocast_enabled())
+
+
 def _knn_mr_shapes_ok(B, N, C, M, has_src, relative_pos, k, d, G, nn_, lp) -> bool:
     """The shape / mode part of _knn_mr_ok (what is known before the tensors exist: fc1 asks on behalf of its output)."""
-    if not (KNN_MR and not lp and knn_graph_tm is _KNN_GRAPH_TM) or (KNN_BF16 and torch.is_autocast_enabled()):
+    if not (KNN_MR and not lp and _knn_ahead_ok()):
         return False
     if C % 16 or M > 65536 or len(nn_) != 3:
         return False
-    flags = _lib.KNN_NORMALIZE | _lib.knn_select_flags() | _lib.relpos_flags(relative_pos)
     return bool(_lib.load().gkg_knn_mr_fused_supported(B, G, C // G, N, M, k, d, 1 if has_src else 0,
-                                                       0 if relative_pos is None else 1, flags))
+                                                       0 if relative_pos is None else 1, knn_prep.problem_flags(relative_pos)))
 
 
 def _knn_mr_ok(x, src, relative_pos, k, d, G, nn_, lp) -> bool:
@@ -1561,12 +1512,13 @@ def _knn_mr_ok(x, src, relative_pos, k, d, G, nn_, lp) -> bool:
 
 
 def _knn_key_for(B, N, C, M, has_src, relative_pos, gc, groups, lp, want_edge):
-    """The _KnnKey of the k-NN call _graph_and_project will make for these shapes (fc1 prepares its queries), or None when the
-    queries cannot be prepared ahead (bf16 contraction, a patched ``knn_graph_tm``: tests that record or force graphs)."""
-    if lp or knn_graph_tm is not _KNN_GRAPH_TM or (KNN_BF16 and torch.is_autocast_enabled()) or (C // groups) % 4:
+    """The KnnProblem of the k-NN call _graph_and_project will make for these shapes (fc1 prepares its queries), or None when the
+    queries cannot be prepared ahead (_knn_ahead_ok) or by the preparation kernel — which takes group widths that are multiples
+    of 4 (the block driver never asks: block.grapher_ok excludes that shape before)."""
+    if lp or not _knn_ahead_ok() or (C // groups) % 4:
         return None
     fused_mr = _knn_mr_shapes_ok(B, N, C, M, has_src, relative_pos, gc.k, gc.d, groups, gc.gconv.nn, lp)
-    return _KnnKey(B, groups, C // groups, N, M, gc.k, gc.d, has_src, relative_pos, fused_mr)
+    return knn_prep.KnnProblem(B, groups, C // groups, N, M, gc.k, gc.d, has_src, relative_pos, fused_mr)
 
 
 def _aggregate_project(x1b, yb, nn_idx, groups, nn_, C, lp):
@@ -1767,15 +1719,10 @@ def grapher_forward(mod, x, relative_pos, groups: int, want_edge: bool = True):
         out = _lin(a2, mod.fc2, residual=x, scale=scale, rows_per_scale=N, want16=lp)
         return _cl_out(out, B, H, W), edge
     if dual:
-        # ... and, once the label block behind has said which k-NN problem it solves over this map (_gkg_label_knn), the same pass
+        # ... and, once the label block behind has said which k-NN problem it solves over this map (KnnProblem.announce), the same pass
         # prepares that problem's KEYS (gkg_bn_apply_knn_prep as_keys): the label graph launches no token preparation at all
-        lk = getattr(mod, "_gkg_label_knn", None) if KNN_PREP else None
-        kk = None
-        if lk is not None and knn_graph_tm is _KNN_GRAPH_TM and not (KNN_BF16 and torch.is_autocast_enabled()):
-            G2, L2, k2, d2, fm2 = lk
-            if C % G2 == 0 and (C // G2) % 4 == 0:
-                kk = _KnnKey(B, G2, C // G2, L2, N, k2, d2, True, None, fm2)
-                kk.as_keys = 1
+        # (its workspace is allocated by the pass itself, only if it runs as the producer: KnnProblem.producer_args)
+        kk = knn_prep.KnnProblem.keys_for_label(B, C, N, knn_prep.announced(mod)) if (KNN_PREP and _knn_ahead_ok()) else None
         out, out_tm = _lin(a2, mod.fc2, residual=xt_r, nchw=(B, C, H, W), dual=True, knn=kk)
         out._gkg_tm = (out._version, out_tm)                        # the token-major companion (grapher_label_forward)
         out._gkg_producer = weakref.ref(mod)
@@ -1798,7 +1745,7 @@ def _label_features(features, B, C):
     elif (DUAL_LAYOUT and ent is not None and ent[0] == features._version and features.dim() == 4 and features.dtype == _F32
           and ent[1].shape == (B * features.shape[2] * features.shape[3], C)):
         ft = ent[1].view(B, -1, C)                                           # the producing block's token-major companion
-        keys_key = getattr(ent[1], "_gkg_knn_keys", None)                    # ... which may carry this graph's prepared keys
+        keys_key = knn_prep.prepared_keys(ent[1])                            # ... which may carry this graph's prepared keys
     else:
         if prod is not None and not prod.__dict__.get("_gkg_want_tm", False):
             prod._gkg_want_tm = True                                         # ... which it emits from its next call on
@@ -1816,13 +1763,8 @@ def grapher_label_forward(mod, e, features, groups: int):
     xm = (B, L) if (XM_DIRECT and not lp and not torch.is_autocast_enabled() and C % 16 == 0) else None
     knn = _knn_key_for(B, L, C, ftc.shape[1], True, None, gc, groups, lp, True) if (xm is not None and KNN_PREP) else None
     if knn is not None:
-        kk = keys_key
-        if kk is not None and kk.ws is not None and kk.tuple() == knn.tuple():      # the producing Grapher prepared the keys: its
-            knn.ws, knn.y_ready = kk.ws, True                                        # workspace is this call's
-        if prod is not None:
-            lk = (groups, L, gc.k, gc.d, knn.fused_mr)
-            if prod.__dict__.get("_gkg_label_knn") != lk:
-                prod._gkg_label_knn = lk                                             # ... from its next call on
+        knn.adopt_keys(keys_key)                 # the producing Grapher prepared the keys: its workspace is this call's
+        knn.announce(prod, groups, L)            # ... or it does, from its next call on
     if not lp:
         from . import block
         if block.label_ok(mod, e, ftc, groups):
