@@ -67,10 +67,11 @@ __device__ __forceinline__ float gelu_grad_f(float z) {
 
 // Train-mode BN whose statistics came out of the projection kernel's epilogue as fp64 column sums (gkg_linear_bn_fwd* with
 // train == 2): the CONSUMER of the projection — the BN-apply pass — derives scale / shift itself instead of a one-block
-// finalize launch in between.  Every workgroup computes the coefficients of its channels once (into LDS), the first
-// workgroup of each group also writes what the backward needs (a, c, mean, invstd) and updates the running statistics, and
-// clears `zero_buf`: the OTHER of two alternating scratch buffers, i.e. what the previous projection accumulated into (see
-// gkg_bn_bwd_atomic for the protocol).  Same arithmetic as bn_sums_finalize_kernel.
+// finalize launch in between.  A workgroup computes the coefficients of the channels it applies (its channel tile / its group:
+// in the tiled apply at most one channel per thread, its sums requested ahead of the first data rows), for every channel exactly one workgroup (`side`)
+// also writes what the backward needs (a, c, mean, invstd) and updates the running statistics, and one workgroup of the launch
+// counts the batch and clears `zero_buf`: the OTHER of two alternating scratch buffers, i.e. what the previous projection
+// accumulated into (see gkg_bn_bwd_atomic for the protocol).  Same arithmetic as bn_sums_finalize_kernel.
 struct BnDerive {
   const double* sums;       // [nb][2][C]; null: the caller passes a / c
   const float* gamma; const float* beta; const float* bias;

@@ -446,29 +446,12 @@ __global__ __launch_bounds__(256) void affine_act_kernel(const float* __restrict
                                                          const float* __restrict__ cs, const float* __restrict__ res,
                                                          OutT* __restrict__ out, size_t total4, int C, int ldo,
                                                          size_t o_bstride, const float* __restrict__ row_scale,
-                                                         int rows_per_scale, uint16_t* __restrict__ out2, BnDerive d,
-                                                         int ochunk = 0) {
-  extern __shared__ float ac_tab[];                 // derive mode: [2][C] scale / shift of this group
+                                                         int rows_per_scale, uint16_t* __restrict__ out2, int ochunk = 0) {
   const int C4 = C >> 2;
   const int q = blockIdx.y;
   y += (size_t)q * total4 * 4; out += (size_t)q * o_bstride;
   if (res) res += (size_t)q * total4 * 4;
-  if (d.sums) {
-    const bool side = blockIdx.x == 0;
-    for (int ch = threadIdx.x; ch < C; ch += 256) {
-      float av, cv;
-      bn_derive_channel(d, (size_t)q * C + ch, d.sums[(size_t)q * 2 * C + ch], d.sums[(size_t)q * 2 * C + C + ch], side, av, cv);
-      ac_tab[ch] = av; ac_tab[C + ch] = cv;
-    }
-    if (side && q == 0) {
-      if (threadIdx.x == 0 && d.nbt) *d.nbt += 1;
-      for (size_t i = threadIdx.x; i < d.zero_doubles; i += 256) d.zero_buf[i] = 0.0;
-    }
-    __syncthreads();
-    a = ac_tab; cs = ac_tab + C;
-  } else {
-    a += (size_t)q * C; cs += (size_t)q * C;
-  }
+  a += (size_t)q * C; cs += (size_t)q * C;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (size_t)gridDim.x * 256) {
     const size_t r = i / C4;
     const int cg = (int)(i - r * C4);
@@ -492,6 +475,84 @@ __global__ __launch_bounds__(256) void affine_act_kernel(const float* __restrict
     const int oc = ochunk > 0 ? 4 * cg + (4 * cg / ochunk) * ochunk : 4 * cg;
     stf4(out + r * (size_t)ldo + oc, o);
     if (out2) stf4(out2 + r * (size_t)ldo + oc, o);           // second, bf16 copy of the same values (gkg_affine_act_dual)
+  }
+}
+
+// The train-mode form of the same pass (gkg_bn_apply_train / _sync, token-major output): scale / shift come from the projection's
+// fp64 column sums (BnDerive).  Decomposed like bn_bwd_stats_kernel, (row chunk) x (channel tile) x nb, so that a workgroup needs
+// the coefficients of ONE tile only: at most 256 channels, one per thread, no loop.  Order of the requests: the tile's sums, then
+// the first AP_PF rows of every thread's column group, then the fp64 chain — it waits for the sums alone (loads return in order,
+// and the row loads are unconditional, out-of-range ones clamped onto the chunk's last row, so that their number is known when
+// the wait is placed) and runs under the rows' round trip.  A thread keeps its 4 + 4 coefficients in registers for all its rows.
+//   tile4: float4 column groups per tile (<= 64); the tile's row lanes are 256 / tile4 (threads past them only derive)
+// Side jobs, exactly once: the first row chunk of every (tile, group) stores the saved statistics and updates the running ones
+// (bn_derive_channel's `side`), workgroup (0, 0, 0) counts the batch and clears zero_buf.
+constexpr int AP_PF = 4;                            // rows a thread has in flight
+template <int ACT, bool RES>
+__global__ __launch_bounds__(256) void bn_apply_tiled_kernel(const float* __restrict__ y, const float* __restrict__ res,
+                                                             float* __restrict__ out, int R, int C, int ldo, size_t o_bstride,
+                                                             const float* __restrict__ row_scale, int rows_per_scale, BnDerive d,
+                                                             int ochunk, int tile4, int rows_per_block) {
+  __shared__ float ac_tab[2][256];                  // scale / shift of the tile's channels
+  const int tid = threadIdx.x;
+  const int q = blockIdx.z;
+  const int C4 = C >> 2;
+  const int RL = 256 / tile4;
+  const int rl = tid / tile4;
+  const int cg = tid - rl * tile4;
+  const int cgi = blockIdx.y * tile4 + cg;          // float4 column group of the matrix
+  const int r1 = (int)min((long long)R, ((long long)blockIdx.x + 1) * rows_per_block);
+  y += (size_t)q * R * C + 4 * min(cgi, C4 - 1); out += (size_t)q * o_bstride;
+  if (RES) res += (size_t)q * R * C + 4 * min(cgi, C4 - 1);
+  int r = (rl < RL && cgi < C4) ? (int)blockIdx.x * rows_per_block + rl : r1;      // idle thread: no rows
+  const int chd = blockIdx.y * 4 * tile4 + tid;     // the channel this thread derives
+  const bool derive = tid < 4 * tile4 && chd < C;
+  double S = 0.0, Q = 0.0;
+  if (derive) { S = d.sums[(size_t)q * 2 * C + chd]; Q = d.sums[(size_t)q * 2 * C + C + chd]; }
+  float4 v[AP_PF], rv[AP_PF];
+  float sc[AP_PF];                                  // DropPath: one factor per image = rows_per_scale consecutive rows
+  auto request = [&]() __attribute__((always_inline)) {
+#pragma unroll
+    for (int u = 0; u < AP_PF; ++u) {
+      const int ru = min(r + u * RL, r1 - 1);
+      v[u] = *reinterpret_cast<const float4*>(y + (size_t)ru * C);
+      if (RES) rv[u] = *reinterpret_cast<const float4*>(res + (size_t)ru * C);
+      if (row_scale) sc[u] = row_scale[ru / rows_per_scale];
+    }
+  };
+  request();
+  if (derive) {
+    float av, cv;
+    bn_derive_channel(d, (size_t)q * C + chd, S, Q, blockIdx.x == 0, av, cv);
+    ac_tab[0][tid] = av; ac_tab[1][tid] = cv;
+  }
+  if (blockIdx.x == 0 && blockIdx.y == 0 && q == 0) {
+    if (tid == 0 && d.nbt) *d.nbt += 1;
+    for (size_t i = tid; i < d.zero_doubles; i += 256) d.zero_buf[i] = 0.0;
+  }
+  __syncthreads();
+  if (r >= r1) return;
+  const float4 a4 = *reinterpret_cast<const float4*>(&ac_tab[0][4 * cg]);
+  const float4 c4 = *reinterpret_cast<const float4*>(&ac_tab[1][4 * cg]);
+  // ochunk > 0: the x half of the grouped projection's [x | m] operand buffer, as in affine_act_kernel
+  out += ochunk > 0 ? 4 * cgi + (4 * cgi / ochunk) * ochunk : 4 * cgi;
+  for (;;) {
+#pragma unroll
+    for (int u = 0; u < AP_PF; ++u) {
+      const int ru = r + u * RL;
+      if (ru < r1) {
+        float4 o;
+        o.x = __builtin_fmaf(a4.x, v[u].x, c4.x); o.y = __builtin_fmaf(a4.y, v[u].y, c4.y);
+        o.z = __builtin_fmaf(a4.z, v[u].z, c4.z); o.w = __builtin_fmaf(a4.w, v[u].w, c4.w);
+        if (ACT == 1) { o.x = gelu_f(o.x); o.y = gelu_f(o.y); o.z = gelu_f(o.z); o.w = gelu_f(o.w); }
+        if (row_scale) { o.x *= sc[u]; o.y *= sc[u]; o.z *= sc[u]; o.w *= sc[u]; }
+        if (RES) { o.x += rv[u].x; o.y += rv[u].y; o.z += rv[u].z; o.w += rv[u].w; }
+        stf4(out + (size_t)ru * ldo, o);
+      }
+    }
+    r += AP_PF * RL;
+    if (r >= r1) break;
+    request();
   }
 }
 
@@ -770,6 +831,26 @@ static int stats_blocks(int R, int C, int nb, int* rows_per_block) {
   return (R + *rows_per_block - 1) / *rows_per_block;
 }
 
+// The tiling of bn_apply_tiled_kernel (EXPERIMENTS.md "Tiled derive-apply": the sweep behind these choices).
+// Channel tiles: 16 float4 column groups where they divide the row (C = 320, 1280: 16 full row lanes, one wave derives), else
+// as few tiles as 64 column groups allow, of equal width (4 x 160 -> one tile of 40 per group: three tiles of 16 would leave
+// a third of the last one idle).
+// Row chunks: ~4 workgroups per CU over (chunks x tiles x nb), every workgroup resident from the start, but not fewer rows
+// than one request round fills (AP_PF per row lane) — the small matrices are one round trip; with GELU one row per lane is
+// enough (the pass is then bound by vector instructions: more workgroups beat fuller ones).
+static int apply_blocks(int R, int C, int nb, int act, int* tile4, int* rows_per_block) {
+  const int C4 = C >> 2;
+  const int tiles = (C4 + 63) / 64;
+  *tile4 = (C4 & 15) == 0 ? 16 : (C4 + tiles - 1) / tiles;
+  const int min_rows = (act == 1 ? 1 : AP_PF) * (256 / *tile4);
+  const int cols = ((C4 + *tile4 - 1) / *tile4) * nb;
+  long long nblk = (1024 + cols - 1) / cols;
+  const long long by_rows = ((long long)R + min_rows - 1) / min_rows;
+  if (nblk > by_rows) nblk = by_rows;
+  *rows_per_block = (int)((R + nblk - 1) / nblk);
+  return (int)((R + (long long)*rows_per_block - 1) / *rows_per_block);
+}
+
 static bool bad_c(int C) { return C <= 0 || (C & 3) != 0 || C > 4096; }
 
 extern "C" size_t gkg_bn_workspace_bytes(int R, int C, int nb) {
@@ -901,12 +982,12 @@ extern "C" int gkg_affine_act(const float* y, const float* a, const float* c, co
   hipStream_t st = (hipStream_t)stream;
   if (out_dtype == GKG_BF16) {
     uint16_t* o = (uint16_t*)out;
-    if (act == 1) hipLaunchKernelGGL((affine_act_kernel<1, uint16_t>), grid, dim3(256), 0, st, y, a, c, res, o, total4, C, ldo, out_bstride, row_scale, rows_per_scale, (uint16_t*)nullptr, BnDerive{}, ochunk);
-    else hipLaunchKernelGGL((affine_act_kernel<0, uint16_t>), grid, dim3(256), 0, st, y, a, c, res, o, total4, C, ldo, out_bstride, row_scale, rows_per_scale, (uint16_t*)nullptr, BnDerive{}, ochunk);
+    if (act == 1) hipLaunchKernelGGL((affine_act_kernel<1, uint16_t>), grid, dim3(256), 0, st, y, a, c, res, o, total4, C, ldo, out_bstride, row_scale, rows_per_scale, (uint16_t*)nullptr, ochunk);
+    else hipLaunchKernelGGL((affine_act_kernel<0, uint16_t>), grid, dim3(256), 0, st, y, a, c, res, o, total4, C, ldo, out_bstride, row_scale, rows_per_scale, (uint16_t*)nullptr, ochunk);
   } else {
     float* o = (float*)out;
-    if (act == 1) hipLaunchKernelGGL((affine_act_kernel<1, float>), grid, dim3(256), 0, st, y, a, c, res, o, total4, C, ldo, out_bstride, row_scale, rows_per_scale, (uint16_t*)nullptr, BnDerive{}, ochunk);
-    else hipLaunchKernelGGL((affine_act_kernel<0, float>), grid, dim3(256), 0, st, y, a, c, res, o, total4, C, ldo, out_bstride, row_scale, rows_per_scale, (uint16_t*)nullptr, BnDerive{}, ochunk);
+    if (act == 1) hipLaunchKernelGGL((affine_act_kernel<1, float>), grid, dim3(256), 0, st, y, a, c, res, o, total4, C, ldo, out_bstride, row_scale, rows_per_scale, (uint16_t*)nullptr, ochunk);
+    else hipLaunchKernelGGL((affine_act_kernel<0, float>), grid, dim3(256), 0, st, y, a, c, res, o, total4, C, ldo, out_bstride, row_scale, rows_per_scale, (uint16_t*)nullptr, ochunk);
   }
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : gkg_fail_hip(e, "affine_act_kernel");
@@ -939,8 +1020,8 @@ extern "C" int gkg_affine_act_dual(const float* y, const float* a, const float* 
   const size_t total4 = (size_t)R * (C >> 2);
   const int blocks = (int)((total4 + 255) / 256 > 2048 ? 2048 : (total4 + 255) / 256);
   hipStream_t st = (hipStream_t)stream;
-  if (act == 1) hipLaunchKernelGGL((affine_act_kernel<1, float>), dim3(blocks, 1), dim3(256), 0, st, y, a, c, res, out_f32, total4, C, C, (size_t)0, row_scale, rows_per_scale, (uint16_t*)out_bf16, BnDerive{});
-  else hipLaunchKernelGGL((affine_act_kernel<0, float>), dim3(blocks, 1), dim3(256), 0, st, y, a, c, res, out_f32, total4, C, C, (size_t)0, row_scale, rows_per_scale, (uint16_t*)out_bf16, BnDerive{});
+  if (act == 1) hipLaunchKernelGGL((affine_act_kernel<1, float>), dim3(blocks, 1), dim3(256), 0, st, y, a, c, res, out_f32, total4, C, C, (size_t)0, row_scale, rows_per_scale, (uint16_t*)out_bf16);
+  else hipLaunchKernelGGL((affine_act_kernel<0, float>), dim3(blocks, 1), dim3(256), 0, st, y, a, c, res, out_f32, total4, C, C, (size_t)0, row_scale, rows_per_scale, (uint16_t*)out_bf16);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : gkg_fail_hip(e, "affine_act_kernel (dual)");
 }
@@ -1156,12 +1237,12 @@ static int bn_apply_train_impl(const float* y, const double* sums, const float* 
     if (ldo < C || (ldo & 3) || (out_bstride & 3)) return gkg_fail(GKG_ERR_SHAPE, "gkg_bn_apply_train: bad output pitch");
     if (ochunk < 0 || (ochunk & 3) || (ochunk > 0 && (C % ochunk || ldo < 2 * C)))
       return gkg_fail(GKG_ERR_SHAPE, "gkg_bn_apply_train: ochunk must be a multiple of 4 dividing C, with ldo >= 2 C");
-    const size_t total4 = (size_t)R * (C >> 2);
-    const int blocks = (int)((total4 + 255) / 256 > 2048 ? 2048 : (total4 + 255) / 256);
-    const dim3 grid(blocks, nb);
-    const size_t lds = (size_t)2 * C * sizeof(float);
-    if (act == 1) hipLaunchKernelGGL((affine_act_kernel<1, float>), grid, dim3(256), lds, st, y, (const float*)nullptr, (const float*)nullptr, res, out, total4, C, ldo, out_bstride, row_scale, rows_per_scale, (uint16_t*)nullptr, d, ochunk);
-    else hipLaunchKernelGGL((affine_act_kernel<0, float>), grid, dim3(256), lds, st, y, (const float*)nullptr, (const float*)nullptr, res, out, total4, C, ldo, out_bstride, row_scale, rows_per_scale, (uint16_t*)nullptr, d, ochunk);
+    if (R > 0x7fffffff - 4 * 256 * AP_PF) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_bn_apply_train: too many rows for one launch");
+    int tile4, rpb;
+    const dim3 grid(apply_blocks(R, C, nb, act, &tile4, &rpb), ((C >> 2) + tile4 - 1) / tile4, nb);
+    auto kern = act == 1 ? (res ? bn_apply_tiled_kernel<1, true> : bn_apply_tiled_kernel<1, false>)
+                         : (res ? bn_apply_tiled_kernel<0, true> : bn_apply_tiled_kernel<0, false>);
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, y, res, out, R, C, ldo, out_bstride, row_scale, rows_per_scale, d, ochunk, tile4, rpb);
   }
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : gkg_fail_hip(e, "bn_apply_train");

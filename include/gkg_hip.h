@@ -401,9 +401,10 @@ int gkg_bn_bwd(const float* dout, const float* y, const float* a, const float* c
 
 /* Train-mode BN-apply straight from the projection kernel's fp64 column sums (gkg_linear_bn_fwd / gkg_linear_bn_fwd_x6 with
  * train == 2: statistics only): the consumer derives scale / shift itself — no finalize launch in between.  Every workgroup
- * computes its channels' coefficients once, the first one per group also writes the saved a / c / mean / invstd [nb][C],
- * updates running_mean / running_var (conv `bias` folded) and num_batches_tracked, and clears `zero_buf` (`zero_doubles`
- * doubles): the OTHER of the caller's two alternating scratch buffers, i.e. what the previous projection accumulated into.
+ * computes the coefficients of the channels it applies (the token-major form: of its channel tile), exactly one per channel
+ * also writes the saved a / c / mean / invstd [nb][C] and updates running_mean / running_var (conv `bias` folded), one
+ * workgroup counts num_batches_tracked and clears `zero_buf` (`zero_doubles` doubles): the OTHER of the caller's two
+ * alternating scratch buffers, i.e. what the previous projection accumulated into.
  * nchw_B == 0: token-major output like gkg_affine_act (fp32); nchw_B > 0: (nchw_B, C, R / nchw_B) channel-major output and
  * residual like gkg_tm_affine_to_nchw (nb == 1, act == 0, row_scale = one factor per image).  Same arithmetic as the
  * finalize + apply launches it replaces. */
