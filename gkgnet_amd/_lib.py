@@ -30,8 +30,9 @@ KNN_X_PREPARED = _K["KNN_X_PREPARED"]
 KNN_Y_PREPARED = _K["KNN_Y_PREPARED"]
 MR_DETERMINISTIC, MR_FP32_ATOMICS = _K["MR_DETERMINISTIC"], _K["MR_FP32_ATOMICS"]
 X6_NO_KS, X6_FORCE_KS = _K["X6_NO_KS"], _K["X6_FORCE_KS"]
+X6_NO_WALK, X6_FORCE_WALK, X6_WALK_CAP_SHIFT = _K["X6_NO_WALK"], _K["X6_FORCE_WALK"], _K["X6_WALK_CAP_SHIFT"]
 ERR_UNSUPPORTED = _K["ERR_UNSUPPORTED"]
-BLOCK_NO_BWD_FUSE, BLOCK_NO_DGRAD_STATS = _K["BLOCK_NO_BWD_FUSE"], _K["BLOCK_NO_DGRAD_STATS"]
+BLOCK_NO_BWD_FUSE, BLOCK_NO_DGRAD_STATS, BLOCK_NO_X6_WALK = _K["BLOCK_NO_BWD_FUSE"], _K["BLOCK_NO_DGRAD_STATS"], _K["BLOCK_NO_X6_WALK"]
 EXPORTS = tuple(_ABI.protos)
 # the profiler's kernel ids GKG_PROF_* (all but the count GKG_PROF_NUM) as lower-case names, in id order
 PROF_KERNELS = tuple(n[5:].lower() for n in sorted((n for n in _K if n.startswith("PROF_") and n != "PROF_NUM"), key=_K.get))

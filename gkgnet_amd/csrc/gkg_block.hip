@@ -33,7 +33,10 @@ struct Ctx {
   bool frozen;
   void* sk_ws; size_t sk_bytes;
   void* st;
+  unsigned x6_flags;                 // GKG_X6_* of every projection launch of the call
 };
+// the projections' per-call flags from a block's bwd_flags
+unsigned x6_flags_of(unsigned bwd_flags) { return (bwd_flags & GKG_BLOCK_NO_X6_WALK) ? GKG_X6_NO_WALK : 0u; }
 
 // ---- the layer steps ---------------------------------------------------------------------------------------------------------------
 // GEMM step, y = x W^T.  Train: with the BN statistics into p.fsum.  Frozen: without, then (a, c) folded from the running
@@ -41,7 +44,7 @@ struct Ctx {
 int proj_gemm(const Ctx& c, const GkgProjBN& p, const float* x, int ldx, size_t x_bstride, int R) {
   GKG_TRY(gkg_linear_bn_fwd_x6_sk(x, ldx, x_bstride, p.planes_fwd, p.Y, R, p.cin, p.cout, p.nb, c.frozen ? 0 : 2, nullptr, nullptr, nullptr,
                                   nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, c.frozen ? nullptr : p.fsum,
-                                  c.sk_ws, c.sk_bytes, 0, c.st));
+                                  c.sk_ws, c.sk_bytes, c.x6_flags, c.st));
   if (!c.frozen) return 0;
   const int n = p.nb * p.cout;
   return gkg_bn_eval_affine(p.gamma, p.beta, p.bias, p.running_mean, p.running_var, p.bn, p.bn + n, n, p.eps, c.st);
@@ -91,10 +94,10 @@ int proj_dgrad(const Ctx& c, const GkgProjBN& p, const GkgProjBN* q, int qact, c
                int ldx, size_t x_bstride) {
   if (!q)
     return gkg_linear_dgrad_x6_sk(dY, p.cout, (size_t)R * p.cout, p.planes_dgrad, dx, R, p.cin, p.cout, p.nb, residual, c.sk_ws, c.sk_bytes,
-                                  ldx, x_bstride, 0, c.st);
+                                  ldx, x_bstride, c.x6_flags, c.st);
   const int n = q->nb * q->cout;
   return gkg_linear_dgrad_x6_bnbwd_sk(dY, p.cout, p.planes_dgrad, dx, R, p.cin, p.cout, residual, q->Y, q->bn, q->bn + n, q->bn + 2 * n,
-                                      q->bn + 3 * n, q->bsum, q->nb, q->cout, qact, c.sk_ws, c.sk_bytes, 0, c.st);
+                                      q->bn + 3 * n, q->bsum, q->nb, q->cout, qact, c.sk_ws, c.sk_bytes, c.x6_flags, c.st);
 }
 // whether p's input-gradient GEMM can take the statistics of the layer in front (never in a frozen block: there are none)
 bool dgrad_stats_ok(const Ctx& c, const GkgProjBN& p, unsigned bwd_flags, int R, bool residual) {
@@ -252,7 +255,7 @@ int check_label(const GkgLabelBlock* b, const GkgWgradProblem* wq, bool bwd) {
 // ---- Grapher (reference torch_vertex.py:325-333): x (B, C, H, W) -> out (B, C, H, W) [+ out_tm (B N, C)] ----------------------
 extern "C" int gkg_grapher_fwd(const GkgGrapherBlock* b, void* st) {
   GKG_TRY(check_grapher(b, nullptr, false));
-  const Ctx c{b->bn_frozen != 0, b->sk_ws, b->sk_bytes, st};
+  const Ctx c{b->bn_frozen != 0, b->sk_ws, b->sk_bytes, st, x6_flags_of(b->bwd_flags)};
   const int B = b->B, C = b->C, N = b->H * b->W, T = B * N;
   // block entry: NCHW -> token-major; then the core on the self graph
   GKG_TRY(gkg_nchw_to_tm(b->x, b->xt, B, C, N, GKG_F32, nullptr, st));
@@ -277,7 +280,7 @@ extern "C" int gkg_grapher_fwd(const GkgGrapherBlock* b, void* st) {
 // dXM (T, 2C), gx1, dY1, dxt (T, C) — caller-owned; dY3 / dY2 / dY1 must stay valid until the weight gradients have run.
 extern "C" int gkg_grapher_bwd(const GkgGrapherBlock* b, GkgWgradProblem* wq, void* st) {
   GKG_TRY(check_grapher(b, wq, true));
-  const Ctx c{b->bn_frozen != 0, b->sk_ws, b->sk_bytes, st};
+  const Ctx c{b->bn_frozen != 0, b->sk_ws, b->sk_bytes, st, x6_flags_of(b->bwd_flags)};
   const int B = b->B, C = b->C, N = b->H * b->W, T = B * N;
   // the output's gradient(s) token-major (g3); it is also the residual branch's gradient
   // (round 8, unless GKG_BLOCK_NO_BWD_FUSE or frozen: the re-layout pass takes fc2's BN backward statistics, the scatter takes fc1's
@@ -294,7 +297,7 @@ extern "C" int gkg_grapher_bwd(const GkgGrapherBlock* b, GkgWgradProblem* wq, vo
   // fc1's input gradient + the residual branch's (g3), channel-major: stored that way by the GEMM (round 8, in both modes), or
   // token-major and re-laid out
   if (nchw_dgrad)
-    return gkg_linear_dgrad_x6_nchw(b->dY1, C, b->fc1.planes_dgrad, b->dx, b->dxt, T, C, C, b->g3, B, N, b->sk_ws, b->sk_bytes, 0, st);
+    return gkg_linear_dgrad_x6_nchw(b->dY1, C, b->fc1.planes_dgrad, b->dx, b->dxt, T, C, C, b->g3, B, N, b->sk_ws, b->sk_bytes, c.x6_flags, st);
   GKG_TRY(proj_dgrad(c, b->fc1, nullptr, 0, b->dY1, T, b->g3, b->dxt, 0, 0));
   return gkg_tm_affine_to_nchw(b->dxt, nullptr, nullptr, nullptr, b->dx, B, C, N, nullptr, st);
 }
@@ -302,7 +305,7 @@ extern "C" int gkg_grapher_bwd(const GkgGrapherBlock* b, GkgWgradProblem* wq, vo
 // ---- GrapherLabel (reference torch_vertex.py:392-403 + FFNLabel :334-360): e (B L, C), keys / values ft (B, M, C) -> E' (B L, C) -----
 extern "C" int gkg_grapher_label_fwd(const GkgLabelBlock* b, void* st) {
   GKG_TRY(check_label(b, nullptr, false));
-  const Ctx c{b->bn_frozen != 0, b->sk_ws, b->sk_bytes, st};
+  const Ctx c{b->bn_frozen != 0, b->sk_ws, b->sk_bytes, st, x6_flags_of(b->bwd_flags)};
   const int C = b->C, T = b->B * b->L, Cf = b->ffn1.cout;
   // the core on the graph from the labels to the image tokens (the train form has always announced "no positional bias" to the
   // query preparation, the frozen form what the graph op carries; a label graph has none)
@@ -319,7 +322,7 @@ extern "C" int gkg_grapher_label_fwd(const GkgLabelBlock* b, void* st) {
 // Temporaries: dY5 (T, C), df1 (T, Cf), dY4 (T, Cf), dh2 (T, C), dY3 (T, C), dA2 (T, 2C), dY2 (4, T, C/2), dXM (T, 2C), gx1, dY1 (T, C).
 extern "C" int gkg_grapher_label_bwd(const GkgLabelBlock* b, GkgWgradProblem* wq, void* st) {
   GKG_TRY(check_label(b, wq, true));
-  const Ctx c{b->bn_frozen != 0, b->sk_ws, b->sk_bytes, st};
+  const Ctx c{b->bn_frozen != 0, b->sk_ws, b->sk_bytes, st, x6_flags_of(b->bwd_flags)};
   const int C = b->C, T = b->B * b->L, Cf = b->ffn1.cout;
   // (round 9, unless GKG_BLOCK_NO_DGRAD_STATS or frozen: each input-gradient GEMM of the chain ffn2 -> ffn1 -> fc2 -> conv takes the
   // backward statistics of the layer in front of it, whose BN backward is then its apply pass — three launches fewer)

@@ -166,9 +166,14 @@ struct X6Args {
   // X6_STORE_NCHW: the tile goes out channel-major, C (M / nchw_n, nchw_c == N, nchw_n) — row m is token m % nchw_n of image
   // m / nchw_n — while `add` stays token-major (row pitch ldc).  nchw_n % 4 == 0 and M == images * nchw_n.
   int nchw_n, nchw_c;
+  int walk_nb;                                          // gemm_x6_walk_kernel: the batches folded into its 1-D grid
 };
 
 enum { X6_STORE = 0, X6_BNSTATS = 1, X6_BNBWD = 2, X6_STORE_NCHW = 3 };
+
+// LDS of gemm_x6_kernel's operand rings: three 16-KiB A stages + two B stage images (+ slack: the unused lanes of a partial last
+// block read past their image row)
+constexpr int x6_ring_bytes(int NI, int BN) { return 3 * 4 * 4096 + 2 * 12 * BN * 16 + (BN != 32 * NI ? 512 : 0); }
 
 __device__ __forceinline__ void x6_chan_merge(double& n, double& mean, double& m2, double nb, double mb, double m2b) {
   if (nb <= 0.0) return;
@@ -192,383 +197,86 @@ __device__ __forceinline__ void x6_dma16(const void* sbase, unsigned voff, unsig
 // 80, so 80-column tiles cover 80 / 160 outputs with one / two workgroups per row block where 64-column tiles need two / three:
 // at the short-K stage-1 / stage-2 shapes the launch time follows the number of requests (A is fetched once per column tile,
 // B once per tile and K-step), not the arithmetic (profiles/r04_x6_one_vs_two_column_tiles.txt).
-template <int NI, int EPI, int BN = 32 * NI>
-__global__ __launch_bounds__(256) void gemm_x6_kernel(X6Args g) {
-  static_assert(BN <= 32 * NI && BN > 32 * (NI - 1) && BN % 16 == 0 && (12 * BN * 16) % 1024 == 0, "tile width");
-  constexpr int BM = 128, BK = 32, SA = 3;
-  constexpr bool PARTIAL = BN != 32 * NI;                // lanes r >= BN - 32 (NI - 1) of the last block hold no column
-  constexpr int A_STAGE = 4 * 4096, B_STAGE = 12 * BN * 16, B_BASE = SA * A_STAGE;
-  constexpr int PIECES = 12 * BN * 16 / 1024;            // 1-KiB pieces of one B stage image
-  constexpr int BI = (PIECES + 3) / 4;                   // ... per wave per K-step (wave w: pieces w, w+4, ...), and the
-  constexpr int BI_MIN = PIECES / 4;                     // fewest any wave issues: what the counted waits may assume
-  extern __shared__ uint4 lds[];
-  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int z = blockIdx.y;
-  const int lin = blockIdx.x, xcd = lin & 7, slot = lin >> 3;
-  // the column tiles and the K splits of one 128-row block run back to back on one XCD
-  const int per_row = g.ntiles * g.ksplit, inner = slot % per_row;
-  const int tn = inner % g.ntiles, ks = inner / g.ntiles, tm = (slot / per_row) * 8 + xcd;
-  if (tm >= g.mtiles) return;
-  const int m0 = tm * BM, n0 = tn * BN;
-  const int M = g.M, N = g.N;
-  const int K = g.ksplit > 1 ? min(g.K - ks * g.kper * BK, g.kper * BK) : g.K;       // this workgroup's share of the contraction
-  const float* A = g.A + (size_t)z * g.a_bstride + (size_t)ks * g.kper * BK;
-  const uint4* P = g.P + (size_t)z * g.p_bstride + (size_t)ks * g.kper * 4 * g.NP;
-  const unsigned lds0 = (unsigned)(size_t)lds;
-  const int nk = (K + BK - 1) / BK;
-  const bool ktail = (K & (BK - 1)) != 0;
+// The kernel's text is gkg_gemm_x6_tile.h, compiled in two forms: one tile per workgroup, and a static walk over several.
+#define X6_WALK 0
+#include "gkg_gemm_x6_tile.h"
+#undef X6_WALK
+#define X6_WALK 1
+#include "gkg_gemm_x6_tile.h"
+#undef X6_WALK
 
-  // A pieces: LDS slot L = 64 i + lane of the wave's 32 x 128-B image holds chunk (L & 7) ^ ((row >> 1) & 7) of row L >> 3
-  unsigned aoff[4];
-  int achunk[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int L = 64 * i + lane, row = L >> 3, chunk = (L & 7) ^ ((row >> 1) & 7);
-    const int gr = min(m0 + 32 * w + row, M - 1);        // rows past the end re-read the last row (never stored)
-    aoff[i] = (unsigned)((size_t)gr * g.lda + chunk * 4) * 4u;
-    achunk[i] = chunk;
+// The attribute (and, for the walk form, the resident-workgroup count) of one instantiation is per DEVICE (a per-process guard left
+// a second GPU of the same process without it — ADVICE r3): set / queried on the first launch there.  slots: out, or null.
+template <int NI, int EPI, int BN, bool WALK>
+static hipError_t x6_kernel_setup(size_t sh, int* slots) {
+  static int known[64] = {};                             // 0: not set up; else the resident workgroups of the device
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  const bool cached = dev >= 0 && dev < 64;
+  int n = cached ? known[dev] : 0;
+  if (n == 0) {
+    const void* fn;
+    if constexpr (WALK) fn = (const void*)gemm_x6_walk_kernel<NI, EPI, BN>;
+    else fn = (const void*)gemm_x6_kernel<NI, EPI, BN>;
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+    if (e != hipSuccess) return e;
+    int per_cu = 0, cus = 0;
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, sh);
+    if (e != hipSuccess) return e;
+    e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e != hipSuccess) return e;
+    n = per_cu * cus;
+    if (n < 8) return hipErrorInvalidConfiguration;
+    if (cached) known[dev] = n;
   }
-  const size_t plane = (size_t)g.KC * g.NP * 16;
-  // B pieces: slot s = 64 piece + lane of the stage image [3 planes][4 chunks][BN] holds n = s % BN of row s / BN (a piece
-  // may straddle two rows when BN is not a multiple of 64: the source address is per lane, the destination linear)
-  unsigned boff[BI];
-#pragma unroll
-  for (int i = 0; i < BI; ++i) {
-    const int sidx = (w + 4 * i) * 64 + lane, rowid = sidx / BN, n = sidx - rowid * BN, p = rowid >> 2, chunk = rowid & 3;
-    boff[i] = (unsigned)(p * plane + ((size_t)chunk * g.NP + n0 + n) * 16);
-  }
-  auto dma_a = [&](int kt) {
-    const char* base = (const char*)A + (size_t)kt * (BK * 4);
-    const unsigned dst = lds0 + (kt % SA) * A_STAGE + w * 4096;
-    const bool last = ktail && kt == nk - 1;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      unsigned o = aoff[i];
-      if (last && kt * BK + achunk[i] * 4 >= K) o -= achunk[i] * 16;      // past K: a valid address, masked after the read
-      x6_dma16(base, o, dst + i * 1024);
-    }
-  };
-  auto dma_b = [&](int kt) {
-    const char* base = (const char*)P + (size_t)kt * 4 * g.NP * 16;
-    const unsigned dst = lds0 + B_BASE + (kt & 1) * B_STAGE;
-#pragma unroll
-    for (int i = 0; i < BI; ++i)
-      if ((i + 1) * 4 <= PIECES || w + 4 * i < PIECES) x6_dma16(base, boff[i], dst + (w + 4 * i) * 1024);
-  };
-
-  x6_f32x16 acc[NI], accs[NI];
-#pragma unroll
-  for (int j = 0; j < NI; ++j)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) { acc[j][q] = 0.f; accs[j][q] = 0.f; }
-
-  const int r = lane & 31, h = lane >> 5, sw = (r >> 1) & 7;
-  int ac[2][2];
-#pragma unroll
-  for (int s = 0; s < 2; ++s) { ac[s][0] = r * 128 + (((4 * s + 2 * h) ^ sw) << 4); ac[s][1] = r * 128 + (((4 * s + 2 * h + 1) ^ sw) << 4); }
-
-  float f[8];                        // raw A fragment of the next half step, split in place
-  unsigned sh_[4], sm_[4], sl_[4], t0_[4], t1_[4];
-  x6_bf16x8 a[2][3], b[2][NI][3];
-
-  auto read_raw = [&](int kt, int s) {
-    const char* ab = (const char*)lds + (kt % SA) * A_STAGE + w * 4096;
-    const float4 f0 = *(const float4*)(ab + ac[s][0]);
-    const float4 f1 = *(const float4*)(ab + ac[s][1]);
-    f[0] = f0.x; f[1] = f0.y; f[2] = f0.z; f[3] = f0.w; f[4] = f1.x; f[5] = f1.y; f[6] = f1.z; f[7] = f1.w;
-    if (ktail && kt == nk - 1) {
-      const int kb = kt * BK + 16 * s + 8 * h;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) f[j] = kb + j < K ? f[j] : 0.f;
-    }
-  };
-  auto read_b = [&](int kt, int s, int buf) {
-    const uint4* bb = lds + (B_BASE + (kt & 1) * B_STAGE) / 16 + r;
-#pragma unroll
-    for (int j = 0; j < NI; ++j)
-#pragma unroll
-      for (int p = 0; p < 3; ++p) b[buf][j][p] = __builtin_bit_cast(x6_bf16x8, bb[(p * 4 + 2 * s + h) * BN + j * 32]);
-  };
-  // The split of f[] as 44 single-instruction steps (asm volatile: fixed order, never sunk into another block).  Step i
-  // works on pair i & 3, so consecutive steps are independent.
-  auto op = [&](int i) {
-    const int p = i & 3, o = i >> 2;
-    float& x0 = f[2 * p]; float& x1 = f[2 * p + 1];
-    if (o == 0) asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(sh_[p]) : "v"(x0), "v"(x1));
-    if (o == 1) asm volatile("v_lshlrev_b32 %0, 16, %1" : "=v"(t0_[p]) : "v"(sh_[p]));
-    if (o == 2) asm volatile("v_and_b32 %0, 0xffff0000, %1" : "=v"(t1_[p]) : "v"(sh_[p]));
-    if (o == 3) asm volatile("v_sub_f32 %0, %0, %1" : "+v"(x0) : "v"(t0_[p]));
-    if (o == 4) asm volatile("v_sub_f32 %0, %0, %1" : "+v"(x1) : "v"(t1_[p]));
-    if (o == 5) asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(sm_[p]) : "v"(x0), "v"(x1));
-    if (o == 6) asm volatile("v_lshlrev_b32 %0, 16, %1" : "=v"(t0_[p]) : "v"(sm_[p]));
-    if (o == 7) asm volatile("v_and_b32 %0, 0xffff0000, %1" : "=v"(t1_[p]) : "v"(sm_[p]));
-    if (o == 8) asm volatile("v_sub_f32 %0, %0, %1" : "+v"(x0) : "v"(t0_[p]));
-    if (o == 9) asm volatile("v_sub_f32 %0, %0, %1" : "+v"(x1) : "v"(t1_[p]));
-    if (o == 10) asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(sl_[p]) : "v"(x0), "v"(x1));
-  };
-  auto commit = [&](int buf) {
-    a[buf][0] = __builtin_bit_cast(x6_bf16x8, uint4{sh_[0], sh_[1], sh_[2], sh_[3]});
-    a[buf][1] = __builtin_bit_cast(x6_bf16x8, uint4{sm_[0], sm_[1], sm_[2], sm_[3]});
-    a[buf][2] = __builtin_bit_cast(x6_bf16x8, uint4{sl_[0], sl_[1], sl_[2], sl_[3]});
-  };
-  // One half step (16 deep): the MFMAs of buffer `cur`; in their gaps the NEXT half step's (stage nkt, half ns) B fragments
-  // are read and its raw A fragment (read at the top) is split into buffer cur ^ 1.
-  constexpr int SLOTS = 6 * NI, OPS_PER = (44 + SLOTS - 2) / (SLOTS - 1);
-  auto half = [&](int cur, bool has_next, int nkt, int ns) {
-    const uint4* bb = lds + (B_BASE + (nkt & 1) * B_STAGE) / 16 + r;
-    if (has_next) read_raw(nkt, ns);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int j = 0; j < NI; ++j) {
-#pragma unroll
-      for (int t = 0; t < 6; ++t) {
-        const int si = j * 6 + t;
-        // small terms first, the hi*hi product into its own accumulator
-        if (t == 0) accs[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[cur][2], b[cur][j][0], accs[j], 0, 0, 0);
-        if (t == 1) accs[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[cur][0], b[cur][j][2], accs[j], 0, 0, 0);
-        if (t == 2) accs[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[cur][1], b[cur][j][1], accs[j], 0, 0, 0);
-        if (t == 3) accs[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[cur][1], b[cur][j][0], accs[j], 0, 0, 0);
-        if (t == 4) accs[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[cur][0], b[cur][j][1], accs[j], 0, 0, 0);
-        if (t == 5) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[cur][0], b[cur][j][0], acc[j], 0, 0, 0);
-        if (has_next) {
-          if (si < 3 * NI) {
-            const int jj = si / 3, pp = si % 3;
-            b[cur ^ 1][jj][pp] = __builtin_bit_cast(x6_bf16x8, bb[(pp * 4 + 2 * ns + h) * BN + jj * 32]);
-          }
-          if (si >= 1) {
-#pragma unroll
-            for (int o = 0; o < OPS_PER; ++o) { const int i = (si - 1) * OPS_PER + o; if (i < 44) op(i); }
-          }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    if (has_next) commit(cur ^ 1);
-  };
-
-  // ---- pipeline.  DMA issue order per wave: [A0] [B0] [A1] [B1] [A2], then per step after the barrier [B kt+2] [A kt+3]:
-  // at the barrier of step kt the wave needs A kt+1 and B kt+1 and may leave A kt+2 (its newest 4 pieces) in flight.
-  dma_a(0); dma_b(0);
-  if (nk > 1) { dma_a(1); dma_b(1); }
-  if (nk > 2) dma_a(2);
-  if (nk > 2) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(8 + BI_MIN) : "memory");
-  else if (nk > 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(4 + BI_MIN) : "memory");
-  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  read_raw(0, 0); read_b(0, 0, 0);
-#pragma unroll
-  for (int i = 0; i < 44; ++i) op(i);
-  commit(0);
-  for (int kt = 0; kt + 1 < nk; ++kt) {
-    half(0, true, kt, 1);                        // s = 0 on buffer 0; fetches and splits (kt, s = 1) into buffer 1
-    if (kt + 2 < nk) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (kt + 2 < nk) dma_b(kt + 2);
-    if (kt + 3 < nk) dma_a(kt + 3);
-    half(1, true, kt + 1, 0);                    // s = 1 on buffer 1; fetches and splits (kt+1, s = 0) into buffer 0
-  }
-  half(0, true, nk - 1, 1);
-  half(1, false, 0, 0);
-
-  // X6_BNBWD: the producer's y values of this lane's 16 rows x NI columns are fetched NOW, ahead of the tile's stores and the
-  // barrier, so that their latency is off the workgroup's tail
-  float yv[EPI == X6_BNBWD ? NI : 1][16];
-  float pav[NI], pcv[NI], pmv[NI], piv[NI];
-  if (EPI == X6_BNBWD) {
-    const int rbase = m0 + 32 * w;
-#pragma unroll
-    for (int j = 0; j < NI; ++j) {
-      const int n = n0 + j * 32 + r;
-      pav[j] = pcv[j] = pmv[j] = piv[j] = 0.f;
-#pragma unroll
-      for (int q = 0; q < 16; ++q) yv[j][q] = 0.f;
-      if (n < N && (!PARTIAL || j * 32 + r < BN)) {
-        const int pq = n / g.pco, pi = n - pq * g.pco;
-        const size_t po = (size_t)pq * g.pco + pi;
-        pav[j] = g.pa[po]; pcv[j] = g.pc[po]; pmv[j] = g.pmean[po]; piv[j] = g.pinvstd[po];
-        const float* yp = g.py + ((size_t)pq * M + rbase) * (size_t)g.pco + pi;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-          const int row = (q & 3) + 8 * (q >> 2) + 4 * h;
-          if (rbase + row < M) yv[j][q] = yp[(size_t)row * g.pco];
-        }
-      }
-    }
-  }
-  // ---- epilogue.  Block j, register q: row 32 w + (q & 3) + 8 (q >> 2) + 4 h, column 32 j + r
-  float* C = g.C + (size_t)z * g.c_bstride;
-#pragma unroll
-  for (int j = 0; j < NI; ++j)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc[j][q] += accs[j][q];
-  if (g.ksplit > 1) {
-    // split-K: the partial goes out in register order (element (j, q) of thread tid at (j * 16 + q) * 256 + tid: every store
-    // instruction of a wave is one 256-byte run).  Hand-off without cache-wide fences (an agent-scope release writes the whole
-    // L2 back: measured 57-150 us per launch in this place): every payload store is write-through (relaxed agent-scope atomic
-    // store = sc1), every storing wave drains its stores, the workgroup meets, ONE lane counts the arrival; the last arrival
-    // reads all partials with sc1 loads (they bypass this CU's L1, the only cache that could hold a stale copy).
-    const size_t tile_id = ((size_t)z * g.mtiles + tm) * g.ntiles + tn;
-    typedef __attribute__((address_space(1))) float gfloat;
-    typedef __attribute__((address_space(1))) unsigned gu32;
-    gfloat* mine = (gfloat*)(g.part + (tile_id * g.ksplit + ks) * (size_t)(NI * 16 * 256));
-    gu32* cnt = (gu32*)(g.cnt + tile_id);
-#pragma unroll
-    for (int j = 0; j < NI; ++j)
-#pragma unroll
-      for (int q = 0; q < 16; ++q) __hip_atomic_store(mine + (j * 16 + q) * 256 + tid, acc[j][q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    unsigned* flag = reinterpret_cast<unsigned*>(lds);
-    if (tid == 0) *flag = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    if (*flag != (unsigned)(g.ksplit - 1)) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");          // no instruction: keeps the loads below the count
-    if (tid == 0) __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // re-armed for the next launch
-    const gfloat* all = (const gfloat*)(g.part + tile_id * g.ksplit * (size_t)(NI * 16 * 256));
-#pragma unroll
-    for (int j = 0; j < NI; ++j)
-#pragma unroll
-      for (int q = 0; q < 16; ++q) acc[j][q] = 0.f;
-    for (int s2 = 0; s2 < g.ksplit; ++s2) {                         // range order: the same bits whoever arrives last
-      const gfloat* ps = all + (size_t)s2 * (NI * 16 * 256) + tid;
-#pragma unroll
-      for (int j = 0; j < NI; ++j)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc[j][q] += __hip_atomic_load(ps + (j * 16 + q) * 256, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-  if constexpr (EPI == X6_STORE_NCHW) {
-    // registers 4 qg .. 4 qg + 3 of a block are four consecutive tokens of ONE channel: 16 contiguous bytes of the (image,
-    // channel, token) tensor.  Tokens per image and M are multiples of 4, so a group never crosses an image and is stored or
-    // skipped as a whole.  Same values as X6_STORE (the residual is read token-major and added in the same order).
-#pragma unroll
-    for (int j = 0; j < NI; ++j) {
-      const int n = n0 + j * 32 + r;
-      const bool mine = n < N && (!PARTIAL || j * 32 + r < BN);
-#pragma unroll
-      for (int qg = 0; qg < 4; ++qg) {
-        const int m = m0 + 32 * w + 8 * qg + 4 * h;
-        if (m < M && mine) {
-          float4 v = make_float4(acc[j][4 * qg], acc[j][4 * qg + 1], acc[j][4 * qg + 2], acc[j][4 * qg + 3]);
-          if (g.add) {
-            const float* ap = g.add + (size_t)z * g.c_bstride + (size_t)m * g.ldc + n;
-            v.x += ap[0]; v.y += ap[g.ldc]; v.z += ap[2 * (size_t)g.ldc]; v.w += ap[3 * (size_t)g.ldc];
-          }
-          const int img = m / g.nchw_n, tok = m - img * g.nchw_n;
-          *reinterpret_cast<float4*>(C + ((size_t)img * g.nchw_c + n) * g.nchw_n + tok) = v;
-        }
-      }
-    }
-    return;
-  }
-#pragma unroll
-  for (int j = 0; j < NI; ++j) {
-    const int n = n0 + j * 32 + r;
-    const bool mine = n < N && (!PARTIAL || j * 32 + r < BN);
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int m = m0 + 32 * w + (q & 3) + 8 * (q >> 2) + 4 * h;
-      if (m < M && mine) {
-        float v = acc[j][q];
-        if (EPI == X6_STORE && g.add) v += g.add[(size_t)z * g.c_bstride + (size_t)m * g.ldc + n];
-        C[(size_t)m * g.ldc + n] = v;
-      }
-    }
-  }
-  if (EPI == X6_BNBWD) {
-    // Backward statistics of the PRODUCER's BN (see X6Args): per lane the 16 rows of its column, y read with the same
-    // 128-byte row segments the tile was stored with; the two half-waves and the four waves are combined through LDS in
-    // fp64 and leave ONE atomic pair per column and tile, like the forward statistics below.
-    __syncthreads();                                   // every wave is done with the DMA rings
-    float* red = reinterpret_cast<float*>(lds);        // [4 waves][BN][2]
-    const int rbase = m0 + 32 * w;
-#pragma unroll
-    for (int j = 0; j < NI; ++j) {
-      const int n = n0 + j * 32 + r;
-      float s0 = 0.f, s1 = 0.f;
-      if (n < N && (!PARTIAL || j * 32 + r < BN)) {
-        const float av = pav[j], cv = pcv[j], mv = pmv[j], iv = piv[j];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-          const int row = (q & 3) + 8 * (q >> 2) + 4 * h;
-          float dz = rbase + row < M ? acc[j][q] : 0.f;
-          if (g.pact == 1) dz *= gelu_grad_f(__builtin_fmaf(av, yv[j][q], cv));
-          s0 += dz;
-          s1 += dz * ((yv[j][q] - mv) * iv);
-        }
-      }
-      s0 += __shfl_xor(s0, 32);
-      s1 += __shfl_xor(s1, 32);
-      if (h == 0 && (!PARTIAL || j * 32 + r < BN)) { float* o = red + ((w * BN) + j * 32 + r) * 2; o[0] = s0; o[1] = s1; }
-    }
-    __syncthreads();
-    if (tid < BN && n0 + tid < N) {
-      double t0 = 0.0, t1 = 0.0;
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) { t0 += (double)red[(rg * BN + tid) * 2]; t1 += (double)red[(rg * BN + tid) * 2 + 1]; }
-      const int n = n0 + tid, pq = n / g.pco, pi = n - pq * g.pco;
-      double* sz = g.psums + (size_t)pq * 2 * g.pco + pi;
-      __hip_atomic_fetch_add(sz, t0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_fetch_add(sz + g.pco, t1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    return;
-  }
-  if (EPI != X6_BNSTATS) return;
-
-  // Train-mode BN statistics of the tile's columns (as gkg_gemm.hip's epilogue): per wave (its 32 rows) centred
-  // (mean, M2) from registers, Chan-merged over the four waves in fp64, then ONE fp64 atomic pair per column and tile:
-  // S += n mean, Q += M2 + n mean^2.  No workgroup waits for another.
-  __syncthreads();                                   // every wave is done with the DMA rings
-  float* red = reinterpret_cast<float*>(lds);        // [4 waves][BN][2]
-  const int rbase = m0 + 32 * w;
-  const int cnt = max(0, min(32, M - rbase));
-#pragma unroll
-  for (int j = 0; j < NI; ++j) {
-    float s = 0.f;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) s += rbase + (q & 3) + 8 * (q >> 2) + 4 * h < M ? acc[j][q] : 0.f;
-    s += __shfl_xor(s, 32);
-    const float mean = cnt > 0 ? s / (float)cnt : 0.f;
-    float m2 = 0.f;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const float d = acc[j][q] - mean;
-      m2 += rbase + (q & 3) + 8 * (q >> 2) + 4 * h < M ? d * d : 0.f;
-    }
-    m2 += __shfl_xor(m2, 32);
-    if (h == 0 && (!PARTIAL || j * 32 + r < BN)) { float* o = red + ((w * BN) + j * 32 + r) * 2; o[0] = mean; o[1] = m2; }
-  }
-  __syncthreads();
-  if (tid < BN && n0 + tid < N) {
-    double n = 0.0, mean = 0.0, m2 = 0.0;
-#pragma unroll
-    for (int rg = 0; rg < 4; ++rg) {
-      const int c = max(0, min(32, M - (m0 + rg * 32)));
-      x6_chan_merge(n, mean, m2, (double)c, (double)red[(rg * BN + tid) * 2], (double)red[(rg * BN + tid) * 2 + 1]);
-    }
-    double* sz = g.sums + ((size_t)(tm % g.nslots) * g.nbatch + z) * 2 * N + n0 + tid;
-    __hip_atomic_fetch_add(sz, n * mean, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_fetch_add(sz + N, m2 + n * mean * mean, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  if (slots) *slots = n;
+  return hipSuccess;
 }
 
-template <int NI, int EPI, int BN = 32 * NI>
-static hipError_t x6_launch_ni(X6Args a, int nb, hipStream_t st) {
+// The launch rule of the walk form — ONE function for the launch and for gkg_x6_walk_workgroups: the grid (workgroups) of the walk
+// launch for `units` row blocks (batches folded in) of `ntiles` column tiles on `slots` resident workgroups, or 0: one tile per
+// workgroup.  The longest XCD sequence (ceil(units / 8) row blocks) needs `rounds` rounds of the slots of one XCD.
+//   * Walks when rounds == 2.  All workgroups of such a launch start together, so both workgroups of a CU are in their prologue
+//     and in their epilogue at the same time, twice; walking, the second tile's first stages land under the first tile's
+//     epilogue (cfg2's grouped 4 x (10 368 x 160 -> 160) products, 972 tiles: 26.7 -> 24.2 and 25.1 -> 21.4 us in the replayed
+//     step, profiles/r11_bench_cfg2_graph_steps.txt).  From three rounds on the hardware dispatcher has de-phased the two
+//     workgroups of a CU — one fills its rings while the other multiplies — and re-balances at every workgroup end, which a
+//     static list cannot: walking everything made cfg2ref / stage3 / cfg4 0.9-2 % SLOWER (profiles/r11_x6_tile_walk_ab.txt).
+//   * The sequence is cut into EQUAL shares: 123 entries on 64 slots are 62 workgroups of 2 (one of 1), not 64 + 59.
+//   * GKG_X6_FORCE_WALK (tests, measurement): whatever the rounds; its cap field c > 0: at most 8 c workgroups.
+static int x6_walk_grid(long long units, int ntiles, int ksplit, int slots, unsigned flags) {
+  if (ksplit > 1 || (flags & GKG_X6_NO_WALK)) return 0;
+  const bool force = (flags & GKG_X6_FORCE_WALK) != 0;
+  const long long seq = (units + 7) / 8 * ntiles, per_xcd = slots / 8;
+  const long long rounds = (seq + per_xcd - 1) / per_xcd;
+  if (!force && rounds != 2) return 0;
+  long long w = (seq + rounds - 1) / rounds;
+  const long long cap = (flags >> GKG_X6_WALK_CAP_SHIFT) & GKG_X6_WALK_CAP_MASK;
+  if (force && cap > 0 && w > cap) w = cap;
+  return (int)(w * 8);
+}
+
+template <int NI, int EPI, int BN = 32 * NI, bool WALKABLE = false>
+static hipError_t x6_launch_ni(X6Args a, int nb, hipStream_t st, unsigned flags = 0) {
   a.mtiles = (a.M + 127) / 128;
   a.ntiles = (a.N + BN - 1) / BN;
   if (a.ksplit < 1) a.ksplit = 1;
-  // A ring + two B stages (+ slack: the unused lanes of a partial last block read past their image row)
-  const size_t sh = 3 * 4 * 4096 + 2 * 12 * BN * 16 + (BN != 32 * NI ? 512 : 0);
-  // the attribute is per DEVICE (a per-process guard left a second GPU of the same process without it — ADVICE r3)
-  static bool once[64] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !once[dev]) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_x6_kernel<NI, EPI, BN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64) once[dev] = true;
+  if constexpr (WALKABLE) {
+    if (a.ksplit == 1 && !(flags & GKG_X6_NO_WALK)) {
+      const size_t shw = x6_ring_bytes(NI, BN) + (EPI == X6_BNSTATS ? 4 * BN * 2 * 4 : 0);      // + the epilogue's own LDS
+      int slots = 0;
+      hipError_t e = x6_kernel_setup<NI, EPI, BN, true>(shw, &slots);
+      if (e != hipSuccess) return e;
+      if (const int grid = x6_walk_grid((long long)nb * a.mtiles, a.ntiles, a.ksplit, slots, flags); grid > 0) {
+        a.walk_nb = nb;
+        hipLaunchKernelGGL((gemm_x6_walk_kernel<NI, EPI, BN>), dim3(grid), dim3(256), shw, st, a);
+        return hipGetLastError();
+      }
+    }
   }
+  const size_t sh = x6_ring_bytes(NI, BN);
+  hipError_t e = x6_kernel_setup<NI, EPI, BN, false>(sh, nullptr);
+  if (e != hipSuccess) return e;
   const int groups = (a.mtiles + 7) / 8;
   hipLaunchKernelGGL((gemm_x6_kernel<NI, EPI, BN>), dim3(groups * 8 * a.ntiles * a.ksplit, nb), dim3(256), sh, st, a);
   return hipGetLastError();
@@ -835,6 +543,14 @@ static bool x6_ks_form(int M, int N, int nb, bool has_ws, unsigned flags) {
          ((flags & GKG_X6_FORCE_KS) || (nb == 1 && N <= 640));
 }
 
+// The cross-workgroup split of the contraction for the 128-row tile kernel (x6_launch's comment): ranges per tile, < 2: none.
+static int x6_tile_ksplit(long long base2, int nk_total, bool has_ws) {
+  if (!has_ws || base2 >= 320 || nk_total < 8) return 1;
+  int ks = (int)(X6_SK_MAX_WG / base2);
+  if (ks > nk_total / 4) ks = nk_total / 4;
+  return ks > 8 ? 8 : ks;
+}
+
 template <int EPI>
 static hipError_t x6_launch(X6Args a, int nb, hipStream_t st, void* sk_ws = nullptr, size_t sk_bytes = 0, unsigned flags = 0) {
   GkgProfScope prof(GKG_PROF_GEMM_X6, st, 2.0 * a.M * a.N * a.K * nb);
@@ -862,22 +578,17 @@ static hipError_t x6_launch(X6Args a, int nb, hipStream_t st, void* sk_ws = null
       return x6_launch_ks<EPI, 1>(a, nb, st);
     }
   }
-  if (sk_ws && sk_bytes >= X6_SK_BYTES && base2 < 320 && base2 <= 1024 && nk_total >= 8) {
-    int ks = (int)(X6_SK_MAX_WG / base2);
-    if (ks > nk_total / 4) ks = nk_total / 4;
-    if (ks > 8) ks = 8;
-    if (ks >= 2) {
-      a.kper = (nk_total + ks - 1) / ks;
-      a.ksplit = (nk_total + a.kper - 1) / a.kper;               // no empty range
-      a.cnt = reinterpret_cast<unsigned*>(sk_ws);
-      a.part = reinterpret_cast<float*>(reinterpret_cast<char*>(sk_ws) + X6_SK_CNT_BYTES);
-      return x6_launch_ni<2, EPI>(a, nb, st);
-    }
+  if (const int ks = x6_tile_ksplit(base2, nk_total, sk_ws && sk_bytes >= X6_SK_BYTES); ks >= 2) {
+    a.kper = (nk_total + ks - 1) / ks;
+    a.ksplit = (nk_total + a.kper - 1) / a.kper;               // no empty range
+    a.cnt = reinterpret_cast<unsigned*>(sk_ws);
+    a.part = reinterpret_cast<float*>(reinterpret_cast<char*>(sk_ws) + X6_SK_CNT_BYTES);
+    return x6_launch_ni<2, EPI>(a, nb, st);
   }
   if constexpr (EPI == X6_BNBWD) {
     if (a.add) return hipErrorInvalidValue;              // the tile body's statistics epilogue takes no residual (never dropped silently)
   }
-  int ni = base2 < 160 ? 1 : 2;
+  int ni = base2 < 160 && !(flags & GKG_X6_FORCE_WALK) ? 1 : 2;       // (the walk form exists for 64-column tiles: same bits)
   // 80 output columns on many rows (GKGNet-576 stage 1): ONE 80-column tile per row block instead of a full and a quarter
   // 64-column tile — 663 552 rows: 80 -> 80 171 -> 133 us, + statistics 208 -> 161, 320 -> 80 345 -> 279, dgrad 320 <- 80
   // 351 -> 279.  Wider outputs measured equal or slower on 80-column tiles (160: +-3 %, 320 / 400 / 640: 3-8 % slower:
@@ -888,7 +599,11 @@ static hipError_t x6_launch(X6Args a, int nb, hipStream_t st, void* sk_ws = null
     if (a.N == 80 && ni == 2) return x6_launch_ni<3, EPI, 80>(a, nb, st);
   }
   if (ni == 1) return x6_launch_ni<1, EPI>(a, nb, st);
-  return x6_launch_ni<2, EPI>(a, nb, st);
+  // Two rounds of resident workgroups: the tile-walk form of the same kernel (x6_walk_grid; GKG_X6_NO_WALK / _FORCE_WALK).  Not with
+  // the BN-backward statistics epilogue: its registers (the y prefetch beside the walk's state) leave the compiler 219 VGPRs and 69
+  // spilled SGPRs for two waves per SIMD, and cfg2's 810-tile launch measured 44.0 -> 47.8 us walking — the flags do nothing there.
+  if constexpr (EPI == X6_BNBWD) return x6_launch_ni<2, EPI>(a, nb, st);
+  else return x6_launch_ni<2, EPI, 64, true>(a, nb, st, flags);
 }
 
 // ---- weight gradient ----------------------------------------------------------------------------------------------------
@@ -1588,6 +1303,21 @@ extern "C" int gkg_linear_bn_fwd_x6_sk(const float* x, int ldx, size_t x_bstride
     return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_bn_fwd_x6_sk: need a 16-byte aligned workspace of gkg_x6_splitk_workspace_bytes() bytes (or NULL: no split)");
   return x6_fwd_impl(x, ldx, x_bstride, planes_fwd, y, R, cin, cout, nb, train, gamma, beta, bias, running_mean, running_var,
                      num_batches_tracked, bn_a, bn_c, bn_mean, bn_invstd, momentum, eps, stats, splitk_ws, splitk_bytes, stream, flags);
+}
+
+// Workgroups of the tile-walk launch that y (nb, R, cout) = x (nb, R, cin) W^T takes on the current device with these flags and
+// with / without a split-K workspace — x6_launch's rules, for callers and tests that must know the launch form beforehand; 0: the
+// launch does not walk (another body, a split contraction, not two rounds, GKG_X6_NO_WALK); < 0: error.
+extern "C" int gkg_x6_walk_workgroups(int R, int cin, int cout, int nb, int has_ws, unsigned flags) {
+  if (R <= 0 || x6_bad_dim(cin) || x6_bad_dim(cout) || nb <= 0 || nb > 64) return gkg_fail(GKG_ERR_SHAPE, "gkg_x6_walk_workgroups: bad shape");
+  const int mt = (R + 127) / 128, nt = (cout + 63) / 64;
+  const long long base2 = (long long)mt * nt * nb;
+  if (x6_ks_form(R, cout, nb, has_ws != 0, flags) || x6_tile_ksplit(base2, (cin + 31) / 32, has_ws != 0) >= 2) return 0;
+  if ((base2 < 160 && !(flags & GKG_X6_FORCE_WALK)) || cout == 80) return 0;          // 32- / 80-column tiles: one-tile form only
+  int slots = 0;
+  hipError_t e = x6_kernel_setup<2, X6_STORE, 64, true>(x6_ring_bytes(2, 64), &slots);
+  if (e != hipSuccess) return gkg_fail_hip(e, "gkg_x6_walk_workgroups");
+  return x6_walk_grid((long long)nb * mt, nt, 1, slots, flags);
 }
 
 // dx (nb, R, cin) = dy (nb, R, cout; row pitch ldg, batch stride g_bstride) * w, the weights given as dgrad planes.

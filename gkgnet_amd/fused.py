@@ -72,6 +72,8 @@ DETERMINISTIC = os.environ.get("GKG_DETERMINISTIC", "0") != "0"
 #                  a Grapher's dx stored channel-major by its input-gradient GEMM (BWD_FUSE below)
 #   dgrad_stats    backward: BN statistics taken by the input-gradient GEMM that writes the layer's upstream gradient, at every
 #                  size (DGRAD_STATS below; bwd_fuse off switches it off too)
+#   x6_walk        projection launches of two rounds of resident workgroups as one round of workgroups that each walk a static
+#                  list of tiles (X6_WALK below; csrc/gkg_gemm_x6_tile.h)
 _DISABLED = _env_list("GKG_DISABLE")
 _ENABLED = _env_list("GKG_ENABLE")
 KNN_BF16 = "knn_bf16" in _ENABLED
@@ -289,7 +291,7 @@ def _dgrad_x6(lib, dY, ldg, g_bs, pd, dx, R, cin, cout, nb, residual=None, ldx=0
     pitch / batch stride of dx (0: contiguous (nb, R, cin)) — the grouped projection writes dXM (R, 2C) with (2C, C/2)."""
     ws = _sk_ws(dY.device)
     _lib.check(lib.gkg_linear_dgrad_x6_sk(_ptr(dY), ldg, g_bs, _ptr(pd), _ptr(dx), R, cin, cout, nb, _ptr(residual), _ptr(ws),
-                                          ws.numel(), ldx, x_bs, 0, _stream()), "gkg_linear_dgrad_x6")
+                                          ws.numel(), ldx, x_bs, _x6_flags(), _stream()), "gkg_linear_dgrad_x6")
 
 
 def _grad_outs(gparams, wshape, nch, dev):
@@ -318,7 +320,7 @@ def _linear_fwd_own(lib, x, W, bias, bn, R, cin, cout, nb, planes, xld=None, xbs
     def fwd(xp, wp, yp, R_, cin_, cout_, nb_, *rest):
         ws = _sk_ws(dev)
         return lib.gkg_linear_bn_fwd_x6_sk(xp, cin_ if xld is None else xld, R_ * cin_ if xbs is None else xbs, _ptr(planes), yp,
-                                           R_, cin_, cout_, nb_, *rest[:-1], _ptr(ws), ws.numel(), 0, rest[-1])
+                                           R_, cin_, cout_, nb_, *rest[:-1], _ptr(ws), ws.numel(), _x6_flags(), rest[-1])
     Y = torch.empty((nb, R, cout) if nb > 1 else (R, cout), dtype=_F32, device=dev)
     a = torch.empty(nb * cout, dtype=_F32, device=dev)
     c = torch.empty_like(a)
@@ -562,7 +564,7 @@ def _train_apply_from_sums(lib, x, W, bias, bn, R, cin, cout, nb, planes, res, o
             ws = _sk_ws(dev)
             rc = lib.gkg_linear_bn_fwd_x6_sk(_ptr(x), cin if xld is None else xld, R * cin if xbs is None else xbs, _ptr(planes),
                                              _ptr(Y), R, cin, cout, nb, 2, *none10, 0.0, 0.0,
-                                             _ptr(cur), _ptr(ws), ws.numel(), 0, _stream())
+                                             _ptr(cur), _ptr(ws), ws.numel(), _x6_flags(), _stream())
         _lib.check(rc, "gkg_linear_bn_fwd_x6 (statistics only)")
         a, c, mean, invstd = torch.empty((4, nb * cout), dtype=_F32, device=dev).unbind(0)     # one allocation
         track = bn.training and bn.track_running_stats
@@ -641,12 +643,21 @@ BWD_FUSE = "bwd_fuse" not in _DISABLED
 # DropPath scale and sums beyond the scratch (the conditions of _bn_link), and with GKG_DISABLE=dgrad_stats — BN_EPILOGUE_MIN_ROWS
 # then decides alone, as before.  The block driver folds the same four (GKG_BLOCK_NO_DGRAD_STATS: off).
 DGRAD_STATS = BWD_FUSE and "dgrad_stats" not in _DISABLED
+# Round 11: the tile-walk form of the 128-row projection kernel, taken by the library where a launch is two rounds of resident
+# workgroups (cfg2: the grouped 4 x (10 368 x 160 -> 160) products, forward and input gradient).  GKG_DISABLE=x6_walk: every projection call carries GKG_X6_NO_WALK (the block driver: GKG_BLOCK_NO_X6_WALK).
+X6_WALK = "x6_walk" not in _DISABLED
+
+
+def _x6_flags() -> int:
+    """The per-call ``flags`` of the projection entry points from the module switches."""
+    return 0 if X6_WALK else _lib.X6_NO_WALK
 
 
 def _block_flags() -> int:
     """GkgGrapherBlock / GkgLabelBlock.bwd_flags from the module switches."""
     return ((0 if BWD_FUSE else _lib.BLOCK_NO_BWD_FUSE)
-            | (0 if (BWD_FUSE and DGRAD_STATS and BN_EPILOGUE) else _lib.BLOCK_NO_DGRAD_STATS))
+            | (0 if (BWD_FUSE and DGRAD_STATS and BN_EPILOGUE) else _lib.BLOCK_NO_DGRAD_STATS)
+            | (0 if X6_WALK else _lib.BLOCK_NO_X6_WALK))
 
 
 def _bwd_fuse_ok(mean, sync, scale, nb, co) -> bool:
@@ -723,7 +734,7 @@ def _dgrad_x6_with_link(lib, dY, pd, R, cin, cout, link, residual=None):
         ws = _sk_ws(dY.device)
         _lib.check(lib.gkg_linear_dgrad_x6_bnbwd_sk(_ptr(dY), cout, _ptr(pd), _ptr(dx), R, cin, cout, _ptr(residual), _ptr(link.Y),
                                                     _ptr(link.a), _ptr(link.c), _ptr(link.mean), _ptr(link.invstd), _ptr(cur),
-                                                    link.nb, link.co, link.act, _ptr(ws), ws.numel(), 0, _stream()),
+                                                    link.nb, link.co, link.act, _ptr(ws), ws.numel(), _x6_flags(), _stream()),
                    "gkg_linear_dgrad_x6_bnbwd_sk")
     scratch.hand_off(link, dx, cur, other, zero)      # the other buffer's clear is deferred to the producer's apply pass
     return dx

@@ -567,6 +567,19 @@ size_t gkg_x6_splitk_workspace_bytes(void);
  * GKG_X6_FORCE_KS takes it for every short matrix. */
 #define GKG_X6_NO_KS 1u
 #define GKG_X6_FORCE_KS 2u
+/* Round 11: a launch of the 128-row tile kernel (64-column tiles, un-split contraction; not the BN-backward statistics epilogue)
+ * that needs exactly TWO rounds of resident workgroups (occupancy x CUs, queried per device) runs as one round of workgroups that
+ * each WALK a static list of tiles, the next tile's first operand stages in flight under the epilogue (csrc/gkg_gemm_x6_tile.h,
+ * gemm_x6_walk_kernel).  Same bits per output element.  Per call (measurement, tests): GKG_X6_NO_WALK never walks,
+ * GKG_X6_FORCE_WALK walks whatever the size, and with it a non-zero cap field
+ * c = (flags >> GKG_X6_WALK_CAP_SHIFT) & GKG_X6_WALK_CAP_MASK launches at most 8 c workgroups. */
+#define GKG_X6_NO_WALK 4u
+#define GKG_X6_FORCE_WALK 8u
+#define GKG_X6_WALK_CAP_SHIFT 8
+#define GKG_X6_WALK_CAP_MASK 255u
+/* Workgroups of the walk launch that gkg_linear_bn_fwd_x6_sk takes for this shape, workspace (0 / 1) and flags on the current
+ * device; 0: that launch does not walk (another kernel body, a split contraction, not two rounds, GKG_X6_NO_WALK); < 0: error. */
+int gkg_x6_walk_workgroups(int R, int cin, int cout, int nb, int has_ws, unsigned flags);
 int gkg_linear_bn_fwd_x6_sk(const float* x, int ldx, size_t x_bstride, const void* planes_fwd, float* y, int R, int cin,
                             int cout, int nb, int train, const float* gamma, const float* beta, const float* bias,
                             float* running_mean, float* running_var, long long* num_batches_tracked, float* bn_a, float* bn_c,
@@ -677,6 +690,9 @@ int gkg_bn_bwd_apply_from_sums(const float* dout, const float* y, const float* a
  * taken in that GEMM's epilogue (gkg_linear_dgrad_x6_bnbwd_sk) and the layer runs its apply pass only: four launches fewer per
  * block pair.  GKG_BLOCK_NO_DGRAD_STATS keeps the stand-alone statistics launches (GKG_BLOCK_NO_BWD_FUSE implies it). */
 #define GKG_BLOCK_NO_DGRAD_STATS 2u
+/* Round 11: every projection launch of the call (forward calls included) with GKG_X6_NO_WALK — the one-tile form of the 128-row
+ * tile kernel whatever the size. */
+#define GKG_BLOCK_NO_X6_WALK 4u
 typedef struct GkgProjBN {
   const void* planes_fwd; const void* planes_dgrad;
   const float* gamma; const float* beta; const float* bias;
