@@ -61,6 +61,14 @@ static size_t gc_ws_layout(int B, int C, int N, int M, int k, char* base, GcWs* 
 }
 
 // ---- transposed graph ---------------------------------------------------------------------------------------------------
+// The counters are cleared by a kernel, not by hipMemsetAsync: every step of the sequence is then a kernel node when the call is
+// captured into a hipGraph (a capture with the two memset nodes between the kernels faulted on replay: EXPERIMENTS.md "GIN / GAT
+// kernels vs fp64").
+__global__ __launch_bounds__(256) void gc_zero_kernel(int* __restrict__ p, long long n) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) p[i] = 0;
+}
+
 __global__ __launch_bounds__(256) void gc_count_kernel(const int64_t* __restrict__ idx, int* __restrict__ cnt, int M, int NK,
                                                        long long E) {
   const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -119,15 +127,13 @@ __global__ __launch_bounds__(256) void gc_sort_kernel(const int* __restrict__ of
 static int gc_transpose(const int64_t* idx, int B, int N, int M, int k, const GcWs& w, hipStream_t st) {
   const int NK = N * k;
   const long long E = (long long)B * NK, BM = (long long)B * M;
-  hipError_t e = hipMemsetAsync(w.cnt, 0, 4 * (size_t)BM, st);
-  if (e != hipSuccess) return gkg_fail_hip(e, "gc_transpose memset");
+  hipLaunchKernelGGL(gc_zero_kernel, dim3((unsigned)((BM + 255) / 256)), dim3(256), 0, st, w.cnt, BM);
   hipLaunchKernelGGL(gc_count_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, idx, w.cnt, M, NK, E);
   hipLaunchKernelGGL(gc_scan_kernel, dim3(B), dim3(256), 0, st, w.cnt, w.off, M);
-  e = hipMemsetAsync(w.cnt, 0, 4 * (size_t)BM, st);                     // the counts become the fill cursors
-  if (e != hipSuccess) return gkg_fail_hip(e, "gc_transpose memset");
+  hipLaunchKernelGGL(gc_zero_kernel, dim3((unsigned)((BM + 255) / 256)), dim3(256), 0, st, w.cnt, BM);   // the counts become the fill cursors
   hipLaunchKernelGGL(gc_fill_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, idx, w.off, w.cnt, w.list, M, NK, E);
   hipLaunchKernelGGL(gc_sort_kernel, dim3((unsigned)((BM + 255) / 256)), dim3(256), 0, st, w.off, w.list, M, NK, BM);
-  e = hipGetLastError();
+  hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : gkg_fail_hip(e, "gc_transpose");
 }
 

@@ -162,7 +162,12 @@ int gkg_edge_bwd(const float* g, const float* qs, const float* qc, const int64_t
  * (edge_index[1][b][n][k] == n, as the k-NN produces it), so edge_index[1] is not an argument.  No (B, C, N, k) tensor is
  * formed, and every backward is bit-identical from run to run: the source gradients are gathers over the transposed graph
  * (built in the workspace, each key's edges in edge order), the parameter gradients fixed-order fp64 reductions.
- *   gkg_gconv_workspace_bytes  workspace the calls below need (0: invalid sizes).
+ *   gkg_gconv_workspace_bytes  workspace the calls below need (0: invalid sizes).  ws: device memory whose base is aligned to 8
+ *                 bytes (it holds int32, fp32 and, at 256-byte offsets, fp64 sections); its contents on entry do not matter (a
+ *                 dirty buffer is fine: every section is written before it is read) and nothing in it outlives the call, so one
+ *                 buffer of the largest size serves forward, backward and any smaller shape in turn.  ws_bytes below the
+ *                 requirement returns GKG_ERR_WORKSPACE with nothing written.  Every launch of a call is a kernel (no memset
+ *                 or copy nodes when the stream is being captured into a hipGraph).
  *   gkg_gin_fwd   h[b][c][n] = (1 + eps[0]) x[b][c][n] + sum_k src[b][c][nn_idx[b][n][k]]   (eps: 1 float in device memory)
  *   gkg_gin_bwd   gx = (1 + eps) gh; gsrc[j] += gh[n] over every edge (gsrc == NULL: into gx, self graph); geps (optional,
  *                 1 double) = sum gh x.  gx, gsrc, geps are fully overwritten.
@@ -171,7 +176,9 @@ int gkg_edge_bwd(const float* g, const float* qs, const float* qc, const int64_t
  *                 backward's input), agg[b][c][n] = sum_k p src[c][nn_idx].
  *   gkg_gat_bwd   g = d agg.  dp = g[n] . src[j], de = p (dp - sum_k p dp); gsrc[j] += p g[n] + de a[C:] (src and gsrc both
  *                 NULL: self graph, into gx); gx[n] += (sum_k de) a[:C]; da (optional, 2C doubles) = [sum (sum_k de) x[n],
- *                 sum de src[j]]; dbias (optional, 1 double) = sum de.  All outputs fully overwritten. */
+ *                 sum de src[j]]; dbias (optional, 1 double) = sum de.  All outputs fully overwritten.  p is an input like any
+ *                 other: any (B, N, k) floats are accepted and used as given (rows need not sum to 1, nothing is recomputed
+ *                 from x, src and a), so the result is the formula above evaluated at that p. */
 size_t gkg_gconv_workspace_bytes(int B, int C, int N, int M, int k);
 int gkg_gin_fwd(const float* x, const float* src, const int64_t* nn_idx, const float* eps, float* h, int B, int C, int N, int M,
                 int k, void* stream);

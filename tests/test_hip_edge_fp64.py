@@ -21,16 +21,14 @@ value at the kernel's argmax must be within the bound of the fp64 maximum, for e
 fp32 operation is exact and everything, argmax included, is compared bit for bit.
 
 Outputs sit between guard bands and are pre-filled; every test asserts the bands untouched."""
-import math
-
 import pytest
 import torch
 
 import edge_ref as E
+from util import Buf
 
 pytestmark = pytest.mark.gpu
 
-G = 64                                   # guard band, elements
 CASES = [(s, q) for s in E.SHAPES for q in (True, False)]
 IDS = ["x".join(map(str, s)) + ("-qc" if q else "-null") for s, q in CASES]
 K255 = (2, 12, 64, 600, 255)
@@ -49,27 +47,6 @@ def _p(t):
 def _st():
     from gkgnet_amd.ops import _stream
     return _stream()
-
-
-class Buf:
-    """An output between two guard bands.  Floats: NaN everywhere (``zero``: the payload cleared); uint8: 255 everywhere."""
-
-    def __init__(self, shape, dtype=torch.float32, zero=False, fill=None):
-        n = math.prod(shape)
-        self.fill = fill if fill is not None else (255 if dtype == torch.uint8 else float("nan"))
-        self.full = torch.full((n + 2 * G,), self.fill, dtype=dtype, device="cuda")
-        self.t = self.full[G:G + n].view(shape)
-        if zero:
-            self.t.zero_()
-
-    def guards_ok(self):
-        lo, hi = self.full[:G], self.full[-G:]
-        if isinstance(self.fill, float) and math.isnan(self.fill):
-            return bool(torch.isnan(lo).all()) and bool(torch.isnan(hi).all())
-        return bool((lo == self.fill).all()) and bool((hi == self.fill).all())
-
-    def cpu(self):
-        return self.t.detach().cpu().clone()
 
 
 def _dev(k):

@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import json
+import math
 import os
 import zlib
 
@@ -93,3 +94,28 @@ def xm_interleaved(XM):
     """XM (T, 2C) -> the reference's interleaved channel order [x_0, m_0, x_1, m_1, ...] (T, 2C) (torch_vertex.py:57-61)."""
     x, m = xm_split(XM)
     return torch.stack([x, m], dim=2).reshape(XM.shape[0], -1)
+
+
+# ---- outputs of C-ABI calls between guard bands ------------------------------------------------------------------------------
+G = 64                                   # guard band, elements
+
+
+class Buf:
+    """An output between two guard bands.  Floats: NaN everywhere (``zero``: the payload cleared); uint8: 255 everywhere."""
+
+    def __init__(self, shape, dtype=torch.float32, zero=False, fill=None):
+        n = math.prod(shape)
+        self.fill = fill if fill is not None else (255 if dtype == torch.uint8 else float("nan"))
+        self.full = torch.full((n + 2 * G,), self.fill, dtype=dtype, device="cuda")
+        self.t = self.full[G:G + n].view(shape)
+        if zero:
+            self.t.zero_()
+
+    def guards_ok(self):
+        lo, hi = self.full[:G], self.full[-G:]
+        if isinstance(self.fill, float) and math.isnan(self.fill):
+            return bool(torch.isnan(lo).all()) and bool(torch.isnan(hi).all())
+        return bool((lo == self.fill).all()) and bool((hi == self.fill).all())
+
+    def cpu(self):
+        return self.t.detach().cpu().clone()
