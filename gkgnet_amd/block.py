@@ -26,7 +26,7 @@ from contextlib import nullcontext
 
 import torch
 
-from . import _abi, _lib, fused, knn_prep
+from . import _abi, _lib, bn_passes, fused, knn_prep
 from .ops import _ptr, _stream
 
 _F32 = torch.float32
@@ -38,11 +38,6 @@ ENABLED = "block_driver" not in fused._DISABLED
 
 
 # ----------------------------------------------------------------------------------------------- eligibility
-def _frozen(bn) -> bool:
-    """A BatchNorm that normalises with its running statistics and does not update them (eval mode, statistics present)."""
-    return (not bn.training and bool(bn.track_running_stats) and bn.running_mean is not None and bn.running_var is not None)
-
-
 def _proj_ok(seq, R, cin, cout, nb, frozen=False) -> bool:
     """One projection + BN in the driver's scope, in train mode or (``frozen``) on its running statistics."""
     conv, bn = seq[0], seq[1]
@@ -51,7 +46,7 @@ def _proj_ok(seq, R, cin, cout, nb, frozen=False) -> bool:
             and (conv.bias is None or conv.bias.dtype == _F32)):
         return False
     if frozen:
-        return (_frozen(bn) and bn.running_mean.dtype == _F32 and bn.running_var.dtype == _F32
+        return (bn_passes.frozen(bn) and bn.running_mean.dtype == _F32 and bn.running_var.dtype == _F32
                 and fused._BnScratch.fits(2 * nb * cout))
     return bn.training and fused._derive_ok(bn, nb, cout, _lib.F32, False)
 
@@ -60,7 +55,7 @@ def _block_mode(bn):
     """The mode every projection of a block must share, read off its first BN: True frozen, False train, None neither."""
     if bn.training:
         return False
-    return True if _frozen(bn) else None
+    return True if bn_passes.frozen(bn) else None
 
 
 def _common_ok(x) -> bool:
@@ -151,11 +146,8 @@ class _Proj:
                   (bn._buffers, "num_batches_tracked", self.nbt)]
 
     def static(self, p: ProjBN):
-        track = self.trs
         p.gamma, p.beta, p.bias = _ptr(self.gamma), _ptr(self.beta), _ptr(self.bias)
-        p.running_mean = _ptr(self.rm) if track else None
-        p.running_var = _ptr(self.rv) if track else None
-        p.nbt = _ptr(self.nbt) if track else None
+        p.running_mean, p.running_var, p.nbt = bn_passes.stats_ptrs(self.bn, self.trs)
         p.momentum, p.eps = float(self.mom), float(self.eps)
         p.cin, p.cout, p.nb = self.cin, self.cout, self.nb
 
@@ -324,10 +316,7 @@ def _proj_fwd(lib, p: ProjBN, pr: _Proj, scratch, keep):
     pf, pd = fused._planes(lib, pr.W, pr.nb, pr.cout, pr.cin, True, True, kperm=pr.kperm)
     p.planes_fwd, p.planes_dgrad = pf.data_ptr(), pd.data_ptr()
     if scratch is not None:                                   # (None: a frozen layer — no statistics pass, nothing written back)
-        if pr.trs:
-            ep = pr.bn.__dict__.get("_gkg_epoch")
-            if ep is not None:
-                pr.bn.__dict__["_gkg_epoch"] = ep + 1         # fused._touch_stats: the kernels update the running statistics
+        bn_passes.touch(pr.bn)                                # the kernels update the running statistics
         cur, other, zero = scratch.acquire(lib, 2 * pr.nch)
         p.fsum, p.fzero, p.fzero_n = cur.data_ptr(), other.data_ptr(), zero
     keep.append(pf)

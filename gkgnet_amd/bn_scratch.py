@@ -10,12 +10,15 @@ from .ops import _stream
 
 
 class _BnLink:
-    """A train-mode BN layer's saved tensors, hung on the tensor it returns: the kernel that writes that tensor's gradient also
-    takes the layer's BN backward statistics and leaves them here (_BnScratch.hand_off / take)."""
-    __slots__ = ("Y", "a", "c", "mean", "invstd", "act", "nb", "co", "R", "ready", "__weakref__")
+    """A BN layer as its passes read it (bn_passes.py): the saved tensors, the sizes, ``sync`` = (group, count) of exchanged
+    statistics and, for a layer on its running statistics (``mean`` None), the module and the conv bias in front of it.  A
+    train-mode layer with rank-local statistics may hang it on the tensor it returns: the kernel that writes that tensor's
+    gradient also takes the layer's BN backward statistics and leaves them here (_BnScratch.hand_off / take)."""
+    __slots__ = ("Y", "a", "c", "mean", "invstd", "act", "nb", "co", "R", "sync", "bn", "bias", "ready", "__weakref__")
 
-    def __init__(self, Y, a, c, mean, invstd, act, nb, co, R):
+    def __init__(self, Y, a, c, mean, invstd, act, nb, co, R, sync=None, bn=None, bias=None):
         self.Y, self.a, self.c, self.mean, self.invstd, self.act, self.nb, self.co, self.R = Y, a, c, mean, invstd, act, nb, co, R
+        self.sync, self.bn, self.bias = sync, bn, bias
         self.ready = None             # (the gradient tensor the sums belong to, its version, cur, other, zero)
 
     def holds_sums(self) -> bool:

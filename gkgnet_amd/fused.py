@@ -28,7 +28,7 @@ import torch
 import torch.distributed as dist
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, bn_passes
 from .ops import _ptr, _stream
 from .parallel import grad_view
 
@@ -83,13 +83,15 @@ from .planes import (_WeightPlanes, _PLANES, _planes, refresh_weight_planes, par
                      mark_parameters_updated)                                                 # planes + staleness: planes.py)
 
 
-def _x6(x, weight, bn, nb=1, kind="fwd") -> bool:
+def _x6(x, weight, bn, nb=1, kind="fwd", group=...) -> bool:
     """This projection GEMM (kind "fwd": y = x W^T, "dgrad": dx = dy W) runs on the x6 kernels.  Eligible: fp32 operands
     outside autocast, batch statistics local to the rank or exchanged in fp64 (_sync_x6_ok), 16-byte aligned rows, the C entry
-    points' size limits (_x6_rule)."""
+    points' size limits (_x6_rule).  ``group``: bn's statistics group when the caller has asked already (_sync_group)."""
     if GEMM_MATH != "x6":
         return False
-    if not (x.dtype == _F32 and weight.dtype == _F32 and not torch.is_autocast_enabled() and _sync_x6_ok(_sync_group(bn))
+    if group is ...:
+        group = _sync_group(bn)
+    if not (x.dtype == _F32 and weight.dtype == _F32 and not torch.is_autocast_enabled() and _sync_x6_ok(group)
             and x.shape[-1] % 4 == 0 and weight.shape[0] % 4 == 0):
         return False
     return _x6_rule(x.shape[-2], x.shape[-1], weight.shape[0] // nb, nb, kind)
@@ -254,10 +256,6 @@ def _wgrad_grouped(dY: torch.Tensor, U: torch.Tensor, out=None, kperm=0) -> torc
     return torch.bmm(dY.transpose(1, 2), U) if out is None else torch.bmm(dY.transpose(1, 2), U, out=out)
 
 
-def _ws(nbytes: int, device) -> torch.Tensor:
-    return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
-
-
 _STATS = {}
 
 
@@ -312,35 +310,33 @@ def _grad_outs(gparams, wshape, nch, dev):
     return w, g, b
 
 
-def _linear_fwd_own(lib, x, W, bias, bn, R, cin, cout, nb, planes, xld=None, xbs=None):
-    """Y, a, c, mean, invstd of BN(x W^T) through gkg_linear_bn_fwd_x6 (statistics in the GEMM epilogue + finalize kernel);
-    ``planes``: the weight's forward bf16 planes; ``xld`` / ``xbs``: row pitch / batch stride of x."""
-    dev = x.device
+def _project_bn(lib, x, planes, geom, mode=0, bn_args=(None,) * 10 + (0.0, 0.0), sums=None):
+    """Y = x W^T on gkg_linear_bn_fwd_x6_sk.  ``geom`` = (R, cin, cout, nb); ``x``: a contiguous (R, cin) matrix or, nb > 1, a
+    (nb, R, cin) tensor read through its strides (the XM operand buffer's groups); ``planes``: the weight's forward bf16 planes.
+    ``mode`` 0: the product alone; 1: BN statistics in the epilogue + the finalize kernel (``bn_args``: gamma .. eps of the entry
+    point, ``sums``: _stats_scratch); 2: the fp64 column sums only, into ``sums`` (a scratch-pair buffer: bn_passes.apply_from_sums
+    reads them)."""
+    R, cin, cout, nb = geom
+    xld, xbs = (x.stride(1), x.stride(0)) if nb > 1 else (cin, R * cin)
+    Y = torch.empty((nb, R, cout) if nb > 1 else (R, cout), dtype=_F32, device=x.device)
+    ws = _sk_ws(x.device)
+    _lib.check(lib.gkg_linear_bn_fwd_x6_sk(_ptr(x), xld, xbs, _ptr(planes), _ptr(Y), R, cin, cout, nb, mode, *bn_args, _ptr(sums),
+                                           _ptr(ws), ws.numel(), _x6_flags(), _stream()),
+               "gkg_linear_bn_fwd_x6 (statistics only)" if mode == 2 else "gkg_linear_bn_fwd")
+    return Y
 
-    def fwd(xp, wp, yp, R_, cin_, cout_, nb_, *rest):
-        ws = _sk_ws(dev)
-        return lib.gkg_linear_bn_fwd_x6_sk(xp, cin_ if xld is None else xld, R_ * cin_ if xbs is None else xbs, _ptr(planes), yp,
-                                           R_, cin_, cout_, nb_, *rest[:-1], _ptr(ws), ws.numel(), _x6_flags(), rest[-1])
-    Y = torch.empty((nb, R, cout) if nb > 1 else (R, cout), dtype=_F32, device=dev)
-    a = torch.empty(nb * cout, dtype=_F32, device=dev)
-    c = torch.empty_like(a)
-    train = bn.training or not bn.track_running_stats
-    if train:
-        mean = torch.empty_like(a)
-        invstd = torch.empty_like(a)
-        track = bn.training and bn.track_running_stats
-        _touch_stats(bn, track)
-        _lib.check(fwd(_ptr(x), _ptr(W), _ptr(Y), R, cin, cout, nb, 1, _ptr(bn.weight), _ptr(bn.bias),
-                                         _ptr(bias), _ptr(bn.running_mean) if track else None,
-                                         _ptr(bn.running_var) if track else None,
-                                         _ptr(bn.num_batches_tracked) if track else None, _ptr(a), _ptr(c), _ptr(mean),
-                                         _ptr(invstd), float(bn.momentum), float(bn.eps), _ptr(_stats_scratch(dev)),
-                                         _stream()), "gkg_linear_bn_fwd")
-        return Y, a, c, mean, invstd
-    _lib.check(fwd(_ptr(x), _ptr(W), _ptr(Y), R, cin, cout, nb, 0, None, None, None, None, None, None,
-                                     None, None, None, None, 0.0, 0.0, None, _stream()), "gkg_linear_bn_fwd")
-    a, c = _bn_eval_ac(lib, bn, bias, nb * cout)
-    return Y, a, c, None, None
+
+def _linear_fwd_own(lib, x, planes, geom, bias, bn):
+    """Y, a, c, mean, invstd of BN(x W^T) through gkg_linear_bn_fwd_x6 (statistics in the GEMM epilogue + finalize kernel); x,
+    planes and geom as _project_bn takes them."""
+    n = geom[2] * geom[3]
+    if not bn_passes.batch_stats(bn):
+        return (_project_bn(lib, x, planes, geom),) + bn_passes.eval_ac(lib, bn, bias, n) + (None, None)
+    a, c, mean, invstd = (torch.empty(n, dtype=_F32, device=x.device) for _ in range(4))
+    Y = _project_bn(lib, x, planes, geom, 1, (_ptr(bn.weight), _ptr(bn.bias), _ptr(bias), *bn_passes.running_stats(bn), _ptr(a),
+                                              _ptr(c), _ptr(mean), _ptr(invstd), float(bn.momentum), float(bn.eps)),
+                    _stats_scratch(x.device))
+    return Y, a, c, mean, invstd
 
 
 def lowp_inference() -> bool:
@@ -460,7 +456,10 @@ def to_token_major(x):
 
 
 
-# ----------------------------------------------------------------------------------------------- BN helpers
+# ----------------------------------------------------------------------------------------------- BN: the policy
+# Which launch sequence a BN layer's forward and backward take is decided here — the switches above and below, and the predicates
+# _sync_group, _sync_x6_ok, _derive_ok, _bwd_fuse_ok, _bn_link, _bn_scale_in_kernel; the sequences themselves, every gkg_bn_* call
+# and the record they read a layer from are bn_passes.py's, which gets the answers as arguments (``group``, ``atomic``).
 def _sync_group(bn):
     """The process group this BN exchanges its batch statistics over (SyncBatchNorm in training under an
     initialised multi-rank group: the reference's DDP semantics), or None for local statistics."""
@@ -477,134 +476,25 @@ def _sync_x6_ok(group) -> bool:
     return group is None or (GEMM_MATH == "x6" and not DETERMINISTIC)
 
 
-def _touch_stats(bn, track):
-    """The kernels about to run update bn's running statistics through raw pointers: invalidate what was derived from them."""
-    if track and hasattr(bn, "_gkg_epoch"):
-        bn._gkg_epoch += 1
+from .bn_scratch import _BnLink, _BnScratch      # noqa: E402  (the layer record + fp64 column-sum scratch of the two-launch BN passes)
 
 
-def _bn_eval_ac(lib, bn, bias, n):
-    """(a, c) of an eval-mode BN folded with the conv bias: out = a*Y + c.  Cached on the module and recomputed (one
-    small kernel) only when one of the tensors it derives from changed — an inference forward launched it per layer."""
-    srcs = [bn.weight, bn.bias, bn.running_mean, bn.running_var] + ([bias] if bias is not None else [])
-    epoch = getattr(bn, "_gkg_epoch", None)
-    key = tuple((param_version(t), t.data_ptr()) for t in srcs) + (bn.eps, n, epoch)
-    ent = getattr(bn, "_gkg_eval_ac", None)
-    if ent is None or ent[0] != key or epoch is None or torch.is_grad_enabled():
-        a = torch.empty(n, dtype=_F32, device=bn.weight.device)
-        c = torch.empty_like(a)
-        _lib.check(lib.gkg_bn_eval_affine(_ptr(bn.weight), _ptr(bn.bias), _ptr(bias), _ptr(bn.running_mean),
-                                          _ptr(bn.running_var), _ptr(a), _ptr(c), n, float(bn.eps), _stream()),
-                   "gkg_bn_eval_affine")
-        if torch.is_grad_enabled() or epoch is None:
-            return a, c
-        ent = (key, a, c)
-        bn._gkg_eval_ac = ent
-    return ent[1], ent[2]
+def _project_apply(lib, x, planes, geom, bias, bn, group, dest, out_tm=None, prep=None):
+    """Projection (statistics in its epilogue: _project_bn mode 2) -> BN-apply straight from the fp64 sums
+    (bn_passes.apply_from_sums, which takes ``group`` .. ``prep``): two launches in one scope of the scratch pair, no finalize
+    kernel -> (Y, a, c, mean, invstd, sync).  With a statistics group the row count rides in the double behind the sums."""
+    R, _, cout, nb = geom
+    with _BnScratch.of(x.device).scoped(lib, 2 * nb * cout + (group is not None)) as sums:
+        Y = _project_bn(lib, x, planes, geom, 2, sums=sums[0])
+        return (Y,) + bn_passes.apply_from_sums(lib, Y, sums, bn, bias, group, (R, cout, nb), dest, out_tm, prep)
 
 
-def _bn_forward_params(lib, Y, bn, bias, R, C, nb):
-    """Returns (a, c, mean, invstd, sync) for out = a*Y + c; updates running statistics in train mode.
-    ``sync`` is None (local statistics) or (group, count): the statistics were summed over the ranks of ``group``
-    (one all-reduce of the column sums, sums of squares and the row count) and ``count`` is the device scalar
-    holding the total number of rows — the backward needs both."""
-    dev = Y.device
-    a = torch.empty(nb * C, dtype=_F32, device=dev)
-    c = torch.empty_like(a)
-    if bn.training or not bn.track_running_stats:
-        mean = torch.empty_like(a)
-        invstd = torch.empty_like(a)
-        ws = _ws(lib.gkg_bn_workspace_bytes(R, C, nb), dev)
-        track = bn.training and bn.track_running_stats
-        _touch_stats(bn, track)
-        rm = _ptr(bn.running_mean) if track else None
-        rv = _ptr(bn.running_var) if track else None
-        nbt = _ptr(bn.num_batches_tracked) if track else None
-        group = _sync_group(bn)
-        if group is None:
-            _lib.check(lib.gkg_bn_train_stats(_ptr(Y), _ptr(bn.weight), _ptr(bn.bias), _ptr(bias), rm, rv,
-                                              _ptr(a), _ptr(c), _ptr(mean), _ptr(invstd), R, C, nb,
-                                              float(bn.momentum), float(bn.eps), nbt, _ptr(ws), ws.numel(), _stream()),
-                       "gkg_bn_train_stats")
-            return a, c, mean, invstd, None
-        buf = torch.empty(nb * 2 * C + 1, dtype=_F32, device=dev)              # [sums | row count]
-        _lib.check(lib.gkg_bn_stats_sums(_ptr(Y), _ptr(buf), R, C, nb, _ptr(ws), ws.numel(), _stream()),
-                   "gkg_bn_stats_sums")
-        count = buf[-1:]
-        count.fill_(float(R))
-        dist.all_reduce(buf, group=group)
-        _lib.check(lib.gkg_bn_finalize(_ptr(buf), _ptr(count), _ptr(bn.weight), _ptr(bn.bias), _ptr(bias), rm, rv,
-                                       _ptr(a), _ptr(c), _ptr(mean), _ptr(invstd), C, nb, float(bn.momentum),
-                                       float(bn.eps), nbt, _stream()), "gkg_bn_finalize")
-        return a, c, mean, invstd, (group, count)
-    a, c = _bn_eval_ac(lib, bn, bias, nb * C)
-    return a, c, None, None, None
-
-
-from .bn_scratch import _BnLink, _BnScratch      # noqa: E402  (fp64 column-sum scratch of the two-launch BN passes)
-
-
-def _train_apply_from_sums(lib, x, W, bias, bn, R, cin, cout, nb, planes, res, out, ldo, obs, act, nchw_B, scale, rows_per_scale,
-                           launch=None, out_tm=None, xld=None, xbs=None, ochunk=0, prep=None):
-    """Projection (statistics in its epilogue) -> BN-apply straight from the fp64 sums: two launches, no finalize kernel.
-    Returns (Y, a, c, mean, invstd, sync).  ``launch(Y, sums) -> rc``: a caller-supplied producer of Y and its column sums (the
-    fused aggregation + projection kernel) instead of the plain projection of ``x``.
-    A SyncBatchNorm in a multi-rank group: the same two launches with ONE fp64 all-reduce between them — the sums and, in the
-    double behind them, the row count — and the _sync form of the apply pass, which divides by the exchanged count;
-    ``sync`` = (group, count as an fp32 device scalar) for the backward, else None."""
-    dev = x.device
-    group = _sync_group(bn)
-    n = 2 * nb * cout
-    with _BnScratch.of(dev).scoped(lib, n + (group is not None)) as (cur, other, zero):
-        Y = torch.empty((nb, R, cout) if nb > 1 else (R, cout), dtype=_F32, device=dev)
-        none10 = [None] * 10
-        if launch is not None:
-            rc = launch(Y, cur)
-        else:
-            ws = _sk_ws(dev)
-            rc = lib.gkg_linear_bn_fwd_x6_sk(_ptr(x), cin if xld is None else xld, R * cin if xbs is None else xbs, _ptr(planes),
-                                             _ptr(Y), R, cin, cout, nb, 2, *none10, 0.0, 0.0,
-                                             _ptr(cur), _ptr(ws), ws.numel(), _x6_flags(), _stream())
-        _lib.check(rc, "gkg_linear_bn_fwd_x6 (statistics only)")
-        a, c, mean, invstd = torch.empty((4, nb * cout), dtype=_F32, device=dev).unbind(0)     # one allocation
-        track = bn.training and bn.track_running_stats
-        _touch_stats(bn, track)
-        sfx, tail, sync = "", (_stream(),), None
-        if group is not None:
-            cur[n:n + 1].fill_(float(R))
-            dist.all_reduce(cur[:n + 1], group=group)
-            count = torch.empty(1, dtype=_F32, device=dev)
-            sfx, tail, sync = "_sync", (cur.data_ptr() + 8 * n, _ptr(count), _stream()), (group, count)
-        if prep is not None:             # the apply pass is also the k-NN's token preparation: prep = the KnnProblem, whose
-            # workspace is allocated now, by the call that is a producer (a label block's fc1 finds the one its keys already live in)
-            _lib.check(getattr(lib, "gkg_bn_apply_knn_prep" + sfx)(_ptr(Y), _ptr(cur), _ptr(bn.weight), _ptr(bn.bias), _ptr(bias),
-                                                 _ptr(bn.running_mean) if track else None, _ptr(bn.running_var) if track else None,
-                                                 _ptr(bn.num_batches_tracked) if track else None, _ptr(a), _ptr(c), _ptr(mean),
-                                                 _ptr(invstd), *prep.producer_args(lib, out, out_tm, res, ldo, ochunk),
-                                                 float(bn.momentum), float(bn.eps), _ptr(other), zero, *tail),
-                       "gkg_bn_apply_knn_prep" + sfx)
-        elif out_tm is not None:         # channel-major AND token-major result, residual token-major (gkg_bn_apply_train_dual)
-            _lib.check(getattr(lib, "gkg_bn_apply_train_dual" + sfx)(_ptr(Y), _ptr(cur), _ptr(bn.weight), _ptr(bn.bias), _ptr(bias),
-                                                   _ptr(bn.running_mean) if track else None, _ptr(bn.running_var) if track else None,
-                                                   _ptr(bn.num_batches_tracked) if track else None, _ptr(a), _ptr(c), _ptr(mean),
-                                                   _ptr(invstd), _ptr(res), _ptr(out), _ptr(out_tm), nchw_B, cout, R // nchw_B,
-                                                   float(bn.momentum), float(bn.eps), _ptr(other), zero, *tail),
-                       "gkg_bn_apply_train_dual" + sfx)
-        else:
-            _lib.check(getattr(lib, "gkg_bn_apply_train" + sfx)(_ptr(Y), _ptr(cur), _ptr(bn.weight), _ptr(bn.bias), _ptr(bias),
-                                              _ptr(bn.running_mean) if track else None, _ptr(bn.running_var) if track else None,
-                                              _ptr(bn.num_batches_tracked) if track else None, _ptr(a), _ptr(c), _ptr(mean), _ptr(invstd),
-                                              _ptr(res), _ptr(out), R, cout, nb, ldo, obs, ochunk, act, nchw_B, _ptr(scale), rows_per_scale,
-                                              float(bn.momentum), float(bn.eps), _ptr(other), zero, *tail),
-                       "gkg_bn_apply_train" + sfx)
-    return Y, a, c, mean, invstd, sync
-
-
-def _derive_ok(bn, nb, cout, code, want16) -> bool:
+def _derive_ok(bn, nb, cout, code, want16, group=...) -> bool:
     """Train-mode statistics (local to the rank, or exchanged as fp64 sums: _sync_x6_ok), fp32 output: the BN-apply pass
-    derives its coefficients from the projection kernel's sums (no finalize launch)."""
-    group = _sync_group(bn)
-    return ((bn.training or not bn.track_running_stats) and _sync_x6_ok(group)
+    derives its coefficients from the projection kernel's sums (no finalize launch).  ``group``: as in _x6."""
+    if group is ...:
+        group = _sync_group(bn)
+    return (bn_passes.batch_stats(bn) and _sync_x6_ok(group)
             and code == _lib.F32 and not want16 and _BnScratch.fits(2 * nb * cout + (group is not None)))
 
 
@@ -698,26 +588,20 @@ def _mr_bwd(lib, g, nn_idx, arg, B, G, C, N, M, k, mode, ak, has_src, xshape, li
     return gx.view(xshape), gsrc
 
 
-def _bn_link(out, Y, a, c, mean, invstd, act, nb, co, R, bn, sync, scale):
-    """Hang a _BnLink on a token-major fp32 layer output (train-mode, rank-local statistics, atomics allowed)."""
-    if (BN_EPILOGUE and (R >= BN_EPILOGUE_MIN_ROWS or (BWD_FUSE and DGRAD_STATS)) and mean is not None and sync is None
+def _bn_link(out, state, meta, scale):
+    """Hang a _BnLink on a token-major fp32 layer output (train-mode, rank-local statistics, atomics allowed).  ``state``: the
+    layer's (Y, a, c, mean, invstd); ``meta``: (act, nb, co, R, sync[, bn, bias]), what its node keeps as ``ctx.bn``."""
+    nb, co, R, sync = meta[1:5]
+    if (BN_EPILOGUE and (R >= BN_EPILOGUE_MIN_ROWS or (BWD_FUSE and DGRAD_STATS)) and state[3] is not None and sync is None
             and scale is None and not DETERMINISTIC and out.dtype == _F32 and _BnScratch.fits(2 * nb * co)):
-        link = _BnLink(Y, a, c, mean, invstd, act, nb, co, R)
-        out._gkg_bn_link = link
+        link = out._gkg_bn_link = _BnLink(*state, *meta)
         return link
     return None
 
 
-def _relayout_bnstats(lib, dout_c, dtm_c, g, Y, mean, invstd, a, c, B, cout, R):
-    """g (R, cout) = dout_c (B, cout, N)^T (+ dtm_c) with the BN backward statistics of  out = BN(Y)  taken in the same pass
-    (gkg_nchw_to_tm_add_bnstats) -> a _BnLink that carries them to _bn_backward, which then runs the apply pass only."""
-    scratch = _BnScratch.of(g.device)
-    with scratch.scoped(lib, 2 * cout) as (cur, other, zero):
-        _lib.check(lib.gkg_nchw_to_tm_add_bnstats(_ptr(dout_c), _ptr(dtm_c), _ptr(g), _ptr(Y), _ptr(mean), _ptr(invstd), _ptr(cur),
-                                                  B, cout, R // B, _stream()), "gkg_nchw_to_tm_add_bnstats")
-    link = _BnLink(Y, a, c, mean, invstd, 0, 1, cout, R)
-    scratch.hand_off(link, g, cur, other, zero)
-    return link
+def _layer_of(ctx, state):
+    """A node's BN layer for its backward: the link its forward hung on the output, else a record of the saved tensors."""
+    return ctx.link if ctx.link is not None else _BnLink(*state, *ctx.bn)
 
 
 def _dgrad_with_link_ok(lib, R, cin, has_res) -> bool:
@@ -741,106 +625,10 @@ def _dgrad_x6_with_link(lib, dY, pd, R, cin, cout, link, residual=None):
 
 
 def _bn_scale_in_kernel(sync, nb, C) -> bool:
-    """Whether _bn_backward will take the two-launch fp64-atomic form, whose kernels can apply a per-image gradient scale
-    (DropPath) themselves instead of a separate elementwise launch in front of them (22 launches, 0.6 ms of the cfg4 step)."""
+    """The ``atomic`` flag of a layer's backward (bn_passes.backward), asked once per node: the two-launch fp64-atomic form on the
+    scratch pair — whose kernels can apply a per-image gradient scale (DropPath) themselves instead of a separate elementwise
+    launch in front of them (22 launches, 0.6 ms of the cfg4 step) — rather than the two-stage workspace form."""
     return (sync is None or GEMM_MATH == "x6") and not DETERMINISTIC and _BnScratch.fits(2 * nb * C)
-
-
-def _bn_backward(lib, g, Y, a, c, mean, invstd, dY, dgamma, dbeta, R, C, nb, ldg, g_bstride, act, sync, link=None, row_scale=None,
-                 rows_per_scale=0):
-    """dY, dgamma, dbeta of out = act(BN_train(Y)) from the upstream gradient g; with ``sync`` the two column sums the
-    input gradient needs are all-reduced over the ranks (dgamma/dbeta stay local, like torch's SyncBatchNorm: the
-    data-parallel gradient exchange averages them) — as fp64, between the two launches of the atomic form
-    (gkg_bn_bwd_stats_f64 / gkg_bn_bwd_apply_sync), or as fp32 between the two-stage halves under GKG_DETERMINISTIC and
-    GKG_GEMM_MATH=vendor.  ``link``: this layer's _BnLink — when the consumer's dgrad epilogue has
-    left the statistics of exactly this gradient tensor on it, only the apply pass runs."""
-    if link is not None and link.holds_sums():
-        scratch = _BnScratch.of(Y.device)
-        sums = scratch.take(link, g, g_bstride == (C if nb > 1 else 0) and ldg == nb * C)
-        if sums is not None:
-            cur, other, zero = sums
-            with scratch:
-                _lib.check(lib.gkg_bn_bwd_apply_from_sums(_ptr(g), _ptr(Y), _ptr(a), _ptr(c), _ptr(mean), _ptr(invstd), _ptr(dY),
-                                                          _ptr(dgamma), _ptr(dbeta), R, C, nb, ldg, g_bstride, act, _ptr(cur),
-                                                          _ptr(other), zero, _stream()), "gkg_bn_bwd_apply_from_sums")
-            return
-    if _bn_scale_in_kernel(sync, nb, C):
-        # two launches: statistics with fp64 atomics into one of two alternating scratch buffers, apply (which also clears
-        # what the previous call left in the other buffer) — no partial rows, no second-stage reduction launch
-        with _BnScratch.of(Y.device).scoped(lib, 2 * nb * C) as (cur, other, zero):
-            if sync is not None:
-                # the same two launches with the exchange in the middle: this rank's sums are kept (dgamma / dbeta), the fp64
-                # buffer itself is all-reduced, the apply pass divides by the exchanged row count
-                group, count = sync
-                rs, rps = (_ptr(row_scale), rows_per_scale) if row_scale is not None else (None, 0)
-                _lib.check(lib.gkg_bn_bwd_stats_f64(_ptr(g), _ptr(Y), _ptr(a), _ptr(c), _ptr(mean), _ptr(invstd), R, C, nb, ldg,
-                                                    g_bstride, act, _ptr(cur), rs, rps, _stream()), "gkg_bn_bwd_stats_f64")
-                local = cur[:2 * nb * C].clone()
-                dist.all_reduce(cur[:2 * nb * C], group=group)
-                _lib.check(lib.gkg_bn_bwd_apply_sync(_ptr(g), _ptr(Y), _ptr(a), _ptr(c), _ptr(mean), _ptr(invstd), _ptr(dY),
-                                                     _ptr(dgamma), _ptr(dbeta), R, C, nb, ldg, g_bstride, act, _ptr(local), _ptr(cur),
-                                                     _ptr(count), _ptr(other), zero, rs, rps, _stream()), "gkg_bn_bwd_apply_sync")
-            elif row_scale is not None:
-                _lib.check(lib.gkg_bn_bwd_atomic_scaled(_ptr(g), _ptr(Y), _ptr(a), _ptr(c), _ptr(mean), _ptr(invstd), _ptr(dY),
-                                                        _ptr(dgamma), _ptr(dbeta), R, C, nb, ldg, g_bstride, act, _ptr(cur), _ptr(other),
-                                                        zero, _ptr(row_scale), rows_per_scale, _stream()), "gkg_bn_bwd_atomic_scaled")
-            else:
-                _lib.check(lib.gkg_bn_bwd_atomic(_ptr(g), _ptr(Y), _ptr(a), _ptr(c), _ptr(mean), _ptr(invstd), _ptr(dY), _ptr(dgamma),
-                                                 _ptr(dbeta), R, C, nb, ldg, g_bstride, act, _ptr(cur), _ptr(other), zero, _stream()),
-                           "gkg_bn_bwd_atomic")
-        return
-    ws = _ws(lib.gkg_bn_workspace_bytes(R, C, nb), Y.device)
-    if sync is None:
-        _lib.check(lib.gkg_bn_bwd(_ptr(g), _ptr(Y), _ptr(a), _ptr(c), _ptr(mean), _ptr(invstd), _ptr(dY),
-                                  _ptr(dgamma), _ptr(dbeta), R, C, nb, ldg, g_bstride, act, _ptr(ws), ws.numel(),
-                                  _stream()), "gkg_bn_bwd")
-        return
-    group, count = sync
-    sums = torch.empty(nb * 2 * C, dtype=_F32, device=Y.device)
-    _lib.check(lib.gkg_bn_bwd_sums(_ptr(g), _ptr(Y), _ptr(a), _ptr(c), _ptr(mean), _ptr(invstd), _ptr(dY), _ptr(sums),
-                                   _ptr(dgamma), _ptr(dbeta), R, C, nb, ldg, g_bstride, act, _ptr(ws), ws.numel(),
-                                   _stream()), "gkg_bn_bwd_sums")
-    dist.all_reduce(sums, group=group)
-    _lib.check(lib.gkg_bn_bwd_apply(_ptr(g), _ptr(Y), _ptr(a), _ptr(c), _ptr(mean), _ptr(invstd), _ptr(sums),
-                                    _ptr(count), _ptr(dY), R, C, nb, ldg, g_bstride, act, _stream()),
-               "gkg_bn_bwd_apply")
-
-
-def _bn_eval_backward(lib, g, Y, a, c, dY, bn, bias, dgamma, dbeta, dbias, R, C, nb, ldg, g_bstride, act, row_scale=None,
-                      rows_per_scale=0):
-    """dY of out = act(BN_eval(Y)) (running statistics: a frozen BN, or a module in eval() with gradients) in ONE sweep
-    (gkg_bn_eval_bwd); ``dgamma`` / ``dbeta`` / ``dbias``: output tensors for the gradients that are wanted (None: not wanted) —
-    with any of them the sweep also takes the two column sums (fp64 atomics into the alternating scratch pair, or the two-stage
-    workspace form under DETERMINISTIC) and a small second launch finishes them; with none (a fully frozen affine) the pass is
-    purely elementwise.  ``dbias`` is the gradient of the conv bias in front of the BN: real here, exactly zero in train mode."""
-    rs, rps = (_ptr(row_scale), rows_per_scale) if row_scale is not None else (None, 0)
-    tail = (_ptr(bn.running_mean), _ptr(bn.running_var), _ptr(bias), float(bn.eps), _ptr(dgamma), _ptr(dbeta), _ptr(dbias))
-    head = (_ptr(g), _ptr(Y), _ptr(a), _ptr(c), _ptr(dY), R, C, nb, ldg, g_bstride, act, rs, rps)
-    if dgamma is None and dbeta is None and dbias is None:
-        _lib.check(lib.gkg_bn_eval_bwd(*head, *tail, None, None, 0, None, 0, _stream()), "gkg_bn_eval_bwd")
-    elif not DETERMINISTIC and _BnScratch.fits(2 * nb * C):
-        with _BnScratch.of(Y.device).scoped(lib, 2 * nb * C) as (cur, other, zero):
-            _lib.check(lib.gkg_bn_eval_bwd(*head, *tail, _ptr(cur), _ptr(other), zero, None, 0, _stream()), "gkg_bn_eval_bwd")
-    else:
-        ws = _ws(lib.gkg_bn_workspace_bytes(R, C, nb), Y.device)
-        _lib.check(lib.gkg_bn_eval_bwd(*head, *tail, None, None, 0, _ptr(ws), ws.numel(), _stream()), "gkg_bn_eval_bwd")
-
-
-def _bn_backward_any(lib, ctx, want, g, Y, a, c, mean, invstd, dY, dgamma, dbeta, R, C, nb, ldg, g_bstride, act, link=None,
-                     row_scale=None, rows_per_scale=0):
-    """The BN backward of a layer's autograd node, train or eval mode -> (dbias, dgamma, dbeta) to return.  ``want``: whether the
-    conv bias, gamma and beta need a gradient (eval mode computes only those); ``ctx.bn_eval``: (bn, conv bias) of an eval-mode
-    layer.  A conv bias in front of train-mode BN has exactly zero gradient (BN removes the mean): not materialised."""
-    if mean is not None:
-        _bn_backward(lib, g, Y, a, c, mean, invstd, dY, dgamma, dbeta, R, C, nb, ldg, g_bstride, act, ctx.sync, link, row_scale,
-                     rows_per_scale)
-        return None, dgamma, dbeta
-    # running statistics: one sweep, and the conv bias HAS a gradient
-    bn, bias = ctx.bn_eval
-    dbias = torch.empty(nb * C, dtype=_F32, device=Y.device) if (bias is not None and want[0]) else None
-    dgamma, dbeta = (dgamma if want[1] else None), (dbeta if want[2] else None)
-    _bn_eval_backward(lib, g, Y, a, c, dY, bn, bias, dgamma, dbeta, dbias, R, C, nb, ldg, g_bstride, act, row_scale, rows_per_scale)
-    return dbias, dgamma, dbeta
 
 
 class _LinearBNAct(torch.autograd.Function):
@@ -865,10 +653,10 @@ class _LinearBNAct(torch.autograd.Function):
         lib = _lib.load()
         R, cin = x.shape
         cout = weight.shape[0]
-        W = weight.view(cout, cin)
         # the layer that produced x (see _BnLink); with ``alias`` the input gradient carries the alias's too (DGRAD_STATS)
         prev = None if (alias and not (BWD_FUSE and DGRAD_STATS)) else getattr(x, "_gkg_bn_link", None)
-        x6f, x6d = _x6(x, weight, bn, 1, "fwd"), _x6(x, weight, bn, 1, "dgrad")
+        group = _sync_group(bn)
+        x6f, x6d = _x6(x, weight, bn, 1, "fwd", group), _x6(x, weight, bn, 1, "dgrad", group)
         own = x6f
         pf, pd = _planes(lib, weight, 1, cout, cin, x6f, x6d) if x6f or x6d else (None, None)
         pf, pd = (pf if x6f else None), (pd if x6d else None)
@@ -893,22 +681,21 @@ class _LinearBNAct(torch.autograd.Function):
         if dual:
             assert nchw is not None and scale is None and res is not None and res.shape == (R, cout) and res.dtype == _F32
             out_tm = torch.empty((R, cout), dtype=_F32, device=x.device)
-        fused_apply = own and _derive_ok(bn, 1, cout, code, want16)
-        if own and not fused_apply and _sync_group(bn) is not None:
+        fused_apply = own and _derive_ok(bn, 1, cout, code, want16, group)
+        if own and not fused_apply and group is not None:
             own = False                               # exchanged statistics reach the x6 forward through the derive form only
         # this call's apply pass is also the producer of ``knn``'s prepared tokens (knn_prep.py): fc1's queries into the XM buffer, or
         # a Grapher's last layer as the producer of the label graph's keys
         prep = knn if (knn is not None and act == 0 and scale is None
                        and ((xm is not None and not knn.as_keys) or (dual and knn.as_keys))) else None
         if fused_apply:                               # projection (statistics epilogue) -> apply from the sums: 2 launches
-            Y, a, c, mean, invstd, sync = _train_apply_from_sums(lib, x, W.contiguous(), bias, bn, R, cin, cout, 1, pf, res, out,
-                                                           ldo, 0, act, 0 if nchw is None else nchw[0], scale, rows_per_scale,
-                                                           out_tm=out_tm, ochunk=ochunk, prep=prep)
+            dest = (res, out, ldo, 0, ochunk, act, 0 if nchw is None else nchw[0], scale, rows_per_scale)
+            Y, a, c, mean, invstd, sync = _project_apply(lib, x, pf, (R, cin, cout, 1), bias, bn, group, dest, out_tm, prep)
         elif own:                                     # projection kernel with the BN statistics in its epilogue
-            Y, a, c, mean, invstd = _linear_fwd_own(lib, x, W.contiguous(), bias, bn, R, cin, cout, 1, planes=pf)
+            Y, a, c, mean, invstd = _linear_fwd_own(lib, x, pf, (R, cin, cout, 1), bias, bn)
         else:
-            Y = _mm_t(x, W, w16)
-            a, c, mean, invstd, sync = _bn_forward_params(lib, Y, bn, bias, R, cout, 1)
+            Y = _mm_t(x, weight.view(cout, cin), w16)
+            a, c, mean, invstd, sync = bn_passes.forward_params(lib, Y, bn, bias, R, cout, 1, group)
         if not fused_apply and not (own and mean is None and code == _lib.F32 and not want16):
             prep = None      # besides the train-mode pass only a frozen layer's affine behind the x6 projection, fp32 out, prepares
         if fused_apply:
@@ -931,21 +718,22 @@ class _LinearBNAct(torch.autograd.Function):
         else:
             _lib.check(lib.gkg_tm_affine_to_nchw(_ptr(Y), _ptr(a), _ptr(c), _ptr(res), _ptr(out), nchw[0], cout,
                                                  R // nchw[0], _ptr(scale), _stream()), "gkg_tm_affine_to_nchw")
-        ctx.save_for_backward(x, weight, Y, a, c, mean, invstd)
-        ctx.bn_eval = (bn, bias) if mean is None else None       # eval-mode BN: the backward reads the running statistics
+        state = (Y, a, c, mean, invstd)
+        ctx.save_for_backward(x, weight, *state)
+        # what the backward's layer record (_layer_of) takes behind the saved tensors; eval-mode BN: it reads the running statistics
+        ctx.bn = (act, 1, cout, R, sync) + ((bn, bias) if mean is None else ())
         ctx.dual = dual
-        ctx.meta = (act, nchw, residual is not None)
+        ctx.meta = (nchw, residual is not None)
         ctx.scale = (scale, rows_per_scale)
         ctx.gparams = (weight, gamma, beta)
-        ctx.sync = sync
         ctx.pd = pd
         ctx.prev = prev if (prev is not None and pd is not None and prev.nb * prev.co == cin and prev.R == R) else None
-        ctx.link = _bn_link(out, Y, a, c, mean, invstd, act, 1, cout, R, bn, sync, scale) if (nchw is None and xm is None) else None
+        ctx.link = _bn_link(out, state, ctx.bn, scale) if (nchw is None and xm is None) else None
         if xm is not None:
             out = _xm_xview(out, xm[0], xm[1], cout)
             if act == 0 and out.dtype == _F32 and _bwd_fuse_ok(mean, sync, scale, 1, cout):
                 # the aggregation behind this layer takes its BN backward statistics in its scatter (_mr_bwd)
-                ctx.link = out._gkg_mr_bn_link = _BnLink(Y, a, c, mean, invstd, act, 1, cout, R)
+                ctx.link = out._gkg_mr_bn_link = _BnLink(*state, *ctx.bn)
             if prep is not None:
                 prep.mark(out)                        # the queries' prepared copies are in prep.ws (knn_prep.consumer_ws_flags)
         if alias:
@@ -961,8 +749,8 @@ class _LinearBNAct(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout, dalias=None):
         lib = _lib.load()
-        x, weight, Y, a, c, mean, invstd = ctx.saved_tensors
-        act, nchw, has_res = ctx.meta
+        x, weight, *state = ctx.saved_tensors
+        nchw, has_res = ctx.meta
         dtm = None
         if ctx.dual:
             dtm, dalias = dalias, None
@@ -974,19 +762,20 @@ class _LinearBNAct(torch.autograd.Function):
         cout = weight.shape[0]
         dres = dout if has_res else None
         row_scale = None
-        link = ctx.link
+        layer = _layer_of(ctx, state)
+        mean, sync = layer.mean, layer.sync
+        atomic = _bn_scale_in_kernel(sync, 1, cout)     # asked once: it serves the DropPath decision below and the launch form
         if ctx.dual:
             # the output went out in both layouts: its two upstream gradients are summed while the NCHW one is re-laid out, and
             # the (token-major) residual's gradient is that very sum
-            fuse_stats = _bwd_fuse_ok(mean, ctx.sync, ctx.scale[0], 1, cout)
-            if fuse_stats:
+            if _bwd_fuse_ok(mean, sync, ctx.scale[0], 1, cout):
                 # the re-layout pass is also this BN's backward statistics pass (BWD_FUSE); like the block driver it takes a
                 # missing NCHW gradient as zeros, so that both issue the same launches
                 if dout is None:
                     dout = torch.zeros(nchw, dtype=_F32, device=dtm.device)
                 g = torch.empty((R, cout), dtype=_F32, device=dout.device)
                 dout_c, dtm_c = dout.contiguous(), (None if dtm is None else dtm.contiguous())
-                link = _relayout_bnstats(lib, dout_c, dtm_c, g, Y, mean, invstd, a, c, nchw[0], cout, R)
+                bn_passes.relayout_bnstats(lib, dout_c, dtm_c, g, layer, nchw[0])
             elif dout is None:
                 g = dtm.contiguous()
             elif dtm is None:
@@ -1000,27 +789,26 @@ class _LinearBNAct(torch.autograd.Function):
                 _lib.check(lib.gkg_nchw_to_tm_add(_ptr(dout_c), _ptr(dtm_c), _ptr(g), nchw[0], cout, R // nchw[0], _stream()),
                            "gkg_nchw_to_tm_add")
             dres = g
-        elif nchw is not None and _bwd_fuse_ok(mean, ctx.sync, ctx.scale[0], 1, cout):
+        elif nchw is not None and _bwd_fuse_ok(mean, sync, ctx.scale[0], 1, cout):
             g = torch.empty((R, cout), dtype=_F32, device=dout.device)
             dout_c = dout.contiguous()
-            link = _relayout_bnstats(lib, dout_c, None, g, Y, mean, invstd, a, c, nchw[0], cout, R)
+            bn_passes.relayout_bnstats(lib, dout_c, None, g, layer, nchw[0])
         elif nchw is not None:
             g = torch.empty((R, cout), dtype=_F32, device=dout.device)
             dout_c = dout.contiguous()           # named: the copy must outlive the launch that reads it
             _lib.check(lib.gkg_nchw_to_tm(_ptr(dout_c), _ptr(g), nchw[0], cout, R // nchw[0], _lib.F32,
                                           _ptr(ctx.scale[0]), _stream()), "gkg_nchw_to_tm")      # DropPath: g * mask / keep
-        elif (ctx.scale[0] is not None and (mean is None or _bn_scale_in_kernel(ctx.sync, 1, cout))
-              and (ctx.link is None or not ctx.link.holds_sums())):
+        elif ctx.scale[0] is not None and (mean is None or atomic) and not layer.holds_sums():
             g = dout.contiguous()                # DropPath: the BN-backward kernels scale the gradient per image themselves
             row_scale = (ctx.scale[0].contiguous().float(), ctx.scale[1])
         elif ctx.scale[0] is not None:
             g = (dout.view(-1, ctx.scale[1], cout) * ctx.scale[0].view(-1, 1, 1)).view(R, cout)
         else:
             g = dout.contiguous()                # (an xm output's gradient arrives (B, N, 4, cout / 4): the same memory as (R, cout))
-        dY = torch.empty_like(Y)
-        dWv, dgamma, dbeta = _grad_outs(ctx.gparams, (cout, cin), cout, Y.device)
-        dbias, dgamma, dbeta = _bn_backward_any(lib, ctx, ctx.needs_input_grad[2:5], g, Y, a, c, mean, invstd, dY, dgamma, dbeta,
-                                                R, cout, 1, cout, 0, act, link, *(row_scale if row_scale is not None else (None, 0)))
+        dY = torch.empty_like(layer.Y)
+        dWv, dgamma, dbeta = _grad_outs(ctx.gparams, (cout, cin), cout, dY.device)
+        dbias, dgamma, dbeta = bn_passes.backward(lib, layer, g, cout, 0, dY, (dgamma, dbeta), ctx.needs_input_grad[2:5], row_scale,
+                                                  atomic)
         W = weight.view(cout, cin)
         if not ctx.needs_input_grad[0]:
             dx = None
@@ -1069,21 +857,22 @@ class _GroupedLinearBNAct(torch.autograd.Function):
         cout = weight.shape[0]
         co = cout // nb
         Wg = weight.view(nb, co, ci)
-        x6f, x6d = _x6(U, weight, bn, nb, "fwd") and act == 1, _x6(U, weight, bn, nb, "dgrad")
+        group = _sync_group(bn)
+        x6f, x6d = _x6(U, weight, bn, nb, "fwd", group) and act == 1, _x6(U, weight, bn, nb, "dgrad", group)
         own = x6f                                                   # (the fp32-MFMA forward kernel takes no operand pitch)
         pf, pd = _planes(lib, weight, nb, co, ci, x6f, x6d, kperm=1) if x6f or x6d else (None, None)
         pf, pd = (pf if x6f else None), (pd if x6d else None)
         dt, code = _tm_dtype(out_lowp)
         out = torch.empty((R, cout), dtype=dt, device=XM.device)
         sync = None
-        fused_apply = own and _derive_ok(bn, nb, co, code, False)
-        if own and not fused_apply and _sync_group(bn) is not None:
+        fused_apply = own and _derive_ok(bn, nb, co, code, False, group)
+        if own and not fused_apply and group is not None:
             own = False
         if fused_apply:
-            Y, a, c, mean, invstd, sync = _train_apply_from_sums(lib, XM, None, bias, bn, R, ci, co, nb, pf, None, out,
-                                                           cout, co, act, 0, None, 0, xld=nb * ci, xbs=ci)
+            Y, a, c, mean, invstd, sync = _project_apply(lib, U, pf, (R, ci, co, nb), bias, bn, group,
+                                                         (None, out, cout, co, 0, act, 0, None, 0))
         elif own:
-            Y, a, c, mean, invstd = _linear_fwd_own(lib, XM, None, bias, bn, R, ci, co, nb, planes=pf, xld=nb * ci, xbs=ci)
+            Y, a, c, mean, invstd = _linear_fwd_own(lib, U, pf, (R, ci, co, nb), bias, bn)
         else:
             if XM.dtype == torch.bfloat16:
                 Wb = weight.to(torch.bfloat16) if w16 is None else w16
@@ -1092,33 +881,32 @@ class _GroupedLinearBNAct(torch.autograd.Function):
                 Y = torch.bmm(U, _kperm_weight(Wg).transpose(1, 2))        # (nb, R, co)
                 if Y.dtype != _F32:
                     Y = Y.float()
-            a, c, mean, invstd, sync = _bn_forward_params(lib, Y, bn, bias, R, co, nb)
+            a, c, mean, invstd, sync = bn_passes.forward_params(lib, Y, bn, bias, R, co, nb, group)
         if not fused_apply:
             _lib.check(lib.gkg_affine_act(_ptr(Y), _ptr(a), _ptr(c), None, _ptr(out), R, co, nb, cout, co, 0, act,
                                           code, None, 0, _stream()), "gkg_affine_act")
-        ctx.save_for_backward(XM, weight, Y, a, c, mean, invstd)
-        ctx.bn_eval = (bn, bias) if mean is None else None
-        ctx.act = act
+        state = (Y, a, c, mean, invstd)
+        ctx.save_for_backward(XM, weight, *state)
+        ctx.bn = (act, nb, co, R, sync) + ((bn, bias) if mean is None else ())
         ctx.gparams = (weight, gamma, beta)
-        ctx.sync = sync
         ctx.pd = pd
-        ctx.link = _bn_link(out, Y, a, c, mean, invstd, act, nb, co, R, bn, sync, None)
+        ctx.link = _bn_link(out, state, ctx.bn, None)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         lib = _lib.load()
-        XM, weight, Y, a, c, mean, invstd = ctx.saved_tensors
-        act = ctx.act
+        XM, weight, *state = ctx.saved_tensors
+        layer = _layer_of(ctx, state)
         nb = 4
         R, ci = XM.shape[0], XM.shape[1] // nb
         cout = weight.shape[0]
         co = cout // nb
         g = dout.contiguous()
-        dY = torch.empty_like(Y)
-        dWv, dgamma, dbeta = _grad_outs(ctx.gparams, (nb, co, ci), cout, Y.device)
-        dbias, dgamma, dbeta = _bn_backward_any(lib, ctx, ctx.needs_input_grad[2:5], g, Y, a, c, mean, invstd, dY, dgamma, dbeta,
-                                                R, co, nb, cout, co, act, ctx.link)
+        dY = torch.empty_like(layer.Y)
+        dWv, dgamma, dbeta = _grad_outs(ctx.gparams, (nb, co, ci), cout, dY.device)
+        dbias, dgamma, dbeta = bn_passes.backward(lib, layer, g, cout, co, dY, (dgamma, dbeta), ctx.needs_input_grad[2:5], None,
+                                                  _bn_scale_in_kernel(layer.sync, nb, co))
         Wg = weight.view(nb, co, ci)
         if not ctx.needs_input_grad[0]:
             dXM = None
@@ -1146,25 +934,25 @@ class _BNActTM(torch.autograd.Function):
     def forward(ctx, Y, gamma, beta, bn, act):
         lib = _lib.load()
         R, C = Y.shape
-        a, c, mean, invstd, sync = _bn_forward_params(lib, Y, bn, None, R, C, 1)
+        a, c, mean, invstd, sync = bn_passes.forward_params(lib, Y, bn, None, R, C, 1, _sync_group(bn))
         out = torch.empty_like(Y)
         _lib.check(lib.gkg_affine_act(_ptr(Y), _ptr(a), _ptr(c), None, _ptr(out), R, C, 1, C, 0, 0, act, _lib.F32, None, 0, _stream()),
                    "gkg_affine_act")
         ctx.save_for_backward(Y, a, c, mean, invstd)
-        ctx.act, ctx.sync, ctx.gparams = act, sync, (None, gamma, beta)
-        ctx.bn_eval = (bn, None) if mean is None else None
+        ctx.bn = (act, 1, C, R, sync) + ((bn, None) if mean is None else ())      # (the conv in front owns its bias)
+        ctx.gparams = (None, gamma, beta)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         lib = _lib.load()
-        Y, a, c, mean, invstd = ctx.saved_tensors
-        R, C = Y.shape
+        layer = _BnLink(*ctx.saved_tensors, *ctx.bn)
+        C = layer.co
         g = dout.contiguous()
-        dY = torch.empty_like(Y)
-        _, dgamma, dbeta = _grad_outs(ctx.gparams, None, C, Y.device)
-        _, dgamma, dbeta = _bn_backward_any(lib, ctx, (False,) + ctx.needs_input_grad[1:3], g, Y, a, c, mean, invstd, dY, dgamma,
-                                            dbeta, R, C, 1, C, 0, ctx.act)            # (the conv in front owns its bias)
+        dY = torch.empty_like(layer.Y)
+        _, dgamma, dbeta = _grad_outs(ctx.gparams, None, C, dY.device)
+        _, dgamma, dbeta = bn_passes.backward(lib, layer, g, C, 0, dY, (dgamma, dbeta), (False,) + ctx.needs_input_grad[1:3], None,
+                                              _bn_scale_in_kernel(layer.sync, 1, C))
         return dY, dgamma, dbeta, None, None
 
 
@@ -1221,7 +1009,7 @@ def conv_bn_act_eval(conv, bn, act_mod, x, want32=True, want16=False):
     the 22.7 ms GKGNet-576 forward, tools/prof_backbone_ops.py cfg3) become one streaming pass per unit."""
     lib = _lib.load()
     cout = conv.out_channels
-    a, c = _bn_eval_ac(lib, bn, conv.bias, cout)
+    a, c = bn_passes.eval_ac(lib, bn, conv.bias, cout)
     ac16 = torch.is_autocast_enabled()
     dt = torch.bfloat16 if ac16 else _F32
     xin = x if (x.dtype == dt and x.is_contiguous(memory_format=torch.channels_last)) else \
@@ -1269,7 +1057,7 @@ def stem_conv_supported(conv, x) -> bool:
 def stem_conv(conv, x, bn=None):
     """Training form: the plain convolution (its BN runs on the token-major kernels behind it, fused.bn_act).  ``bn``: the
     BatchNorm directly behind it — in training mode the bias gradient is exactly zero and is not reduced."""
-    bn_behind = (STEM_BN and isinstance(bn, torch.nn.modules.batchnorm._BatchNorm) and (bn.training or not bn.track_running_stats))
+    bn_behind = STEM_BN and isinstance(bn, torch.nn.modules.batchnorm._BatchNorm) and bn_passes.batch_stats(bn)
     return _StemConv.apply(x, conv.weight, conv.bias, bn_behind)
 
 
@@ -1279,7 +1067,7 @@ def conv_before_bn(conv, bn, x):
     statistics (training), the module call otherwise."""
     if (ENABLED and STEM_BN and x.is_cuda and x.dtype == _F32 and not torch.is_autocast_enabled() and torch.is_grad_enabled()
             and isinstance(conv, torch.nn.Conv2d) and isinstance(bn, torch.nn.modules.batchnorm._BatchNorm)
-            and (bn.training or not bn.track_running_stats) and conv.groups == 1 and tuple(conv.dilation) == (1, 1)
+            and bn_passes.batch_stats(bn) and conv.groups == 1 and tuple(conv.dilation) == (1, 1)
             and conv.padding_mode == "zeros" and not isinstance(conv.padding, str) and conv.weight.dtype == _F32):
         return _ConvBeforeBN.apply(x, conv.weight, conv.bias, list(conv.stride), list(conv.padding))
     return conv(x)
@@ -1300,7 +1088,7 @@ def stem_conv_bn_act_eval(conv, bn, act_mod, x, out_bf16: bool):
     lib = _lib.load()
     B, cin, H, W = x.shape
     cout = conv.out_channels
-    a, c = _bn_eval_ac(lib, bn, conv.bias, cout)                      # conv bias folded into the shift
+    a, c = bn_passes.eval_ac(lib, bn, conv.bias, cout)                      # conv bias folded into the shift
     out = torch.empty((B, (H + 1) // 2, (W + 1) // 2, cout), dtype=torch.bfloat16 if out_bf16 else _F32, device=x.device)
     _lib.check(lib.gkg_stem_conv3x3s2_fwd(_ptr(x.contiguous()), _ptr(conv.weight.contiguous()), None, _ptr(a), _ptr(c), _ptr(out), B, cin,
                                           H, W, cout, 0 if act_mod is None else 1, _lib.BF16 if out_bf16 else _lib.F32, _stream()),
@@ -1581,7 +1369,7 @@ def mr_grouped_linear_eval(x, src, nn_idx, G, conv, bn, act=1):
     M = N if src is None else src.shape[1]
     x = x.contiguous()
     src = None if src is None else src.contiguous()
-    a, c = _bn_eval_ac(lib, bn, conv.bias, 2 * C)
+    a, c = bn_passes.eval_ac(lib, bn, conv.bias, 2 * C)
     out = torch.empty((B * N, 2 * C), dtype=torch.bfloat16, device=x.device)
     fn = lib.gkg_mr_linear_bf16_nn16 if nn_idx.dtype == torch.int16 else lib.gkg_mr_linear_bf16      # compact lists: knn_graph_tm16
     _lib.check(fn(_ptr(x), _ptr(src), _ptr(nn_idx), _ptr(_mr_planes_of(conv)), _ptr(a), _ptr(c), _ptr(out),

@@ -371,14 +371,16 @@ def test_frozen_bn_under_bf16_autocast():
 
 # ------------------------------------------------------------------------------------------------ (9) backbone
 def _count_eval_bwd(fused):
-    """Wraps fused._bn_eval_backward with a call counter -> (counter list, restore())."""
-    real, calls = fused._bn_eval_backward, [0]
+    """Wraps the eval-mode BN backward (bn_passes._eval_backward, which the fused path's nodes reach through bn_passes.backward)
+    with a call counter -> (counter list, restore())."""
+    from gkgnet_amd import bn_passes
+    real, calls = bn_passes._eval_backward, [0]
 
     def counted(*args, **kw):
         calls[0] += 1
         return real(*args, **kw)
-    fused._bn_eval_backward = counted
-    return calls, lambda: setattr(fused, "_bn_eval_backward", real)
+    bn_passes._eval_backward = counted
+    return calls, lambda: setattr(bn_passes, "_eval_backward", real)
 
 
 @pytest.mark.parametrize("unit", ["stem", "downsample", "ffn"])

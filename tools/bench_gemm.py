@@ -27,13 +27,15 @@ def main():
         W = torch.randn(nb, cout, cin, device=dev) / cin ** 0.5
         bn = torch.nn.BatchNorm2d(nb * cout).to(dev).train()
         fl = 2.0 * R * cin * cout * nb
-        Y, a, c, mean, invstd = fused._linear_fwd_own(lib, x, W, None, bn, R, cin, cout, nb)
+        pf, _ = fused._planes(lib, W, nb, cout, cin, True, False)
+        xv = x if nb > 1 else x[0]                    # (nb, R, cin) view, or the (R, cin) matrix
+        Y, a, c, mean, invstd = fused._linear_fwd_own(lib, xv, pf, (R, cin, cout, nb), None, bn)
         Yr = torch.bmm(x, W.transpose(1, 2))
         err = (Y.view(nb, R, cout) - Yr).abs().max().item()
         m_ref, v_ref = Yr.mean(1).flatten(), Yr.var(1, unbiased=False).flatten()
         merr = (mean - m_ref).abs().max().item()
         verr = ((1 / invstd ** 2 - 1e-5) - v_ref).abs().max().item() / v_ref.max().item()
-        t_own = timeit(lambda: fused._linear_fwd_own(lib, x, W, None, bn, R, cin, cout, nb))
+        t_own = timeit(lambda: fused._linear_fwd_own(lib, xv, pf, (R, cin, cout, nb), None, bn))
         t_lib = timeit(lambda: torch.bmm(x, W.transpose(1, 2)))
         # backward
         g = torch.randn(nb, R, cout, device=dev)
