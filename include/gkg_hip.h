@@ -110,6 +110,8 @@ int gkg_knn_fwd(const void* x, const void* y, const float* relpos, int64_t* nn_i
  *   src      (BG, c, M) or NULL (-> src = x, M = N)
  *   m_out    (BG, c, N)
  *   argmax   (BG, c, N) u8   out, optional: first j attaining the max (needed by gkg_mr_bwd)
+ * An nn_idx entry outside [0, M) is clamped on its full 64-bit value (< 0 -> 0, >= M -> M - 1): never an out-of-bounds read.
+ * The maximum follows torch.max: the first of equal values wins, a NaN difference is the maximum and the first NaN stays.
  */
 int gkg_mr_fwd(const void* x, const void* src, const int64_t* nn_idx, void* m_out, uint8_t* argmax,
                int BG, int c, int N, int M, int k, int dtype, void* stream);
@@ -304,7 +306,9 @@ int gkg_knn_mr_fwd_tm(const float* x, int ldx, int xchunk, const float* y, const
                       uint16_t* arg_out, uint16_t* nn16_out, int64_t* nn_idx_out, int64_t* center_out, int B, int G, int c, int N,
                       int M, int k, int dilation, unsigned flags, void* workspace, size_t workspace_bytes, void* stream);
 /* arg_kind: what `argmax` holds — 0: (B,N,C) u8, the winning slot j (as gkg_mr_fwd); 1: (B,N,C) u16, the winning
- * neighbour's row index itself (M <= 65536), which lets the backward scatter without looking the index row up again. */
+ * neighbour's row index itself (M <= 65536), which lets the backward scatter without looking the index row up again.
+ * An nn_idx entry outside [0, M) is clamped as in gkg_mr_fwd (int64 lists on the full 64-bit value; the u16 lists of
+ * gkg_mr_fwd_tm16: >= M -> M - 1), and with arg_kind 1 the row stored is the CLAMPED one, always < M. */
 int gkg_mr_fwd_tm(const float* x, int ldx, int xchunk, const float* src, const int64_t* nn_idx, void* out /* out_dtype elements */,
                   uint8_t* argmax, int B, int G, int c, int N, int M, int k, int mode, int out_dtype, int arg_kind,
                   void* stream);
@@ -336,7 +340,8 @@ int gkg_mr_bwd_tm_bnstats_supported(int B, int G, int c, int N, int M, int k, in
  *            rounded up to 32: fragment (q, f, n) = W[q*co + n][8f .. 8f+7] (zero outside); gkg_mr_linear_planes_bytes(C)
  *   a, cshift (2C) fp32: out = act(a * conv + cshift) per output channel (eval-mode BN folded with the conv bias)
  *   out (B*N, ldo) bf16, columns [0, 2C) written (column q*co + n), ldo >= 2C, ldo % 8 == 0; act: 0 none, 1 GELU (erf)
- * The max-relative arithmetic is gkg_mr_fwd_tm's (bit-identical m before rounding). */
+ * The max-relative arithmetic is gkg_mr_fwd_tm's (bit-identical m before rounding), an nn_idx / nn16 entry outside [0, M)
+ * included: it is clamped (< 0 -> 0, >= M -> M - 1). */
 size_t gkg_mr_linear_planes_bytes(int C);
 int gkg_mr_linear_bf16(const float* x, const float* src, const int64_t* nn_idx, const void* wplanes, const float* a,
                        const float* cshift, void* out, int ldo, int B, int G, int c, int N, int M, int k, int act,

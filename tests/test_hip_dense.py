@@ -107,7 +107,8 @@ def test_grouped_linear_matches_grouped_conv(gemm_mode):
 
 def test_layout_round_trip_and_token_major_graph_ops():
     """to_token_major / its backward are exact transposes; the token-major k-NN and aggregation return exactly
-    what the channel-major operators (already pinned to the oracle) return."""
+    what the channel-major operators (already pinned to the oracle) return.  The aggregation entry points themselves
+    (gkg_mr_fwd, gkg_mr_fwd_tm, gkg_mr_fwd_tm16) are pinned to their definition in tests/test_hip_mr_fwd_exact.py."""
     from gkgnet_amd import fused, ops
     torch.manual_seed(2)
     B, C, H, G, k = 3, 32, 10, 2, 5

@@ -1,6 +1,8 @@
 """Row g2: the fused k-NN + max-relative aggregation kernel (gkg_knn_mr_fwd_tm, csrc/gkg_knn_tile.h MRF) through the C ABI.
 Bit-exact against the C oracle (O.knn -> O.mr_fwd, the contract of reference torch_edge.py:164-176 -> torch_vertex.py:49-61)
-and against the two-launch form it replaces (gkg_knn_fwd_tm -> gkg_mr_fwd_tm), incl. exact ties through the fused epilogue."""
+and against the two-launch form it replaces (gkg_knn_fwd_tm -> gkg_mr_fwd_tm), incl. exact ties through the fused epilogue.
+The two-launch aggregation this file compares against (gkg_mr_fwd_tm, for NaN / inf the only reference used here) is itself pinned
+to its definition, bit for bit, in tests/test_hip_mr_fwd_exact.py."""
 import ctypes
 
 import numpy as np
