@@ -1,0 +1,287 @@
+// gkg_linear_bf16.hip — bf16 inference: a dense 1x1 projection (Conv2d 1x1 + eval-mode BN [+ GELU] [+ residual]) as ONE kernel.
+//
+// Reference layers (mmcls/models/backbones/vig_model/torch_vertex.py:290-306 Grapher.fc1 / fc2, mmcls/models/backbones/gkgnet.py:46-72
+// FFN.fc1 / fc2, torch_nn.py:57-69) under bf16 autocast with gradients off.  The library-GEMM form of these layers is
+// (GEMM with a bias epilogue) for fc1 and (GEMM -> fp32 (T, cout) matrix in memory -> gkg_affine_act_dual) for the layers with a
+// residual; here the BN scale / shift, the GELU, the fp32 residual add and BOTH output precisions (the fp32 residual stream and the
+// bf16 operand of the next projection) are the GEMM's epilogue: the pre-BN matrix never exists in memory.
+//
+// One workgroup (4 waves, stacked on rows) owns a 128-row x (32 NB)-column tile, NB = 4 or 2:
+//   main loop  contraction chunks of 64: the A rows (already bf16: no split, no conversion) and the B fragments ([ci_pad/8][co_pad][8]
+//              planes: 16 B x (32 NB) contiguous pieces per fragment row) go global -> registers -> LDS, double-buffered, the loads
+//              of chunk c + 2 issued before the MFMAs of chunk c (two register sets), ONE barrier per chunk;
+//              v_mfma_f32_32x32x16_bf16, wave w takes rows [32 w, 32 w + 32) x NB column blocks.  A rows have a 16-byte pad
+//              (pitch 144 B): conflict-free 16-byte reads.
+//   epilogue   in the 32x32 accumulator layout a lane owns ONE column per block: a[n] / cshift[n] are one register each.
+//              z = act(fma(a, acc, c)) goes to the (now free) LDS, each wave into its own quarter; the wave then walks its 32 rows as
+//              8-column segments: residual read as 2 x float4, fp32 result stored as 2 x 16 B, bf16 result as 16 B.
+// Workgroups are dealt to the XCDs so that each XCD (own L2) walks a contiguous range of tiles, the column tiles of one row tile
+// adjacent: the A rows are read from memory once.  Partial tiles in every dimension: rows >= R, columns >= cout and contraction
+// granules >= cin are zero-filled on the way in and never stored on the way out; nothing is read or written outside the operands.
+//
+// Resource usage (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage; no scratch in either):
+//   linear_bf16_kernel<4>  128 x 128 tile   234 VGPRs, 0 AGPRs, 66 SGPRs   LDS 69 632 B (dynamic)   2 waves / SIMD by registers
+//   linear_bf16_kernel<2>  128 x  64 tile   152 VGPRs, 0 AGPRs, 62 SGPRs   LDS 53 248 B (dynamic)   3 waves / SIMD by registers
+// The LDS allows 2 (<4>) / 3 (<2>) workgroups of 4 waves per CU, i.e. the same 2 / 3 waves per SIMD: registers and LDS agree.
+// (The straight-line chunk body and the edge-tile body keep separate accumulator registers: 138 / 94 VGPRs before them, at
+// 5–10 % more time per layer.)
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "gkg_common.h"
+
+namespace gkg {
+
+typedef float lb_f32x16 __attribute__((ext_vector_type(16)));
+typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 lb_bf16x8;
+
+constexpr int LB_BM = 128;                       // rows per workgroup: 4 waves x 32
+constexpr int LB_KC = 64;                        // contraction elements per LDS stage (4 MFMA steps of 16)
+constexpr int LB_NT = 256;
+constexpr int LB_APITCH = (LB_KC + 8) * 2;       // bytes per A row in LDS
+constexpr int LB_ABYTES = LB_BM * LB_APITCH;     // 18 432
+
+struct LinBf16Args {
+  const uint16_t* x; int ldx;       // (R, ldx) bf16
+  const uint4* wp;                  // [ci_pad / 8][co_pad] fragments of 8 consecutive input channels (bf16)
+  const float* a;                   // [cout] or null (= 1)
+  const float* cs;                  // [cout]
+  const float* res; int ldr;        // (R, ldr) fp32 or null
+  float* o32; int ldo32;            // (R, ldo32) or null
+  uint16_t* o16; int ldo16;         // (R, ldo16) bf16 or null
+  int R, cin, cout, ci_pad, co_pad, act;
+  int col_tiles, tiles, tiles_per_xcd;
+};
+
+constexpr size_t lb_lds_bytes(int NB) { return 2 * (size_t)(LB_ABYTES + (LB_KC / 8) * 32 * NB * 16); }
+
+template <int NB>
+__global__ __launch_bounds__(LB_NT, 2) void linear_bf16_kernel(LinBf16Args g) {
+  extern __shared__ __align__(16) unsigned char lb_lds[];
+  constexpr int BN = 32 * NB;
+  constexpr int BBYTES = (LB_KC / 8) * BN * 16;
+  constexpr int NA = LB_BM * (LB_KC / 8) / LB_NT;        // 16-byte A granules per thread and chunk: 4
+  constexpr int NBG = (LB_KC / 8) * BN / LB_NT;          // B granules per thread and chunk: 4 (NB = 4), 2 (NB = 2)
+  constexpr int SP = BN + 4;                             // floats per row of a wave's epilogue stage
+  static_assert(4 * 32 * SP * 4 <= 2 * (LB_ABYTES + BBYTES), "the epilogue stage must fit the operand buffers");
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // XCD-aware map (workgroups are dealt round-robin over the 8 XCDs): XCD i walks tiles [i * tiles_per_xcd, ...), column tile fastest
+  const int lin = blockIdx.x;
+  const int tl = lin >> 3, tile = (lin & 7) * g.tiles_per_xcd + tl;
+  if (tl >= g.tiles_per_xcd || tile >= g.tiles) return;
+  const int rt = tile / g.col_tiles, ct = tile - rt * g.col_tiles;
+  const long long r0 = (long long)rt * LB_BM;
+  const int n0 = ct * BN;
+  unsigned char* abuf = lb_lds;                          // [2][128][144 B]
+  unsigned char* bbuf = lb_lds + 2 * LB_ABYTES;          // [2][8][BN][16 B]
+
+  const int S = g.ci_pad >> 4;                           // MFMA steps
+  const int NC = (g.ci_pad + LB_KC - 1) / LB_KC;         // LDS chunks
+  const int nfrag = g.ci_pad >> 3;
+
+  // two register sets: the loads of chunk c + 2 are issued before the MFMAs of chunk c (set c & 1), the set holding chunk c + 1 is
+  // written to the other LDS buffer after them — a load has two chunks of matrix work (and the CU's other workgroups) to land
+  uint4 ra[2][NA], rb[2][NBG];
+  auto fetch = [&](int c, uint4 (&qa)[NA], uint4 (&qb)[NBG]) __attribute__((always_inline)) {
+    const int k0 = c * LB_KC;
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+      const int gi = tid + LB_NT * i;
+      const long long row = r0 + (gi >> 3);
+      const int k = k0 + 8 * (gi & 7);
+      qa[i] = (row < g.R && k < g.cin) ? *reinterpret_cast<const uint4*>(g.x + (size_t)row * g.ldx + k) : make_uint4(0, 0, 0, 0);
+    }
+#pragma unroll
+    for (int i = 0; i < NBG; ++i) {
+      const int gi = tid + LB_NT * i;
+      const int f = (k0 >> 3) + gi / BN, n = n0 + (gi % BN);
+      qb[i] = (f < nfrag && n < g.co_pad) ? g.wp[(size_t)f * g.co_pad + n] : make_uint4(0, 0, 0, 0);
+    }
+  };
+  auto stash = [&](int buf, const uint4 (&qa)[NA], const uint4 (&qb)[NBG]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+      const int gi = tid + LB_NT * i;
+      *reinterpret_cast<uint4*>(abuf + buf * LB_ABYTES + (gi >> 3) * LB_APITCH + 16 * (gi & 7)) = qa[i];
+    }
+#pragma unroll
+    for (int i = 0; i < NBG; ++i) *reinterpret_cast<uint4*>(bbuf + buf * BBYTES + 16 * (tid + LB_NT * i)) = qb[i];
+  };
+
+  const int l31 = lane & 31, kg = lane >> 5;
+  bool has[NB];
+#pragma unroll
+  for (int u = 0; u < NB; ++u) has[u] = n0 + 32 * u < g.co_pad;     // workgroup-uniform
+  lb_f32x16 acc[NB];
+#pragma unroll
+  for (int u = 0; u < NB; ++u)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[u][r] = 0.f;
+
+  auto compute = [&](int c, int buf) __attribute__((always_inline)) {
+    const unsigned char* ap = abuf + buf * LB_ABYTES + (32 * w + l31) * LB_APITCH + 16 * kg;
+    const unsigned char* bp = bbuf + buf * BBYTES + (kg * BN + l31) * 16;
+    const int steps = min(LB_KC / 16, S - c * (LB_KC / 16));
+    auto step = [&](int s, bool all) __attribute__((always_inline)) {
+      const lb_bf16x8 av = __builtin_bit_cast(lb_bf16x8, *reinterpret_cast<const uint4*>(ap + 32 * s));
+#pragma unroll
+      for (int u = 0; u < NB; ++u)
+        if (all || has[u]) {
+          const lb_bf16x8 bv = __builtin_bit_cast(lb_bf16x8, *reinterpret_cast<const uint4*>(bp + (2 * s * BN + 32 * u) * 16));
+          acc[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc[u], 0, 0, 0);
+        }
+    };
+    if (steps == LB_KC / 16 && has[NB - 1]) {
+      // a full chunk of a full column tile: straight-line code, a step's fragment reads issue under the MFMAs of the one before
+#pragma unroll
+      for (int s = 0; s < LB_KC / 16; ++s) step(s, true);
+    } else {
+      for (int s = 0; s < steps; ++s) step(s, false);
+    }
+  };
+
+  fetch(0, ra[0], rb[0]);
+  if (NC > 1) fetch(1, ra[1], rb[1]);
+  stash(0, ra[0], rb[0]);
+  __syncthreads();
+  for (int c = 0; c < NC; c += 2) {
+    // chunk c (LDS buffer 0).  A stash targets the buffer the PREVIOUS chunk was read from, behind the barrier that ended it.
+    if (c + 2 < NC) fetch(c + 2, ra[0], rb[0]);
+    compute(c, 0);
+    if (c + 1 < NC) stash(1, ra[1], rb[1]);
+    __syncthreads();
+    if (c + 1 >= NC) break;
+    // chunk c + 1 (LDS buffer 1)
+    if (c + 3 < NC) fetch(c + 3, ra[1], rb[1]);
+    compute(c + 1, 1);
+    if (c + 2 < NC) stash(0, ra[0], rb[0]);
+    __syncthreads();
+  }
+
+  // ---------------------------------------------------------------- epilogue (the last barrier freed the operand buffers)
+  float* st = reinterpret_cast<float*>(lb_lds) + w * 32 * SP;        // this wave's 32 rows x BN columns
+  auto affine = [&](bool scaled, bool gelu) __attribute__((always_inline)) {
+#pragma unroll
+    for (int u = 0; u < NB; ++u) {
+      const int col = n0 + 32 * u + l31;
+      if (has[u] && col < g.cout) {
+        const float cv = g.cs[col];
+        const float av = scaled ? g.a[col] : 1.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int row = (r & 3) + 8 * (r >> 2) + 4 * kg;
+          float z = scaled ? __builtin_fmaf(av, acc[u][r], cv) : acc[u][r] + cv;
+          if (gelu) z = gelu_f(z);
+          st[row * SP + 32 * u + l31] = z;
+        }
+      }
+    }
+  };
+  if (g.a) {                                                         // the mode tests once, not per element
+    if (g.act == 1) affine(true, true); else affine(true, false);
+  } else {
+    if (g.act == 1) affine(false, true); else affine(false, false);
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  constexpr int NG = BN / 8;                                         // 8-column segments per row
+  for (int it = lane; it < 32 * NG; it += 64) {
+    const int rl = it / NG, col = n0 + 8 * (it % NG);
+    const long long row = r0 + 32 * w + rl;
+    if (row < g.R && col < g.cout) {
+      float4 z0 = *reinterpret_cast<const float4*>(st + rl * SP + 8 * (it % NG));
+      float4 z1 = *reinterpret_cast<const float4*>(st + rl * SP + 8 * (it % NG) + 4);
+      if (g.res) {
+        const float* rp = g.res + (size_t)row * g.ldr + col;
+        const float4 q0 = *reinterpret_cast<const float4*>(rp), q1 = *reinterpret_cast<const float4*>(rp + 4);
+        z0.x += q0.x; z0.y += q0.y; z0.z += q0.z; z0.w += q0.w;
+        z1.x += q1.x; z1.y += q1.y; z1.z += q1.z; z1.w += q1.w;
+      }
+      if (g.o32) {
+        float* op = g.o32 + (size_t)row * g.ldo32 + col;
+        *reinterpret_cast<float4*>(op) = z0;
+        *reinterpret_cast<float4*>(op + 4) = z1;
+      }
+      if (g.o16)
+        *reinterpret_cast<uint4*>(g.o16 + (size_t)row * g.ldo16 + col) =
+            make_uint4(pack_bf16x2(z0.x, z0.y), pack_bf16x2(z0.z, z0.w), pack_bf16x2(z1.x, z1.y), pack_bf16x2(z1.z, z1.w));
+    }
+  }
+}
+
+template <int NB>
+static hipError_t lb_launch(const LinBf16Args& g, hipStream_t st) {
+  constexpr size_t lds = lb_lds_bytes(NB);
+  if (lds > 64 * 1024) {
+    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_bf16_kernel<NB>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (ea != hipSuccess) return ea;
+  }
+  hipLaunchKernelGGL((linear_bf16_kernel<NB>), dim3((unsigned)(g.tiles_per_xcd * 8)), dim3(LB_NT), lds, st, g);
+  return hipGetLastError();
+}
+
+// The one place that knows the paddings of the fragment array: contraction to 16 (one MFMA step), output columns to 32 (one block).
+static inline int lb_ci_pad(int cin) { return (cin + 15) & ~15; }
+static inline int lb_co_pad(int cout) { return (cout + 31) & ~31; }
+
+// Tiles of the launch for NB column blocks per workgroup; 0 when the grid would not fit an int.
+static long long lb_tiles(int R, int co_pad, int NB, int* col_tiles) {
+  const long long rt = ((long long)R + LB_BM - 1) / LB_BM;
+  *col_tiles = (co_pad + 32 * NB - 1) / (32 * NB);
+  return rt * *col_tiles;
+}
+// Column blocks per workgroup: 128-column tiles while they give every CU (256) a workgroup, 64-column tiles for narrow layers and
+// for matrices of fewer tiles than that.  (Measured at the last stage of GKGNet-576, 10 368 rows x 640 columns = 405 tiles of 128
+// columns: one round of those ran 13-20 % faster than the 810 64-column tiles, which are one full round of 768 resident
+// workgroups plus a tail.)
+static int lb_pick_nb(int R, int co_pad) {
+  int ct;
+  return (co_pad <= 64 || lb_tiles(R, co_pad, 4, &ct) < 256) ? 2 : 4;
+}
+
+}  // namespace gkg
+using namespace gkg;
+
+extern "C" size_t gkg_linear_bf16_planes_bytes(int cin, int cout) {
+  if (cin <= 0 || cout <= 0 || (cin & 7) || (cout & 7)) return 0;
+  return (size_t)(lb_ci_pad(cin) / 8) * lb_co_pad(cout) * 16;
+}
+
+extern "C" int gkg_linear_bf16_supported(int R, int cin, int cout, int has_res, int want_f32, int want_bf16, int act) {
+  (void)has_res;
+  if (R < 1 || cin <= 0 || cout <= 0 || (cin & 7) || (cout & 7) || cin > (1 << 24) || cout > (1 << 24)) return 0;
+  if ((!want_f32 && !want_bf16) || act < 0 || act > 1) return 0;
+  int ct;
+  return lb_tiles(R, lb_co_pad(cout), lb_pick_nb(R, lb_co_pad(cout)), &ct) <= 0x3fffffffLL ? 1 : 0;
+}
+
+extern "C" int gkg_linear_bf16(const void* x, int ldx, const void* wplanes, const float* a, const float* cshift, const float* res,
+                               int ldr, float* out_f32, int ldo32, void* out_bf16, int ldo16, int R, int cin, int cout, int act,
+                               void* stream) {
+  if (!x || !wplanes || !cshift || (!out_f32 && !out_bf16)) return gkg_fail(GKG_ERR_NULL, "gkg_linear_bf16: null pointer");
+  if (R < 1 || cin <= 0 || cout <= 0 || act < 0 || act > 1)
+    return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_bf16: bad sizes (need R >= 1, cin, cout > 0, act in 0..1)");
+  if (!gkg_linear_bf16_supported(R, cin, cout, res != nullptr, out_f32 != nullptr, out_bf16 != nullptr, act))
+    return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_bf16: need cin % 8 == 0, cout % 8 == 0 and a grid that fits");
+  if ((ldx & 7) || (out_bf16 && (ldo16 & 7)) || (out_f32 && (ldo32 & 3)) || (res && (ldr & 3)))
+    return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_bf16: need ldx % 8 == 0, ldo16 % 8 == 0, ldo32 % 4 == 0, ldr % 4 == 0");
+  if (((uintptr_t)x | (uintptr_t)wplanes | (uintptr_t)res | (uintptr_t)out_f32 | (uintptr_t)out_bf16) & 15)
+    return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_bf16: x, wplanes, res and the outputs must be 16-byte aligned");
+  if (ldx < cin || (out_bf16 && ldo16 < cout) || (out_f32 && ldo32 < cout) || (res && ldr < cout))
+    return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_bf16: a row pitch is below the row's width");
+  LinBf16Args g;
+  g.x = (const uint16_t*)x; g.ldx = ldx; g.wp = (const uint4*)wplanes; g.a = a; g.cs = cshift; g.res = res; g.ldr = ldr;
+  g.o32 = out_f32; g.ldo32 = ldo32; g.o16 = (uint16_t*)out_bf16; g.ldo16 = ldo16;
+  g.R = R; g.cin = cin; g.cout = cout; g.ci_pad = lb_ci_pad(cin); g.co_pad = lb_co_pad(cout); g.act = act;
+  const int NB = lb_pick_nb(R, g.co_pad);
+  const long long tiles = lb_tiles(R, g.co_pad, NB, &g.col_tiles);
+  g.tiles = (int)tiles;
+  g.tiles_per_xcd = (int)((tiles + 7) / 8);
+  hipStream_t st = (hipStream_t)stream;
+  const hipError_t e = NB == 4 ? lb_launch<4>(g, st) : lb_launch<2>(g, st);
+  return e == hipSuccess ? 0 : gkg_fail_hip(e, "linear_bf16_kernel");
+}

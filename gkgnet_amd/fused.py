@@ -60,6 +60,11 @@ DETERMINISTIC = os.environ.get("GKG_DETERMINISTIC", "0") != "0"
 #                  bit-exact index contract (neighbour-set agreement 0.91-0.997 with the exact graph), hence
 #                  opt-in since round 4: by default autocast callers get the SAME graphs as fp32 callers (north_star:
 #                  "bit-exact neighbor indices"); bench.py --workload cfg3 / cfg5 prints both legs.
+#   lin_bf16       bf16 inference on the channels-last chain: the four dense projections of a Grapher + FFN pair (fc1, fc2,
+#                  FFN.fc1, FFN.fc2) run on the library's own bf16 kernel with eval-mode BN, GELU, the fp32 residual and both
+#                  output precisions in its epilogue (gkg_linear_bf16; linear_bf16.py) instead of the vendor GEMM (+ a stand-alone
+#                  affine pass).  The BN scale stays fp32 (the weight is not folded), so fc1's rounding differs from the default
+#                  path's.  Opt-in until its per-shape measurements decide the default (EXPERIMENTS.md).
 # GKG_DISABLE — comma-separated list of optimisations to switch off (A/B measurements).  Round 6 cut the list to the eight
 # structural ones (the per-kernel switches of rounds 2-5 are gone with the alternatives they selected):
 #   knn_mr         k-NN + aggregation as one kernel (row g2)          knn_compact   u16 neighbour lists between two launches
@@ -77,6 +82,7 @@ DETERMINISTIC = os.environ.get("GKG_DETERMINISTIC", "0") != "0"
 _DISABLED = _env_list("GKG_DISABLE")
 _ENABLED = _env_list("GKG_ENABLE")
 KNN_BF16 = "knn_bf16" in _ENABLED
+LIN_BF16 = "lin_bf16" in _ENABLED          # a module constant the tests flip (like MR_GEMM)
 
 
 from .planes import (_WeightPlanes, _PLANES, _planes, refresh_weight_planes, param_version,      # noqa: E402,F401  (x6 weight
@@ -406,6 +412,7 @@ def _mm_t(x, W, W16=None):
     return Y if Y.dtype == _F32 else Y.float()
 
 
+from .linear_bf16 import _lin_planes_of, lin_bf16_ok, linear_bf16_eval      # noqa: E402,F401  (GKG_ENABLE=lin_bf16: linear_bf16.py)
 from .layout import _tm_dtype, _TokenMajorToCL, _ToTokenMajor, _BlockEntry, _AvgPoolTM      # noqa: E402  (layout Functions: layout.py)
 
 
@@ -1411,11 +1418,12 @@ def fused_supported(mod, x, groups: int) -> bool:
 
 
 def _lin(x, seq, act=0, residual=None, nchw=None, out_lowp=False, scale=None, rows_per_scale=0, want16=False, alias=False,
-         dual=False, xm=None, knn=None):
+         dual=False, xm=None, knn=None, chain=False):
     """``scale`` (one factor per image; token-major outputs: per ``rows_per_scale`` consecutive rows) multiplies the BN
     output before the residual is added: the reference's DropPath on the branch (torch_vertex.py:332,355,402).
     ``alias``: returns ``(out, x')`` with ``x'`` the input again, to be used as a later layer's residual (see
-    _LinearBNAct.forward)."""
+    _LinearBNAct.forward).  ``chain``: the caller is a Grapher / FFN on the channels-last chain (what GKG_ENABLE=lin_bf16
+    covers)."""
     if alias:
         if not (torch.is_grad_enabled() and x.requires_grad):
             return _lin(x, seq, act, residual, nchw, out_lowp, scale, rows_per_scale, want16, xm=xm, knn=knn), x
@@ -1424,6 +1432,14 @@ def _lin(x, seq, act=0, residual=None, nchw=None, out_lowp=False, scale=None, ro
         return _LinearBNAct.apply(x, conv.weight, conv.bias, bn.weight, bn.bias, residual, bn, act, nchw, out_lowp, w16, scale,
                                   rows_per_scale, want16, True, False, xm, knn)
     conv, bn = seq[0], seq[1]
+    if LIN_BF16 and lin_bf16_ok(LIN_BF16, lowp_inference(), x, conv, bn, chain, nchw, scale, xm, knn, alias, dual):
+        # bf16 inference, opt-in: the library's own projection kernel, BN (+ GELU) (+ residual) and both precisions in its epilogue
+        o32, o16 = linear_bf16_eval(x, conv, bn, act, residual, want_f32=not out_lowp, want_bf16=out_lowp or want16)
+        if out_lowp:
+            return o16
+        if want16:
+            o32._gkg_bf16_tm = o16
+        return o32
     if (FOLD_EPILOGUE and out_lowp and x.dtype == torch.bfloat16 and residual is None and nchw is None and scale is None
             and not torch.is_grad_enabled() and not bn.training and bn.track_running_stats and conv.weight.dim() == 4
             and conv.groups == 1):
@@ -1508,14 +1524,14 @@ def grapher_forward(mod, x, relative_pos, groups: int, want_edge: bool = True):
     if dual:
         x1, xt_r = _lin(xt, mod.fc1, alias=True, xm=xm, knn=knn)    # xt_r: xt again, the (token-major) residual of fc2
     else:
-        x1 = _lin(xt, mod.fc1, xm=xm, knn=knn)                      # fc1 + BN
+        x1 = _lin(xt, mod.fc1, xm=xm, knn=knn, chain=cl)            # fc1 + BN
     x1b = x1 if xm is not None else x1.view(B, N, C)
     yb = None
     if gc.r > 1:                                                    # pooled keys (torch_vertex.py:194-196)
         yb = _AvgPoolTM.apply(x1b, H, W, gc.r)
     a2, edge = _graph_and_project(x1b, yb, relative_pos, gc, groups, C, lp, want_edge)
     if cl:                                                          # fc2 + BN (+ DropPath) + residual, token-major = channels-last
-        out = _lin(a2, mod.fc2, residual=x, scale=scale, rows_per_scale=N, want16=lp)
+        out = _lin(a2, mod.fc2, residual=x, scale=scale, rows_per_scale=N, want16=lp, chain=True)
         return _cl_out(out, B, H, W), edge
     if dual:
         # ... and, once the label block behind has said which k-NN problem it solves over this map (KnnProblem.announce), the same pass
@@ -1596,8 +1612,9 @@ def ffn_forward(mod, x):
     lp = lowp_inference()
     B, C, H, W = x.shape
     xt, x, cl = _block_entry(x, lp)
-    h = _lin(xt, mod.fc1, act=1, out_lowp=lp)
+    h = _lin(xt, mod.fc1, act=1, out_lowp=lp, chain=cl)
     if cl:
-        out = _lin(h, mod.fc2, residual=x, scale=_drop_scale(mod.drop_path, B, x.device), rows_per_scale=H * W, want16=lp)
+        out = _lin(h, mod.fc2, residual=x, scale=_drop_scale(mod.drop_path, B, x.device), rows_per_scale=H * W, want16=lp,
+                   chain=True)
         return _cl_out(out, B, H, W)
     return _lin(h, mod.fc2, residual=x, nchw=(B, C, H, W), scale=_drop_scale(mod.drop_path, B, x.device))

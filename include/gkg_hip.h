@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define GKG_ABI_VERSION 13
+#define GKG_ABI_VERSION 14
 
 /* dtype codes */
 #define GKG_F32 0
@@ -349,6 +349,36 @@ int gkg_mr_linear_bf16(const float* x, const float* src, const int64_t* nn_idx, 
 int gkg_mr_linear_bf16_nn16(const float* x, const float* src, const uint16_t* nn16, const void* wplanes, const float* a,
                             const float* cshift, void* out, int ldo, int B, int G, int c, int N, int M, int k, int act,
                             void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Inference, bf16 operands: a dense 1x1 projection with its eval-mode BN, activation and residual as ONE launch
+ * (csrc/gkg_linear_bf16.hip).  The layers are Conv2d(1x1) + BN of Grapher.fc1 / fc2 (reference torch_vertex.py:290-306), FFN.fc1 /
+ * fc2 (gkgnet.py:46-72: fc1 + GELU, fc2 + shortcut) and the Conv2d + BN (+ GELU) of BasicConv (torch_nn.py:57-69), for callers under
+ * bf16 autocast with gradients off.  Token-major rows:
+ *   x (R, ldx) bf16, columns [0, cin) read
+ *   wplanes: bf16 weight fragments [ci_pad/8][co_pad][8], fragment (f, n) = w[n][8f .. 8f+7] (zero outside cin / cout) — the
+ *            gkg_mr_linear_bf16 layout with one group; ci_pad = cin rounded up to 16, co_pad = cout rounded up to 32;
+ *            gkg_linear_bf16_planes_bytes(cin, cout) bytes (0: invalid sizes), the only place that encodes the paddings
+ *   acc[r][n] = sum_k x[r][k] * w[n][k]         exact bf16 x bf16 products, fp32 accumulation on v_mfma_f32_32x32x16_bf16
+ *   z = fmaf(a[n], acc, cshift[n])              a == NULL: z = acc + cshift[n] (a, cshift: [cout] fp32, e.g. gkg_bn_eval_affine)
+ *   act == 1: z = GELU(z)                       the erf form all kernels of the library share (|erf error| <= 1.5e-7): the bits of
+ *                                               gkg_affine_act's GELU
+ *   res != NULL: z += res[r][n]                 res (R, ldr) fp32; an fp32 add AFTER the activation, the order of gkg_affine_act
+ *   out_f32[r][n] = z (row pitch ldo32),  out_bf16[r][n] = round-to-nearest-even(z) (row pitch ldo16); at least one of the two is
+ *   non-NULL, with both the bf16 output is the rounding of the fp32 one (gkg_affine_act_dual's pair).  Nothing outside columns
+ *   [0, cout) of rows [0, R) of either output is written, nothing outside [0, cin) / [0, cout) of a row of x / res is read.
+ * R, cin and cout need not be multiples of any tile; row offsets are 64-bit.  Preconditions, otherwise GKG_ERR_UNSUPPORTED with
+ * nothing launched: R >= 1, cin % 8 == 0, cout % 8 == 0, ldx % 8 == 0, ldo16 % 8 == 0, ldo32 % 4 == 0, ldr % 4 == 0 (pitches of
+ * absent operands are ignored), x / wplanes / res / out_f32 / out_bf16 16-byte aligned.  A pitch below its row's width is
+ * GKG_ERR_SHAPE.  gkg_linear_bf16_supported: 1 when the sizes pass (pure host code; pitches and pointers are the call's to check). */
+int gkg_linear_bf16_supported(int R, int cin, int cout, int has_res, int want_f32, int want_bf16, int act);
+size_t gkg_linear_bf16_planes_bytes(int cin, int cout);
+int gkg_linear_bf16(const void* x /* bf16 (R, ldx) */, int ldx, const void* wplanes,
+                    const float* a /* [cout] or NULL = 1 */, const float* cshift /* [cout] */,
+                    const float* res /* fp32 (R, ldr) or NULL */, int ldr,
+                    float* out_f32 /* (R, ldo32) or NULL */, int ldo32,
+                    void* out_bf16 /* (R, ldo16) or NULL */, int ldo16,
+                    int R, int cin, int cout, int act /* 0 none, 1 GELU */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Bandwidth kernels between the dense 1x1 projections (Conv2d 1x1 + SyncBN [+ GELU], reference
