@@ -88,6 +88,107 @@ __global__ __launch_bounds__(256) void nchw_to_tm_kernel(const float* __restrict
   }
 }
 
+// The fp32 -> fp32 forms of the pass above with 16-byte accesses on both sides (tm_wide_form: N and C multiples of 4, 16-byte
+// aligned operands, no img_scale).  ADD: + add_tm; STATS: also the BN-backward statistics pass, as above.
+// Tile: TW_C = 32 channels x tn4 <= 32 float4 of tokens; the host cuts an image's N / 4 float4 columns into equal tiles (N = 324:
+// 81 -> 3 x 27, nothing wasted; ceil(N / 128) tiles, so the statistics form issues exactly the atomics of the form above).
+//   load   thread i of the tile (channel i / tn4, float4 column i % tn4): one float4 along the token axis, up to four a thread,
+//          requested together — with them the addend and y of the thread's (up to four) outputs (plain: 4, add + statistics:
+//          14 requests before the first wait; the add-only and statistics-only forms wait once after six)
+//   LDS    tile[channel][128 tokens], the 16-byte slot of float4 column n4 of channel ch at n4 ^ ((ch >> 2) & 7): written with
+//          one 16-byte store (eight consecutive lanes = eight different slots mod 8), read back dword by dword for output
+//          (token, channels 4 c4 .. 4 c4 + 3) — a half wave is 8 c4 x 4 tokens of one slot row: bank 4 ((tok >> 2) ^ c4) + (tok & 3),
+//          all 32 different
+//   store  one float4 along the channel axis: 8 lanes = the 128 bytes of the tile's 32 channels of one token
+// `out` has the bits of the form above: x, or one fp32 add.
+constexpr int TW_C = 32;
+
+template <bool ADD, bool STATS>
+__global__ __launch_bounds__(256) void nchw_to_tm_wide_kernel(const float* __restrict__ x, float* __restrict__ out, int C, int N,
+                                                              int tn4, const float* __restrict__ add_tm,
+                                                              const float* __restrict__ y, const float* __restrict__ mean,
+                                                              const float* __restrict__ invstd, double* __restrict__ asums) {
+  __shared__ __align__(16) float tile[TW_C * 128];
+  const int tid = threadIdx.x, b = blockIdx.z, c0 = blockIdx.y * TW_C, n40 = blockIdx.x * tn4;
+  const int N4 = N >> 2;
+  const int here4 = min(tn4, N4 - n40);                   // float4 columns of this tile
+  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 xv[4];
+  int slot[4];                                            // 16-byte slot of the thread's k-th float4 in the tile, < 0: none
+  // (the LDS store below tests `slot`, not the load's own guard, on purpose: a load whose only use sits under the guard it was
+  // issued under is sunk into that branch and waited for there, one request at a time)
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int i = tid + 256 * k, ch = i / tn4, n4 = i - ch * tn4;
+    const bool ok = ch < TW_C && c0 + ch < C && n4 < here4;
+    xv[k] = z4;
+    if (ok) xv[k] = *reinterpret_cast<const float4*>(x + ((size_t)b * C + c0 + ch) * N + 4 * (n40 + n4));
+    slot[k] = ok ? ch * 32 + (n4 ^ ((ch >> 2) & 7)) : -1;
+  }
+  const int c4 = tid & 7, tk = tid >> 3;                  // output: channels c0 + 4 c4 .., local tokens tk + 32 k
+  const bool ch_ok = c0 + 4 * c4 < C;
+  float4 av[4], yv[4], m4, i4;
+  if constexpr (ADD || STATS) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int tok = tk + 32 * k;
+      const bool ok = ch_ok && tok < 4 * here4;
+      const size_t o = ((size_t)b * N + 4 * n40 + tok) * C + c0 + 4 * c4;
+      if constexpr (ADD) av[k] = z4;
+      if constexpr (STATS) yv[k] = z4;
+      if (ok) {
+        if constexpr (ADD) av[k] = *reinterpret_cast<const float4*>(add_tm + o);
+        if constexpr (STATS) yv[k] = *reinterpret_cast<const float4*>(y + o);
+      }
+    }
+    if constexpr (STATS) {
+      m4 = *reinterpret_cast<const float4*>(mean + c0 + (ch_ok ? 4 * c4 : 0));
+      i4 = *reinterpret_cast<const float4*>(invstd + c0 + (ch_ok ? 4 * c4 : 0));
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (slot[k] >= 0) reinterpret_cast<float4*>(tile)[slot[k]] = xv[k];
+  __syncthreads();
+  float4 s0 = z4, s1 = z4;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int tok = tk + 32 * k;
+    if (ch_ok && tok < 4 * here4) {
+      const float* p = &tile[4 * c4 * 128 + 4 * ((tok >> 2) ^ c4) + (tok & 3)];
+      float4 v = make_float4(p[0], p[128], p[256], p[384]);
+      if constexpr (ADD) { v.x += av[k].x; v.y += av[k].y; v.z += av[k].z; v.w += av[k].w; }
+      *reinterpret_cast<float4*>(out + ((size_t)b * N + 4 * n40 + tok) * C + c0 + 4 * c4) = v;
+      if constexpr (STATS) {
+        s0.x += v.x; s0.y += v.y; s0.z += v.z; s0.w += v.w;
+        s1.x += v.x * ((yv[k].x - m4.x) * i4.x); s1.y += v.y * ((yv[k].y - m4.y) * i4.y);
+        s1.z += v.z * ((yv[k].z - m4.z) * i4.z); s1.w += v.w * ((yv[k].w - m4.w) * i4.w);
+      }
+    }
+  }
+  if constexpr (STATS) {
+    __shared__ double red[4][2][TW_C];
+    double d[8] = {(double)s0.x, (double)s0.y, (double)s0.z, (double)s0.w, (double)s1.x, (double)s1.y, (double)s1.z, (double)s1.w};
+#pragma unroll
+    for (int off = 8; off < 64; off <<= 1)                // the eight lanes of a wave that share c4
+#pragma unroll
+      for (int k = 0; k < 8; ++k) d[k] += __shfl_xor(d[k], off);
+    if ((tid & 63) < 8) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        red[tid >> 6][0][4 * c4 + k] = d[k];
+        red[tid >> 6][1][4 * c4 + k] = d[4 + k];
+      }
+    }
+    __syncthreads();
+    if (tid < 2 * TW_C) {
+      const int which = tid / TW_C, col = tid % TW_C;
+      const double acc = ((red[0][which][col] + red[1][which][col]) + red[2][which][col]) + red[3][which][col];
+      if (c0 + col < C) __hip_atomic_fetch_add(asums + (size_t)which * C + c0 + col, acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
 // out(B,C,N) = act(a[ch]*y_tm[t][ch] + c[ch]) + res(B,C,N)     (a/c/res optional)
 __global__ __launch_bounds__(256) void tm_affine_to_nchw_kernel(const float* __restrict__ y, const float* __restrict__ a,
                                                                 const float* __restrict__ cs, const float* __restrict__ res,
@@ -860,6 +961,24 @@ extern "C" size_t gkg_bn_workspace_bytes(int R, int C, int nb) {
   return (size_t)nb * (nblk + 1) * 2 * C * sizeof(float);
 }
 
+// The rule for nchw_to_tm_wide_kernel (fp32 out, no img_scale — the callers see to those two): float4 along the token axis needs
+// N % 4 == 0, float4 along the channel axis C % 4 == 0, and every operand it reads or writes that way 16-byte aligned (NULL
+// counts as aligned).  Everything else — bf16 output, DropPath scale, 7x7 and 9x9 maps, views at an odd offset — keeps
+// nchw_to_tm_kernel.
+static bool tm_wide_form(int C, int N, const void* x, const void* out, const void* add_tm, const void* y,
+                         const void* mean = nullptr, const void* invstd = nullptr) {
+  return (N & 3) == 0 && (C & 3) == 0 && (((size_t)x | (size_t)out | (size_t)add_tm | (size_t)y | (size_t)mean | (size_t)invstd) & 15) == 0;
+}
+
+template <bool ADD, bool STATS>
+static void tm_wide_launch(const float* x, float* out, int B, int C, int N, const float* add_tm, const float* y, const float* mean,
+                           const float* invstd, double* sums, hipStream_t st) {
+  const int N4 = N >> 2, tiles = (N4 + 31) / 32;          // equal token tiles of at most 32 float4
+  const int tn4 = (N4 + tiles - 1) / tiles;
+  hipLaunchKernelGGL((nchw_to_tm_wide_kernel<ADD, STATS>), dim3((N4 + tn4 - 1) / tn4, (C + TW_C - 1) / TW_C, B), dim3(256), 0, st, x, out, C, N,
+                     tn4, add_tm, y, mean, invstd, sums);
+}
+
 extern "C" int gkg_nchw_to_tm(const float* x, void* out, int B, int C, int N, int out_dtype, const float* img_scale,
                               void* stream) {
   if (!x || !out) return gkg_fail(GKG_ERR_NULL, "gkg_nchw_to_tm: null pointer");
@@ -867,6 +986,7 @@ extern "C" int gkg_nchw_to_tm(const float* x, void* out, int B, int C, int N, in
   if (out_dtype != GKG_F32 && out_dtype != GKG_BF16) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_nchw_to_tm: out_dtype is GKG_F32 or GKG_BF16");
   dim3 grid((N + 31) / 32, (C + 31) / 32, B);
   if (out_dtype == GKG_BF16) hipLaunchKernelGGL(nchw_to_tm_kernel<uint16_t>, grid, dim3(256), 0, (hipStream_t)stream, x, (uint16_t*)out, C, N, img_scale);
+  else if (!img_scale && tm_wide_form(C, N, x, out, nullptr, nullptr)) tm_wide_launch<false, false>(x, (float*)out, B, C, N, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
   else hipLaunchKernelGGL(nchw_to_tm_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, x, (float*)out, C, N, img_scale);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : gkg_fail_hip(e, "nchw_to_tm_kernel");
@@ -878,7 +998,8 @@ extern "C" int gkg_nchw_to_tm_add(const float* x, const float* add_tm, float* ou
   if (!x || !add_tm || !out) return gkg_fail(GKG_ERR_NULL, "gkg_nchw_to_tm_add: null pointer");
   if (B <= 0 || C <= 0 || N <= 0 || B > 65535) return gkg_fail(GKG_ERR_SHAPE, "gkg_nchw_to_tm_add: bad sizes");
   dim3 grid((N + 31) / 32, (C + 31) / 32, B);
-  hipLaunchKernelGGL(nchw_to_tm_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, x, out, C, N, (const float*)nullptr, add_tm);
+  if (tm_wide_form(C, N, x, out, add_tm, nullptr)) tm_wide_launch<true, false>(x, out, B, C, N, add_tm, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
+  else hipLaunchKernelGGL(nchw_to_tm_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, x, out, C, N, (const float*)nullptr, add_tm);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : gkg_fail_hip(e, "nchw_to_tm_kernel (add)");
 }
@@ -892,7 +1013,11 @@ extern "C" int gkg_nchw_to_tm_add_bnstats(const float* x, const float* add_tm, f
   if (!x || !out || !y || !mean || !invstd || !sums) return gkg_fail(GKG_ERR_NULL, "gkg_nchw_to_tm_add_bnstats: null pointer");
   if (B <= 0 || C <= 0 || N <= 0 || B > 65535) return gkg_fail(GKG_ERR_SHAPE, "gkg_nchw_to_tm_add_bnstats: bad sizes");
   dim3 grid((N + 127) / 128, (C + 31) / 32, B);
-  hipLaunchKernelGGL((nchw_to_tm_kernel<float, true>), grid, dim3(256), 0, (hipStream_t)stream, x, out, C, N, (const float*)nullptr, add_tm,
+  if (tm_wide_form(C, N, x, out, add_tm, y, mean, invstd)) {
+    if (add_tm) tm_wide_launch<true, true>(x, out, B, C, N, add_tm, y, mean, invstd, sums, (hipStream_t)stream);
+    else tm_wide_launch<false, true>(x, out, B, C, N, add_tm, y, mean, invstd, sums, (hipStream_t)stream);
+  }
+  else hipLaunchKernelGGL((nchw_to_tm_kernel<float, true>), grid, dim3(256), 0, (hipStream_t)stream, x, out, C, N, (const float*)nullptr, add_tm,
                      y, mean, invstd, sums);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : gkg_fail_hip(e, "nchw_to_tm_kernel (add + BN backward statistics)");
@@ -1155,6 +1280,9 @@ static int bn_bwd_atomic_impl(const float* dout, const float* y, const float* a,
                               const float* count) {
   // (A one-launch form with a grid barrier was built and measured in round 5 — a barrier of a few hundred workgroups costs
   // more than the kernel boundary it replaces, EXPERIMENTS.md — and removed in round 6.)
+  // (A one-launch form WITHOUT waiting — a workgroup owns a strip of 8 or 16 channels over all R <= 4096 rows and keeps it in
+  // registers between the statistics and the apply phase — was measured in round 12: C / 8 workgroups cannot pull a cold matrix
+  // in: 17.0 us against 7.1 + 5.0 us at 2 560 x 320 inside the cfg2 step; EXPERIMENTS.md.  Not kept.)
   int rpb;
   const int nblk = stats_blocks(R, C, nb, &rpb);
   hipStream_t st = (hipStream_t)stream;
