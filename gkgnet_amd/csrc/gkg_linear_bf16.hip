@@ -25,10 +25,32 @@
 // The LDS allows 2 (<4>) / 3 (<2>) workgroups of 4 waves per CU, i.e. the same 2 / 3 waves per SIMD: registers and LDS agree.
 // (The straight-line chunk body and the edge-tile body keep separate accumulator registers: 138 / 94 VGPRs before them, at
 // 5–10 % more time per layer.)
+//
+// PREP = true (gkg_linear_bf16_knn_prep: a Grapher's fc1, fp32 result only): the same tiling, accumulation order and epilogue, then
+// the launch also prepares its output as the QUERIES of the k-NN call behind it (gkg_knn_prep.h: token_prep_coop_body — the ordered
+// chains need a token's whole group, c = 12 .. 320 channels, which a column tile holds only for the narrowest layers).  Where one
+// column tile covers all of cout, the workgroup prepares the rows it has just stored.  Otherwise every workgroup stores its tile
+// write-through, drains the stores, meets and counts its arrival in a per-row-tile counter; the LAST of a row tile's column tiles
+// acquires, re-arms the counter (zero on entry, zero on exit: no memset per call) and walks the tile's rows — per image the tile meets, per
+// group, TK = 64 / 32 / 16 tokens at a time (c <= 192 / 384 / 600: c (TK + 1) floats in the operand LDS, free by then), reading the
+// rows back from `out` (just written by the same XCD's neighbours where the column tiles are adjacent).  Where the k-NN call's
+// plan has prefilter planes, the tile's hi / lo planes follow from the normalised tile in LDS, and the row tile that holds an
+// image's last token writes that image's pad rows: one writer per (b, g).  Narrow groups (c <= 52: c x 256 floats fit) take
+// token_prep_flat_rows instead: one thread per (row, group) pair and no barrier, one pass per two groups.  Measured (MI355X,
+// tools/bench_lin_bf16.py --prep; the rule and its table: linear_bf16.py prep_pays): it pays where one column tile holds every
+// group and the groups are narrow — the stage-1 shapes, fc1 94 -> 220 us against a 145 us preparation launch — and loses wherever
+// a last arrival works alone behind its neighbours.  The plan (workspace offsets, cpad, planes or not) is
+// knn_fwd_impl's own (knn_query_prep_plan), nothing of it is restated here.
+//   linear_bf16_kernel<4, true>   237 VGPRs, 0 AGPRs, 106 SGPRs   same LDS, no scratch   2 waves / SIMD
+//   linear_bf16_kernel<2, true>   155 VGPRs, 0 AGPRs, 106 SGPRs   same LDS, no scratch   3 waves / SIMD
+// The non-PREP instantiations are unchanged by the parameter (234 / 66 and 152 / 62 as above).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "gkg_common.h"
+#include "gkg_knn_prep.h"
 
 namespace gkg {
 
@@ -53,10 +75,53 @@ struct LinBf16Args {
   int col_tiles, tiles, tiles_per_xcd;
 };
 
-constexpr size_t lb_lds_bytes(int NB) { return 2 * (size_t)(LB_ABYTES + (LB_KC / 8) * 32 * NB * 16); }
+// PREP (gkg_linear_bf16_knn_prep): the layer is a Grapher's fc1 and the launch also prepares its output as the QUERIES of the k-NN
+// call behind it.  q: the queries' set of that call's own plan (knn_query_prep_plan; q.s.t == o32, token-major rows of B images x
+// N tokens, G groups of c channels); cnt: one arrival counter per row tile, zero between launches.
+struct LinBf16PrepArgs : LinBf16Args { KnnQueryPrep q; unsigned* cnt; int B, G, c, N; };
 
-template <int NB>
-__global__ __launch_bounds__(LB_NT, 2) void linear_bf16_kernel(LinBf16Args g) {
+constexpr size_t lb_lds_bytes(int NB) { return 2 * (size_t)(LB_ABYTES + (LB_KC / 8) * 32 * NB * 16); }
+// tokens per cooperative preparation tile: c (TK + 1) floats fit the operand buffers of either tile form (53 248 B)
+constexpr bool lb_prep_fits(int cmax, int TK) { return (size_t)cmax * (TK + 1) * 4 <= lb_lds_bytes(2); }
+static_assert(lb_prep_fits(192, 64) && lb_prep_fits(384, 32) && lb_prep_fits(600, 16), "the preparation tile must fit the operand buffers");
+
+// A 16-byte store that goes through to memory at device scope (what a relaxed agent-scope atomic store is, per dword): visible to
+// the other XCDs' workgroups once the issuing wave's store counter has drained.
+typedef float lb_f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void lb_store_wt(float* p, const float4& v) {
+  const lb_f32x4 d = {v.x, v.y, v.z, v.w};
+  asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(p), "v"(d) : "memory");
+}
+
+// The last workgroup of a row tile prepares the tile's tokens, rows [row, rend) of `out`: per image the tile meets, per group, TK
+// tokens at a time (token_prep_coop_body: the bits of the stand-alone launch), the prefilter planes where the plan has them, and
+// the planes' pad rows for the image whose last token the tile holds (one row tile per image: one writer per (b, g)).
+template <bool NORM, int TK>
+__device__ __forceinline__ void lb_prep_rows(const LinBf16PrepArgs& g, float* col, long long row, long long rend) {
+  const PrepSet& S = g.q.s;
+  const bool planes = S.tb_lo != nullptr;
+  while (row < rend) {
+    const int b = (int)(row / g.N), nlo = (int)(row - (long long)b * g.N);
+    const int nhi = (int)min((long long)g.N, nlo + (rend - row));
+    for (int gi = 0; gi < g.G; ++gi) {
+      const int bg = b * g.G + gi;
+      for (int n0 = nlo; n0 < nhi; n0 += TK) {
+        const int nt = min(TK, nhi - n0);
+        token_prep_coop_body<NORM, TK, false>(S, col, bg, n0, nt, g.c, g.q.cpad, BnDerive{}, nullptr, nullptr);
+        if (planes) {
+          __syncthreads();
+          token_prep_planes_tile<TK>(S, col, bg, n0, nt, g.c);
+        }
+        __syncthreads();                       // the tile is free again
+      }
+      if (planes && nhi == g.N) token_prep_planes_pad(S, bg, g.c);
+    }
+    row += nhi - nlo;
+  }
+}
+
+template <int NB, bool PREP = false>
+__global__ __launch_bounds__(LB_NT, 2) void linear_bf16_kernel(std::conditional_t<PREP, LinBf16PrepArgs, LinBf16Args> g) {
   extern __shared__ __align__(16) unsigned char lb_lds[];
   constexpr int BN = 32 * NB;
   constexpr int BBYTES = (LB_KC / 8) * BN * 16;
@@ -202,25 +267,71 @@ __global__ __launch_bounds__(LB_NT, 2) void linear_bf16_kernel(LinBf16Args g) {
       }
       if (g.o32) {
         float* op = g.o32 + (size_t)row * g.ldo32 + col;
-        *reinterpret_cast<float4*>(op) = z0;
-        *reinterpret_cast<float4*>(op + 4) = z1;
+        if (PREP && g.col_tiles > 1) {                               // another workgroup prepares these rows: write-through stores
+          lb_store_wt(op, z0);
+          lb_store_wt(op + 4, z1);
+        } else {
+          *reinterpret_cast<float4*>(op) = z0;
+          *reinterpret_cast<float4*>(op + 4) = z1;
+        }
       }
       if (g.o16)
         *reinterpret_cast<uint4*>(g.o16 + (size_t)row * g.ldo16 + col) =
             make_uint4(pack_bf16x2(z0.x, z0.y), pack_bf16x2(z0.z, z0.w), pack_bf16x2(z1.x, z1.y), pack_bf16x2(z1.z, z1.w));
     }
   }
+  if constexpr (PREP) {
+    if (g.col_tiles > 1) {
+      // The hand-off of the split-K last-arriver reduce (gkg_gemm_x6_tile.h), without cache-wide fences (an agent-scope release
+      // writes the whole L2 back — once per workgroup here: measured 1.4 ms on a 98 us launch): the tile went out write-through
+      // (lb_store_wt), every wave drains its stores, the workgroup meets, ONE lane counts the arrival; the last of the row tile's
+      // column tiles acquires (its L1 is the only cache that could hold stale lines of `out`), re-arms the counter for the next
+      // launch and prepares the rows.
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      unsigned* flag = reinterpret_cast<unsigned*>(lb_lds);          // (the barrier freed the epilogue stage)
+      if (tid == 0) *flag = __hip_atomic_fetch_add(g.cnt + rt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __syncthreads();
+      const bool last = *flag == (unsigned)(g.col_tiles - 1);
+      __syncthreads();                                               // everyone has read the flag: the LDS is the preparation's
+      if (!last) return;
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      if (tid == 0) __hip_atomic_store(g.cnt + rt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else {
+      // one column tile holds every group: the workgroup prepares the rows it has just stored itself
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+      __syncthreads();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+    float* col = reinterpret_cast<float*>(lb_lds);
+    const long long rend = min(r0 + LB_BM, (long long)g.R);
+    const int c = g.c;
+    if ((size_t)c * LB_NT * sizeof(float) <= lb_lds_bytes(2)) {
+      // narrow groups (c <= 52): one thread per (row, group) pair, no barriers — one pass per two groups instead of 2 G dependent
+      // cooperative tiles (measured at the stage-1 shape of GKGNet-576, c = 40: 205 us of tail with the cooperative form)
+      if (g.q.norm) token_prep_flat_rows<true>(g.q.s, col, r0, (int)(rend - r0), g.G, c, g.q.cpad);
+      else token_prep_flat_rows<false>(g.q.s, col, r0, (int)(rend - r0), g.G, c, g.q.cpad);
+    } else if (g.q.norm) {
+      if (c <= 192) lb_prep_rows<true, 64>(g, col, r0, rend);
+      else if (c <= 384) lb_prep_rows<true, 32>(g, col, r0, rend);
+      else lb_prep_rows<true, 16>(g, col, r0, rend);
+    } else {
+      if (c <= 192) lb_prep_rows<false, 64>(g, col, r0, rend);
+      else if (c <= 384) lb_prep_rows<false, 32>(g, col, r0, rend);
+      else lb_prep_rows<false, 16>(g, col, r0, rend);
+    }
+  }
 }
 
-template <int NB>
-static hipError_t lb_launch(const LinBf16Args& g, hipStream_t st) {
+template <int NB, bool PREP = false, typename Args>
+static hipError_t lb_launch(const Args& g, hipStream_t st) {
   constexpr size_t lds = lb_lds_bytes(NB);
   if (lds > 64 * 1024) {
-    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_bf16_kernel<NB>),
+    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_bf16_kernel<NB, PREP>),
                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (ea != hipSuccess) return ea;
   }
-  hipLaunchKernelGGL((linear_bf16_kernel<NB>), dim3((unsigned)(g.tiles_per_xcd * 8)), dim3(LB_NT), lds, st, g);
+  hipLaunchKernelGGL((linear_bf16_kernel<NB, PREP>), dim3((unsigned)(g.tiles_per_xcd * 8)), dim3(LB_NT), lds, st, g);
   return hipGetLastError();
 }
 
@@ -241,6 +352,19 @@ static long long lb_tiles(int R, int co_pad, int NB, int* col_tiles) {
 static int lb_pick_nb(int R, int co_pad) {
   int ct;
   return (co_pad <= 64 || lb_tiles(R, co_pad, 4, &ct) < 256) ? 2 : 4;
+}
+
+// The launch's arguments and tile form (returned: column blocks per workgroup) for checked operands
+static int lb_fill(LinBf16Args& g, const void* x, int ldx, const void* wplanes, const float* a, const float* cshift, const float* res,
+                   int ldr, float* out_f32, int ldo32, void* out_bf16, int ldo16, int R, int cin, int cout, int act) {
+  g.x = (const uint16_t*)x; g.ldx = ldx; g.wp = (const uint4*)wplanes; g.a = a; g.cs = cshift; g.res = res; g.ldr = ldr;
+  g.o32 = out_f32; g.ldo32 = ldo32; g.o16 = (uint16_t*)out_bf16; g.ldo16 = ldo16;
+  g.R = R; g.cin = cin; g.cout = cout; g.ci_pad = lb_ci_pad(cin); g.co_pad = lb_co_pad(cout); g.act = act;
+  const int NB = lb_pick_nb(R, g.co_pad);
+  const long long tiles = lb_tiles(R, g.co_pad, NB, &g.col_tiles);
+  g.tiles = (int)tiles;
+  g.tiles_per_xcd = (int)((tiles + 7) / 8);
+  return NB;
 }
 
 }  // namespace gkg
@@ -274,14 +398,62 @@ extern "C" int gkg_linear_bf16(const void* x, int ldx, const void* wplanes, cons
   if (ldx < cin || (out_bf16 && ldo16 < cout) || (out_f32 && ldo32 < cout) || (res && ldr < cout))
     return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_bf16: a row pitch is below the row's width");
   LinBf16Args g;
-  g.x = (const uint16_t*)x; g.ldx = ldx; g.wp = (const uint4*)wplanes; g.a = a; g.cs = cshift; g.res = res; g.ldr = ldr;
-  g.o32 = out_f32; g.ldo32 = ldo32; g.o16 = (uint16_t*)out_bf16; g.ldo16 = ldo16;
-  g.R = R; g.cin = cin; g.cout = cout; g.ci_pad = lb_ci_pad(cin); g.co_pad = lb_co_pad(cout); g.act = act;
-  const int NB = lb_pick_nb(R, g.co_pad);
-  const long long tiles = lb_tiles(R, g.co_pad, NB, &g.col_tiles);
-  g.tiles = (int)tiles;
-  g.tiles_per_xcd = (int)((tiles + 7) / 8);
+  const int NB = lb_fill(g, x, ldx, wplanes, a, cshift, res, ldr, out_f32, ldo32, out_bf16, ldo16, R, cin, cout, act);
   hipStream_t st = (hipStream_t)stream;
   const hipError_t e = NB == 4 ? lb_launch<4>(g, st) : lb_launch<2>(g, st);
   return e == hipSuccess ? 0 : gkg_fail_hip(e, "linear_bf16_kernel");
+}
+
+// ---------------------------------------------------------------------------------------------- fc1 + the k-NN's token preparation
+// Scope of the fused form (include/gkg_hip.h): queries of a plain token-major output, fp32 contraction.  0: in scope.
+static int lbp_scope(int ochunk, int as_keys, const float* res_tm, const float* out_nchw, unsigned knn_flags) {
+  return (ochunk != 0 || as_keys != 0 || res_tm || out_nchw || (knn_flags & GKG_KNN_BF16_CONTRACT)) ? GKG_ERR_UNSUPPORTED : 0;
+}
+static bool lbp_sizes_ok(int cin, int B, int G, int c, int N) {
+  if (B <= 0 || G <= 0 || c <= 0 || N <= 0 || (c & 3)) return false;
+  if ((long long)B * N > 0x7fffffffLL || (long long)G * c > (1 << 24)) return false;
+  return gkg_linear_bf16_supported(B * N, cin, G * c, 0, 1, 0, 0) != 0;
+}
+
+extern "C" size_t gkg_linear_bf16_knn_prep_scratch_bytes(int R) {
+  return R < 1 ? 0 : sizeof(unsigned) * (size_t)(((long long)R + LB_BM - 1) / LB_BM);      // one arrival counter per row tile
+}
+
+extern "C" int gkg_linear_bf16_knn_prep_supported(int cin, int B, int G, int c, int N, int M, int k, int dilation, int has_y,
+                                                  int has_relpos, unsigned knn_flags, int fused_mr) {
+  if (lbp_scope(0, 0, nullptr, nullptr, knn_flags) != 0 || !lbp_sizes_ok(cin, B, G, c, N)) return 0;
+  static float dummy[4];                            // the plan only computes addresses: nothing is read or written
+  KnnQueryPrep q;
+  return knn_query_prep_plan(dummy, G * c, B, G, c, N, M, k, dilation, has_y, has_relpos, knn_flags, fused_mr, dummy, ~(size_t)0, &q) == 0;
+}
+
+extern "C" int gkg_linear_bf16_knn_prep(const void* x, int ldx, const void* wplanes, int cin, const float* a, const float* cshift,
+                                        float* out, int ldo, int ochunk, int B, int G, int c, int N, int M, int k, int dilation,
+                                        int has_y, int has_relpos, unsigned knn_flags, int fused_mr, int as_keys, const float* res_tm,
+                                        float* out_nchw, void* knn_workspace, size_t knn_workspace_bytes, void* scratch,
+                                        size_t scratch_bytes, void* stream) {
+  if (!x || !wplanes || !cshift || !out || !knn_workspace) return gkg_fail(GKG_ERR_NULL, "gkg_linear_bf16_knn_prep: null pointer");
+  if (lbp_scope(ochunk, as_keys, res_tm, out_nchw, knn_flags) != 0)
+    return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_bf16_knn_prep: queries into plain rows only (no ochunk, as_keys, res_tm, out_nchw, bf16 contraction)");
+  if (B <= 0 || G <= 0 || c <= 0 || N <= 0 || cin <= 0) return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_bf16_knn_prep: bad sizes");
+  if (!lbp_sizes_ok(cin, B, G, c, N))
+    return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_bf16_knn_prep: need c % 4 == 0, cin % 8 == 0, (G c) % 8 == 0 and a grid that fits");
+  const int R = B * N, cout = G * c;
+  if (ldo == 0) ldo = cout;
+  if ((ldx & 7) || (ldo & 3)) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_bf16_knn_prep: need ldx % 8 == 0, ldo % 4 == 0");
+  if (((uintptr_t)x | (uintptr_t)wplanes | (uintptr_t)out) & 15)
+    return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_bf16_knn_prep: x, wplanes and out must be 16-byte aligned");
+  if (ldx < cin || ldo < cout) return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_bf16_knn_prep: a row pitch is below the row's width");
+  if (!scratch || ((uintptr_t)scratch & 3) || scratch_bytes < gkg_linear_bf16_knn_prep_scratch_bytes(R))
+    return gkg_fail(GKG_ERR_WORKSPACE, "gkg_linear_bf16_knn_prep: scratch too small (see gkg_linear_bf16_knn_prep_scratch_bytes)");
+  LinBf16PrepArgs g;
+  const int rc = knn_query_prep_plan(out, ldo, B, G, c, N, M, k, dilation, has_y, has_relpos, knn_flags, fused_mr, knn_workspace,
+                                     knn_workspace_bytes, &g.q);
+  if (rc != 0) return rc;
+  if (g.q.s.tb && !g.q.s.tb_lo) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_bf16_knn_prep: not with the bf16 contraction");
+  const int NB = lb_fill(g, x, ldx, wplanes, a, cshift, nullptr, 0, out, ldo, nullptr, 0, R, cin, cout, 0);
+  g.cnt = (unsigned*)scratch; g.B = B; g.G = G; g.c = c; g.N = N;
+  hipStream_t st = (hipStream_t)stream;
+  const hipError_t e = NB == 4 ? lb_launch<4, true>(g, st) : lb_launch<2, true>(g, st);
+  return e == hipSuccess ? 0 : gkg_fail_hip(e, "linear_bf16_kernel (k-NN preparation)");
 }

@@ -65,6 +65,13 @@ DETERMINISTIC = os.environ.get("GKG_DETERMINISTIC", "0") != "0"
 #                  output precisions in its epilogue (gkg_linear_bf16; linear_bf16.py) instead of the vendor GEMM (+ a stand-alone
 #                  affine pass).  The BN scale stays fp32 (the weight is not folded), so fc1's rounding differs from the default
 #                  path's.  Opt-in until its per-shape measurements decide the default (EXPERIMENTS.md).
+#   lin_bf16_prep  with lin_bf16 only: a Grapher's fc1 launch also prepares its output as the k-NN's queries (normalised copies,
+#                  |t|^2, prefilter planes: gkg_linear_bf16_knn_prep; linear_bf16.py) — the last workgroup of a row tile runs the
+#                  preparation on the rows the tile completed, and the k-NN call behind it (GKG_KNN_X_PREPARED) launches no
+#                  token preparation for the queries.  Same bits as lin_bf16 alone.  Not with knn_bf16 or a patched knn_graph_tm.
+#                  Taken only at the shapes where it measured at least as fast as the two launches (linear_bf16.prep_pays: the
+#                  stage-1 shapes of cfg3 / cfg5); lin_bf16_prep_all takes it wherever the library accepts the shape (tests,
+#                  measurements).
 # GKG_DISABLE — comma-separated list of optimisations to switch off (A/B measurements).  Round 6 cut the list to the eight
 # structural ones (the per-kernel switches of rounds 2-5 are gone with the alternatives they selected):
 #   knn_mr         k-NN + aggregation as one kernel (row g2)          knn_compact   u16 neighbour lists between two launches
@@ -83,6 +90,8 @@ _DISABLED = _env_list("GKG_DISABLE")
 _ENABLED = _env_list("GKG_ENABLE")
 KNN_BF16 = "knn_bf16" in _ENABLED
 LIN_BF16 = "lin_bf16" in _ENABLED          # a module constant the tests flip (like MR_GEMM)
+# likewise (False | True: the measured shapes | "all": every supported shape); acts only together with LIN_BF16
+LIN_BF16_PREP = "all" if "lin_bf16_prep_all" in _ENABLED else ("lin_bf16_prep" in _ENABLED)
 
 
 from .planes import (_WeightPlanes, _PLANES, _planes, refresh_weight_planes, param_version,      # noqa: E402,F401  (x6 weight
@@ -412,7 +421,8 @@ def _mm_t(x, W, W16=None):
     return Y if Y.dtype == _F32 else Y.float()
 
 
-from .linear_bf16 import _lin_planes_of, lin_bf16_ok, linear_bf16_eval      # noqa: E402,F401  (GKG_ENABLE=lin_bf16: linear_bf16.py)
+from .linear_bf16 import (_lin_planes_of, lin_bf16_ok, linear_bf16_eval,      # noqa: E402,F401  (GKG_ENABLE=lin_bf16: linear_bf16.py)
+                          lin_bf16_prep_ok, linear_bf16_knn_prep_eval)
 from .layout import _tm_dtype, _TokenMajorToCL, _ToTokenMajor, _BlockEntry, _AvgPoolTM      # noqa: E402  (layout Functions: layout.py)
 
 
@@ -1317,11 +1327,12 @@ def _knn_mr_ok(x, src, relative_pos, k, d, G, nn_, lp) -> bool:
     return _knn_mr_shapes_ok(B, N, C, M, src is not None, relative_pos, k, d, G, nn_, lp)
 
 
-def _knn_key_for(B, N, C, M, has_src, relative_pos, gc, groups, lp, want_edge):
+def _knn_key_for(B, N, C, M, has_src, relative_pos, gc, groups, lp, want_edge, lp_prep=False):
     """The KnnProblem of the k-NN call _graph_and_project will make for these shapes (fc1 prepares its queries), or None when the
     queries cannot be prepared ahead (_knn_ahead_ok) or by the preparation kernel — which takes group widths that are multiples
-    of 4 (the block driver never asks: block.grapher_ok excludes that shape before)."""
-    if lp or not _knn_ahead_ok() or (C // groups) % 4:
+    of 4 (the block driver never asks: block.grapher_ok excludes that shape before).  bf16 inference (``lp``) prepares only
+    inside the own bf16 projection's launch (``lp_prep``: GKG_ENABLE=lin_bf16,lin_bf16_prep on the channels-last chain)."""
+    if (lp and not lp_prep) or not _knn_ahead_ok() or (C // groups) % 4:
         return None
     fused_mr = _knn_mr_shapes_ok(B, N, C, M, has_src, relative_pos, gc.k, gc.d, groups, gc.gconv.nn, lp)
     return knn_prep.KnnProblem(B, groups, C // groups, N, M, gc.k, gc.d, has_src, relative_pos, fused_mr)
@@ -1432,6 +1443,13 @@ def _lin(x, seq, act=0, residual=None, nchw=None, out_lowp=False, scale=None, ro
         return _LinearBNAct.apply(x, conv.weight, conv.bias, bn.weight, bn.bias, residual, bn, act, nchw, out_lowp, w16, scale,
                                   rows_per_scale, want16, True, False, xm, knn)
     conv, bn = seq[0], seq[1]
+    if knn is not None and lowp_inference():
+        # only grapher_forward's bf16-inference branch hands a problem over here (both switches on): fc1 + the k-NN's token
+        # preparation in one launch where the predicate takes it, else fc1 as without the problem
+        if (not out_lowp and not want16 and act == 0 and residual is None
+                and lin_bf16_prep_ok(LIN_BF16 and LIN_BF16_PREP, True, x, conv, bn, knn, chain, nchw, scale, xm, alias, dual)):
+            return linear_bf16_knn_prep_eval(x, conv, bn, knn)
+        knn = None
     if LIN_BF16 and lin_bf16_ok(LIN_BF16, lowp_inference(), x, conv, bn, chain, nchw, scale, xm, knn, alias, dual):
         # bf16 inference, opt-in: the library's own projection kernel, BN (+ GELU) (+ residual) and both precisions in its epilogue
         o32, o16 = linear_bf16_eval(x, conv, bn, act, residual, want_f32=not out_lowp, want_bf16=out_lowp or want16)
@@ -1521,11 +1539,17 @@ def grapher_forward(mod, x, relative_pos, groups: int, want_edge: bool = True):
     # fc1's BN-apply also prepares the k-NN's queries (normalised copies, norms): no token-preparation launch behind it
     Mk = (H // gc.r) * (W // gc.r) if gc.r > 1 else N
     knn = _knn_key_for(B, N, C, Mk, gc.r > 1, relative_pos, gc, groups, lp, want_edge) if (xm is not None and KNN_PREP) else None
+    if lp and cl and LIN_BF16 and LIN_BF16_PREP and KNN_PREP:
+        # bf16 inference on the channels-last chain: the own projection kernel prepares the queries in fc1's launch (pooled keys,
+        # r > 1, are prepared by the k-NN call as always)
+        knn = _knn_key_for(B, N, C, Mk, gc.r > 1, relative_pos, gc, groups, lp, want_edge, lp_prep=True)
     if dual:
         x1, xt_r = _lin(xt, mod.fc1, alias=True, xm=xm, knn=knn)    # xt_r: xt again, the (token-major) residual of fc2
     else:
         x1 = _lin(xt, mod.fc1, xm=xm, knn=knn, chain=cl)            # fc1 + BN
     x1b = x1 if xm is not None else x1.view(B, N, C)
+    if xm is None and getattr(x1, "_gkg_knn", None) is not None:
+        x1._gkg_knn.mark(x1b)                                       # the view is a new object: the mark travels with the tokens
     yb = None
     if gc.r > 1:                                                    # pooled keys (torch_vertex.py:194-196)
         yb = _AvgPoolTM.apply(x1b, H, W, gc.r)

@@ -1,7 +1,8 @@
 """bf16 inference: a dense 1x1 projection with its eval-mode BN (+ GELU) (+ residual) as ONE launch of the library's own kernel
 (gkg_linear_bf16, csrc/gkg_linear_bf16.hip) — the weight's fragment array, the call, and the predicate ``fused._lin`` asks before
-it dispatches here.  Mechanism only: the switch (``fused.LIN_BF16``) and the mode test (``fused.lowp_inference``) stay in
-``fused.py`` and arrive as arguments."""
+it dispatches here — and the same launch with the k-NN's token preparation riding on it (gkg_linear_bf16_knn_prep: a Grapher's
+fc1).  Mechanism only: the switches (``fused.LIN_BF16``, ``fused.LIN_BF16_PREP``) and the mode test (``fused.lowp_inference``)
+stay in ``fused.py`` and arrive as arguments."""
 from __future__ import annotations
 
 import torch
@@ -80,3 +81,81 @@ def linear_bf16_eval(x16, conv, bn, act=0, residual=None, want_f32=True, want_bf
                                    0 if residual is None else residual.stride(0), _ptr(o32), cout, _ptr(o16), cout, R, cin, cout,
                                    act, _stream()), "gkg_linear_bf16")
     return o32, o16
+
+
+# ---- fc1 + the k-NN's token preparation in one launch (gkg_linear_bf16_knn_prep) ---------------------------------------------
+# DISPATCH RULE (``prep_pays``): the fused launch only where it measured at least as fast as the pair it replaces (gkg_linear_bf16
+# + the token_prep launch of the k-NN call), i.e. within the spread of the repeated pair measurements or better.  MI355X,
+# tools/bench_lin_bf16.py --prep, us per (fc1 [+ prep] launch, k-NN call) pair, median of 11 alternating replays [min, max], two
+# runs of cfg3 on one box (EXPERIMENTS.md, profiles/lin_bf16_prep_layers_*.txt):
+#   cfg3 (GKGNet-576, B 32)   C  80  c  40  R 663 552   pair 1771 [1761, 1913] / 1769   fused 1751 [1743, 1887] / 1757   taken
+#                             C 160  c  80  R 165 888   pair  776 [773, 781]            fused  908 [906, 916]            not taken
+#                             C 400  c 200  R  41 472   pair  479 [477, 485]            fused  675 [626, 679]            not taken
+#                             C 640  c 320  R  10 368   pair  150 [147, 151]            fused  252 [249, 254]            not taken
+#   cfg5 (pvig_m 768^2, B 16) C  96  c  12  R 589 824   pair 6597 [6580, 6638]          fused 6580 [6552, 6625]          taken
+#                             C 192  c  24  R 147 456   pair 2702 [2684, 2743]          fused 2745 [2732, 2758]          not taken
+#                             C 384  c  48  R  36 864   pair  963 [958, 976]            fused 1008 [998, 1021]           not taken
+#                             C 768  c  96  R   9 216   pair  220 [217, 223]            fused  303 [299, 306]            not taken
+# The two winners are the stage-1 shapes: one 128-column tile holds every group, so each workgroup prepares the rows it has just
+# stored (no hand-off between workgroups), with one thread per (row, group) pair (c <= 52).  Everywhere else the last arrival of
+# a row tile runs the preparation of 128 rows x G groups behind its neighbours, and that serial tail costs more than the launch
+# it removes — the wide 18 x 18 stages most (fc1 35 -> 159 us against a 22 us preparation launch).  The rule takes the measured
+# winners and what lies beyond them in the direction the measurements support (more rows of the same form), nothing in between:
+PREP_MAX_COUT, PREP_MAX_GROUP, PREP_MIN_ROWS = 128, 40, 1 << 19
+
+
+def prep_pays(R, cout, c) -> bool:
+    """The measured dispatch rule above: rows, columns and group width of a Grapher's fc1."""
+    return cout <= PREP_MAX_COUT and c <= PREP_MAX_GROUP and R >= PREP_MIN_ROWS
+
+
+def lin_bf16_prep_ok(on, lp, x, conv, bn, knn, chain=True, nchw=None, scale=None, xm=None, alias=False, dual=False,
+                     supported=None, prep_supported=None) -> bool:
+    """Whether ``fused._lin`` hands a Grapher's fc1 WITH its k-NN problem ``knn`` (a knn_prep.KnnProblem: queries, fp32 contraction)
+    to linear_bf16_knn_prep_eval: lin_bf16_ok's conditions without its ``knn`` exclusion, a problem over exactly this layer's
+    rows and columns, the measured rule (``on`` == "all" — GKG_ENABLE=lin_bf16_prep_all, tests, measurements — skips it: every
+    shape the library takes) and the library's own answer (``prep_supported(cin, knn)`` stands in for it in tests)."""
+    if knn is None or not lin_bf16_ok(on, lp, x, conv, bn, chain, nchw, scale, xm, None, alias, dual, supported):
+        return False
+    cout, cin = conv.weight.shape[0], conv.weight.shape[1]
+    if knn.as_keys or knn.B * knn.N != x.shape[0] or knn.G * knn.c != cout or knn.c % 4:
+        return False
+    if on != "all" and not prep_pays(x.shape[0], cout, knn.c):
+        return False
+    if prep_supported is not None:
+        return bool(prep_supported(cin, knn))
+    return bool(_lib.load().gkg_linear_bf16_knn_prep_supported(cin, knn.B, knn.G, knn.c, knn.N, knn.M, knn.k, knn.d, knn.has_y,
+                                                               knn.has_rp, knn.flags, knn.fused_mr))
+
+
+_PREP_SCRATCH = {}       # (device, stream) -> the zeroed arrival counters every launch leaves zero (grown on demand)
+
+
+def _prep_scratch(lib, device, stream, R) -> torch.Tensor:
+    need = int(lib.gkg_linear_bf16_knn_prep_scratch_bytes(R))
+    t = _PREP_SCRATCH.get((device, stream))
+    if t is None or t.numel() < need:
+        t = torch.zeros(max(need, 4096), dtype=torch.uint8, device=device)
+        _PREP_SCRATCH[(device, stream)] = t
+    return t
+
+
+@torch.no_grad()
+def linear_bf16_knn_prep_eval(x16, conv, bn, knn):
+    """x16 (B N, cin) bf16 -> BN_eval(Conv1x1(x16)) (B N, G c) fp32 — the bits of linear_bf16_eval(x16, conv, bn)[0] — with the
+    tokens prepared in ``knn``'s workspace as the queries of the k-NN call behind (reference torch_vertex.py:326 ->
+    torch_edge.py:167-173); the result carries the problem (knn.mark)."""
+    lib = _lib.load()
+    R, cin = x16.shape
+    cout = conv.weight.shape[0]
+    assert x16.dtype == torch.bfloat16 and R == knn.B * knn.N and cout == knn.G * knn.c and not knn.as_keys
+    x16 = _rows(x16, 8)
+    a, c = bn_passes.eval_ac(lib, bn, conv.bias, cout)
+    out = torch.empty((R, cout), dtype=_F32, device=x16.device)
+    stream = _stream()
+    scratch = _prep_scratch(lib, x16.device, stream, R)
+    _lib.check(lib.gkg_linear_bf16_knn_prep(_ptr(x16), x16.stride(0), _ptr(_lin_planes_of(conv)), cin, _ptr(a), _ptr(c),
+                                            *knn.producer_args(lib, out, None, None, cout, 0), _ptr(scratch), scratch.numel(),
+                                            stream), "gkg_linear_bf16_knn_prep")
+    knn.mark(out)
+    return out

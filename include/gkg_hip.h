@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define GKG_ABI_VERSION 14
+#define GKG_ABI_VERSION 15
 
 /* dtype codes */
 #define GKG_F32 0
@@ -379,6 +379,32 @@ int gkg_linear_bf16(const void* x /* bf16 (R, ldx) */, int ldx, const void* wpla
                     float* out_f32 /* (R, ldo32) or NULL */, int ldo32,
                     void* out_bf16 /* (R, ldo16) or NULL */, int ldo16,
                     int R, int cin, int cout, int act /* 0 none, 1 GELU */, void* stream);
+/* Grapher.fc1 under bf16 autocast with gradients off AND the token preparation of the k-NN call behind it, as ONE launch: the
+ * projection above with R = B N rows, cout = G c, act == 0, no residual, fp32 result only, whose last workgroup per row tile also
+ * prepares the rows it completes as the QUERIES of the k-NN problem (B, G, c, N, M, k, dilation, has_y, has_relpos, knn_flags,
+ * fused_mr).  The arguments `out` .. `knn_workspace_bytes` are the producers' shared run of gkg_affine_knn_prep.  Bit for bit:
+ *   out            = gkg_linear_bf16(x, ldx, wplanes, a, cshift, NULL, 0, out, ldo, NULL, 0, B N, cin, G c, 0, stream)
+ *   knn_workspace  = what gkg_affine_knn_prep leaves there for the same problem, fed the raw accumulators with the same a / cshift:
+ *                    the fp32 normalised channel-major copies with their zero pad channels, |t|^2 and, where that call's plan has
+ *                    them, the bf16 hi / lo prefilter planes with their pad rows and the two |t|^2 channels
+ * and the k-NN call with the same problem follows with GKG_KNN_X_PREPARED and x = out: it launches no preparation for the queries
+ * (the keys of a problem with has_y are prepared by that call as always).
+ * Scope, otherwise GKG_ERR_UNSUPPORTED with nothing launched: queries into plain rows only — ochunk == 0, as_keys == 0, res_tm ==
+ * out_nchw == NULL, no GKG_KNN_BF16_CONTRACT in knn_flags; gkg_linear_bf16's preconditions (cin % 8, (G c) % 8, ldx % 8, ldo % 4,
+ * 16-byte alignment; a pitch below its row's width is GKG_ERR_SHAPE) and c % 4 == 0; everything the k-NN plan itself refuses comes
+ * back with that call's code.  ldo == 0 means G c.
+ * scratch: gkg_linear_bf16_knn_prep_scratch_bytes(B N) bytes (one arrival counter per 128-row tile), caller-owned, 4-byte
+ * aligned, ZERO on entry and left zero on exit: no memset per call, the launch can be captured in a graph.  Too small or NULL:
+ * GKG_ERR_WORKSPACE.  gkg_linear_bf16_knn_prep_supported: 1 when sizes, flags and the k-NN plan pass (pure host code). */
+size_t gkg_linear_bf16_knn_prep_scratch_bytes(int R);
+int gkg_linear_bf16_knn_prep_supported(int cin, int B, int G, int c, int N, int M, int k, int dilation, int has_y, int has_relpos,
+                                       unsigned knn_flags, int fused_mr);
+int gkg_linear_bf16_knn_prep(const void* x /* bf16 (B N, ldx) */, int ldx, const void* wplanes, int cin,
+                             const float* a /* [G c] or NULL */, const float* cshift /* [G c] */,
+                             float* out, int ldo, int ochunk, int B, int G, int c, int N, int M, int k, int dilation,
+                             int has_y, int has_relpos, unsigned knn_flags, int fused_mr, int as_keys,
+                             const float* res_tm, float* out_nchw, void* knn_workspace, size_t knn_workspace_bytes,
+                             void* scratch, size_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Bandwidth kernels between the dense 1x1 projections (Conv2d 1x1 + SyncBN [+ GELU], reference

@@ -10,7 +10,17 @@ four dense projections of a Grapher + FFN pair for every stage of GKGNet-576 (cf
 Both sides run in the same process, alternating, each replayed from a hipGraph (no launch gaps) with the operands evicted from
 the caches by a 512 MB sweep before every replay (in-step conditions, as tools/bench_x6.py); the figure is the median of the
 replays.  Reported per layer: microseconds, effective TFLOP/s (2 R cin cout over the time) and the bytes the side's launches
-move over the layer's algorithmic bytes.    python tools/bench_lin_bf16.py [--out FILE.json] [--reps 15] [--batch 32] [--widths 400,640]"""
+move over the layer's algorithmic bytes.    python tools/bench_lin_bf16.py [--out FILE.json] [--reps 15] [--batch 32] [--widths 400,640]
+
+--prep cfg3|cfg5: the Grapher.fc1 leg with the k-NN's token preparation riding on it (gkg_linear_bf16_knn_prep,
+GKG_ENABLE=lin_bf16,lin_bf16_prep) at every fc1 shape of GKGNet-576 (cfg3, B 32) or pvig_m at 768 x 768 (cfg5, B 16):
+
+    fused   gkg_linear_bf16_knn_prep, then gkg_knn_fwd_tm16 with GKG_KNN_X_PREPARED (no preparation launch for the queries)
+    pair    gkg_linear_bf16,          then gkg_knn_fwd_tm16 (whose first launch is the queries' token_prep)
+
+The k-NN call is part of both sides because the library has no entry point that is the preparation launch alone; fc1_only_us /
+fc1_prep_us time the two projection launches without it (their difference is what the last-arriver tail costs, the pair's
+difference what the removed launch saves on top).  Same alternation, hipGraph replays and cache sweep as above."""
 import argparse
 import json
 import os
@@ -48,17 +58,102 @@ def capture(fn):
     return g
 
 
+# (C, side of the token grid, side of the pooled key grid) per stage
+PREP_CONFIGS = {"cfg3": dict(batch=32, G=2, k=9, stages=((80, 144, 36), (160, 72, 36), (400, 36, 36), (640, 18, 18))),
+                "cfg5": dict(batch=16, G=8, k=18, stages=((96, 192, 48), (192, 96, 48), (384, 48, 48), (768, 24, 24)))}
+
+
+def prep_leg(args, lib, flush):
+    cfg = PREP_CONFIGS[args.prep]
+    B, G, k, d = (args.batch or cfg["batch"]), cfg["G"], cfg["k"], 1
+    rows = []
+    for C, side, kside in cfg["stages"]:
+        N, M, c, R = side * side, kside * kside, C // G, B * side * side
+        has_y = M != N
+        gen = torch.Generator(device="cuda").manual_seed(C)
+        x = torch.randn(R, C, device="cuda", generator=gen).to(BF16)
+        w = torch.randn(C, C, device="cuda", generator=gen) / C ** 0.5
+        a = torch.rand(C, device="cuda", generator=gen) + 0.5
+        cs = torch.randn(C, device="cuda", generator=gen) * 0.2
+        W = torch.zeros((C + 31) // 32 * 32, (C + 15) // 16 * 16, device="cuda", dtype=BF16)
+        W[:C, :C] = w.to(BF16)
+        planes = W.view(W.shape[0], W.shape[1] // 8, 8).permute(1, 0, 2).contiguous()
+        y = torch.randn(B, M, C, device="cuda", generator=gen) if has_y else None
+        rp = -torch.rand(N, M, device="cuda", generator=gen)
+        flags = _lib.KNN_NORMALIZE | _lib.KNN_RELPOS_UNIT
+        if not lib.gkg_linear_bf16_knn_prep_supported(C, B, G, c, N, M, k, d, int(has_y), 1, flags, 0):
+            print(f"C={C}: not supported", flush=True)
+            continue
+        wsb = int(lib.gkg_knn_workspace_bytes(B * G, c, N, M, k, d, _lib.F32, _lib.KNN_NORMALIZE))
+        ws = torch.empty(wsb, dtype=torch.uint8, device="cuda")
+        out = torch.empty(R, C, device="cuda")
+        nn16 = torch.empty(B * G, N, k, dtype=torch.int16, device="cuda")
+        scratch = torch.zeros(int(lib.gkg_linear_bf16_knn_prep_scratch_bytes(R)), dtype=torch.uint8, device="cuda")
+
+        def fc1():
+            _lib.check(lib.gkg_linear_bf16(_ptr(x), C, _ptr(planes), _ptr(a), _ptr(cs), None, 0, _ptr(out), C, None, 0, R, C, C, 0,
+                                           _stream()), "gkg_linear_bf16")
+
+        def fc1_prep():
+            _lib.check(lib.gkg_linear_bf16_knn_prep(_ptr(x), C, _ptr(planes), C, _ptr(a), _ptr(cs), _ptr(out), C, 0, B, G, c, N, M, k, d,
+                                                    int(has_y), 1, flags, 0, 0, None, None, _ptr(ws), wsb, _ptr(scratch), scratch.numel(),
+                                                    _stream()), "gkg_linear_bf16_knn_prep")
+
+        def knn(prepared):
+            _lib.check(lib.gkg_knn_fwd_tm16(_ptr(out), 0, 0, _ptr(y), _ptr(rp), _ptr(nn16), B, G, c, N, M, k, d, _lib.F32,
+                                            flags | (_lib.KNN_X_PREPARED if prepared else 0), _ptr(ws), wsb, _stream()), "gkg_knn_fwd_tm16")
+
+        def pair():
+            fc1()
+            knn(False)
+
+        def fused():
+            fc1_prep()
+            knn(True)
+        pair()
+        want = nn16.clone()
+        fused()
+        torch.cuda.synchronize()
+        assert torch.equal(nn16, want) and int(scratch.sum()) == 0               # a sanity check of the comparison, not a test
+        graphs = [capture(f) for f in (pair, fused, fc1, fc1_prep)]
+        t = [[] for _ in graphs]
+        for _ in range(args.reps):                                               # alternate the legs
+            for i, g in enumerate(graphs):
+                t[i].append(1e3 * replay_ms(g, flush))
+        med = [statistics.median(v) for v in t]
+        row = dict(config=args.prep, C=C, B=B, G=G, c=c, N=N, M=M, k=k, R=R, pair_us=round(med[0], 1), fused_us=round(med[1], 1),
+                   pair_us_min=round(min(t[0]), 1), pair_us_max=round(max(t[0]), 1), fused_us_min=round(min(t[1]), 1),
+                   fused_us_max=round(max(t[1]), 1), fc1_only_us=round(med[2], 1), fc1_prep_us=round(med[3], 1),
+                   winner="fused" if med[1] < med[0] else "pair")
+        rows.append(row)
+        print(f"{args.prep} C={C:4d} c={c:3d} N={N:6d} M={M:5d} R={R:7d}: pair {med[0]:8.1f} us [{min(t[0]):.1f}, {max(t[0]):.1f}]  "
+              f"fused {med[1]:8.1f} us [{min(t[1]):.1f}, {max(t[1]):.1f}]  fc1 {med[2]:7.1f} us  fc1+prep {med[3]:7.1f} us  -> {row['winner']}",
+              flush=True)
+        del x, y, rp, ws, out, nn16, graphs
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--prep", default=None, choices=sorted(PREP_CONFIGS), help="run the fc1 + k-NN preparation leg at this config's shapes")
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=15)
-    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--batch", type=int, default=None, help="default: 32 (cfg3), 16 (--prep cfg5)")
     ap.add_argument("--widths", default="80,160,400,640", help="stage widths C to run (default: all four stages of cfg3)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_lin_bf16: needs a GPU (a timing anywhere else says nothing)")
     lib = _lib.load()
     flush = torch.empty(128 << 20, dtype=torch.float32, device="cuda")
+    if args.prep:
+        rows = prep_leg(args, lib, flush)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as fh:
+                json.dump(dict(tool="bench_lin_bf16 --prep", config=args.prep, reps=args.reps, device=torch.cuda.get_device_name(0),
+                               rows=rows), fh, indent=1)
+        return
+    args.batch = args.batch or 32
     rows = []
     widths = {int(t) for t in args.widths.split(",")}
     for C, side in ((80, 144), (160, 72), (400, 36), (640, 18)):
