@@ -1,4 +1,5 @@
 // gkg_linear_bf16.hip — bf16 inference: a dense 1x1 projection (Conv2d 1x1 + eval-mode BN [+ GELU] [+ residual]) as ONE kernel.
+// (F32A below: the same kernel with an fp32 A operand, a training layer's forward and input gradient under bf16 autocast.)
 //
 // Reference layers (mmcls/models/backbones/vig_model/torch_vertex.py:290-306 Grapher.fc1 / fc2, mmcls/models/backbones/gkgnet.py:46-72
 // FFN.fc1 / fc2, torch_nn.py:57-69) under bf16 autocast with gradients off.  The library-GEMM form of these layers is
@@ -44,6 +45,15 @@
 //   linear_bf16_kernel<4, true>   237 VGPRs, 0 AGPRs, 106 SGPRs   same LDS, no scratch   2 waves / SIMD
 //   linear_bf16_kernel<2, true>   155 VGPRs, 0 AGPRs, 106 SGPRs   same LDS, no scratch   3 waves / SIMD
 // The non-PREP instantiations are unchanged by the parameter (234 / 66 and 152 / 62 as above).
+//
+// F32A = true (gkg_linear_bf16_f32a: training under bf16 autocast, where the activations and gradients stay fp32): x is fp32
+// (R, ldx); a granule of 8 floats is fetched as two 16-byte loads and rounded to bf16 (pack_bf16x2, round to nearest even) when
+// it is stashed, so the LDS image, the contraction order and the epilogue — and with them every output bit — are those of the
+// bf16 kernel on x.to(bf16).  The staged A registers double (32 -> 64 with the two chunks of look-ahead kept), which the <4> form
+// (234 VGPRs) cannot take without scratch: this entry point runs the 64-column form at EVERY shape (the tile form changes no
+// bit: an output element's contraction runs in the same order in both), look-ahead unchanged.
+//   linear_bf16_kernel<2, false, true>   186 VGPRs, 0 AGPRs, 62 SGPRs   LDS 53 248 B (dynamic), no scratch   2 waves / SIMD by registers
+// The other four instantiations keep their figures (234 / 66, 152 / 62, 237 / 106, 155 / 106).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -120,13 +130,15 @@ __device__ __forceinline__ void lb_prep_rows(const LinBf16PrepArgs& g, float* co
   }
 }
 
-template <int NB, bool PREP = false>
+template <int NB, bool PREP = false, bool F32A = false>
 __global__ __launch_bounds__(LB_NT, 2) void linear_bf16_kernel(std::conditional_t<PREP, LinBf16PrepArgs, LinBf16Args> g) {
+  static_assert(!(PREP && F32A), "the fp32-A form has no token preparation");
   extern __shared__ __align__(16) unsigned char lb_lds[];
   constexpr int BN = 32 * NB;
   constexpr int BBYTES = (LB_KC / 8) * BN * 16;
   constexpr int NA = LB_BM * (LB_KC / 8) / LB_NT;        // 16-byte A granules per thread and chunk: 4
   constexpr int NBG = (LB_KC / 8) * BN / LB_NT;          // B granules per thread and chunk: 4 (NB = 4), 2 (NB = 2)
+  constexpr int NAR = F32A ? 2 * NA : NA;                // registers (16 B) an A chunk is staged in: an fp32 granule is two of them
   constexpr int SP = BN + 4;                             // floats per row of a wave's epilogue stage
   static_assert(4 * 32 * SP * 4 <= 2 * (LB_ABYTES + BBYTES), "the epilogue stage must fit the operand buffers");
   const int tid = threadIdx.x;
@@ -148,15 +160,22 @@ __global__ __launch_bounds__(LB_NT, 2) void linear_bf16_kernel(std::conditional_
 
   // two register sets: the loads of chunk c + 2 are issued before the MFMAs of chunk c (set c & 1), the set holding chunk c + 1 is
   // written to the other LDS buffer after them — a load has two chunks of matrix work (and the CU's other workgroups) to land
-  uint4 ra[2][NA], rb[2][NBG];
-  auto fetch = [&](int c, uint4 (&qa)[NA], uint4 (&qb)[NBG]) __attribute__((always_inline)) {
+  uint4 ra[2][NAR], rb[2][NBG];
+  auto fetch = [&](int c, uint4 (&qa)[NAR], uint4 (&qb)[NBG]) __attribute__((always_inline)) {
     const int k0 = c * LB_KC;
 #pragma unroll
     for (int i = 0; i < NA; ++i) {
       const int gi = tid + LB_NT * i;
       const long long row = r0 + (gi >> 3);
       const int k = k0 + 8 * (gi & 7);
-      qa[i] = (row < g.R && k < g.cin) ? *reinterpret_cast<const uint4*>(g.x + (size_t)row * g.ldx + k) : make_uint4(0, 0, 0, 0);
+      if constexpr (F32A) {                                // x is fp32 (R, ldx): the granule's 8 floats stay fp32 until the stash
+        const uint4* xp = reinterpret_cast<const uint4*>(reinterpret_cast<const float*>(g.x) + (size_t)row * g.ldx + k);
+        const bool in = row < g.R && k < g.cin;
+        qa[2 * i] = in ? xp[0] : make_uint4(0, 0, 0, 0);
+        qa[2 * i + 1] = in ? xp[1] : make_uint4(0, 0, 0, 0);
+      } else {
+        qa[i] = (row < g.R && k < g.cin) ? *reinterpret_cast<const uint4*>(g.x + (size_t)row * g.ldx + k) : make_uint4(0, 0, 0, 0);
+      }
     }
 #pragma unroll
     for (int i = 0; i < NBG; ++i) {
@@ -165,11 +184,18 @@ __global__ __launch_bounds__(LB_NT, 2) void linear_bf16_kernel(std::conditional_
       qb[i] = (f < nfrag && n < g.co_pad) ? g.wp[(size_t)f * g.co_pad + n] : make_uint4(0, 0, 0, 0);
     }
   };
-  auto stash = [&](int buf, const uint4 (&qa)[NA], const uint4 (&qb)[NBG]) __attribute__((always_inline)) {
+  auto stash = [&](int buf, const uint4 (&qa)[NAR], const uint4 (&qb)[NBG]) __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < NA; ++i) {
       const int gi = tid + LB_NT * i;
-      *reinterpret_cast<uint4*>(abuf + buf * LB_ABYTES + (gi >> 3) * LB_APITCH + 16 * (gi & 7)) = qa[i];
+      uint4 v;
+      if constexpr (F32A) {                                // round to nearest even here: the LDS image is the bf16 kernel's
+        const float4 f0 = __builtin_bit_cast(float4, qa[2 * i]), f1 = __builtin_bit_cast(float4, qa[2 * i + 1]);
+        v = make_uint4(pack_bf16x2(f0.x, f0.y), pack_bf16x2(f0.z, f0.w), pack_bf16x2(f1.x, f1.y), pack_bf16x2(f1.z, f1.w));
+      } else {
+        v = qa[i];
+      }
+      *reinterpret_cast<uint4*>(abuf + buf * LB_ABYTES + (gi >> 3) * LB_APITCH + 16 * (gi & 7)) = v;
     }
 #pragma unroll
     for (int i = 0; i < NBG; ++i) *reinterpret_cast<uint4*>(bbuf + buf * BBYTES + 16 * (tid + LB_NT * i)) = qb[i];
@@ -232,7 +258,9 @@ __global__ __launch_bounds__(LB_NT, 2) void linear_bf16_kernel(std::conditional_
     for (int u = 0; u < NB; ++u) {
       const int col = n0 + 32 * u + l31;
       if (has[u] && col < g.cout) {
-        const float cv = g.cs[col];
+        float cv;
+        if constexpr (F32A) cv = g.cs ? g.cs[col] : 0.f;               // (the fp32-A entry point only: no shift vector = zeros)
+        else cv = g.cs[col];
         const float av = scaled ? g.a[col] : 1.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -323,15 +351,15 @@ __global__ __launch_bounds__(LB_NT, 2) void linear_bf16_kernel(std::conditional_
   }
 }
 
-template <int NB, bool PREP = false, typename Args>
+template <int NB, bool PREP = false, bool F32A = false, typename Args>
 static hipError_t lb_launch(const Args& g, hipStream_t st) {
   constexpr size_t lds = lb_lds_bytes(NB);
   if (lds > 64 * 1024) {
-    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_bf16_kernel<NB, PREP>),
+    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_bf16_kernel<NB, PREP, F32A>),
                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (ea != hipSuccess) return ea;
   }
-  hipLaunchKernelGGL((linear_bf16_kernel<NB, PREP>), dim3((unsigned)(g.tiles_per_xcd * 8)), dim3(LB_NT), lds, st, g);
+  hipLaunchKernelGGL((linear_bf16_kernel<NB, PREP, F32A>), dim3((unsigned)(g.tiles_per_xcd * 8)), dim3(LB_NT), lds, st, g);
   return hipGetLastError();
 }
 
@@ -356,11 +384,11 @@ static int lb_pick_nb(int R, int co_pad) {
 
 // The launch's arguments and tile form (returned: column blocks per workgroup) for checked operands
 static int lb_fill(LinBf16Args& g, const void* x, int ldx, const void* wplanes, const float* a, const float* cshift, const float* res,
-                   int ldr, float* out_f32, int ldo32, void* out_bf16, int ldo16, int R, int cin, int cout, int act) {
+                   int ldr, float* out_f32, int ldo32, void* out_bf16, int ldo16, int R, int cin, int cout, int act, int force_nb = 0) {
   g.x = (const uint16_t*)x; g.ldx = ldx; g.wp = (const uint4*)wplanes; g.a = a; g.cs = cshift; g.res = res; g.ldr = ldr;
   g.o32 = out_f32; g.ldo32 = ldo32; g.o16 = (uint16_t*)out_bf16; g.ldo16 = ldo16;
   g.R = R; g.cin = cin; g.cout = cout; g.ci_pad = lb_ci_pad(cin); g.co_pad = lb_co_pad(cout); g.act = act;
-  const int NB = lb_pick_nb(R, g.co_pad);
+  const int NB = force_nb ? force_nb : lb_pick_nb(R, g.co_pad);
   const long long tiles = lb_tiles(R, g.co_pad, NB, &g.col_tiles);
   g.tiles = (int)tiles;
   g.tiles_per_xcd = (int)((tiles + 7) / 8);
@@ -402,6 +430,33 @@ extern "C" int gkg_linear_bf16(const void* x, int ldx, const void* wplanes, cons
   hipStream_t st = (hipStream_t)stream;
   const hipError_t e = NB == 4 ? lb_launch<4>(g, st) : lb_launch<2>(g, st);
   return e == hipSuccess ? 0 : gkg_fail_hip(e, "linear_bf16_kernel");
+}
+
+// ---------------------------------------------------------------------------------------------- fp32 A operand (training)
+extern "C" int gkg_linear_bf16_f32a_supported(int R, int cin, int cout, int has_res, int want_f32, int want_bf16, int act) {
+  if (!gkg_linear_bf16_supported(R, cin, cout, has_res, want_f32, want_bf16, act)) return 0;
+  int ct;
+  return lb_tiles(R, lb_co_pad(cout), 2, &ct) <= 0x3fffffffLL ? 1 : 0;              // the 64-column form at every shape
+}
+
+extern "C" int gkg_linear_bf16_f32a(const float* x, int ldx, const void* wplanes, const float* a, const float* cshift, const float* res,
+                                    int ldr, float* out_f32, int ldo32, void* out_bf16, int ldo16, int R, int cin, int cout, int act,
+                                    void* stream) {
+  if (!x || !wplanes || (!out_f32 && !out_bf16)) return gkg_fail(GKG_ERR_NULL, "gkg_linear_bf16_f32a: null pointer");
+  if (R < 1 || cin <= 0 || cout <= 0 || act < 0 || act > 1)
+    return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_bf16_f32a: bad sizes (need R >= 1, cin, cout > 0, act in 0..1)");
+  if (!gkg_linear_bf16_f32a_supported(R, cin, cout, res != nullptr, out_f32 != nullptr, out_bf16 != nullptr, act))
+    return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_bf16_f32a: need cin % 8 == 0, cout % 8 == 0 and a grid that fits");
+  if ((ldx & 3) || (out_bf16 && (ldo16 & 7)) || (out_f32 && (ldo32 & 3)) || (res && (ldr & 3)))
+    return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_bf16_f32a: need ldx % 4 == 0, ldo16 % 8 == 0, ldo32 % 4 == 0, ldr % 4 == 0");
+  if (((uintptr_t)x | (uintptr_t)wplanes | (uintptr_t)res | (uintptr_t)out_f32 | (uintptr_t)out_bf16) & 15)
+    return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_bf16_f32a: x, wplanes, res and the outputs must be 16-byte aligned");
+  if (ldx < cin || (out_bf16 && ldo16 < cout) || (out_f32 && ldo32 < cout) || (res && ldr < cout))
+    return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_bf16_f32a: a row pitch is below the row's width");
+  LinBf16Args g;
+  lb_fill(g, x, ldx, wplanes, a, cshift, res, ldr, out_f32, ldo32, out_bf16, ldo16, R, cin, cout, act, 2);
+  const hipError_t e = lb_launch<2, false, true>(g, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : gkg_fail_hip(e, "linear_bf16_kernel (fp32 A)");
 }
 
 // ---------------------------------------------------------------------------------------------- fc1 + the k-NN's token preparation

@@ -72,6 +72,13 @@ DETERMINISTIC = os.environ.get("GKG_DETERMINISTIC", "0") != "0"
 #                  Taken only at the shapes where it measured at least as fast as the two launches (linear_bf16.prep_pays: the
 #                  stage-1 shapes of cfg3 / cfg5); lin_bf16_prep_all takes it wherever the library accepts the shape (tests,
 #                  measurements).
+#   train_bf16     training under bf16 autocast: the three products of a dense projection of a Grapher / FFN block (_LinearBNAct under
+#                  autocast: Y = x W^T, dx = dY W (+ the skip gradient), dW = dY^T x) run on the library's own bf16 kernels — bf16
+#                  operands rounded from the fp32 tensors on their way into LDS, fp32 accumulation (gkg_linear_bf16_f32a,
+#                  gkg_linear_wgrad_bf16; linear_bf16.py) — instead of the autocast vendor GEMM with its casts, the fp32 vendor GEMM
+#                  and the six-product x6 weight gradient.  bf16 autocast with gradients only; not under GKG_DETERMINISTIC (the
+#                  weight gradient adds its row slabs atomically); the grouped projection, fp16 autocast and the BN passes keep
+#                  their paths.  Opt-in: per-layer measurements in EXPERIMENTS.md.
 # GKG_DISABLE — comma-separated list of optimisations to switch off (A/B measurements).  Round 6 cut the list to the eight
 # structural ones (the per-kernel switches of rounds 2-5 are gone with the alternatives they selected):
 #   knn_mr         k-NN + aggregation as one kernel (row g2)          knn_compact   u16 neighbour lists between two launches
@@ -92,6 +99,7 @@ KNN_BF16 = "knn_bf16" in _ENABLED
 LIN_BF16 = "lin_bf16" in _ENABLED          # a module constant the tests flip (like MR_GEMM)
 # likewise (False | True: the measured shapes | "all": every supported shape); acts only together with LIN_BF16
 LIN_BF16_PREP = "all" if "lin_bf16_prep_all" in _ENABLED else ("lin_bf16_prep" in _ENABLED)
+TRAIN_BF16 = "train_bf16" in _ENABLED      # likewise a module constant the tests flip
 
 
 from .planes import (_WeightPlanes, _PLANES, _planes, refresh_weight_planes, param_version,      # noqa: E402,F401  (x6 weight
@@ -423,6 +431,8 @@ def _mm_t(x, W, W16=None):
 
 from .linear_bf16 import (_lin_planes_of, lin_bf16_ok, linear_bf16_eval,      # noqa: E402,F401  (GKG_ENABLE=lin_bf16: linear_bf16.py)
                           lin_bf16_prep_ok, linear_bf16_knn_prep_eval)
+from .linear_bf16 import (_lin_planes_t_of, train_bf16_ok, linear_bf16_train_fwd,      # noqa: E402,F401  (GKG_ENABLE=train_bf16)
+                          linear_bf16_dgrad, linear_bf16_wgrad)
 from .layout import _tm_dtype, _TokenMajorToCL, _ToTokenMajor, _BlockEntry, _AvgPoolTM      # noqa: E402  (layout Functions: layout.py)
 
 
@@ -654,8 +664,11 @@ class _LinearBNAct(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, gamma, beta, residual, bn, act, nchw, out_lowp=False, w16=None, scale=None,
-                rows_per_scale=0, want16=False, alias=False, dual=False, xm=None, knn=None):
-        """``alias``: also return ``x`` itself as a second output (a view).  A caller that uses the layer's input again
+                rows_per_scale=0, want16=False, alias=False, dual=False, xm=None, knn=None, conv=None):
+        """``conv``: the projection's module (travels like ``w16``), handed over by ``_lin`` only where GKG_ENABLE=train_bf16 takes
+        the layer (train_bf16_ok, asked there: in here gradients are switched off): its two cached fragment arrays are what the
+        own bf16 products of this node's forward and backward stream.
+        ``alias``: also return ``x`` itself as a second output (a view).  A caller that uses the layer's input again
         as the residual of a later layer takes the alias for that: both gradient contributions then arrive at THIS node
         and the input-gradient GEMM adds the residual one in its epilogue (``addmm``), instead of autograd summing two
         tensors with a stand-alone add kernel.
@@ -675,6 +688,7 @@ class _LinearBNAct(torch.autograd.Function):
         group = _sync_group(bn)
         x6f, x6d = _x6(x, weight, bn, 1, "fwd", group), _x6(x, weight, bn, 1, "dgrad", group)
         own = x6f
+        tb16 = None
         pf, pd = _planes(lib, weight, 1, cout, cin, x6f, x6d) if x6f or x6d else (None, None)
         pf, pd = (pf if x6f else None), (pd if x6d else None)
         res = None if residual is None else residual.contiguous()
@@ -711,7 +725,10 @@ class _LinearBNAct(torch.autograd.Function):
         elif own:                                     # projection kernel with the BN statistics in its epilogue
             Y, a, c, mean, invstd = _linear_fwd_own(lib, x, pf, (R, cin, cout, 1), bias, bn)
         else:
-            Y = _mm_t(x, weight.view(cout, cin), w16)
+            # bf16 autocast with gradients, opt-in: the product on the own bf16 kernel (fp32 A operand rounded on its way into LDS).
+            # The backward runs outside autocast: the decision is recorded here
+            tb16 = conv
+            Y = linear_bf16_train_fwd(x, conv) if tb16 is not None else _mm_t(x, weight.view(cout, cin), w16)
             a, c, mean, invstd, sync = bn_passes.forward_params(lib, Y, bn, bias, R, cout, 1, group)
         if not fused_apply and not (own and mean is None and code == _lib.F32 and not want16):
             prep = None      # besides the train-mode pass only a frozen layer's affine behind the x6 projection, fp32 out, prepares
@@ -744,6 +761,7 @@ class _LinearBNAct(torch.autograd.Function):
         ctx.scale = (scale, rows_per_scale)
         ctx.gparams = (weight, gamma, beta)
         ctx.pd = pd
+        ctx.tb16 = tb16
         ctx.prev = prev if (prev is not None and pd is not None and prev.nb * prev.co == cin and prev.R == R) else None
         ctx.link = _bn_link(out, state, ctx.bn, scale) if (nchw is None and xm is None) else None
         if xm is not None:
@@ -772,9 +790,9 @@ class _LinearBNAct(torch.autograd.Function):
         if ctx.dual:
             dtm, dalias = dalias, None
             if dout is None and dtm is None:
-                return (None,) * 18
+                return (None,) * 19
         elif dout is None:                                 # only the alias was used downstream
-            return (dalias,) + (None,) * 17
+            return (dalias,) + (None,) * 18
         R, cin = x.shape
         cout = weight.shape[0]
         dres = dout if has_res else None
@@ -845,6 +863,11 @@ class _LinearBNAct(torch.autograd.Function):
             _dgrad_x6(lib, dY, cout, R * cout, ctx.pd, dx, R, cin, cout, 1, res)
             if res is not None:
                 dalias = None
+        elif ctx.tb16 is not None:                         # GKG_ENABLE=train_bf16: the own bf16 product, the skip gradient in its epilogue
+            res = dalias if (dalias is not None and dalias.dtype == _F32 and dalias.shape == (R, cin)) else None
+            dx = linear_bf16_dgrad(dY, ctx.tb16, residual=res)
+            if res is not None:
+                dalias = None
         elif dalias is not None and dalias.dtype == dY.dtype:
             dx = torch.addmm(dalias, dY, W)                # the residual-path gradient rides in the GEMM epilogue
             dalias = None
@@ -854,8 +877,12 @@ class _LinearBNAct(torch.autograd.Function):
             dx = dx + dalias
         elif dalias is not None:
             dx = dalias
-        dW = _wgrad(dY, x, dWv).view_as(weight)
-        return dx, dW, dbias, dgamma, dbeta, dres, None, None, None, None, None, None, None, None, None, None, None, None
+        if ctx.tb16 is not None:
+            # launched from the node: the deferred weight-gradient queue's problem records are x6 problems
+            dW = linear_bf16_wgrad(dY, x, dWv).view_as(weight)
+        else:
+            dW = _wgrad(dY, x, dWv).view_as(weight)
+        return dx, dW, dbias, dgamma, dbeta, dres, None, None, None, None, None, None, None, None, None, None, None, None, None
 
 
 class _GroupedLinearBNAct(torch.autograd.Function):
@@ -1428,6 +1455,12 @@ def fused_supported(mod, x, groups: int) -> bool:
     return ENABLED
 
 
+def _train_bf16_conv(x, conv, bn):
+    """The module _LinearBNAct takes its own bf16 products' fragment arrays from, or None: GKG_ENABLE=train_bf16 and the layer is
+    in its scope (linear_bf16.train_bf16_ok — asked here, where the caller's gradient mode is still visible)."""
+    return conv if train_bf16_ok(TRAIN_BF16, x, conv, bn) else None
+
+
 def _lin(x, seq, act=0, residual=None, nchw=None, out_lowp=False, scale=None, rows_per_scale=0, want16=False, alias=False,
          dual=False, xm=None, knn=None, chain=False):
     """``scale`` (one factor per image; token-major outputs: per ``rows_per_scale`` consecutive rows) multiplies the BN
@@ -1441,7 +1474,7 @@ def _lin(x, seq, act=0, residual=None, nchw=None, out_lowp=False, scale=None, ro
         conv, bn = seq[0], seq[1]
         w16 = _w16_of(conv) if x.dtype == torch.bfloat16 else None
         return _LinearBNAct.apply(x, conv.weight, conv.bias, bn.weight, bn.bias, residual, bn, act, nchw, out_lowp, w16, scale,
-                                  rows_per_scale, want16, True, False, xm, knn)
+                                  rows_per_scale, want16, True, False, xm, knn, _train_bf16_conv(x, conv, bn))
     conv, bn = seq[0], seq[1]
     if knn is not None and lowp_inference():
         # only grapher_forward's bf16-inference branch hands a problem over here (both switches on): fc1 + the k-NN's token
@@ -1473,7 +1506,7 @@ def _lin(x, seq, act=0, residual=None, nchw=None, out_lowp=False, scale=None, ro
         return torch.addmm(_folded_shift32(conv, bn), x, wf.t(), out_dtype=_F32)
     w16 = _w16_of(conv) if x.dtype == torch.bfloat16 else None
     return _LinearBNAct.apply(x, conv.weight, conv.bias, bn.weight, bn.bias, residual, bn, act, nchw, out_lowp, w16, scale,
-                              rows_per_scale, want16, False, dual, xm, knn)
+                              rows_per_scale, want16, False, dual, xm, knn, _train_bf16_conv(x, conv, bn))
 
 
 # ---- a block output in both layouts (round 5) ---------------------------------------------------------------------------

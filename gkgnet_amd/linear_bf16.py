@@ -1,8 +1,10 @@
 """bf16 inference: a dense 1x1 projection with its eval-mode BN (+ GELU) (+ residual) as ONE launch of the library's own kernel
 (gkg_linear_bf16, csrc/gkg_linear_bf16.hip) — the weight's fragment array, the call, and the predicate ``fused._lin`` asks before
 it dispatches here — and the same launch with the k-NN's token preparation riding on it (gkg_linear_bf16_knn_prep: a Grapher's
-fc1).  Mechanism only: the switches (``fused.LIN_BF16``, ``fused.LIN_BF16_PREP``) and the mode test (``fused.lowp_inference``)
-stay in ``fused.py`` and arrive as arguments."""
+fc1).  Also the training side (GKG_ENABLE=train_bf16): the same kernel reading an fp32 A operand for a layer's forward and input
+gradient (gkg_linear_bf16_f32a), the bf16 weight-gradient kernel (gkg_linear_wgrad_bf16) and their predicate.  Mechanism only: the
+switches (``fused.LIN_BF16``, ``fused.LIN_BF16_PREP``, ``fused.TRAIN_BF16``) and the mode test (``fused.lowp_inference``) stay in
+``fused.py`` and arrive as arguments."""
 from __future__ import annotations
 
 import torch
@@ -31,6 +33,27 @@ def _lin_planes_of(conv) -> torch.Tensor:
         assert planes.numel() * 2 == nbytes
         ent = (param_version(w), w.data_ptr(), planes)
         conv._gkg_linplanes = ent
+    return ent[2]
+
+
+def _lin_planes_t_of(conv) -> torch.Tensor:
+    """The fragment array of the TRANSPOSED weight, what the input gradient dx = dY W streams (gkg_linear_bf16_f32a with
+    contraction cout and output columns cin): [co_pad'/8][ci_pad'][8], fragment (f, n) = w[8f .. 8f+7][n] — _lin_planes_of's
+    layout built from w.t(), with that product's paddings (cout to 16, cin to 32).  Cached on the module like _lin_planes_of."""
+    w = conv.weight
+    ent = getattr(conv, "_gkg_linplanes_t", None)
+    if ent is None or ent[0] != param_version(w) or ent[1] != w.data_ptr():
+        co, ci = w.shape[0], w.numel() // w.shape[0]
+        nbytes = int(_lib.load().gkg_linear_bf16_planes_bytes(co, ci))       # contraction co, columns ci
+        k_pad = (co + 15) // 16 * 16
+        n_pad = nbytes // (2 * k_pad) if nbytes else 0
+        assert nbytes and n_pad >= ci and n_pad * k_pad * 2 == nbytes, (ci, co, nbytes)
+        Wt = torch.zeros((n_pad, k_pad), dtype=torch.bfloat16, device=w.device)
+        Wt[:ci, :co] = w.detach().reshape(co, ci).t().to(torch.bfloat16)
+        planes = Wt.view(n_pad, k_pad // 8, 8).permute(1, 0, 2).contiguous()
+        assert planes.numel() * 2 == nbytes
+        ent = (param_version(w), w.data_ptr(), planes)
+        conv._gkg_linplanes_t = ent
     return ent[2]
 
 
@@ -158,4 +181,84 @@ def linear_bf16_knn_prep_eval(x16, conv, bn, knn):
                                             *knn.producer_args(lib, out, None, None, cout, 0), _ptr(scratch), scratch.numel(),
                                             stream), "gkg_linear_bf16_knn_prep")
     knn.mark(out)
+    return out
+
+
+# ---- training under bf16 autocast (GKG_ENABLE=train_bf16): the layer's three products on the own bf16 kernels ------------------
+# Y = x W^T and dx = dY W (+ the skip gradient) are gkg_linear_bf16_f32a (the projection kernel reading its A operand as fp32 and
+# rounding it on the way into LDS), dW = dY^T x is gkg_linear_wgrad_bf16 (csrc/gkg_linear_bf16_train.hip): one bf16 matrix
+# product with fp32 accumulation each, no vendor GEMM, no cast launch.  Mechanism only: ``fused.TRAIN_BF16`` arrives as ``on``.
+def train_bf16_ok(on, x, conv, bn, supported=None) -> bool:
+    """Whether ``fused._LinearBNAct.forward`` takes its product from linear_bf16_train_fwd (and the backward its two from
+    linear_bf16_dgrad / linear_bf16_wgrad): the switch, gradients on, bf16 autocast, not GKG_DETERMINISTIC (the weight gradient adds
+    with atomics), an fp32 CUDA matrix with unit column stride and a pitch that is a multiple of 4, a dense 1x1 weight over
+    exactly its columns, and the library's answers for all three products (``supported(R, cin, cout)`` stands in for them in
+    tests).  ``bn`` takes no part: the BN passes behind the product are the caller's, unchanged."""
+    if not on:
+        return False
+    from . import fused
+    if not torch.is_grad_enabled() or fused.DETERMINISTIC:
+        return False
+    if not torch.is_autocast_enabled() or torch.get_autocast_dtype("cuda") != torch.bfloat16:
+        return False
+    if x.dtype != _F32 or not x.is_cuda or len(x.shape) != 2 or x.stride(1) != 1 or x.stride(0) % 4:
+        return False
+    wshape = tuple(conv.weight.shape)
+    if conv.groups != 1 or len(wshape) != 4 or wshape[2:] != (1, 1) or wshape[1] != x.shape[1]:
+        return False
+    R, cin, cout = x.shape[0], wshape[1], wshape[0]
+    if supported is not None:
+        return bool(supported(R, cin, cout))
+    lib = _lib.load()
+    return bool(lib.gkg_linear_bf16_f32a_supported(R, cin, cout, 0, 1, 0, 0) and lib.gkg_linear_bf16_f32a_supported(R, cout, cin, 1, 1, 0, 0)
+                and lib.gkg_linear_wgrad_bf16_supported(R, cin, cout))
+
+
+def _f32a(lib, x, planes, res, R, cin, cout, what):
+    """out (R, cout) fp32 = bf16(x) (R, cin) . planes (+ res) on gkg_linear_bf16_f32a."""
+    x = _rows(x, 4)
+    if res is not None:
+        res = _rows(res, 4)
+    out = torch.empty((R, cout), dtype=_F32, device=x.device)
+    _lib.check(lib.gkg_linear_bf16_f32a(_ptr(x), x.stride(0), _ptr(planes), None, None, _ptr(res), 0 if res is None else res.stride(0),
+                                        _ptr(out), cout, None, 0, R, cin, cout, 0, _stream()), what)
+    return out
+
+
+@torch.no_grad()
+def linear_bf16_train_fwd(x, conv):
+    """x (R, cin) fp32 -> Y = bf16(x) bf16(W)^T (R, cout) fp32: the pre-BN matrix (the conv bias stays in the BN passes)."""
+    assert x.dtype == _F32 and x.dim() == 2
+    cout = conv.weight.shape[0]
+    return _f32a(_lib.load(), x, _lin_planes_of(conv), None, x.shape[0], x.shape[1], cout, "gkg_linear_bf16_f32a (forward)")
+
+
+@torch.no_grad()
+def linear_bf16_dgrad(dY, conv, residual=None):
+    """dY (R, cout) fp32 -> dx = bf16(dY) bf16(W) (+ residual (R, cin) fp32: the skip gradient, added in the epilogue) (R, cin)."""
+    assert dY.dtype == _F32 and dY.dim() == 2
+    w = conv.weight
+    cout, cin = w.shape[0], w.numel() // w.shape[0]
+    assert dY.shape[1] == cout
+    if residual is not None:
+        assert residual.dtype == _F32 and tuple(residual.shape) == (dY.shape[0], cin)
+    return _f32a(_lib.load(), dY, _lin_planes_t_of(conv), residual, dY.shape[0], cout, cin, "gkg_linear_bf16_f32a (input gradient)")
+
+
+@torch.no_grad()
+def linear_bf16_wgrad(dY, x, out=None):
+    """dW (cout, cin) = bf16(dY)^T bf16(x) over the rows, fp32 accumulation, atomically added slabs (run-dependent order).  ``out``
+    as in ``fused._wgrad``'s x6 branch: a gradient-bucket slot is zeroed unless it carries ``_gkg_zero``; without one a fresh
+    zeroed tensor."""
+    assert dY.dtype == _F32 and x.dtype == _F32 and dY.shape[0] == x.shape[0]
+    R, cin, cout = x.shape[0], x.shape[1], dY.shape[1]
+    dY, x = _rows(dY, 4), _rows(x, 4)
+    if out is not None and (out.dtype != _F32 or not out.is_contiguous() or out.data_ptr() % 16):
+        out = None
+    if out is None:
+        out = torch.zeros((cout, cin), dtype=_F32, device=x.device)
+    elif not getattr(out, "_gkg_zero", False):          # a bucket slot cleared by GradBucket.release(prezero=True) is clean
+        out.zero_()
+    _lib.check(_lib.load().gkg_linear_wgrad_bf16(_ptr(dY), dY.stride(0), _ptr(x), x.stride(0), _ptr(out), R, cin, cout, _stream()),
+               "gkg_linear_wgrad_bf16")
     return out

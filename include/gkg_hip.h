@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define GKG_ABI_VERSION 15
+#define GKG_ABI_VERSION 16
 
 /* dtype codes */
 #define GKG_F32 0
@@ -405,6 +405,39 @@ int gkg_linear_bf16_knn_prep(const void* x /* bf16 (B N, ldx) */, int ldx, const
                              int has_y, int has_relpos, unsigned knn_flags, int fused_mr, int as_keys,
                              const float* res_tm, float* out_nchw, void* knn_workspace, size_t knn_workspace_bytes,
                              void* scratch, size_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Training under bf16 autocast (opt-in GKG_ENABLE=train_bf16): the three products of a dense 1x1 projection on bf16 operands with
+ * fp32 accumulation, the operands read as the fp32 tensors training keeps and rounded (round-to-nearest-even) on their way into
+ * LDS (csrc/gkg_linear_bf16.hip, csrc/gkg_linear_bf16_train.hip).  Reference layers as above, under mixed precision
+ * (configs: fp16 = dict(loss_scale='dynamic')).
+ *
+ * gkg_linear_bf16_f32a: gkg_linear_bf16 with an fp32 A operand, x (R, ldx) fp32.  Bit for bit the result of gkg_linear_bf16 called
+ * on the bf16 rounding of x, in every form (same contraction order and epilogue; the 64-column tile form at every shape, which
+ * changes no bit).  cshift == NULL means zero (this entry point only).  Preconditions: gkg_linear_bf16's with ldx % 4 == 0
+ * instead of ldx % 8 == 0; same error codes.  It serves
+ *   the forward         Y = x W^T:            a = cshift = NULL, fp32 out (the conv bias stays in the BN passes)
+ *   the input gradient  dx = dY W (+ dalias): x := dY, wplanes := the fragment array of W^T (contraction cout, output columns
+ *                                             cin), res := dalias.
+ * gkg_linear_bf16_f32a_supported: gkg_linear_bf16_supported's arguments and meaning for this entry point. */
+int gkg_linear_bf16_f32a_supported(int R, int cin, int cout, int has_res, int want_f32, int want_bf16, int act);
+int gkg_linear_bf16_f32a(const float* x /* fp32 (R, ldx) */, int ldx, const void* wplanes,
+                         const float* a /* [cout] or NULL = 1 */, const float* cshift /* [cout] or NULL = 0 */,
+                         const float* res /* fp32 (R, ldr) or NULL */, int ldr,
+                         float* out_f32 /* (R, ldo32) or NULL */, int ldo32,
+                         void* out_bf16 /* (R, ldo16) or NULL */, int ldo16,
+                         int R, int cin, int cout, int act /* 0 none, 1 GELU */, void* stream);
+/* The weight gradient: dw (cout, cin) += bf16(dy)^T bf16(x) over the R rows, dy (R, ldg) and x (R, ldx) fp32 in memory, exact
+ * bf16 x bf16 products, fp32 accumulation on v_mfma_f32_32x32x16_bf16.  gkg_linear_wgrad_x6's accumulation contract: a workgroup
+ * owns one dw tile and one slab of rows and ADDS its partial tile to dw (contiguous, row pitch cin) with fp32 atomics — the
+ * caller zeroes dw, the summation order is run-dependent.  R, cin and cout need not be multiples of any tile; nothing outside
+ * columns [0, cout) / [0, cin) of rows [0, R) of dy / x is read, nothing outside dw is written.  Preconditions, otherwise
+ * GKG_ERR_UNSUPPORTED with nothing launched: cin % 8 == 0, cout % 8 == 0, ldg % 4 == 0, ldx % 4 == 0, ldg >= cout, ldx >= cin,
+ * dy / x / dw 16-byte aligned, R <= INT_MAX - 32, a grid that fits; a size <= 0 is GKG_ERR_SHAPE, a null pointer GKG_ERR_NULL.
+ * gkg_linear_wgrad_bf16_supported: 1 when the sizes pass (pure host code). */
+int gkg_linear_wgrad_bf16_supported(int R, int cin, int cout);
+int gkg_linear_wgrad_bf16(const float* dy /* (R, ldg) */, int ldg, const float* x /* (R, ldx) */, int ldx,
+                          float* dw /* (cout, cin), += */, int R, int cin, int cout, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Bandwidth kernels between the dense 1x1 projections (Conv2d 1x1 + SyncBN [+ GELU], reference

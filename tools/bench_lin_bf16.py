@@ -20,7 +20,16 @@ GKG_ENABLE=lin_bf16,lin_bf16_prep) at every fc1 shape of GKGNet-576 (cfg3, B 32)
 
 The k-NN call is part of both sides because the library has no entry point that is the preparation launch alone; fc1_only_us /
 fc1_prep_us time the two projection launches without it (their difference is what the last-arriver tail costs, the pair's
-difference what the removed launch saves on top).  Same alternation, hipGraph replays and cache sweep as above."""
+difference what the removed launch saves on top).  Same alternation, hipGraph replays and cache sweep as above.
+
+--train: the three products of a dense layer under bf16 autocast WITH gradients (GKG_ENABLE=train_bf16) at the four dense layers of
+the four stage shapes of the cfg4 training step (GKGNet-576, B 32), each against what it replaces in ``fused._LinearBNAct``:
+
+    fwd     gkg_linear_bf16_f32a (fp32 x, fp32 Y)            vs  fused._mm_t under autocast (two casts + vendor GEMM + cast back)
+    dgrad   gkg_linear_bf16_f32a (fp32 dY, fragments of W^T)  vs  torch.mm(dY, W) in fp32 (autograd runs the backward outside autocast)
+    wgrad   gkg_linear_wgrad_bf16 (+ clearing dW)             vs  gkg_linear_wgrad_x6 (+ clearing dW)
+
+Same alternation, hipGraph replays and cache sweep."""
 import argparse
 import json
 import os
@@ -133,8 +142,77 @@ def prep_leg(args, lib, flush):
     return rows
 
 
+def train_leg(args, lib, flush):
+    from gkgnet_amd import fused
+    B = args.batch or 32
+    widths = {int(t) for t in args.widths.split(",")}
+    rows = []
+    for C, side in ((80, 144), (160, 72), (400, 36), (640, 18)):
+        if C not in widths:
+            continue
+        R = B * side * side
+        for name, cin, cout in (("fc1", C, C), ("fc2", 2 * C, C), ("ffn_fc1", C, 4 * C), ("ffn_fc2", 4 * C, C)):
+            gen = torch.Generator(device="cuda").manual_seed(cin * 7 + cout)
+            conv = torch.nn.Conv2d(cin, cout, 1).cuda()
+            x = torch.randn(R, cin, device="cuda", generator=gen)
+            dY = torch.randn(R, cout, device="cuda", generator=gen)
+            W = conv.weight.detach().view(cout, cin)
+            pf, pt = fused._lin_planes_of(conv), fused._lin_planes_t_of(conv)
+            Y, dx = torch.empty(R, cout, device="cuda"), torch.empty(R, cin, device="cuda")
+            dw_own, dw_x6 = torch.empty(cout, cin, device="cuda"), torch.empty(cout, cin, device="cuda")
+            V = {}
+
+            def fwd_own():
+                _lib.check(lib.gkg_linear_bf16_f32a(_ptr(x), cin, _ptr(pf), None, None, None, 0, _ptr(Y), cout, None, 0, R, cin, cout, 0,
+                                                    _stream()), "gkg_linear_bf16_f32a")
+
+            def fwd_old():
+                with torch.autocast("cuda", dtype=BF16):
+                    V["Y"] = fused._mm_t(x, W)
+
+            def dgrad_own():
+                _lib.check(lib.gkg_linear_bf16_f32a(_ptr(dY), cout, _ptr(pt), None, None, None, 0, _ptr(dx), cin, None, 0, R, cout, cin, 0,
+                                                    _stream()), "gkg_linear_bf16_f32a")
+
+            def dgrad_old():
+                V["dx"] = torch.mm(dY, W)
+
+            def wgrad_own():
+                dw_own.zero_()
+                _lib.check(lib.gkg_linear_wgrad_bf16(_ptr(dY), cout, _ptr(x), cin, _ptr(dw_own), R, cin, cout, _stream()),
+                           "gkg_linear_wgrad_bf16")
+
+            def wgrad_old():
+                dw_x6.zero_()
+                _lib.check(lib.gkg_linear_wgrad_x6(_ptr(dY), cout, 0, _ptr(x), cin, 0, _ptr(dw_x6), R, cin, cout, 1, 0, _stream()),
+                           "gkg_linear_wgrad_x6")
+            legs = (("fwd", fwd_own, fwd_old), ("dgrad", dgrad_own, dgrad_old), ("wgrad", wgrad_own, wgrad_old))
+            graphs = [(capture(a), capture(b)) for _, a, b in legs]
+            t = [([], []) for _ in legs]
+            for _ in range(args.reps):                                           # alternate all six
+                for i, (ga, gb) in enumerate(graphs):
+                    t[i][0].append(1e3 * replay_ms(ga, flush))
+                    t[i][1].append(1e3 * replay_ms(gb, flush))
+            # the two sides agree to bf16 resolution: a sanity check of the comparison, not a test
+            diffs = [(((a - b).abs().max() / b.abs().max()).item()) for a, b in ((Y, V["Y"]), (dx, V["dx"]), (dw_own, dw_x6))]
+            row = dict(layer=name, C=C, R=R, cin=cin, cout=cout)
+            msg = f"C={C:4d} {name:8s} R={R:6d} {cin:4d}->{cout:4d}:"
+            for (leg, _, _), (to, tv), d in zip(legs, t, diffs):
+                uo, uv = statistics.median(to), statistics.median(tv)
+                row.update({f"{leg}_own_us": round(uo, 1), f"{leg}_old_us": round(uv, 1), f"{leg}_own_us_min": round(min(to), 1),
+                            f"{leg}_own_us_max": round(max(to), 1), f"{leg}_old_us_min": round(min(tv), 1),
+                            f"{leg}_old_us_max": round(max(tv), 1), f"{leg}_own_tflops": round(2.0 * R * cin * cout / uo * 1e-6, 1),
+                            f"{leg}_max_rel_diff": float(f"{d:.3e}"), f"{leg}_winner": "own" if uo < uv else "old"})
+                msg += f"  {leg} own {uo:7.1f} [{min(to):.1f}, {max(to):.1f}] old {uv:7.1f} [{min(tv):.1f}, {max(tv):.1f}] us"
+            rows.append(row)
+            print(msg + "  (max rel diff " + " ".join(f"{d:.1e}" for d in diffs) + ")", flush=True)
+            del x, dY, Y, dx, V, graphs
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--train", action="store_true", help="run the three training products (GKG_ENABLE=train_bf16) at the cfg4 shapes")
     ap.add_argument("--prep", default=None, choices=sorted(PREP_CONFIGS), help="run the fc1 + k-NN preparation leg at this config's shapes")
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=15)
@@ -145,6 +223,14 @@ def main():
         raise SystemExit("bench_lin_bf16: needs a GPU (a timing anywhere else says nothing)")
     lib = _lib.load()
     flush = torch.empty(128 << 20, dtype=torch.float32, device="cuda")
+    if args.train:
+        rows = train_leg(args, lib, flush)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as fh:
+                json.dump(dict(tool="bench_lin_bf16 --train", batch=args.batch or 32, reps=args.reps,
+                               device=torch.cuda.get_device_name(0), rows=rows), fh, indent=1)
+        return
     if args.prep:
         rows = prep_leg(args, lib, flush)
         if args.out:
