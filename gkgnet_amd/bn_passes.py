@@ -12,10 +12,9 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
-from . import _lib
+from . import _lib, derived
 from .bn_scratch import _BnScratch
 from .ops import _ptr, _stream
-from .planes import param_version
 
 _F32 = torch.float32
 
@@ -58,23 +57,17 @@ def _ws(lib, R, C, nb, device) -> torch.Tensor:
 
 # ---- forward
 def eval_ac(lib, bn, bias, n):
-    """(a, c) of an eval-mode BN folded with the conv bias: out = a*Y + c.  Cached on the module and recomputed (one
-    small kernel) only when one of the tensors it derives from changed — an inference forward launched it per layer."""
-    srcs = [bn.weight, bn.bias, bn.running_mean, bn.running_var] + ([bias] if bias is not None else [])
-    epoch = getattr(bn, "_gkg_epoch", None)
-    key = tuple((param_version(t), t.data_ptr()) for t in srcs) + (bn.eps, n, epoch)
-    ent = getattr(bn, "_gkg_eval_ac", None)
-    if ent is None or ent[0] != key or epoch is None or torch.is_grad_enabled():
+    """(a, c) of an eval-mode BN folded with the conv bias: out = a*Y + c.  One small kernel, kept between calls (derived.get) —
+    an inference forward launched it per layer —, never with gradients on."""
+    def build():
         a = torch.empty(n, dtype=_F32, device=bn.weight.device)
         c = torch.empty_like(a)
         _lib.check(lib.gkg_bn_eval_affine(_ptr(bn.weight), _ptr(bn.bias), _ptr(bias), _ptr(bn.running_mean),
                                           _ptr(bn.running_var), _ptr(a), _ptr(c), n, float(bn.eps), _stream()),
                    "gkg_bn_eval_affine")
-        if torch.is_grad_enabled() or epoch is None:
-            return a, c
-        ent = (key, a, c)
-        bn._gkg_eval_ac = ent
-    return ent[1], ent[2]
+        return a, c
+    srcs = (bn.weight, bn.bias, bn.running_mean, bn.running_var) + (() if bias is None else (bias,))
+    return derived.get(bn, "eval_ac", srcs, build, extra=(bn.eps, n), stats_of=bn, cacheable=not torch.is_grad_enabled())
 
 
 def forward_params(lib, Y, bn, bias, R, C, nb, group):

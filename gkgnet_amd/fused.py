@@ -28,7 +28,7 @@ import torch
 import torch.distributed as dist
 import torch.nn.functional as F
 
-from . import _lib, bn_passes
+from . import _lib, bn_passes, derived
 from .ops import _ptr, _stream
 from .parallel import grad_view
 
@@ -370,54 +370,7 @@ def lowp_inference() -> bool:
             and torch.get_autocast_dtype("cuda") == torch.bfloat16)
 
 
-def _w16_of(conv) -> torch.Tensor:
-    """bf16 copy of a projection's weight, cached ON the module (inference: cast once, not per call) and refreshed
-    whenever the parameter is updated in place or replaced."""
-    w = conv.weight
-    ent = getattr(conv, "_gkg_w16", None)
-    if ent is None or ent[0] != param_version(w) or ent[1] != w.data_ptr():
-        ent = (param_version(w), w.data_ptr(), w.detach().to(torch.bfloat16))
-        conv._gkg_w16 = ent
-    return ent[2]
-
-
 FOLD_EPILOGUE = "fold_epilogue" not in _DISABLED
-
-
-def _folded_of(conv, bn):
-    """Inference (eval-mode BN): the BN scale folded into a bf16 copy of the weight and the shift (conv bias and running
-    mean included) as a bf16 bias — (W' (cout, cin), c' (cout)) — cached on the module and refreshed when any of the six
-    tensors it derives from changes.  With them out = act(x W'^T + c') is ONE library GEMM with a bias(+GELU) epilogue."""
-    srcs = [conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var] + ([conv.bias] if conv.bias is not None else [])
-    # the running statistics can change behind the version counters (layers._StatsEpoch): norm layers without the epoch
-    # counter are never cached
-    epoch = getattr(bn, "_gkg_epoch", None)
-    key = tuple((param_version(t), t.data_ptr()) for t in srcs) + (bn.eps, epoch)
-    ent = getattr(conv, "_gkg_fold", None)
-    if ent is None or ent[0] != key or epoch is None:
-        with torch.no_grad():
-            a = bn.weight.float() * torch.rsqrt(bn.running_var.float() + bn.eps)
-            shift = bn.bias.float() - a * bn.running_mean.float()
-            if conv.bias is not None:
-                shift = shift + a * conv.bias.float()
-            wf = (conv.weight.float().view(conv.weight.shape[0], -1) * a.view(-1, 1)).to(torch.bfloat16).contiguous()
-            ent = (key, wf, shift.to(torch.bfloat16).contiguous())
-        conv._gkg_fold = ent
-    return ent[1], ent[2]
-
-
-def _folded_shift32(conv, bn) -> torch.Tensor:
-    """The fp32 shift that goes with _folded_of's weights (cached beside them)."""
-    ent = conv._gkg_fold
-    if len(ent) < 4:
-        with torch.no_grad():
-            a = bn.weight.float() * torch.rsqrt(bn.running_var.float() + bn.eps)
-            shift = bn.bias.float() - a * bn.running_mean.float()
-            if conv.bias is not None:
-                shift = shift + a * conv.bias.float()
-        ent = ent + (shift.contiguous(),)
-        conv._gkg_fold = ent
-    return ent[3]
 
 
 def _mm_t(x, W, W16=None):
@@ -429,9 +382,9 @@ def _mm_t(x, W, W16=None):
     return Y if Y.dtype == _F32 else Y.float()
 
 
-from .linear_bf16 import (_lin_planes_of, lin_bf16_ok, linear_bf16_eval,      # noqa: E402,F401  (GKG_ENABLE=lin_bf16: linear_bf16.py)
+from .linear_bf16 import (lin_bf16_ok, linear_bf16_eval,      # noqa: E402,F401  (GKG_ENABLE=lin_bf16: linear_bf16.py)
                           lin_bf16_prep_ok, linear_bf16_knn_prep_eval)
-from .linear_bf16 import (_lin_planes_t_of, train_bf16_ok, linear_bf16_train_fwd,      # noqa: E402,F401  (GKG_ENABLE=train_bf16)
+from .linear_bf16 import (train_bf16_ok, linear_bf16_train_fwd,      # noqa: E402,F401  (GKG_ENABLE=train_bf16)
                           linear_bf16_dgrad, linear_bf16_wgrad)
 from .layout import _tm_dtype, _TokenMajorToCL, _ToTokenMajor, _BlockEntry, _AvgPoolTM      # noqa: E402  (layout Functions: layout.py)
 
@@ -1058,7 +1011,7 @@ def conv_bn_act_eval(conv, bn, act_mod, x, want32=True, want16=False):
     dt = torch.bfloat16 if ac16 else _F32
     xin = x if (x.dtype == dt and x.is_contiguous(memory_format=torch.channels_last)) else \
         x.to(dtype=dt, memory_format=torch.channels_last)
-    w = _w16_of(conv) if ac16 else conv.weight
+    w = derived.w16(conv) if ac16 else conv.weight
     with torch.autocast("cuda", enabled=False):
         y = torch.ops.aten.convolution(xin, w, None, list(conv.stride), list(conv.padding), list(conv.dilation), False, [0, 0], 1)
     if not y.is_contiguous(memory_format=torch.channels_last):
@@ -1372,7 +1325,7 @@ def _aggregate_project(x1b, yb, nn_idx, groups, nn_, C, lp):
         return mr_grouped_linear_eval(x1b, yb, nn_idx, groups, nn_[0], nn_[1])
     XM = _MaxRelativeTM.apply(x1b, yb, nn_idx, groups, 1, lp)       # (T, 2C) operand buffer [x | m]
     return _GroupedLinearBNAct.apply(XM, nn_[0].weight, nn_[0].bias, nn_[1].weight, nn_[1].bias, nn_[1], 1, lp,
-                                     _w16_of(nn_[0]) if lp else None)   # (T, 2C)
+                                     derived.w16(nn_[0]) if lp else None)   # (T, 2C)
 
 
 # ----------------------------------------------------------------------------------------------- row g1 (inference)
@@ -1380,23 +1333,6 @@ def _aggregate_project(x1b, yb, nn_idx, groups, nn_, C, lp):
 # (csrc/gkg_mrgemm.hip) — the [x, m] operand is produced tile by tile in LDS and never written.  GKG_DISABLE=mr_gemm restores
 # the three-launch form (gkg_mr_fwd_tm -> batched GEMM -> gkg_affine_act).
 MR_GEMM = "mr_gemm" not in _DISABLED
-
-
-def _mr_planes_of(conv) -> torch.Tensor:
-    """The grouped projection's weight as the bf16 fragment array gkg_mr_linear_bf16 streams: [4][ci_pad/8][co_pad][8]
-    (include/gkg_hip.h), cached on the module and rebuilt when the parameter changes."""
-    w = conv.weight
-    ent = getattr(conv, "_gkg_mrplanes", None)
-    if ent is None or ent[0] != param_version(w) or ent[1] != w.data_ptr():
-        co, ci = w.shape[0] // 4, w.shape[1]
-        ci_pad, co_pad = (ci + 15) // 16 * 16, (co + 31) // 32 * 32
-        W = torch.zeros((4, co_pad, ci_pad), dtype=torch.bfloat16, device=w.device)
-        W[:, :co, :ci] = w.detach().reshape(4, co, ci).to(torch.bfloat16)
-        planes = W.view(4, co_pad, ci_pad // 8, 8).permute(0, 2, 1, 3).contiguous()
-        assert planes.numel() * 2 == _lib.load().gkg_mr_linear_planes_bytes(4 * ci // 2)
-        ent = (param_version(w), w.data_ptr(), planes)
-        conv._gkg_mrplanes = ent
-    return ent[2]
 
 
 def _mr_gemm_ok(nn_, C, lp) -> bool:
@@ -1417,7 +1353,7 @@ def mr_grouped_linear_eval(x, src, nn_idx, G, conv, bn, act=1):
     a, c = bn_passes.eval_ac(lib, bn, conv.bias, 2 * C)
     out = torch.empty((B * N, 2 * C), dtype=torch.bfloat16, device=x.device)
     fn = lib.gkg_mr_linear_bf16_nn16 if nn_idx.dtype == torch.int16 else lib.gkg_mr_linear_bf16      # compact lists: knn_graph_tm16
-    _lib.check(fn(_ptr(x), _ptr(src), _ptr(nn_idx), _ptr(_mr_planes_of(conv)), _ptr(a), _ptr(c), _ptr(out),
+    _lib.check(fn(_ptr(x), _ptr(src), _ptr(nn_idx), _ptr(derived.mr_planes(conv)), _ptr(a), _ptr(c), _ptr(out),
                   2 * C, B, G, C // G, N, M, nn_idx.shape[2], act, _stream()), "gkg_mr_linear_bf16")
     return out
 
@@ -1472,7 +1408,7 @@ def _lin(x, seq, act=0, residual=None, nchw=None, out_lowp=False, scale=None, ro
         if not (torch.is_grad_enabled() and x.requires_grad):
             return _lin(x, seq, act, residual, nchw, out_lowp, scale, rows_per_scale, want16, xm=xm, knn=knn), x
         conv, bn = seq[0], seq[1]
-        w16 = _w16_of(conv) if x.dtype == torch.bfloat16 else None
+        w16 = derived.w16(conv) if x.dtype == torch.bfloat16 else None
         return _LinearBNAct.apply(x, conv.weight, conv.bias, bn.weight, bn.bias, residual, bn, act, nchw, out_lowp, w16, scale,
                                   rows_per_scale, want16, True, False, xm, knn, _train_bf16_conv(x, conv, bn))
     conv, bn = seq[0], seq[1]
@@ -1495,16 +1431,16 @@ def _lin(x, seq, act=0, residual=None, nchw=None, out_lowp=False, scale=None, ro
             and not torch.is_grad_enabled() and not bn.training and bn.track_running_stats and conv.weight.dim() == 4
             and conv.groups == 1):
         # bf16 inference, activation only feeds the next GEMM: BN folded into the weights, bias (+ GELU) in the GEMM epilogue
-        wf, cf = _folded_of(conv, bn)
+        wf, cf, _ = derived.folded(conv, bn)
         return torch._addmm_activation(cf, x, wf.t(), use_gelu=(act == 1))
     if (FOLD_EPILOGUE and not out_lowp and act == 0 and x.dtype == torch.bfloat16 and residual is None and nchw is None
             and scale is None and not want16 and not torch.is_grad_enabled() and not bn.training and bn.track_running_stats
             and conv.weight.dim() == 4 and conv.groups == 1):
         # bf16 inference, fp32 result wanted (the Grapher's fc1: the k-NN and the aggregation read it in fp32): BN scale
         # folded into the bf16 weights, the shift as an fp32 bias in the GEMM epilogue, fp32 accumulate AND fp32 output
-        wf, _ = _folded_of(conv, bn)
-        return torch.addmm(_folded_shift32(conv, bn), x, wf.t(), out_dtype=_F32)
-    w16 = _w16_of(conv) if x.dtype == torch.bfloat16 else None
+        wf, _, cf32 = derived.folded(conv, bn)
+        return torch.addmm(cf32, x, wf.t(), out_dtype=_F32)
+    w16 = derived.w16(conv) if x.dtype == torch.bfloat16 else None
     return _LinearBNAct.apply(x, conv.weight, conv.bias, bn.weight, bn.bias, residual, bn, act, nchw, out_lowp, w16, scale,
                               rows_per_scale, want16, False, dual, xm, knn, _train_bf16_conv(x, conv, bn))
 

@@ -45,8 +45,8 @@ def _guard_memory_format(norm_forward):
 class _StatsEpoch:
     """``_gkg_epoch`` changes whenever the running statistics may have changed behind PyTorch's version counters: the fused
     path's kernels update them through raw pointers (and a captured training step does so without running any Python), so
-    every train() / eval() switch and every eager train-mode update bumps it.  Inference-time caches derived from the
-    statistics (bn_passes.eval_ac, fused._folded_of) are keyed on it; bn_passes.touch is the bump of an eager update."""
+    every train() / eval() switch and every eager train-mode update bumps it.  What derived.get keeps of values computed from the
+    statistics (``stats_of``: the eval_ac and folded slots) is keyed on it; bn_passes.touch is the bump of an eager update."""
     _gkg_epoch = 0
 
     def train(self, mode: bool = True):

@@ -1,5 +1,5 @@
 """bf16 inference: a dense 1x1 projection with its eval-mode BN (+ GELU) (+ residual) as ONE launch of the library's own kernel
-(gkg_linear_bf16, csrc/gkg_linear_bf16.hip) — the weight's fragment array, the call, and the predicate ``fused._lin`` asks before
+(gkg_linear_bf16, csrc/gkg_linear_bf16.hip) — the call (the weight's fragment array: derived.lin_planes) and the predicate ``fused._lin`` asks before
 it dispatches here — and the same launch with the k-NN's token preparation riding on it (gkg_linear_bf16_knn_prep: a Grapher's
 fc1).  Also the training side (GKG_ENABLE=train_bf16): the same kernel reading an fp32 A operand for a layer's forward and input
 gradient (gkg_linear_bf16_f32a), the bf16 weight-gradient kernel (gkg_linear_wgrad_bf16) and their predicate.  Mechanism only: the
@@ -9,52 +9,10 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib, bn_passes
+from . import _lib, bn_passes, derived
 from .ops import _ptr, _stream
-from .planes import param_version
 
 _F32 = torch.float32
-
-
-def _lin_planes_of(conv) -> torch.Tensor:
-    """The projection's UNFOLDED weight as the bf16 fragment array gkg_linear_bf16 streams: [ci_pad/8][co_pad][8], fragment
-    (f, n) = w[n][8f .. 8f+7], zero outside (include/gkg_hip.h) — cached on the module and rebuilt when the parameter changes."""
-    w = conv.weight
-    ent = getattr(conv, "_gkg_linplanes", None)
-    if ent is None or ent[0] != param_version(w) or ent[1] != w.data_ptr():
-        co, ci = w.shape[0], w.numel() // w.shape[0]
-        nbytes = int(_lib.load().gkg_linear_bf16_planes_bytes(ci, co))       # the library owns the paddings
-        ci_pad = (ci + 15) // 16 * 16
-        co_pad = nbytes // (2 * ci_pad) if nbytes else 0
-        assert nbytes and co_pad >= co and co_pad * ci_pad * 2 == nbytes, (ci, co, nbytes)
-        W = torch.zeros((co_pad, ci_pad), dtype=torch.bfloat16, device=w.device)
-        W[:co, :ci] = w.detach().reshape(co, ci).to(torch.bfloat16)
-        planes = W.view(co_pad, ci_pad // 8, 8).permute(1, 0, 2).contiguous()
-        assert planes.numel() * 2 == nbytes
-        ent = (param_version(w), w.data_ptr(), planes)
-        conv._gkg_linplanes = ent
-    return ent[2]
-
-
-def _lin_planes_t_of(conv) -> torch.Tensor:
-    """The fragment array of the TRANSPOSED weight, what the input gradient dx = dY W streams (gkg_linear_bf16_f32a with
-    contraction cout and output columns cin): [co_pad'/8][ci_pad'][8], fragment (f, n) = w[8f .. 8f+7][n] — _lin_planes_of's
-    layout built from w.t(), with that product's paddings (cout to 16, cin to 32).  Cached on the module like _lin_planes_of."""
-    w = conv.weight
-    ent = getattr(conv, "_gkg_linplanes_t", None)
-    if ent is None or ent[0] != param_version(w) or ent[1] != w.data_ptr():
-        co, ci = w.shape[0], w.numel() // w.shape[0]
-        nbytes = int(_lib.load().gkg_linear_bf16_planes_bytes(co, ci))       # contraction co, columns ci
-        k_pad = (co + 15) // 16 * 16
-        n_pad = nbytes // (2 * k_pad) if nbytes else 0
-        assert nbytes and n_pad >= ci and n_pad * k_pad * 2 == nbytes, (ci, co, nbytes)
-        Wt = torch.zeros((n_pad, k_pad), dtype=torch.bfloat16, device=w.device)
-        Wt[:ci, :co] = w.detach().reshape(co, ci).t().to(torch.bfloat16)
-        planes = Wt.view(n_pad, k_pad // 8, 8).permute(1, 0, 2).contiguous()
-        assert planes.numel() * 2 == nbytes
-        ent = (param_version(w), w.data_ptr(), planes)
-        conv._gkg_linplanes_t = ent
-    return ent[2]
 
 
 def lin_bf16_ok(on, lp, x, conv, bn, chain=True, nchw=None, scale=None, xm=None, knn=None, alias=False, dual=False,
@@ -100,7 +58,7 @@ def linear_bf16_eval(x16, conv, bn, act=0, residual=None, want_f32=True, want_bf
     a, c = bn_passes.eval_ac(lib, bn, conv.bias, cout)
     o32 = torch.empty((R, cout), dtype=_F32, device=x16.device) if want_f32 else None
     o16 = torch.empty((R, cout), dtype=torch.bfloat16, device=x16.device) if want_bf16 else None
-    _lib.check(lib.gkg_linear_bf16(_ptr(x16), x16.stride(0), _ptr(_lin_planes_of(conv)), _ptr(a), _ptr(c), _ptr(residual),
+    _lib.check(lib.gkg_linear_bf16(_ptr(x16), x16.stride(0), _ptr(derived.lin_planes(conv)), _ptr(a), _ptr(c), _ptr(residual),
                                    0 if residual is None else residual.stride(0), _ptr(o32), cout, _ptr(o16), cout, R, cin, cout,
                                    act, _stream()), "gkg_linear_bf16")
     return o32, o16
@@ -177,7 +135,7 @@ def linear_bf16_knn_prep_eval(x16, conv, bn, knn):
     out = torch.empty((R, cout), dtype=_F32, device=x16.device)
     stream = _stream()
     scratch = _prep_scratch(lib, x16.device, stream, R)
-    _lib.check(lib.gkg_linear_bf16_knn_prep(_ptr(x16), x16.stride(0), _ptr(_lin_planes_of(conv)), cin, _ptr(a), _ptr(c),
+    _lib.check(lib.gkg_linear_bf16_knn_prep(_ptr(x16), x16.stride(0), _ptr(derived.lin_planes(conv)), cin, _ptr(a), _ptr(c),
                                             *knn.producer_args(lib, out, None, None, cout, 0), _ptr(scratch), scratch.numel(),
                                             stream), "gkg_linear_bf16_knn_prep")
     knn.mark(out)
@@ -230,7 +188,7 @@ def linear_bf16_train_fwd(x, conv):
     """x (R, cin) fp32 -> Y = bf16(x) bf16(W)^T (R, cout) fp32: the pre-BN matrix (the conv bias stays in the BN passes)."""
     assert x.dtype == _F32 and x.dim() == 2
     cout = conv.weight.shape[0]
-    return _f32a(_lib.load(), x, _lin_planes_of(conv), None, x.shape[0], x.shape[1], cout, "gkg_linear_bf16_f32a (forward)")
+    return _f32a(_lib.load(), x, derived.lin_planes(conv), None, x.shape[0], x.shape[1], cout, "gkg_linear_bf16_f32a (forward)")
 
 
 @torch.no_grad()
@@ -242,7 +200,7 @@ def linear_bf16_dgrad(dY, conv, residual=None):
     assert dY.shape[1] == cout
     if residual is not None:
         assert residual.dtype == _F32 and tuple(residual.shape) == (dY.shape[0], cin)
-    return _f32a(_lib.load(), dY, _lin_planes_t_of(conv), residual, dY.shape[0], cout, cin, "gkg_linear_bf16_f32a (input gradient)")
+    return _f32a(_lib.load(), dY, derived.lin_planes_t(conv), residual, dY.shape[0], cout, cin, "gkg_linear_bf16_f32a (input gradient)")
 
 
 @torch.no_grad()

@@ -268,7 +268,7 @@ def test_gradients_stay_as_close_to_fp32_as_torch_autocast_does(monkeypatch):
 
 
 def test_two_sgd_steps_rebuild_the_fragments(monkeypatch):
-    from gkgnet_amd import fused
+    from gkgnet_amd import derived, fused
     x, cot = _inputs()
     rec, _, _ = _instrument(monkeypatch)
     monkeypatch.setattr(fused, "TRAIN_BF16", True)
@@ -282,7 +282,7 @@ def test_two_sgd_steps_rebuild_the_fragments(monkeypatch):
             rec[k].clear()
         w_at.append(conv.weight.detach().clone())
         out, dx, grads = _step(g, ffn, x, cot)
-        planes.append((conv._gkg_linplanes[2], conv._gkg_linplanes_t[2]))
+        planes.append((derived.peek(conv, "lin_planes"), derived.peek(conv, "lin_planes_t")))
         for t in (out, dx, *grads.values()):
             assert bool(torch.isfinite(t).all())
         opt.step()

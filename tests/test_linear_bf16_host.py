@@ -37,10 +37,10 @@ def test_host_functions_answer_without_a_device():
 
 
 def test_planes_are_the_fragments_of_the_unfolded_weight_and_cached():
-    from gkgnet_amd import _lib, fused
+    from gkgnet_amd import _lib, derived
     torch.manual_seed(3)
     conv = torch.nn.Conv2d(24, 40, 1)
-    p = fused._lin_planes_of(conv)
+    p = derived.lin_planes(conv)
     assert p.dtype == torch.bfloat16 and p.is_contiguous()
     assert p.numel() * 2 == _lib.load().gkg_linear_bf16_planes_bytes(24, 40)
     nf, co_pad, _ = p.shape
@@ -52,10 +52,10 @@ def test_planes_are_the_fragments_of_the_unfolded_weight_and_cached():
                 want = w16[n, 8 * f:8 * f + 8]
             assert torch.equal(p[f, n], want), (f, n)
     assert (p[3:] == 0).all() and (p[:, 40:] == 0).all()                         # the pad region
-    assert fused._lin_planes_of(conv) is p                                       # cached
+    assert derived.lin_planes(conv) is p                                       # cached
     with torch.no_grad():
         conv.weight.mul_(2.0)
-    p2 = fused._lin_planes_of(conv)
+    p2 = derived.lin_planes(conv)
     assert p2 is not p and torch.equal(p2[:3, :40].float(), 2.0 * p[:3, :40].float())
 
 

@@ -116,20 +116,20 @@ def _fragments(w2d):
 
 
 def test_transposed_planes_are_the_fragments_of_w_t_and_cached():
-    from gkgnet_amd import _lib, fused
+    from gkgnet_amd import _lib, derived
     torch.manual_seed(5)
     conv = torch.nn.Conv2d(24, 40, 1)                                            # cout 40 -> contraction pad 48, cin 24 -> 32 columns
-    pt = fused._lin_planes_t_of(conv)
+    pt = derived.lin_planes_t(conv)
     assert pt.dtype == torch.bfloat16 and pt.is_contiguous() and tuple(pt.shape) == (6, 32, 8)
     assert pt.numel() * 2 == _lib.load().gkg_linear_bf16_planes_bytes(40, 24)
     w = conv.weight.detach().reshape(40, 24)
     assert torch.equal(pt.view(torch.int16), _fragments(w.t()).view(torch.int16))
     # the forward array is the same layout of w itself: the two are one construction
-    assert torch.equal(fused._lin_planes_of(conv).view(torch.int16), _fragments(w).view(torch.int16))
+    assert torch.equal(derived.lin_planes(conv).view(torch.int16), _fragments(w).view(torch.int16))
     assert bool((pt[5] == 0).all()) and bool((pt[:, 24:] == 0).all())            # the pad region
-    assert fused._lin_planes_t_of(conv) is pt                                    # cached
+    assert derived.lin_planes_t(conv) is pt                                    # cached
     with torch.no_grad():
         conv.weight.mul_(2.0)                                                    # an in-place parameter update
-    pt2 = fused._lin_planes_t_of(conv)
+    pt2 = derived.lin_planes_t(conv)
     assert pt2 is not pt and torch.equal(pt2.float(), 2.0 * pt.float())
     assert torch.equal(pt2.view(torch.int16), _fragments(conv.weight.detach().reshape(40, 24).t()).view(torch.int16))

@@ -30,13 +30,13 @@ def test_token_moves_with_a_fused_step_and_with_the_manual_mark():
 
 
 def test_bf16_weight_copy_follows_a_fused_step():
-    from gkgnet_amd import fused
+    from gkgnet_amd import derived
     conv = torch.nn.Conv2d(8, 8, 1)
-    w0 = fused._w16_of(conv).clone()
-    assert fused._w16_of(conv) is fused._w16_of(conv)             # cached
+    w0 = derived.w16(conv).clone()
+    assert derived.w16(conv) is derived.w16(conv)             # cached
     conv.weight.grad = torch.ones_like(conv.weight)
     _fused_adamw([conv.weight], 0.5).step()
-    w1 = fused._w16_of(conv)
+    w1 = derived.w16(conv)
     assert not torch.equal(w0, w1)
     assert torch.equal(w1, conv.weight.detach().to(torch.bfloat16))
 

@@ -143,7 +143,7 @@ def prep_leg(args, lib, flush):
 
 
 def train_leg(args, lib, flush):
-    from gkgnet_amd import fused
+    from gkgnet_amd import derived, fused
     B = args.batch or 32
     widths = {int(t) for t in args.widths.split(",")}
     rows = []
@@ -157,7 +157,7 @@ def train_leg(args, lib, flush):
             x = torch.randn(R, cin, device="cuda", generator=gen)
             dY = torch.randn(R, cout, device="cuda", generator=gen)
             W = conv.weight.detach().view(cout, cin)
-            pf, pt = fused._lin_planes_of(conv), fused._lin_planes_t_of(conv)
+            pf, pt = derived.lin_planes(conv), derived.lin_planes_t(conv)
             Y, dx = torch.empty(R, cout, device="cuda"), torch.empty(R, cin, device="cuda")
             dw_own, dw_x6 = torch.empty(cout, cin, device="cuda"), torch.empty(cout, cin, device="cuda")
             V = {}
@@ -260,7 +260,7 @@ def main():
             W[:cout, :cin] = w.to(BF16)
             planes = W.view(co_pad, ci_pad // 8, 8).permute(1, 0, 2).contiguous()
             assert planes.numel() * 2 == lib.gkg_linear_bf16_planes_bytes(cin, cout)
-            wf = (w * a.view(-1, 1)).to(BF16).contiguous()       # the vendor side's folded weight (fused._folded_of)
+            wf = (w * a.view(-1, 1)).to(BF16).contiguous()       # the vendor side's folded weight (derived.folded)
             w16 = w.to(BF16).contiguous()
             o32 = torch.empty(R, cout, device="cuda") if f32 else None
             o16 = torch.empty(R, cout, device="cuda", dtype=BF16) if b16 else None
