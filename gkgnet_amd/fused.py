@@ -72,6 +72,10 @@ DETERMINISTIC = os.environ.get("GKG_DETERMINISTIC", "0") != "0"
 #                  Taken only at the shapes where it measured at least as fast as the two launches (linear_bf16.prep_pays: the
 #                  stage-1 shapes of cfg3 / cfg5); lin_bf16_prep_all takes it wherever the library accepts the shape (tests,
 #                  measurements).
+#   ffn_bf16       with lin_bf16 only: an FFN's two projections (fc1 + BN + GELU, fc2 + BN + residual) as ONE launch that keeps the
+#                  (T, 4C) bf16 hidden matrix in LDS instead of writing it and reading it back (gkg_ffn_bf16; linear_bf16.py).
+#                  Same bits as lin_bf16 alone.  C <= 192 (the stages with the most rows); wider FFNs, an active DropPath, NCHW
+#                  input and the label branch keep the two launches.  Opt-in: per-shape measurements in EXPERIMENTS.md.
 #   train_bf16     training under bf16 autocast: the three products of a dense projection of a Grapher / FFN block (_LinearBNAct under
 #                  autocast: Y = x W^T, dx = dY W (+ the skip gradient), dW = dY^T x) run on the library's own bf16 kernels — bf16
 #                  operands rounded from the fp32 tensors on their way into LDS, fp32 accumulation (gkg_linear_bf16_f32a,
@@ -99,6 +103,7 @@ KNN_BF16 = "knn_bf16" in _ENABLED
 LIN_BF16 = "lin_bf16" in _ENABLED          # a module constant the tests flip (like MR_GEMM)
 # likewise (False | True: the measured shapes | "all": every supported shape); acts only together with LIN_BF16
 LIN_BF16_PREP = "all" if "lin_bf16_prep_all" in _ENABLED else ("lin_bf16_prep" in _ENABLED)
+FFN_BF16 = "ffn_bf16" in _ENABLED          # likewise; acts only together with LIN_BF16
 TRAIN_BF16 = "train_bf16" in _ENABLED      # likewise a module constant the tests flip
 
 
@@ -384,6 +389,7 @@ def _mm_t(x, W, W16=None):
 
 from .linear_bf16 import (lin_bf16_ok, linear_bf16_eval,      # noqa: E402,F401  (GKG_ENABLE=lin_bf16: linear_bf16.py)
                           lin_bf16_prep_ok, linear_bf16_knn_prep_eval)
+from .linear_bf16 import ffn_bf16_ok, ffn_bf16_eval      # noqa: E402,F401  (GKG_ENABLE=lin_bf16,ffn_bf16)
 from .linear_bf16 import (train_bf16_ok, linear_bf16_train_fwd,      # noqa: E402,F401  (GKG_ENABLE=train_bf16)
                           linear_bf16_dgrad, linear_bf16_wgrad)
 from .layout import _tm_dtype, _TokenMajorToCL, _ToTokenMajor, _BlockEntry, _AvgPoolTM      # noqa: E402  (layout Functions: layout.py)
@@ -1601,13 +1607,20 @@ def ffn_supported(mod, x) -> bool:
 
 
 def ffn_forward(mod, x):
-    """reference gkgnet.py:66-72 on token-major activations: two library GEMMs + the BN/GELU/residual kernels."""
+    """reference gkgnet.py:66-72 on token-major activations: two library GEMMs + the BN/GELU/residual kernels (bf16 inference,
+    opt-in: the two projections on the own bf16 kernel, as two launches or — GKG_ENABLE=lin_bf16,ffn_bf16 — as one)."""
     lp = lowp_inference()
     B, C, H, W = x.shape
     xt, x, cl = _block_entry(x, lp)
-    h = _lin(xt, mod.fc1, act=1, out_lowp=lp, chain=cl)
     if cl:
-        out = _lin(h, mod.fc2, residual=x, scale=_drop_scale(mod.drop_path, B, x.device), rows_per_scale=H * W, want16=lp,
-                   chain=True)
+        scale = _drop_scale(mod.drop_path, B, x.device)
+        if LIN_BF16 and ffn_bf16_ok(FFN_BF16, lp, xt, mod.fc1, mod.fc2, x, scale, True):
+            # bf16 inference, opt-in: both projections in ONE launch, the (T, 4C) hidden matrix stays on chip (the pair's bits)
+            out, o16 = ffn_bf16_eval(xt, mod.fc1, mod.fc2, x, want_f32=True, want_bf16=True)
+            out._gkg_bf16_tm = o16
+        else:
+            h = _lin(xt, mod.fc1, act=1, out_lowp=lp, chain=True)
+            out = _lin(h, mod.fc2, residual=x, scale=scale, rows_per_scale=H * W, want16=lp, chain=True)
         return _cl_out(out, B, H, W)
+    h = _lin(xt, mod.fc1, act=1, out_lowp=lp)
     return _lin(h, mod.fc2, residual=x, nchw=(B, C, H, W), scale=_drop_scale(mod.drop_path, B, x.device))

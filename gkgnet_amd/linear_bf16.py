@@ -1,9 +1,9 @@
 """bf16 inference: a dense 1x1 projection with its eval-mode BN (+ GELU) (+ residual) as ONE launch of the library's own kernel
 (gkg_linear_bf16, csrc/gkg_linear_bf16.hip) — the call (the weight's fragment array: derived.lin_planes) and the predicate ``fused._lin`` asks before
 it dispatches here — and the same launch with the k-NN's token preparation riding on it (gkg_linear_bf16_knn_prep: a Grapher's
-fc1).  Also the training side (GKG_ENABLE=train_bf16): the same kernel reading an fp32 A operand for a layer's forward and input
+fc1) — and an FFN's two projections as one launch with the hidden matrix kept on chip (gkg_ffn_bf16, csrc/gkg_ffn_bf16.hip).  Also the training side (GKG_ENABLE=train_bf16): the same kernel reading an fp32 A operand for a layer's forward and input
 gradient (gkg_linear_bf16_f32a), the bf16 weight-gradient kernel (gkg_linear_wgrad_bf16) and their predicate.  Mechanism only: the
-switches (``fused.LIN_BF16``, ``fused.LIN_BF16_PREP``, ``fused.TRAIN_BF16``) and the mode test (``fused.lowp_inference``) stay in
+switches (``fused.LIN_BF16``, ``fused.LIN_BF16_PREP``, ``fused.FFN_BF16``, ``fused.TRAIN_BF16``) and the mode test (``fused.lowp_inference``) stay in
 ``fused.py`` and arrive as arguments."""
 from __future__ import annotations
 
@@ -61,6 +61,68 @@ def linear_bf16_eval(x16, conv, bn, act=0, residual=None, want_f32=True, want_bf
     _lib.check(lib.gkg_linear_bf16(_ptr(x16), x16.stride(0), _ptr(derived.lin_planes(conv)), _ptr(a), _ptr(c), _ptr(residual),
                                    0 if residual is None else residual.stride(0), _ptr(o32), cout, _ptr(o16), cout, R, cin, cout,
                                    act, _stream()), "gkg_linear_bf16")
+    return o32, o16
+
+
+# ---- an FFN as one launch (gkg_ffn_bf16, csrc/gkg_ffn_bf16.hip): fc1 + BN + GELU + fc2 + BN + residual, the hidden kept on chip ----
+# No dispatch rule beyond the library's envelope (cin, cout <= 192): every FFN shape inside it measured faster than the pair of
+# gkg_linear_bf16 launches.  MI355X, tools/bench_lin_bf16.py --ffn, us per FFN, median of 11 alternating replays [min, max], one box
+# (EXPERIMENTS.md "Fused bf16 FFN", profiles/ffn_bf16_layers_*.txt):
+#   cfg3 (GKGNet-576, B 32)   C  80  hid 320  R 663 552   pair 543 [534, 581]   fused 296 [285, 317]
+#                             C 160  hid 640  R 165 888   pair 337 [333, 342]   fused 234 [231, 239]
+#   cfg5 (pvig_m 768^2, B 16) C  96  hid 384  R 589 824   pair 535 [516, 570]   fused 314 [309, 338]
+#                             C 192  hid 768  R 147 456   pair 344 [338, 350]   fused 244 [240, 251]
+# (C 400 / 640 / 384 / 768, stages 3-4: outside the envelope, the two launches.)
+class _Rows:
+    """What lin_bf16_ok reads of an operand (dtype, shape): the bf16 hidden matrix the fused launch never makes."""
+
+    def __init__(self, R, C):
+        self.dtype, self.shape = torch.bfloat16, (R, C)
+
+
+def ffn_bf16_ok(on, lp, x, fc1, fc2, residual, scale, chain, supported=None, act=1) -> bool:
+    """Whether ``fused.ffn_forward`` hands the FFN (``fc1`` / ``fc2``: its (conv, bn) pairs) to ffn_bf16_eval instead of two
+    linear_bf16_eval calls: the switch, lin_bf16_ok for both layers (bf16 autocast with gradients off, the channels-last chain,
+    eval-mode BN, dense 1x1 convs), no DropPath scale, a GELU on the hidden (``act`` == 1), an fp32 residual of the output's shape
+    (or none) and the library's answer for the sizes (``supported(R, cin, hid, cout)`` stands in for it in tests)."""
+    if not on or scale is not None or act != 1:
+        return False
+    fine = (lambda R, ci, co: True) if supported is not None else None        # the pair's own answer is asked below, once
+    if not lin_bf16_ok(on, lp, x, fc1[0], fc1[1], chain, scale=scale, supported=fine):
+        return False
+    R, cin, hid = x.shape[0], x.shape[1], fc1[0].weight.shape[0]
+    if not lin_bf16_ok(on, lp, _Rows(R, hid), fc2[0], fc2[1], chain, scale=scale, supported=fine):
+        return False
+    cout = fc2[0].weight.shape[0]
+    if residual is not None and (residual.dtype != _F32 or tuple(residual.shape) != (R, cout)):
+        return False
+    if supported is not None:
+        return bool(supported(R, cin, hid, cout))
+    return bool(_lib.load().gkg_ffn_bf16_supported(R, cin, hid, cout, int(residual is not None), 1, 1, 1))
+
+
+@torch.no_grad()
+def ffn_bf16_eval(x16, fc1, fc2, residual=None, want_f32=True, want_bf16=False):
+    """x16 (R, cin) bf16 -> BN2(fc2(bf16(GELU(BN1(fc1(x16)))))) (+ residual (R, cout) fp32) as (out_f32 | None, out_bf16 | None): the
+    bits of linear_bf16_eval(x16, *fc1, act=1, want_f32=False, want_bf16=True) followed by linear_bf16_eval(h16, *fc2, 0, residual,
+    ...), in one launch that keeps the (R, hid) hidden matrix on chip (reference gkgnet.py:66-72)."""
+    lib = _lib.load()
+    R, cin = x16.shape
+    (conv1, bn1), (conv2, bn2) = (fc1[0], fc1[1]), (fc2[0], fc2[1])
+    hid, cout = conv1.weight.shape[0], conv2.weight.shape[0]
+    assert x16.dtype == torch.bfloat16 and conv2.weight.shape[1] == hid and (want_f32 or want_bf16)
+    x16 = _rows(x16, 8)
+    if residual is not None:
+        assert residual.dtype == _F32 and tuple(residual.shape) == (R, cout)
+        residual = _rows(residual, 4)
+    a1, c1 = bn_passes.eval_ac(lib, bn1, conv1.bias, hid)
+    a2, c2 = bn_passes.eval_ac(lib, bn2, conv2.bias, cout)
+    o32 = torch.empty((R, cout), dtype=_F32, device=x16.device) if want_f32 else None
+    o16 = torch.empty((R, cout), dtype=torch.bfloat16, device=x16.device) if want_bf16 else None
+    _lib.check(lib.gkg_ffn_bf16(_ptr(x16), x16.stride(0), _ptr(derived.lin_planes(conv1)), _ptr(a1), _ptr(c1),
+                                _ptr(derived.lin_planes(conv2)), _ptr(a2), _ptr(c2), _ptr(residual),
+                                0 if residual is None else residual.stride(0), _ptr(o32), cout, _ptr(o16), cout, R, cin, hid, cout,
+                                1, _stream()), "gkg_ffn_bf16")
     return o32, o16
 
 

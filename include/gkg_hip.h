@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define GKG_ABI_VERSION 16
+#define GKG_ABI_VERSION 17
 
 /* dtype codes */
 #define GKG_F32 0
@@ -405,6 +405,27 @@ int gkg_linear_bf16_knn_prep(const void* x /* bf16 (B N, ldx) */, int ldx, const
                              int has_y, int has_relpos, unsigned knn_flags, int fused_mr, int as_keys,
                              const float* res_tm, float* out_nchw, void* knn_workspace, size_t knn_workspace_bytes,
                              void* scratch, size_t scratch_bytes, void* stream);
+/* An FFN (reference gkgnet.py:46-72: fc1 + BN + GELU, fc2 + BN + shortcut) under bf16 autocast with gradients off as ONE launch
+ * (csrc/gkg_ffn_bf16.hip): the (R, hid) hidden matrix stays on chip.  w1planes / w2planes are the gkg_linear_bf16 fragment arrays of
+ * the cin -> hid and hid -> cout layers (gkg_linear_bf16_planes_bytes(cin, hid) / (hid, cout) bytes), a1 / c1 / a2 / c2 their BN
+ * scale / shift vectors, act the activation ON THE HIDDEN.  Bit for bit, in every form, the outputs of the two launches
+ *   gkg_linear_bf16(x, ldx, w1planes, a1, c1, NULL, 0, NULL, 0, h16, hid, R, cin, hid, act, stream)        h16 (R, hid) bf16
+ *   gkg_linear_bf16(h16, hid, w2planes, a2, c2, res, ldr, out_f32, ldo32, out_bf16, ldo16, R, hid, cout, 0, stream)
+ * (both contractions in the same order on v_mfma_f32_32x32x16_bf16, the hidden rounded to bf16 by the same helpers); h16 is never
+ * written.  Every workgroup is independent (no counters, no flags).  Nothing outside columns [0, cout) of rows [0, R) of either
+ * output is written, nothing outside [0, cin) / [0, cout) of a row of x / res or outside a1 / c1 [0, hid), a2 / c2 [0, cout) is read.
+ * Envelope, otherwise GKG_ERR_UNSUPPORTED with nothing launched (the caller keeps the two launches): R >= 1, cin % 8 == hid % 8 ==
+ * cout % 8 == 0, cin <= 192, cout <= 192 (any hid; cin != cout allowed), and gkg_linear_bf16's pitch multiples and 16-byte
+ * alignment.  A null pointer is GKG_ERR_NULL, a pitch below its row's width GKG_ERR_SHAPE.  gkg_ffn_bf16_supported: 1 when the
+ * sizes pass (pure host code; pitches and pointers are the call's to check). */
+int gkg_ffn_bf16_supported(int R, int cin, int hid, int cout, int has_res, int want_f32, int want_bf16, int act);
+int gkg_ffn_bf16(const void* x /* bf16 (R, ldx) */, int ldx,
+                 const void* w1planes, const float* a1 /* [hid] or NULL = 1 */, const float* c1 /* [hid] */,
+                 const void* w2planes, const float* a2 /* [cout] or NULL = 1 */, const float* c2 /* [cout] */,
+                 const float* res /* fp32 (R, ldr) or NULL */, int ldr,
+                 float* out_f32 /* (R, ldo32) or NULL */, int ldo32,
+                 void* out_bf16 /* (R, ldo16) or NULL */, int ldo16,
+                 int R, int cin, int hid, int cout, int act /* on the hidden: 0 none, 1 GELU */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Training under bf16 autocast (opt-in GKG_ENABLE=train_bf16): the three products of a dense 1x1 projection on bf16 operands with

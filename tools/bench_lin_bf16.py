@@ -22,6 +22,14 @@ The k-NN call is part of both sides because the library has no entry point that 
 fc1_prep_us time the two projection launches without it (their difference is what the last-arriver tail costs, the pair's
 difference what the removed launch saves on top).  Same alternation, hipGraph replays and cache sweep as above.
 
+--ffn cfg3|cfg5: an FFN's two projections as ONE launch with the hidden kept on chip (gkg_ffn_bf16, GKG_ENABLE=lin_bf16,ffn_bf16) at
+every FFN shape (C -> 4C -> C, residual, fp32 + bf16 out) of GKGNet-576 (cfg3, B 32) or pvig_m at 768 x 768 (cfg5, B 16):
+
+    fused   gkg_ffn_bf16
+    pair    gkg_linear_bf16 (GELU, bf16 hidden out), then gkg_linear_bf16 (residual, both outputs) — the same bits
+
+Same alternation, hipGraph replays and cache sweep; shapes outside the fused kernel's envelope report the pair alone.
+
 --train: the three products of a dense layer under bf16 autocast WITH gradients (GKG_ENABLE=train_bf16) at the four dense layers of
 the four stage shapes of the cfg4 training step (GKGNet-576, B 32), each against what it replaces in ``fused._LinearBNAct``:
 
@@ -142,6 +150,73 @@ def prep_leg(args, lib, flush):
     return rows
 
 
+def _frag(w16):
+    """bf16 weight (cout, cin) -> the fragment array [ci_pad/8][co_pad][8] of gkg_linear_bf16."""
+    co, ci = w16.shape
+    W = torch.zeros((co + 31) // 32 * 32, (ci + 15) // 16 * 16, device=w16.device, dtype=BF16)
+    W[:co, :ci] = w16
+    return W.view(W.shape[0], W.shape[1] // 8, 8).permute(1, 0, 2).contiguous()
+
+
+def ffn_leg(args, lib, flush):
+    cfg = PREP_CONFIGS[args.ffn]
+    B = args.batch or cfg["batch"]
+    rows = []
+    for C, side, _ in cfg["stages"]:
+        R, H = B * side * side, 4 * C
+        gen = torch.Generator(device="cuda").manual_seed(C)
+        x = torch.randn(R, C, device="cuda", generator=gen).to(BF16)
+        p1 = _frag((torch.randn(H, C, device="cuda", generator=gen) / C ** 0.5).to(BF16))
+        p2 = _frag((torch.randn(C, H, device="cuda", generator=gen) / H ** 0.5).to(BF16))
+        a1, c1 = torch.rand(H, device="cuda", generator=gen) + 0.5, torch.randn(H, device="cuda", generator=gen) * 0.2
+        a2, c2 = torch.rand(C, device="cuda", generator=gen) + 0.5, torch.randn(C, device="cuda", generator=gen) * 0.2
+        res = torch.randn(R, C, device="cuda", generator=gen)
+        h16 = torch.empty(R, H, device="cuda", dtype=BF16)
+        o32, o16 = torch.empty(R, C, device="cuda"), torch.empty(R, C, device="cuda", dtype=BF16)
+        f32, f16 = torch.empty(R, C, device="cuda"), torch.empty(R, C, device="cuda", dtype=BF16)
+
+        def pair():
+            _lib.check(lib.gkg_linear_bf16(_ptr(x), C, _ptr(p1), _ptr(a1), _ptr(c1), None, 0, None, 0, _ptr(h16), H, R, C, H, 1,
+                                           _stream()), "gkg_linear_bf16")
+            _lib.check(lib.gkg_linear_bf16(_ptr(h16), H, _ptr(p2), _ptr(a2), _ptr(c2), _ptr(res), C, _ptr(o32), C, _ptr(o16), C, R, H, C,
+                                           0, _stream()), "gkg_linear_bf16")
+
+        def fused():
+            _lib.check(lib.gkg_ffn_bf16(_ptr(x), C, _ptr(p1), _ptr(a1), _ptr(c1), _ptr(p2), _ptr(a2), _ptr(c2), _ptr(res), C, _ptr(f32), C,
+                                        _ptr(f16), C, R, C, H, C, 1, _stream()), "gkg_ffn_bf16")
+        # algorithmic bytes: x, both weights, residual, both outputs; the pair moves the hidden twice on top
+        ab = R * C * 2 + 2 * C * H * 2 + R * C * (4 + 4 + 2)
+        row = dict(config=args.ffn, C=C, hid=H, B=B, R=R, algorithmic_bytes=ab, pair_bytes_ratio=round((ab + 2 * R * H * 2) / ab, 2))
+        gp = capture(pair)
+        if not lib.gkg_ffn_bf16_supported(R, C, H, C, 1, 1, 1, 1):
+            tp = [1e3 * replay_ms(gp, flush) for _ in range(args.reps)]
+            row.update(pair_us=round(statistics.median(tp), 1), pair_us_min=round(min(tp), 1), pair_us_max=round(max(tp), 1),
+                       fused_us=None, winner="pair (fused: outside the envelope)")
+            rows.append(row)
+            print(f"{args.ffn} C={C:4d} hid={H:5d} R={R:7d}: pair {row['pair_us']:8.1f} us [{min(tp):.1f}, {max(tp):.1f}]  "
+                  f"fused: outside the envelope", flush=True)
+            continue
+        fused()
+        torch.cuda.synchronize()
+        assert torch.equal(f32, o32) and torch.equal(f16, o16)                   # a sanity check of the comparison, not a test
+        gf = capture(fused)
+        tp, tf = [], []
+        for _ in range(args.reps):                                               # alternate the legs
+            tp.append(1e3 * replay_ms(gp, flush))
+            tf.append(1e3 * replay_ms(gf, flush))
+        up, uf = statistics.median(tp), statistics.median(tf)
+        flop = 4.0 * R * C * H
+        row.update(pair_us=round(up, 1), pair_us_min=round(min(tp), 1), pair_us_max=round(max(tp), 1), fused_us=round(uf, 1),
+                   fused_us_min=round(min(tf), 1), fused_us_max=round(max(tf), 1), fused_tflops=round(flop / uf * 1e-6, 1),
+                   pair_tflops=round(flop / up * 1e-6, 1), fused_GBps=round(ab / uf * 1e-3, 0), winner="fused" if uf < up else "pair")
+        rows.append(row)
+        print(f"{args.ffn} C={C:4d} hid={H:5d} R={R:7d}: pair {up:8.1f} us [{min(tp):.1f}, {max(tp):.1f}]  "
+              f"fused {uf:8.1f} us [{min(tf):.1f}, {max(tf):.1f}] ({row['fused_tflops']:.1f} TFLOP/s, {row['fused_GBps']:.0f} GB/s)"
+              f"  -> {row['winner']}", flush=True)
+        del x, res, h16, o32, o16, f32, f16, gp, gf
+    return rows
+
+
 def train_leg(args, lib, flush):
     from gkgnet_amd import derived, fused
     B = args.batch or 32
@@ -214,6 +289,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--train", action="store_true", help="run the three training products (GKG_ENABLE=train_bf16) at the cfg4 shapes")
     ap.add_argument("--prep", default=None, choices=sorted(PREP_CONFIGS), help="run the fc1 + k-NN preparation leg at this config's shapes")
+    ap.add_argument("--ffn", default=None, choices=sorted(PREP_CONFIGS), help="run the fused FFN launch against the two-launch pair at this config's shapes")
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--batch", type=int, default=None, help="default: 32 (cfg3), 16 (--prep cfg5)")
@@ -230,6 +306,14 @@ def main():
             with open(args.out, "w") as fh:
                 json.dump(dict(tool="bench_lin_bf16 --train", batch=args.batch or 32, reps=args.reps,
                                device=torch.cuda.get_device_name(0), rows=rows), fh, indent=1)
+        return
+    if args.ffn:
+        rows = ffn_leg(args, lib, flush)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as fh:
+                json.dump(dict(tool="bench_lin_bf16 --ffn", config=args.ffn, reps=args.reps, device=torch.cuda.get_device_name(0),
+                               rows=rows), fh, indent=1)
         return
     if args.prep:
         rows = prep_leg(args, lib, flush)
