@@ -76,6 +76,13 @@ DETERMINISTIC = os.environ.get("GKG_DETERMINISTIC", "0") != "0"
 #                  (T, 4C) bf16 hidden matrix in LDS instead of writing it and reading it back (gkg_ffn_bf16; linear_bf16.py).
 #                  Same bits as lin_bf16 alone.  C <= 192 (the stages with the most rows); wider FFNs, an active DropPath, NCHW
 #                  input and the label branch keep the two launches.  Opt-in: per-shape measurements in EXPERIMENTS.md.
+#   mr_fc2_bf16    with lin_bf16 only (and mr_gemm not disabled): the second half of a Grapher on the channels-last chain — aggregation +
+#                  grouped projection + BN + GELU, then fc2 + BN + residual — as ONE launch that keeps the (T, 2C) bf16 matrix
+#                  between the two projections in LDS instead of writing it and reading it back (gkg_mr_fc2_bf16; linear_bf16.py).
+#                  Same bits as lin_bf16 alone.  C <= 192 (the stages with the most rows); wider Graphers, an active DropPath, NCHW
+#                  input and the label branch keep the two launches.  Taken only at the shapes where it measured at least as fast
+#                  as the two launches (linear_bf16.mr_fc2_pays); mr_fc2_bf16_all takes it wherever the library accepts the shape
+#                  (tests, measurements).
 #   train_bf16     training under bf16 autocast: the three products of a dense projection of a Grapher / FFN block (_LinearBNAct under
 #                  autocast: Y = x W^T, dx = dY W (+ the skip gradient), dW = dY^T x) run on the library's own bf16 kernels — bf16
 #                  operands rounded from the fp32 tensors on their way into LDS, fp32 accumulation (gkg_linear_bf16_f32a,
@@ -104,6 +111,8 @@ LIN_BF16 = "lin_bf16" in _ENABLED          # a module constant the tests flip (l
 # likewise (False | True: the measured shapes | "all": every supported shape); acts only together with LIN_BF16
 LIN_BF16_PREP = "all" if "lin_bf16_prep_all" in _ENABLED else ("lin_bf16_prep" in _ENABLED)
 FFN_BF16 = "ffn_bf16" in _ENABLED          # likewise; acts only together with LIN_BF16
+# likewise (False | True: the measured shapes | "all": every supported shape); acts only together with LIN_BF16 and MR_GEMM
+MR_FC2_BF16 = "all" if "mr_fc2_bf16_all" in _ENABLED else ("mr_fc2_bf16" in _ENABLED)
 TRAIN_BF16 = "train_bf16" in _ENABLED      # likewise a module constant the tests flip
 
 
@@ -390,6 +399,7 @@ def _mm_t(x, W, W16=None):
 from .linear_bf16 import (lin_bf16_ok, linear_bf16_eval,      # noqa: E402,F401  (GKG_ENABLE=lin_bf16: linear_bf16.py)
                           lin_bf16_prep_ok, linear_bf16_knn_prep_eval)
 from .linear_bf16 import ffn_bf16_ok, ffn_bf16_eval      # noqa: E402,F401  (GKG_ENABLE=lin_bf16,ffn_bf16)
+from .linear_bf16 import mr_fc2_bf16_ok, mr_fc2_bf16_eval      # noqa: E402,F401  (GKG_ENABLE=lin_bf16,mr_fc2_bf16)
 from .linear_bf16 import (train_bf16_ok, linear_bf16_train_fwd,      # noqa: E402,F401  (GKG_ENABLE=train_bf16)
                           linear_bf16_dgrad, linear_bf16_wgrad)
 from .layout import _tm_dtype, _TokenMajorToCL, _ToTokenMajor, _BlockEntry, _AvgPoolTM      # noqa: E402  (layout Functions: layout.py)
@@ -1476,12 +1486,18 @@ def _graph_and_project(x1b, yb, relative_pos, gc, groups, C, lp, want_edge):
         XM, edge = _KnnMaxRelativeTM.apply(x1b, yb, relative_pos, gc.k, gc.d, groups, want_edge)
         a2 = _GroupedLinearBNAct.apply(XM, nn_[0].weight, nn_[0].bias, nn_[1].weight, nn_[1].bias, nn_[1], 1, False, None)
         return a2, (edge if want_edge else None)
-    M = N if yb is None else yb.shape[1]
+    nn_idx, edge = _graph_lists(x1b, yb, relative_pos, gc, groups, want_edge)
+    return _aggregate_project(x1b, yb, nn_idx, groups, nn_, C, lp), edge       # row g1: aggregation = the projection's operand producer
+
+
+def _graph_lists(x1b, yb, relative_pos, gc, groups, want_edge):
+    """The k-NN call of a block whose graph and aggregation are separate launches -> (neighbour lists (B G, N, k), edge_index | None):
+    the compact u16 lists where nobody asked for the graph, else the int64 edge_index and its neighbour plane."""
+    M = x1b.shape[1] if yb is None else yb.shape[1]
     if KNN_COMPACT and not want_edge and M <= 65536 and knn_graph_tm is _KNN_GRAPH_TM:
-        nn16 = knn_graph_tm16(x1b, yb, relative_pos, gc.k, gc.d, groups)        # u16 lists: no int64 edge_index, no centre plane
-        return _aggregate_project(x1b, yb, nn16, groups, nn_, C, lp), None
+        return knn_graph_tm16(x1b, yb, relative_pos, gc.k, gc.d, groups), None  # u16 lists: no int64 edge_index, no centre plane
     edge = knn_graph_tm(x1b, yb, relative_pos, gc.k, gc.d, groups)
-    return _aggregate_project(x1b, yb, edge[0], groups, nn_, C, lp), edge      # row g1: aggregation = the projection's operand producer
+    return edge[0], edge
 
 
 # fc1's output written straight into the grouped projection's operand buffer (see _LinearBNAct.forward ``xm``): fp32 blocks
@@ -1528,6 +1544,17 @@ def grapher_forward(mod, x, relative_pos, groups: int, want_edge: bool = True):
     yb = None
     if gc.r > 1:                                                    # pooled keys (torch_vertex.py:194-196)
         yb = _AvgPoolTM.apply(x1b, H, W, gc.r)
+    if cl and lp and LIN_BF16 and MR_FC2_BF16:
+        # bf16 inference on the channels-last chain, opt-in: the graph, then aggregation + grouped projection + fc2 in ONE launch where
+        # the predicate takes it (the (T, 2C) matrix stays on chip: the pair's bits), else the two launches as below
+        nn_idx, edge = _graph_lists(x1b, yb, relative_pos, gc, groups, want_edge)
+        if mr_fc2_bf16_ok(MR_FC2_BF16, lp, x1b, yb, nn_idx, groups, gc.gconv.nn, mod.fc2, x, scale, True):
+            out, o16 = mr_fc2_bf16_eval(x1b, yb, nn_idx, groups, gc.gconv.nn, mod.fc2, x, want_f32=True, want_bf16=True)
+            out._gkg_bf16_tm = o16
+        else:
+            a2 = _aggregate_project(x1b, yb, nn_idx, groups, gc.gconv.nn, C, lp)
+            out = _lin(a2, mod.fc2, residual=x, scale=scale, rows_per_scale=N, want16=lp, chain=True)
+        return _cl_out(out, B, H, W), edge
     a2, edge = _graph_and_project(x1b, yb, relative_pos, gc, groups, C, lp, want_edge)
     if cl:                                                          # fc2 + BN (+ DropPath) + residual, token-major = channels-last
         out = _lin(a2, mod.fc2, residual=x, scale=scale, rows_per_scale=N, want16=lp, chain=True)

@@ -1,9 +1,10 @@
 """bf16 inference: a dense 1x1 projection with its eval-mode BN (+ GELU) (+ residual) as ONE launch of the library's own kernel
 (gkg_linear_bf16, csrc/gkg_linear_bf16.hip) — the call (the weight's fragment array: derived.lin_planes) and the predicate ``fused._lin`` asks before
 it dispatches here — and the same launch with the k-NN's token preparation riding on it (gkg_linear_bf16_knn_prep: a Grapher's
-fc1) — and an FFN's two projections as one launch with the hidden matrix kept on chip (gkg_ffn_bf16, csrc/gkg_ffn_bf16.hip).  Also the training side (GKG_ENABLE=train_bf16): the same kernel reading an fp32 A operand for a layer's forward and input
+fc1) — and an FFN's two projections as one launch with the hidden matrix kept on chip (gkg_ffn_bf16, csrc/gkg_ffn_bf16.hip) — and a Grapher's aggregation, grouped projection and fc2 as one launch
+(gkg_mr_fc2_bf16, csrc/gkg_mr_fc2_bf16.hip).  Also the training side (GKG_ENABLE=train_bf16): the same kernel reading an fp32 A operand for a layer's forward and input
 gradient (gkg_linear_bf16_f32a), the bf16 weight-gradient kernel (gkg_linear_wgrad_bf16) and their predicate.  Mechanism only: the
-switches (``fused.LIN_BF16``, ``fused.LIN_BF16_PREP``, ``fused.FFN_BF16``, ``fused.TRAIN_BF16``) and the mode test (``fused.lowp_inference``) stay in
+switches (``fused.LIN_BF16``, ``fused.LIN_BF16_PREP``, ``fused.FFN_BF16``, ``fused.MR_FC2_BF16``, ``fused.TRAIN_BF16``) and the mode test (``fused.lowp_inference``) stay in
 ``fused.py`` and arrive as arguments."""
 from __future__ import annotations
 
@@ -123,6 +124,92 @@ def ffn_bf16_eval(x16, fc1, fc2, residual=None, want_f32=True, want_bf16=False):
                                 _ptr(derived.lin_planes(conv2)), _ptr(a2), _ptr(c2), _ptr(residual),
                                 0 if residual is None else residual.stride(0), _ptr(o32), cout, _ptr(o16), cout, R, cin, hid, cout,
                                 1, _stream()), "gkg_ffn_bf16")
+    return o32, o16
+
+
+# ---- a Grapher's tail as one launch (gkg_mr_fc2_bf16, csrc/gkg_mr_fc2_bf16.hip): aggregation + grouped projection + BN + GELU + fc2 +
+# BN + residual, the (T, 2C) bf16 matrix between the two projections kept on chip ---------------------------------------------------
+# DISPATCH RULE (``mr_fc2_pays``): the fused launch only where it measured at least as fast as the pair it replaces
+# (gkg_mr_linear_bf16_nn16 -> gkg_linear_bf16) beyond the spread of the repeated pair measurements.
+# MI355X, tools/bench_lin_bf16.py --tail, us per Grapher tail over the lists gkg_knn_fwd_tm16 finds for seeded tokens, median of 11
+# alternating replays [min, max], two runs per config on one box (EXPERIMENTS.md "Fused bf16 Grapher tail",
+# profiles/mr_fc2_bf16_layers_*.txt):
+#   cfg3 (GKGNet-576, B 32)   C  80  G 2  k  9  R 663 552   pair 533 [524, 552] / 531   fused 430 [420, 445] / 427   taken
+#                             C 160  G 2  k  9  R 165 888   pair 324 [322, 326] / 328   fused 245 [242, 247] / 247   taken
+#   cfg5 (pvig_m 768^2, B 16) C  96  G 8  k 18  R 589 824   pair 986 [975, 1031] / 994  fused 909 [901, 944] / 915   taken
+#                             C 192  G 8  k 18  R 147 456   pair 454 [448, 460] / 451   fused 380 [379, 381] / 378   taken
+# (C 400 / 640 / 384 / 768, stages 3-4: outside the library's envelope, the two launches.)
+# Every measured class is faster than the pair by more than the pair's two medians differ (2-9 us): the rule keeps all four.  The
+# narrowest margin is cfg5 stage 1 (1.08x: k = 18 keeps the gather at two workgroups per CU); nothing was measured below these row
+# counts, so the rule takes the measured widths' envelope and says nothing about size:
+MR_FC2_MAX_C = 192
+
+
+def mr_fc2_pays(T, C) -> bool:
+    """The measured dispatch rule above: rows and channels of a Grapher."""
+    return C <= MR_FC2_MAX_C
+
+
+def mr_fc2_bf16_ok(on, lp, x, src, nn_idx, G, nn_, fc2, residual, scale, chain, supported=None) -> bool:
+    """Whether ``fused.grapher_forward`` hands the second half of a Grapher — the aggregation over ``nn_idx`` (B G, N, k) of ``x``
+    (B, N, C) fp32 (keys ``src`` (B, M, C) | None), the grouped projection ``nn_`` (conv, bn, GELU) and ``fc2`` (conv, bn) — to
+    mr_fc2_bf16_eval instead of mr_grouped_linear_eval + linear_bf16_eval: the switch (``on`` == "all" —
+    GKG_ENABLE=mr_fc2_bf16_all, tests, measurements — skips the measured rule: every shape the library takes), the conditions of the
+    first launch (``fused._mr_gemm_ok``: bf16 autocast with gradients off, eval-mode BN, groups == 4, ``fused.MR_GEMM``; c % 4 == 0),
+    lin_bf16_ok for fc2 on the (T, 2C) bf16 matrix the launch never makes (the channels-last chain, eval-mode BN, a dense 1x1 conv), no
+    DropPath scale, an fp32 residual of the output's shape (or none) and the library's answer for the sizes
+    (``supported(B, G, c, N, M, k)`` stands in for it in tests)."""
+    if not on or scale is not None or len(x.shape) != 3 or x.dtype != _F32:
+        return False
+    from . import fused
+    B, N, C = x.shape
+    if G <= 0 or C % G or (C // G) % 4 or not fused._mr_gemm_ok(nn_, C, lp):
+        return False
+    if src is not None and (src.dtype != _F32 or len(src.shape) != 3 or src.shape[0] != B or src.shape[2] != C):
+        return False
+    M = N if src is None else src.shape[1]
+    if len(nn_idx.shape) != 3 or tuple(nn_idx.shape[:2]) != (B * G, N) or (nn_idx.dtype == torch.int16 and M > 65536):
+        return False
+    fine = (lambda R, ci, co: True) if supported is not None else None        # the pair's own answer is asked below, once
+    if not lin_bf16_ok(on, lp, _Rows(B * N, 2 * C), fc2[0], fc2[1], chain, scale=scale, supported=fine):
+        return False
+    if fc2[0].weight.shape[0] != C:
+        return False
+    if residual is not None and (residual.dtype != _F32 or tuple(residual.shape) != (B * N, C)):
+        return False
+    if on != "all" and not mr_fc2_pays(B * N, C):
+        return False
+    k = nn_idx.shape[2]
+    if supported is not None:
+        return bool(supported(B, G, C // G, N, M, k))
+    return bool(_lib.load().gkg_mr_fc2_bf16_supported(B, G, C // G, N, M, k, int(residual is not None), 1, 1, 1))
+
+
+@torch.no_grad()
+def mr_fc2_bf16_eval(x, src, nn_idx, G, nn_, fc2, residual=None, want_f32=True, want_bf16=False):
+    """x (B, N, C) fp32, src (B, M, C) fp32 | None, nn_idx (B G, N, k) int64 | int16 (the bits of u16 rows) ->
+    BN2(fc2(bf16(GELU(BN1(BasicConv([x, max_k(src[idx] - x)])))))) (+ residual (B N, C) fp32) as (out_f32 | None, out_bf16 | None): the
+    bits of fused.mr_grouped_linear_eval(x, src, nn_idx, G, *nn_) followed by linear_bf16_eval(h16, *fc2, 0, residual, ...), in one
+    launch that keeps the (B N, 2C) matrix on chip (reference torch_vertex.py:47-62, torch_nn.py:57-69, torch_vertex.py:325-333)."""
+    lib = _lib.load()
+    B, N, C = x.shape
+    M = N if src is None else src.shape[1]
+    (conv1, bn1), (conv2, bn2) = (nn_[0], nn_[1]), (fc2[0], fc2[1])
+    assert x.dtype == _F32 and conv2.weight.shape[1] == 2 * C and conv2.weight.shape[0] == C and (want_f32 or want_bf16)
+    x = x.contiguous()
+    src = None if src is None else src.contiguous()
+    nn_idx = nn_idx.contiguous()
+    if residual is not None:
+        assert residual.dtype == _F32 and tuple(residual.shape) == (B * N, C)
+        residual = _rows(residual, 4)
+    a1, c1 = bn_passes.eval_ac(lib, bn1, conv1.bias, 2 * C)
+    a2, c2 = bn_passes.eval_ac(lib, bn2, conv2.bias, C)
+    o32 = torch.empty((B * N, C), dtype=_F32, device=x.device) if want_f32 else None
+    o16 = torch.empty((B * N, C), dtype=torch.bfloat16, device=x.device) if want_bf16 else None
+    fn = lib.gkg_mr_fc2_bf16_nn16 if nn_idx.dtype == torch.int16 else lib.gkg_mr_fc2_bf16      # compact lists: knn_graph_tm16
+    _lib.check(fn(_ptr(x), _ptr(src), _ptr(nn_idx), _ptr(derived.mr_planes(conv1)), _ptr(a1), _ptr(c1),
+                  _ptr(derived.lin_planes(conv2)), _ptr(a2), _ptr(c2), _ptr(residual), 0 if residual is None else residual.stride(0),
+                  _ptr(o32), C, _ptr(o16), C, B, G, C // G, N, M, nn_idx.shape[2], 1, _stream()), "gkg_mr_fc2_bf16")
     return o32, o16
 
 

@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define GKG_ABI_VERSION 17
+#define GKG_ABI_VERSION 18
 
 /* dtype codes */
 #define GKG_F32 0
@@ -426,6 +426,42 @@ int gkg_ffn_bf16(const void* x /* bf16 (R, ldx) */, int ldx,
                  float* out_f32 /* (R, ldo32) or NULL */, int ldo32,
                  void* out_bf16 /* (R, ldo16) or NULL */, int ldo16,
                  int R, int cin, int hid, int cout, int act /* on the hidden: 0 none, 1 GELU */, void* stream);
+/* The second half of a Grapher (reference torch_vertex.py:47-62 MRConv2d.forward + torch_nn.py:57-69 BasicConv, then
+ * torch_vertex.py:325-333 fc2 + shortcut) under bf16 autocast with gradients off as ONE launch (csrc/gkg_mr_fc2_bf16.hip): gather,
+ * max_k(x_j - x_i), [x, m] interleave, the grouped 1x1 projection (groups = 4) with eval-mode BN and the activation, AND the dense
+ * 2C -> C projection behind it with its eval-mode BN, fp32 residual and both output precisions; the (B N, 2C) bf16 matrix between
+ * the two projections stays on chip.  The arguments are gkg_mr_linear_bf16's operands — x (B, N, C) fp32, src (B, M, C) fp32 or
+ * NULL (self graph, M == N), nn_idx (B*G, N, k) int64 | nn16 (B*G, N, k) u16 (M <= 65536), wplanes (gkg_mr_linear_planes_bytes(C)
+ * bytes), a1 / c1 [2C], act ON THE HIDDEN — followed by gkg_linear_bf16's for the 2C -> C layer: w2planes
+ * (gkg_linear_bf16_planes_bytes(2C, C) bytes), a2 [C] (NULL = 1), c2 [C], res fp32 (B N, ldr) or NULL, out_f32 / ldo32 and
+ * out_bf16 / ldo16 (at least one non-NULL).  Bit for bit, in every form, the outputs of the two launches
+ *   gkg_mr_linear_bf16[_nn16](x, src, idx, wplanes, a1, c1, h16, 2C, B, G, c, N, M, k, act, stream)          h16 (B N, 2C) bf16
+ *   gkg_linear_bf16(h16, 2C, w2planes, a2, c2, res, ldr, out_f32, ldo32, out_bf16, ldo16, B N, 2C, C, 0, stream)
+ * (one definition of the gather, the index clamp — < 0 -> 0, >= M -> M - 1 —, the maximum's tie rule, the GELU and the hidden's
+ * rounding; both contractions on v_mfma_f32_32x32x16_bf16 over ascending steps of 16, no K-split; the second launch's epilogue:
+ * fmaf(a2, acc, c2), + res in fp32, the bf16 output the rounding of the fp32 one); h16 is never written.  Every workgroup is
+ * independent (no counters, no flags, no scratch buffer).  Nothing outside columns [0, C) of rows [0, B N) of either output is
+ * written.  Envelope, otherwise GKG_ERR_UNSUPPORTED with nothing launched (the caller keeps the two launches): C = G c with
+ * C % 16 == 0, c % 4 == 0, C <= 192, k <= 64, index rows that fit the LDS beside the tile (64 G k entries of 2 bytes where
+ * M <= 65536, of 4 beyond; every shape of the models does), _nn16: M <= 65536, gkg_linear_bf16's pitch multiples (ldo16 % 8,
+ * ldo32 % 4, ldr % 4; pitches of absent operands are ignored) and 16-byte alignment of x, src, the fragment arrays, res and the
+ * outputs.  A null required pointer is GKG_ERR_NULL; non-positive sizes, a self graph with M != N and a pitch below its row's width
+ * are GKG_ERR_SHAPE.  gkg_mr_fc2_bf16_supported: 1 when the sizes pass (pure host code; pitches and pointers are the call's to check). */
+int gkg_mr_fc2_bf16_supported(int B, int G, int c, int N, int M, int k, int has_res, int want_f32, int want_bf16, int act);
+int gkg_mr_fc2_bf16(const float* x, const float* src, const int64_t* nn_idx, const void* wplanes,
+                    const float* a1 /* [2C] */, const float* c1 /* [2C] */,
+                    const void* w2planes, const float* a2 /* [C] or NULL = 1 */, const float* c2 /* [C] */,
+                    const float* res /* fp32 (B N, ldr) or NULL */, int ldr,
+                    float* out_f32 /* (B N, ldo32) or NULL */, int ldo32,
+                    void* out_bf16 /* (B N, ldo16) or NULL */, int ldo16,
+                    int B, int G, int c, int N, int M, int k, int act /* on the hidden: 0 none, 1 GELU */, void* stream);
+int gkg_mr_fc2_bf16_nn16(const float* x, const float* src, const uint16_t* nn16, const void* wplanes,
+                         const float* a1 /* [2C] */, const float* c1 /* [2C] */,
+                         const void* w2planes, const float* a2 /* [C] or NULL = 1 */, const float* c2 /* [C] */,
+                         const float* res /* fp32 (B N, ldr) or NULL */, int ldr,
+                         float* out_f32 /* (B N, ldo32) or NULL */, int ldo32,
+                         void* out_bf16 /* (B N, ldo16) or NULL */, int ldo16,
+                         int B, int G, int c, int N, int M, int k, int act /* on the hidden: 0 none, 1 GELU */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Training under bf16 autocast (opt-in GKG_ENABLE=train_bf16): the three products of a dense 1x1 projection on bf16 operands with

@@ -30,6 +30,16 @@ every FFN shape (C -> 4C -> C, residual, fp32 + bf16 out) of GKGNet-576 (cfg3, B
 
 Same alternation, hipGraph replays and cache sweep; shapes outside the fused kernel's envelope report the pair alone.
 
+--tail cfg3|cfg5: the second half of a Grapher as ONE launch with the (T, 2C) matrix kept on chip (gkg_mr_fc2_bf16_nn16,
+GKG_ENABLE=lin_bf16,mr_fc2_bf16) at the stage shapes of GKGNet-576 (cfg3, B 32) or pvig_m at 768 x 768 (cfg5, B 16) inside the kernel's
+envelope (C <= 192), over the neighbour lists gkg_knn_fwd_tm16 finds for seeded tokens and their pooled keys (the gather's locality
+is part of what is measured):
+
+    fused   gkg_mr_fc2_bf16_nn16
+    pair    gkg_mr_linear_bf16_nn16 (bf16 (T, 2C) out), then gkg_linear_bf16 (residual, both outputs) — the same bits
+
+Same alternation, hipGraph replays and cache sweep; shapes outside the envelope report the pair alone.
+
 --train: the three products of a dense layer under bf16 autocast WITH gradients (GKG_ENABLE=train_bf16) at the four dense layers of
 the four stage shapes of the cfg4 training step (GKGNet-576, B 32), each against what it replaces in ``fused._LinearBNAct``:
 
@@ -217,6 +227,85 @@ def ffn_leg(args, lib, flush):
     return rows
 
 
+def tail_leg(args, lib, flush):
+    from gkgnet_amd import derived
+    cfg = PREP_CONFIGS[args.tail]
+    B, G, k, d = (args.batch or cfg["batch"]), cfg["G"], cfg["k"], 1
+    rows = []
+    for C, side, kside in cfg["stages"]:
+        N, M, c, R = side * side, kside * kside, C // G, B * side * side
+        has_y = M != N
+        gen = torch.Generator(device="cuda").manual_seed(C)
+        x = torch.randn(B, N, C, device="cuda", generator=gen)
+        y = None
+        if has_y:                                                                # pooled keys, as the block makes them
+            r = side // kside
+            y = x.view(B, kside, r, kside, r, C).mean(dim=(2, 4)).reshape(B, M, C).contiguous()
+        rp = -torch.rand(N, M, device="cuda", generator=gen)
+        flags = _lib.KNN_NORMALIZE | _lib.KNN_RELPOS_UNIT
+        wsb = int(lib.gkg_knn_workspace_bytes(B * G, c, N, M, k, d, _lib.F32, _lib.KNN_NORMALIZE))
+        ws = torch.empty(wsb, dtype=torch.uint8, device="cuda")
+        nn16 = torch.empty(B * G, N, k, dtype=torch.int16, device="cuda")
+        _lib.check(lib.gkg_knn_fwd_tm16(_ptr(x), 0, 0, _ptr(y), _ptr(rp), _ptr(nn16), B, G, c, N, M, k, d, _lib.F32, flags, _ptr(ws), wsb,
+                                        _stream()), "gkg_knn_fwd_tm16")
+        torch.cuda.synchronize()
+        del ws, rp
+        conv = torch.nn.Conv2d(2 * C, 2 * C, 1, groups=4).cuda()
+        p1 = derived.mr_planes(conv)
+        p2 = _frag((torch.randn(C, 2 * C, device="cuda", generator=gen) / (2 * C) ** 0.5).to(BF16))
+        a1, c1 = torch.rand(2 * C, device="cuda", generator=gen) + 0.5, torch.randn(2 * C, device="cuda", generator=gen) * 0.2
+        a2, c2 = torch.rand(C, device="cuda", generator=gen) + 0.5, torch.randn(C, device="cuda", generator=gen) * 0.2
+        res = torch.randn(R, C, device="cuda", generator=gen)
+        h16 = torch.empty(R, 2 * C, device="cuda", dtype=BF16)
+        o32, o16 = torch.empty(R, C, device="cuda"), torch.empty(R, C, device="cuda", dtype=BF16)
+        f32, f16 = torch.empty(R, C, device="cuda"), torch.empty(R, C, device="cuda", dtype=BF16)
+
+        def pair():
+            _lib.check(lib.gkg_mr_linear_bf16_nn16(_ptr(x), _ptr(y), _ptr(nn16), _ptr(p1), _ptr(a1), _ptr(c1), _ptr(h16), 2 * C, B, G, c,
+                                                   N, M, k, 1, _stream()), "gkg_mr_linear_bf16_nn16")
+            _lib.check(lib.gkg_linear_bf16(_ptr(h16), 2 * C, _ptr(p2), _ptr(a2), _ptr(c2), _ptr(res), C, _ptr(o32), C, _ptr(o16), C, R,
+                                           2 * C, C, 0, _stream()), "gkg_linear_bf16")
+
+        def fused():
+            _lib.check(lib.gkg_mr_fc2_bf16_nn16(_ptr(x), _ptr(y), _ptr(nn16), _ptr(p1), _ptr(a1), _ptr(c1), _ptr(p2), _ptr(a2), _ptr(c2),
+                                                _ptr(res), C, _ptr(f32), C, _ptr(f16), C, B, G, c, N, M, k, 1, _stream()),
+                       "gkg_mr_fc2_bf16_nn16")
+        # algorithmic bytes: tokens, keys, lists, both weights, residual, both outputs (a gathered row counted once: the rest is
+        # cache traffic); the pair moves the (T, 2C) bf16 matrix twice on top
+        ab = R * C * 4 + (B * M * C * 4 if has_y else 0) + B * G * N * k * 2 + C * C * 2 + 2 * C * C * 2 + R * C * (4 + 4 + 2)
+        row = dict(config=args.tail, C=C, B=B, G=G, c=c, N=N, M=M, k=k, R=R, algorithmic_bytes=ab,
+                   pair_bytes_ratio=round((ab + 2 * R * 2 * C * 2) / ab, 2), fused_bytes_ratio=1.0)
+        if not lib.gkg_mr_fc2_bf16_supported(B, G, c, N, M, k, 1, 1, 1, 1):
+            gp = capture(pair)
+            tp = [1e3 * replay_ms(gp, flush) for _ in range(args.reps)]
+            row.update(pair_us=round(statistics.median(tp), 1), pair_us_min=round(min(tp), 1), pair_us_max=round(max(tp), 1),
+                       fused_us=None, winner="pair (fused: outside the envelope)")
+            rows.append(row)
+            print(f"{args.tail} C={C:4d} N={N:6d} M={M:5d} R={R:7d}: pair {row['pair_us']:8.1f} us [{min(tp):.1f}, {max(tp):.1f}]  "
+                  f"fused: outside the envelope", flush=True)
+            del x, y, res, h16, o32, o16, f32, f16, gp
+            continue
+        pair()
+        fused()
+        torch.cuda.synchronize()
+        assert torch.equal(f32, o32) and torch.equal(f16, o16)                   # a sanity check of the comparison, not a test
+        gp, gf = capture(pair), capture(fused)
+        tp, tf = [], []
+        for _ in range(args.reps):                                               # alternate the legs
+            tp.append(1e3 * replay_ms(gp, flush))
+            tf.append(1e3 * replay_ms(gf, flush))
+        up, uf = statistics.median(tp), statistics.median(tf)
+        row.update(pair_us=round(up, 1), pair_us_min=round(min(tp), 1), pair_us_max=round(max(tp), 1), fused_us=round(uf, 1),
+                   fused_us_min=round(min(tf), 1), fused_us_max=round(max(tf), 1), fused_GBps=round(ab / uf * 1e-3, 0),
+                   pair_GBps=round(ab / up * 1e-3, 0), winner="fused" if uf < up else "pair")
+        rows.append(row)
+        print(f"{args.tail} C={C:4d} N={N:6d} M={M:5d} R={R:7d}: pair {up:8.1f} us [{min(tp):.1f}, {max(tp):.1f}] (bytes x{row['pair_bytes_ratio']})  "
+              f"fused {uf:8.1f} us [{min(tf):.1f}, {max(tf):.1f}] ({row['fused_GBps']:.0f} GB/s of algorithmic bytes)  -> {row['winner']}",
+              flush=True)
+        del x, y, res, h16, o32, o16, f32, f16, gp, gf
+    return rows
+
+
 def train_leg(args, lib, flush):
     from gkgnet_amd import derived, fused
     B = args.batch or 32
@@ -290,6 +379,7 @@ def main():
     ap.add_argument("--train", action="store_true", help="run the three training products (GKG_ENABLE=train_bf16) at the cfg4 shapes")
     ap.add_argument("--prep", default=None, choices=sorted(PREP_CONFIGS), help="run the fc1 + k-NN preparation leg at this config's shapes")
     ap.add_argument("--ffn", default=None, choices=sorted(PREP_CONFIGS), help="run the fused FFN launch against the two-launch pair at this config's shapes")
+    ap.add_argument("--tail", default=None, choices=sorted(PREP_CONFIGS), help="run the fused Grapher tail (aggregation + grouped projection + fc2) against the two-launch pair at this config's shapes")
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--batch", type=int, default=None, help="default: 32 (cfg3), 16 (--prep cfg5)")
@@ -313,6 +403,14 @@ def main():
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             with open(args.out, "w") as fh:
                 json.dump(dict(tool="bench_lin_bf16 --ffn", config=args.ffn, reps=args.reps, device=torch.cuda.get_device_name(0),
+                               rows=rows), fh, indent=1)
+        return
+    if args.tail:
+        rows = tail_leg(args, lib, flush)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as fh:
+                json.dump(dict(tool="bench_lin_bf16 --tail", config=args.tail, reps=args.reps, device=torch.cuda.get_device_name(0),
                                rows=rows), fh, indent=1)
         return
     if args.prep:
