@@ -50,10 +50,19 @@ extern "C" {
 
 /* gkg_knn_fwd flags */
 #define GKG_KNN_NORMALIZE 1u /* L2-normalise tokens over the group's channels first (torch_edge.py:167-173) */
-#define GKG_KNN_BF16_CONTRACT 2u /* x.y^T on the bf16 matrix cores: tokens rounded to bf16 after normalisation, exact
-                                  * products, fp32 accumulation and fp32 norms.  For callers under bf16 autocast, where the
-                                  * reference computes this product in bf16 and rounds it to bf16.  Outside the bit-exact
-                                  * index contract; ignored for c < 9. */
+#define GKG_KNN_BF16_CONTRACT 2u /* x.y^T on the bf16 matrix cores.  For callers under bf16 autocast, where the reference computes
+                                  * this product in bf16 and rounds it to bf16.  Token preparation is the contract's (s, den, th, sq
+                                  * above; sq from the UNROUNDED fp32 th); the distance is
+                                  *     dist = ( relpos[n][m] + sum_ch (-2 bf(xh[ch][n])) * bf(yh[ch][m]) ) + sqy[m]
+                                  * bf = bf16 round-to-nearest-even of the fp32 th; the products are exact, the accumulator is fp32
+                                  * and STARTS at relpos[n][m] (0 without a bias), sqy[m] is added last in fp32; the query's own
+                                  * |x|^2 (one constant per query: no effect on the order) is left out.  Only the order of the c
+                                  * additions inside the 16-deep matrix-core steps is the hardware's, so a distance lies within
+                                  * (c + 2) 2^-24 (max|relpos| + 3.1) of its real value for normalised tokens
+                                  * (tests/knn_bf16_ref.py).  Neighbour rule as above (ties: smaller key index first).  Outside the
+                                  * bit-exact index contract; ignored for c < 9 (the call is then the fp32 contract).  Not with
+                                  * GKG_KNN_X_PREPARED / GKG_KNN_Y_PREPARED or as knn_flags of a preparing producer
+                                  * (GKG_ERR_UNSUPPORTED). */
 #define GKG_KNN_SELECT_DIRECT 4u   /* force the direct sorted insert / the buffered selection of the tile kernel instead of */
 #define GKG_KNN_SELECT_BUFFERED 8u /* the library's per-shape rule (measurement, tests): identical results either way */
 #define GKG_KNN_NO_PREFILTER 16u   /* evaluate every distance with the contract's fp32 chain (knn_tile_kernel) instead of the

@@ -27,7 +27,7 @@ def lib():
     global _LIB
     if _LIB is None:
         _LIB = C.CDLL(build())
-        for fn in ("oracle_knn_fwd", "oracle_mr_fwd", "oracle_mr_bwd"):
+        for fn in ("oracle_knn_fwd", "oracle_mr_fwd", "oracle_mr_bwd", "oracle_token_prep"):
             getattr(_LIB, fn).restype = C.c_int
     return _LIB
 
@@ -56,6 +56,19 @@ def knn(x, y=None, relpos=None, k=9, dilation=1, normalize=True, want_dist=False
     if rc != 0:
         raise ValueError(f"oracle_knn_fwd failed: {rc}")
     return (idx, center, dist) if want_dist else (idx, center)
+
+
+def token_prep(x, normalize=True):
+    """x (BG,c,T) -> th (BG,c,T), sq (BG,T): the contract's token preparation (normalised copy, its squared norm)."""
+    x = _f32(x)
+    BG, c, T = x.shape
+    th = np.empty((BG, c, T), np.float32)
+    sq = np.empty((BG, T), np.float32)
+    rc = lib().oracle_token_prep(_p(x, C.c_float), _p(th, C.c_float), _p(sq, C.c_float), BG, c, T,
+                                 C.c_uint(NORMALIZE if normalize else 0))
+    if rc != 0:
+        raise ValueError(f"oracle_token_prep failed: {rc}")
+    return th, sq
 
 
 def mr_fwd(x, src, nn_idx):

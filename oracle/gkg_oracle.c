@@ -45,6 +45,16 @@ static void token_prep(const float* t, float* th, float* sq, int c, int T, unsig
   }
 }
 
+/* token_prep for every problem of t (BG,c,T): th (BG,c,T), sq (BG,T).  The reference of the bf16-contraction k-NN
+   (tests/knn_bf16_ref.py) starts from these values.  Returns 0 on success, negative on bad arguments. */
+int oracle_token_prep(const float* t, float* th, float* sq, int BG, int c, int T, unsigned flags) {
+  if (!t || !th || !sq) return -1;
+  if (BG <= 0 || c <= 0 || T <= 0) return -2;
+  for (int bg = 0; bg < BG; ++bg)
+    token_prep(t + (size_t)bg * c * T, th + (size_t)bg * c * T, sq + (size_t)bg * T, c, T, flags);
+  return 0;
+}
+
 /* Full distance row for query n of one (bg) problem. */
 static void dist_row(const float* xh, const float* yh, const float* sqx, const float* sqy,
                      const float* relpos, int c, int N, int M, int n, float* out) {
