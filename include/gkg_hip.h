@@ -131,6 +131,12 @@ int gkg_mr_fwd(const void* x, const void* src, const int64_t* nn_idx, void* m_ou
  *     gsrc[bg][ch][nn_idx[bg][n][argmax]] +=  g[bg][ch][n]
  *   gsrc == NULL  -> self graph: both terms are accumulated into gx (M must equal N).
  *   gx, gsrc are fully overwritten (no pre-zeroing needed).
+ * The destination row is clamped exactly as the forward clamps its gathers: the slot as min(argmax, k - 1), then the entry it
+ * names on its full 64-bit value (< 0 -> 0, >= M -> M - 1) — never an out-of-bounds access, whatever argmax and nn_idx hold.
+ * The fan-in of a row is summed with fp32 atomics (in LDS; in global memory when one row of M accumulators exceeds the LDS
+ * budget — fp32 tensors only there, GKG_ERR_UNSUPPORTED for bf16 / fp16): any summation order, so the last bits may differ
+ * from run to run; |error| <= fan_in * 2^-24 * sum|addend| to first order (the self graph's -g counts as one addend), and a
+ * bf16 / fp16 result is that fp32 sum rounded once.  Gradients whose partial sums are all exact in fp32 give the exact result.
  */
 int gkg_mr_bwd(const void* g, const int64_t* nn_idx, const uint8_t* argmax, void* gx, void* gsrc,
                int BG, int c, int N, int M, int k, int dtype, void* stream);
@@ -223,6 +229,22 @@ int gkg_gat_bwd(const float* g, const float* x, const float* src, const int64_t*
  *                    the exact two-sweep form.  Still order-independent and bit-identical from run to run.
  *                    flags & GKG_MR_FP32_ATOMICS: the round-1 fp32 LDS-atomic kernels (fan-in summed in arrival order);
  *                    flags & GKG_MR_DETERMINISTIC (shapes beyond the LDS budget): private accumulators, fixed order.
+ *                    Destination rows: arg_kind 0 — the slot is clamped to min(argmax, k - 1) and the nn_idx entry it names on
+ *                    its full 64-bit value (< 0 -> 0, >= M -> M - 1); arg_kind 1 — min(row, M - 1), nn_idx is not read and may
+ *                    be NULL.  Every form clamps: no out-of-bounds access, whatever argmax and nn_idx hold.
+ *                    gx = direct - g in fp32 (direct = 0 in mode 0); the self graph adds it to the row's sum as one more fp32
+ *                    operation.  Order-independent (the same bits from run to run, whatever the order the lanes arrive in):
+ *                    the fixed-point forms (two-sweep and streaming).  Fixed order, also the same bits from run to run: the
+ *                    private-accumulator form and the ordered walk of GKG_MR_DETERMINISTIC (fp32 additions in query order).
+ *                    Arrival order: the fp32-atomic forms — LDS images of more than 512 rows under fewer than 160 query rows,
+ *                    images beyond the LDS budget (global atomics), GKG_MR_FP32_ATOMICS, and the chunk of a fixed-point
+ *                    workgroup that meets an inf / NaN; there |error| <= fan_in * 2^-24 * sum|addend| to first order.
+ *                    Exactness of the fixed-point forms: a row's sum is float32(the exact sum), rounded once, whenever no
+ *                    addend loses bits and the integer total passes through a double unrounded, i.e. when every |g| of the
+ *                    (image, channel chunk) lies within a factor 2^(SHMAX - 6) of the chunk's largest (SHMAX = 38 - bits(N); the
+ *                    6 is the streaming form's headroom, the two-sweep form needs none) and 24 + s + bits(N) <= 53 for gradients
+ *                    spread over s binary orders: e.g. any gradients spread over up to 8 binary orders, subnormal ones included,
+ *                    at N <= 4095.  Smaller addends are truncated toward zero below 2^-SHMAX of the scale.
  *
  * XM layout (round 6) — the reference's MRConv2d interleaves [x_0, m_0, x_1, m_1, ...] (torch_vertex.py:57-61) and feeds
  * Conv2d(2C, 2C, 1, groups=4) (torch_nn.py:61): conv group q reads interleaved channels [q C/2, (q+1) C/2) = the x and m values
