@@ -28,6 +28,7 @@ KNN_FORCE_PREFILTER = _K["KNN_FORCE_PREFILTER"]
 KNN_RELPOS_UNIT = _K["KNN_RELPOS_UNIT"]
 KNN_X_PREPARED = _K["KNN_X_PREPARED"]
 KNN_Y_PREPARED = _K["KNN_Y_PREPARED"]
+KNN_F16_CONTRACT = _K["KNN_F16_CONTRACT"]
 MR_DETERMINISTIC, MR_FP32_ATOMICS = _K["MR_DETERMINISTIC"], _K["MR_FP32_ATOMICS"]
 X6_NO_KS, X6_FORCE_KS = _K["X6_NO_KS"], _K["X6_FORCE_KS"]
 X6_NO_WALK, X6_FORCE_WALK, X6_WALK_CAP_SHIFT = _K["X6_NO_WALK"], _K["X6_FORCE_WALK"], _K["X6_WALK_CAP_SHIFT"]

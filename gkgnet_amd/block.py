@@ -123,7 +123,7 @@ _PLANS = weakref.WeakKeyDictionary()           # module -> {(shape key, switches
 
 def _switches():
     return (ENABLED, fused.ENABLED, fused.GEMM_MATH, fused.DETERMINISTIC, fused.XM_DIRECT, fused.KNN_MR, fused.KNN_COMPACT,
-            fused.KNN_PREP, fused.KNN_BF16, fused.BN_EPILOGUE_MIN_ROWS, fused.knn_graph_tm is fused._KNN_GRAPH_TM)
+            fused.KNN_PREP, fused.KNN_BF16, fused.KNN_F16, fused.BN_EPILOGUE_MIN_ROWS, fused.knn_graph_tm is fused._KNN_GRAPH_TM)
 
 
 class _Proj:

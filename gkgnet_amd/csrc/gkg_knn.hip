@@ -32,9 +32,10 @@
 namespace gkg {
 
 // ------------------------------------------------------------------------------------------ prep (bodies: gkg_knn_prep.h)
-template <typename T, bool NORM, int PT>
+// HF: the octet-major planes (PrepSet::tb) hold fp16 (GKG_KNN_F16_CONTRACT) instead of bf16
+template <typename T, bool NORM, int PT, bool HF = false>
 __global__ __launch_bounds__(PT) void token_prep_kernel(PrepSet s1, PrepSet s2, int nbx1, int c, int cpad) {
-  token_prep_body<T, NORM, PT, false>(s1, s2, nbx1, c, cpad, BnDerive{}, nullptr, nullptr);
+  token_prep_body<T, NORM, PT, false, HF>(s1, s2, nbx1, c, cpad, BnDerive{}, nullptr, nullptr);
 }
 // The same pass as a projection's BN-apply (PrepSet::raw): what a trace shows for the Grapher's fc1 / the label block's fc1 / the
 // Grapher's fc2 in front of a label block — one launch = BN-apply (+ residual, + both layouts) + the k-NN's token preparation
@@ -195,7 +196,8 @@ extern "C" size_t gkg_knn_workspace_bytes(int BG, int c, int N, int M, int k, in
 struct PrepAffine { BnDerive d; const float* a; const float* c; };
 
 template <typename T, int PT>
-static void launch_prep_pt(const PrepSet& s1, const PrepSet* s2, int BG, int c, int cpad, bool norm, hipStream_t st, const PrepAffine& pa) {
+static void launch_prep_pt(const PrepSet& s1, const PrepSet* s2, int BG, int c, int cpad, bool norm, hipStream_t st, const PrepAffine& pa,
+                           bool hf) {
   const int nbx1 = ((s1.tb_lo ? s1.rows : s1.Tn) + PT - 1) / PT;
   const int nbx2 = s2 ? ((s2->tb_lo ? s2->rows : s2->Tn) + PT - 1) / PT : 0;
   dim3 grid(nbx1 + nbx2, BG);
@@ -206,6 +208,10 @@ static void launch_prep_pt(const PrepSet& s1, const PrepSet* s2, int BG, int c, 
       if (norm) hipLaunchKernelGGL((bn_apply_knn_prep_kernel<true, PT>), grid, dim3(PT), lds, st, s1, c, cpad, pa.d, pa.a, pa.c);
       else hipLaunchKernelGGL((bn_apply_knn_prep_kernel<false, PT>), grid, dim3(PT), lds, st, s1, c, cpad, pa.d, pa.a, pa.c);
     }
+    return;
+  }
+  if (hf) {                                      // fp16 planes: normalised tokens only (knn_fwd_impl)
+    hipLaunchKernelGGL((token_prep_kernel<T, true, PT, true>), grid, dim3(PT), lds, st, s1, second, nbx1, c, cpad);
     return;
   }
   if (norm) hipLaunchKernelGGL((token_prep_kernel<T, true, PT>), grid, dim3(PT), lds, st, s1, second, nbx1, c, cpad);
@@ -234,7 +240,7 @@ static bool prep_coop_ok(const PrepSet& s) {       // fp32 token-major rows of w
 
 template <typename T>
 static hipError_t launch_prep(const PrepSet& s1, const PrepSet* s2, int BG, int c, int cpad, bool norm, hipStream_t st,
-                              const PrepAffine& pa = PrepAffine{}) {
+                              const PrepAffine& pa = PrepAffine{}, bool hf = false) {     // hf: fp16 planes in PrepSet::tb
   GkgProfScope prof(GKG_PROF_TOKEN_PREP, st);
   if (sizeof(T) == 4 && (c & 3) == 0 && prep_coop_ok(s1) && (!s2 || prep_coop_ok(*s2)) &&
       (size_t)(s1.Tn + (s2 ? s2->Tn : 0)) * BG <= 262144) {                          // latency-bound sizes only
@@ -243,9 +249,9 @@ static hipError_t launch_prep(const PrepSet& s1, const PrepSet* s2, int BG, int 
     else launch_prep_coop<16>(s1, s2, BG, c, cpad, norm, st, pa);
     return hipGetLastError();
   }
-  if (c <= 192) launch_prep_pt<T, 64>(s1, s2, BG, c, cpad, norm, st, pa);          // <= 48 KB column block
-  else if (c <= 384) launch_prep_pt<T, 32>(s1, s2, BG, c, cpad, norm, st, pa);
-  else launch_prep_pt<T, 16>(s1, s2, BG, c, cpad, norm, st, pa);                    // c <= 600 (plan limit)
+  if (c <= 192) launch_prep_pt<T, 64>(s1, s2, BG, c, cpad, norm, st, pa, hf);      // <= 48 KB column block
+  else if (c <= 384) launch_prep_pt<T, 32>(s1, s2, BG, c, cpad, norm, st, pa, hf);
+  else launch_prep_pt<T, 16>(s1, s2, BG, c, cpad, norm, st, pa, hf);                // c <= 600 (plan limit)
   return hipGetLastError();
 }
 
@@ -279,6 +285,17 @@ static int knn_fwd_impl(const void* x, const void* y, const float* relpos, int64
   // exactly where the k-NN call with the same arguments + GKG_KNN_X_PREPARED expects them (same plan, same decisions: this IS that
   // call up to its preparation launch); y / relpos / mr are only tested for presence.
   const bool prep_only = prod != nullptr;
+  // fp16 contraction (GKG_KNN_F16_CONTRACT): normalised tokens only (raw ones can overflow fp16), one 16-bit format per call, no
+  // prepared copies, no preparing producer, not the fused k-NN + aggregation.  Rejected on the flag word, before anything else.
+  const bool f16_asked = (flags & GKG_KNN_F16_CONTRACT) != 0;
+  if (f16_asked) {
+    if (probe_only) return GKG_ERR_UNSUPPORTED;
+    if (!(flags & GKG_KNN_NORMALIZE)) return gkg_fail(GKG_ERR_UNSUPPORTED, "GKG_KNN_F16_CONTRACT: needs GKG_KNN_NORMALIZE");
+    if (flags & GKG_KNN_BF16_CONTRACT) return gkg_fail(GKG_ERR_UNSUPPORTED, "GKG_KNN_F16_CONTRACT: not together with GKG_KNN_BF16_CONTRACT");
+    if (flags & (GKG_KNN_X_PREPARED | GKG_KNN_Y_PREPARED)) return gkg_fail(GKG_ERR_UNSUPPORTED, "GKG_KNN_X/Y_PREPARED: not with the fp16 contraction");
+    if (prep_only) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_bn_apply_knn_prep: not with the fp16 contraction");
+    if (mr) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_knn_mr_fwd_tm: not with the fp16 contraction");
+  }
   const bool x_prepared = (flags & GKG_KNN_X_PREPARED) != 0, y_prepared = (flags & GKG_KNN_Y_PREPARED) != 0;
   if (y_prepared && (!y || prep_only || G_tm <= 0 || dtype != GKG_F32 || (c & 3)))
     return gkg_fail(GKG_ERR_SHAPE, "GKG_KNN_Y_PREPARED: a token-major fp32 k-NN call with keys");
@@ -321,7 +338,9 @@ static int knn_fwd_impl(const void* x, const void* y, const float* relpos, int64
   // bf16 contraction: the normalised copies are bf16 octet-major planes (they fit the fp32 copies' workspace slots); needs
   // c >= 9, i.e. cpad >= 16 (below that the fp32 staging area, which sizes the LDS, is smaller than the bf16 one) —
   // otherwise the flag is ignored
-  const bool bf = (flags & GKG_KNN_BF16_CONTRACT) != 0 && p.cpad >= 16;
+  // (fp16 contraction: fp16 planes of the same size in the same slots, the same launch plan; `bf` covers both 16-bit formats)
+  const bool hf = f16_asked && p.cpad >= 16;
+  const bool bf = ((flags & GKG_KNN_BF16_CONTRACT) != 0 && p.cpad >= 16) || hf;
   const int cp16 = (c + 15) & ~15;
   const int cp16p = (c + 2 + 15) & ~15;            // prefilter planes: + the two |th|^2 channels (see PrepSet)
   const int Nr = (N + 31) & ~31, Mr = (M + 31) & ~31;
@@ -401,9 +420,9 @@ static int knn_fwd_impl(const void* x, const void* y, const float* relpos, int64
     if (!x_prepared) e = launch_prep<float>(sx, nullptr, BG, c, p.cpad, norm, st);
     else e = (y && !y_prepared) ? launch_prep<float>(sy, nullptr, BG, c, p.cpad, norm, st) : hipSuccess;
   }
-  else if (dtype == GKG_F32) e = launch_prep<float>(sx, y ? &sy : nullptr, BG, c, p.cpad, norm, st);
-  else if (dtype == GKG_F16) e = launch_prep<_Float16>(sx, y ? &sy : nullptr, BG, c, p.cpad, norm, st);
-  else e = launch_prep<uint16_t>(sx, y ? &sy : nullptr, BG, c, p.cpad, norm, st);
+  else if (dtype == GKG_F32) e = launch_prep<float>(sx, y ? &sy : nullptr, BG, c, p.cpad, norm, st, PrepAffine{}, hf);
+  else if (dtype == GKG_F16) e = launch_prep<_Float16>(sx, y ? &sy : nullptr, BG, c, p.cpad, norm, st, PrepAffine{}, hf);
+  else e = launch_prep<uint16_t>(sx, y ? &sy : nullptr, BG, c, p.cpad, norm, st, PrepAffine{}, hf);
   if (e != hipSuccess) return gkg_fail_hip(e, "token_prep");
   gkg_prof_add_work(GKG_PROF_KNN_TILE, 2.0 * BG * (double)c * N * (double)M);    // algorithmic flop of the distance contraction
   KnnArgs a;
@@ -419,7 +438,7 @@ static int knn_fwd_impl(const void* x, const void* y, const float* relpos, int64
   a.mr_ldx = a.mr_lds = c; a.mr_xchunk = a.mr_schunk = 0; a.mr_write_x = 1;
   dim3 grid((unsigned)(a.nqt * ((BG + 7) / 8) * 8), 1, p.S);
   a.rp_major = 0; a.rp_group = 1;
-  // bf16 form with a positional bias at least twice the size of the keys it meets (64 x 4 B of relative_pos against
+  // bf16 / fp16 form with a positional bias at least twice the size of the keys it meets (64 x 4 B of relative_pos against
   // 2 x cp16 B of a key per (query tile, key) pair, i.e. c <= 64) and enough query tiles to spread over the XCDs: map the
   // workgroups relative_pos-major (see the kernel).  Measured (tools/bench_knn_bf.py, us): pvig_m stages 1-2 6031 -> 5101,
   // 1590 -> 1487; pvig_s stage 1 1259 -> 1187.
@@ -469,7 +488,7 @@ static int knn_fwd_impl(const void* x, const void* y, const float* relpos, int64
     const bool pays_bf = p.tps >= 2 * NW && (p.tps >= 4 * NW || p.KD >= 18 || p.S > 1);
     if (force == 1 || (force == 0 && !pays_bf)) wbuf = 0;
     if (force == 2 && wbuf == 0) wbuf = 12;
-    e = launch_knn_tile_bf(a, grid, lds, p.KD, wbuf, solo && wbuf > 0, st);
+    e = (hf ? launch_knn_tile_hf : launch_knn_tile_bf)(a, grid, lds, p.KD, wbuf, solo && wbuf > 0, st);
   } else {
     // fp32 contract forms: direct (guarded / guard-less for short streams) or buffered selection — gkg_knn_f32.hip
     // single-wave workgroups for the narrowest groups (pvig_m stage 1: c = 12, 36 864 queries x 2 304 keys, k*d = 18): one list

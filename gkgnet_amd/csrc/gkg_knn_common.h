@@ -107,7 +107,7 @@ struct KnnArgs {
   int rp_major;         // workgroup -> (problem, query tile) map (knn_map): 0 problem-major, 1 = all problems of one query
                         // tile adjacent on one XCD, 2 = groups of rp_group problems of an XCD interleaved per query tile
   int rp_group;
-  const uint16_t* xb;   // BF mode: (BG, N, cp16) / (BG, M, cp16) normalised bf16 token-major copies (prefilter: hi planes)
+  const uint16_t* xb;   // BF mode: (BG, N, cp16) / (BG, M, cp16) normalised bf16 (fp16 form: fp16) copies (prefilter: hi planes)
   const uint16_t* yb;
   int cp16;
   // prefilter mode (knn_pf_kernel)
@@ -163,6 +163,8 @@ __device__ __forceinline__ bool knn_map(const KnnArgs& a, int lin, int& bg, int&
 hipError_t launch_knn_prefilter(const KnnArgs& a, dim3 grid, int KD, hipStream_t st);
 // gkg_knn_bf.hip: the tile kernel's bf16-contraction forms (direct / buffered selection; solo: one wave per query tile)
 hipError_t launch_knn_tile_bf(const KnnArgs& a, dim3 grid, size_t lds, int KD, int wbuf, bool solo, hipStream_t st);
+// gkg_knn_hf.hip: the same forms with the fp16 contraction (xb / yb hold fp16 planes)
+hipError_t launch_knn_tile_hf(const KnnArgs& a, dim3 grid, size_t lds, int KD, int wbuf, bool solo, hipStream_t st);
 // gkg_knn_f32.hip: the tile kernel's fp32-contract forms (mode 0 direct + guard, 1 direct without it, 2 buffered)
 hipError_t launch_knn_tile_f32(const KnnArgs& a, dim3 grid, size_t lds, int KD, int mode, hipStream_t st);
 // gkg_knn_f32_mr.hip: the same forms with the max-relative aggregation in the epilogue (modes 0-2, lists up to 36 entries)

@@ -21,7 +21,8 @@ struct PrepStrides { int G; size_t sb, sg, sc, sn; int chunk; };      // chunk >
 // channels — a matrix-core operand fragment (one token, 8 consecutive channels) is 16 contiguous bytes and the fragments of
 // consecutive tokens are adjacent, so a wave's fragment load / store touches 8 full cache lines instead of 32+ partial ones
 // (measured: the token-major (bg, n, cp16) form left the contraction bound by the texture-address path) — instead of fp32
-// channel-major th.
+// channel-major th.  HF (GKG_KNN_F16_CONTRACT): those planes hold fp16 instead — round-to-nearest-even of the fp32 th, a
+// subnormal result replaced by +0 (pack_f16x2_flush) — same geometry; |th|^2 comes from the unrounded th either way.
 // tb_lo != null (prefilter mode, see knn_pf_kernel): besides the fp32 channel-major copy th (the exact re-rank reads it) the
 // two leading bf16 terms of every normalised value, hi = bf16(v) and lo = bf16(v - hi), are written as token-major
 // (bg, n, cp16) planes (tb = hi, tb_lo = lo) for the matrix-core prefilter.
@@ -61,7 +62,17 @@ __device__ __forceinline__ void prep_affine_table(const BnDerive& d, const float
   __syncthreads();
 }
 
-template <typename T, bool NORM, int PT, bool PROD>
+// fp32 pair -> packed fp16, round-to-nearest-even (the plain conversion under the default rounding mode; the pk_rtz conversion
+// truncates and is not this), with a result below 2^-14 in magnitude — an fp16 subnormal, or a zero of either sign — stored as +0:
+// the contraction never depends on what the matrix core does with subnormal inputs, and a zero exponent field means zero.
+__device__ __forceinline__ uint32_t pack_f16x2_flush(float lo, float hi) {
+  uint32_t l = __builtin_bit_cast(uint16_t, (_Float16)lo), h = __builtin_bit_cast(uint16_t, (_Float16)hi);
+  l = (l & 0x7c00u) ? l : 0u;
+  h = (h & 0x7c00u) ? h : 0u;
+  return l | (h << 16);
+}
+
+template <typename T, bool NORM, int PT, bool PROD, bool HF = false>
 __device__ __forceinline__ void token_prep_body(const PrepSet& s1, const PrepSet& s2, int nbx1, int c, int cpad, const BnDerive& d,
                                                 const float* __restrict__ aff_a, const float* __restrict__ aff_c) {
   extern __shared__ float col[];          // [c][PT] (+ [2][c] scale / shift: PROD)
@@ -193,7 +204,7 @@ __device__ __forceinline__ void token_prep_body(const PrepSet& s1, const PrepSet
     }
     return;
   }
-  if (S.tb) {                                       // bf16 token-major copy: 16-byte stores of 8 channels
+  if (S.tb) {                                       // bf16 (HF: fp16) octet-major copy: 16-byte stores of 8 channels
     uint4* ob = reinterpret_cast<uint4*>(S.tb) + (size_t)bg * (S.cp16 >> 3) * Tn + n;      // octet-major (bg, cp16/8, Tn, 8)
     for (int c0 = 0; c0 < S.cp16; c0 += 8) {
       uint32_t wv[4];
@@ -204,7 +215,7 @@ __device__ __forceinline__ void token_prep_body(const PrepSet& s1, const PrepSet
         if (NORM) { v0 = v0 / den; v1 = v1 / den; }
         q2 = __builtin_fmaf(v0, v0, q2);
         q2 = __builtin_fmaf(v1, v1, q2);
-        wv[u] = pack_bf16x2(v0, v1);
+        wv[u] = HF ? pack_f16x2_flush(v0, v1) : pack_bf16x2(v0, v1);
       }
       ob[(size_t)(c0 >> 3) * Tn] = make_uint4(wv[0], wv[1], wv[2], wv[3]);
     }

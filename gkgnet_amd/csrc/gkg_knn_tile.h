@@ -1,5 +1,6 @@
-// The fused k-NN tile kernel (template) and its launcher, shared by the two translation units that instantiate it:
-// gkg_knn.hip (fp32 contract forms) and gkg_knn_bf.hip (bf16-contraction forms), compiled in parallel.
+// The fused k-NN tile kernel (template) and its launcher, shared by the translation units that instantiate it:
+// gkg_knn.hip (fp32 contract forms), gkg_knn_bf.hip (bf16-contraction forms) and gkg_knn_hf.hip (fp16-contraction forms), compiled
+// in parallel.
 // Arithmetic contract: include/gkg_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -35,6 +36,12 @@ namespace gkg {
 // norms added in fp32.  For callers under bf16 autocast, where the reference itself runs x.y^T in bf16 AND rounds the
 // product matrix to bf16 (torch_edge.py:35-51 under autocast) — this form keeps more of the fp32 answer than that.  Not
 // covered by the bit-exact index contract (the accumulation order inside the 16-deep dot product is the hardware's).
+// BF is the contraction's element format: KNN_EL_F32 (none of the above: the fp32 contract), KNN_EL_BF16, or KNN_EL_F16
+// (GKG_KNN_F16_CONTRACT: v_mfma_f32_32x32x16_f16, the same rate and the same operand lane maps as the bf16 instruction) — the
+// planes then hold fp16 values (normalised tokens lie in [-1, 1]: three more significand bits than bf16, subnormal results
+// flushed to +0 by the preparation), and the form differs from the bf16 one in two places only: the packed -2x of the query
+// staging (exponent field 0x7c00, one step 0x0400) and the matrix instruction.  Layout, LDS pitch, launch bounds, bias as the
+// initial accumulator, side fetches and selection are shared.
 // NWV — waves per workgroup.  4 (default): the waves split the KEY tiles of one 64-query tile and their lists are merged at
 // the end — the only way to fill the chip when a launch has few query tiles.  1: a workgroup is ONE wave that streams all
 // keys for its 64 queries — one list per query instead of four quarter-stream lists, i.e. k·d·(1 + ln(M / k·d)) expected
@@ -48,7 +55,15 @@ namespace gkg {
 // U[q][t][2i+1] = max_j (x_j - x_i) and the winning rows (u16) the backward scatters from.  Replaces the launch pair
 // knn_tile_kernel -> mr_fwd_tm_kernel (reference torch_edge.py:164-176 -> torch_vertex.py:49-61); while one workgroup of a
 // CU gathers, the CU's other two or three are in their matrix phase.
-template <int KD, bool HAS_RP, int KU, bool GUARD = true, int BUF = 0, bool BF = false, int NWV = NW, bool MRF = false>
+constexpr int KNN_EL_F32 = 0, KNN_EL_BF16 = 1, KNN_EL_F16 = 2;
+
+// one 16-deep matrix-core step of either 16-bit format: 8-element operand fragments, the same lane maps
+typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 bf16x8_t;
+typedef __attribute__((__vector_size__(8 * sizeof(_Float16)))) _Float16 f16x8_t;
+__device__ __forceinline__ f32x16 knn_mfma16(bf16x8_t a, bf16x8_t b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ f32x16 knn_mfma16(f16x8_t a, f16x8_t b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+
+template <int KD, bool HAS_RP, int KU, bool GUARD = true, int BUF = 0, int BF = KNN_EL_F32, int NWV = NW, bool MRF = false>
 __global__ __launch_bounds__(64 * NWV, (BF && HAS_RP) ? (KD <= 18 ? 3 : 2) : (KD <= 12 ? (MRF ? 3 : 4) : (KD <= 27 ? 3 : 2))) void knn_tile_kernel(KnnArgs a) {
   // (MRF with the 9-entry list: three workgroups per SIMD instead of four — at 128 registers the gather's k float4 rows next to
   // the bias row of the matrix phase spilled 11-15 registers; the 18 x 18 stages it serves launch three workgroups per CU)
@@ -141,14 +156,17 @@ __global__ __launch_bounds__(64 * NWV, (BF && HAS_RP) ? (KD <= 18 ? 3 : 2) : (KD
       const int ck = i >> 6, q = i & 63;           // consecutive threads: consecutive queries of one octet (coalesced)
       uint4 v = make_uint4(0, 0, 0, 0);
       if (n0 + q < N) v = xbp[(size_t)ck * N + n0 + q];
-      // x -> -2x on packed bf16: exponent + 1 and sign flip, zeros stay zeros (|x| <= 1 after normalisation; raw inputs
-      // near the top of the range would overflow to inf like any -2x)
+      // x -> -2x on packed bf16 / fp16: exponent + 1 and sign flip, zeros stay zeros (|x| <= 1 after normalisation; raw inputs
+      // near the top of the range would overflow to inf like any -2x).  fp16 planes hold no subnormals (flushed by the
+      // preparation), so a zero exponent field means zero there too.
+      constexpr unsigned EM = BF == KNN_EL_F16 ? 0x7c00u : 0x7f80u;   // exponent field
+      constexpr unsigned E1 = BF == KNN_EL_F16 ? 0x0400u : 0x0080u;   // one exponent step
       auto m2h = [](unsigned hv) -> unsigned {
-        const unsigned e = hv & 0x7f80u;
+        const unsigned e = hv & EM;
         if (e == 0u) return 0u;                                   // zero / denormal
-        if (e == 0x7f80u) return hv ^ 0x8000u;                     // inf / NaN keep their class
-        if (e == 0x7f00u) return ((hv ^ 0x8000u) & 0x8000u) | 0x7f80u;   // overflow -> inf
-        return (hv + 0x80u) ^ 0x8000u;
+        if (e == EM) return hv ^ 0x8000u;                          // inf / NaN keep their class
+        if (e == EM - E1) return ((hv ^ 0x8000u) & 0x8000u) | EM;  // overflow -> inf
+        return (hv + E1) ^ 0x8000u;
       };
       auto m2 = [&](unsigned wv) { return m2h(wv & 0xffffu) | (m2h(wv >> 16) << 16); };
       v.x = m2(v.x); v.y = m2(v.y); v.z = m2(v.z); v.w = m2(v.w);
@@ -354,7 +372,7 @@ __global__ __launch_bounds__(64 * NWV, (BF && HAS_RP) ? (KD <= 18 ? 3 : 2) : (KD
     }
     if (BF) {
       // keys = A operand (lane: key l31, 8 channels 16 s + 8 kk ...), the two query blocks = B operands from LDS
-      typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 bf16x8_t;
+      typedef std::conditional_t<BF == KNN_EL_F16, f16x8_t, bf16x8_t> frag_t;
       const uint4* ykp = ybp + (size_t)kk * M + mk;
       const uint4* ykn = ybp + (size_t)kk * M + mk_next;
       const char* xq0 = reinterpret_cast<const char*>(smem) + l31 * qpitch + 16 * kk;
@@ -373,12 +391,12 @@ __global__ __launch_bounds__(64 * NWV, (BF && HAS_RP) ? (KD <= 18 ? 3 : 2) : (KD
 #pragma unroll
         for (int u = 0; u < KB; ++u) {
           if (s0 + u < S16) {
-            const bf16x8_t av = __builtin_bit_cast(bf16x8_t, ac[u]);
-            const bf16x8_t b0 = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(xq0 + 32 * (s0 + u)));
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, b0, acc0, 0, 0, 0);
+            const frag_t av = __builtin_bit_cast(frag_t, ac[u]);
+            const frag_t b0 = __builtin_bit_cast(frag_t, *reinterpret_cast<const uint4*>(xq0 + 32 * (s0 + u)));
+            acc0 = knn_mfma16(av, b0, acc0);
             if (two_blocks) {
-              const bf16x8_t b1 = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(xq1 + 32 * (s0 + u)));
-              acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, b1, acc1, 0, 0, 0);
+              const frag_t b1 = __builtin_bit_cast(frag_t, *reinterpret_cast<const uint4*>(xq1 + 32 * (s0 + u)));
+              acc1 = knn_mfma16(av, b1, acc1);
             }
           }
         }
@@ -709,7 +727,7 @@ __global__ __launch_bounds__(64 * NWV, (BF && HAS_RP) ? (KD <= 18 ? 3 : 2) : (KD
 
 constexpr int KNN_BUF = 16;        // buffered selection: entries per lane (8 bytes each: 32 KB per workgroup)
 
-template <int KD, bool HAS_RP, int KU, bool GUARD = true, int BUF = 0, bool BF = false, int NWV = NW, bool MRF = false>
+template <int KD, bool HAS_RP, int KU, bool GUARD = true, int BUF = 0, int BF = KNN_EL_F32, int NWV = NW, bool MRF = false>
 static hipError_t launch_tile_v(const KnnArgs& a, dim3 grid, size_t lds, hipStream_t st) {
   // staged query tile: fp32 [cpad][64], or (bf16 form) 64 rows of cp16 + 8 bf16
   const size_t qbytes = BF ? (size_t)QT * (a.cp16 + 8) * 2 : (size_t)a.cpad * QT * sizeof(float);

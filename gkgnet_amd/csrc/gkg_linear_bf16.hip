@@ -460,9 +460,9 @@ extern "C" int gkg_linear_bf16_f32a(const float* x, int ldx, const void* wplanes
 }
 
 // ---------------------------------------------------------------------------------------------- fc1 + the k-NN's token preparation
-// Scope of the fused form (include/gkg_hip.h): queries of a plain token-major output, fp32 contraction.  0: in scope.
+// Scope of the fused form (include/gkg_hip.h): queries of a plain token-major output, fp32 contraction (neither 16-bit one).  0: in scope.
 static int lbp_scope(int ochunk, int as_keys, const float* res_tm, const float* out_nchw, unsigned knn_flags) {
-  return (ochunk != 0 || as_keys != 0 || res_tm || out_nchw || (knn_flags & GKG_KNN_BF16_CONTRACT)) ? GKG_ERR_UNSUPPORTED : 0;
+  return (ochunk != 0 || as_keys != 0 || res_tm || out_nchw || (knn_flags & (GKG_KNN_BF16_CONTRACT | GKG_KNN_F16_CONTRACT))) ? GKG_ERR_UNSUPPORTED : 0;
 }
 static bool lbp_sizes_ok(int cin, int B, int G, int c, int N) {
   if (B <= 0 || G <= 0 || c <= 0 || N <= 0 || (c & 3)) return false;
@@ -489,7 +489,7 @@ extern "C" int gkg_linear_bf16_knn_prep(const void* x, int ldx, const void* wpla
                                         size_t scratch_bytes, void* stream) {
   if (!x || !wplanes || !cshift || !out || !knn_workspace) return gkg_fail(GKG_ERR_NULL, "gkg_linear_bf16_knn_prep: null pointer");
   if (lbp_scope(ochunk, as_keys, res_tm, out_nchw, knn_flags) != 0)
-    return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_bf16_knn_prep: queries into plain rows only (no ochunk, as_keys, res_tm, out_nchw, bf16 contraction)");
+    return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_bf16_knn_prep: queries into plain rows only (no ochunk, as_keys, res_tm, out_nchw, bf16 / fp16 contraction)");
   if (B <= 0 || G <= 0 || c <= 0 || N <= 0 || cin <= 0) return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_bf16_knn_prep: bad sizes");
   if (!lbp_sizes_ok(cin, B, G, c, N))
     return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_bf16_knn_prep: need c % 4 == 0, cin % 8 == 0, (G c) % 8 == 0 and a grid that fits");

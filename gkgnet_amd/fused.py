@@ -60,6 +60,12 @@ DETERMINISTIC = os.environ.get("GKG_DETERMINISTIC", "0") != "0"
 #                  bit-exact index contract (neighbour-set agreement 0.91-0.997 with the exact graph), hence
 #                  opt-in since round 4: by default autocast callers get the SAME graphs as fp32 callers (north_star:
 #                  "bit-exact neighbor indices"); bench.py --workload cfg3 / cfg5 prints both legs.
+#   knn_f16        under CUDA autocast of either 16-bit dtype the contraction runs on the fp16 matrix cores instead
+#                  (GKG_KNN_F16_CONTRACT: normalised tokens lie in [-1, 1], where fp16 keeps three more significand bits than
+#                  bf16 at the same matrix-core rate — about eight times fewer changed neighbours; under fp16 autocast
+#                  the reference itself contracts in fp16).  Outside the bit-exact index contract like knn_bf16, hence opt-in.
+#                  With both switches on, knn_bf16 wins where it acts (bf16 autocast): bench.py flips KNN_BF16 for its second
+#                  leg, so GKG_ENABLE=knn_f16 python bench.py --workload cfg3 times fp16 (first leg) and bf16 in one process.
 #   lin_bf16       bf16 inference on the channels-last chain: the four dense projections of a Grapher + FFN pair (fc1, fc2,
 #                  FFN.fc1, FFN.fc2) run on the library's own bf16 kernel with eval-mode BN, GELU, the fp32 residual and both
 #                  output precisions in its epilogue (gkg_linear_bf16; linear_bf16.py) instead of the vendor GEMM (+ a stand-alone
@@ -68,7 +74,7 @@ DETERMINISTIC = os.environ.get("GKG_DETERMINISTIC", "0") != "0"
 #   lin_bf16_prep  with lin_bf16 only: a Grapher's fc1 launch also prepares its output as the k-NN's queries (normalised copies,
 #                  |t|^2, prefilter planes: gkg_linear_bf16_knn_prep; linear_bf16.py) — the last workgroup of a row tile runs the
 #                  preparation on the rows the tile completed, and the k-NN call behind it (GKG_KNN_X_PREPARED) launches no
-#                  token preparation for the queries.  Same bits as lin_bf16 alone.  Not with knn_bf16 or a patched knn_graph_tm.
+#                  token preparation for the queries.  Same bits as lin_bf16 alone.  Not with knn_bf16 / knn_f16 or a patched knn_graph_tm.
 #                  Taken only at the shapes where it measured at least as fast as the two launches (linear_bf16.prep_pays: the
 #                  stage-1 shapes of cfg3 / cfg5); lin_bf16_prep_all takes it wherever the library accepts the shape (tests,
 #                  measurements).
@@ -107,6 +113,7 @@ DETERMINISTIC = os.environ.get("GKG_DETERMINISTIC", "0") != "0"
 _DISABLED = _env_list("GKG_DISABLE")
 _ENABLED = _env_list("GKG_ENABLE")
 KNN_BF16 = "knn_bf16" in _ENABLED
+KNN_F16 = "knn_f16" in _ENABLED            # likewise a module constant (tests and bench legs flip them)
 LIN_BF16 = "lin_bf16" in _ENABLED          # a module constant the tests flip (like MR_GEMM)
 # likewise (False | True: the measured shapes | "all": every supported shape); acts only together with LIN_BF16
 LIN_BF16_PREP = "all" if "lin_bf16_prep_all" in _ENABLED else ("lin_bf16_prep" in _ENABLED)
@@ -1170,8 +1177,8 @@ def _knn_graph(x, y, relative_pos, k, dilation, G, compact):
     M = N if y is None else y.shape[1]
     rp = None if relative_pos is None else _rp_arg(relative_pos, N, M)
     # (under opt-in bf16 autocast the reference's own x.y^T runs in bf16, and rounds the result to bf16)
-    flags = knn_prep.problem_flags(relative_pos, KNN_BF16 and torch.is_autocast_enabled()
-                                   and torch.get_autocast_dtype("cuda") == torch.bfloat16)
+    contract = knn_contract()
+    flags = knn_prep.problem_flags(relative_pos, contract == "bf16", contract == "f16")
     if compact:
         out, entry = torch.empty((B * G, N, k), dtype=torch.int16, device=x.device), "gkg_knn_fwd_tm16"
         outs = (_ptr(out),)
@@ -1182,6 +1189,17 @@ def _knn_graph(x, y, relative_pos, k, dilation, G, compact):
     _lib.check(getattr(lib, entry)(_ptr(x), ldx, xchunk, _ptr(y), _ptr(rp), *outs, B, G, c, N, M, k, dilation, _lib.F32, flags,
                                    _ptr(ws), ws.numel(), _stream()), entry)
     return out
+
+
+def knn_contract():
+    """The opt-in 16-bit contraction the k-NN call made right now would take: "bf16" (KNN_BF16 under bf16 autocast), "f16" (KNN_F16
+    under CUDA autocast of either 16-bit dtype; bf16 wins when both apply) or None (the index-exact fp32 contract)."""
+    if not ((KNN_BF16 or KNN_F16) and torch.is_autocast_enabled()):
+        return None
+    dt = torch.get_autocast_dtype("cuda")
+    if KNN_BF16 and dt == torch.bfloat16:
+        return "bf16"
+    return "f16" if KNN_F16 and dt in (torch.bfloat16, torch.float16) else None
 
 
 def knn_graph_tm(x, y, relative_pos, k, dilation, G):
@@ -1300,8 +1318,8 @@ class _KnnMaxRelativeTM(torch.autograd.Function):
 
 def _knn_ahead_ok() -> bool:
     """The k-NN problem of a call can be told before its tokens exist (the fused kernel chosen, the tokens prepared by their
-    producer): not with the bf16 contraction, nor with a patched ``knn_graph_tm`` (tests that record or force graphs)."""
-    return knn_graph_tm is _KNN_GRAPH_TM and not (KNN_BF16 and torch.is_autocast_enabled())
+    producer): not with the bf16 / fp16 contraction, nor with a patched ``knn_graph_tm`` (tests that record or force graphs)."""
+    return knn_graph_tm is _KNN_GRAPH_TM and not ((KNN_BF16 or KNN_F16) and torch.is_autocast_enabled())
 
 
 def _knn_mr_shapes_ok(B, N, C, M, has_src, relative_pos, k, d, G, nn_, lp) -> bool:

@@ -25,10 +25,11 @@ from . import _lib
 from .ops import _ptr
 
 
-def problem_flags(relative_pos, bf16_contract=False) -> int:
-    """The flag word of a block's k-NN problem: what producer and consumer compare, and the k-NN call's flags before the _PREPARED bits."""
+def problem_flags(relative_pos, bf16_contract=False, f16_contract=False) -> int:
+    """The flag word of a block's k-NN problem: what producer and consumer compare, and the k-NN call's flags before the _PREPARED bits.
+    At most one 16-bit contraction: the library rejects both bits together, and bf16 wins here (fused.knn_contract)."""
     return (_lib.KNN_NORMALIZE | _lib.knn_select_flags() | _lib.relpos_flags(relative_pos)
-            | (_lib.KNN_BF16_CONTRACT if bf16_contract else 0))
+            | (_lib.KNN_BF16_CONTRACT if bf16_contract else (_lib.KNN_F16_CONTRACT if f16_contract else 0)))
 
 
 def _workspace(lib, device, B, G, c, N, M, k, d) -> torch.Tensor:
@@ -112,10 +113,10 @@ def prepared_keys(out_tm):
 
 def consumer_ws_flags(lib, x, B, G, c, N, M, k, d, has_y, has_rp, flags, fused_mr):
     """(workspace, flags) for a k-NN call on queries ``x``: the producer's workspace + GKG_KNN_X_PREPARED (+ _Y_PREPARED) when x carries
-    prepared copies for exactly this problem (KnnProblem.mark), else a fresh workspace and the flags as given.  The bf16 contraction
-    reads no prepared copies."""
+    prepared copies for exactly this problem (KnnProblem.mark), else a fresh workspace and the flags as given.  The bf16 and fp16
+    contractions read no prepared copies."""
     p = getattr(x, "_gkg_knn", None)
-    if (p is not None and p.ws is not None and not (flags & _lib.KNN_BF16_CONTRACT)
+    if (p is not None and p.ws is not None and not (flags & (_lib.KNN_BF16_CONTRACT | _lib.KNN_F16_CONTRACT))
             and p.tuple() == (B, G, c, N, M, k, d, int(bool(has_y)), int(bool(has_rp)), flags, int(bool(fused_mr)))):
         return p.ws, flags | _lib.KNN_X_PREPARED | (_lib.KNN_Y_PREPARED if p.y_ready else 0)
     return _workspace(lib, x.device, B, G, c, N, M, k, d), flags

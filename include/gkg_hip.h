@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define GKG_ABI_VERSION 18
+#define GKG_ABI_VERSION 19
 
 /* dtype codes */
 #define GKG_F32 0
@@ -81,6 +81,28 @@ extern "C" {
                                     * launches no preparation for them (none at all for a self graph) */
 #define GKG_KNN_Y_PREPARED 256u     /* likewise for the KEYS (gkg_bn_apply_knn_prep with as_keys: a label graph's keys, produced by the
                                     * Grapher in front of it) */
+#define GKG_KNN_F16_CONTRACT 512u   /* x.y^T on the fp16 matrix cores (v_mfma_f32_32x32x16_f16: the bf16 form's rate), for callers under
+                                    * 16-bit autocast who want fewer changed neighbours than GKG_KNN_BF16_CONTRACT gives: normalised
+                                    * tokens lie in [-1, 1], where fp16 rounds 2^-12 relative against bf16's 2^-9.  Accepted by
+                                    * gkg_knn_fwd, gkg_knn_fwd_tm, gkg_knn_fwd_tm16 and gkg_knn_workspace_bytes (the workspace plan is
+                                    * the bf16 form's: planes of the same size).  Token preparation is the contract's (s, den, th, sq
+                                    * above; sq from the UNROUNDED fp32 th); the planes hold h(th) = fp16 round-to-nearest-even of the
+                                    * fp32 th, with a result of magnitude below 2^-14 (an fp16 subnormal) replaced by +0; the distance is
+                                    *     dist = ( relpos[n][m] + sum_ch (-2 h(xh[ch][n])) * h(yh[ch][m]) ) + sqy[m]
+                                    * The products are exact in fp32 (11 x 11 significand bits, exponents >= 2^-28), the accumulator
+                                    * is fp32 and STARTS at relpos[n][m] (0 without a bias), sqy[m] is added last in fp32, the query's
+                                    * own |x|^2 is left out.  Only the order of the c additions inside the 16-deep matrix-core steps
+                                    * is the hardware's: a distance lies within (c + 2) 2^-24 (max|relpos| + 3.1) of its real value
+                                    * (tests/knn_f16_ref.py).  Neighbours: the k d smallest (dist, m) pairs, smaller index first on
+                                    * equal distance; ranks 0, d, 2d, ... are emitted.  The flush is a decision of this definition:
+                                    * the result does not depend on what the matrix core does with subnormal inputs, and -2 h(x) is
+                                    * an exact exponent step (a zero exponent field means zero).
+                                    *   GKG_ERR_UNSUPPORTED, nothing launched: without GKG_KNN_NORMALIZE (raw tokens can overflow
+                                    * fp16); together with GKG_KNN_BF16_CONTRACT; with GKG_KNN_X_PREPARED / GKG_KNN_Y_PREPARED; as
+                                    * knn_flags of gkg_bn_apply_knn_prep[_sync], gkg_affine_knn_prep or gkg_linear_bf16_knn_prep;
+                                    * through gkg_knn_mr_fwd_tm.  gkg_knn_mr_fused_supported and gkg_linear_bf16_knn_prep_supported
+                                    * answer 0.  The prefilter is never taken.  Outside the bit-exact index contract; ignored for
+                                    * c < 9 (the call is then the fp32 contract). */
 
 /* argument errors */
 #define GKG_ERR_NULL -1        /* required pointer is NULL */
@@ -421,7 +443,7 @@ int gkg_linear_bf16(const void* x /* bf16 (R, ldx) */, int ldx, const void* wpla
  * and the k-NN call with the same problem follows with GKG_KNN_X_PREPARED and x = out: it launches no preparation for the queries
  * (the keys of a problem with has_y are prepared by that call as always).
  * Scope, otherwise GKG_ERR_UNSUPPORTED with nothing launched: queries into plain rows only — ochunk == 0, as_keys == 0, res_tm ==
- * out_nchw == NULL, no GKG_KNN_BF16_CONTRACT in knn_flags; gkg_linear_bf16's preconditions (cin % 8, (G c) % 8, ldx % 8, ldo % 4,
+ * out_nchw == NULL, no GKG_KNN_BF16_CONTRACT / GKG_KNN_F16_CONTRACT in knn_flags; gkg_linear_bf16's preconditions (cin % 8, (G c) % 8, ldx % 8, ldo % 4,
  * 16-byte alignment; a pitch below its row's width is GKG_ERR_SHAPE) and c % 4 == 0; everything the k-NN plan itself refuses comes
  * back with that call's code.  ldo == 0 means G c.
  * scratch: gkg_linear_bf16_knn_prep_scratch_bytes(B N) bytes (one arrival counter per 128-row tile), caller-owned, 4-byte
