@@ -112,84 +112,23 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const float* __restrict_
 // ================================================================================================ host side
 using namespace gkg;
 
-// list sizes of the tile kernel: the lengths GKGNet's configurations use (k*d = 9, 18, 27; pvig_m k = 18: 18, 36) plus 16
-// and 64 to cover everything else (each instantiation is a kernel of its own: 6 sizes x 2 x 2 x 3 selection forms)
-static const int kListSizes[] = {9, 18, 27, 36, 64};   // k*d of GKGNet's layers + one catch-all (10..18 share the 18-entry list)
-
-static int pick_list(int kd) {
-  for (int s : kListSizes) if (s >= kd) return s;
-  return -1;
-}
-
-static int pick_splits(int BG, int N, int M) {
-  const int qtiles = (N + QT - 1) / QT;
-  const int ktiles = (M + KT - 1) / KT;
-  const long wgs = (long)qtiles * BG;
-  int S = 1;
-  if (wgs < 256) {                                 // fewer workgroups than CUs: split the keys
-    S = (int)((512 + wgs - 1) / wgs);
-    const int smax = (ktiles + 7) / 8;          // keep >= 8 key tiles (2 per wave) per split
-    if (S > smax) S = smax;
-    if (S < 1) S = 1;
-    if (S > 64) S = 64;
-  }
-  return S;
-}
-
-struct KnnPlan {
-  int cpad, kd, KD, S, tps;
-  size_t off_xh, off_yh, off_sqx, off_sqy, off_pv, off_pi, off_xp, off_yp, off_flags, total;
-};
-
-static int make_plan(int BG, int c, int N, int M, int k, int dilation, bool has_y, KnnPlan* p) {
-  if (BG <= 0 || c <= 0 || N <= 0 || M <= 0 || k <= 0 || dilation <= 0) return GKG_ERR_SHAPE;
-  if ((long)k * dilation > M) return GKG_ERR_SHAPE;
-  if (!has_y && M != N) return GKG_ERR_SHAPE;
-  p->cpad = (c + 7) & ~7;          // zero-padded channels: fma(0,0,acc) == acc keeps the chain exact
-  p->kd = k * dilation;
-  p->KD = pick_list(p->kd);
-  if (p->KD < 0) return GKG_ERR_UNSUPPORTED;
-  if ((size_t)p->cpad * QT * sizeof(float) > 150 * 1024) return GKG_ERR_UNSUPPORTED;   // c <= 600
-  if (BG > 65535) return GKG_ERR_UNSUPPORTED;           // token_prep uses grid.y = BG
-  if ((long)M + KT > (long)IDX_BITS) return GKG_ERR_UNSUPPORTED;   // key indices live in 29 bits of the list keys
-  p->S = pick_splits(BG, N, M);
-  const int ktiles = (M + KT - 1) / KT;
-  p->tps = (ktiles + p->S - 1) / p->S;
-  p->S = (ktiles + p->tps - 1) / p->tps;
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  size_t o = 0;
-  p->off_xh = o; o = al(o + sizeof(float) * (size_t)BG * p->cpad * N);
-  p->off_sqx = o; o = al(o + sizeof(float) * ((size_t)BG * N + 32));
-  if (has_y) {
-    p->off_yh = o; o = al(o + sizeof(float) * (size_t)BG * p->cpad * M);
-    p->off_sqy = o; o = al(o + sizeof(float) * ((size_t)BG * M + 32));
-  } else {
-    p->off_yh = p->off_xh; p->off_sqy = p->off_sqx;
-  }
-  if (p->S > 1) {
-    p->off_pv = o; o = al(o + sizeof(float) * (size_t)p->S * BG * N * p->kd);
-    p->off_pi = o; o = al(o + sizeof(int) * (size_t)p->S * BG * N * p->kd);
-    p->off_xp = p->off_yp = p->off_flags = 0;
-  } else {
-    p->off_pv = p->off_pi = 0;
-    // prefilter mode (un-split problems): bf16 hi + lo planes (BG, T, cp16) of the queries and keys
-    const size_t cp16 = (size_t)((c + 2 + 15) & ~15);               // + the two |th|^2 channels (see PrepSet)
-    const size_t Nr = (size_t)((N + 31) & ~31), Mr = (size_t)((M + 31) & ~31);
-    p->off_xp = o; o = al(o + 2 * sizeof(uint16_t) * (size_t)BG * Nr * cp16);
-    if (has_y) { p->off_yp = o; o = al(o + 2 * sizeof(uint16_t) * (size_t)BG * Mr * cp16); }
-    else p->off_yp = p->off_xp;
-    p->off_flags = o; o = al(o + sizeof(int) * (size_t)((N + QT - 1) / QT) * ((BG + 7) / 8) * 8);   // one per workgroup
-  }
-  p->total = o;
-  return 0;
+// The request of a token-major entry point (B images x G groups) as a value
+static KnnCall knn_call_tm(KnnRole role, int B, int G, int c, int N, int M, int k, int dilation, int dtype, unsigned flags, bool has_y,
+                           bool has_relpos, int ldx, int xchunk, bool consumer_fused = false) {
+  KnnCall q{};
+  q.BG = B * G; q.G_tm = G; q.c = c; q.N = N; q.M = M; q.k = k; q.dilation = dilation; q.dtype = dtype; q.flags = flags;
+  q.has_y = has_y; q.has_relpos = has_relpos; q.ldx = ldx; q.xchunk = xchunk; q.role = role; q.consumer_fused = consumer_fused;
+  return q;
 }
 
 extern "C" size_t gkg_knn_workspace_bytes(int BG, int c, int N, int M, int k, int dilation, int dtype, unsigned flags) {
   (void)dtype; (void)flags;
-  KnnPlan p;
   // y presence is unknown here: budget for it (upper bound) unless the shapes make it impossible
-  if (make_plan(BG, c, N, M, k, dilation, true, &p) != 0) return 0;
-  return p.total;
+  KnnCall q = knn_call_tm(KNN_GRAPH, BG, 1, c, N, M, k, dilation, GKG_F32, 0, true, false, 0, 0);
+  q.G_tm = 0;
+  KnnPlan p;
+  const char* msg;
+  return knn_plan(q, &p, &msg) == 0 ? p.total : 0;
 }
 
 // BN-apply producer of the queries (PrepSet::raw): coefficients derived from column sums (d.sums) or given (a, c)
@@ -210,7 +149,7 @@ static void launch_prep_pt(const PrepSet& s1, const PrepSet* s2, int BG, int c, 
     }
     return;
   }
-  if (hf) {                                      // fp16 planes: normalised tokens only (knn_fwd_impl)
+  if (hf) {                                      // fp16 planes: normalised tokens only (knn_plan)
     hipLaunchKernelGGL((token_prep_kernel<T, true, PT, true>), grid, dim3(PT), lds, st, s1, second, nbx1, c, cpad);
     return;
   }
@@ -255,79 +194,36 @@ static hipError_t launch_prep(const PrepSet& s1, const PrepSet* s2, int BG, int 
   return hipGetLastError();
 }
 
-// The queries' BN-apply riding in their preparation pass (gkg_bn_apply_knn_prep)
-// want != null: no launch — the producer runs the preparation inside a kernel of its own (gkg_linear_bf16_knn_prep) and asks for
-// the queries' PrepSet, cpad and the normalisation switch of exactly this plan instead.
-struct KnnProducer { PrepAffine aff; float* raw; int raw_ld, raw_chunk; int as_keys; const float* res_tm; float* nchw;
-                     KnnQueryPrep* want; };
-
-// Fused aggregation request of gkg_knn_mr_fwd_tm (token-major fp32 callers): outputs of knn_tile_kernel<..., MRF = true>.
-struct KnnMrFuse {
-  float* out;             // XM (B * N, 2 C): m into the m chunks; x into the x chunks unless x already lives there
-  uint16_t* arg;          // (B, N, C)
-  uint16_t* nn16;         // (B * G, N, k) or null
+// What a call hands over besides its KnnCall.  Producer roles: `x` is a projection's pre-BN output (B, T, C); the preparation pass
+// applies the BN (aff), stores the result to `raw` (keys: + res_tm, also to nchw) and leaves the normalised copies / norms
+// (/ prefilter planes) in the workspace exactly where the k-NN call with the same problem + GKG_KNN_X_PREPARED (_Y_PREPARED) expects
+// them.  KNN_QUERY_PREP_PLAN: no launch — the producer runs the preparation inside a kernel of its own and gets the queries'
+// PrepSet, cpad and the normalisation switch of this plan in *want.
+struct KnnPtrs {
+  const void* x; const void* y; const float* relpos;
+  int64_t* nn_idx; int64_t* center;     // (BG, N, k) int64 lists / centre plane, or null
+  uint16_t* nn16;                       // compact u16 lists INSTEAD of (KNN_FUSED: besides) the int64 plane, or null
+  void* workspace; size_t workspace_bytes; void* stream;
+  float* mr_out; uint16_t* mr_arg;      // KNN_FUSED: XM (B * N, 2 C) and the winning neighbour rows (B, N, C)
+  PrepAffine aff; float* raw; int raw_ld, raw_chunk; const float* res_tm; float* nchw;
+  KnnQueryPrep* want;
 };
 
-// The launch-plan part of the eligibility of the fused form (the caller checks dtype / channel alignment): the fp32 tile
-// kernel with merged per-wave lists — no key splits, no prefilter, no single-wave form — and lists of at most 36 entries.
-static bool knn_mr_plan_ok(const KnnPlan& p, int c, int N, int M, int k, bool pf, bool solo32) {
-  return p.S == 1 && !pf && !solo32 && p.KD <= 36 && k <= 18 && M <= 65536 && (c & 3) == 0 &&
-         (size_t)NW * p.KD * 64 * 8 + (size_t)k * 64 * 4 <= 150 * 1024;
-}
-
-static int knn_fwd_impl(const void* x, const void* y, const float* relpos, int64_t* nn_idx, int64_t* center,
-                        int BG, int c, int N, int M, int k, int dilation, int dtype, unsigned flags,
-                        void* workspace, size_t workspace_bytes, void* stream, int G_tm, const KnnMrFuse* mr = nullptr,
-                        bool probe_only = false, uint16_t* nn16_only = nullptr, int ldx = 0, int xchunk = 0,
-                        const KnnProducer* prod = nullptr) {
-  // prod != null (gkg_bn_apply_knn_prep): PREPARATION ONLY — `x` is a projection's pre-BN output (B, N, C); the queries' pass
-  // applies the BN, stores the result to prod->raw and leaves the normalised copies / norms (/ prefilter planes) in the workspace
-  // exactly where the k-NN call with the same arguments + GKG_KNN_X_PREPARED expects them (same plan, same decisions: this IS that
-  // call up to its preparation launch); y / relpos / mr are only tested for presence.
-  const bool prep_only = prod != nullptr;
-  // fp16 contraction (GKG_KNN_F16_CONTRACT): normalised tokens only (raw ones can overflow fp16), one 16-bit format per call, no
-  // prepared copies, no preparing producer, not the fused k-NN + aggregation.  Rejected on the flag word, before anything else.
-  const bool f16_asked = (flags & GKG_KNN_F16_CONTRACT) != 0;
-  if (f16_asked) {
-    if (probe_only) return GKG_ERR_UNSUPPORTED;
-    if (!(flags & GKG_KNN_NORMALIZE)) return gkg_fail(GKG_ERR_UNSUPPORTED, "GKG_KNN_F16_CONTRACT: needs GKG_KNN_NORMALIZE");
-    if (flags & GKG_KNN_BF16_CONTRACT) return gkg_fail(GKG_ERR_UNSUPPORTED, "GKG_KNN_F16_CONTRACT: not together with GKG_KNN_BF16_CONTRACT");
-    if (flags & (GKG_KNN_X_PREPARED | GKG_KNN_Y_PREPARED)) return gkg_fail(GKG_ERR_UNSUPPORTED, "GKG_KNN_X/Y_PREPARED: not with the fp16 contraction");
-    if (prep_only) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_bn_apply_knn_prep: not with the fp16 contraction");
-    if (mr) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_knn_mr_fwd_tm: not with the fp16 contraction");
-  }
-  const bool x_prepared = (flags & GKG_KNN_X_PREPARED) != 0, y_prepared = (flags & GKG_KNN_Y_PREPARED) != 0;
-  if (y_prepared && (!y || prep_only || G_tm <= 0 || dtype != GKG_F32 || (c & 3)))
-    return gkg_fail(GKG_ERR_SHAPE, "GKG_KNN_Y_PREPARED: a token-major fp32 k-NN call with keys");
-  if (prep_only && x_prepared) return gkg_fail(GKG_ERR_SHAPE, "gkg_bn_apply_knn_prep: GKG_KNN_X_PREPARED makes no sense here");
-  if ((prep_only || x_prepared) && (G_tm <= 0 || dtype != GKG_F32 || (c & 3)))
-    return gkg_fail(GKG_ERR_UNSUPPORTED, "prepared queries: token-major fp32 callers with c % 4 == 0 only");
-  // ldx / xchunk (token-major fp32 callers, G_tm > 0): x as a view — row pitch ldx floats (0: G_tm * c), chunk xchunk
-  // (gkg_common.h "XM layout": xchunk = C / 4 with ldx = 2 C is the x half of the grouped projection's operand buffer)
-  if (G_tm > 0) {
-    const int C = G_tm * c;
-    if (ldx == 0) ldx = C;
-    if (ldx < C || xchunk < 0 || (xchunk > 0 && (dtype != GKG_F32 || (xchunk & 3) || (c & 3) || (ldx & 3) || C % xchunk || ldx < 2 * C)))
-      return gkg_fail(GKG_ERR_SHAPE, "gkg_knn_fwd_tm: bad x view (ldx >= C; a chunk needs fp32, c % 4 == 0, chunk % 4 == 0, chunk | C, ldx >= 2 C)");
-  } else if (ldx != 0 || xchunk != 0) {
-    return gkg_fail(GKG_ERR_SHAPE, "gkg_knn_fwd: x views are a token-major feature");
-  }
-  // nn16_only (gkg_knn_fwd_tm16): the neighbour lists as u16 rows INSTEAD of the int64 plane (M <= 65 536)
-  if (!probe_only && (!x || (!nn_idx && !mr && !nn16_only && !prep_only) || !workspace)) return gkg_fail(GKG_ERR_NULL, "gkg_knn_fwd: x, nn_idx and workspace must be non-null");
-  if (dtype != GKG_F32 && dtype != GKG_BF16 && dtype != GKG_F16) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_knn_fwd: dtype must be GKG_F32, GKG_BF16 or GKG_F16");
+// The launch sequence of every role: plan, the two operand sets, the preparation launch the plan asks for, then (k-NN calls) the
+// prefilter if planned, the tile kernel, the merge of split keys.  Every decision is the plan's (gkg_knn_plan.h).
+static int knn_fwd_impl(const KnnCall& q, const KnnPtrs& t) {
   KnnPlan p;
-  int rc = make_plan(BG, c, N, M, k, dilation, y != nullptr, &p);
-  if (rc == GKG_ERR_SHAPE) return gkg_fail(rc, "gkg_knn_fwd: bad sizes (need >0, k*dilation <= M, M == N for the self graph)");
-  if (rc != 0) return gkg_fail(rc, "gkg_knn_fwd: unsupported size (k*dilation <= 64, c <= 600, BG <= 65535)");
-  if (!probe_only && workspace_bytes < p.total) return gkg_fail(GKG_ERR_WORKSPACE, "gkg_knn_fwd: workspace too small (see gkg_knn_workspace_bytes)");
-  hipStream_t st = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  float* xh = (float*)(ws + p.off_xh);
-  float* yh = (float*)(ws + p.off_yh);
-  float* sqx = (float*)(ws + p.off_sqx);
-  float* sqy = (float*)(ws + p.off_sqy);
-  const bool norm = (flags & GKG_KNN_NORMALIZE) != 0;
-  hipError_t e;
+  const char* msg;
+  const int rc = knn_plan(q, &p, &msg);
+  if (rc != 0) return msg ? gkg_fail(rc, msg) : rc;
+  if (!t.x || !t.workspace || (q.role == KNN_GRAPH && !t.nn_idx && !t.nn16)) return gkg_fail(GKG_ERR_NULL, "gkg_knn_fwd: x, nn_idx and workspace must be non-null");
+  if (t.workspace_bytes < p.total) return gkg_fail(GKG_ERR_WORKSPACE, "gkg_knn_fwd: workspace too small (see gkg_knn_workspace_bytes)");
+  const int BG = q.BG, c = q.c, N = q.N, M = q.M, G_tm = q.G_tm;
+  hipStream_t st = (hipStream_t)t.stream;
+  char* ws = (char*)t.workspace;
+  float *xh = (float*)(ws + p.off_xh), *yh = (float*)(ws + p.off_yh), *sqx = (float*)(ws + p.off_sqx), *sqy = (float*)(ws + p.off_sqy);
+  uint16_t *xpl = (uint16_t*)(ws + p.off_xp), *ypl = (uint16_t*)(ws + p.off_yp);                     // prefilter planes: hi, then lo
+  uint16_t *xpl_lo = xpl + (size_t)BG * p.Nr * p.cp16p, *ypl_lo = ypl + (size_t)BG * p.Mr * p.cp16p;
   // input addressing: channel-major (BG,c,T)  or  token-major (B,T,C=G*c) when G_tm > 0
   auto strides = [&](int Tn, int ld, int chunk) {
     PrepStrides ps;
@@ -335,186 +231,64 @@ static int knn_fwd_impl(const void* x, const void* y, const float* relpos, int64
     else { ps.G = 1; ps.sb = (size_t)c * Tn; ps.sg = 0; ps.sc = Tn; ps.sn = 1; ps.chunk = 0; }
     return ps;
   };
-  // bf16 contraction: the normalised copies are bf16 octet-major planes (they fit the fp32 copies' workspace slots); needs
-  // c >= 9, i.e. cpad >= 16 (below that the fp32 staging area, which sizes the LDS, is smaller than the bf16 one) —
-  // otherwise the flag is ignored
-  // (fp16 contraction: fp16 planes of the same size in the same slots, the same launch plan; `bf` covers both 16-bit formats)
-  const bool hf = f16_asked && p.cpad >= 16;
-  const bool bf = ((flags & GKG_KNN_BF16_CONTRACT) != 0 && p.cpad >= 16) || hf;
-  const int cp16 = (c + 15) & ~15;
-  const int cp16p = (c + 2 + 15) & ~15;            // prefilter planes: + the two |th|^2 channels (see PrepSet)
-  const int Nr = (N + 31) & ~31, Mr = (M + 31) & ~31;
-  // prefilter mode: the bit-exact contract path for normalised, un-split problems with lists up to 36 entries (LDS)
-  const size_t pf_stage = (size_t)2 * QT * (cp16p + 8) * 2;
-  // Where it pays (MI355X, tools/bench_ops.py, prefilter vs fp32 tile kernel, us per launch incl. the extra preparation
-  // work): long key streams, where the contraction dominates — pvig_s@576 stage 3 (c = 200, 1296 x 1296) k*d = 18:
-  // 437 + 92 vs 594 + 57, k*d = 27: 525 + 91 vs 827 + 56; stage 2 (c = 80, 5184 x 1296, k*d = 9): 675 + 82 vs 882 + 58;
-  // stage 1 (c = 40, 20736 x 1296): 2203 + 143 vs 2382 + 97.  It loses on short streams, where its serial tail (merge,
-  // exact pass, final ranking in one wave) is not amortised (cfg2 label graph 34 vs 25, C = 640 / k*d = 27 at 18 x 18: 210
-  // vs 119; the cfg2 Grapher graph is a tie: 51 + 22 vs 54 + 15), and against the BUFFERED selection of narrow groups with
-  // long lists (pvig_m: c = 24 / k*d = 18: 4469 vs 3149).  GKG_KNN_FORCE_PREFILTER overrides the rule (tests).
-  const bool pf_pays = M >= 1024 && (p.KD <= 12 ? p.cpad >= 40 : (p.KD <= 27 && p.cpad >= 128));
-  // The prefilter's error bound (knn_pf_kernel, step 3) is derived for |relative_pos| <= 1.125: the bias is the initial value of
-  // the accumulators, so the rounding of the accumulation scales with |bias| + 2.  A call with a bias takes the prefilter only
-  // when the caller vouches for that range (GKG_KNN_RELPOS_UNIT; GKGNet's bias -2 PE PE^T / D lies in [-1, 0]) — ADVICE r3.
-  const bool rp_ok = !relpos || (flags & GKG_KNN_RELPOS_UNIT);
-  const bool pf = !bf && norm && p.S == 1 && c >= 16 && p.KD <= 36 && !(flags & GKG_KNN_NO_PREFILTER) && rp_ok
-                  && pf_stage <= 150 * 1024 && (pf_pays || (flags & GKG_KNN_FORCE_PREFILTER));
-  size_t lds_q = (size_t)p.cpad * QT * sizeof(float);
-  size_t lds_m = (size_t)NW * p.KD * 64 * 2 * sizeof(float);
-  size_t lds = lds_q > lds_m ? lds_q : lds_m;
-  const bool short_stream = p.tps < 10 * NW;
-  // Selection mode.  Buffered selection (see the kernel) wins where the per-candidate insert dominates and its 32 KB
-  // buffer does not cost occupancy — measured on MI355X (tools/bench_ops.py, direct -> buffered): pvig_m@768 k=18
-  // stage 1 (c=12, kd=18) 15.97 -> 10.61 ms, stage 2 4.46 -> 3.13 ms, stage 3 (c=48, kd=36) 2.59 -> 1.55 ms; pvig_s@576
-  // stage 1 2.52 -> 2.42 ms, stage 2 0.96 -> 0.89 ms, label graph over 20 736 keys 250 -> 214 us; it LOSES with wide groups
-  // (c=200: query tile 51 KB + buffer -> one workgroup per CU, 607 -> 876 us) and on short streams with 9-entry lists
-  // (cfg2 label graph 24.6 -> 31.5 us).  The GKG_KNN_SELECT_DIRECT / _BUFFERED flags override the rule (measurement / tests).
-  const int force = (flags & GKG_KNN_SELECT_BUFFERED) ? 2 : ((flags & GKG_KNN_SELECT_DIRECT) ? 1 : 0);
-  const bool lds_ok = lds_q + (size_t)KNN_BUF * 256 * 8 + NW * 64 * 4 <= 150 * 1024;
-  const bool pays = lds_q <= 24 * 1024 && p.tps >= 2 * NW && (p.tps >= 4 * NW || p.KD >= 18 || p.S > 1);
-  const bool buffered = lds_ok && (force == 2 || (force == 0 && pays));
-  // fp32 contract forms: single-wave workgroups for the narrowest groups (see the launch below)
-  const int nqt_ = (N + QT - 1) / QT;
-  const bool solo32 = buffered && !pf && p.S == 1 && (size_t)nqt_ * BG >= 2048 && lds_q <= 4 * 1024;
-  // Round 5: the buffered fp32 forms also exist with 6 k-pairs per operand batch — channels padded to a multiple of 12 where
-  // that is no more than the multiple of 8 (c = 9..12, 17..24, 33..36, 57..60: pvig_m's groups of 12 and 24).  The workspace was sized
-  // for the wider padding; cpad is only the row count / stride of the prepared copies.
-  {
-    const int c12 = (c + 11) / 12 * 12;
-    if (buffered && !pf && !bf && !mr && !probe_only && p.KD <= 36 && (c12 % 16) != 0 && (c12 < p.cpad || (c12 == p.cpad && (p.cpad % 16) != 0))) {
-      p.cpad = c12;
-      lds_q = (size_t)p.cpad * QT * sizeof(float);
-      lds = lds_q > lds_m ? lds_q : lds_m;
-    }
+  // 16-bit contraction: the normalised copies are octet-major 16-bit planes in the fp32 copies' workspace slots
+  const bool bf = p.el != KNN_EL_F32, hf = p.el == KNN_EL_F16;
+  const bool pq = q.role == KNN_PRODUCE_QUERIES || q.role == KNN_QUERY_PREP_PLAN, pk = q.role == KNN_PRODUCE_KEYS;
+  const PrepSet sx{t.x, xh, sqx, N, strides(N, p.ldx, q.xchunk), p.pf ? xpl : (bf ? (uint16_t*)xh : nullptr), p.pf ? p.cp16p : p.cp16,
+                   p.pf ? xpl_lo : nullptr, p.Nr, pq ? t.raw : nullptr, pq ? t.raw_ld : 0, pq ? t.raw_chunk : 0, nullptr, nullptr};
+  // (a keys producer reads its pre-BN input through `x`)
+  const PrepSet sy{pk ? t.x : t.y, yh, sqy, M, strides(M, G_tm * c, 0), p.pf ? ypl : (bf ? (uint16_t*)yh : nullptr), p.pf ? p.cp16p : p.cp16,
+                   p.pf ? ypl_lo : nullptr, p.Mr, pk ? t.raw : nullptr, pk ? t.raw_ld : 0, pk ? t.raw_chunk : 0, pk ? t.res_tm : nullptr,
+                   pk ? t.nchw : nullptr};
+  if (q.role == KNN_QUERY_PREP_PLAN) { *t.want = KnnQueryPrep{sx, p.cpad, p.norm ? 1 : 0}; return 0; }
+  hipError_t e = hipSuccess;
+  if (const PrepSet* first = p.prep_x ? &sx : (p.prep_y ? &sy : nullptr)) {      // ONE launch for what this call prepares
+    const PrepSet* second = p.prep_x && p.prep_y ? &sy : nullptr;
+    if (q.dtype == GKG_F32) e = launch_prep<float>(*first, second, BG, c, p.cpad, p.norm, st, t.aff, hf);
+    else if (q.dtype == GKG_F16) e = launch_prep<_Float16>(*first, second, BG, c, p.cpad, p.norm, st, t.aff, hf);
+    else e = launch_prep<uint16_t>(*first, second, BG, c, p.cpad, p.norm, st, t.aff, hf);
+    if (e != hipSuccess) return gkg_fail_hip(e, "token_prep");
   }
-  if (mr || probe_only) {
-    const bool ok = !bf && dtype == GKG_F32 && G_tm > 0 && knn_mr_plan_ok(p, c, N, M, k, pf, solo32);
-    if (probe_only) return ok ? 0 : GKG_ERR_UNSUPPORTED;
-    if (!ok) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_knn_mr_fwd_tm: this shape does not take the fused form (gkg_knn_mr_fused_supported)");
-  }
-  uint16_t* xpl = (uint16_t*)(ws + p.off_xp);
-  uint16_t* ypl = (uint16_t*)(ws + p.off_yp);
-  const bool pq = prod && !prod->as_keys, pk = prod && prod->as_keys;
-  const PrepSet sx{x, xh, sqx, N, strides(N, ldx, xchunk), pf ? xpl : (bf ? (uint16_t*)xh : nullptr), pf ? cp16p : cp16,
-                   pf ? xpl + (size_t)BG * Nr * cp16p : nullptr, Nr,
-                   pq ? prod->raw : nullptr, pq ? prod->raw_ld : 0, pq ? prod->raw_chunk : 0, nullptr, nullptr};
-  // (a keys producer reads its pre-BN input through `x`: the presence-only `y` is a dummy there)
-  const PrepSet sy{pk ? x : y, yh, sqy, M, strides(M, G_tm * c, 0), pf ? ypl : (bf ? (uint16_t*)yh : nullptr), pf ? cp16p : cp16,
-                   pf ? ypl + (size_t)BG * Mr * cp16p : nullptr, Mr,
-                   pk ? prod->raw : nullptr, pk ? prod->raw_ld : 0, pk ? prod->raw_chunk : 0, pk ? prod->res_tm : nullptr,
-                   pk ? prod->nchw : nullptr};
-  if (prep_only) {                               // ONE operand (with its BN-apply): the other belongs to its own producer / the k-NN call
-    if (bf) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_bn_apply_knn_prep: not with the bf16 contraction");
-    if (pk && !y) return gkg_fail(GKG_ERR_SHAPE, "gkg_bn_apply_knn_prep: a keys producer needs a k-NN problem with keys");
-    if (prod->want) {
-      if (pk) return gkg_fail(GKG_ERR_UNSUPPORTED, "a producer that runs its own preparation prepares queries only");
-      prod->want->s = sx; prod->want->cpad = p.cpad; prod->want->norm = norm ? 1 : 0;
-      return 0;
-    }
-    e = launch_prep<float>(pk ? sy : sx, nullptr, BG, c, p.cpad, norm, st, prod->aff);
-    return e == hipSuccess ? 0 : gkg_fail_hip(e, "token_prep (BN-apply producer)");
-  }
-  if (x_prepared || y_prepared) {                // copies already in place (gkg_bn_apply_knn_prep): only what is missing
-    if (bf) return gkg_fail(GKG_ERR_UNSUPPORTED, "GKG_KNN_X/Y_PREPARED: not with the bf16 contraction");
-    if (!x_prepared) e = launch_prep<float>(sx, nullptr, BG, c, p.cpad, norm, st);
-    else e = (y && !y_prepared) ? launch_prep<float>(sy, nullptr, BG, c, p.cpad, norm, st) : hipSuccess;
-  }
-  else if (dtype == GKG_F32) e = launch_prep<float>(sx, y ? &sy : nullptr, BG, c, p.cpad, norm, st, PrepAffine{}, hf);
-  else if (dtype == GKG_F16) e = launch_prep<_Float16>(sx, y ? &sy : nullptr, BG, c, p.cpad, norm, st, PrepAffine{}, hf);
-  else e = launch_prep<uint16_t>(sx, y ? &sy : nullptr, BG, c, p.cpad, norm, st, PrepAffine{}, hf);
-  if (e != hipSuccess) return gkg_fail_hip(e, "token_prep");
+  if (pq || pk) return 0;
   gkg_prof_add_work(GKG_PROF_KNN_TILE, 2.0 * BG * (double)c * N * (double)M);    // algorithmic flop of the distance contraction
-  KnnArgs a;
-  a.xh = xh; a.yh = yh; a.sqx = sqx; a.sqy = sqy; a.relpos = relpos;
-  a.nn_idx = nn_idx; a.center = center;
+  KnnArgs a{};
+  a.xh = xh; a.yh = yh; a.sqx = sqx; a.sqy = sqy; a.relpos = t.relpos;
+  a.nn_idx = t.nn_idx; a.center = t.center;
   a.part_v = (float*)(ws + p.off_pv); a.part_i = (int*)(ws + p.off_pi);
-  a.BG = BG; a.cpad = p.cpad; a.N = N; a.M = M; a.k = k; a.dilation = dilation; a.kd = p.kd;
-  a.splits = p.S; a.tiles_per_split = p.tps;
-  a.nqt = (N + QT - 1) / QT;
-  a.xb = (const uint16_t*)xh; a.yb = (const uint16_t*)yh; a.cp16 = cp16;
-  a.xb_lo = a.yb_lo = nullptr; a.margin = 0.f; a.wg_flags = nullptr;
-  a.mr_x = a.mr_src = nullptr; a.mr_out = nullptr; a.mr_arg = nullptr; a.nn16 = nn16_only; a.mr_G = 1; a.mr_c = c;
-  a.mr_ldx = a.mr_lds = c; a.mr_xchunk = a.mr_schunk = 0; a.mr_write_x = 1;
-  dim3 grid((unsigned)(a.nqt * ((BG + 7) / 8) * 8), 1, p.S);
-  a.rp_major = 0; a.rp_group = 1;
-  // bf16 / fp16 form with a positional bias at least twice the size of the keys it meets (64 x 4 B of relative_pos against
-  // 2 x cp16 B of a key per (query tile, key) pair, i.e. c <= 64) and enough query tiles to spread over the XCDs: map the
-  // workgroups relative_pos-major (see the kernel).  Measured (tools/bench_knn_bf.py, us): pvig_m stages 1-2 6031 -> 5101,
-  // 1590 -> 1487; pvig_s stage 1 1259 -> 1187.
-  if (bf && relpos && !pf && a.nqt >= 64 && BG >= 8 && (size_t)QT * 4 >= (size_t)cp16 * 2 * 2) {
-    a.rp_major = 1;
-    grid = dim3((unsigned)(((a.nqt + 7) / 8) * 8 * BG), 1, p.S);
-  }
-  // Exact forms (fp32 tile kernel, prefilter kernel) with a positional bias that is far beyond an L2 (>= 8 MB: GKGNet-576
-  // stage 1: 107 MB, stage 2: 27 MB; pvig_m stage 1: 340 MB): problem-major order streams the WHOLE bias once per problem
-  // (counters, pvig_s stage 1: 7.5 GB of L2 misses per launch at B*G = 64 — the launch ran at the speed of that stream).
-  // Interleave the XCD's problems in groups whose key sets stay in the L2 (<= 2 MB): the bias is fetched once per group.
-  if (relpos && a.rp_major == 0 && p.S == 1 && BG >= 16 && (size_t)N * M * 4 >= ((size_t)8 << 20)) {
-    const size_t key_bytes = (size_t)M * (pf ? (size_t)cp16p * 4 : (size_t)p.cpad * 4);
-    const int bpx = (BG + 7) / 8;
-    int g = (int)(((size_t)2 << 20) / (key_bytes ? key_bytes : 1));
-    g = g > bpx ? bpx : g;
-    while (g >= 2 && bpx % g) --g;               // a divisor of the XCD's problem count: the grid (and the flag array) keep their size
-    if (g >= 2) { a.rp_major = 2; a.rp_group = g; }
-  }
-  if (pf) {
-    a.xb = xpl; a.xb_lo = xpl + (size_t)BG * Nr * cp16p;
-    a.yb = y ? ypl : xpl; a.yb_lo = y ? ypl + (size_t)BG * Mr * cp16p : a.xb_lo;
-    a.cp16 = cp16p; a.pf_c = c; a.pf_nrows = Nr; a.pf_mrows = y ? Mr : Nr;
-    // eps = split terms dropped (3 * 2^-18 * 2 = 2.3e-5) + |y|^2 entering as its two leading bf16 terms (2^-17 |y|^2 <= 7.7e-6)
-    // + fp32 accumulation of the 3c + 2 products and the bias on partial sums <= |bias| + 2 + |y|^2 <= 4.125 (12.4c * 2^-24) +
-    // the contract's own chain (2c * 2^-24): 14.4 c u = 8.6e-7 c; margin = 2 eps
-    a.margin = 2.0f * (4.0e-5f + 9.0e-7f * (float)cp16p);
+  a.BG = BG; a.cpad = p.cpad; a.N = N; a.M = M; a.k = q.k; a.dilation = q.dilation; a.kd = p.kd;
+  a.splits = p.S; a.tiles_per_split = p.tps; a.nqt = p.nqt; a.rp_major = p.rp_major; a.rp_group = p.rp_group;
+  a.xb = (const uint16_t*)xh; a.yb = (const uint16_t*)yh; a.cp16 = p.cp16;
+  a.margin = p.margin; a.nn16 = t.nn16; a.mr_G = 1; a.mr_c = c; a.mr_ldx = a.mr_lds = c; a.mr_write_x = 1;
+  if (p.pf) {
+    a.xb = xpl; a.xb_lo = xpl_lo;
+    a.yb = t.y ? ypl : xpl; a.yb_lo = t.y ? ypl_lo : xpl_lo;
+    a.cp16 = p.cp16p; a.pf_c = c; a.pf_nrows = p.Nr; a.pf_mrows = t.y ? p.Mr : p.Nr;
     a.wg_flags = (int*)(ws + p.off_flags);
-    e = hipMemsetAsync(a.wg_flags, 0, sizeof(int) * (size_t)grid.x, st);
+    e = hipMemsetAsync(a.wg_flags, 0, sizeof(int) * (size_t)p.grid_x, st);
     if (e != hipSuccess) return gkg_fail_hip(e, "knn_pf_kernel (flags)");
-    e = launch_knn_prefilter(a, grid, p.KD, st);
+    e = launch_knn_prefilter(a, p, st);
     if (e != hipSuccess) return gkg_fail_hip(e, "knn_pf_kernel");
-    // fall through: the fp32 tile kernel below runs as the clean-up pass over the tiles the prefilter flagged
+    // the fp32 tile kernel below runs as the clean-up pass over the tiles the prefilter flagged
     // (a.wg_flags != null: every other workgroup exits at once)
   }
-  // enough query tiles to fill the chip with single-wave workgroups (2+ waves per SIMD) and the keys not split: one list per query
-  // (measured, bf16 form, 4 waves -> 1: pvig_s stage 1 1353 -> 1257 us, pvig_m stages 1-3 6661 -> 6051, 1697 -> 1592,
-  // 801 -> 731; it loses when the per-wave query image costs occupancy: stage 2, c = 80, 458 -> 540)
-  const bool solo = p.S == 1 && (size_t)a.nqt * BG >= 2048 && (size_t)QT * (cp16 + 8) * 2 <= 8 * 1024;
-  if (bf) {
-    // bf16 form: the staged query tile is 64 x (cp16 + 8) bf16 — buffered selection with the largest candidate buffer (16 or
-    // 12 entries per lane) that keeps the workgroups per CU the register budget allows
-    const size_t q_bf = (size_t)QT * (cp16 + 8) * 2;
-    const int wgs = relpos ? (p.KD <= 18 ? 3 : 2) : (p.KD <= 12 ? 4 : (p.KD <= 27 ? 3 : 2));
-    const size_t per_wg = (size_t)160 * 1024 / wgs;
-    int wbuf = q_bf + 16 * 2048 + 1024 <= per_wg ? 16 : (q_bf + 12 * 2048 + 1024 <= per_wg ? 12 : 0);
-    const bool pays_bf = p.tps >= 2 * NW && (p.tps >= 4 * NW || p.KD >= 18 || p.S > 1);
-    if (force == 1 || (force == 0 && !pays_bf)) wbuf = 0;
-    if (force == 2 && wbuf == 0) wbuf = 12;
-    e = (hf ? launch_knn_tile_hf : launch_knn_tile_bf)(a, grid, lds, p.KD, wbuf, solo && wbuf > 0, st);
-  } else {
-    // fp32 contract forms: direct (guarded / guard-less for short streams) or buffered selection — gkg_knn_f32.hip
-    // single-wave workgroups for the narrowest groups (pvig_m stage 1: c = 12, 36 864 queries x 2 304 keys, k*d = 18): one list
-    // per query instead of four quarter-stream lists — measured on the model's activations 9 045 -> 7 872 us per launch; no
-    // gain at c = 24 / 48 (2 748 -> 2 761, 1 225 -> 1 238 us), where the per-wave query image costs occupancy
-    if (mr) {
-      a.mr_x = (const float*)x; a.mr_src = (const float*)(y ? y : x);
-      a.mr_out = mr->out; a.mr_arg = mr->arg; a.nn16 = mr->nn16; a.mr_G = G_tm; a.mr_c = c;
-      a.mr_ldx = ldx; a.mr_xchunk = xchunk;
-      a.mr_lds = y ? G_tm * c : ldx; a.mr_schunk = y ? 0 : xchunk;
-      // x already lives in the operand buffer when the caller passes that buffer's x half as the view of x
-      a.mr_write_x = !((const void*)x == (const void*)mr->out && ldx == 2 * G_tm * c && xchunk == (G_tm * c) / 4);
-      e = launch_knn_tile_f32_mr(a, grid, lds, p.KD, buffered ? 2 : ((short_stream && p.KD == 9) ? 1 : 0), st);
-    } else {
-      e = launch_knn_tile_f32(a, grid, lds, p.KD, solo32 ? 5 : (buffered ? 2 : ((short_stream && p.KD == 9) ? 1 : 0)), st);
-    }
+  if (q.role == KNN_FUSED) {
+    a.mr_x = (const float*)t.x; a.mr_src = (const float*)(t.y ? t.y : t.x);
+    a.mr_out = t.mr_out; a.mr_arg = t.mr_arg; a.mr_G = G_tm; a.mr_c = c;
+    a.mr_ldx = p.ldx; a.mr_xchunk = q.xchunk;
+    a.mr_lds = t.y ? G_tm * c : p.ldx; a.mr_schunk = t.y ? 0 : q.xchunk;
+    // x already lives in the operand buffer when the caller passes that buffer's x half as the view of x
+    a.mr_write_x = !((const void*)t.x == (const void*)t.mr_out && p.ldx == 2 * G_tm * c && q.xchunk == (G_tm * c) / 4);
   }
+  e = (hf ? launch_knn_tile_hf : (bf ? launch_knn_tile_bf : (p.mrf ? launch_knn_tile_f32_mr : launch_knn_tile_f32)))(a, p, st);
   if (e != hipSuccess) return gkg_fail_hip(e, "knn_tile_kernel");
   if (p.S > 1) {
     const size_t ne = (size_t)BG * N * p.kd * p.S;
     GkgProfScope prof(GKG_PROF_KNN_MERGE, st);
     // ranks that no finite candidate claims (non-finite inputs only) must still hold a valid index
-    if (nn16_only) (void)hipMemsetAsync(nn16_only, 0, sizeof(uint16_t) * (size_t)BG * N * k, st);
-    else (void)hipMemsetAsync(nn_idx, 0, sizeof(int64_t) * (size_t)BG * N * k, st);
+    if (t.nn16) (void)hipMemsetAsync(t.nn16, 0, sizeof(uint16_t) * (size_t)BG * N * q.k, st);
+    else (void)hipMemsetAsync(t.nn_idx, 0, sizeof(int64_t) * (size_t)BG * N * q.k, st);
     hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, a.part_v, a.part_i,
-                       nn_idx, center, nn16_only, p.S, BG, N, M, k, dilation, p.kd);
+                       t.nn_idx, t.center, t.nn16, p.S, BG, N, M, q.k, q.dilation, p.kd);
     e = hipGetLastError();
     if (e != hipSuccess) return gkg_fail_hip(e, "knn_merge_kernel");
   }
@@ -524,16 +298,17 @@ static int knn_fwd_impl(const void* x, const void* y, const float* relpos, int64
 extern "C" int gkg_knn_fwd(const void* x, const void* y, const float* relpos, int64_t* nn_idx, int64_t* center,
                            int BG, int c, int N, int M, int k, int dilation, int dtype, unsigned flags,
                            void* workspace, size_t workspace_bytes, void* stream) {
-  return knn_fwd_impl(x, y, relpos, nn_idx, center, BG, c, N, M, k, dilation, dtype, flags, workspace, workspace_bytes,
-                      stream, 0);
+  KnnCall q = knn_call_tm(KNN_GRAPH, BG, 1, c, N, M, k, dilation, dtype, flags, y != nullptr, relpos != nullptr, 0, 0);
+  q.G_tm = 0;                                    // channel-major (BG, c, T)
+  return knn_fwd_impl(q, KnnPtrs{x, y, relpos, nn_idx, center, nullptr, workspace, workspace_bytes, stream});
 }
 
 extern "C" int gkg_knn_fwd_tm(const void* x, int ldx, int xchunk, const void* y, const float* relpos, int64_t* nn_idx, int64_t* center,
                               int B, int G, int c, int N, int M, int k, int dilation, int dtype, unsigned flags,
                               void* workspace, size_t workspace_bytes, void* stream) {
   if (B <= 0 || G <= 0) return gkg_fail(GKG_ERR_SHAPE, "gkg_knn_fwd_tm: bad B / G");
-  return knn_fwd_impl(x, y, relpos, nn_idx, center, B * G, c, N, M, k, dilation, dtype, flags, workspace, workspace_bytes,
-                      stream, G, nullptr, false, nullptr, ldx, xchunk);
+  return knn_fwd_impl(knn_call_tm(KNN_GRAPH, B, G, c, N, M, k, dilation, dtype, flags, y != nullptr, relpos != nullptr, ldx, xchunk),
+                      KnnPtrs{x, y, relpos, nn_idx, center, nullptr, workspace, workspace_bytes, stream});
 }
 
 // The same graph as gkg_knn_fwd_tm with COMPACT neighbour lists: nn16 (B * G, N, k) u16 rows instead of the (2, B G, N, k) int64
@@ -545,8 +320,8 @@ extern "C" int gkg_knn_fwd_tm16(const void* x, int ldx, int xchunk, const void* 
   if (B <= 0 || G <= 0) return gkg_fail(GKG_ERR_SHAPE, "gkg_knn_fwd_tm16: bad B / G");
   if (!nn16) return gkg_fail(GKG_ERR_NULL, "gkg_knn_fwd_tm16: nn16 must be non-null");
   if (M > 65536) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_knn_fwd_tm16: M <= 65536 (u16 rows)");
-  return knn_fwd_impl(x, y, relpos, nullptr, nullptr, B * G, c, N, M, k, dilation, dtype, flags, workspace, workspace_bytes,
-                      stream, G, nullptr, false, nn16, ldx, xchunk);
+  return knn_fwd_impl(knn_call_tm(KNN_GRAPH, B, G, c, N, M, k, dilation, dtype, flags, y != nullptr, relpos != nullptr, ldx, xchunk),
+                      KnnPtrs{x, y, relpos, nullptr, nullptr, nn16, workspace, workspace_bytes, stream});
 }
 
 // Row g2: k-NN + max-relative aggregation in one kernel (knn_tile_kernel<..., MRF = true>) for token-major fp32 callers.
@@ -559,9 +334,11 @@ extern "C" int gkg_knn_fwd_tm16(const void* x, int ldx, int xchunk, const void* 
 extern "C" int gkg_knn_mr_fused_supported(int B, int G, int c, int N, int M, int k, int dilation, int has_y, int has_relpos,
                                           unsigned flags) {
   if (B <= 0 || G <= 0 || c <= 0 || ((G * c) & 15)) return 0;
-  static const float dummy = 0.f;
-  return knn_fwd_impl(nullptr, has_y ? &dummy : nullptr, has_relpos ? &dummy : nullptr, nullptr, nullptr, B * G, c, N, M, k,
-                      dilation, GKG_F32, flags, nullptr, 0, nullptr, G, nullptr, true) == 0 ? 1 : 0;
+  KnnPlan p;
+  const char* msg;
+  const int rc = knn_plan(knn_call_tm(KNN_FUSED_PROBE, B, G, c, N, M, k, dilation, GKG_F32, flags, has_y != 0, has_relpos != 0, 0, 0), &p, &msg);
+  if (rc != 0 && msg) gkg_fail(rc, msg);
+  return rc == 0 ? 1 : 0;
 }
 
 extern "C" int gkg_knn_mr_fwd_tm(const float* x, int ldx, int xchunk, const float* y, const float* relpos, float* xm_out,
@@ -575,12 +352,10 @@ extern "C" int gkg_knn_mr_fwd_tm(const float* x, int ldx, int xchunk, const floa
     return gkg_fail(GKG_ERR_SHAPE, "gkg_knn_mr_fwd_tm: 16-byte aligned rows");
   if ((const void*)x == (const void*)xm_out && !(ldx == 2 * G * c && xchunk == (G * c) / 4))
     return gkg_fail(GKG_ERR_SHAPE, "gkg_knn_mr_fwd_tm: x aliases xm_out but is not its x half (ldx = 2 C, xchunk = C / 4)");
-  const KnnMrFuse mr{xm_out, arg_out, nn16_out};
   if (center_out && !nn_idx_out) return gkg_fail(GKG_ERR_NULL, "gkg_knn_mr_fwd_tm: center_out without nn_idx_out");
-  return knn_fwd_impl(x, y, relpos, nn_idx_out, center_out, B * G, c, N, M, k, dilation, GKG_F32, flags, workspace, workspace_bytes,
-                      stream, G, &mr, false, nullptr, ldx, xchunk);
+  return knn_fwd_impl(knn_call_tm(KNN_FUSED, B, G, c, N, M, k, dilation, GKG_F32, flags, y != nullptr, relpos != nullptr, ldx, xchunk),
+                      KnnPtrs{x, y, relpos, nn_idx_out, center_out, nn16_out, workspace, workspace_bytes, stream, xm_out, arg_out});
 }
-
 
 // The Grapher's fc1 BN-apply (train mode, statistics from the projection's fp64 column sums: gkg_bn_apply_train's contract with
 // nb == 1, act == 0, no residual) and the k-NN's token preparation of the SAME tokens in one pass (round 6):
@@ -607,15 +382,12 @@ static int bn_apply_knn_prep_impl(const float* y, const double* sums, const floa
   if (ldo < C || (ldo & 3) || ochunk < 0 || (ochunk & 3) || (ochunk > 0 && (C % ochunk || ldo < 2 * C)) || ((size_t)out & 15) || ((size_t)y & 15) ||
       (zero_doubles && !zero_buf))
     return gkg_fail(GKG_ERR_SHAPE, "gkg_bn_apply_knn_prep: bad output view");
-  KnnProducer prod{};
-  prod.aff.d = BnDerive{sums, gamma, beta, bias, running_mean, running_var, num_batches_tracked, a, c_out, mean, invstd,
-                        B * (as_keys ? M : N), momentum, eps, zero_buf, zero_doubles, count, count_out};
-  prod.raw = out; prod.raw_ld = ldo; prod.raw_chunk = ochunk;
-  prod.as_keys = as_keys ? 1 : 0; prod.res_tm = res_tm; prod.nchw = out_nchw;
-  static const float dummy = 0.f;
-  static KnnMrFuse mr_dummy{nullptr, nullptr, nullptr};
-  return knn_fwd_impl(y, has_y ? &dummy : nullptr, has_relpos ? &dummy : nullptr, nullptr, nullptr, B * G, c, N, M, k, dilation, GKG_F32,
-                      knn_flags, knn_workspace, knn_workspace_bytes, stream, G, fused_mr ? &mr_dummy : nullptr, false, nullptr, 0, 0, &prod);
+  KnnPtrs t{y, nullptr, nullptr, nullptr, nullptr, nullptr, knn_workspace, knn_workspace_bytes, stream};
+  t.aff.d = BnDerive{sums, gamma, beta, bias, running_mean, running_var, num_batches_tracked, a, c_out, mean, invstd,
+                     B * (as_keys ? M : N), momentum, eps, zero_buf, zero_doubles, count, count_out};
+  t.raw = out; t.raw_ld = ldo; t.raw_chunk = ochunk; t.res_tm = res_tm; t.nchw = out_nchw;
+  return knn_fwd_impl(knn_call_tm(as_keys ? KNN_PRODUCE_KEYS : KNN_PRODUCE_QUERIES, B, G, c, N, M, k, dilation, GKG_F32, knn_flags, has_y != 0,
+                                  has_relpos != 0, 0, 0, fused_mr != 0), t);
 }
 
 extern "C" int gkg_bn_apply_knn_prep(const float* y, const double* sums, const float* gamma, const float* beta, const float* bias,
@@ -648,16 +420,13 @@ extern "C" int gkg_bn_apply_knn_prep_sync(const float* y, const double* sums, co
 }
 
 // gkg_knn_prep.h: the queries' preparation plan for a producer that prepares tokens it has just written to `tokens` (B N rows of
-// pitch ld floats) inside its own kernel.  Goes through knn_fwd_impl like every producer: same plan, same decisions, no launch.
+// pitch ld floats) inside its own kernel.  The plan of the k-NN call that follows (knn_plan, role KNN_QUERY_PREP_PLAN), no launch.
 int gkg::knn_query_prep_plan(const float* tokens, int ld, int B, int G, int c, int N, int M, int k, int dilation, int has_y, int has_relpos,
                         unsigned knn_flags, int fused_mr, void* knn_workspace, size_t knn_workspace_bytes, KnnQueryPrep* plan) {
-  KnnProducer prod{};
-  prod.want = plan;
-  static const float dummy = 0.f;
-  static KnnMrFuse mr_dummy{nullptr, nullptr, nullptr};
-  return knn_fwd_impl(tokens, has_y ? &dummy : nullptr, has_relpos ? &dummy : nullptr, nullptr, nullptr, B * G, c, N, M, k, dilation,
-                      GKG_F32, knn_flags, knn_workspace, knn_workspace_bytes, nullptr, G, fused_mr ? &mr_dummy : nullptr, false, nullptr,
-                      ld, 0, &prod);
+  KnnPtrs t{tokens, nullptr, nullptr, nullptr, nullptr, nullptr, knn_workspace, knn_workspace_bytes};
+  t.want = plan;
+  return knn_fwd_impl(knn_call_tm(KNN_QUERY_PREP_PLAN, B, G, c, N, M, k, dilation, GKG_F32, knn_flags, has_y != 0, has_relpos != 0, ld, 0,
+                                  fused_mr != 0), t);
 }
 
 // The same pass behind an eval-mode (frozen) BatchNorm: the caller passes the folded scale / shift (gkg_bn_eval_affine) instead of
@@ -676,12 +445,9 @@ extern "C" int gkg_affine_knn_prep(const float* y, const float* a, const float* 
   if (ldo == 0) ldo = C;
   if (ldo < C || (ldo & 3) || ochunk < 0 || (ochunk & 3) || (ochunk > 0 && (C % ochunk || ldo < 2 * C)) || ((size_t)out & 15) || ((size_t)y & 15))
     return gkg_fail(GKG_ERR_SHAPE, "gkg_affine_knn_prep: bad output view");
-  KnnProducer prod{};                              // aff.d.sums == null: the table is copied from a / c
-  prod.aff.a = a; prod.aff.c = c_in;
-  prod.raw = out; prod.raw_ld = ldo; prod.raw_chunk = ochunk;
-  prod.as_keys = as_keys ? 1 : 0; prod.res_tm = res_tm; prod.nchw = out_nchw;
-  static const float dummy = 0.f;
-  static KnnMrFuse mr_dummy{nullptr, nullptr, nullptr};
-  return knn_fwd_impl(y, has_y ? &dummy : nullptr, has_relpos ? &dummy : nullptr, nullptr, nullptr, B * G, c, N, M, k, dilation, GKG_F32,
-                      knn_flags, knn_workspace, knn_workspace_bytes, stream, G, fused_mr ? &mr_dummy : nullptr, false, nullptr, 0, 0, &prod);
+  KnnPtrs t{y, nullptr, nullptr, nullptr, nullptr, nullptr, knn_workspace, knn_workspace_bytes, stream};
+  t.aff.a = a; t.aff.c = c_in;                     // aff.d.sums == null: the table is copied from a / c
+  t.raw = out; t.raw_ld = ldo; t.raw_chunk = ochunk; t.res_tm = res_tm; t.nchw = out_nchw;
+  return knn_fwd_impl(knn_call_tm(as_keys ? KNN_PRODUCE_KEYS : KNN_PRODUCE_QUERIES, B, G, c, N, M, k, dilation, GKG_F32, knn_flags, has_y != 0,
+                                  has_relpos != 0, 0, 0, fused_mr != 0), t);
 }

@@ -8,62 +8,28 @@ using namespace gkg;
 
 #ifndef GKG_KNN_EL_PART
 #define GKG_KNN_EL_PART KNN_EL_BF16
-#define GKG_KNN_EL_NAME(base) base##_bf
-#define GKG_KNN_EL_NAME_NORP(base) base##_bf_norp
+#define GKG_KNN_EL_LAUNCHER launch_knn_tile_bf
 #endif
 
-// 16-bit matrix-core contraction (GKG_KNN_BF16_CONTRACT / GKG_KNN_F16_CONTRACT): direct or buffered selection, guarded insert
-// HAS_RP is a compile-time parameter of the launcher: the relative_pos forms are instantiated in this translation unit, the
-// others in gkg_knn_bf_norp.hip (the same source with GKG_KNN_NORP_PART defined).
+// 16-bit matrix-core contraction (GKG_KNN_BF16_CONTRACT / GKG_KNN_F16_CONTRACT), KU 4.  The forms this unit holds, by the plan's
+// fields: direct selection with the guard (every list size); lists up to 36: buffered with 12 entries per lane, with KNN_BUF (lists
+// above 12), and one wave per 64-query tile (see the kernel's NWV) with 12 (9-entry list) or KNN_BUF entries.  Why each: knn_plan.
+// (The forms without a bias: gkg_knn_bf_norp.hip, the same source with GKG_KNN_NORP_PART defined.)
 template <int KD, bool HAS_RP>
-static hipError_t launch_tile_bf(const KnnArgs& a, dim3 grid, size_t lds, hipStream_t st, int wbuf, bool solo) {
+static hipError_t launch_tile_bf(const KnnArgs& a, const KnnPlan& p, hipStream_t st) {
   constexpr int EL = GKG_KNN_EL_PART;
-  const bool buffered = wbuf > 0 && KD <= 36;   // 64-entry lists: direct insert only (the buffered forms spilled to scratch)
   GkgProfScope prof(GKG_PROF_KNN_TILE, st);
+  if (p.el != EL || p.ku != 4 || p.mrf) return hipErrorInvalidValue;
   if constexpr (KD <= 36) {
-  if (buffered && solo) {                       // one wave per 64-query tile, all keys (see the kernel's NWV)
-    // 9-entry lists: 12-entry candidate buffers (flush when a lane holds more than 4) — with one short list per query the
-    // fresher threshold is worth more than fuller flushes (cfg3 forward, k-NN kernels 5.08 -> 4.90 ms); longer lists keep
-    // 16 (cfg5, k*d = 18 / 36: 29.8 -> 33.2 ms with 12).  Measured on the models' own activations: random tokens
-    // (tools/bench_knn_bf.py) rank the two the other way round for k*d = 18.
     constexpr int SBUF = KD <= 12 ? 12 : KNN_BUF;
-    return launch_tile_v<KD, HAS_RP, 4, false, SBUF, EL, 1>(a, grid, lds, st);
-  }
-  if (buffered) {
-    // 9-entry lists: 12 entries per lane (fresher thresholds); longer lists: 16, or 12 where 16 would cost a workgroup per CU
-    if (KD <= 12 || wbuf < 16) {
-      return launch_tile_v<KD, HAS_RP, 4, false, 12, EL>(a, grid, lds, st);
-    }
+    if (!p.guard && p.waves == 1 && p.buf == SBUF) return launch_tile_v<KD, HAS_RP, 4, false, SBUF, EL, 1>(a, p, st);
+    if (!p.guard && p.waves == NW && p.buf == 12) return launch_tile_v<KD, HAS_RP, 4, false, 12, EL>(a, p, st);
     if constexpr (KD > 12) {
-      return launch_tile_v<KD, HAS_RP, 4, false, KNN_BUF, EL>(a, grid, lds, st);
+      if (!p.guard && p.waves == NW && p.buf == KNN_BUF) return launch_tile_v<KD, HAS_RP, 4, false, KNN_BUF, EL>(a, p, st);
     }
   }
-  }   // KD <= 36
-  return launch_tile_v<KD, HAS_RP, 4, true, 0, EL>(a, grid, lds, st);
+  if (p.guard && p.waves == NW && p.buf == 0) return launch_tile_v<KD, HAS_RP, 4, true, 0, EL>(a, p, st);
+  return hipErrorInvalidValue;
 }
 
-namespace gkg {
-#ifdef GKG_KNN_NORP_PART
-hipError_t GKG_KNN_EL_NAME_NORP(launch_knn_tile)(const KnnArgs& a, dim3 grid, size_t lds, int KD, int wbuf, bool solo, hipStream_t st) {
-  switch (KD) {
-    case 9: return launch_tile_bf<9, false>(a, grid, lds, st, wbuf, solo);
-    case 18: return launch_tile_bf<18, false>(a, grid, lds, st, wbuf, solo);
-    case 27: return launch_tile_bf<27, false>(a, grid, lds, st, wbuf, solo);
-    case 36: return launch_tile_bf<36, false>(a, grid, lds, st, wbuf, solo);
-    default: return launch_tile_bf<64, false>(a, grid, lds, st, wbuf, solo);
-  }
-}
-#else
-hipError_t GKG_KNN_EL_NAME_NORP(launch_knn_tile)(const KnnArgs& a, dim3 grid, size_t lds, int KD, int wbuf, bool solo, hipStream_t st);
-hipError_t GKG_KNN_EL_NAME(launch_knn_tile)(const KnnArgs& a, dim3 grid, size_t lds, int KD, int wbuf, bool solo, hipStream_t st) {
-  if (!a.relpos) return GKG_KNN_EL_NAME_NORP(launch_knn_tile)(a, grid, lds, KD, wbuf, solo, st);
-  switch (KD) {
-    case 9: return launch_tile_bf<9, true>(a, grid, lds, st, wbuf, solo);
-    case 18: return launch_tile_bf<18, true>(a, grid, lds, st, wbuf, solo);
-    case 27: return launch_tile_bf<27, true>(a, grid, lds, st, wbuf, solo);
-    case 36: return launch_tile_bf<36, true>(a, grid, lds, st, wbuf, solo);
-    default: return launch_tile_bf<64, true>(a, grid, lds, st, wbuf, solo);
-  }
-}
-#endif
-}  // namespace gkg
+GKG_KNN_LAUNCHER(GKG_KNN_EL_LAUNCHER, launch_tile_bf, 64)

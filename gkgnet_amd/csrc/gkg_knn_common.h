@@ -5,14 +5,11 @@
 #include <stdint.h>
 
 #include "gkg_common.h"
+#include "gkg_knn_plan.h"      // geometry constants (QT, KT, NW, IDX_BITS, KNN_BUF, list sizes) and the launch plan
 
 namespace gkg {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int QT = 64;   // queries per workgroup (one per lane)
-constexpr int KT = 32;   // keys per MFMA tile
-constexpr int NW = 4;    // waves per workgroup
 
 // ------------------------------------------------------------------------------------------ top-KD list
 // Sorted ascending.  A list entry is ONE fp64 key that orders exactly like the pair (distance, key index): the fp32
@@ -26,7 +23,6 @@ constexpr int NW = 4;    // waves per workgroup
 // the list untouched, exactly like the strict '<' of a scalar insert.  Keys past M are masked with a large FINITE
 // |y|^2 (MASKED_SQ) instead of +inf; they can only surface when fewer than k*d real candidates exist at all, and the
 // output stage keeps indices in range for that case.  (A distance is never -0.0: |x|^2 >= +0 heads the sum.)
-constexpr uint32_t IDX_BITS = 0x1fffffffu;          // 29 bits: key index < 2^29
 constexpr float MASKED_SQ = 3.0e38f;
 
 __device__ __forceinline__ double pack_key(float d, int m) {
@@ -159,15 +155,48 @@ __device__ __forceinline__ bool knn_map(const KnnArgs& a, int lin, int& bg, int&
   return bg < a.BG && qt < nqt;
 }
 
-// gkg_knn_pf.hip: launches knn_pf_kernel for list size KD (9, 16, 18, 27 or 36)
-hipError_t launch_knn_prefilter(const KnnArgs& a, dim3 grid, int KD, hipStream_t st);
-// gkg_knn_bf.hip: the tile kernel's bf16-contraction forms (direct / buffered selection; solo: one wave per query tile)
-hipError_t launch_knn_tile_bf(const KnnArgs& a, dim3 grid, size_t lds, int KD, int wbuf, bool solo, hipStream_t st);
-// gkg_knn_hf.hip: the same forms with the fp16 contraction (xb / yb hold fp16 planes)
-hipError_t launch_knn_tile_hf(const KnnArgs& a, dim3 grid, size_t lds, int KD, int wbuf, bool solo, hipStream_t st);
-// gkg_knn_f32.hip: the tile kernel's fp32-contract forms (mode 0 direct + guard, 1 direct without it, 2 buffered)
-hipError_t launch_knn_tile_f32(const KnnArgs& a, dim3 grid, size_t lds, int KD, int mode, hipStream_t st);
-// gkg_knn_f32_mr.hip: the same forms with the max-relative aggregation in the epilogue (modes 0-2, lists up to 36 entries)
-hipError_t launch_knn_tile_f32_mr(const KnnArgs& a, dim3 grid, size_t lds, int KD, int mode, hipStream_t st);
+// The per-unit launchers: switchboards from the plan's form fields (gkg_knn_plan.h) to the instantiations their translation unit
+// holds; a form the unit does not instantiate is hipErrorInvalidValue.  Grid (p.grid_x, 1, p.S), LDS p.lds_pf / p.lds_tile.
+hipError_t launch_knn_prefilter(const KnnArgs& a, const KnnPlan& p, hipStream_t st);      // gkg_knn_pf.hip: knn_pf_kernel
+hipError_t launch_knn_tile_bf(const KnnArgs& a, const KnnPlan& p, hipStream_t st);        // gkg_knn_bf.hip: bf16-contraction forms
+hipError_t launch_knn_tile_hf(const KnnArgs& a, const KnnPlan& p, hipStream_t st);        // gkg_knn_hf.hip: fp16-contraction forms
+hipError_t launch_knn_tile_f32(const KnnArgs& a, const KnnPlan& p, hipStream_t st);       // gkg_knn_f32.hip: fp32-contract forms
+hipError_t launch_knn_tile_f32_mr(const KnnArgs& a, const KnnPlan& p, hipStream_t st);    // gkg_knn_f32_mr.hip: + aggregation epilogue
+
+// One launch of a k-NN kernel with the plan's dynamic LDS size
+static inline hipError_t knn_launch(void (*kernel)(KnnArgs), dim3 grid, int threads, size_t lds, hipStream_t st, const KnnArgs& a) {
+  if (lds > 64 * 1024) {
+    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (ea != hipSuccess) return ea;
+  }
+  hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, st, a);
+  return hipGetLastError();
+}
+
+// Every launcher is compiled as two units: NAME (forms with a positional bias; hands the others on) and, the same source with
+// GKG_KNN_NORP_PART defined, NAME_norp, so that they compile in parallel.  FORM<KD, HAS_RP>(a, p, st) is the unit's switchboard for
+// one list size (up to MAXKD).  Used at global scope.
+#define GKG_KNN_CAT(a, b) a##b
+#define GKG_KNN_LAUNCHER(NAME, FORM, MAXKD) GKG_KNN_LAUNCHER_(NAME, GKG_KNN_CAT(NAME, _norp), FORM, MAXKD)
+#define GKG_KNN_BY_LIST(FORM, MAXKD, RP)                                                     \
+  switch (p.KD) {                                                                            \
+    case 9: return FORM<9, RP>(a, p, st);                                                    \
+    case 18: return FORM<18, RP>(a, p, st);                                                  \
+    case 27: return FORM<27, RP>(a, p, st);                                                  \
+    case 36: return FORM<36, RP>(a, p, st);                                                  \
+    case 64: if (MAXKD >= 64) return FORM<(MAXKD >= 64 ? 64 : 36), RP>(a, p, st);           \
+    default: return hipErrorInvalidValue;                                                    \
+  }
+#ifdef GKG_KNN_NORP_PART
+#define GKG_KNN_LAUNCHER_(NAME, NORP, FORM, MAXKD) \
+  namespace gkg { hipError_t NORP(const KnnArgs& a, const KnnPlan& p, hipStream_t st) { GKG_KNN_BY_LIST(FORM, MAXKD, false) } }
+#else
+#define GKG_KNN_LAUNCHER_(NAME, NORP, FORM, MAXKD)                                     \
+  namespace gkg { hipError_t NORP(const KnnArgs& a, const KnnPlan& p, hipStream_t st); } \
+  hipError_t gkg::NAME(const KnnArgs& a, const KnnPlan& p, hipStream_t st) {             \
+    if (!a.relpos) return NORP(a, p, st);                                                \
+    GKG_KNN_BY_LIST(FORM, MAXKD, true)                                                   \
+  }
+#endif
 
 }  // namespace gkg

@@ -2,6 +2,5 @@
 // gkg_knn_bf_norp.hip, compiled beside them.
 #define GKG_KNN_NORP_PART 1
 #define GKG_KNN_EL_PART KNN_EL_F16
-#define GKG_KNN_EL_NAME(base) base##_hf
-#define GKG_KNN_EL_NAME_NORP(base) base##_hf_norp
+#define GKG_KNN_EL_LAUNCHER launch_knn_tile_hf
 #include "gkg_knn_bf.hip"

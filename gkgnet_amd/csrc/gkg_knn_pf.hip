@@ -35,7 +35,7 @@ namespace gkg {
 // ~1 300 workgroups that exit on their first instruction; on degenerate data the cost is bounded by prefilter + plain
 // kernel.  (An in-lane exact re-scan of all M keys was the first form of this fallback: one degenerate block of the
 // random-init GKGNet-576 train step took 6.9 ms instead of 0.45.)
-constexpr int PF_EXTRA = 8;       // survivors beyond KD a query may have before it takes the slow path
+// (PF_EXTRA, gkg_knn_plan.h: survivors beyond KD a query may have before it takes the slow path)
 
 // The contract's distance (without relative_pos) of query n and key m from the fp32 channel-major normalised copies: the
 // ordered fmaf chain over the cpad (zero-padded) channels with the query pre-scaled by -2 — what knn_tile_kernel's fp32
@@ -504,59 +504,26 @@ __global__ __launch_bounds__(256, KDW <= 16 ? 3 : 2) void knn_pf_kernel(KnnArgs 
 
 using namespace gkg;
 
-// prefilter + exact re-rank (knn_pf_kernel): un-split, normalised, fp32-contract problems
-template <int KD, int KDW, bool HAS_RP, int PBUF, bool SB = false>
-static hipError_t launch_pf_v(const KnnArgs& a, dim3 grid, size_t lds, hipStream_t st) {
-  if constexpr (KDW <= 16 && HAS_RP && !SB) {                     // single-batch form (see the kernel): narrow groups
-    if (a.cp16 <= 64) return launch_pf_v<KD, KDW, HAS_RP, PBUF, true>(a, grid, lds, st);
+// prefilter + exact re-rank (knn_pf_kernel): un-split, normalised, fp32-contract problems.  Grid and LDS size are the plan's (knn_pf_lds).
+// The forms this unit holds: candidate buffers of 16 / 12 / 0 entries, each also as the single-batch form (see the kernel) for lists
+// up to 16 entries with a bias (the forms without a bias: gkg_knn_pf_norp.hip, the same source with GKG_KNN_NORP_PART defined).
+template <int KD, int KDW, bool HAS_RP, int PBUF>
+static hipError_t launch_pf_v(const KnnArgs& a, const KnnPlan& p, hipStream_t st) {
+  if constexpr (KDW <= 16 && HAS_RP) {
+    if (p.pf_sb) return knn_launch(&knn_pf_kernel<KD, KDW, HAS_RP, PBUF, true>, dim3(p.grid_x), 256, p.lds_pf, st, a);
   }
-  if (lds > 64 * 1024) {
-    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&knn_pf_kernel<KD, KDW, HAS_RP, PBUF, SB>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (ea != hipSuccess) return ea;
-  }
-  hipLaunchKernelGGL((knn_pf_kernel<KD, KDW, HAS_RP, PBUF, SB>), grid, dim3(256), lds, st, a);
-  return hipGetLastError();
+  return p.pf_sb ? hipErrorInvalidValue : knn_launch(&knn_pf_kernel<KD, KDW, HAS_RP, PBUF, false>, dim3(p.grid_x), 256, p.lds_pf, st, a);
 }
 
-// HAS_RP is a compile-time parameter of the launcher: the relative_pos forms are instantiated in this translation unit,
-// the others in gkg_knn_pf_norp.hip (the same source with GKG_KNN_NORP_PART defined), so that they compile in parallel.
-template <int KD, int KDW, bool HAS_RP>
-static hipError_t launch_pf(const KnnArgs& a, dim3 grid, hipStream_t st) {
+template <int KD, bool HAS_RP>
+static hipError_t launch_pf(const KnnArgs& a, const KnnPlan& p, hipStream_t st) {
+  constexpr int KDW = KD <= 9 ? 12 : KD;         // KDW exceeds KD for the short list (see the kernel)
   GkgProfScope prof(GKG_PROF_KNN_TILE, st);
-  const size_t stage = (size_t)2 * QT * (a.cp16 + 8) * 2;
-  const size_t lists = (size_t)2 * NW * KDW * 64 * 4 + (size_t)(KD + PF_EXTRA) * 64 * (4 + 2) + 64 * 4 + 16;
-  // buffered selection with the largest candidate buffer (16 or 12 entries per lane: 32 / 24 KiB) that keeps the
-  // workgroups per CU the register budget allows (3 for lists <= 16, 2 above)
-  const size_t per_wg = (size_t)160 * 1024 / (KDW <= 16 ? 3 : 2);
-  const int pbuf = stage + 16 * 2048 <= per_wg ? 16 : (stage + 12 * 2048 <= per_wg ? 12 : 0);
-  const size_t need = stage + (size_t)pbuf * 2048 + (pbuf ? NW * 64 * sizeof(float) : 0);      // + the shared admission bounds
-  const size_t lds = need > lists ? need : lists;
-  if (pbuf == 16) return launch_pf_v<KD, KDW, HAS_RP, 16>(a, grid, lds, st);
-  if (pbuf == 12) return launch_pf_v<KD, KDW, HAS_RP, 12>(a, grid, lds, st);
-  return launch_pf_v<KD, KDW, HAS_RP, 0>(a, grid, lds, st);
+  if (p.pf_kdw != KDW) return hipErrorInvalidValue;
+  if (p.pf_buf == 16) return launch_pf_v<KD, KDW, HAS_RP, 16>(a, p, st);
+  if (p.pf_buf == 12) return launch_pf_v<KD, KDW, HAS_RP, 12>(a, p, st);
+  if (p.pf_buf == 0) return launch_pf_v<KD, KDW, HAS_RP, 0>(a, p, st);
+  return hipErrorInvalidValue;
 }
 
-namespace gkg {
-#ifdef GKG_KNN_NORP_PART
-hipError_t launch_knn_prefilter_norp(const KnnArgs& a, dim3 grid, int KD, hipStream_t st) {
-  switch (KD) {
-    case 9: return launch_pf<9, 12, false>(a, grid, st);
-    case 18: return launch_pf<18, 18, false>(a, grid, st);
-    case 27: return launch_pf<27, 27, false>(a, grid, st);
-    default: return launch_pf<36, 36, false>(a, grid, st);
-  }
-}
-#else
-hipError_t launch_knn_prefilter_norp(const KnnArgs& a, dim3 grid, int KD, hipStream_t st);
-hipError_t launch_knn_prefilter(const KnnArgs& a, dim3 grid, int KD, hipStream_t st) {
-  if (!a.relpos) return launch_knn_prefilter_norp(a, grid, KD, st);
-  switch (KD) {
-    case 9: return launch_pf<9, 12, true>(a, grid, st);
-    case 18: return launch_pf<18, 18, true>(a, grid, st);
-    case 27: return launch_pf<27, 27, true>(a, grid, st);
-    default: return launch_pf<36, 36, true>(a, grid, st);
-  }
-}
-#endif
-}  // namespace gkg
+GKG_KNN_LAUNCHER(launch_knn_prefilter, launch_pf, 36)

@@ -474,7 +474,7 @@ __device__ __forceinline__ void token_prep_flat_rows(const PrepSet& S, float* co
   }
 }
 
-// What a producer that runs the queries' preparation inside its own kernel needs of the k-NN call's plan (knn_fwd_impl, the one
+// What a producer that runs the queries' preparation inside its own kernel needs of the k-NN call's plan (knn_plan, gkg_knn_plan.h: the one
 // place that makes it): the queries' set (workspace addresses, plane geometry; tb_lo != null: prefilter planes exist), the row
 // count of the normalised copies, the normalisation switch.  Host code, gkg_knn.hip; nothing is launched.  Returns 0 or a GKG_ERR_*
 // code with the error string set.

@@ -55,8 +55,6 @@ namespace gkg {
 // U[q][t][2i+1] = max_j (x_j - x_i) and the winning rows (u16) the backward scatters from.  Replaces the launch pair
 // knn_tile_kernel -> mr_fwd_tm_kernel (reference torch_edge.py:164-176 -> torch_vertex.py:49-61); while one workgroup of a
 // CU gathers, the CU's other two or three are in their matrix phase.
-constexpr int KNN_EL_F32 = 0, KNN_EL_BF16 = 1, KNN_EL_F16 = 2;
-
 // one 16-deep matrix-core step of either 16-bit format: 8-element operand fragments, the same lane maps
 typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 bf16x8_t;
 typedef __attribute__((__vector_size__(8 * sizeof(_Float16)))) _Float16 f16x8_t;
@@ -725,36 +723,10 @@ __global__ __launch_bounds__(64 * NWV, (BF && HAS_RP) ? (KD <= 18 ? 3 : 2) : (KD
   }
 }
 
-constexpr int KNN_BUF = 16;        // buffered selection: entries per lane (8 bytes each: 32 KB per workgroup)
-
+// Launch of one instantiation: grid and dynamic LDS size are the plan's (gkg_knn_plan.h knn_tile_lds)
 template <int KD, bool HAS_RP, int KU, bool GUARD = true, int BUF = 0, int BF = KNN_EL_F32, int NWV = NW, bool MRF = false>
-static hipError_t launch_tile_v(const KnnArgs& a, dim3 grid, size_t lds, hipStream_t st) {
-  // staged query tile: fp32 [cpad][64], or (bf16 form) 64 rows of cp16 + 8 bf16
-  const size_t qbytes = BF ? (size_t)QT * (a.cp16 + 8) * 2 : (size_t)a.cpad * QT * sizeof(float);
-  if (BF) {                                     // the caller sized `lds` for the fp32 tile: keep only what the merge needs
-    const size_t merge = NWV == 1 ? 0 : (size_t)NWV * KD * 64 * 2 * sizeof(float);
-    lds = qbytes > merge ? qbytes : merge;
-  }
-  if (NWV == 1 && !BF) lds = qbytes;            // no merge area
-  if (NWV > NW && !BF) {                        // the caller sized the merge area for 4 lists
-    const size_t merge = (size_t)NWV * KD * 64 * 2 * sizeof(float);
-    if (lds < merge) lds = merge;
-  }
-  if (BUF > 0) {                                // candidate buffer + the per-wave shared admission bounds behind the queries
-    const size_t need = qbytes + (size_t)BUF * 64 * NWV * sizeof(float2) + NWV * 64 * sizeof(float);
-    if (lds < need) lds = need;
-  }
-  if (MRF) {                                    // the final lists of the 64 queries behind the merge area
-    const size_t need = (size_t)NWV * KD * 64 * 2 * sizeof(float) + (size_t)a.k * 64 * sizeof(int);
-    if (lds < need) lds = need;
-  }
-  if (lds > 64 * 1024) {
-    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&knn_tile_kernel<KD, HAS_RP, KU, GUARD, BUF, BF, NWV, MRF>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (ea != hipSuccess) return ea;
-  }
-  hipLaunchKernelGGL((knn_tile_kernel<KD, HAS_RP, KU, GUARD, BUF, BF, NWV, MRF>), grid, dim3(64 * NWV), lds, st, a);
-  return hipGetLastError();
+static hipError_t launch_tile_v(const KnnArgs& a, const KnnPlan& p, hipStream_t st) {
+  return knn_launch(&knn_tile_kernel<KD, HAS_RP, KU, GUARD, BUF, BF, NWV, MRF>, dim3(p.grid_x, 1, p.S), 64 * NWV, p.lds_tile, st, a);
 }
 
 }  // namespace gkg

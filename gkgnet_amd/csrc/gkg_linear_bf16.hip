@@ -41,7 +41,7 @@
 // tools/bench_lin_bf16.py --prep; the rule and its table: linear_bf16.py prep_pays): it pays where one column tile holds every
 // group and the groups are narrow — the stage-1 shapes, fc1 94 -> 220 us against a 145 us preparation launch — and loses wherever
 // a last arrival works alone behind its neighbours.  The plan (workspace offsets, cpad, planes or not) is
-// knn_fwd_impl's own (knn_query_prep_plan), nothing of it is restated here.
+// knn_plan's own (gkg_knn_plan.h, through knn_query_prep_plan), nothing of it is restated here.
 //   linear_bf16_kernel<4, true>   237 VGPRs, 0 AGPRs, 106 SGPRs   same LDS, no scratch   2 waves / SIMD
 //   linear_bf16_kernel<2, true>   155 VGPRs, 0 AGPRs, 106 SGPRs   same LDS, no scratch   3 waves / SIMD
 // The non-PREP instantiations are unchanged by the parameter (234 / 66 and 152 / 62 as above).

@@ -23,7 +23,7 @@ A helper module, not a test module and not a conftest; it imports nothing of the
 import numpy as np
 import torch
 
-# (B, G, c, N, M (None = self graph), k, d, bias): the forms of knn_fwd_impl's bf16 branch; see tests/test_hip_knn_bf16_abi.py
+# (B, G, c, N, M (None = self graph), k, d, bias): the forms of knn_plan's 16-bit branch (csrc/gkg_knn_plan.h); see tests/test_hip_knn_bf16_abi.py
 FORMS = [(2, 1, 12, 77, None, 3, 2, True), (2, 4, 80, 324, None, 9, 1, True), (2, 2, 40, 80, 1000, 9, 1, False),
          (8, 1, 40, 4100, 300, 9, 2, True), (32, 1, 12, 4100, 520, 9, 1, True), (32, 1, 12, 4100, 520, 18, 1, False),
          (1, 2, 200, 300, None, 9, 2, True), (1, 1, 320, 200, None, 9, 3, True), (1, 1, 320, 200, None, 9, 2, True),

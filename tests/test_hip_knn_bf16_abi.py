@@ -8,8 +8,8 @@ definition distance of the returned key within 2 E of the reference's, and the s
 ranking at most the case's near-tie share (<= 5 %: tests/test_knn_bf16_reference_host.py).  Each case prints its mismatch share and
 its largest tolerated gap / 2E under ``pytest -s`` (figures: EXPERIMENTS.md "bf16-contraction k-NN at the C ABI").
 
-FORMS (R.FORMS: B, G, c, N, M or self, k, d, bias), after knn_fwd_impl (csrc/gkg_knn.hip) and launch_tile_bf (csrc/gkg_knn_bf.hip).
-Query tiles are 64 wide, key tiles 32; S = key splits (pick_splits: only below 256 workgroups, at least 8 key tiles per split), tps =
+FORMS (R.FORMS: B, G, c, N, M or self, k, d, bias), after knn_plan (csrc/gkg_knn_plan.h; held to these claims by tests/test_knn_plan_host.py).
+Query tiles are 64 wide, key tiles 32; S = key splits (knn_pick_splits: only below 256 workgroups, at least 8 key tiles per split), tps =
 key tiles per split; the list size KD is the first of 9, 18, 27, 36, 64 that holds k d; cp16 = c rounded up to 16.  The rule takes the
 buffered selection when tps >= 8 and (tps >= 16 or KD >= 18 or S > 1); the candidate buffer has 16 entries per lane if the query image
 64 (cp16 + 8) 2 B plus 33 KB fits the workgroup's LDS share (160 KB / 3 with a bias and KD <= 18, / 2 with a bias otherwise; without
