@@ -15,11 +15,9 @@
 #include <type_traits>
 
 #include "gkg_common.h"
-#include <optional>
+#include "gkg_mr_plan.h"
 
 namespace gkg {
-
-constexpr int MR_LDS_BUDGET = 96 * 1024;   // bytes of LDS for source rows / accumulators
 
 // Caller-provided neighbour indices are trusted to be in [0, M); clamping costs two integer ops per index and keeps a
 // corrupted index tensor from becoming an out-of-bounds access.
@@ -1107,145 +1105,100 @@ __global__ __launch_bounds__(256) void mr_bwd_tm_scatter_atomic_kernel(const flo
 
 using namespace gkg;
 
-static int pick_ch(int c, int M, int extra_bytes) {
-  long ch = ((long)MR_LDS_BUDGET - extra_bytes) / ((long)M * 4);
-  if (ch > c) ch = c;
-  if (ch > 64) ch = 64;
-  return (int)ch;
+// ------------------------------------------------------------------------------------------ entry points
+// Each one fills a call, asks gkg_mr_plan.h for the plan, opens the profiler scope and launches what the plan names.
+
+// Three runtime switches -> compile-time constants: f(std::bool_constant<a>, std::bool_constant<b>, std::bool_constant<c>).  The
+// token-major kernels are instantiated per (self graph, mode, arg kind) — the forward per (k == 9, arg kind, bf16 out) — and picked here.
+template <typename F>
+static void mr_dispatch3(bool a, bool b, bool c, F&& f) {
+  auto on_c = [&](auto A, auto B) { if (c) f(A, B, std::true_type{}); else f(A, B, std::false_type{}); };
+  auto on_b = [&](auto A) { if (b) on_c(A, std::true_type{}); else on_c(A, std::false_type{}); };
+  if (a) on_b(std::true_type{}); else on_b(std::false_type{});
 }
 
-template <typename T>
-static hipError_t mr_fwd_launch(const void* x, const void* src, const int64_t* nn_idx, void* m_out, uint8_t* argmax,
-                                int BG, int c, int N, int M, int k, int CH, hipStream_t st) {
-  GkgProfScope prof(GKG_PROF_MR_FWD, st);
-  const size_t lds = (size_t)CH * M * 4 + (size_t)k * 256 * 4;
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mr_fwd_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  dim3 grid((N + 255) / 256, (c + CH - 1) / CH, BG);
-  hipLaunchKernelGGL((mr_fwd_kernel<T>), grid, dim3(256), lds, st, (const T*)x, (const T*)src, nn_idx, (T*)m_out, argmax,
-                     c, N, M, k, CH);
-  return hipGetLastError();
+// f(T{}) for the element type of a channel-major call (the plan has rejected every other dtype)
+template <typename F>
+static void mr_dispatch_dtype(int dtype, F&& f) {
+  if (dtype == GKG_F32) f(float{}); else if (dtype == GKG_F16) f(_Float16{}); else f(uint16_t{});
 }
+
+// a launch with more than 64 KB of dynamic LDS has to be allowed per kernel
+template <typename K>
+static void mr_allow_lds(K* kernel, size_t lds) {
+  if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
+
+static int mr_done(const char* where) { const hipError_t e = hipGetLastError(); return e == hipSuccess ? 0 : gkg_fail_hip(e, where); }
 
 extern "C" int gkg_mr_fwd(const void* x, const void* src, const int64_t* nn_idx, void* m_out, uint8_t* argmax,
                           int BG, int c, int N, int M, int k, int dtype, void* stream) {
   if (!x || !nn_idx || !m_out) return gkg_fail(GKG_ERR_NULL, "gkg_mr_fwd: x, nn_idx and m_out must be non-null");
-  if (BG <= 0 || c <= 0 || N <= 0 || M <= 0 || k <= 0 || k > 255) return gkg_fail(GKG_ERR_SHAPE, "gkg_mr_fwd: bad sizes (k <= 255)");
-  if (!src) { if (M != N) return gkg_fail(GKG_ERR_SHAPE, "gkg_mr_fwd: self graph needs M == N"); src = x; }
-  if (dtype != GKG_F32 && dtype != GKG_BF16 && dtype != GKG_F16) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_mr_fwd: dtype");
-  if (BG > 65535) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_mr_fwd: BG <= 65535");
-  const int extra = k * 256 * 4;
-  // channels per workgroup: as many source rows as fit, but keep enough workgroups to fill the chip
-  int CH = pick_ch(c, M, extra);
-  if (CH < 1) {                      // source row does not fit in LDS: gather from L2
-    GkgProfScope prof(GKG_PROF_MR_FWD, (hipStream_t)stream);
-    dim3 grid((N + 255) / 256, c < 64 ? c : 64, BG);
-    if (dtype == GKG_F32) hipLaunchKernelGGL((mr_fwd_gather_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)x, (const float*)src, nn_idx, (float*)m_out, argmax, c, N, M, k);
-    else if (dtype == GKG_F16) hipLaunchKernelGGL((mr_fwd_gather_kernel<_Float16>), grid, dim3(256), 0, (hipStream_t)stream, (const _Float16*)x, (const _Float16*)src, nn_idx, (_Float16*)m_out, argmax, c, N, M, k);
-    else hipLaunchKernelGGL((mr_fwd_gather_kernel<uint16_t>), grid, dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, (const uint16_t*)src, nn_idx, (uint16_t*)m_out, argmax, c, N, M, k);
-    hipError_t e2 = hipGetLastError();
-    return e2 == hipSuccess ? 0 : gkg_fail_hip(e2, "mr_fwd_gather_kernel");
-  }
-  const long ntiles = (N + 255) / 256;
-  while (CH > 4 && ntiles * ((c + CH - 1) / CH) * BG < 1024) CH = (CH + 1) / 2;
-  hipError_t e = dtype == GKG_F32 ? mr_fwd_launch<float>(x, src, nn_idx, m_out, argmax, BG, c, N, M, k, CH, (hipStream_t)stream)
-               : dtype == GKG_F16 ? mr_fwd_launch<_Float16>(x, src, nn_idx, m_out, argmax, BG, c, N, M, k, CH, (hipStream_t)stream)
-                                  : mr_fwd_launch<uint16_t>(x, src, nn_idx, m_out, argmax, BG, c, N, M, k, CH, (hipStream_t)stream);
-  if (e != hipSuccess) return gkg_fail_hip(e, "mr_fwd_kernel");
-  return 0;
-}
-
-template <typename T>
-static hipError_t mr_bwd_launch(const void* g, const int64_t* nn_idx, const uint8_t* argmax, void* gx, void* gsrc,
-                                int BG, int c, int N, int M, int k, int CH, hipStream_t st) {
-  GkgProfScope prof(GKG_PROF_MR_BWD, st);
-  const size_t lds = (size_t)CH * M * 4 + (size_t)k * 256 * 4;
-  dim3 grid((c + CH - 1) / CH, BG);
-  if (gsrc) {
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mr_bwd_kernel<T, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((mr_bwd_kernel<T, false>), grid, dim3(256), lds, st, (const T*)g, nn_idx, argmax, (T*)gx, (T*)gsrc, c, N, M, k, CH);
-  } else {
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mr_bwd_kernel<T, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((mr_bwd_kernel<T, true>), grid, dim3(256), lds, st, (const T*)g, nn_idx, argmax, (T*)gx, (T*)nullptr, c, N, M, k, CH);
-  }
-  return hipGetLastError();
+  MrCmPlan p;
+  const char* msg = nullptr;
+  if (const int rc = mr_cm_plan(MrCmCall{false, BG, c, N, M, k, dtype, src == nullptr}, &p, &msg)) return gkg_fail(rc, msg);
+  if (!src) src = x;
+  hipStream_t st = (hipStream_t)stream;
+  GkgProfScope prof(GKG_PROF_MR_FWD, st);
+  const dim3 grid(p.grid_x, p.grid_y, p.grid_z);
+  if (p.fallback) mr_dispatch_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((mr_fwd_gather_kernel<T>), grid, dim3(256), 0, st, (const T*)x, (const T*)src, nn_idx, (T*)m_out, argmax, c, N, M, k);
+  });
+  else mr_dispatch_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    mr_allow_lds(&mr_fwd_kernel<T>, p.lds);
+    hipLaunchKernelGGL((mr_fwd_kernel<T>), grid, dim3(256), p.lds, st, (const T*)x, (const T*)src, nn_idx, (T*)m_out, argmax, c, N, M, k, p.CH);
+  });
+  return mr_done(p.fallback ? "mr_fwd_gather_kernel" : "mr_fwd_kernel");
 }
 
 extern "C" int gkg_mr_bwd(const void* g, const int64_t* nn_idx, const uint8_t* argmax, void* gx, void* gsrc,
                           int BG, int c, int N, int M, int k, int dtype, void* stream) {
   if (!g || !nn_idx || !argmax || !gx) return gkg_fail(GKG_ERR_NULL, "gkg_mr_bwd: g, nn_idx, argmax and gx must be non-null");
-  if (BG <= 0 || c <= 0 || N <= 0 || M <= 0 || k <= 0 || k > 255) return gkg_fail(GKG_ERR_SHAPE, "gkg_mr_bwd: bad sizes (k <= 255)");
-  if (!gsrc && M != N) return gkg_fail(GKG_ERR_SHAPE, "gkg_mr_bwd: self graph needs M == N");
-  if (dtype != GKG_F32 && dtype != GKG_BF16 && dtype != GKG_F16) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_mr_bwd: dtype");
-  if (BG > 65535) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_mr_bwd: BG <= 65535");
-  const int extra = k * 256 * 4;
-  int CH = pick_ch(c, M, extra);
-  if (CH < 1) {                      // accumulator row does not fit in LDS: fp32 global atomics (fp32 tensors only)
-    if (dtype != GKG_F32) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_mr_bwd: M too large for the LDS accumulator and dtype is not fp32");
-    hipStream_t st = (hipStream_t)stream;
-    GkgProfScope prof(GKG_PROF_MR_BWD, st);
-    const size_t nx = (size_t)BG * c * N;
-    if (gsrc) (void)hipMemsetAsync(gsrc, 0, sizeof(float) * (size_t)BG * c * M, st);
-    else hipLaunchKernelGGL(negate_kernel, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, st, (const float*)g, (float*)gx, nx);
-    dim3 grid((N + 255) / 256, c < 64 ? c : 64, BG);
+  MrCmPlan p;
+  const char* msg = nullptr;
+  if (const int rc = mr_cm_plan(MrCmCall{true, BG, c, N, M, k, dtype, gsrc == nullptr}, &p, &msg)) return gkg_fail(rc, msg);
+  hipStream_t st = (hipStream_t)stream;
+  GkgProfScope prof(GKG_PROF_MR_BWD, st);
+  const dim3 grid(p.grid_x, p.grid_y, p.grid_z);
+  if (p.fallback) {                  // fp32 global atomics into gsrc = 0 / gx = -g
+    if (p.gsrc_bytes) (void)hipMemsetAsync(gsrc, 0, p.gsrc_bytes, st);
+    if (p.seed_grid) hipLaunchKernelGGL(negate_kernel, dim3(p.seed_grid), dim3(256), 0, st, (const float*)g, (float*)gx, (size_t)BG * c * N);
     hipLaunchKernelGGL(mr_bwd_atomic_kernel, grid, dim3(256), 0, st, (const float*)g, nn_idx, argmax, (float*)gx,
                        gsrc ? (float*)gsrc : (float*)gx, c, N, M, k, gsrc ? 0 : 1);
-    hipError_t e2 = hipGetLastError();
-    return e2 == hipSuccess ? 0 : gkg_fail_hip(e2, "mr_bwd_atomic_kernel");
+    return mr_done("mr_bwd_atomic_kernel");
   }
-  while (CH > 2 && (long)((c + CH - 1) / CH) * BG < 1024) CH = (CH + 1) / 2;
-  hipError_t e = dtype == GKG_F32 ? mr_bwd_launch<float>(g, nn_idx, argmax, gx, gsrc, BG, c, N, M, k, CH, (hipStream_t)stream)
-               : dtype == GKG_F16 ? mr_bwd_launch<_Float16>(g, nn_idx, argmax, gx, gsrc, BG, c, N, M, k, CH, (hipStream_t)stream)
-                                  : mr_bwd_launch<uint16_t>(g, nn_idx, argmax, gx, gsrc, BG, c, N, M, k, CH, (hipStream_t)stream);
-  if (e != hipSuccess) return gkg_fail_hip(e, "mr_bwd_kernel");
-  return 0;
+  mr_dispatch_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    auto go = [&](auto* kernel) {
+      mr_allow_lds(kernel, p.lds);
+      hipLaunchKernelGGL(kernel, grid, dim3(256), p.lds, st, (const T*)g, nn_idx, argmax, (T*)gx, (T*)gsrc, c, N, M, k, p.CH);
+    };
+    if (gsrc) go(&mr_bwd_kernel<T, false>); else go(&mr_bwd_kernel<T, true>);
+  });
+  return mr_done("mr_bwd_kernel");
 }
 
 // ------------------------------------------------------------------------------------------ token-major entry points
 template <typename IdxT>
 static int mr_fwd_tm_impl(const float* x, int ldx, int xchunk, const float* src, const IdxT* nn_idx, void* out, uint8_t* argmax,
                           int B, int G, int c, int N, int M, int k, int mode, int out_dtype, int arg_kind, void* stream) {
-  if (arg_kind != 0 && arg_kind != 1) return gkg_fail(GKG_ERR_SHAPE, "gkg_mr_fwd_tm: arg_kind is 0 (u8 slot) or 1 (u16 row index)");
-  if (arg_kind == 1 && M > 65536) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_mr_fwd_tm: arg_kind 1 needs M <= 65536");
+  const MrFwdTmCall q{B, G, c, N, M, k, mode, out_dtype, arg_kind, ldx, xchunk, src != nullptr, (const void*)x == (const void*)out,
+                      argmax != nullptr, sizeof(IdxT) == 2};
+  MrFwdTmPlan p;
+  const char* msg = nullptr;
+  if (const int rc = mr_fwd_tm_plan(q, &p, &msg)) return gkg_fail(rc, msg);
   if (!x || !nn_idx || !out) return gkg_fail(GKG_ERR_NULL, "gkg_mr_fwd_tm: x, nn_idx and out must be non-null");
-  if (B <= 0 || G <= 0 || c <= 0 || N <= 0 || M <= 0 || k <= 0 || k > 255 || (c & 3)) return gkg_fail(GKG_ERR_SHAPE, "gkg_mr_fwd_tm: bad sizes (c % 4 == 0, k <= 255)");
-  if (mode != 0 && mode != 1) return gkg_fail(GKG_ERR_SHAPE, "gkg_mr_fwd_tm: mode is 0 or 1");
-  if (mode == 1 && ((G * c) & 15)) return gkg_fail(GKG_ERR_SHAPE, "gkg_mr_fwd_tm: mode 1 needs C % 16 == 0");
-  if (out_dtype != GKG_F32 && out_dtype != GKG_BF16) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_mr_fwd_tm: out_dtype is GKG_F32 or GKG_BF16");
-  const int C = G * c;
-  if (ldx == 0) ldx = C;
-  if (ldx < C || (ldx & 3) || xchunk < 0 || (xchunk & 3) || (xchunk > 0 && (C % xchunk || ldx < 2 * C)))
-    return gkg_fail(GKG_ERR_SHAPE, "gkg_mr_fwd_tm: bad x view (ldx >= C, ldx % 4 == 0; a chunk is a multiple of 4 dividing C, with ldx >= 2 C)");
-  const bool has_src = src != nullptr;
-  int lds_ = C, schunk = 0;
-  if (!src) { if (M != N) return gkg_fail(GKG_ERR_SHAPE, "gkg_mr_fwd_tm: self graph needs M == N"); src = x; lds_ = ldx; schunk = xchunk; }
-  // mode 1: x already lives in the operand buffer when the caller passes that buffer's x half as the view of x
-  const int write_x = !(mode == 1 && (const void*)x == (const void*)out && ldx == 2 * C && xchunk == (C >> 2) && out_dtype == GKG_F32);
-  if (mode == 1 && (const void*)x == (const void*)out && write_x) return gkg_fail(GKG_ERR_SHAPE, "gkg_mr_fwd_tm: x aliases out but is not its x half (ldx = 2 C, xchunk = C / 4, fp32)");
-  // algorithmic bytes (SURVEY §8d "MR gather-max fwd"): x + (keys) + int64 indices + m (+ 1 byte of argmax per element)
-  const double e_out = out_dtype == GKG_BF16 ? 2.0 : 4.0;
-  const double work = 4.0 * B * (double)G * c * N + (has_src ? 4.0 * B * (double)G * c * M : 0.0) + (double)sizeof(IdxT) * B * (double)G * N * k
-                      + e_out * B * (double)G * c * N + (argmax ? 1.0 * B * (double)G * c * N : 0.0);
-  GkgProfScope prof(GKG_PROF_MR_FWD, (hipStream_t)stream, work);
-  // one channel quad per thread: two quads per thread (shared index row) measured 20 % slower at cfg2 — the kernel
-  // wants more threads in flight, not fewer index loads
-  const long bpi = ((long)N * (G * c / 4) + 255) / 256;
-  if (bpi * (((long)B + 7) / 8) * 8 > 0x7fffffffL) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_mr_fwd_tm: problem too large for one launch");
-  const dim3 grid((unsigned)(bpi * ((B + 7) / 8) * 8));
+  if (!src) src = x;
   hipStream_t st = (hipStream_t)stream;
-  if (out_dtype == GKG_BF16) {
-    uint16_t* o = (uint16_t*)out;
-    if (k == 9) { if (arg_kind == 1) hipLaunchKernelGGL((mr_fwd_tm_kernel<9, 1, uint16_t, 1, IdxT>), grid, dim3(256), 0, st, x, src, nn_idx, o, argmax, B, G, c, N, M, k, mode, ldx, xchunk, lds_, schunk, write_x); else hipLaunchKernelGGL((mr_fwd_tm_kernel<9, 1, uint16_t, 0, IdxT>), grid, dim3(256), 0, st, x, src, nn_idx, o, argmax, B, G, c, N, M, k, mode, ldx, xchunk, lds_, schunk, write_x); }
-    else { if (arg_kind == 1) hipLaunchKernelGGL((mr_fwd_tm_kernel<0, 1, uint16_t, 1, IdxT>), grid, dim3(256), 0, st, x, src, nn_idx, o, argmax, B, G, c, N, M, k, mode, ldx, xchunk, lds_, schunk, write_x); else hipLaunchKernelGGL((mr_fwd_tm_kernel<0, 1, uint16_t, 0, IdxT>), grid, dim3(256), 0, st, x, src, nn_idx, o, argmax, B, G, c, N, M, k, mode, ldx, xchunk, lds_, schunk, write_x); }
-  } else {
-    float* o = (float*)out;
-    if (k == 9) { if (arg_kind == 1) hipLaunchKernelGGL((mr_fwd_tm_kernel<9, 1, float, 1, IdxT>), grid, dim3(256), 0, st, x, src, nn_idx, o, argmax, B, G, c, N, M, k, mode, ldx, xchunk, lds_, schunk, write_x); else hipLaunchKernelGGL((mr_fwd_tm_kernel<9, 1, float, 0, IdxT>), grid, dim3(256), 0, st, x, src, nn_idx, o, argmax, B, G, c, N, M, k, mode, ldx, xchunk, lds_, schunk, write_x); }
-    else { if (arg_kind == 1) hipLaunchKernelGGL((mr_fwd_tm_kernel<0, 1, float, 1, IdxT>), grid, dim3(256), 0, st, x, src, nn_idx, o, argmax, B, G, c, N, M, k, mode, ldx, xchunk, lds_, schunk, write_x); else hipLaunchKernelGGL((mr_fwd_tm_kernel<0, 1, float, 0, IdxT>), grid, dim3(256), 0, st, x, src, nn_idx, o, argmax, B, G, c, N, M, k, mode, ldx, xchunk, lds_, schunk, write_x); }
-  }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : gkg_fail_hip(e, "mr_fwd_tm_kernel");
+  GkgProfScope prof(GKG_PROF_MR_FWD, st, p.work);
+  mr_dispatch3(p.out_bf16, p.KS == 9, p.AK == 1, [&](auto BF, auto K9, auto A) {
+    using OutT = std::conditional_t<BF.value, uint16_t, float>;
+    hipLaunchKernelGGL((mr_fwd_tm_kernel<K9.value ? 9 : 0, 1, OutT, A.value ? 1 : 0, IdxT>), dim3(p.grid), dim3(256), 0, st, x, src, nn_idx,
+                       (OutT*)out, argmax, B, G, c, N, M, k, mode, p.ldx, xchunk, p.lds_, p.schunk, p.write_x);
+  });
+  return mr_done("mr_fwd_tm_kernel");
 }
 
 extern "C" int gkg_mr_fwd_tm(const float* x, int ldx, int xchunk, const float* src, const int64_t* nn_idx, void* out, uint8_t* argmax,
@@ -1257,240 +1210,92 @@ extern "C" int gkg_mr_fwd_tm(const float* x, int ldx, int xchunk, const float* s
 // index stream is a quarter of the int64 one (SURVEY §8d "MR gather-max fwd": 8 B G N k -> 2 B G N k bytes).
 extern "C" int gkg_mr_fwd_tm16(const float* x, int ldx, int xchunk, const float* src, const uint16_t* nn16, void* out, uint8_t* argmax,
                                int B, int G, int c, int N, int M, int k, int mode, int out_dtype, int arg_kind, void* stream) {
-  if (M > 65536) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_mr_fwd_tm16: M <= 65536 (u16 rows)");
   return mr_fwd_tm_impl<uint16_t>(x, ldx, xchunk, src, nn16, out, argmax, B, G, c, N, M, k, mode, out_dtype, arg_kind, stream);
 }
 
-// The LDS-image backward kernels are instantiated per (self graph, mode, arg kind): 8 forms each, picked here.
-template <bool DET, bool SELF, int MODE, int AK>
-static void launch_tm_lds_one(dim3 grid, dim3 block, size_t lds, hipStream_t st, const float* gin, const int64_t* nn_idx,
-                              const uint8_t* argmax, float* gx, float* gsrc, int B, int G, int c, int N, int M, int k, int last) {
-  if (DET) {
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mr_bwd_tm_det_kernel<SELF, MODE, AK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((mr_bwd_tm_det_kernel<SELF, MODE, AK>), grid, block, lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, MODE, last, AK);
-  } else {
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mr_bwd_tm_scatter_kernel<SELF, MODE, AK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((mr_bwd_tm_scatter_kernel<SELF, MODE, AK>), grid, block, lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, MODE, last, AK);
+struct MrBwdTmPtrs { const float* gin; const int64_t* nn_idx; const uint8_t* argmax; float* gx; float* gsrc; MrBnArgs bn; };
+
+// The LDS-image backward kernels are instantiated per (self graph, mode, arg kind): f(bool_constant<SELF>, integral_constant<int, MODE>,
+// integral_constant<int, AK>) for the call's three
+template <typename F>
+static void mr_bwd_tm_dispatch(const MrBwdTmCall& q, F&& f) {
+  mr_dispatch3(q.self_graph, q.mode == 0, q.arg_kind == 1, [&](auto S, auto M0, auto A) {
+    f(S, std::integral_constant<int, M0.value ? 0 : 1>{}, std::integral_constant<int, A.value ? 1 : 0>{});
+  });
+}
+// go(kernel) for the streaming / two-sweep instantiation of the call; with the BN backward statistics of gx (MrStat): the XM gradient
+// layout (mode 1) only
+template <int NT, int ACC, int U, bool STATS, typename Go>
+static void mr_bwd_tm_stream(const MrBwdTmCall& q, Go&& go) {
+  mr_bwd_tm_dispatch(q, [&](auto S, auto MO, auto A) {
+    if constexpr (!STATS || MO.value == 1) go(&mr_bwd_tm_stream_kernel<NT, S.value, MO.value, A.value, ACC, U, STATS>);
+  });
+}
+template <bool STATS, typename Go>
+static void mr_bwd_tm_i64(const MrBwdTmCall& q, Go&& go) {
+  mr_bwd_tm_dispatch(q, [&](auto S, auto MO, auto A) {
+    if constexpr (!STATS || MO.value == 1) go(&mr_bwd_tm_scatter_i64_kernel<S.value, MO.value, A.value, STATS>);
+  });
+}
+
+// The launches of a planned backward.  hipErrorInvalidValue: the plan names a form no kernel of this unit holds.
+static hipError_t mr_bwd_tm_launch(const MrBwdTmCall& q, const MrBwdTmPlan& p, const MrBwdTmPtrs& a, hipStream_t st) {
+  const dim3 grid(p.grid_x, p.grid_y), block(p.block);
+  if (p.seed_grid) {                 // seed (gx = direct - gm; gsrc = 0), then the ordered walk / the fp32 global atomics
+    if (p.form != MR_DET_WALK && p.form != MR_GLOBAL_F32) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(mr_bwd_tm_init_kernel, dim3(p.seed_grid), dim3(256), 0, st, a.gin, a.gx, q.G * q.c, (size_t)q.B * q.N, q.mode);
+    if (p.gsrc_bytes) (void)hipMemsetAsync(a.gsrc, 0, p.gsrc_bytes, st);
+    hipLaunchKernelGGL(p.form == MR_DET_WALK ? mr_bwd_tm_det_global_kernel : mr_bwd_tm_scatter_atomic_kernel, grid, block, 0, st, a.gin,
+                       a.nn_idx, a.argmax, a.gsrc ? a.gsrc : a.gx, q.B, q.G, q.c, q.N, q.M, q.k, q.mode, q.arg_kind);
+    return hipSuccess;
   }
+  hipError_t e = hipErrorInvalidValue;
+  auto go = [&](auto* kernel, auto... tail) {                // every kernel of the family starts with the same eleven arguments
+    mr_allow_lds(kernel, p.lds);
+    hipLaunchKernelGGL(kernel, grid, block, p.lds, st, a.gin, a.nn_idx, a.argmax, a.gx, a.gsrc, q.B, q.G, q.c, q.N, q.M, q.k, tail...);
+    e = hipSuccess;
+  };
+  auto i64 = [&](auto* kernel) { go(kernel, p.cw, p.shmax, a.bn); };
+  auto stream = [&](auto* kernel) { go(kernel, p.cw, p.shmax & 0xffff, p.shmax >> 16, a.bn); };
+  auto is_stream = [&](int nt, int acc, int u, bool stats) {
+    return p.form == (acc ? MR_STREAM_F64 : MR_STREAM) && p.NT == nt && p.ACC == acc && p.U == u && p.STATS == stats;
+  };
+  if (p.form == MR_TWO_SWEEP && !p.STATS) mr_bwd_tm_i64<false>(q, i64);
+  else if (is_stream(512, 0, 4, true)) mr_bwd_tm_stream<512, 0, 4, true>(q, stream);
+  else if (is_stream(512, 1, 4, false)) mr_bwd_tm_stream<512, 1, 4, false>(q, stream);
+  else if (is_stream(256, 0, 8, false)) mr_bwd_tm_stream<256, 0, 8, false>(q, stream);
+  else if (is_stream(256, 0, 4, false)) mr_bwd_tm_stream<256, 0, 4, false>(q, stream);
+  else if (is_stream(512, 0, 8, false)) mr_bwd_tm_stream<512, 0, 8, false>(q, stream);
+  else if (is_stream(512, 0, 4, false)) mr_bwd_tm_stream<512, 0, 4, false>(q, stream);
+  else if (p.form == MR_TWO_SWEEP) mr_bwd_tm_i64<true>(q, i64);
+  else if (p.form == MR_DET_PRIVATE || p.form == MR_LDS_F32)
+    mr_bwd_tm_dispatch(q, [&](auto S, auto MO, auto A) {
+      if (p.form == MR_DET_PRIVATE) go(&mr_bwd_tm_det_kernel<S.value, MO.value, A.value>, MO.value, p.cw, A.value);
+      else go(&mr_bwd_tm_scatter_kernel<S.value, MO.value, A.value>, MO.value, p.cw, A.value);
+    });
+  return e;
 }
 
-template <bool DET>
-static void launch_tm_lds(bool self, int mode, int ak, dim3 grid, dim3 block, size_t lds, hipStream_t st, const float* gin,
-                          const int64_t* nn_idx, const uint8_t* argmax, float* gx, float* gsrc, int B, int G, int c, int N, int M,
-                          int k, int last) {
-#define GKG_TM_CASE(S, MO, A) launch_tm_lds_one<DET, S, MO, A>(grid, block, lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, last)
-  if (self) {
-    if (mode == 0) { if (ak) GKG_TM_CASE(true, 0, 1); else GKG_TM_CASE(true, 0, 0); }
-    else { if (ak) GKG_TM_CASE(true, 1, 1); else GKG_TM_CASE(true, 1, 0); }
-  } else {
-    if (mode == 0) { if (ak) GKG_TM_CASE(false, 0, 1); else GKG_TM_CASE(false, 0, 0); }
-    else { if (ak) GKG_TM_CASE(false, 1, 1); else GKG_TM_CASE(false, 1, 0); }
-  }
-#undef GKG_TM_CASE
-}
-
-template <bool SELF, int MODE, int AK>
-static void launch_tm_i64_one(dim3 grid, size_t lds, hipStream_t st, const float* gin, const int64_t* nn_idx, const uint8_t* argmax,
-                              float* gx, float* gsrc, int B, int G, int c, int N, int M, int k, int CW, int shmax) {
-  if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mr_bwd_tm_scatter_i64_kernel<SELF, MODE, AK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((mr_bwd_tm_scatter_i64_kernel<SELF, MODE, AK>), grid, dim3(256), lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, CW, shmax);
-}
-static void launch_tm_i64(bool self, int mode, int ak, dim3 grid, size_t lds, hipStream_t st, const float* gin, const int64_t* nn_idx,
-                          const uint8_t* argmax, float* gx, float* gsrc, int B, int G, int c, int N, int M, int k, int CW, int shmax) {
-#define GKG_TM64_CASE(S, MO, A) launch_tm_i64_one<S, MO, A>(grid, lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, CW, shmax)
-  if (self) {
-    if (mode == 0) { if (ak) GKG_TM64_CASE(true, 0, 1); else GKG_TM64_CASE(true, 0, 0); }
-    else { if (ak) GKG_TM64_CASE(true, 1, 1); else GKG_TM64_CASE(true, 1, 0); }
-  } else {
-    if (mode == 0) { if (ak) GKG_TM64_CASE(false, 0, 1); else GKG_TM64_CASE(false, 0, 0); }
-    else { if (ak) GKG_TM64_CASE(false, 1, 1); else GKG_TM64_CASE(false, 1, 0); }
-  }
-#undef GKG_TM64_CASE
-}
-
-template <int NT, bool SELF, int MODE, int AK, int ACC, int U>
-static void launch_tm_stream_one(dim3 grid, size_t lds, hipStream_t st, const float* gin, const int64_t* nn_idx, const uint8_t* argmax,
-                                 float* gx, float* gsrc, int B, int G, int c, int N, int M, int k, int CW, int shmax) {
-  if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mr_bwd_tm_stream_kernel<NT, SELF, MODE, AK, ACC, U>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((mr_bwd_tm_stream_kernel<NT, SELF, MODE, AK, ACC, U>), grid, dim3(NT), lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, CW, shmax & 0xffff, shmax >> 16);
-}
-template <int NT, int ACC, int U>
-static void launch_tm_stream_nt(bool self, int mode, int ak, dim3 grid, size_t lds, hipStream_t st, const float* gin, const int64_t* nn_idx,
-                                const uint8_t* argmax, float* gx, float* gsrc, int B, int G, int c, int N, int M, int k, int CW, int shmax) {
-#define GKG_TMS_CASE(S, MO, A) launch_tm_stream_one<NT, S, MO, A, ACC, U>(grid, lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, CW, shmax)
-  if (self) {
-    if (mode == 0) { if (ak) GKG_TMS_CASE(true, 0, 1); else GKG_TMS_CASE(true, 0, 0); }
-    else { if (ak) GKG_TMS_CASE(true, 1, 1); else GKG_TMS_CASE(true, 1, 0); }
-  } else {
-    if (mode == 0) { if (ak) GKG_TMS_CASE(false, 0, 1); else GKG_TMS_CASE(false, 0, 0); }
-    else { if (ak) GKG_TMS_CASE(false, 1, 1); else GKG_TMS_CASE(false, 1, 0); }
-  }
-#undef GKG_TMS_CASE
-}
-
-// The two scatter forms with the BN backward statistics of gx (MrStat): the XM gradient layout (mode 1), chunk widths 4 / 8 / 16,
-// the 512-thread / 4-rows-in-flight streaming form or the two-sweep form.
-template <bool SELF, int AK>
-static void launch_tm_stream_stats(dim3 grid, size_t lds, hipStream_t st, const float* gin, const int64_t* nn_idx, const uint8_t* argmax,
-                                   float* gx, float* gsrc, int B, int G, int c, int N, int M, int k, int CW, int shmax, const MrBnArgs& bn) {
-  if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mr_bwd_tm_stream_kernel<512, SELF, 1, AK, 0, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((mr_bwd_tm_stream_kernel<512, SELF, 1, AK, 0, 4, true>), grid, dim3(512), lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, CW, shmax, 0, bn);
-}
-template <bool SELF, int AK>
-static void launch_tm_i64_stats(dim3 grid, size_t lds, hipStream_t st, const float* gin, const int64_t* nn_idx, const uint8_t* argmax,
-                                float* gx, float* gsrc, int B, int G, int c, int N, int M, int k, int CW, int shmax, const MrBnArgs& bn) {
-  if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mr_bwd_tm_scatter_i64_kernel<SELF, 1, AK, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((mr_bwd_tm_scatter_i64_kernel<SELF, 1, AK, true>), grid, dim3(256), lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, CW, shmax, bn);
-}
-
-static int mr_bwd_tm_impl(const float* gin, const int64_t* nn_idx, const uint8_t* argmax, float* gx, float* gsrc, int B, int G, int c,
-                          int N, int M, int k, int mode, int arg_kind, unsigned flags, void* stream, const MrBnArgs* bn,
-                          bool dry = false) {
-  if (arg_kind != 0 && arg_kind != 1) return gkg_fail(GKG_ERR_SHAPE, "gkg_mr_bwd_tm: arg_kind is 0 or 1");
+static int mr_bwd_tm_run(const MrBwdTmPtrs& a, int B, int G, int c, int N, int M, int k, int mode, int arg_kind, unsigned flags,
+                         bool want_stats, void* stream) {
+  const MrBwdTmCall q{B, G, c, N, M, k, mode, arg_kind, flags, a.gsrc == nullptr, want_stats};
+  MrBwdTmPlan p;
+  const char* msg = nullptr;
+  if (const int rc = mr_bwd_tm_plan(q, &p, &msg)) return gkg_fail(rc, msg);
   // arg_kind 1: the saved winning ROWS are the scatter targets — the index tensor is not read and may be null (the fused
   // k-NN + aggregation forward, gkg_knn_mr_fwd_tm, never materialises one)
-  if (!dry && (!gin || (!nn_idx && arg_kind != 1) || !argmax || !gx)) return gkg_fail(GKG_ERR_NULL, "gkg_mr_bwd_tm: gin, argmax, gx (and nn_idx unless arg_kind == 1) must be non-null");
-  if (B <= 0 || G <= 0 || c <= 0 || N <= 0 || M <= 0 || k <= 0 || k > 255 || (c & 3)) return gkg_fail(GKG_ERR_SHAPE, "gkg_mr_bwd_tm: bad sizes");
-  if (mode != 0 && mode != 1) return gkg_fail(GKG_ERR_SHAPE, "gkg_mr_bwd_tm: mode is 0 or 1");
-  if (mode == 1 && ((G * c) & 15)) return gkg_fail(GKG_ERR_SHAPE, "gkg_mr_bwd_tm: mode 1 needs C % 16 == 0");
-  if (!gsrc && M != N) return gkg_fail(GKG_ERR_SHAPE, "gkg_mr_bwd_tm: self graph needs M == N");
+  if (!a.gin || (!a.nn_idx && arg_kind != 1) || !a.argmax || !a.gx) return gkg_fail(GKG_ERR_NULL, "gkg_mr_bwd_tm: gin, argmax, gx (and nn_idx unless arg_kind == 1) must be non-null");
   hipStream_t st = (hipStream_t)stream;
-  // algorithmic bytes (SURVEY §8d "MR bwd"): g + int64 indices + argmax + gx (+ gsrc); arg_kind 1: u16 winning rows, no indices
-  const double work = 4.0 * B * (double)G * c * N + (arg_kind == 1 ? 0.0 : 8.0 * B * (double)G * N * k) + (arg_kind == 1 ? 2.0 : 1.0) * B * (double)G * c * N
-                      + 4.0 * B * (double)G * c * N + (gsrc ? 4.0 * B * (double)G * c * M : 0.0);
-  std::optional<GkgProfScope> prof;
-  if (!dry) prof.emplace(GKG_PROF_MR_BWD, st, work);       // (a dry run — gkg_mr_bwd_tm_bnstats_supported — launches nothing)
-  const int C = G * c;
-  const size_t T = (size_t)B * N;
-  const size_t total = T * (C / 4);
-  // Exact integer accumulation (see mr_bwd_tm_scatter_i64_kernel): the default whenever an (image, channel chunk) of 64-bit
-  // accumulators fits the LDS budget — order-independent, so it is also the deterministic form.  GKG_MR_FP32_ATOMICS keeps
-  // the fp32-atomic kernels (measurement, tests).
-  // Where it is selected (MI355X, tools/bench_mr_bwd.py, us, exact vs fp32 atomics at their best chunk widths): 18 x 18
-  // images — cfg2 21.2 vs 24.4-27.6, its label graph 9.4 vs 10.9, C = 640 39.3 vs 44.9-51.5; a tie at 36 x 36 (116.7 vs
-  // 113.5-118.2); it LOSES where the gradients stream from HBM and are swept twice (pooled 1 296-key images under 5 184 /
-  // 20 736 queries: 209 vs 164, 492 vs 425).  Rule: destination images of up to 512 rows; with GKG_MR_DETERMINISTIC wherever it
-  // fits (the private-accumulator form it replaces there is 1.6x the fp32 time).  Chunk width 8 (measured best or tied at
-  // every shape: the kernel lives on workgroups per CU), 4 when 8 does not fit.
-  // Streaming fixed-point form (mr_bwd_tm_stream_kernel, round 5): the default from 160 query rows per image wherever an (image,
-  // channel chunk) of 64-bit accumulators fits the LDS budget — one sweep, 4 / 8 rows per thread in flight, 512 threads.  Order-
-  // independent like the two-sweep form, so it serves GKG_MR_DETERMINISTIC too.  Measured against what it replaces
-  // (tools/bench_mr_bwd.py, us, profiles/r05_bench_mr_bwd_stream.txt): cfg2 21.8 -> 16.6, C = 640 at 18 x 18 38.7 -> 25.1,
-  // 36 x 36 self graph 117.6 -> 89.9, pooled 1 296-key images under 5 184 / 20 736 queries 165 -> 133 / 424 -> 359; the label
-  // graphs (80 queries) keep the two-sweep kernel (8.6 vs 9.2-9.9).  Chunk width: the widest of 16 / 8 / 4 channels that fits.
-  // Measurement: flags bits 16..17 = 1 force this form (bits 8..15 chunk width, 20..21 = 2: 256 threads, bit 22: 8 rows in
-  // flight), 2 = its fp64-atomic variant (ds_add_f64: 45-98 cycles per wave instruction against 170-183 for ds_add_f32 —
-  // tools/ubench/lds_atomic_rate.hip), 3 = the two-sweep kernel wherever it fits.
-  const int sv = (int)((flags >> 16) & 3);
-  // with statistics: only the library's own choice among the two exact forms (no measurement overrides), XM gradient layout
-  if (bn && (mode != 1 || sv || ((flags >> 8) & 0xff) || (flags & GKG_MR_FP32_ATOMICS)))
-    return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_mr_bwd_tm_bnstats: mode 1 and the default scatter form only");
-  if (N < (1 << 24) && (sv == 1 || sv == 2 || (sv == 0 && !(flags & GKG_MR_FP32_ATOMICS) && N >= 160))) {
-    int CW = (int)((flags >> 8) & 0xff);
-    auto sfits = [&](int cw) { return (size_t)M * cw * 8 + 16 <= (size_t)MR_LDS_BUDGET && C % cw == 0 && c % cw == 0; };
-    if (!CW || !sv) CW = sfits(16) ? 16 : (sfits(8) ? 8 : 4);
-    if ((sv && (size_t)M * CW * 8 + 16 <= 150 * 1024 && C % CW == 0 && c % CW == 0) || sfits(CW)) {
-      // long sweeps over a pooled key image (GKGNet-576 stages 1 / 2: N = 16 M / 4 M, M = 1 296): 256-thread workgroups with 4 rows
-      // in flight — two workgroups per CU overlap one's store phase with the other's sweep (round 6, on the XM gradient layout,
-      // us: stage 1 379.6 -> 334.9, stage 2 145.7 -> 141.0; the self graphs keep 512 threads: 36 x 36 89.7 vs 93.5)
-      const bool long_sweep = M > 512 && (long)N >= 4L * M;
-      const bool nt256 = sv ? ((flags >> 20) & 3) == 2 : long_sweep;
-      const bool u8 = sv ? ((flags >> 22) & 1) != 0 : (M > 512 && !long_sweep);       // 8 rows in flight
-      size_t lds = (size_t)M * CW * 8 + 16;
-      int bitsN = 0;
-      while ((1 << bitsN) <= N) ++bitsN;
-      const dim3 grid((C / CW) * ((B + 7) / 8) * 8);
-      const bool self = gsrc == nullptr;
-      if (bn) {
-        if (nt256 || u8) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_mr_bwd_tm_bnstats: long-sweep streaming forms carry no statistics");
-        if (lds < (size_t)(512 / 64) * 2 * CW * 8) lds = (size_t)(512 / 64) * 2 * CW * 8;       // room for MrStat::flush
-        if (dry) return 0;
-        if (self) { if (arg_kind) launch_tm_stream_stats<true, 1>(grid, lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, CW, 38 - bitsN, *bn);
-                    else launch_tm_stream_stats<true, 0>(grid, lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, CW, 38 - bitsN, *bn); }
-        else { if (arg_kind) launch_tm_stream_stats<false, 1>(grid, lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, CW, 38 - bitsN, *bn);
-               else launch_tm_stream_stats<false, 0>(grid, lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, CW, 38 - bitsN, *bn); }
-        hipError_t eb = hipGetLastError();
-        return eb == hipSuccess ? 0 : gkg_fail_hip(eb, "mr_bwd_tm_stream_kernel (BN backward statistics)");
-      }
-      const int planes_bit = (sv && ((flags >> 23) & 1) && arg_kind == 1) ? (1 << 16) : 0;      // measurement: 8-channel planes of winning rows
-      if (sv == 2) launch_tm_stream_nt<512, 1, 4>(self, mode, arg_kind, grid, lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, CW, (38 - bitsN) | planes_bit);
-      else if (nt256 && u8) launch_tm_stream_nt<256, 0, 8>(self, mode, arg_kind, grid, lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, CW, (38 - bitsN) | planes_bit);
-      else if (nt256) launch_tm_stream_nt<256, 0, 4>(self, mode, arg_kind, grid, lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, CW, (38 - bitsN) | planes_bit);
-      else if (u8) launch_tm_stream_nt<512, 0, 8>(self, mode, arg_kind, grid, lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, CW, (38 - bitsN) | planes_bit);
-      else launch_tm_stream_nt<512, 0, 4>(self, mode, arg_kind, grid, lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, CW, (38 - bitsN) | planes_bit);
-      hipError_t es = hipGetLastError();
-      return es == hipSuccess ? 0 : gkg_fail_hip(es, "mr_bwd_tm_stream_kernel");
-    }
-    if (sv) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_mr_bwd_tm: forced streaming form does not fit");
-  }
-  if (!(flags & GKG_MR_FP32_ATOMICS) && N < (1 << 24) && (M <= 512 || sv == 3 || (flags & GKG_MR_DETERMINISTIC))) {
-    int CW = 8;
-    const int forced = (int)((flags >> 8) & 0xff);          // measurement only: bits 8..15 force the chunk width
-    auto fits = [&](int cw, size_t budget) { return (size_t)M * cw * 8 + 16 <= budget && C % cw == 0 && c % cw == 0; };
-    if (!fits(CW, (size_t)MR_LDS_BUDGET)) CW = 4;
-    if (forced) CW = forced;
-    if (fits(CW, (size_t)MR_LDS_BUDGET) && (long)(C / CW) * (B + 7) < 0x7fffffffL) {
-      int bitsN = 0;
-      while ((1 << bitsN) <= N) ++bitsN;                  // N < 2^bitsN
-      if (bn) {
-        size_t lds = (size_t)M * CW * 8 + 16;
-        if (lds < (size_t)(256 / 64) * 2 * CW * 8) lds = (size_t)(256 / 64) * 2 * CW * 8;       // room for MrStat::flush
-        if (dry) return 0;
-        const dim3 grid((C / CW) * ((B + 7) / 8) * 8);
-        if (!gsrc) { if (arg_kind) launch_tm_i64_stats<true, 1>(grid, lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, CW, 38 - bitsN, *bn);
-                     else launch_tm_i64_stats<true, 0>(grid, lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, CW, 38 - bitsN, *bn); }
-        else { if (arg_kind) launch_tm_i64_stats<false, 1>(grid, lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, CW, 38 - bitsN, *bn);
-               else launch_tm_i64_stats<false, 0>(grid, lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, CW, 38 - bitsN, *bn); }
-        hipError_t eb = hipGetLastError();
-        return eb == hipSuccess ? 0 : gkg_fail_hip(eb, "mr_bwd_tm_scatter_i64_kernel (BN backward statistics)");
-      }
-      launch_tm_i64(gsrc == nullptr, mode, arg_kind, dim3((C / CW) * ((B + 7) / 8) * 8), (size_t)M * CW * 8 + 16, st, gin, nn_idx,
-                    argmax, gx, gsrc, B, G, c, N, M, k, CW, 38 - bitsN);
-      hipError_t ei = hipGetLastError();
-      return ei == hipSuccess ? 0 : gkg_fail_hip(ei, "mr_bwd_tm_scatter_i64_kernel");
-    }
-  }
-  if (bn) return dry ? GKG_ERR_UNSUPPORTED : gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_mr_bwd_tm_bnstats: this shape takes a scatter form without statistics");
-  if (flags & GKG_MR_DETERMINISTIC) {
-    if (B > 65535) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_mr_bwd_tm: B <= 65535");
-    long TL = (long)(144 * 1024) / ((long)M * 16);
-    if (TL > 64) TL = 64;
-    if (TL >= 1) {
-      const size_t lds = (size_t)TL * M * 16;
-      launch_tm_lds<true>(gsrc == nullptr, mode, arg_kind, dim3(C / 4, B), dim3(64), lds, st, gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k,
-                          (int)TL);
-    } else {                         // seed (gx = direct - gm; gsrc = 0), then the ordered global walk
-      hipLaunchKernelGGL(mr_bwd_tm_init_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, gin, gx, C, T, mode);
-      if (gsrc) (void)hipMemsetAsync(gsrc, 0, sizeof(float) * (size_t)B * M * C, st);
-      hipLaunchKernelGGL(mr_bwd_tm_det_global_kernel, dim3((unsigned)((B * (C / 4) + 63) / 64)), dim3(64), 0, st, gin, nn_idx,
-                         argmax, gsrc ? gsrc : gx, B, G, c, N, M, k, mode, arg_kind);
-    }
-    hipError_t ed = hipGetLastError();
-    return ed == hipSuccess ? 0 : gkg_fail_hip(ed, "mr_bwd_tm (deterministic)");
-  }
-  // channel chunk: largest power of two (4..64) dividing C and c whose [M][CW] fp32 image fits the LDS budget, shrunk
-  // until the grid has ~2 workgroups per CU
-  int CW = 64;
-  while (CW > 4 && ((size_t)M * CW * 4 > (size_t)MR_LDS_BUDGET || C % CW || c % CW)) CW >>= 1;
-  while (CW > 8 && (long)(C / CW) * B < 512) CW >>= 1;
-  if ((flags >> 8) & 0xff) CW = (int)((flags >> 8) & 0xff);       // measurement only
-  if ((size_t)M * CW * 4 <= (size_t)MR_LDS_BUDGET && C % CW == 0 && c % CW == 0 && (long)(C / CW) * (B + 7) < 0x7fffffffL) {
-    const size_t lds = (size_t)M * CW * 4;
-    launch_tm_lds<false>(gsrc == nullptr, mode, arg_kind, dim3((C / CW) * ((B + 7) / 8) * 8), dim3(256), lds, st, gin, nn_idx, argmax, gx, gsrc,
-                         B, G, c, N, M, k, CW);
-  } else {                           // destination image too large for LDS: elementwise seed + fp32 global atomics
-    hipLaunchKernelGGL(mr_bwd_tm_init_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, gin, gx, C, T, mode);
-    if (gsrc) (void)hipMemsetAsync(gsrc, 0, sizeof(float) * (size_t)B * M * C, st);
-    hipLaunchKernelGGL(mr_bwd_tm_scatter_atomic_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, gin, nn_idx,
-                       argmax, gsrc ? gsrc : gx, B, G, c, N, M, k, mode, arg_kind);
-  }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : gkg_fail_hip(e, "mr_bwd_tm");
+  GkgProfScope prof(GKG_PROF_MR_BWD, st, p.work);
+  static const char* const where[] = {"mr_bwd_tm_stream_kernel", "mr_bwd_tm_stream_kernel", "mr_bwd_tm_scatter_i64_kernel", "mr_bwd_tm (deterministic)",
+                                      "mr_bwd_tm (deterministic)", "mr_bwd_tm", "mr_bwd_tm"};       // by MrBwdForm
+  const hipError_t e = mr_bwd_tm_launch(q, p, a, st);
+  return e != hipSuccess ? gkg_fail_hip(e, where[p.form]) : mr_done(where[p.form]);
 }
 
 extern "C" int gkg_mr_bwd_tm(const float* gin, const int64_t* nn_idx, const uint8_t* argmax, float* gx, float* gsrc,
                              int B, int G, int c, int N, int M, int k, int mode, int arg_kind, unsigned flags, void* stream) {
-  return mr_bwd_tm_impl(gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, mode, arg_kind, flags, stream, nullptr);
+  return mr_bwd_tm_run(MrBwdTmPtrs{gin, nn_idx, argmax, gx, gsrc, MrBnArgs{}}, B, G, c, N, M, k, mode, arg_kind, flags, false, stream);
 }
 
 // gkg_mr_bwd_tm that is ALSO the statistics pass of the BN backward whose upstream gradient gx is (the layer x = BN(y) in front
@@ -1503,19 +1308,15 @@ extern "C" int gkg_mr_bwd_tm_bnstats(const float* gin, const int64_t* nn_idx, co
                                      int B, int G, int c, int N, int M, int k, int mode, int arg_kind, unsigned flags,
                                      const float* y, const float* mean, const float* invstd, double* sums, void* stream) {
   if (!y || !mean || !invstd || !sums) return gkg_fail(GKG_ERR_NULL, "gkg_mr_bwd_tm_bnstats: null pointer");
-  const MrBnArgs bn{y, mean, invstd, sums};
-  return mr_bwd_tm_impl(gin, nn_idx, argmax, gx, gsrc, B, G, c, N, M, k, mode, arg_kind, flags, stream, &bn);
+  return mr_bwd_tm_run(MrBwdTmPtrs{gin, nn_idx, argmax, gx, gsrc, MrBnArgs{y, mean, invstd, sums}}, B, G, c, N, M, k, mode, arg_kind, flags,
+                       true, stream);
 }
 
-// 1 when gkg_mr_bwd_tm_bnstats would run for these sizes and flags (0: GKG_ERR_UNSUPPORTED or bad sizes); pure host code, for
+// 1 when gkg_mr_bwd_tm_bnstats would run for these sizes and flags (0: GKG_ERR_UNSUPPORTED or bad sizes): the plan's answer, for
 // callers that must book their scratch buffer before the call.
 extern "C" int gkg_mr_bwd_tm_bnstats_supported(int B, int G, int c, int N, int M, int k, int mode, int arg_kind, int self_graph,
                                                unsigned flags) {
-  if (B <= 0 || G <= 0 || c <= 0 || N <= 0 || M <= 0 || k <= 0 || k > 255 || (c & 3) || (mode != 0 && mode != 1) ||
-      (arg_kind != 0 && arg_kind != 1) || (self_graph && M != N))
-    return 0;
-  const MrBnArgs bn{};
-  float dummy;
-  return mr_bwd_tm_impl(nullptr, nullptr, nullptr, nullptr, self_graph ? nullptr : &dummy, B, G, c, N, M, k, mode, arg_kind, flags, nullptr,
-                        &bn, true) == 0;
+  MrBwdTmPlan p;
+  const char* msg = nullptr;
+  return mr_bwd_tm_plan(MrBwdTmCall{B, G, c, N, M, k, mode, arg_kind, flags, self_graph != 0, true}, &p, &msg) == 0;
 }

@@ -378,8 +378,8 @@ int gkg_mr_bwd_tm(const float* gin, const int64_t* nn_idx, const uint8_t* argmax
 int gkg_mr_bwd_tm_bnstats(const float* gin, const int64_t* nn_idx, const uint8_t* argmax, float* gx, float* gsrc,
                           int B, int G, int c, int N, int M, int k, int mode, int arg_kind, unsigned flags,
                           const float* y, const float* mean, const float* invstd, double* sums, void* stream);
-/* 1 when gkg_mr_bwd_tm_bnstats would run for these sizes and flags, 0 when it would return GKG_ERR_UNSUPPORTED (pure host code:
- * for callers that book their scratch buffer before the call). */
+/* 1 when gkg_mr_bwd_tm_bnstats would run for these sizes and flags, 0 when it would return GKG_ERR_UNSUPPORTED (pure host code, the
+ * call's own plan — csrc/gkg_mr_plan.h mr_bwd_tm_plan; for callers that book their scratch buffer before the call). */
 int gkg_mr_bwd_tm_bnstats_supported(int B, int G, int c, int N, int M, int k, int mode, int arg_kind, int self_graph, unsigned flags);
 
 /* ------------------------------------------------------------------------------------------------

@@ -402,7 +402,7 @@ def exact_scale(kind):
     return {"integer": 3, "binades": 27, "nonfinite": 27, "tiny": 149}[kind]
 
 
-# ---- the dispatch rule of gkg_mr_bwd_tm, restated (csrc/gkg_mr.hip mr_bwd_tm_impl) ----------------------------------------------
+# ---- the dispatch rule of gkg_mr_bwd_tm, restated (csrc/gkg_mr_plan.h mr_bwd_tm_plan; tests/test_mr_plan_host.py holds the two together) ----
 def bwd_form(B, G, c, N, M, flags=0):
     """-> (form, chunk width or None).  Forms: 'stream' (fixed point, one sweep), 'stream-f64' (its fp64-atomic variant), 'two-sweep'
     (fixed point), 'private' / 'walk' (GKG_MR_DETERMINISTIC beyond the LDS budget), 'lds-f32' / 'global-f32' (fp32 atomics),
@@ -411,7 +411,8 @@ def bwd_form(B, G, c, N, M, flags=0):
     sv, fcw = (flags >> 16) & 3, (flags >> 8) & 0xFF
     div = lambda cw: C % cw == 0 and c % cw == 0                                           # noqa: E731
     fits8 = lambda cw, budget=LDS_BUDGET: M * cw * 8 + 16 <= budget and div(cw)            # noqa: E731
-    if sv in (1, 2) or (sv == 0 and not flags & MR_F32 and N >= 160):
+    one_launch = lambda cw: (C // cw) * (B + 7) < 0x7FFFFFFF                               # noqa: E731
+    if N < 1 << 24 and (sv in (1, 2) or (sv == 0 and not flags & MR_F32 and N >= 160)):
         cw = fcw if (fcw and sv) else (16 if fits8(16) else 8 if fits8(8) else 4)
         if (sv and fits8(cw, 150 * 1024)) or fits8(cw):
             long_sweep = M > 512 and N >= 4 * M
@@ -422,9 +423,9 @@ def bwd_form(B, G, c, N, M, flags=0):
             return ("stream-f64" if sv == 2 else "stream"), cw, (nt, u, N <= (nt // (cw // 4)) * u)
         if sv:
             return "unsupported", None, None
-    if not flags & MR_F32 and (M <= 512 or sv == 3 or flags & MR_DET):
+    if not flags & MR_F32 and N < 1 << 24 and (M <= 512 or sv == 3 or flags & MR_DET):
         cw = fcw or (8 if fits8(8) else 4)
-        if fits8(cw):
+        if fits8(cw) and one_launch(cw):
             return "two-sweep", cw, None
     if flags & MR_DET:
         return ("private", 4, min(64, (144 * 1024) // (M * 16))) if (144 * 1024) // (M * 16) >= 1 else ("walk", 4, None)
@@ -434,7 +435,7 @@ def bwd_form(B, G, c, N, M, flags=0):
     while cw > 8 and (C // cw) * B < 512:
         cw >>= 1
     cw = fcw or cw
-    return ("lds-f32", cw, None) if M * cw * 4 <= LDS_BUDGET and div(cw) else ("global-f32", None, None)
+    return ("lds-f32", cw, None) if M * cw * 4 <= LDS_BUDGET and div(cw) and one_launch(cw) else ("global-f32", None, None)
 
 
 FIXED_POINT = ("stream", "two-sweep")                        # order-independent AND exact on the kinds of BWD_KINDS

@@ -1,5 +1,5 @@
 """The max-relative aggregation's backward entry points through the C ABI — gkg_mr_bwd_tm, gkg_mr_bwd_tm_bnstats and the channel-major
-gkg_mr_bwd (csrc/gkg_mr.hip) — against the fp64 definition tests/mr_ref.py::mr_bwd, in EVERY scatter form mr_bwd_tm_impl chooses
+gkg_mr_bwd (csrc/gkg_mr.hip) — against the fp64 definition tests/mr_ref.py::mr_bwd, in EVERY scatter form mr_bwd_tm_plan chooses
 among.  tests/test_mr_bwd_reference_host.py pins that definition on the CPU and proves, per case, that its fp64 sums are the exact
 sums; this file then asks for
 
