@@ -31,6 +31,7 @@
 //     from HBM into that L2 once.
 #include "gkg_common.h"
 #include <stdlib.h>
+#include <vector>
 
 namespace gkg {
 
@@ -673,98 +674,18 @@ __device__ __forceinline__ void x6w_slots(const X6WFrag& fc, X6WFrag& fn, x6_f32
   }
 }
 
-__global__ __launch_bounds__(256) void wgrad_x6_kernel(X6WgradArgs g) {
-  __shared__ float red[4 * 64 * 64];
-  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int z = blockIdx.y;
-  // XCD-aware: the tiles of one row slab run on one XCD (its rows are fetched into that L2 once)
-  const int ntile = g.mtiles * g.ntiles;
-  const int lin = blockIdx.x, xcd = lin & 7, slot = lin >> 3;
-  const int split = (slot / ntile) * 8 + xcd, tile = slot % ntile;
-  if (split >= g.splits) return;
-  const int m0 = (tile / g.ntiles) * 64, n0 = (tile % g.ntiles) * 64;
-  const int r = lane & 31, h = lane >> 5;
-  const int rows_per_wave = g.rows_per_split >> 2;
-  const long long k_begin = (long long)split * g.rows_per_split + (long long)w * rows_per_wave;
-  const int T = rows_per_wave >> 4;                                  // 16-row steps of this wave (even)
-  const char* Az = (const char*)(g.A + (size_t)z * g.a_bstride);
-  const char* Bz = (const char*)(g.B + (size_t)z * g.b_bstride);
-  const long long abytes = (long long)g.K * g.lda * 4, bbytes = (long long)g.K * g.ldb * 4;
-
-  // per-lane byte offset of each fragment's first row (8 h) at its column; the 8 rows j of a fragment come from 8
-  // descriptors whose base is advanced by j rows (so the hardware range check stays exact at the end of the tensor);
-  // columns outside the matrix get an offset no range check passes
-  unsigned off[4];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int ca = m0 + 32 * i + r, cb = n0 + 32 * i + r;
-    off[i] = ca < g.M ? (unsigned)((8 * h * g.lda + ca) * 4) : 0xfffffff0u;
-    off[2 + i] = cb < g.N ? (unsigned)((8 * h * g.ldb + cb) * 4) : 0xfffffff0u;
-  }
-  auto load = [&](float (&raw)[4][8], int s) __attribute__((always_inline)) {
-    const long long row0 = k_begin + 16ll * s;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const long long ao = (row0 + j) * g.lda * 4, bo = (row0 + j) * g.ldb * 4;
-      const long long ra_ = abytes - ao, rb_ = bbytes - bo;
-      const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)(Az + (ra_ > 0 ? ao : 0)), 0,
-                                                                          (int)(ra_ > 0 ? (ra_ > 0x7fffffffll ? 0x7fffffffll : ra_) : 0), 0x00020000);
-      const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)(Bz + (rb_ > 0 ? bo : 0)), 0,
-                                                                          (int)(rb_ > 0 ? (rb_ > 0x7fffffffll ? 0x7fffffffll : rb_) : 0), 0x00020000);
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        raw[i][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ra, off[i], 0, 0));
-        raw[2 + i][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rb, off[2 + i], 0, 0));
-      }
-    }
-  };
-  float raw0[4][8], raw1[4][8];                 // raw fragments two 16-row steps deep
-  X6WFrag fr0, fr1;
-  unsigned t0[4], t1[4];
-  x6_f32x16 acc[2][2], accs[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int q = 0; q < 16; ++q) { acc[i][j][q] = 0.f; accs[i][j][q] = 0.f; }
-
-  // one 16-row step s: MFMAs on `fc`; the gaps split `rs` (step s + 1) into `fn`; then `rs` is reloaded for step s + 3.
-  // The last step (no split) is peeled out of the loop: two variants of the MFMA chain inside it would put the
-  // accumulators behind phi nodes (the register allocator then copies whole tiles per MFMA).
-  load(raw0, 0);
-  if (T > 1) load(raw1, 1);
-  x6w_ops<0, 176>(raw0, fr0, t0, t1);
-  if (T > 2) load(raw0, 2);
-  for (int s = 0; s + 2 < T; s += 2) {          // buffer roles alternate: 2 steps per trip (T is even)
-    x6w_slots<0, true>(fr0, fr1, acc, accs, raw1, t0, t1);       // step s: splits step s+1 (raw1) ...
-    if (s + 3 < T) load(raw1, s + 3);                             // ... then raw1 <- step s+3
-    x6w_slots<0, true>(fr1, fr0, acc, accs, raw0, t0, t1);       // step s+1: splits step s+2 (raw0)
-    if (s + 4 < T) load(raw0, s + 4);
-  }
-  x6w_slots<0, true>(fr0, fr1, acc, accs, raw1, t0, t1);         // step T-2
-  x6w_slots<0, false>(fr1, fr0, acc, accs, raw0, t0, t1);        // step T-1
-
-  // ---- the four waves' tiles -> LDS -> one atomic add per element
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const int row = 32 * i + (q & 3) + 8 * (q >> 2) + 4 * h, col = 32 * j + r;
-        red[w * 4096 + row * 64 + col] = acc[i][j][q] + accs[i][j][q];
-      }
-  __syncthreads();
-  float* C = g.C + (size_t)z * g.c_bstride;
-#pragma unroll
-  for (int u = 0; u < 16; ++u) {
-    const int e = tid + 256 * u, row = e >> 6, col = e & 63;
-    const float v = (red[e] + red[4096 + e]) + (red[8192 + e] + red[12288 + e]);
-    if (m0 + row < g.M && n0 + col < g.N)
-      __hip_atomic_fetch_add(C + (size_t)(m0 + row) * g.ldc + (g.kperm ? x6_kperm_src(n0 + col, g.N) : n0 + col), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
+// DET (all three bodies): the workgroup STORES its tile of slab `split` into image `split` of a workspace (g.C: image 0 of this
+// launch, `sstride` floats per image of nb x M x N elements, laid out like dW) instead of adding it to dW — the deterministic
+// entry points (gkg_linear_wgrad_x6_det), whose ordered reduction (wgrad_x6_det_reduce_kernel) then writes dW.  Same
+// decomposition and arithmetic up to that store; the atomic forms are the kernels they were before the deterministic ones came.
+// The register-load kernel's text is gkg_wgrad_x6_rows.h, compiled in both forms (as a template body called from two kernels
+// the atomic form came out with 16 more VGPRs); the two LDS-DMA bodies are templates.
+#define X6W_DET 0
+#include "gkg_wgrad_x6_rows.h"
+#undef X6W_DET
+#define X6W_DET 1
+#include "gkg_wgrad_x6_rows.h"
+#undef X6W_DET
 
 // The same workgroup / wave decomposition with the rows staged through LDS: each wave copies the next 16 rows of its own K
 // range (64 columns of dY, 64 of X: 8 KiB) global -> a private 4-stage LDS ring by LDS-DMA — eight 16-byte-per-lane
@@ -790,7 +711,8 @@ __device__ __forceinline__ bool x6w_map(const X6WgradArgs& g, int lin, int& spli
   return split < g.splits;
 }
 
-__device__ __forceinline__ void wgrad_x6_dma_body(const X6WgradArgs& g, const int lin, const int z) {
+template <bool DET>
+__device__ __forceinline__ void wgrad_x6_dma_body(const X6WgradArgs& g, const int lin, const int z, const size_t sstride) {
   extern __shared__ float wlds[];               // [4 waves][4 stages][2 operands][16 rows][64 cols], then reused for the reduce
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   int split, tile;
@@ -903,12 +825,16 @@ __device__ __forceinline__ void wgrad_x6_dma_body(const X6WgradArgs& g, const in
   for (int u = 0; u < 16; ++u) {
     const int e = tid + 256 * u, row = e >> 6, col = e & 63;
     const float v = (red[e] + red[4096 + e]) + (red[8192 + e] + red[12288 + e]);
-    if (m0 + row < g.M && n0 + col < g.N)
-      __hip_atomic_fetch_add(C + (size_t)(m0 + row) * g.ldc + (g.kperm ? x6_kperm_src(n0 + col, g.N) : n0 + col), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (m0 + row < g.M && n0 + col < g.N) {
+      float* dst = C + (size_t)(m0 + row) * g.ldc + (g.kperm ? x6_kperm_src(n0 + col, g.N) : n0 + col);
+      if constexpr (DET) dst[(size_t)split * sstride] = v;
+      else __hip_atomic_fetch_add(dst, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
   }
 }
 
-__global__ __launch_bounds__(256) void wgrad_x6_dma_kernel(X6WgradArgs g) { wgrad_x6_dma_body(g, blockIdx.x, blockIdx.y); }
+__global__ __launch_bounds__(256) void wgrad_x6_dma_kernel(X6WgradArgs g) { wgrad_x6_dma_body<false>(g, blockIdx.x, blockIdx.y, 0); }
+__global__ __launch_bounds__(256) void wgrad_x6_dma_det_kernel(X6WgradArgs g, size_t sstride) { wgrad_x6_dma_body<true>(g, blockIdx.x, blockIdx.y, sstride); }
 
 // ---- wide form: 64 x 128 output tile per workgroup --------------------------------------------------------------------
 // Same decomposition (a workgroup = one tile of dW x one slab of rows, its 4 waves a quarter of the slab each, private LDS
@@ -959,7 +885,8 @@ __device__ __forceinline__ void x6ww_slots(const X6WFragW& fc, X6WFragW& fn, x6_
   }
 }
 
-__device__ __forceinline__ void wgrad_x6_wide_body(const X6WgradArgs& g, const int lin, const int z) {
+template <bool DET>
+__device__ __forceinline__ void wgrad_x6_wide_body(const X6WgradArgs& g, const int lin, const int z, const size_t sstride) {
   extern __shared__ float wlds[];               // [4 waves][3 stages][16 x 64 | 16 x 128], then reused for the reduce
   constexpr int STAGE_BYTES = 16 * 192 * 4, STAGE_F = 16 * 192;
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1083,12 +1010,14 @@ __device__ __forceinline__ void wgrad_x6_wide_body(const X6WgradArgs& g, const i
       const int wr = g.swap ? n0 + col : m0 + row, wc0 = g.swap ? m0 + row : n0 + col;
       const int wc = g.kperm ? x6_kperm_src(wc0, g.swap ? g.M : g.N) : wc0;
       float* dst = C + (size_t)wr * g.ldc + wc;
-      __hip_atomic_fetch_add(dst, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if constexpr (DET) dst[(size_t)split * sstride] = v;
+      else __hip_atomic_fetch_add(dst, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
 }
 
-__global__ __launch_bounds__(256) void wgrad_x6_wide_kernel(X6WgradArgs g) { wgrad_x6_wide_body(g, blockIdx.x, blockIdx.y); }
+__global__ __launch_bounds__(256) void wgrad_x6_wide_kernel(X6WgradArgs g) { wgrad_x6_wide_body<false>(g, blockIdx.x, blockIdx.y, 0); }
+__global__ __launch_bounds__(256) void wgrad_x6_wide_det_kernel(X6WgradArgs g, size_t sstride) { wgrad_x6_wide_body<true>(g, blockIdx.x, blockIdx.y, sstride); }
 
 // ---- batched form: the weight gradients of SEVERAL layers in one launch ------------------------------------------------
 // A weight gradient is off the backward's critical path (nothing downstream reads dW), and at this path's sizes each one is
@@ -1113,8 +1042,58 @@ __global__ __launch_bounds__(256) void wgrad_x6_batch_kernel(X6WgradBatch b) {
   const int local = bid - b.begin[i], gx = b.gridx[i];
   const int z = local / gx, lin = local - z * gx;
   const X6WgradArgs g = b.p[i];
-  if (b.wide[i]) wgrad_x6_wide_body(g, lin, z);
-  else wgrad_x6_dma_body(g, lin, z);
+  if (b.wide[i]) wgrad_x6_wide_body<false>(g, lin, z, 0);
+  else wgrad_x6_dma_body<false>(g, lin, z, 0);
+}
+
+// The deterministic batch: the same launch with every problem's tiles stored into that problem's slab images (p[i].C: image 0)
+struct X6WgradBatchDet {
+  X6WgradBatch b;
+  size_t sstride[X6W_BATCH];                    // floats per slab image of problem i (nb x cout x cin)
+};
+
+__global__ __launch_bounds__(256) void wgrad_x6_batch_det_kernel(X6WgradBatchDet d) {
+  const int bid = blockIdx.x;
+  int i = 0;
+  while (i + 1 < d.b.n && bid >= d.b.begin[i + 1]) ++i;
+  const int local = bid - d.b.begin[i], gx = d.b.gridx[i];
+  const int z = local / gx, lin = local - z * gx;
+  const X6WgradArgs g = d.b.p[i];
+  if (d.b.wide[i]) wgrad_x6_wide_body<true>(g, lin, z, d.sstride[i]);
+  else wgrad_x6_dma_body<true>(g, lin, z, d.sstride[i]);
+}
+
+// The ordered reduction behind the deterministic launches: thread e of problem i walks the S slab images of its element in
+// slab order, dw[e] = (((0 + P_0) + P_1) + ...) + P_{S-1} — fp32, eight independent loads in flight, the adds sequential —
+// and stores it: every element of dw exactly once, whatever it held.  Workgroups [begin[i], begin[i+1]) serve problem i.
+struct X6WdetReduce {
+  int n;
+  int S[X6W_BATCH];
+  int begin[X6W_BATCH + 1];
+  float* dw[X6W_BATCH];
+  const float* ws[X6W_BATCH];
+  size_t E[X6W_BATCH];
+};
+
+__global__ __launch_bounds__(256) void wgrad_x6_det_reduce_kernel(X6WdetReduce d) {
+  const int bid = blockIdx.x;
+  int i = 0;
+  while (i + 1 < d.n && bid >= d.begin[i + 1]) ++i;
+  const size_t E = d.E[i], e = (size_t)(bid - d.begin[i]) * 256 + threadIdx.x;
+  if (e >= E) return;
+  const float* p = d.ws[i] + e;
+  const int S = d.S[i];
+  float v = 0.f;
+  int s = 0;
+  for (; s + 8 <= S; s += 8) {
+    float t[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) t[j] = p[(size_t)(s + j) * E];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v += t[j];
+  }
+  for (; s < S; ++s) v += p[(size_t)s * E];
+  d.dw[i][e] = v;
 }
 
 inline bool x6_bad_dim(int v) { return v <= 0 || (v & 3) != 0; }
@@ -1480,7 +1459,8 @@ static int x6_wgrad_set_attr(bool wide) {
 // problems (gkg_linear_wgrad_x6_batch) — slabs of ~`batched` units whatever the tile count, few-slab problems spread over the
 // XCDs by tiles.
 static int x6_wgrad_plan(const float* dy, int ldg, size_t g_bstride, const float* x, int ldx, size_t x_bstride, float* dw, int R,
-                         int cin, int cout, int nb, int batched, X6WgradPlan& pl, int kperm = 0) {
+                         int cin, int cout, int nb, int batched, X6WgradPlan& pl, int kperm = 0, int force_slabs = 0,
+                         int aligned_as = -1) {
   if (!dy || !x || !dw) return gkg_fail(GKG_ERR_NULL, "gkg_linear_wgrad_x6: null pointer");
   if (kperm && (cin & 1)) return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_wgrad_x6: kperm needs an even cin");
   if (R <= 0 || cin <= 0 || cout <= 0 || nb <= 0 || nb > 64 || ldg < cout || ldx < cin)
@@ -1495,8 +1475,10 @@ static int x6_wgrad_plan(const float* dy, int ldg, size_t g_bstride, const float
   a.mtiles = (cout + 63) / 64; a.ntiles = (cin + 63) / 64;
   // whole 128-row units go through an LDS-DMA kernel when the rows are 16-byte aligned; the ragged rest (and everything,
   // when they are not) through the register-load kernel
-  const bool aligned = (cin & 3) == 0 && (cout & 3) == 0 && (ldg & 3) == 0 && (ldx & 3) == 0 && (g_bstride & 3) == 0 &&
-                       (x_bstride & 3) == 0 && ((size_t)dy & 15) == 0 && ((size_t)x & 15) == 0 &&
+  // (aligned_as >= 0, the host-side queries of the deterministic form: the caller's word for the pointers and batch strides)
+  const bool aligned = (cin & 3) == 0 && (cout & 3) == 0 && (ldg & 3) == 0 && (ldx & 3) == 0 &&
+                       (aligned_as >= 0 ? aligned_as != 0
+                                        : (g_bstride & 3) == 0 && (x_bstride & 3) == 0 && ((size_t)dy & 15) == 0 && ((size_t)x & 15) == 0) &&
                        (size_t)R * ldg * 4 < 0xffffffffull && (size_t)R * ldx * 4 < 0xffffffffull;
   // 64 x 128 tiles (wgrad_x6_wide_kernel) when one of the two widths pads to 128 at no more than a tenth of extra work
   // (measured in the cfg2 step, wide vs 64 x 64: 640 -> 320 42.6 -> 35.6 us, 1280 -> 320 37.9 -> 30.9, but 320 -> 320 at
@@ -1550,7 +1532,8 @@ static int x6_wgrad_plan(const float* dy, int ldg, size_t g_bstride, const float
     // over tiles x ceil(slabs / 8) workgroups: pick the slab count that minimises rounds x (units per slab + fixed cost), the
     // fixed cost (ring fill, LDS reduction, the tile's atomics) being worth about 6 units of streaming.  (Counting rounds over
     // the whole chip instead put 36 workgroups on two XCDs at 6 tiles x 42 slabs: 245 -> 393 us at 663 552 x 160 -> 80.)
-    splits = sp_alone;
+    // (force_slabs > 0, gkg_linear_wgrad_x6_det: the caller's slab count, cut to the number of units below)
+    splits = force_slabs > 0 ? force_slabs : sp_alone;
   }
   a.rows_per_split = units > 0 ? (units + splits - 1) / splits * 128 : 128;
   const int main_rows = aligned ? units * 128 : 0;
@@ -1664,4 +1647,229 @@ extern "C" int gkg_linear_wgrad_x6_batch(const GkgWgradProblem* p, int n, int un
     }
   }
   return flush();
+}
+
+// ---- deterministic weight gradients (gkg_linear_wgrad_x6_det, _batch_det; include/gkg_hip.h has the definition) ---------------
+// The launches of the entry points above with the DET instantiations of their bodies — slab s of the plan stores its tiles into
+// image s of the caller's workspace (main launch's slabs first, then the ragged remainder's, both in ascending row order) —
+// and ONE small launch behind them that adds the images in that order and writes dW.  No atomics, no memset, no counters: the
+// kernel boundary orders the partial stores before the reduction's loads.
+namespace gkg {
+constexpr size_t X6W_SH_WIDE = (size_t)4 * 3 * 16 * 192 * 4, X6W_SH_DMA = (size_t)4 * 4 * 8192;
+
+static int x6_wdet_set_attr(int kind) {          // 0: 64 x 64 DMA body, 1: wide body, 2: batch
+  static bool once[3][64] = {};
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (dev < 0 || dev >= 64 || !once[kind][dev]) {
+    const void* f = kind == 0 ? (const void*)wgrad_x6_dma_det_kernel
+                              : kind == 1 ? (const void*)wgrad_x6_wide_det_kernel : (const void*)wgrad_x6_batch_det_kernel;
+    hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kind == 0 ? X6W_SH_DMA : X6W_SH_WIDE));
+    if (e != hipSuccess) return gkg_fail_hip(e, "wgrad_x6 deterministic kernel (attribute)");
+    if (dev >= 0 && dev < 64) once[kind][dev] = true;
+  }
+  return 0;
+}
+
+inline int x6_wdet_main_slabs(const X6WgradPlan& pl) { return pl.main.K > 0 ? pl.main.splits : 0; }
+inline int x6_wdet_slabs(const X6WgradPlan& pl) { return x6_wdet_main_slabs(pl) + (pl.rest.K > 0 ? pl.rest.splits : 0); }
+// elements of dw = floats of one slab image; the reduction's grid is counted in ints
+inline bool x6_wdet_elems_ok(int cin, int cout, int nb) {
+  return cin > 0 && cout > 0 && nb > 0 && (unsigned long long)nb * (unsigned long long)cout * (unsigned long long)cin <= (1ull << 31);
+}
+static const float* const X6W_ANY = reinterpret_cast<const float*>(16);      // the queries plan without operands
+
+// the reduction launches of up to X6W_BATCH problems each
+struct X6WdetReducer {
+  X6WdetReduce d{};
+  hipStream_t st;
+  int flush() {
+    if (d.n == 0) return 0;
+    hipLaunchKernelGGL(wgrad_x6_det_reduce_kernel, dim3(d.begin[d.n]), dim3(256), 0, st, d);
+    hipError_t e = hipGetLastError();
+    d.n = 0;
+    return e == hipSuccess ? 0 : gkg_fail_hip(e, "wgrad_x6_det_reduce_kernel");
+  }
+  int add(float* dw, const float* ws, size_t E, int S) {
+    const long long blocks = (long long)((E + 255) / 256);
+    if (d.n == X6W_BATCH || (d.n > 0 && (long long)d.begin[d.n] + blocks > 0x7fffffffll)) {
+      int rc = flush();
+      if (rc) return rc;
+    }
+    const int i = d.n;
+    d.dw[i] = dw; d.ws[i] = ws; d.E[i] = E; d.S[i] = S;
+    d.begin[i + 1] = d.begin[i] + (int)blocks;
+    d.n = i + 1;
+    return 0;
+  }
+};
+}  // namespace gkg
+
+extern "C" size_t gkg_linear_wgrad_x6_det_workspace_bytes(int R, int cin, int cout, int nb, int ldg, int ldx, int slabs) {
+  if (slabs < 0 || slabs > 4096 || !x6_wdet_elems_ok(cin, cout, nb)) return 0;
+  int S = 0;
+  for (int al = 0; al < 2; ++al) {               // the larger of the aligned and the unaligned plan
+    X6WgradPlan pl;
+    if (x6_wgrad_plan(X6W_ANY, ldg, 0, X6W_ANY, ldx, 0, const_cast<float*>(X6W_ANY), R, cin, cout, nb, 0, pl, 0, slabs, al)) return 0;
+    const int s = x6_wdet_slabs(pl);
+    if (s > S) S = s;
+  }
+  return ((size_t)S * nb * cout * cin * 4 + 15) & ~(size_t)15;
+}
+
+extern "C" int gkg_linear_wgrad_x6_det_slabs(int R, int cin, int cout, int nb, int ldg, int ldx, int aligned, int units_per_slab,
+                                             int slabs, int* first_row, int* rows, int cap) {
+  if (slabs < 0 || slabs > 4096 || units_per_slab < 0 || units_per_slab > 4096)
+    return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_wgrad_x6_det_slabs: slabs / units_per_slab out of range");
+  if (cap > 0 && (!first_row || !rows)) return gkg_fail(GKG_ERR_NULL, "gkg_linear_wgrad_x6_det_slabs: null pointer");
+  if (!x6_wdet_elems_ok(cin, cout, nb) && cin > 0 && cout > 0 && nb > 0)
+    return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_wgrad_x6_det: more than 2^31 elements of dw");
+  X6WgradPlan pl;
+  int rc = x6_wgrad_plan(X6W_ANY, ldg, 0, X6W_ANY, ldx, 0, const_cast<float*>(X6W_ANY), R, cin, cout, nb, units_per_slab, pl, 0,
+                         units_per_slab > 0 ? 0 : slabs, aligned ? 1 : 0);
+  if (rc) return rc;
+  int n = 0;
+  const X6WgradArgs& m = pl.main;
+  for (int s = 0; s < x6_wdet_main_slabs(pl); ++s, ++n)
+    if (n < cap) {
+      first_row[n] = 128 * (s * m.ubase + (s < m.urem ? s : m.urem));
+      rows[n] = 128 * (m.ubase + (s < m.urem ? 1 : 0));
+    }
+  if (pl.rest.K > 0) {
+    const int done = R - pl.rest.K;
+    for (int s = 0; s < pl.rest.splits; ++s, ++n)
+      if (n < cap) {
+        first_row[n] = done + s * pl.rest.rows_per_split;
+        rows[n] = pl.rest.K - s * pl.rest.rows_per_split < pl.rest.rows_per_split ? pl.rest.K - s * pl.rest.rows_per_split
+                                                                                  : pl.rest.rows_per_split;
+      }
+  }
+  return n;
+}
+
+extern "C" int gkg_linear_wgrad_x6_det(const float* dy, int ldg, size_t g_bstride, const float* x, int ldx, size_t x_bstride,
+                                       float* dw, int R, int cin, int cout, int nb, int kperm, int slabs, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+  if (slabs < 0 || slabs > 4096) return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_wgrad_x6_det: slabs out of range (0 .. 4096)");
+  X6WgradPlan pl;
+  int rc = x6_wgrad_plan(dy, ldg, g_bstride, x, ldx, x_bstride, dw, R, cin, cout, nb, 0, pl, kperm, slabs);
+  if (rc) return rc;
+  if (!x6_wdet_elems_ok(cin, cout, nb)) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_wgrad_x6_det: more than 2^31 elements of dw");
+  const size_t need = gkg_linear_wgrad_x6_det_workspace_bytes(R, cin, cout, nb, ldg, ldx, slabs);
+  if (!workspace || ((size_t)workspace & 15) || workspace_bytes < need || need == 0)
+    return gkg_fail(GKG_ERR_WORKSPACE, "gkg_linear_wgrad_x6_det: workspace NULL, not 16-byte aligned or below gkg_linear_wgrad_x6_det_workspace_bytes()");
+  hipStream_t st = (hipStream_t)stream;
+  float* ws = (float*)workspace;
+  const size_t E = (size_t)nb * cout * cin;
+  const int Sm = x6_wdet_main_slabs(pl), S = x6_wdet_slabs(pl);
+  if (pl.main.K > 0) {
+    if ((rc = x6_wdet_set_attr(pl.wide ? 1 : 0))) return rc;
+    pl.main.C = ws;
+    const dim3 grid(pl.grid_x, nb);
+    if (pl.wide) hipLaunchKernelGGL(wgrad_x6_wide_det_kernel, grid, dim3(256), X6W_SH_WIDE, st, pl.main, E);
+    else hipLaunchKernelGGL(wgrad_x6_dma_det_kernel, grid, dim3(256), X6W_SH_DMA, st, pl.main, E);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return gkg_fail_hip(e, "wgrad_x6 deterministic DMA kernel");
+  }
+  if (pl.rest.K > 0) {
+    pl.rest.C = ws + (size_t)Sm * E;
+    hipLaunchKernelGGL(wgrad_x6_det_kernel, dim3(pl.rest_grid_x, nb), dim3(256), 0, st, pl.rest, E);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return gkg_fail_hip(e, "wgrad_x6_det_kernel");
+  }
+  X6WdetReducer red;
+  red.st = st;
+  if ((rc = red.add(dw, ws, E, S))) return rc;
+  return red.flush();
+}
+
+namespace gkg {
+// validation and plans of a deterministic batch, in launch order (largest problems first); `floats`: the workspace they need
+static int x6_wdet_batch_plan(const GkgWgradProblem* p, int n, int units_per_slab, int* order, std::vector<X6WgradPlan>& pls,
+                              size_t& floats) {
+  if (!p || n <= 0) return gkg_fail(GKG_ERR_NULL, "gkg_linear_wgrad_x6_batch_det: no problems");
+  if (units_per_slab < 0 || units_per_slab > 4096) return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_wgrad_x6_batch_det: units_per_slab out of range");
+  if (n > 256) return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_wgrad_x6_batch_det: at most 256 problems per call");
+  if (units_per_slab == 0) units_per_slab = 20;
+  for (int i = 0; i < n; ++i) order[i] = i;
+  auto work = [&](int i) { return (double)p[i].R * p[i].cin * p[i].cout * p[i].nb; };
+  for (int i = 1; i < n; ++i)                     // insertion sort, descending work
+    for (int j = i; j > 0 && work(order[j]) > work(order[j - 1]); --j) { const int t = order[j]; order[j] = order[j - 1]; order[j - 1] = t; }
+  pls.resize(n);
+  floats = 0;
+  for (int oi = 0; oi < n; ++oi) {
+    const GkgWgradProblem& q = p[order[oi]];
+    int rc = x6_wgrad_plan(q.dy, q.ldg, q.g_bstride, q.x, q.ldx, q.x_bstride, q.dw, q.R, q.cin, q.cout, q.nb, units_per_slab, pls[oi], q.kperm);
+    if (rc) return rc;
+    if (!x6_wdet_elems_ok(q.cin, q.cout, q.nb)) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_wgrad_x6_batch_det: more than 2^31 elements of a dw");
+    floats += (size_t)x6_wdet_slabs(pls[oi]) * q.nb * q.cout * q.cin;
+  }
+  return 0;
+}
+}  // namespace gkg
+
+extern "C" size_t gkg_linear_wgrad_x6_batch_det_workspace_bytes(const GkgWgradProblem* p, int n, int units_per_slab) {
+  int order[256];
+  std::vector<X6WgradPlan> pls;
+  size_t floats = 0;
+  if (x6_wdet_batch_plan(p, n, units_per_slab, order, pls, floats)) return 0;
+  return (floats * 4 + 15) & ~(size_t)15;
+}
+
+extern "C" int gkg_linear_wgrad_x6_batch_det(const GkgWgradProblem* p, int n, int units_per_slab, void* workspace,
+                                             size_t workspace_bytes, void* stream) {
+  int order[256];
+  std::vector<X6WgradPlan> pls;
+  size_t floats = 0;
+  int rc = x6_wdet_batch_plan(p, n, units_per_slab, order, pls, floats);
+  if (rc) return rc;
+  if (!workspace || ((size_t)workspace & 15) || workspace_bytes < ((floats * 4 + 15) & ~(size_t)15))
+    return gkg_fail(GKG_ERR_WORKSPACE, "gkg_linear_wgrad_x6_batch_det: workspace NULL, not 16-byte aligned or below gkg_linear_wgrad_x6_batch_det_workspace_bytes()");
+  hipStream_t st = (hipStream_t)stream;
+  X6WgradBatchDet b{};
+  int rot = 0;
+  auto flush = [&]() -> int {
+    if (b.b.n == 0) return 0;
+    int rc2 = x6_wdet_set_attr(2);
+    if (rc2) return rc2;
+    hipLaunchKernelGGL(wgrad_x6_batch_det_kernel, dim3(b.b.begin[b.b.n]), dim3(256), X6W_SH_WIDE, st, b);
+    hipError_t e = hipGetLastError();
+    b.b.n = 0;
+    return e == hipSuccess ? 0 : gkg_fail_hip(e, "wgrad_x6_batch_det_kernel");
+  };
+  float* cur = (float*)workspace;
+  for (int oi = 0; oi < n; ++oi) {                // every problem's slab images: one launch per 16 problems + the ragged remainders
+    const GkgWgradProblem& q = p[order[oi]];
+    X6WgradPlan& pl = pls[oi];
+    const size_t E = (size_t)q.nb * q.cout * q.cin;
+    if (pl.main.K > 0) {
+      const int i = b.b.n;
+      pl.main.rot = rot;
+      rot = (rot + (pl.main.share > 1 ? 0 : pl.main.splits)) & 7;
+      pl.main.C = cur;
+      b.b.p[i] = pl.main; b.b.wide[i] = pl.wide ? 1 : 0; b.b.gridx[i] = pl.grid_x; b.sstride[i] = E;
+      b.b.begin[i + 1] = b.b.begin[i] + pl.grid_x * q.nb;
+      b.b.n = i + 1;
+      if (b.b.n == X6W_BATCH && (rc = flush())) return rc;
+    }
+    if (pl.rest.K > 0) {
+      pl.rest.C = cur + (size_t)x6_wdet_main_slabs(pl) * E;
+      hipLaunchKernelGGL(wgrad_x6_det_kernel, dim3(pl.rest_grid_x, q.nb), dim3(256), 0, st, pl.rest, E);
+      hipError_t e = hipGetLastError();
+      if (e != hipSuccess) return gkg_fail_hip(e, "wgrad_x6_det_kernel");
+    }
+    cur += (size_t)x6_wdet_slabs(pl) * E;
+  }
+  if ((rc = flush())) return rc;
+  X6WdetReducer red;                              // then every dw, in slab order
+  red.st = st;
+  cur = (float*)workspace;
+  for (int oi = 0; oi < n; ++oi) {
+    const GkgWgradProblem& q = p[order[oi]];
+    const size_t E = (size_t)q.nb * q.cout * q.cin;
+    const int S = x6_wdet_slabs(pls[oi]);
+    if ((rc = red.add(q.dw, cur, E, S))) return rc;
+    cur += (size_t)S * E;
+  }
+  return red.flush();
 }

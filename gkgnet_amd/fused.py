@@ -52,7 +52,8 @@ if GEMM_MATH not in ("x6", "vendor"):
     raise ValueError(f"GKG_GEMM_MATH={GEMM_MATH!r}: expected x6 | vendor")
 # GKG_DETERMINISTIC=1 — run-to-run bit-identical backward: the neighbour-gradient scatter is order-independent by
 # construction (exact fixed-point accumulation, gkg_mr_bwd_tm); the atomically accumulated x6 weight gradients and the
-# fp64-atomic BN statistics give way to the library GEMM / the two-stage reductions.
+# fp64-atomic BN statistics give way to the library GEMM / the two-stage reductions (GKG_ENABLE=wgrad_det keeps the weight
+# gradients on the x6 kernels instead, in their run-independent form).
 DETERMINISTIC = os.environ.get("GKG_DETERMINISTIC", "0") != "0"
 # GKG_ENABLE — comma-separated list of OPT-IN modes (off by default):
 #   knn_bf16       under bf16 autocast the k-NN distance contraction runs on the bf16 matrix cores (GKG_KNN_BF16_CONTRACT:
@@ -96,6 +97,12 @@ DETERMINISTIC = os.environ.get("GKG_DETERMINISTIC", "0") != "0"
 #                  and the six-product x6 weight gradient.  bf16 autocast with gradients only; not under GKG_DETERMINISTIC (the
 #                  weight gradient adds its row slabs atomically); the grouped projection, fp16 autocast and the BN passes keep
 #                  their paths.  Opt-in: per-layer measurements in EXPERIMENTS.md.
+#   wgrad_det      with GKG_DETERMINISTIC=1 and GKG_GEMM_MATH=x6 only: the projections' weight gradients stay on the library's x6
+#                  kernels in their run-independent form (gkg_linear_wgrad_x6_det / _batch_det: the row slabs' partial tiles go to
+#                  a workspace and are added in slab order; no atomics, no cleared slot) instead of the vendor batched GEMM + sum —
+#                  the XM operand view with its column permutation included, and batched into one launch per backward pass like
+#                  the default path.  Bit-identical from run to run, but other bits than the vendor path's.  Without
+#                  GKG_DETERMINISTIC it does nothing.  Opt-in: measurements in EXPERIMENTS.md.
 # GKG_DISABLE — comma-separated list of optimisations to switch off (A/B measurements).  Round 6 cut the list to the eight
 # structural ones (the per-kernel switches of rounds 2-5 are gone with the alternatives they selected):
 #   knn_mr         k-NN + aggregation as one kernel (row g2)          knn_compact   u16 neighbour lists between two launches
@@ -121,6 +128,7 @@ FFN_BF16 = "ffn_bf16" in _ENABLED          # likewise; acts only together with L
 # likewise (False | True: the measured shapes | "all": every supported shape); acts only together with LIN_BF16 and MR_GEMM
 MR_FC2_BF16 = "all" if "mr_fc2_bf16_all" in _ENABLED else ("mr_fc2_bf16" in _ENABLED)
 TRAIN_BF16 = "train_bf16" in _ENABLED      # likewise a module constant the tests flip
+WGRAD_DET = "wgrad_det" in _ENABLED        # likewise; acts only together with DETERMINISTIC and GEMM_MATH == "x6"
 
 
 from .planes import (_WeightPlanes, _PLANES, _planes, refresh_weight_planes, param_version,      # noqa: E402,F401  (x6 weight
@@ -165,6 +173,24 @@ def _x6_wgrad_ok(dY, x, nb=1) -> bool:
     return max(dY.stride(-2), x.stride(-2)) * 4 * 16 <= 0x7fffffff and nb <= 64     # gkg_linear_wgrad_x6's row-pitch / batch limits
 
 
+def _x6_wgrad_det_ok(dY, x, nb=1) -> bool:
+    """The same kernels in their run-independent form (gkg_linear_wgrad_x6_det: every slab's partial tile stored to a workspace,
+    the slabs added in row order by a second small launch) — what GKG_DETERMINISTIC=1 runs with GKG_ENABLE=wgrad_det."""
+    if GEMM_MATH != "x6" or dY.dtype != _F32 or x.dtype != _F32 or not (DETERMINISTIC and WGRAD_DET):
+        return False
+    return max(dY.stride(-2), x.stride(-2)) * 4 * 16 <= 0x7fffffff and nb <= 64     # gkg_linear_wgrad_x6's row-pitch / batch limits
+
+
+def _wgrad_det_call(dY, ldg, g_bs, x, ldx, x_bs, out, R, cin, cout, nb, kperm, what):
+    """gkg_linear_wgrad_x6_det with the library's slab rule, the device's workspace (wgrad_queue.det_workspace) and the slot as
+    it is: the call overwrites every element."""
+    lib = _lib.load()
+    ws = _det_workspace(x.device, lib.gkg_linear_wgrad_x6_det_workspace_bytes(R, cin, cout, nb, ldg, ldx, 0))
+    _lib.check(lib.gkg_linear_wgrad_x6_det(_ptr(dY), ldg, g_bs, _ptr(x), ldx, x_bs, _ptr(out), R, cin, cout, nb, kperm, 0, _ptr(ws),
+                                           ws.numel(), _stream()), what)
+    return out
+
+
 # ---- batched weight gradients (round 5) ---------------------------------------------------------------------------------
 # wgrad_queue.py owns the queue and its protocol; here is the policy, what goes into it.  Queued only when the gradient has a slot
 # in a GradBucket (the kernel writes there; autograd adopts the returned view as ``p.grad``; GradBucket flushes the queue before
@@ -175,7 +201,7 @@ WGRAD_UNITS = 0          # rows per workgroup of the batched launch / 128 (0: th
 
 from . import parallel as _parallel      # noqa: E402
 from . import planes as _planes_mod      # noqa: E402
-from .wgrad_queue import QUEUE as _WQ    # noqa: E402
+from .wgrad_queue import QUEUE as _WQ, det_workspace as _det_workspace    # noqa: E402
 _parallel._ZERO_DEFER[:] = [_planes_mod.defer_zero, _planes_mod.flush_deferred_zero]
 
 
@@ -186,11 +212,12 @@ def flush_wgrads():
 
 def _wgrad_queue(device):
     """The queue to defer a weight gradient into right now (opened for the running backward pass on the current stream), or None:
-    batching switched off, or no backward pass that would flush it."""
-    if not (WGRAD_BATCH and not DETERMINISTIC and GEMM_MATH == "x6"):
+    batching switched off, or no backward pass that would flush it.  Under GKG_DETERMINISTIC it opens only for the run-independent
+    launch (WGRAD_DET: gkg_linear_wgrad_x6_batch_det)."""
+    if not (WGRAD_BATCH and (WGRAD_DET or not DETERMINISTIC) and GEMM_MATH == "x6"):
         return None
     task = _WQ.task_id()
-    return _WQ.open(task, device, WGRAD_UNITS) if task >= 0 else None
+    return _WQ.open(task, device, WGRAD_UNITS, det=DETERMINISTIC) if task >= 0 else None
 
 
 def _wgrad_defer(dY, x, out, R, cin, cout, nb, ldg, g_bs, ldx, x_bs, kperm=0) -> bool:
@@ -207,7 +234,7 @@ def _wgrad_defer(dY, x, out, R, cin, cout, nb, ldg, g_bs, ldx, x_bs, kperm=0) ->
     q = _wgrad_queue(dY.device)
     if q is None:
         return False
-    if not getattr(out, "_gkg_zero", False):
+    if not q.det and not getattr(out, "_gkg_zero", False):       # (the run-independent launch overwrites the slot)
         out.zero_()
     q.push((_lib.WgradProblem(dY.data_ptr(), x.data_ptr(), out.data_ptr(), g_bs, x_bs, ldg, ldx, R, cin, cout, nb, kperm),), (out,),
            (dY, x))
@@ -245,6 +272,11 @@ def _wgrad(dY: torch.Tensor, x: torch.Tensor, out=None) -> torch.Tensor:
         _lib.check(_lib.load().gkg_linear_wgrad_x6(_ptr(dY), dY.stride(0), 0, _ptr(x), x.stride(0), 0, _ptr(out), R, cin, cout,
                                                    1, 0, _stream()), "gkg_linear_wgrad_x6")
         return out
+    if _x6_wgrad_det_ok(dY, x) and dY.stride(1) == 1 and x.stride(1) == 1 and dY.stride(0) % 4 == 0 and x.stride(0) % 4 == 0:
+        cout, cin = dY.shape[1], x.shape[1]
+        if out is None:
+            out = torch.empty((cout, cin), dtype=_F32, device=x.device)
+        return _wgrad_det_call(dY, dY.stride(0), 0, x, x.stride(0), 0, out, R, cin, cout, 1, 0, "gkg_linear_wgrad_x6_det")
     if R >= 4096:                # short contractions (the label branch): the partial-sum kernel costs more than it saves
         for S in (8, 6, 4, 3, 2):
             if R % S == 0 and R // S >= 1024:
@@ -292,6 +324,12 @@ def _wgrad_grouped(dY: torch.Tensor, U: torch.Tensor, out=None, kperm=0) -> torc
         _lib.check(_lib.load().gkg_linear_wgrad_x6(_ptr(dY), dY.stride(1), dY.stride(0), _ptr(U), U.stride(1), U.stride(0), _ptr(out),
                                                    R, ci, co, nb, kperm, _stream()), "gkg_linear_wgrad_x6 (grouped)")
         return out
+    if (_x6_wgrad_det_ok(dY, U, nb) and dY.stride(2) == 1 and U.stride(2) == 1
+            and all(t.stride(d) % 4 == 0 for t in (dY, U) for d in (0, 1))):
+        if out is None:
+            out = torch.empty((nb, co, ci), dtype=_F32, device=U.device)
+        return _wgrad_det_call(dY, dY.stride(1), dY.stride(0), U, U.stride(1), U.stride(0), out, R, ci, co, nb, kperm,
+                               "gkg_linear_wgrad_x6_det (grouped)")
     if kperm:
         return _kperm_grad_back(_wgrad_grouped(dY, U.contiguous() if R >= 4096 else U, None, 0), out)
     if R >= 4096 and R % S == 0 and U.is_contiguous():

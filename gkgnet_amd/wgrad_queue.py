@@ -1,5 +1,6 @@
 """The deferred weight-gradient queue: the host-side protocol of the ONE batched dW launch at the end of a backward pass
-(gkg_linear_wgrad_x6_batch) — what is queued, what keeps its operands alive, where and when it is launched."""
+(gkg_linear_wgrad_x6_batch; under GKG_DETERMINISTIC with GKG_ENABLE=wgrad_det its run-independent form, _batch_det, and the
+workspace that form needs) — what is queued, what keeps its operands alive, where and when it is launched."""
 from __future__ import annotations
 
 import torch
@@ -44,6 +45,7 @@ class WgradQueue:
         self.items, self.keep, self.bytes, self.task = [], [], 0, -1
         self.stream, self.device = None, None        # where the queued operands are produced: the batch is launched THERE
         self.units = 0                               # rows per workgroup / 128 of that launch (fused.WGRAD_UNITS)
+        self.det = False                             # that launch is gkg_linear_wgrad_x6_batch_det (fused.WGRAD_DET)
 
     def task_id(self) -> int:
         """Id of the backward pass this thread is executing (-1: none — nobody would flush a queue —, or one that builds a graph:
@@ -60,8 +62,14 @@ class WgradQueue:
         torch.autograd.Variable._execution_engine.queue_callback(self.flush)
 
     def _launch_batch(self, arr, n):
+        lib = _lib.load()
         with torch.cuda.device(self.device):
-            _lib.check(_lib.load().gkg_linear_wgrad_x6_batch(arr, n, self.units, self.stream), "gkg_linear_wgrad_x6_batch")
+            if self.det:        # the run-independent form: partial tiles into a workspace, added in slab order (no cleared slots)
+                ws = det_workspace(self.device, lib.gkg_linear_wgrad_x6_batch_det_workspace_bytes(arr, n, self.units))
+                _lib.check(lib.gkg_linear_wgrad_x6_batch_det(arr, n, self.units, ws.data_ptr(), ws.numel(), self.stream),
+                           "gkg_linear_wgrad_x6_batch_det")
+            else:
+                _lib.check(lib.gkg_linear_wgrad_x6_batch(arr, n, self.units, self.stream), "gkg_linear_wgrad_x6_batch")
 
     def _order_caller_behind(self):
         ev = torch.cuda.Event()
@@ -70,18 +78,19 @@ class WgradQueue:
                       else torch.cuda.default_stream(self.device))
         torch.cuda.current_stream(self.device).wait_event(ev)
 
-    def open(self, task, device, units=0):
+    def open(self, task, device, units=0, det=False):
         """The queue of backward pass ``task`` on the current stream: registers the flush callback on the pass's first use, sends
         what another pass (a nested / re-entrant backward, or one that raised before its callback), stream or device left queued
-        out where it was produced."""
+        out where it was produced.  ``det``: its launch is the run-independent form (what was queued for the other form — slots
+        cleared or not — goes out first)."""
         st = self._raw_stream()
         if self.task != task:
             self._launch()
             self.task = task
             self._on_backward_end()
-        elif self.items and (self.stream != st or self.device != device):
+        elif self.items and (self.stream != st or self.device != device or self.det != bool(det)):
             self._launch()
-        self.stream, self.device, self.units = st, device, units
+        self.stream, self.device, self.units, self.det = st, device, units, bool(det)
         return self
 
     def push(self, problems, outs, keep):
@@ -118,6 +127,22 @@ class WgradQueue:
                 self._launch_batch((_lib.WgradProblem * len(items))(*items), len(items))
         finally:
             self.keep, self.bytes = [], 0
+
+
+_DET_WS = {}
+
+
+def det_workspace(device, nbytes) -> torch.Tensor:
+    """Workspace of the run-independent weight-gradient entry points (gkg_linear_wgrad_x6_det / _batch_det: the slabs' partial
+    tiles, include/gkg_hip.h): ONE grow-only buffer per device — its contents mean nothing between calls, and calls on a stream
+    are ordered.  A buffer that has to grow inside a hipGraph capture is not kept (it lives in the capture's pool)."""
+    key = (device.type, device.index)
+    t = _DET_WS.get(key)
+    if t is None or t.numel() < nbytes:
+        t = torch.empty(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=device)
+        if not torch.cuda.is_current_stream_capturing():
+            _DET_WS[key] = t
+    return t
 
 
 QUEUE = WgradQueue()

@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define GKG_ABI_VERSION 19
+#define GKG_ABI_VERSION 20
 
 /* dtype codes */
 #define GKG_F32 0
@@ -108,7 +108,7 @@ extern "C" {
 #define GKG_ERR_NULL -1        /* required pointer is NULL */
 #define GKG_ERR_SHAPE -2       /* non-positive / inconsistent sizes, k*dilation > M, ... */
 #define GKG_ERR_UNSUPPORTED -3 /* dtype / size outside what this build supports */
-#define GKG_ERR_WORKSPACE -4   /* workspace too small */
+#define GKG_ERR_WORKSPACE -4   /* workspace too small (gkg_linear_wgrad_x6_det: also NULL or not 16-byte aligned) */
 
 /* ABI version of the loaded library (== GKG_ABI_VERSION it was built with). */
 int gkg_version(void);
@@ -831,6 +831,48 @@ typedef struct GkgWgradProblem {
   int kperm;
 } GkgWgradProblem;
 int gkg_linear_wgrad_x6_batch(const GkgWgradProblem* problems, int n, int units_per_slab, void* stream);
+/* Run-independent forms of the two calls above (ABI 20): the same launches — the same tile shapes, row slabs, waves and
+ * per-workgroup arithmetic, down to the LDS reduction — except that the workgroup of slab s STORES its fp32 partial tile into a
+ * caller-owned workspace instead of adding it to dw with atomics, and one small launch behind them adds the partials in slab
+ * order and writes dw.  No atomics, no memset node, no host synchronisation: every launch is a kernel, capturable in a hipGraph.
+ *
+ * Definition.  For every element of every group
+ *     dw = (((0 + P_0) + P_1) + ... ) + P_{S-1}            all additions fp32, round to nearest
+ * where P_s is the float32 partial the workgroup of slab s computes for that element exactly as in gkg_linear_wgrad_x6: each of
+ * its four waves' acc + accs over its quarter of the slab's rows, the waves added (w0 + w1) + (w2 + w3).  Slab order: the main
+ * launch's slabs (whole 128-row units, 16-byte aligned operands) in ascending row order, then the remainder launch's slabs
+ * (ragged or unaligned rows) in ascending row order — what gkg_linear_wgrad_x6_det_slabs reports.  kperm is applied where the
+ * element is stored.  dw is OVERWRITTEN: each of its nb * cout * cin elements is stored exactly once; it need not be zero on
+ * entry and stale contents do not leak.  The result depends on the arguments only, never on the order in which workgroups run.
+ *
+ *   gkg_linear_wgrad_x6_det   slabs == 0: the library's slab rule (that of gkg_linear_wgrad_x6); slabs > 0 (tests,
+ *                             measurements): exactly min(slabs, R / 128) balanced main slabs — with one slab over R rows the
+ *                             call computes that slab's P.  `workspace`: at least gkg_linear_wgrad_x6_det_workspace_bytes()
+ *                             bytes for the same sizes, 16-byte aligned, contents irrelevant on entry and undefined afterwards;
+ *                             stream-ordered, so one buffer serves every call on a stream.
+ *   ..._det_workspace_bytes   pure host code; an upper bound over operand alignments (slab images of nb * cout * cin floats); 0
+ *                             where the call would fail on these arguments.
+ *   ..._det_slabs             pure host code: the slab count S of the call with these sizes (`aligned` != 0: base pointers % 16
+ *                             == 0 and batch strides % 4 == 0, which the sizes do not tell) and, for the first min(S, cap) slabs
+ *                             in reduction order, first row and row count.  units_per_slab > 0: the plan of this problem
+ *                             inside gkg_linear_wgrad_x6_batch_det called with that units_per_slab (`slabs` is ignored);
+ *                             units_per_slab == 0: the plan of gkg_linear_wgrad_x6_det with `slabs`.  < 0: GKG_ERR_*.
+ *   gkg_linear_wgrad_x6_batch_det   the problems of gkg_linear_wgrad_x6_batch (same struct, same plans, one launch per 16
+ *                             problems) under the definition above, then one reduction launch per 16 problems; workspace of
+ *                             gkg_linear_wgrad_x6_batch_det_workspace_bytes(problems, n, units_per_slab) bytes (pure host code,
+ *                             exact for these pointers; 0 where the call would fail).
+ * Errors: the argument errors of gkg_linear_wgrad_x6 / _batch; slabs outside 0 .. 4096 GKG_ERR_SHAPE; more than 2^31 elements
+ * in a dw GKG_ERR_UNSUPPORTED; GKG_ERR_WORKSPACE for a workspace that is NULL, too small or not 16-byte aligned.  Every argument
+ * of every problem is checked before the first launch: nothing is launched on any error. */
+int gkg_linear_wgrad_x6_det(const float* dy, int ldg, size_t g_bstride, const float* x, int ldx, size_t x_bstride, float* dw,
+                            int R, int cin, int cout, int nb, int kperm, int slabs, void* workspace, size_t workspace_bytes,
+                            void* stream);
+size_t gkg_linear_wgrad_x6_det_workspace_bytes(int R, int cin, int cout, int nb, int ldg, int ldx, int slabs);
+int gkg_linear_wgrad_x6_det_slabs(int R, int cin, int cout, int nb, int ldg, int ldx, int aligned, int units_per_slab, int slabs,
+                                  int* first_row, int* rows, int cap);
+int gkg_linear_wgrad_x6_batch_det(const GkgWgradProblem* problems, int n, int units_per_slab, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+size_t gkg_linear_wgrad_x6_batch_det_workspace_bytes(const GkgWgradProblem* problems, int n, int units_per_slab);
 
 /*
  * Input gradient of a projection with the BACKWARD statistics of the layer in front of it in its epilogue (round 4).
