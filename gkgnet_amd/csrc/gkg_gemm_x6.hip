@@ -616,8 +616,10 @@ static hipError_t x6_launch(X6Args a, int nb, hipStream_t st, void* sk_ws = null
 // the slab each (2 x 2 blocks of 32 x 32 per wave: 24 MFMAs per 16 rows), add their tiles through LDS and issue ONE set of
 // fp32 atomics into the pre-zeroed dW (summation order over slabs is run-dependent, like the vendor library's split-K).
 // Loads run three 16-row steps ahead in a 3-deep register ring; the 176-instruction split of the next step's four
-// fragments sits in the MFMA gaps (7-8 per gap: this kernel is VALU-bound at ~1.6x the matrix time — for the long-K,
-// small-output shapes it exists for it is the HBM stream that sets the time).
+// fragments sits in the MFMA gaps (7-8 per gap; the compiled loop, counted by tools/count_loop_insts.py, holds 417 vector and
+// 263 scalar instructions per 48 MFMAs — 8.7 / MFMA, most of the rest address and bounds arithmetic of the 32 loads: it is
+// address-bound, and for the long-K, small-output shapes it exists for it is the HBM stream that sets the time).  The three
+// kernels of this section share ONE definition of the split sequence (x6w_op).
 struct X6WgradArgs {
   const float* A;  size_t a_bstride;  int lda;       // dY (nb, K, M)
   const float* B;  size_t b_bstride;  int ldb;       // X  (nb, K, N)
@@ -632,16 +634,29 @@ struct X6WgradArgs {
 };
 
 typedef unsigned x6_u32x4 __attribute__((ext_vector_type(4)));
+typedef float x6_f32x2 __attribute__((ext_vector_type(2)));
 typedef x6_u32x4 X6WFrag[4][3];               // [A0, A1, B0, B1][hi, mid, lo]: 4 packed bf16 pairs = one MFMA operand each
+typedef x6_u32x4 X6WFragW[6][3];              // wide form: [A0, A1, B0, B1, B2, B3][hi, mid, lo]
 
 __device__ __forceinline__ x6_bf16x8 x6w_operand(const x6_u32x4& f) { return __builtin_bit_cast(x6_bf16x8, f); }
-// step I (0..175) of the split of four raw fragments into `fn`: block I / 44, and within a block the four pairs
-// interleaved (4 independent chains).  Single-instruction asm volatile: fixed order, not sunk, not SLP-packed.
-template <int I>
-__device__ __forceinline__ void x6w_op(float (&raw)[4][8], X6WFrag& fn, unsigned (&t0)[4], unsigned (&t1)[4]) {
+// step I (0 .. 44 NB - 1) of the split of NB raw fragments into `fn`: block I / 44, and within a block the four pairs
+// interleaved (4 independent chains).  Single-instruction asm volatile: fixed order, not sunk, not SLP-packed.  ONE definition
+// for the register-load kernel (NB = 4), the 64 x 64 LDS-DMA body (NB = 4) and the wide body (NB = 6).
+// The two residual subtractions of a pair stay two v_sub_f32: one v_pk_add_f32 on a register pair is 9 instructions per pair
+// instead of 11, but beside MFMAs the packed instruction costs more than the two it replaces (tools/ubench/mfma_bf16_fill,
+// ksplit: 28.4 against 23.1 ns per MFMA slot for this very stream; EXPERIMENTS.md).
+// LDSW (the LDS-DMA bodies): the fragments were read by x6w_readblk — 4 ds_read2 per block, in block order, which the compiler's
+// waitcnt bookkeeping does not see — so the first step of block b waits until at most the 4 (NB - 1 - b) reads of the later
+// blocks are outstanding (LDS reads return in order; 15 is the counter's largest operand, a smaller one only waits longer).
+template <int I, int NB, bool LDSW>
+__device__ __forceinline__ void x6w_op(float (&raw)[NB][8], x6_u32x4 (&fn)[NB][3], unsigned (&t0)[4], unsigned (&t1)[4]) {
   constexpr int blk = I / 44, u = I % 44, p = u & 3, o = u >> 2;
   float& x0 = raw[blk][2 * p]; float& x1 = raw[blk][2 * p + 1];
   unsigned w;
+  if constexpr (LDSW && u == 0) {
+    constexpr int left = 4 * (NB - 1 - blk);
+    asm volatile("s_waitcnt lgkmcnt(%0)" :: "n"(left < 15 ? left : 15) : "memory");
+  }
   if constexpr (o == 0) { asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(w) : "v"(x0), "v"(x1)); fn[blk][0][p] = w; }
   if constexpr (o == 1) asm volatile("v_lshlrev_b32 %0, 16, %1" : "=v"(t0[p]) : "v"(fn[blk][0][p]));
   if constexpr (o == 2) asm volatile("v_and_b32 %0, 0xffff0000, %1" : "=v"(t1[p]) : "v"(fn[blk][0][p]));
@@ -654,12 +669,12 @@ __device__ __forceinline__ void x6w_op(float (&raw)[4][8], X6WFrag& fn, unsigned
   if constexpr (o == 9) asm volatile("v_sub_f32 %0, %0, %1" : "+v"(x1) : "v"(t1[p]));
   if constexpr (o == 10) { asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(w) : "v"(x0), "v"(x1)); fn[blk][2][p] = w; }
 }
-template <int I, int END>
-__device__ __forceinline__ void x6w_ops(float (&raw)[4][8], X6WFrag& fn, unsigned (&t0)[4], unsigned (&t1)[4]) {
-  if constexpr (I < END && I < 176) { x6w_op<I>(raw, fn, t0, t1); x6w_ops<I + 1, END>(raw, fn, t0, t1); }
+template <int I, int END, bool LDSW = false, int NB>
+__device__ __forceinline__ void x6w_ops(float (&raw)[NB][8], x6_u32x4 (&fn)[NB][3], unsigned (&t0)[4], unsigned (&t1)[4]) {
+  if constexpr (I < END && I < 44 * NB) { x6w_op<I, NB, LDSW>(raw, fn, t0, t1); x6w_ops<I + 1, END, LDSW>(raw, fn, t0, t1); }
 }
 // MFMA slot SI (0..23) of a 16-row step: block (i, j) = SI / 6, product t = SI % 6; then 8 split steps in its shadow
-template <int SI, bool SPLIT>
+template <int SI, bool SPLIT, bool LDSW = false>
 __device__ __forceinline__ void x6w_slots(const X6WFrag& fc, X6WFrag& fn, x6_f32x16 (&acc)[2][2], x6_f32x16 (&accs)[2][2],
                                           float (&raw)[4][8], unsigned (&t0)[4], unsigned (&t1)[4]) {
   if constexpr (SI < 24) {
@@ -668,9 +683,9 @@ __device__ __forceinline__ void x6w_slots(const X6WFrag& fc, X6WFrag& fn, x6_f32
     constexpr int pb = t == 1 ? 2 : (t == 2 || t == 4) ? 1 : 0;
     if constexpr (t < 5) accs[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x6w_operand(fc[i][pa]), x6w_operand(fc[2 + j][pb]), accs[i][j], 0, 0, 0);
     else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x6w_operand(fc[i][0]), x6w_operand(fc[2 + j][0]), acc[i][j], 0, 0, 0);
-    if constexpr (SPLIT) x6w_ops<SI * 8, SI * 8 + 8>(raw, fn, t0, t1);
+    if constexpr (SPLIT) x6w_ops<SI * 8, SI * 8 + 8, LDSW>(raw, fn, t0, t1);
     __builtin_amdgcn_sched_barrier(0);
-    x6w_slots<SI + 1, SPLIT>(fc, fn, acc, accs, raw, t0, t1);
+    x6w_slots<SI + 1, SPLIT, LDSW>(fc, fn, acc, accs, raw, t0, t1);
   }
 }
 
@@ -692,8 +707,10 @@ __device__ __forceinline__ void x6w_slots(const X6WFrag& fc, X6WFrag& fn, x6_f32
 // instructions per step where the register form above needs 32 dword loads (16 address cycles per 256 B each: measured
 // texture-address-bound) — and reads the column fragments back with ds_read_b32.  No barriers: a wave only ever reads what
 // it copied itself.  Requires every row of the launch to be inside the tensor (the host gives the ragged remainder to the
-// register-load kernel) and 16-byte aligned rows; columns past M / N are read from a clamped address and zeroed after the
-// LDS read.  Step s issues the DMA of step s + 4, waits until step s + 2 has landed (counted vmcnt) and reads it.
+// register-load kernel) and 16-byte aligned rows; columns past M / N are DMA'd from a clamped address and never read: their
+// lanes read a zero-filled region instead (below).  Step s issues the DMA of step s + 4, waits until step s + 2 has landed
+// (counted vmcnt) and reads it.  Compiled loop (two steps, tools/count_loop_insts.py): 48 MFMAs, 370 vector instructions
+// (7.7 / MFMA, 7.33 of them the split), 57 scalar; edge and interior tiles run the same instructions.
 // (split, tile) of workgroup `lin` of a weight-gradient launch.  Default map: slab s runs with ALL its tiles on XCD s % 8 (lin & 7
 // is the XCD the hardware dispatches workgroup lin to).  g.share = t > 1 (batched launches of few-slab problems, splits * t == 8):
 // t XCDs share a slab and take every t-th tile of it each, so that a problem of 1 / 2 / 4 slabs still spreads over all 8 XCDs
@@ -709,6 +726,42 @@ __device__ __forceinline__ bool x6w_map(const X6WgradArgs& g, int lin, int& spli
   split = (slot / ntile) * 8 + xcd;
   tile = slot % ntile;
   return split < g.splits;
+}
+
+// Beside the rings lies a zero-filled region of X6W_ZERO_BYTES, cleared once per workgroup: a lane whose column lies outside
+// the matrix reads its fragments THERE (its read base is chosen per step from a per-lane mask, one select per block) instead
+// of reading the clamped column's values and zeroing them after every LDS read (8 selects per block).  Exactly 0.0f, as before.
+// The region covers the eight row offsets of a fragment at the 128-column pitch: 7 x 512 + 4 bytes.
+constexpr unsigned X6W_ZERO_BYTES = 4096;
+constexpr size_t X6W_SH_DMA = (size_t)4 * 4 * 8192 + X6W_ZERO_BYTES, X6W_SH_WIDE = (size_t)4 * 3 * 16 * 192 * 4 + X6W_ZERO_BYTES;
+
+// LDS-DMA of four consecutive 1-KiB pieces (x6_dma16) in one statement: M0 is saved and restored once and stepped by 1 KiB
+// between the pieces — 14 instructions where four x6_dma16 are 24.
+__device__ __forceinline__ void x6w_dma4(const void* sbase, unsigned v0, unsigned v1, unsigned v2, unsigned v3, unsigned lds_dst) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %5\n\t"
+               "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %5\n\t"
+               "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %5\n\t"
+               "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %5\n\t"
+               "s_mov_b32 m0, %0"
+               : "=&s"(keep) : "v"(v0), "v"(v1), "v"(v2), "v"(v3), "s"(sbase), "s"(lds_dst) : "memory", "scc");
+}
+// One fragment block: rows 0 .. 7 of one column from LDS byte address `addr`, row pitch 64 PB floats, as four ds_read2st64_b32
+// (rows 2p and 2p + 1 in one instruction, address + immediate: no per-row address arithmetic).  Asynchronous and unknown to
+// the compiler's waitcnt bookkeeping: the split steps wait (x6w_op, LDSW).
+template <int PB>
+__device__ __forceinline__ void x6w_readblk(float (&f)[8], unsigned addr) {
+  x6_f32x2 v0, v1, v2, v3;
+  asm volatile("ds_read2st64_b32 %0, %1 offset0:%2 offset1:%3" : "=v"(v0) : "v"(addr), "n"(0), "n"(PB) : "memory");
+  asm volatile("ds_read2st64_b32 %0, %1 offset0:%2 offset1:%3" : "=v"(v1) : "v"(addr), "n"(2 * PB), "n"(3 * PB) : "memory");
+  asm volatile("ds_read2st64_b32 %0, %1 offset0:%2 offset1:%3" : "=v"(v2) : "v"(addr), "n"(4 * PB), "n"(5 * PB) : "memory");
+  asm volatile("ds_read2st64_b32 %0, %1 offset0:%2 offset1:%3" : "=v"(v3) : "v"(addr), "n"(6 * PB), "n"(7 * PB) : "memory");
+  f[0] = v0.x; f[1] = v0.y; f[2] = v1.x; f[3] = v1.y; f[4] = v2.x; f[5] = v2.y; f[6] = v3.x; f[7] = v3.y;
+}
+// the workgroup clears the zero region (256 threads x 16 bytes); the caller's barrier orders it before the first fragment read
+__device__ __forceinline__ void x6w_clear_zero(float* wlds, unsigned ring_bytes, int tid) {
+  static_assert(X6W_ZERO_BYTES == 256 * 16, "one 16-byte store per thread");
+  reinterpret_cast<float4*>(wlds + ring_bytes / 4)[tid] = float4{0.f, 0.f, 0.f, 0.f};
 }
 
 template <bool DET>
@@ -729,43 +782,42 @@ __device__ __forceinline__ void wgrad_x6_dma_body(const X6WgradArgs& g, const in
   const int T = rows_per_wave >> 4;
   const char* Az = (const char*)(g.A + (size_t)z * g.a_bstride);
   const char* Bz = (const char*)(g.B + (size_t)z * g.b_bstride);
-  const unsigned lds0 = (unsigned)(size_t)wlds + w * (4 * 8192);
+  constexpr unsigned RING_BYTES = 4 * 4 * 8192;
+  const unsigned lds_base = (unsigned)(size_t)wlds;
+  const unsigned lds0 = lds_base + w * (4 * 8192), lds_end = lds0 + 4 * 8192, lds_zero = lds_base + RING_BYTES;
+  x6w_clear_zero(wlds, RING_BYTES, tid);
 
-  // DMA piece p (4 per operand): rows 4p .. 4p+3; lane -> row 4p + (lane >> 4), 16-byte column chunk lane & 15
+  // DMA piece p (4 per operand): rows 4p .. 4p+3; lane -> row 4p + (lane >> 4), 16-byte column chunk lane & 15.  The per-piece
+  // offsets are formed once; a step advances the two row bases and the destination stage
   const int prow = lane >> 4, pch = lane & 15;
-  const int ca = min(m0 + 4 * pch, g.M - 4), cb = min(n0 + 4 * pch, g.N - 4);      // clamped: masked after the LDS read
+  const int ca = min(m0 + 4 * pch, g.M - 4), cb = min(n0 + 4 * pch, g.N - 4);      // clamped: such columns are never read
   const unsigned dA = (unsigned)(((size_t)prow * g.lda + ca) * 4), dB = (unsigned)(((size_t)prow * g.ldb + cb) * 4);
   const unsigned strideA = (unsigned)g.lda * 16u, strideB = (unsigned)g.ldb * 16u;            // 4 rows, bytes
-  auto dma = [&](int s) __attribute__((always_inline)) {
-    const long long row0 = k_begin + 16ll * s;
-    const char* ab = Az + row0 * g.lda * 4;
-    const char* bb = Bz + row0 * g.ldb * 4;
-    const unsigned dst = lds0 + (s & 3) * 8192;
+  unsigned va[4], vb[4];
 #pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      x6_dma16(ab, dA + p * strideA, dst + p * 1024);
-      x6_dma16(bb, dB + p * strideB, dst + 4096 + p * 1024);
-    }
+  for (int p = 0; p < 4; ++p) { va[p] = dA + p * strideA; vb[p] = dB + p * strideB; }
+  const char* arow = Az + k_begin * g.lda * 4;                                                // step 0's 16 rows
+  const char* brow = Bz + k_begin * g.ldb * 4;
+  const size_t stepA = (size_t)g.lda * 64, stepB = (size_t)g.ldb * 64;                        // 16 rows, bytes
+  unsigned wr = lds0;                                                                         // stage the next DMA step fills
+  auto dma = [&]() __attribute__((always_inline)) {
+    x6w_dma4(arow, va[0], va[1], va[2], va[3], wr);
+    x6w_dma4(brow, vb[0], vb[1], vb[2], vb[3], wr + 4096);
+    arow += stepA; brow += stepB;
+    wr += 8192;
+    if (wr == lds_end) wr = lds0;
   };
-  // fragment (block i of operand o) of stage st: lane (r, h) reads rows 8h .. 8h+7 at column 32 i + r
-  const bool va0 = m0 + r < g.M, va1 = m0 + 32 + r < g.M, vb0 = n0 + r < g.N, vb1 = n0 + 32 + r < g.N;
-  const bool tail = m0 + 64 > g.M || n0 + 64 > g.N;                                           // uniform
-  auto readfr = [&](float (&raw)[4][8], int s) __attribute__((always_inline)) {
-    const float* base = wlds + w * (4 * 2048) + (s & 3) * 2048 + (8 * h) * 64 + r;
+  // fragment (block i of operand o) of a stage: lane (r, h) reads rows 8h .. 8h+7 at column 32 i + r — or the zero region
+  const bool ok[4] = {m0 + r < g.M, m0 + 32 + r < g.M, n0 + r < g.N, n0 + 32 + r < g.N};
+  unsigned lo[4];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      raw[0][j] = base[j * 64];
-      raw[1][j] = base[j * 64 + 32];
-      raw[2][j] = base[1024 + j * 64];
-      raw[3][j] = base[1024 + j * 64 + 32];
-    }
-    if (tail) {
+  for (int q = 0; q < 4; ++q) lo[q] = (unsigned)(((q >> 1) * 1024 + (8 * h) * 64 + 32 * (q & 1) + r) * 4);
+  unsigned rd = lds0;                                                                         // stage the next read step reads
+  auto readfr = [&](float (&raw)[4][8]) __attribute__((always_inline)) {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        raw[0][j] = va0 ? raw[0][j] : 0.f; raw[1][j] = va1 ? raw[1][j] : 0.f;
-        raw[2][j] = vb0 ? raw[2][j] : 0.f; raw[3][j] = vb1 ? raw[3][j] : 0.f;
-      }
-    }
+    for (int q = 0; q < 4; ++q) x6w_readblk<1>(raw[q], ok[q] ? rd + lo[q] : lds_zero);
+    rd += 8192;
+    if (rd == lds_end) rd = lds0;
   };
   float raw0[4][8], raw1[4][8];
   X6WFrag fr0, fr1;
@@ -779,32 +831,33 @@ __device__ __forceinline__ void wgrad_x6_dma_body(const X6WgradArgs& g, const in
       for (int q = 0; q < 16; ++q) { acc[i][j][q] = 0.f; accs[i][j][q] = 0.f; }
 
   // prologue: DMA steps 0..3; read steps 0 and 1; split step 0
-  dma(0);
-  if (T > 1) dma(1);
-  if (T > 2) dma(2);
-  if (T > 3) dma(3);
+  dma();
+  if (T > 1) dma();
+  if (T > 2) dma();
+  if (T > 3) dma();
+  __syncthreads();                              // the zero region is cleared
   if (T > 3) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
   else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  readfr(raw0, 0);
-  if (T > 1) readfr(raw1, 1);
-  x6w_ops<0, 176>(raw0, fr0, t0, t1);
+  readfr(raw0);
+  if (T > 1) readfr(raw1);
+  x6w_ops<0, 176, true>(raw0, fr0, t0, t1);
   // step s (fr[s&1]): splits raw[(s+1)&1] (step s+1); then DMA step s+4, wait for step s+2, read it into raw[s&1]
   auto tailwork = [&](float (&rawn)[4][8], int s) __attribute__((always_inline)) {
-    if (s + 4 < T) dma(s + 4);
+    if (s + 4 < T) dma();
     if (s + 2 < T) {
       if (s + 4 < T) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");       // steps s+3, s+4 may stay in flight
       else if (s + 3 < T) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      readfr(rawn, s + 2);
+      readfr(rawn);
     }
   };
   for (int s = 0; s + 2 < T; s += 2) {
-    x6w_slots<0, true>(fr0, fr1, acc, accs, raw1, t0, t1);     // step s: splits step s+1 (raw1) into fr1
-    tailwork(raw0, s);                                            // raw0 <- step s+2
-    x6w_slots<0, true>(fr1, fr0, acc, accs, raw0, t0, t1);     // step s+1: splits step s+2 (raw0) into fr0
-    tailwork(raw1, s + 1);                                        // raw1 <- step s+3
+    x6w_slots<0, true, true>(fr0, fr1, acc, accs, raw1, t0, t1);     // step s: splits step s+1 (raw1) into fr1
+    tailwork(raw0, s);                                                  // raw0 <- step s+2
+    x6w_slots<0, true, true>(fr1, fr0, acc, accs, raw0, t0, t1);     // step s+1: splits step s+2 (raw0) into fr0
+    tailwork(raw1, s + 1);                                              // raw1 <- step s+3
   }
-  x6w_slots<0, true>(fr0, fr1, acc, accs, raw1, t0, t1);
+  x6w_slots<0, true, true>(fr0, fr1, acc, accs, raw1, t0, t1);
   x6w_slots<0, false>(fr1, fr0, acc, accs, raw0, t0, t1);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
@@ -839,36 +892,17 @@ __global__ __launch_bounds__(256) void wgrad_x6_dma_det_kernel(X6WgradArgs g, si
 // ---- wide form: 64 x 128 output tile per workgroup --------------------------------------------------------------------
 // Same decomposition (a workgroup = one tile of dW x one slab of rows, its 4 waves a quarter of the slab each, private LDS
 // rings filled by DMA, no barriers in the loop), but a wave owns 2 x 4 blocks of 32 x 32: six fragments per 16-row step feed
-// 48 MFMAs, so the split is 264 / 48 = 5.5 vector instructions per MFMA — inside what a bf16 MFMA's shadow hides
-// (tools/ubench/mfma_bf16_fill) — where the 64 x 64 form needs 176 / 24 = 7.3 and runs at ~2.6x its matrix time.  The
+// 48 MFMAs, so the split is 264 / 48 = 5.5 vector instructions per MFMA where the 64 x 64 form needs 176 / 24 = 7.33.  The
+// compiled loop (two steps, tools/count_loop_insts.py) holds 96 MFMAs, 554 vector instructions (5.77 / MFMA: the split, and
+// per step six read-base additions and six selects) and 61 scalar, the same in edge and interior tiles; about 5 vector
+// instructions hide in a bf16 MFMA's shadow (tools/ubench/mfma_bf16_fill), so this loop is still paced by the split.  The
 // products are issued product-major over the eight accumulators (a dependent MFMA is 8 slots away), small terms first, all
 // into ONE accumulator per block: 128 accumulator registers + 2 x 48 raw + 2 x 72 split fragments fit the 512 of a
 // one-wave-per-SIMD kernel.  Ring: 3 stages x (16 x 64 of dY | 16 x 128 of X) x 4 B = 36 KiB per wave, 144 KiB per workgroup;
 // step s issues the DMA of step s + 3 into the stage whose rows were read two steps ago, waits (counted vmcnt) for step
-// s + 2 and reads its fragments, which are split during step s + 1.
-typedef x6_u32x4 X6WFragW[6][3];              // [A0, A1, B0, B1, B2, B3][hi, mid, lo]
+// s + 2 and reads its fragments, which are split during step s + 1.  The fragment reads are written out (x6w_readblk) and
+// waited for inside the split (x6w_op, LDSW); a step's twelve DMA pieces are three statements (x6w_dma4).
 
-template <int I>
-__device__ __forceinline__ void x6ww_op(float (&raw)[6][8], X6WFragW& fn, unsigned (&t0)[4], unsigned (&t1)[4]) {
-  constexpr int blk = I / 44, u = I % 44, p = u & 3, o = u >> 2;
-  float& x0 = raw[blk][2 * p]; float& x1 = raw[blk][2 * p + 1];
-  unsigned w;
-  if constexpr (o == 0) { asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(w) : "v"(x0), "v"(x1)); fn[blk][0][p] = w; }
-  if constexpr (o == 1) asm volatile("v_lshlrev_b32 %0, 16, %1" : "=v"(t0[p]) : "v"(fn[blk][0][p]));
-  if constexpr (o == 2) asm volatile("v_and_b32 %0, 0xffff0000, %1" : "=v"(t1[p]) : "v"(fn[blk][0][p]));
-  if constexpr (o == 3) asm volatile("v_sub_f32 %0, %0, %1" : "+v"(x0) : "v"(t0[p]));
-  if constexpr (o == 4) asm volatile("v_sub_f32 %0, %0, %1" : "+v"(x1) : "v"(t1[p]));
-  if constexpr (o == 5) { asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(w) : "v"(x0), "v"(x1)); fn[blk][1][p] = w; }
-  if constexpr (o == 6) asm volatile("v_lshlrev_b32 %0, 16, %1" : "=v"(t0[p]) : "v"(fn[blk][1][p]));
-  if constexpr (o == 7) asm volatile("v_and_b32 %0, 0xffff0000, %1" : "=v"(t1[p]) : "v"(fn[blk][1][p]));
-  if constexpr (o == 8) asm volatile("v_sub_f32 %0, %0, %1" : "+v"(x0) : "v"(t0[p]));
-  if constexpr (o == 9) asm volatile("v_sub_f32 %0, %0, %1" : "+v"(x1) : "v"(t1[p]));
-  if constexpr (o == 10) { asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(w) : "v"(x0), "v"(x1)); fn[blk][2][p] = w; }
-}
-template <int I, int END>
-__device__ __forceinline__ void x6ww_ops(float (&raw)[6][8], X6WFragW& fn, unsigned (&t0)[4], unsigned (&t1)[4]) {
-  if constexpr (I < END && I < 264) { x6ww_op<I>(raw, fn, t0, t1); x6ww_ops<I + 1, END>(raw, fn, t0, t1); }
-}
 // MFMA slot SI (0..47) of a 16-row step: product t = SI / 8 (small terms first, hi x hi last), block (i, j) = SI % 8;
 // then its share (5 or 6) of the next step's 264 split instructions
 template <int SI, bool SPLIT>
@@ -879,7 +913,7 @@ __device__ __forceinline__ void x6ww_slots(const X6WFragW& fc, X6WFragW& fn, x6_
     constexpr int pa = t == 0 ? 2 : (t == 2 || t == 3) ? 1 : 0;
     constexpr int pb = t == 1 ? 2 : (t == 2 || t == 4) ? 1 : 0;
     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x6w_operand(fc[i][pa]), x6w_operand(fc[2 + j][pb]), acc[i][j], 0, 0, 0);
-    if constexpr (SPLIT) x6ww_ops<(SI * 11) / 2, ((SI + 1) * 11) / 2>(raw, fn, t0, t1);
+    if constexpr (SPLIT) x6w_ops<(SI * 11) / 2, ((SI + 1) * 11) / 2, true>(raw, fn, t0, t1);
     __builtin_amdgcn_sched_barrier(0);
     x6ww_slots<SI + 1, SPLIT>(fc, fn, acc, raw, t0, t1);
   }
@@ -903,47 +937,49 @@ __device__ __forceinline__ void wgrad_x6_wide_body(const X6WgradArgs& g, const i
   const int T = rows_per_wave >> 4;              // even, >= 2
   const char* Az = (const char*)(g.A + (size_t)z * g.a_bstride);
   const char* Bz = (const char*)(g.B + (size_t)z * g.b_bstride);
-  const unsigned lds0 = (unsigned)(size_t)wlds + w * (3 * STAGE_BYTES);
+  constexpr unsigned RING_BYTES = 4 * 3 * STAGE_BYTES;
+  const unsigned lds_base = (unsigned)(size_t)wlds;
+  const unsigned lds0 = lds_base + w * (3 * STAGE_BYTES), lds_end = lds0 + 3 * STAGE_BYTES, lds_zero = lds_base + RING_BYTES;
+  x6w_clear_zero(wlds, RING_BYTES, tid);
 
   // DMA pieces of 1 KiB: dY 4 x (4 rows x 256 B), X 8 x (2 rows x 512 B); columns past M / N come from a clamped address
-  // and are zeroed after the LDS read
+  // and are never read.  The per-piece offsets are formed once; a step advances the two row bases and the destination stage
   const int ca = min(m0 + 4 * (lane & 15), g.M - 4), cb = min(n0 + 4 * (lane & 31), g.N - 4);
   const unsigned dA = (unsigned)(((size_t)(lane >> 4) * g.lda + ca) * 4), dB = (unsigned)(((size_t)(lane >> 5) * g.ldb + cb) * 4);
   const unsigned strideA = (unsigned)g.lda * 16u, strideB = (unsigned)g.ldb * 8u;
-  auto dma = [&](int s) __attribute__((always_inline)) {
-    const long long row0 = k_begin + 16ll * s;
-    const char* ab = Az + row0 * g.lda * 4;
-    const char* bb = Bz + row0 * g.ldb * 4;
-    const unsigned dst = lds0 + (s % 3) * STAGE_BYTES;
+  unsigned va[4], vb[8];
 #pragma unroll
-    for (int p = 0; p < 4; ++p) x6_dma16(ab, dA + p * strideA, dst + p * 1024);
+  for (int p = 0; p < 4; ++p) va[p] = dA + p * strideA;
 #pragma unroll
-    for (int p = 0; p < 8; ++p) x6_dma16(bb, dB + p * strideB, dst + 4096 + p * 1024);
+  for (int p = 0; p < 8; ++p) vb[p] = dB + p * strideB;
+  const char* arow = Az + k_begin * g.lda * 4;                                                // step 0's 16 rows
+  const char* brow = Bz + k_begin * g.ldb * 4;
+  const size_t stepA = (size_t)g.lda * 64, stepB = (size_t)g.ldb * 64;                        // 16 rows, bytes
+  unsigned wr = lds0;                                                                         // stage the next DMA step fills
+  auto dma = [&]() __attribute__((always_inline)) {
+    x6w_dma4(arow, va[0], va[1], va[2], va[3], wr);
+    x6w_dma4(brow, vb[0], vb[1], vb[2], vb[3], wr + 4096);
+    x6w_dma4(brow, vb[4], vb[5], vb[6], vb[7], wr + 8192);
+    arow += stepA; brow += stepB;
+    wr += STAGE_BYTES;
+    if (wr == lds_end) wr = lds0;
   };
-  bool va[2], vb[4];
+  // fragment block q (0, 1: dY columns 32 q + r; 2 .. 5: X columns 32 (q - 2) + r) of a stage: lane (r, h) reads rows 8h .. 8h+7
+  // of its column — or the zero region
+  bool ok[6];
+  unsigned lo[6];
 #pragma unroll
-  for (int i = 0; i < 2; ++i) va[i] = m0 + 32 * i + r < g.M;
+  for (int q = 0; q < 2; ++q) { ok[q] = m0 + 32 * q + r < g.M; lo[q] = (unsigned)(((8 * h) * 64 + 32 * q + r) * 4); }
 #pragma unroll
-  for (int j = 0; j < 4; ++j) vb[j] = n0 + 32 * j + r < g.N;
-  const bool tail = m0 + 64 > g.M || n0 + 128 > g.N;                                          // uniform
-  auto readfr = [&](float (&raw)[6][8], int s) __attribute__((always_inline)) {
-    const float* ba = wlds + w * (3 * STAGE_F) + (s % 3) * STAGE_F + (8 * h) * 64 + r;
-    const float* bb = wlds + w * (3 * STAGE_F) + (s % 3) * STAGE_F + 1024 + (8 * h) * 128 + r;
+  for (int q = 0; q < 4; ++q) { ok[2 + q] = n0 + 32 * q + r < g.N; lo[2 + q] = (unsigned)((1024 + (8 * h) * 128 + 32 * q + r) * 4); }
+  unsigned rd = lds0;                                                                         // stage the next read step reads
+  auto readfr = [&](float (&raw)[6][8]) __attribute__((always_inline)) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      raw[0][j] = ba[j * 64];
-      raw[1][j] = ba[j * 64 + 32];
+    for (int q = 0; q < 2; ++q) x6w_readblk<1>(raw[q], ok[q] ? rd + lo[q] : lds_zero);
 #pragma unroll
-      for (int q = 0; q < 4; ++q) raw[2 + q][j] = bb[j * 128 + 32 * q];
-    }
-    if (tail) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        raw[0][j] = va[0] ? raw[0][j] : 0.f; raw[1][j] = va[1] ? raw[1][j] : 0.f;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) raw[2 + q][j] = vb[q] ? raw[2 + q][j] : 0.f;
-      }
-    }
+    for (int q = 2; q < 6; ++q) x6w_readblk<2>(raw[q], ok[q] ? rd + lo[q] : lds_zero);
+    rd += STAGE_BYTES;
+    if (rd == lds_end) rd = lds0;
   };
   float raw0[6][8], raw1[6][8];
   X6WFragW fr0, fr1;
@@ -957,21 +993,22 @@ __device__ __forceinline__ void wgrad_x6_wide_body(const X6WgradArgs& g, const i
       for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
 
   // prologue: DMA steps 0..2; read steps 0 and 1; split step 0
-  dma(0);
-  dma(1);
-  if (T > 2) dma(2);
+  dma();
+  dma();
+  if (T > 2) dma();
+  __syncthreads();                              // the zero region is cleared
   if (T > 2) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
   else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  readfr(raw0, 0);
-  readfr(raw1, 1);
-  x6ww_ops<0, 264>(raw0, fr0, t0, t1);
+  readfr(raw0);
+  readfr(raw1);
+  x6w_ops<0, 264, true>(raw0, fr0, t0, t1);
   // after step s: DMA step s + 3 (its stage held step s, read two steps ago), wait for step s + 2, read it
   auto tailwork = [&](float (&rawn)[6][8], int s) __attribute__((always_inline)) {
-    if (s + 3 < T) dma(s + 3);
+    if (s + 3 < T) dma();
     if (s + 2 < T) {
       if (s + 3 < T) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      readfr(rawn, s + 2);
+      readfr(rawn);
     }
   };
   for (int s = 0; s + 2 < T; s += 2) {
@@ -1440,7 +1477,7 @@ static int x6_wgrad_set_attr(bool wide) {
   static bool once[3][64] = {};
   int dev = 0;
   (void)hipGetDevice(&dev);
-  const size_t sh_w = (size_t)4 * 3 * 16 * 192 * 4, sh_d = (size_t)4 * 4 * 8192;
+  const size_t sh_w = X6W_SH_WIDE, sh_d = X6W_SH_DMA;
   if (dev < 0 || dev >= 64 || !once[wide][dev]) {
     hipError_t e = hipFuncSetAttribute(wide ? (const void*)wgrad_x6_wide_kernel : (const void*)wgrad_x6_dma_kernel,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)(wide ? sh_w : sh_d));
@@ -1489,9 +1526,9 @@ static int x6_wgrad_plan(const float* dy, int ldg, size_t g_bstride, const float
   bool swap = wide && padm < padn;
   if (batched > 0 && aligned) {
     // inside a batched launch the tile count of ONE problem no longer decides how well the chip is filled, only the matrix
-    // time does: the 64 x 128 body runs at about its MFMA time, the 64 x 64 body at ~1.5x (7.3 vs 5.5 split instructions per
-    // MFMA) — padding up to 128 pays until it costs that much (160 x 160: 3 x 2 wide tiles against 3 x 3; 320 x 320: 5 x 3
-    // against 5 x 5)
+    // time does: per MFMA the 64 x 64 loop carries 7.7 vector instructions and the 64 x 128 loop 5.8 (compiled counts, at the
+    // bodies), so a 64 x 64 tile (24 MFMAs per step) is charged 36 and a wide tile 48 — padding up to 128 pays until it costs
+    // that much (160 x 160: 3 x 2 wide tiles against 3 x 3; 320 x 320: 5 x 3 against 5 x 5)
     const long long c64 = (long long)a.mtiles * a.ntiles * 36;
     const long long cwn = (long long)a.mtiles * ((cin + 127) / 128) * 48, cwm = (long long)a.ntiles * ((cout + 127) / 128) * 48;
     wide = (cwn < cwm ? cwn : cwm) <= c64;
@@ -1586,7 +1623,7 @@ extern "C" int gkg_linear_wgrad_x6(const float* dy, int ldg, size_t g_bstride, c
   hipError_t e = hipSuccess;
   if (pl.main.K > 0) {
     if ((rc = x6_wgrad_set_attr(pl.wide))) return rc;
-    const size_t sh = pl.wide ? (size_t)4 * 3 * 16 * 192 * 4 : (size_t)4 * 4 * 8192;
+    const size_t sh = pl.wide ? X6W_SH_WIDE : X6W_SH_DMA;
     const dim3 grid(pl.grid_x, nb);
     if (pl.wide) hipLaunchKernelGGL(wgrad_x6_wide_kernel, grid, dim3(256), sh, st, pl.main);
     else hipLaunchKernelGGL(wgrad_x6_dma_kernel, grid, dim3(256), sh, st, pl.main);
@@ -1621,7 +1658,7 @@ extern "C" int gkg_linear_wgrad_x6_batch(const GkgWgradProblem* p, int n, int un
     if (b.n == 0) return 0;
     int rc = x6_wgrad_set_attr(true);
     if (rc) return rc;
-    hipLaunchKernelGGL(wgrad_x6_batch_kernel, dim3(b.begin[b.n]), dim3(256), (size_t)4 * 3 * 16 * 192 * 4, st, b);
+    hipLaunchKernelGGL(wgrad_x6_batch_kernel, dim3(b.begin[b.n]), dim3(256), X6W_SH_WIDE, st, b);
     hipError_t e = hipGetLastError();
     b.n = 0;
     return e == hipSuccess ? 0 : gkg_fail_hip(e, "wgrad_x6_batch_kernel");
@@ -1655,8 +1692,6 @@ extern "C" int gkg_linear_wgrad_x6_batch(const GkgWgradProblem* p, int n, int un
 // and ONE small launch behind them that adds the images in that order and writes dW.  No atomics, no memset, no counters: the
 // kernel boundary orders the partial stores before the reduction's loads.
 namespace gkg {
-constexpr size_t X6W_SH_WIDE = (size_t)4 * 3 * 16 * 192 * 4, X6W_SH_DMA = (size_t)4 * 4 * 8192;
-
 static int x6_wdet_set_attr(int kind) {          // 0: 64 x 64 DMA body, 1: wide body, 2: batch
   static bool once[3][64] = {};
   int dev = 0;
