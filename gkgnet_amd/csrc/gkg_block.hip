@@ -102,7 +102,7 @@ int proj_dgrad(const Ctx& c, const GkgProjBN& p, const GkgProjBN* q, int qact, c
 // whether p's input-gradient GEMM can take the statistics of the layer in front (never in a frozen block: there are none)
 bool dgrad_stats_ok(const Ctx& c, const GkgProjBN& p, unsigned bwd_flags, int R, bool residual) {
   return !c.frozen && !(bwd_flags & (GKG_BLOCK_NO_BWD_FUSE | GKG_BLOCK_NO_DGRAD_STATS)) && p.nb == 1 &&
-         gkg_linear_dgrad_x6_bnbwd_sk_supported(R, p.cin, residual ? 1 : 0, c.sk_ws ? 1 : 0, 0);
+         gkg_linear_dgrad_x6_bnbwd_sk_supported(R, p.cin, residual ? 1 : 0, c.sk_ws ? 1 : 0, c.x6_flags);
 }
 // A layer's backward: the BN-backward step (`have`: its statistics came with g), then the input-gradient step (`give`: with the
 // statistics of the layer q in front)

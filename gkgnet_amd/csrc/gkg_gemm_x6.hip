@@ -30,8 +30,8 @@
 //   * XCD-aware 1-D grid: the column tiles of one 128-row block run back to back on one XCD, so the row block is fetched
 //     from HBM into that L2 once.
 #include "gkg_common.h"
+#include "gkg_x6_plan.h"
 #include <stdlib.h>
-#include <vector>
 
 namespace gkg {
 
@@ -39,8 +39,6 @@ typedef float x6_f32x16 __attribute__((ext_vector_type(16)));
 typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 x6_bf16x8;
 typedef __bf16 x6_bf16x2 __attribute__((ext_vector_type(2)));
 typedef float x6_f32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int X6_NPAD = 128;             // plane rows are padded to this many n (covers NI = 2 and 4 column tiles)
 
 __device__ __forceinline__ unsigned x6_cvt2(float a, float b) {
   x6_f32x2 v = {a, b};
@@ -170,12 +168,6 @@ struct X6Args {
   int walk_nb;                                          // gemm_x6_walk_kernel: the batches folded into its 1-D grid
 };
 
-enum { X6_STORE = 0, X6_BNSTATS = 1, X6_BNBWD = 2, X6_STORE_NCHW = 3 };
-
-// LDS of gemm_x6_kernel's operand rings: three 16-KiB A stages + two B stage images (+ slack: the unused lanes of a partial last
-// block read past their image row)
-constexpr int x6_ring_bytes(int NI, int BN) { return 3 * 4 * 4096 + 2 * 12 * BN * 16 + (BN != 32 * NI ? 512 : 0); }
-
 __device__ __forceinline__ void x6_chan_merge(double& n, double& mean, double& m2, double nb, double mb, double m2b) {
   if (nb <= 0.0) return;
   const double tot = n + nb;
@@ -206,87 +198,35 @@ __device__ __forceinline__ void x6_dma16(const void* sbase, unsigned voff, unsig
 #include "gkg_gemm_x6_tile.h"
 #undef X6_WALK
 
-// The attribute (and, for the walk form, the resident-workgroup count) of one instantiation is per DEVICE (a per-process guard left
-// a second GPU of the same process without it — ADVICE r3): set / queried on the first launch there.  slots: out, or null.
-template <int NI, int EPI, int BN, bool WALK>
-static hipError_t x6_kernel_setup(size_t sh, int* slots) {
-  static int known[64] = {};                             // 0: not set up; else the resident workgroups of the device
+// The dynamic-LDS attribute of ONE kernel (the one about to be launched) and, where `slots` asks, its resident-workgroup count
+// (workgroups per CU x CUs) are per DEVICE (a per-process guard left a second GPU of the same process without the attribute —
+// ADVICE r3): set / queried on the first use there.  The only hipFuncSetAttribute of this file.
+template <auto KERNEL>
+static hipError_t x6_kernel_once(size_t sh, int* slots = nullptr) {
+  static int known[64] = {};                             // 0: not set up; -1: attribute set; else the resident workgroups of the device
   int dev = 0;
   (void)hipGetDevice(&dev);
   const bool cached = dev >= 0 && dev < 64;
   int n = cached ? known[dev] : 0;
   if (n == 0) {
-    const void* fn;
-    if constexpr (WALK) fn = (const void*)gemm_x6_walk_kernel<NI, EPI, BN>;
-    else fn = (const void*)gemm_x6_kernel<NI, EPI, BN>;
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+    hipError_t e = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
     if (e != hipSuccess) return e;
+    n = -1;
+  }
+  if (n < 0 && slots) {
     int per_cu = 0, cus = 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, sh);
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)KERNEL, 256, sh);
     if (e != hipSuccess) return e;
     e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     if (e != hipSuccess) return e;
     n = per_cu * cus;
     if (n < 8) return hipErrorInvalidConfiguration;
-    if (cached) known[dev] = n;
   }
+  if (cached) known[dev] = n;
   if (slots) *slots = n;
   return hipSuccess;
 }
 
-// The launch rule of the walk form — ONE function for the launch and for gkg_x6_walk_workgroups: the grid (workgroups) of the walk
-// launch for `units` row blocks (batches folded in) of `ntiles` column tiles on `slots` resident workgroups, or 0: one tile per
-// workgroup.  The longest XCD sequence (ceil(units / 8) row blocks) needs `rounds` rounds of the slots of one XCD.
-//   * Walks when rounds == 2.  All workgroups of such a launch start together, so both workgroups of a CU are in their prologue
-//     and in their epilogue at the same time, twice; walking, the second tile's first stages land under the first tile's
-//     epilogue (cfg2's grouped 4 x (10 368 x 160 -> 160) products, 972 tiles: 26.7 -> 24.2 and 25.1 -> 21.4 us in the replayed
-//     step, profiles/r11_bench_cfg2_graph_steps.txt).  From three rounds on the hardware dispatcher has de-phased the two
-//     workgroups of a CU — one fills its rings while the other multiplies — and re-balances at every workgroup end, which a
-//     static list cannot: walking everything made cfg2ref / stage3 / cfg4 0.9-2 % SLOWER (profiles/r11_x6_tile_walk_ab.txt).
-//   * The sequence is cut into EQUAL shares: 123 entries on 64 slots are 62 workgroups of 2 (one of 1), not 64 + 59.
-//   * GKG_X6_FORCE_WALK (tests, measurement): whatever the rounds; its cap field c > 0: at most 8 c workgroups.
-static int x6_walk_grid(long long units, int ntiles, int ksplit, int slots, unsigned flags) {
-  if (ksplit > 1 || (flags & GKG_X6_NO_WALK)) return 0;
-  const bool force = (flags & GKG_X6_FORCE_WALK) != 0;
-  const long long seq = (units + 7) / 8 * ntiles, per_xcd = slots / 8;
-  const long long rounds = (seq + per_xcd - 1) / per_xcd;
-  if (!force && rounds != 2) return 0;
-  long long w = (seq + rounds - 1) / rounds;
-  const long long cap = (flags >> GKG_X6_WALK_CAP_SHIFT) & GKG_X6_WALK_CAP_MASK;
-  if (force && cap > 0 && w > cap) w = cap;
-  return (int)(w * 8);
-}
-
-template <int NI, int EPI, int BN = 32 * NI, bool WALKABLE = false>
-static hipError_t x6_launch_ni(X6Args a, int nb, hipStream_t st, unsigned flags = 0) {
-  a.mtiles = (a.M + 127) / 128;
-  a.ntiles = (a.N + BN - 1) / BN;
-  if (a.ksplit < 1) a.ksplit = 1;
-  if constexpr (WALKABLE) {
-    if (a.ksplit == 1 && !(flags & GKG_X6_NO_WALK)) {
-      const size_t shw = x6_ring_bytes(NI, BN) + (EPI == X6_BNSTATS ? 4 * BN * 2 * 4 : 0);      // + the epilogue's own LDS
-      int slots = 0;
-      hipError_t e = x6_kernel_setup<NI, EPI, BN, true>(shw, &slots);
-      if (e != hipSuccess) return e;
-      if (const int grid = x6_walk_grid((long long)nb * a.mtiles, a.ntiles, a.ksplit, slots, flags); grid > 0) {
-        a.walk_nb = nb;
-        hipLaunchKernelGGL((gemm_x6_walk_kernel<NI, EPI, BN>), dim3(grid), dim3(256), shw, st, a);
-        return hipGetLastError();
-      }
-    }
-  }
-  const size_t sh = x6_ring_bytes(NI, BN);
-  hipError_t e = x6_kernel_setup<NI, EPI, BN, false>(sh, nullptr);
-  if (e != hipSuccess) return e;
-  const int groups = (a.mtiles + 7) / 8;
-  hipLaunchKernelGGL((gemm_x6_kernel<NI, EPI, BN>), dim3(groups * 8 * a.ntiles * a.ksplit, nb), dim3(256), sh, st, a);
-  return hipGetLastError();
-}
-
-// Column-tile width (32 NI).  More columns per wave amortise the 44-instruction A split over more MFMAs (NI = 1 is
-// VALU-bound, NI = 2 about balanced) but leave fewer workgroups: NI = 2, and NI = 1 when that leaves the chip under-filled
-// (few rows: the label branch).  Measured cold-cache per shape with tools/bench_x6.py; NI = 5 (160 columns, one
-// workgroup per CU) was tried and is slower everywhere (cfg2 fc1 25.8 vs 22.9 us).
 // ---- few rows: the waves of a workgroup split K, not M (round 5) --------------------------------------------------------
 // gemm_x6_kernel has a floor of ~10 us per launch whatever the size (2.4 us of prologue DMA issue for three 16 KB A stages and
 // two B stages per workgroup, a barrier per K-step, a 128-row epilogue) and needed a cross-workgroup split-K seam (5-13 us) to
@@ -511,100 +451,82 @@ __global__ __launch_bounds__(256, MI == 1 ? 2 : 1) void gemm_x6_ks_kernel(X6Args
   }
 }
 
-                                        // bit 2 / bit 3 = always 32-row / 64-row tiles in it (A/B, tests)
-
-template <int EPI, int MI>
-static hipError_t x6_launch_ks(X6Args a, int nb, hipStream_t st) {
-  a.mtiles = (a.M + 32 * MI - 1) / (32 * MI);
-  a.ntiles = (a.N + 63) / 64;
-  const size_t sh = MI == 1 ? 4 * 3 * 4096 : 4 * 2 * 8192;      // 48 / 64 KB of A rings (the 32 / 64 KB of partials alias them)
-  if (MI == 2) {
-    static bool once[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !once[dev]) {
-      hipError_t e = hipFuncSetAttribute((const void*)gemm_x6_ks_kernel<EPI, MI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-      if (e != hipSuccess) return e;
-      if (dev >= 0 && dev < 64) once[dev] = true;
-    }
+// ---- the launch: what the plan (gkg_x6_plan.h) names, nothing decided here ----------------------------------------------
+template <auto KERNEL>
+static hipError_t x6_go(const X6GemmPlan& pl, const X6Args& a, hipStream_t st, bool attr = true) {
+  if (attr) {
+    if (hipError_t e = x6_kernel_once<KERNEL>(pl.lds); e != hipSuccess) return e;
   }
-  const int groups = (a.mtiles + 7) / 8;
-  hipLaunchKernelGGL((gemm_x6_ks_kernel<EPI, MI>), dim3(groups * 8 * a.ntiles, nb), dim3(256), sh, st, a);
+  hipLaunchKernelGGL(KERNEL, dim3(pl.grid_x, pl.grid_y), dim3(256), pl.lds, st, a);
   return hipGetLastError();
 }
 
-// Split-K workspace (caller-owned, gkg_x6_splitk_workspace_bytes()): [1024 tile counters, zero between launches][partials].
-constexpr size_t X6_SK_CNT_BYTES = 4096, X6_SK_MAX_WG = 512;
-constexpr size_t X6_SK_BYTES = X6_SK_CNT_BYTES + X6_SK_MAX_WG * (size_t)(2 * 16 * 256 * 4);
-
-// The rule for the short-matrix body (gemm_x6_ks_kernel; measured in x6_launch's comment below) — ONE predicate for the launch and
-// for the entry points that must know beforehand which body a shape takes.
-static bool x6_ks_form(int M, int N, int nb, bool has_ws, unsigned flags) {
-  return has_ws && !(flags & GKG_X6_NO_KS) && M <= 4096 && (long long)((M + 31) / 32) * ((N + 63) / 64) * nb <= 65535 * 8 &&
-         ((flags & GKG_X6_FORCE_KS) || (nb == 1 && N <= 640));
-}
-
-// The cross-workgroup split of the contraction for the 128-row tile kernel (x6_launch's comment): ranges per tile, < 2: none.
-static int x6_tile_ksplit(long long base2, int nk_total, bool has_ws) {
-  if (!has_ws || base2 >= 320 || nk_total < 8) return 1;
-  int ks = (int)(X6_SK_MAX_WG / base2);
-  if (ks > nk_total / 4) ks = nk_total / 4;
-  return ks > 8 ? 8 : ks;
-}
-
+// Where the plan says that the device's resident-workgroup count decides (X6GemmPlan::walkable): ask about the walk instantiation
+// of this epilogue — the kernel the launch would be, with the LDS the plan names for it (walk_lds) — and plan again.  The
+// instantiation is the switchboard's X6_BODY_WALK entry: the ladder's walk rung is NI = 2, BN = 64 and nothing else.
 template <int EPI>
-static hipError_t x6_launch(X6Args a, int nb, hipStream_t st, void* sk_ws = nullptr, size_t sk_bytes = 0, unsigned flags = 0) {
-  GkgProfScope prof(GKG_PROF_GEMM_X6, st, 2.0 * a.M * a.N * a.K * nb);
-  const int mt = (a.M + 127) / 128;
-  // Few rows under a long contraction (the label branch: 2 560 x 1280 -> 320 is 100 workgroups of 40 K-steps on 256 CUs): the
-  // contraction is cut into ksplit ranges so that the launch fills the chip's 512 workgroup slots, at least 4 K-steps each
-  // (the pipeline's fill is worth about two).  The last arrival per tile sums the partials in split order (deterministic) and
-  // runs the normal epilogue, BN statistics included.
-  const long long base2 = (long long)mt * ((a.N + 63) / 64) * nb;
-  const int nk_total = (a.K + 31) / 32;
-  // Few rows (<= 4 096: the label branch): the waves of a workgroup split K instead of M (gemm_x6_ks_kernel) — taken by the _sk
-  // entry points, i.e. by callers that asked for the short-matrix forms
-  // Where it pays (measured inside the cfg2 step, same box, us, this body vs gemm_x6_kernel with cross-workgroup split-K:
-  // profiles/r05_x6_ks_vs_tile_kernel.txt): 2 560 x 320 -> 320 11.0 vs 13.1 (input gradient + residual 11.7 vs 20.7), 640 -> 320
-  // 15.2 vs 21.2, 1280 -> 320 24.3 vs 29.6 (input gradient of 320 -> 1280: 25.4 vs 36.5); a tie at 320 -> 640 (16.4); it LOSES
-  // where every 32-row workgroup re-reads a wide B (320 -> 1280: 30.0 vs 22.4, its transpose 27.3 vs 21.3: 196 MB of plane
-  // traffic) and on the grouped 4 x (160 -> 160) products (15.5 vs 13.5).  Rule: un-grouped, at most 640 output columns.
-  // The caller's `flags` (GKG_X6_NO_KS / GKG_X6_FORCE_KS: measurement, tests) override the rule per call.
-  // (X6_BNBWD comes here with a workspace only from gkg_linear_dgrad_x6_bnbwd_sk, which wants the body — and so the bits of dx —
-  // that X6_STORE takes for the same shape)
-  if constexpr (EPI != X6_STORE_NCHW) {
-    if (x6_ks_form(a.M, a.N, nb, sk_ws != nullptr, flags)) {
-      // (64-row tiles — half the plane traffic, one wave per SIMD — measured no better on the long contractions they were built
-      // for: 2 560 x 1280 -> 320 26.8 vs 24.3 us; what bounds those launches is the wave-serial K loop, not the B planes)
-      return x6_launch_ks<EPI, 1>(a, nb, st);
+static hipError_t x6_plan_walk(X6GemmCall& q, X6GemmPlan& pl) {
+  if constexpr (EPI != X6_BNBWD) {
+    if (pl.walkable && q.slots <= 0) {
+      hipError_t e = x6_kernel_once<gemm_x6_walk_kernel<2, EPI, 64>>(pl.walk_lds, &q.slots);
+      if (e != hipSuccess) return e;
+      x6_gemm_ladder(q, &pl);
     }
   }
-  if (const int ks = x6_tile_ksplit(base2, nk_total, sk_ws && sk_bytes >= X6_SK_BYTES); ks >= 2) {
-    a.kper = (nk_total + ks - 1) / ks;
-    a.ksplit = (nk_total + a.kper - 1) / a.kper;               // no empty range
+  return hipSuccess;
+}
+
+// The operand-independent half of a call, the operands and the size-dependent half of the kernel arguments, each filled in ONE place.
+static X6GemmCall x6_call(X6Role role, int M, int N, int K, int nb, const float* A, int lda, size_t a_bstride, const void* sk_ws,
+                          size_t sk_bytes, unsigned flags) {
+  X6GemmCall q{};
+  q.role = role; q.M = M; q.N = N; q.K = K; q.nb = nb;
+  q.lda = lda; q.a_bstride = a_bstride; q.a_aligned = ((size_t)A & 15) == 0;
+  q.has_ws = sk_ws != nullptr; q.ws_aligned = ((size_t)sk_ws & 15) == 0; q.ws_bytes = sk_bytes;
+  q.flags = flags;
+  return q;
+}
+
+static X6Args x6_operands(const float* A, const void* planes, float* C, size_t c_bstride, int ldc, const float* add = nullptr) {
+  X6Args a{};
+  a.A = A; a.P = (const uint4*)planes; a.C = C; a.c_bstride = c_bstride; a.ldc = ldc; a.add = add;
+  return a;
+}
+
+static void x6_sizes(X6Args& a, const X6GemmCall& q, const X6GemmPlan& pl, void* sk_ws) {
+  a.a_bstride = q.a_bstride; a.lda = q.lda;
+  a.p_bstride = pl.p_bstride; a.NP = pl.NP; a.KC = pl.KC;
+  a.M = q.M; a.N = q.N; a.K = q.K;
+  a.mtiles = pl.mtiles; a.ntiles = pl.ntiles; a.ksplit = pl.ksplit; a.kper = pl.kper;
+  if (pl.ksplit > 1) {                                   // the split-K workspace: [tile counters][partials] (the plan checked its size)
     a.cnt = reinterpret_cast<unsigned*>(sk_ws);
     a.part = reinterpret_cast<float*>(reinterpret_cast<char*>(sk_ws) + X6_SK_CNT_BYTES);
-    return x6_launch_ni<2, EPI>(a, nb, st);
   }
-  if constexpr (EPI == X6_BNBWD) {
-    if (a.add) return hipErrorInvalidValue;              // the tile body's statistics epilogue takes no residual (never dropped silently)
+  a.nslots = pl.nslots; a.nbatch = q.nb;
+  a.walk_nb = pl.body == X6_BODY_WALK ? q.nb : 0;
+}
+
+// (body, NI, BN, EPI, walk) -> instantiation; a combination the library does not hold is hipErrorInvalidValue.  80-column tiles
+// exist for the plain and the BN-statistics epilogue, the walk form not for X6_BNBWD, the short-matrix body (48 KiB: no attribute)
+// not with the channel-major store.  `a` arrives with the operands and leaves with the plan's sizes.
+template <int EPI>
+static hipError_t x6_launch(X6GemmCall& q, X6GemmPlan& pl, X6Args a, void* sk_ws, hipStream_t st) {
+  GkgProfScope prof(GKG_PROF_GEMM_X6, st, pl.work);
+  if (pl.epi != EPI) return hipErrorInvalidValue;
+  if (hipError_t e = x6_plan_walk<EPI>(q, pl); e != hipSuccess) return e;
+  x6_sizes(a, q, pl, sk_ws);
+  if (pl.body == X6_BODY_KS) {
+    if constexpr (EPI != X6_STORE_NCHW) return x6_go<gemm_x6_ks_kernel<EPI, 1>>(pl, a, st, false);
+  } else if (pl.body == X6_BODY_TILE && pl.NI == 2 && pl.BN == 64) {
+    return x6_go<gemm_x6_kernel<2, EPI, 64>>(pl, a, st);
+  } else if (pl.body == X6_BODY_TILE && pl.NI == 3 && pl.BN == 80) {
+    if constexpr (EPI == X6_STORE || EPI == X6_BNSTATS) return x6_go<gemm_x6_kernel<3, EPI, 80>>(pl, a, st);
+  } else if (pl.body == X6_BODY_TILE && pl.NI == 1 && pl.BN == 32) {
+    return x6_go<gemm_x6_kernel<1, EPI, 32>>(pl, a, st);
+  } else if (pl.body == X6_BODY_WALK && pl.NI == 2 && pl.BN == 64) {
+    if constexpr (EPI != X6_BNBWD) return x6_go<gemm_x6_walk_kernel<2, EPI, 64>>(pl, a, st);
   }
-  int ni = base2 < 160 && !(flags & GKG_X6_FORCE_WALK) ? 1 : 2;       // (the walk form exists for 64-column tiles: same bits)
-  // 80 output columns on many rows (GKGNet-576 stage 1): ONE 80-column tile per row block instead of a full and a quarter
-  // 64-column tile — 663 552 rows: 80 -> 80 171 -> 133 us, + statistics 208 -> 161, 320 -> 80 345 -> 279, dgrad 320 <- 80
-  // 351 -> 279.  Wider outputs measured equal or slower on 80-column tiles (160: +-3 %, 320 / 400 / 640: 3-8 % slower:
-  // profiles/r04_x6_80_column_tiles_ab.txt); the BN-backward epilogue's registers do not fit two waves per SIMD there.
-  // Round 9 tried them for the grouped 4 x (160 -> 160) products of cfg2 (10 368 rows: 648 workgroups instead of 972, fewer
-  // rounds of 512): the replayed step got 3-4 us SLOWER (profiles/r09_dgrad_stats_ab.txt) — not taken.
-  if constexpr (EPI != X6_BNBWD && EPI != X6_STORE_NCHW) {
-    if (a.N == 80 && ni == 2) return x6_launch_ni<3, EPI, 80>(a, nb, st);
-  }
-  if (ni == 1) return x6_launch_ni<1, EPI>(a, nb, st);
-  // Two rounds of resident workgroups: the tile-walk form of the same kernel (x6_walk_grid; GKG_X6_NO_WALK / _FORCE_WALK).  Not with
-  // the BN-backward statistics epilogue: its registers (the y prefetch beside the walk's state) leave the compiler 219 VGPRs and 69
-  // spilled SGPRs for two waves per SIMD, and cfg2's 810-tile launch measured 44.0 -> 47.8 us walking — the flags do nothing there.
-  if constexpr (EPI == X6_BNBWD) return x6_launch_ni<2, EPI>(a, nb, st);
-  else return x6_launch_ni<2, EPI, 64, true>(a, nb, st, flags);
+  return hipErrorInvalidValue;
 }
 
 // ---- weight gradient ----------------------------------------------------------------------------------------------------
@@ -732,8 +654,6 @@ __device__ __forceinline__ bool x6w_map(const X6WgradArgs& g, int lin, int& spli
 // the matrix reads its fragments THERE (its read base is chosen per step from a per-lane mask, one select per block) instead
 // of reading the clamped column's values and zeroing them after every LDS read (8 selects per block).  Exactly 0.0f, as before.
 // The region covers the eight row offsets of a fragment at the 128-column pitch: 7 x 512 + 4 bytes.
-constexpr unsigned X6W_ZERO_BYTES = 4096;
-constexpr size_t X6W_SH_DMA = (size_t)4 * 4 * 8192 + X6W_ZERO_BYTES, X6W_SH_WIDE = (size_t)4 * 3 * 16 * 192 * 4 + X6W_ZERO_BYTES;
 
 // LDS-DMA of four consecutive 1-KiB pieces (x6_dma16) in one statement: M0 is saved and restored once and stepped by 1 KiB
 // between the pieces — 14 instructions where four x6_dma16 are 24.
@@ -1063,7 +983,6 @@ __global__ __launch_bounds__(256) void wgrad_x6_wide_det_kernel(X6WgradArgs g, s
 // begin[i+1]) belong to problem i (begin[] in multiples of 8, so lin & 7 stays the XCD inside a problem), which runs the
 // 64 x 64 or the 64 x 128 body above exactly as its own launch would.  The descriptors travel in the kernel arguments (a
 // hipGraph node keeps them by value).
-constexpr int X6W_BATCH = 16;
 struct X6WgradBatch {
   int n;
   int begin[X6W_BATCH + 1];
@@ -1133,11 +1052,6 @@ __global__ __launch_bounds__(256) void wgrad_x6_det_reduce_kernel(X6WdetReduce d
   d.dw[i][e] = v;
 }
 
-inline bool x6_bad_dim(int v) { return v <= 0 || (v & 3) != 0; }
-inline size_t x6_plane_units(int n, int k, int nb) {       // uint4 units of one orientation: B[n][k]
-  return (size_t)nb * 3 * ((k + 31) / 32 * 4) * ((n + X6_NPAD - 1) / X6_NPAD * X6_NPAD);
-}
-
 }  // namespace gkg
 using namespace gkg;
 
@@ -1194,8 +1108,6 @@ hipError_t launch_bn_sums_finalize(double* stats, int R, int cout, int nb, const
 
 }  // namespace gkg
 
-// fp64 column-sum scratch of the projections' BN-statistics epilogue: doubles per buffer (4 groups x 2 x 4096 channels)
-extern "C" int gkg_linear_stats_doubles() { return 2 * 4096 * 4; }
 
 extern "C" size_t gkg_x6_planes_bytes(int cin, int cout, int nb, int dgrad) {
   if (x6_bad_dim(cin) || x6_bad_dim(cout) || nb <= 0) return 0;
@@ -1252,48 +1164,42 @@ extern "C" int gkg_x6_prep_weights_zero(const void* descs_dev, int ndesc, long l
   return x6_prep_impl(descs_dev, ndesc, total_units, zero0, zero0_bytes, zero1, zero1_bytes, stream);
 }
 
-// gkg_linear_bn_fwd with the weights given as forward planes (gkg_x6_prep_weights).  x (nb, R, cin) with row pitch ldx and
-// batch stride x_bstride (floats); y (nb, R, cout) contiguous.  Same `train` modes and outputs as gkg_linear_bn_fwd.
+// ---- entry points: fill a call, plan it (gkg_x6_plan.h), check the pointers, launch what the plan names -------------------------
+// fp64 column-sum scratch of the projections' BN-statistics epilogue: doubles per buffer
+extern "C" int gkg_linear_stats_doubles() { return X6_STATS_DOUBLES; }
+
 extern "C" size_t gkg_x6_splitk_workspace_bytes(void) { return X6_SK_BYTES; }
 
-static int x6_fwd_impl(const float* x, int ldx, size_t x_bstride, const void* planes_fwd, float* y, int R,
-                       int cin, int cout, int nb, int train, const float* gamma, const float* beta,
-                       const float* bias, float* running_mean, float* running_var,
-                       long long* num_batches_tracked, float* bn_a, float* bn_c, float* bn_mean,
-                       float* bn_invstd, float momentum, float eps, double* stats, void* sk_ws, size_t sk_bytes, void* stream,
-                       unsigned flags = 0) {
+// gkg_linear_bn_fwd with the weights given as forward planes (gkg_x6_prep_weights).  x (nb, R, cin) with row pitch ldx and
+// batch stride x_bstride (floats); y (nb, R, cout) contiguous.  Same `train` modes and outputs as gkg_linear_bn_fwd.
+// The _sk form takes a split-K workspace (gkg_x6_splitk_workspace_bytes() bytes, its first 4 KiB ZERO before the first use; every
+// launch leaves them zero again): few-row / long-contraction shapes then run as several K ranges per tile.
+extern "C" int gkg_linear_bn_fwd_x6_sk(const float* x, int ldx, size_t x_bstride, const void* planes_fwd, float* y, int R,
+                                       int cin, int cout, int nb, int train, const float* gamma, const float* beta,
+                                       const float* bias, float* running_mean, float* running_var,
+                                       long long* num_batches_tracked, float* bn_a, float* bn_c, float* bn_mean,
+                                       float* bn_invstd, float momentum, float eps, double* stats, void* splitk_ws,
+                                       size_t splitk_bytes, unsigned flags, void* stream) {
+  X6GemmCall q = x6_call(X6R_FWD, R, cout, cin, nb, x, ldx, x_bstride, splitk_ws, splitk_bytes, flags);
+  q.train = train;
+  X6GemmPlan pl;
+  const char* msg = nullptr;
+  if (const int rc = x6_gemm_plan(q, &pl, &msg)) return gkg_fail(rc, msg);
   if (!x || !planes_fwd || !y) return gkg_fail(GKG_ERR_NULL, "gkg_linear_bn_fwd_x6: null pointer");
-  if (R <= 0 || x6_bad_dim(cin) || x6_bad_dim(cout) || nb <= 0 || nb > 64 || ldx < cin || (ldx & 3) || (x_bstride & 3) ||
-      ((size_t)x & 15))
-    return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_bn_fwd_x6: need R > 0, cin % 4 == 0, cout % 4 == 0, 1 <= nb <= 64, 16-byte aligned rows");
-  if ((size_t)R * ldx * 4 > 0xffffffffull) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_bn_fwd_x6: operand larger than 4 GiB per batch");
-  X6Args a{};
-  a.A = x; a.a_bstride = x_bstride; a.lda = ldx;
-  a.NP = (cout + X6_NPAD - 1) / X6_NPAD * X6_NPAD; a.KC = (cin + 31) / 32 * 4;
-  a.P = (const uint4*)planes_fwd; a.p_bstride = (size_t)3 * a.KC * a.NP;
-  a.C = y; a.c_bstride = (size_t)R * cout; a.ldc = cout;
-  a.M = R; a.N = cout; a.K = cin;
-  hipStream_t st = (hipStream_t)stream;
-  hipError_t e;
   if (train) {
     if (!stats) return gkg_fail(GKG_ERR_NULL, "gkg_linear_bn_fwd_x6: training needs the stats scratch");
-    if ((size_t)nb * 2 * cout > (size_t)gkg_linear_stats_doubles()) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_bn_fwd_x6: nb * cout too large for the stats scratch");
     if (train != 2) {
       if (!gamma || !beta || !bn_a || !bn_c || !bn_mean || !bn_invstd) return gkg_fail(GKG_ERR_NULL, "gkg_linear_bn_fwd_x6: training needs gamma, beta and the four outputs");
       if ((running_mean == nullptr) != (running_var == nullptr)) return gkg_fail(GKG_ERR_NULL, "gkg_linear_bn_fwd_x6: running stats come in pairs");
     }
-    a.sums = stats; a.nbatch = nb;
-    // copies of the sums to spread the row tiles' atomics over (train == 2 leaves the sums for a consumer that knows one copy)
-    const int fit = gkg_linear_stats_doubles() / (nb * 2 * cout), want = (R + 127) / 128 / 64;
-    a.nslots = train == 2 ? 1 : (want < 1 ? 1 : (want > 16 ? 16 : want));
-    if (a.nslots > fit) a.nslots = fit;
-    e = x6_launch<X6_BNSTATS>(a, nb, st, sk_ws, sk_bytes, flags);
-    if (e == hipSuccess && train != 2) {
-      e = launch_bn_sums_finalize(stats, R, cout, nb, gamma, beta, bias, running_mean, running_var, bn_a, bn_c, bn_mean,
-                                  bn_invstd, momentum, eps, num_batches_tracked, st, a.nslots);
-    }
-  } else {
-    e = x6_launch<X6_STORE>(a, nb, st, sk_ws, sk_bytes, flags);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  X6Args a = x6_operands(x, planes_fwd, y, (size_t)R * cout, cout);
+  a.sums = stats;
+  hipError_t e = train ? x6_launch<X6_BNSTATS>(q, pl, a, splitk_ws, st) : x6_launch<X6_STORE>(q, pl, a, splitk_ws, st);
+  if (e == hipSuccess && train && train != 2) {
+    e = launch_bn_sums_finalize(stats, R, cout, nb, gamma, beta, bias, running_mean, running_var, bn_a, bn_c, bn_mean, bn_invstd,
+                                momentum, eps, num_batches_tracked, st, pl.nslots);
   }
   return e == hipSuccess ? 0 : gkg_fail_hip(e, "gemm_x6_kernel (forward)");
 }
@@ -1303,109 +1209,69 @@ extern "C" int gkg_linear_bn_fwd_x6(const float* x, int ldx, size_t x_bstride, c
                                     const float* bias, float* running_mean, float* running_var,
                                     long long* num_batches_tracked, float* bn_a, float* bn_c, float* bn_mean,
                                     float* bn_invstd, float momentum, float eps, double* stats, void* stream) {
-  return x6_fwd_impl(x, ldx, x_bstride, planes_fwd, y, R, cin, cout, nb, train, gamma, beta, bias, running_mean, running_var,
-                     num_batches_tracked, bn_a, bn_c, bn_mean, bn_invstd, momentum, eps, stats, nullptr, 0, stream);
-}
-
-// The same call with a split-K workspace (gkg_x6_splitk_workspace_bytes() bytes, its first 4 KiB ZERO before the first use;
-// every launch leaves them zero again): few-row / long-contraction shapes then run as several K ranges per tile.
-extern "C" int gkg_linear_bn_fwd_x6_sk(const float* x, int ldx, size_t x_bstride, const void* planes_fwd, float* y, int R,
-                                       int cin, int cout, int nb, int train, const float* gamma, const float* beta,
-                                       const float* bias, float* running_mean, float* running_var,
-                                       long long* num_batches_tracked, float* bn_a, float* bn_c, float* bn_mean,
-                                       float* bn_invstd, float momentum, float eps, double* stats, void* splitk_ws,
-                                       size_t splitk_bytes, unsigned flags, void* stream) {
-  if (splitk_ws && (splitk_bytes < X6_SK_BYTES || ((size_t)splitk_ws & 15)))
-    return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_bn_fwd_x6_sk: need a 16-byte aligned workspace of gkg_x6_splitk_workspace_bytes() bytes (or NULL: no split)");
-  return x6_fwd_impl(x, ldx, x_bstride, planes_fwd, y, R, cin, cout, nb, train, gamma, beta, bias, running_mean, running_var,
-                     num_batches_tracked, bn_a, bn_c, bn_mean, bn_invstd, momentum, eps, stats, splitk_ws, splitk_bytes, stream, flags);
+  return gkg_linear_bn_fwd_x6_sk(x, ldx, x_bstride, planes_fwd, y, R, cin, cout, nb, train, gamma, beta, bias, running_mean, running_var,
+                                 num_batches_tracked, bn_a, bn_c, bn_mean, bn_invstd, momentum, eps, stats, nullptr, 0, 0, stream);
 }
 
 // Workgroups of the tile-walk launch that y (nb, R, cout) = x (nb, R, cin) W^T takes on the current device with these flags and
-// with / without a split-K workspace — x6_launch's rules, for callers and tests that must know the launch form beforehand; 0: the
-// launch does not walk (another body, a split contraction, not two rounds, GKG_X6_NO_WALK); < 0: error.
+// with / without a split-K workspace — the forward's plan with the plain epilogue (X6GemmCall::slots has the quirk), for callers and
+// tests that must know the launch form beforehand; 0: the launch does not walk (another body, a split contraction, not two rounds,
+// GKG_X6_NO_WALK); < 0: error.
 extern "C" int gkg_x6_walk_workgroups(int R, int cin, int cout, int nb, int has_ws, unsigned flags) {
   if (R <= 0 || x6_bad_dim(cin) || x6_bad_dim(cout) || nb <= 0 || nb > 64) return gkg_fail(GKG_ERR_SHAPE, "gkg_x6_walk_workgroups: bad shape");
-  const int mt = (R + 127) / 128, nt = (cout + 63) / 64;
-  const long long base2 = (long long)mt * nt * nb;
-  if (x6_ks_form(R, cout, nb, has_ws != 0, flags) || x6_tile_ksplit(base2, (cin + 31) / 32, has_ws != 0) >= 2) return 0;
-  if ((base2 < 160 && !(flags & GKG_X6_FORCE_WALK)) || cout == 80) return 0;          // 32- / 80-column tiles: one-tile form only
-  int slots = 0;
-  hipError_t e = x6_kernel_setup<2, X6_STORE, 64, true>(x6_ring_bytes(2, 64), &slots);
-  if (e != hipSuccess) return gkg_fail_hip(e, "gkg_x6_walk_workgroups");
-  return x6_walk_grid((long long)nb * mt, nt, 1, slots, flags);
+  X6GemmCall q = x6_call(X6R_FWD, R, cout, cin, nb, nullptr, cin, (size_t)R * cin, nullptr, has_ws ? X6_SK_BYTES : 0, flags);
+  q.has_ws = has_ws != 0;
+  X6GemmPlan pl;
+  x6_gemm_ladder(q, &pl);
+  if (hipError_t e = x6_plan_walk<X6_STORE>(q, pl); e != hipSuccess) return gkg_fail_hip(e, "gkg_x6_walk_workgroups");
+  return pl.body == X6_BODY_WALK ? (int)pl.grid_x : 0;
 }
 
-// dx (nb, R, cin) = dy (nb, R, cout; row pitch ldg, batch stride g_bstride) * w, the weights given as dgrad planes.
-static int x6_dgrad_impl(const float* dy, int ldg, size_t g_bstride, const void* planes_dgrad, float* dx, int R,
-                         int cin, int cout, int nb, const float* residual, void* sk_ws, size_t sk_bytes, void* stream,
-                         int ldx = 0, size_t x_bstride = 0, unsigned flags = 0) {
+// dx (nb, R, cin) = dy (nb, R, cout; row pitch ldg, batch stride g_bstride) * w, the weights given as dgrad planes; dx with row
+// pitch ldx / batch stride x_bstride (ldx == 0: contiguous).  `residual` (nb, R, cin) contiguous or null: dx = dy w + residual —
+// the gradient that reaches the layer's input along a skip connection (reference torch_vertex.py:331,354,402 `+ _tmp`), added in
+// the epilogue instead of by a stand-alone kernel.
+extern "C" int gkg_linear_dgrad_x6_sk(const float* dy, int ldg, size_t g_bstride, const void* planes_dgrad, float* dx, int R,
+                                      int cin, int cout, int nb, const float* residual, void* splitk_ws, size_t splitk_bytes,
+                                      int ldx, size_t x_bstride, unsigned flags, void* stream) {
+  X6GemmCall q = x6_call(X6R_DGRAD, R, cin, cout, nb, dy, ldg, g_bstride, splitk_ws, splitk_bytes, flags);
+  q.ldc = ldx; q.c_bstride = x_bstride; q.has_residual = residual != nullptr;
+  X6GemmPlan pl;
+  const char* msg = nullptr;
+  if (const int rc = x6_gemm_plan(q, &pl, &msg)) return gkg_fail(rc, msg);
   if (!dy || !planes_dgrad || !dx) return gkg_fail(GKG_ERR_NULL, "gkg_linear_dgrad_x6: null pointer");
-  if (ldx == 0) { ldx = cin; x_bstride = (size_t)R * cin; }
-  if (ldx < cin || (ldx & 3) || (x_bstride & 3)) return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_dgrad_x6: bad dx pitch / batch stride");
-  if (R <= 0 || x6_bad_dim(cin) || x6_bad_dim(cout) || nb <= 0 || nb > 64 || ldg < cout || (ldg & 3) || (g_bstride & 3) ||
-      ((size_t)dy & 15))
-    return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_dgrad_x6: need R > 0, cin % 4 == 0, cout % 4 == 0, 1 <= nb <= 64, 16-byte aligned rows");
-  if ((size_t)R * ldg * 4 > 0xffffffffull) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_dgrad_x6: operand larger than 4 GiB per batch");
-  X6Args a{};
-  a.A = dy; a.a_bstride = g_bstride; a.lda = ldg;
-  a.NP = (cin + X6_NPAD - 1) / X6_NPAD * X6_NPAD; a.KC = (cout + 31) / 32 * 4;
-  a.P = (const uint4*)planes_dgrad; a.p_bstride = (size_t)3 * a.KC * a.NP;
-  a.C = dx; a.c_bstride = x_bstride; a.ldc = ldx;
-  a.M = R; a.N = cin; a.K = cout;
-  a.add = residual;
-  hipError_t e = x6_launch<X6_STORE>(a, nb, (hipStream_t)stream, sk_ws, sk_bytes, flags);
+  const X6Args a = x6_operands(dy, planes_dgrad, dx, ldx ? x_bstride : (size_t)R * cin, ldx ? ldx : cin, residual);
+  hipError_t e = x6_launch<X6_STORE>(q, pl, a, splitk_ws, (hipStream_t)stream);
   return e == hipSuccess ? 0 : gkg_fail_hip(e, "gemm_x6_kernel (dgrad)");
 }
 
 extern "C" int gkg_linear_dgrad_x6(const float* dy, int ldg, size_t g_bstride, const void* planes_dgrad, float* dx, int R,
                                    int cin, int cout, int nb, void* stream) {
-  return x6_dgrad_impl(dy, ldg, g_bstride, planes_dgrad, dx, R, cin, cout, nb, nullptr, nullptr, 0, stream);
-}
-
-// `residual` (nb, R, cin) contiguous or null: dx = dy w + residual — the gradient that reaches the layer's input along a
-// skip connection (reference torch_vertex.py:331,354,402 `+ _tmp`), added in the epilogue instead of by a stand-alone kernel.
-extern "C" int gkg_linear_dgrad_x6_sk(const float* dy, int ldg, size_t g_bstride, const void* planes_dgrad, float* dx, int R,
-                                      int cin, int cout, int nb, const float* residual, void* splitk_ws, size_t splitk_bytes,
-                                      int ldx, size_t x_bstride, unsigned flags, void* stream) {
-  if (splitk_ws && (splitk_bytes < X6_SK_BYTES || ((size_t)splitk_ws & 15)))
-    return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_dgrad_x6_sk: need a 16-byte aligned workspace of gkg_x6_splitk_workspace_bytes() bytes (or NULL: no split)");
-  return x6_dgrad_impl(dy, ldg, g_bstride, planes_dgrad, dx, R, cin, cout, nb, residual, splitk_ws, splitk_bytes, stream, ldx, x_bstride, flags);
+  return gkg_linear_dgrad_x6_sk(dy, ldg, g_bstride, planes_dgrad, dx, R, cin, cout, nb, nullptr, nullptr, 0, 0, 0, 0, stream);
 }
 
 // The un-grouped input gradient (+ token-major residual) stored CHANNEL-MAJOR: dx (B, cin, N) = (dy w + residual)^T per image,
 // R == B * N rows — a block's first layer, whose input gradient leaves the block as an NCHW tensor (round 8: the re-layout pass
-// behind gkg_linear_dgrad_x6_sk and its kernel boundary are gone).  The 128-row tile kernel stores so itself (X6_STORE_NCHW) when
-// N % 4 == 0 and the shape takes that kernel; otherwise (the short-matrix body, 80-column tiles, N % 4 != 0) the two launches
-// run as before: gkg_linear_dgrad_x6_sk into `dx_tm` (R, cin; scratch, required) and gkg_tm_affine_to_nchw.  Either way dx
-// has the bits of that two-launch form.
+// behind gkg_linear_dgrad_x6_sk and its kernel boundary are gone).  The 128-row tile kernel stores so itself (X6_STORE_NCHW) where
+// the plan allows (x6_nchw_two_launch); otherwise the two launches run as before: gkg_linear_dgrad_x6_sk into `dx_tm` (R, cin;
+// scratch, required) and gkg_tm_affine_to_nchw.  Either way dx has the bits of that two-launch form.
 extern "C" int gkg_linear_dgrad_x6_nchw(const float* dy, int ldg, const void* planes_dgrad, float* dx, float* dx_tm, int R, int cin,
                                         int cout, const float* residual, int B, int N, void* splitk_ws, size_t splitk_bytes,
                                         unsigned flags, void* stream) {
+  X6GemmCall q = x6_call(X6R_DGRAD_NCHW, R, cin, cout, 1, dy, ldg, 0, splitk_ws, splitk_bytes, flags);
+  q.has_residual = residual != nullptr; q.nchw_b = B; q.nchw_n = N; q.dx_aligned = ((size_t)dx & 15) == 0;
+  X6GemmPlan pl;
+  const char* msg = nullptr;
+  if (const int rc = x6_gemm_plan(q, &pl, &msg)) return gkg_fail(rc, msg);
   if (!dy || !planes_dgrad || !dx || !dx_tm) return gkg_fail(GKG_ERR_NULL, "gkg_linear_dgrad_x6_nchw: null pointer");
-  if (B <= 0 || N <= 0 || (long long)B * N != R) return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_dgrad_x6_nchw: R == B * N");
-  if (splitk_ws && (splitk_bytes < X6_SK_BYTES || ((size_t)splitk_ws & 15)))
-    return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_dgrad_x6_nchw: need a 16-byte aligned workspace of gkg_x6_splitk_workspace_bytes() bytes (or NULL: no split)");
-  // x6_launch's rule for the short-matrix body (which has no channel-major store)
-  const bool ks_form = x6_ks_form(R, cin, 1, splitk_ws != nullptr, flags);
-  const bool tile80 = cin == 80 && (long long)((R + 127) / 128) * ((cin + 63) / 64) >= 160;
-  if ((N & 3) || ks_form || tile80 || ((size_t)dx & 15)) {
-    const int rc = x6_dgrad_impl(dy, ldg, (size_t)R * cout, planes_dgrad, dx_tm, R, cin, cout, 1, residual, splitk_ws, splitk_bytes, stream, 0, 0, flags);
-    if (rc != 0) return rc;
-    return gkg_tm_affine_to_nchw(dx_tm, nullptr, nullptr, nullptr, dx, B, cin, N, nullptr, stream);
+  if (pl.two_launch) {
+    const int rc = gkg_linear_dgrad_x6_sk(dy, ldg, (size_t)R * cout, planes_dgrad, dx_tm, R, cin, cout, 1, residual, splitk_ws, splitk_bytes, 0, 0,
+                                          flags, stream);
+    return rc != 0 ? rc : gkg_tm_affine_to_nchw(dx_tm, nullptr, nullptr, nullptr, dx, B, cin, N, nullptr, stream);
   }
-  if (R <= 0 || x6_bad_dim(cin) || x6_bad_dim(cout) || ldg < cout || (ldg & 3) || ((size_t)dy & 15))
-    return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_dgrad_x6_nchw: need R > 0, cin % 4 == 0, cout % 4 == 0, 16-byte aligned rows");
-  if ((size_t)R * ldg * 4 > 0xffffffffull) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_dgrad_x6_nchw: operand larger than 4 GiB");
-  X6Args a{};
-  a.A = dy; a.a_bstride = 0; a.lda = ldg;
-  a.NP = (cin + X6_NPAD - 1) / X6_NPAD * X6_NPAD; a.KC = (cout + 31) / 32 * 4;
-  a.P = (const uint4*)planes_dgrad; a.p_bstride = (size_t)3 * a.KC * a.NP;
-  a.C = dx; a.c_bstride = (size_t)R * cin; a.ldc = cin;
-  a.M = R; a.N = cin; a.K = cout;
-  a.add = residual;
+  X6Args a = x6_operands(dy, planes_dgrad, dx, (size_t)R * cin, cin, residual);
   a.nchw_n = N; a.nchw_c = cin;
-  hipError_t e = x6_launch<X6_STORE_NCHW>(a, 1, (hipStream_t)stream, splitk_ws, splitk_bytes, flags);
+  hipError_t e = x6_launch<X6_STORE_NCHW>(q, pl, a, splitk_ws, (hipStream_t)stream);
   return e == hipSuccess ? 0 : gkg_fail_hip(e, "gemm_x6_kernel (dgrad, channel-major store)");
 }
 
@@ -1413,10 +1279,32 @@ extern "C" int gkg_linear_dgrad_x6_nchw(const float* dy, int ldg, const void* pl
 // gradient of the layer  h = act(BN(py))  that made this projection's input; psums [pnb][2][pco] fp64 receives (atomics)
 // sum dz and sum dz * yhat per channel — what gkg_bn_bwd_atomic's statistics pass would compute from dx and py.  Un-grouped
 // projections only (nb == 1): dx (R, cin), cin == pnb * pco, py (pnb, R, pco).
+// With gkg_linear_dgrad_x6_sk's choice of kernel body (round 9): given the split-K workspace the launch takes the short-matrix
+// body / the cross-workgroup split exactly where gkg_linear_dgrad_x6_sk does for the same shape and flags, so dx has that call's
+// bits, and `residual` (R, cin; or NULL) is added in front of the statistics (the BN's upstream gradient is the sum).  The 128-row
+// tile body takes no residual here: gkg_linear_dgrad_x6_bnbwd_sk_supported() tells, and an unsupported call returns
+// GKG_ERR_UNSUPPORTED with nothing launched.
+extern "C" int gkg_linear_dgrad_x6_bnbwd_sk_supported(int R, int cin, int has_residual, int has_ws, unsigned flags) {
+  return (!has_residual || x6_bnbwd_takes_residual(R, cin, has_ws != 0, flags)) ? 1 : 0;
+}
+
 extern "C" int gkg_linear_dgrad_x6_bnbwd_sk(const float* dy, int ldg, const void* planes_dgrad, float* dx, int R, int cin, int cout,
                                             const float* residual, const float* py, const float* pa, const float* pc,
                                             const float* pmean, const float* pinvstd, double* psums, int pnb, int pco, int pact,
-                                            void* splitk_ws, size_t splitk_bytes, unsigned flags, void* stream);
+                                            void* splitk_ws, size_t splitk_bytes, unsigned flags, void* stream) {
+  X6GemmCall q = x6_call(X6R_DGRAD_BNBWD, R, cin, cout, 1, dy, ldg, 0, splitk_ws, splitk_bytes, flags);
+  q.has_residual = residual != nullptr; q.pnb = pnb; q.pco = pco; q.pact = pact;
+  X6GemmPlan pl;
+  const char* msg = nullptr;
+  if (const int rc = x6_gemm_plan(q, &pl, &msg)) return gkg_fail(rc, msg);
+  if (!dy || !planes_dgrad || !dx || !py || !pa || !pc || !pmean || !pinvstd || !psums)
+    return gkg_fail(GKG_ERR_NULL, "gkg_linear_dgrad_x6_bnbwd_sk: null pointer");
+  X6Args a = x6_operands(dy, planes_dgrad, dx, (size_t)R * cin, cin, residual);
+  a.py = py; a.pa = pa; a.pc = pc; a.pmean = pmean; a.pinvstd = pinvstd; a.psums = psums; a.pco = pco; a.pact = pact;
+  hipError_t e = x6_launch<X6_BNBWD>(q, pl, a, splitk_ws, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : gkg_fail_hip(e, "gemm_x6 (dgrad + BN backward statistics)");
+}
+
 extern "C" int gkg_linear_dgrad_x6_bnbwd(const float* dy, int ldg, const void* planes_dgrad, float* dx, int R, int cin, int cout,
                                          const float* py, const float* pa, const float* pc, const float* pmean,
                                          const float* pinvstd, double* psums, int pnb, int pco, int pact, void* stream) {
@@ -1425,294 +1313,74 @@ extern "C" int gkg_linear_dgrad_x6_bnbwd(const float* dy, int ldg, const void* p
                                       nullptr, 0, 0, stream);
 }
 
-// gkg_linear_dgrad_x6_bnbwd with gkg_linear_dgrad_x6_sk's choice of kernel body (round 9): given the split-K workspace the launch
-// takes the short-matrix body / the cross-workgroup split exactly where gkg_linear_dgrad_x6_sk does for the same shape and flags,
-// so dx has that call's bits, and `residual` (R, cin; or NULL) is added in front of the statistics (the BN's upstream gradient is
-// the sum).  The 128-row tile body takes no residual here: gkg_linear_dgrad_x6_bnbwd_sk_supported() tells, and an unsupported
-// call returns GKG_ERR_UNSUPPORTED with nothing launched.
-extern "C" int gkg_linear_dgrad_x6_bnbwd_sk_supported(int R, int cin, int has_residual, int has_ws, unsigned flags) {
-  return (!has_residual || x6_ks_form(R, cin, 1, has_ws != 0, flags)) ? 1 : 0;
-}
-
-extern "C" int gkg_linear_dgrad_x6_bnbwd_sk(const float* dy, int ldg, const void* planes_dgrad, float* dx, int R, int cin, int cout,
-                                            const float* residual, const float* py, const float* pa, const float* pc,
-                                            const float* pmean, const float* pinvstd, double* psums, int pnb, int pco, int pact,
-                                            void* splitk_ws, size_t splitk_bytes, unsigned flags, void* stream) {
-  if (!dy || !planes_dgrad || !dx || !py || !pa || !pc || !pmean || !pinvstd || !psums)
-    return gkg_fail(GKG_ERR_NULL, "gkg_linear_dgrad_x6_bnbwd_sk: null pointer");
-  if (splitk_ws && (splitk_bytes < X6_SK_BYTES || ((size_t)splitk_ws & 15)))
-    return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_dgrad_x6_bnbwd_sk: need a 16-byte aligned workspace of gkg_x6_splitk_workspace_bytes() bytes (or NULL: no split)");
-  if (R <= 0 || x6_bad_dim(cin) || x6_bad_dim(cout) || ldg < cout || (ldg & 3) || ((size_t)dy & 15) || pnb <= 0 || pco <= 0 ||
-      (long long)pnb * pco != cin || (pact != 0 && pact != 1))
-    return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_dgrad_x6_bnbwd_sk: need R > 0, cin % 4 == 0, cout % 4 == 0, cin == pnb * pco, 16-byte aligned rows");
-  if ((size_t)R * ldg * 4 > 0xffffffffull) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_dgrad_x6_bnbwd_sk: operand larger than 4 GiB");
-  if (residual && !x6_ks_form(R, cin, 1, splitk_ws != nullptr, flags))
-    return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_dgrad_x6_bnbwd_sk: a residual needs the short-matrix body");
-  X6Args a{};
-  a.A = dy; a.a_bstride = 0; a.lda = ldg;
-  a.NP = (cin + X6_NPAD - 1) / X6_NPAD * X6_NPAD; a.KC = (cout + 31) / 32 * 4;
-  a.P = (const uint4*)planes_dgrad; a.p_bstride = (size_t)3 * a.KC * a.NP;
-  a.C = dx; a.c_bstride = (size_t)R * cin; a.ldc = cin;
-  a.M = R; a.N = cin; a.K = cout;
-  a.add = residual;
-  a.py = py; a.pa = pa; a.pc = pc; a.pmean = pmean; a.pinvstd = pinvstd; a.psums = psums; a.pco = pco; a.pact = pact;
-  hipError_t e = x6_launch<X6_BNBWD>(a, 1, (hipStream_t)stream, splitk_ws, splitk_bytes, flags);
-  return e == hipSuccess ? 0 : gkg_fail_hip(e, "gemm_x6 (dgrad + BN backward statistics)");
-}
-
+// ---- weight gradients ---------------------------------------------------------------------------------------------------------
 // dw (nb, cout, cin) += dy^T x over the R rows; dw must be ZERO on entry (the slabs of rows are added with fp32 atomics).
 // dy (nb, R, cout) row pitch ldg / batch stride g_bstride, x (nb, R, cin) row pitch ldx / batch stride x_bstride (floats).
+// The deterministic forms (gkg_linear_wgrad_x6_det, _batch_det; include/gkg_hip.h has the definition) are the same launches with
+// the DET instantiations of their bodies — slab s of the plan stores its tiles into image s of the caller's workspace (main
+// launch's slabs first, then the ragged remainder's, both in ascending row order) — and ONE small launch behind them that adds
+// the images in that order and writes dW.  No atomics, no memset, no counters: the kernel boundary orders the partial stores
+// before the reduction's loads.
 namespace gkg {
-struct X6WgradPlan {
-  X6WgradArgs main;              // the LDS-DMA launch over the whole 128-row units (main.K rows; 0: none)
-  bool wide;
-  int grid_x;                    // workgroups per group of the main launch
-  X6WgradArgs rest;              // the register-load launch over the ragged remainder (rest.K rows; 0: none)
-  int rest_grid_x;
-};
-
-static int x6_wgrad_set_attr(bool wide) {
-  // the attribute is per DEVICE: the guard is indexed by the current device (a per-process guard left a second GPU of the
-  // same process without it — ADVICE r3)
-  static bool once[3][64] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const size_t sh_w = X6W_SH_WIDE, sh_d = X6W_SH_DMA;
-  if (dev < 0 || dev >= 64 || !once[wide][dev]) {
-    hipError_t e = hipFuncSetAttribute(wide ? (const void*)wgrad_x6_wide_kernel : (const void*)wgrad_x6_dma_kernel,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(wide ? sh_w : sh_d));
-    if (e != hipSuccess) return gkg_fail_hip(e, "wgrad_x6 DMA kernel (attribute)");
-    if (dev >= 0 && dev < 64) once[wide][dev] = true;
-  }
-  if (dev < 0 || dev >= 64 || !once[2][dev]) {
-    hipError_t e = hipFuncSetAttribute((const void*)wgrad_x6_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh_w);
-    if (e != hipSuccess) return gkg_fail_hip(e, "wgrad_x6 batch kernel (attribute)");
-    if (dev >= 0 && dev < 64) once[2][dev] = true;
-  }
-  return 0;
+static X6WgradCall x6w_call(const float* dy, int ldg, size_t g_bstride, const float* x, int ldx, size_t x_bstride, int R, int cin, int cout,
+                            int nb, int kperm, int force_slabs) {
+  return X6WgradCall{R, cin, cout, nb, ldg, ldx, g_bstride, x_bstride, (((size_t)dy | (size_t)x) & 15) == 0, 0, kperm, force_slabs};
+}
+static X6WgradCall x6w_call(const GkgWgradProblem& q) {
+  return x6w_call(q.dy, q.ldg, q.g_bstride, q.x, q.ldx, q.x_bstride, q.R, q.cin, q.cout, q.nb, q.kperm, 0);
 }
 
-// Tile shape, operand roles and row slabs of one weight gradient.  `batched` > 0: the launch shares the chip with other
-// problems (gkg_linear_wgrad_x6_batch) — slabs of ~`batched` units whatever the tile count, few-slab problems spread over the
-// XCDs by tiles.
-static int x6_wgrad_plan(const float* dy, int ldg, size_t g_bstride, const float* x, int ldx, size_t x_bstride, float* dw, int R,
-                         int cin, int cout, int nb, int batched, X6WgradPlan& pl, int kperm = 0, int force_slabs = 0,
-                         int aligned_as = -1) {
-  if (!dy || !x || !dw) return gkg_fail(GKG_ERR_NULL, "gkg_linear_wgrad_x6: null pointer");
-  if (kperm && (cin & 1)) return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_wgrad_x6: kperm needs an even cin");
-  if (R <= 0 || cin <= 0 || cout <= 0 || nb <= 0 || nb > 64 || ldg < cout || ldx < cin)
-    return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_wgrad_x6: need R, cin, cout > 0, 1 <= nb <= 64, pitches >= widths");
-  if ((size_t)ldg * 4 * 16 > 0x7fffffffull || (size_t)ldx * 4 * 16 > 0x7fffffffull) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_wgrad_x6: row pitch too large");
+// bind: the operands of one planned launch (`part`: the plan's main or rest) into its kernel arguments.  C: dw, or image 0 of the
+// launch in a deterministic workspace.
+static X6WgradArgs x6w_bind(const X6WgradCall& q, const X6WgradPlan& pl, const X6WgradPart& part, const float* dy, const float* x, float* C) {
   X6WgradArgs a{};
-  a.A = dy; a.a_bstride = g_bstride; a.lda = ldg;
-  a.B = x; a.b_bstride = x_bstride; a.ldb = ldx;
-  a.C = dw; a.c_bstride = (size_t)cout * cin; a.ldc = cin;
-  a.M = cout; a.N = cin; a.K = R;
-  a.kperm = kperm ? 1 : 0;
-  a.mtiles = (cout + 63) / 64; a.ntiles = (cin + 63) / 64;
-  // whole 128-row units go through an LDS-DMA kernel when the rows are 16-byte aligned; the ragged rest (and everything,
-  // when they are not) through the register-load kernel
-  // (aligned_as >= 0, the host-side queries of the deterministic form: the caller's word for the pointers and batch strides)
-  const bool aligned = (cin & 3) == 0 && (cout & 3) == 0 && (ldg & 3) == 0 && (ldx & 3) == 0 &&
-                       (aligned_as >= 0 ? aligned_as != 0
-                                        : (g_bstride & 3) == 0 && (x_bstride & 3) == 0 && ((size_t)dy & 15) == 0 && ((size_t)x & 15) == 0) &&
-                       (size_t)R * ldg * 4 < 0xffffffffull && (size_t)R * ldx * 4 < 0xffffffffull;
-  // 64 x 128 tiles (wgrad_x6_wide_kernel) when one of the two widths pads to 128 at no more than a tenth of extra work
-  // (measured in the cfg2 step, wide vs 64 x 64: 640 -> 320 42.6 -> 35.6 us, 1280 -> 320 37.9 -> 30.9, but 320 -> 320 at
-  // 20 % padding 22.3 -> 24.3); the 128-wide side is cin, or — roles of the operands exchanged, dW written transposed — cout
-  const long long padn = (long long)((cin + 127) / 128) * 128 * 100 / ((long long)a.ntiles * 64);
-  const long long padm = (long long)((cout + 127) / 128) * 128 * 100 / ((long long)a.mtiles * 64);
-  bool wide = aligned && (padn <= 110 || padm <= 110);
-  bool swap = wide && padm < padn;
-  if (batched > 0 && aligned) {
-    // inside a batched launch the tile count of ONE problem no longer decides how well the chip is filled, only the matrix
-    // time does: per MFMA the 64 x 64 loop carries 7.7 vector instructions and the 64 x 128 loop 5.8 (compiled counts, at the
-    // bodies), so a 64 x 64 tile (24 MFMAs per step) is charged 36 and a wide tile 48 — padding up to 128 pays until it costs
-    // that much (160 x 160: 3 x 2 wide tiles against 3 x 3; 320 x 320: 5 x 3 against 5 x 5)
-    const long long c64 = (long long)a.mtiles * a.ntiles * 36;
-    const long long cwn = (long long)a.mtiles * ((cin + 127) / 128) * 48, cwm = (long long)a.ntiles * ((cout + 127) / 128) * 48;
-    wide = (cwn < cwm ? cwn : cwm) <= c64;
-    swap = wide && cwm < cwn;
-  }
-  const int main_mtiles = !wide ? a.mtiles : (swap ? a.ntiles : a.mtiles);
-  const int main_ntiles = !wide ? a.ntiles : (swap ? (cout + 127) / 128 : (cin + 127) / 128);
-  const int tiles = main_mtiles * main_ntiles * nb, units = R / 128;
-  int splits = 1, share = 0;
-  // the stand-alone rule (below): the slab count that minimises rounds x (units per slab + fixed cost) over an XCD's 32 CUs
-  int sp_alone = 1;
-  {
-    long long best = -1;
-    for (int sp = 1; sp <= units && sp <= 4096; ++sp) {
-      const long long per_xcd = (long long)tiles * ((sp + 7) / 8);
-      const long long rounds = (per_xcd + 31) / 32;
-      const long long cost = rounds * ((units + sp - 1) / sp + 6);
-      if (best < 0 || cost < best) { best = cost; sp_alone = sp; }
-    }
-  }
-  // a problem that fills the chip on its own (GKGNet-576's stage-1 / stage-2 weight gradients: thousands of 128-row units) keeps
-  // its stand-alone slabs inside a batch too — ~20-unit slabs doubled its workgroup count (cfg4: 12.6 -> 13.3 ms of weight
-  // gradients per step)
-  if (batched && (long long)tiles * sp_alone >= 512) batched = 0;
-  if (batched) {
-    // ~`batched` (default 20) units of 128 rows per workgroup (its fixed cost — ring fill, LDS reduction, the tile's atomics — is worth about 6):
-    // 1 / 2 / 4 slabs shared by 8 / 4 / 2 XCDs each, or a multiple of 8 slabs on one XCD each
-    const int want = (units + batched - 1) / batched;
-    if (want <= 1) splits = 1;
-    else if (want <= 2) splits = 2;
-    else if (want <= 5) splits = 4;
-    else splits = (want + 7) / 8 * 8;
-    if (splits > units) splits = units > 0 ? units : 1;
-    if (splits < 8) { while (8 % splits) --splits; share = 8 / splits; }
-  } else {
-    // Slabs of whole 128-row units (4 waves x 2 steps x 16 rows).  One workgroup per CU fits (128 / 144 KiB of LDS rings) and
-    // slab s runs with all its tiles on XCD s % 8 (its rows are fetched into that L2 once), so an XCD's 32 CUs work in rounds
-    // over tiles x ceil(slabs / 8) workgroups: pick the slab count that minimises rounds x (units per slab + fixed cost), the
-    // fixed cost (ring fill, LDS reduction, the tile's atomics) being worth about 6 units of streaming.  (Counting rounds over
-    // the whole chip instead put 36 workgroups on two XCDs at 6 tiles x 42 slabs: 245 -> 393 us at 663 552 x 160 -> 80.)
-    // (force_slabs > 0, gkg_linear_wgrad_x6_det: the caller's slab count, cut to the number of units below)
-    splits = force_slabs > 0 ? force_slabs : sp_alone;
-  }
-  a.rows_per_split = units > 0 ? (units + splits - 1) / splits * 128 : 128;
-  const int main_rows = aligned ? units * 128 : 0;
-  pl.wide = wide;
-  pl.main = a;
-  pl.main.K = 0;
-  pl.grid_x = 0;
-  if (main_rows > 0) {
-    X6WgradArgs m = a;
-    m.mtiles = main_mtiles; m.ntiles = main_ntiles;
-    if (swap) {                                    // the kernel's "A" (64-wide side) is x, its "B" (128-wide side) dy
-      m.A = x; m.a_bstride = x_bstride; m.lda = ldx; m.M = cin;
-      m.B = dy; m.b_bstride = g_bstride; m.ldb = ldg; m.N = cout;
-      m.swap = 1;
-    }
-    m.K = main_rows; m.splits = splits < units ? splits : units;
-    m.ubase = units / m.splits; m.urem = units % m.splits;
-    if (share > 1 && m.splits * share == 8) {
-      m.share = share;
-      pl.grid_x = (m.mtiles * m.ntiles + share - 1) / share * 8;
-    } else {
-      pl.grid_x = (m.splits + 7) / 8 * 8 * m.mtiles * m.ntiles;
-    }
-    pl.main = m;
-  }
-  const int done = main_rows, rest = R - done;
-  pl.rest = a;
-  pl.rest.K = 0;
-  pl.rest_grid_x = 0;
-  if (rest > 0) {
-    X6WgradArgs t = a;
-    t.A = dy + (size_t)done * ldg; t.B = x + (size_t)done * ldx; t.K = rest;
-    const int tunits = (rest + 127) / 128;
-    int ts = splits > tunits ? tunits : splits;
-    t.rows_per_split = (tunits + ts - 1) / ts * 128;
-    t.splits = (rest + t.rows_per_split - 1) / t.rows_per_split;
-    pl.rest = t;
-    pl.rest_grid_x = (t.splits + 7) / 8 * 8 * a.mtiles * a.ntiles;
-  }
-  return 0;
+  const bool swap = &part == &pl.main && pl.swap;      // the kernel's "A" (64-wide side) is x, its "B" (128-wide side) dy
+  dy += (size_t)part.row0 * q.ldg; x += (size_t)part.row0 * q.ldx;
+  a.A = swap ? x : dy; a.a_bstride = swap ? q.x_bstride : q.g_bstride; a.lda = swap ? q.ldx : q.ldg;
+  a.B = swap ? dy : x; a.b_bstride = swap ? q.g_bstride : q.x_bstride; a.ldb = swap ? q.ldg : q.ldx;
+  a.C = C; a.c_bstride = (size_t)q.cout * q.cin; a.ldc = q.cin;
+  a.M = part.M; a.N = part.N; a.K = part.rows;
+  a.mtiles = part.mtiles; a.ntiles = part.ntiles; a.splits = part.splits; a.rows_per_split = part.rows_per_split;
+  a.swap = swap ? 1 : 0; a.share = part.share; a.ubase = part.ubase; a.urem = part.urem;
+  a.kperm = pl.kperm;
+  return a;
 }
-}  // namespace gkg
 
-extern "C" int gkg_linear_wgrad_x6(const float* dy, int ldg, size_t g_bstride, const float* x, int ldx, size_t x_bstride,
-                                   float* dw, int R, int cin, int cout, int nb, int kperm, void* stream) {
-  X6WgradPlan pl;
-  int rc = x6_wgrad_plan(dy, ldg, g_bstride, x, ldx, x_bstride, dw, R, cin, cout, nb, 0, pl, kperm);
-  if (rc) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipSuccess;
-  if (pl.main.K > 0) {
-    if ((rc = x6_wgrad_set_attr(pl.wide))) return rc;
+// the ragged remainder's own launch (register-load kernel); E: floats per slab image (DET)
+template <bool DET>
+static int x6w_launch_rest(const X6WgradArgs& t, int grid_x, int nb, size_t E, hipStream_t st) {
+  if constexpr (DET) hipLaunchKernelGGL(wgrad_x6_det_kernel, dim3(grid_x, nb), dim3(256), 0, st, t, E);
+  else hipLaunchKernelGGL(wgrad_x6_kernel, dim3(grid_x, nb), dim3(256), 0, st, t);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : gkg_fail_hip(e, DET ? "wgrad_x6_det_kernel" : "wgrad_x6_kernel");
+}
+
+// one problem's launches.  C: dw (zero on entry), or DET the workspace (slab images of E floats)
+template <bool DET>
+static int x6w_run(const X6WgradCall& q, const X6WgradPlan& pl, const float* dy, const float* x, float* C, size_t E, hipStream_t st) {
+  if (pl.main.rows > 0) {
+    const X6WgradArgs m = x6w_bind(q, pl, pl.main, dy, x, C);
     const size_t sh = pl.wide ? X6W_SH_WIDE : X6W_SH_DMA;
-    const dim3 grid(pl.grid_x, nb);
-    if (pl.wide) hipLaunchKernelGGL(wgrad_x6_wide_kernel, grid, dim3(256), sh, st, pl.main);
-    else hipLaunchKernelGGL(wgrad_x6_dma_kernel, grid, dim3(256), sh, st, pl.main);
-    e = hipGetLastError();
-    if (e != hipSuccess) return gkg_fail_hip(e, "wgrad_x6 DMA kernel");
-  }
-  if (pl.rest.K > 0) {
-    hipLaunchKernelGGL(wgrad_x6_kernel, dim3(pl.rest_grid_x, nb), dim3(256), 0, st, pl.rest);
-    e = hipGetLastError();
-  }
-  return e == hipSuccess ? 0 : gkg_fail_hip(e, "wgrad_x6_kernel");
-}
-
-// The weight gradients of n layers in ONE launch per 16 problems (wgrad_x6_batch_kernel): problem i is what
-// gkg_linear_wgrad_x6(p[i].dy, ..., p[i].nb) would compute — every dw ZERO on entry.  Problems whose rows are not whole
-// 128-row units / 16-byte aligned fall back to their own launches.  Largest problems first (the tail of the launch is made of
-// the short ones).
-extern "C" int gkg_linear_wgrad_x6_batch(const GkgWgradProblem* p, int n, int units_per_slab, void* stream) {
-  if (!p || n <= 0) return gkg_fail(GKG_ERR_NULL, "gkg_linear_wgrad_x6_batch: no problems");
-  if (units_per_slab < 0 || units_per_slab > 4096) return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_wgrad_x6_batch: units_per_slab out of range");
-  if (units_per_slab == 0) units_per_slab = 20;
-  hipStream_t st = (hipStream_t)stream;
-  int order[256];
-  if (n > 256) return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_wgrad_x6_batch: at most 256 problems per call");
-  for (int i = 0; i < n; ++i) order[i] = i;
-  auto work = [&](int i) { return (double)p[i].R * p[i].cin * p[i].cout * p[i].nb; };
-  for (int i = 1; i < n; ++i)                     // insertion sort, descending work
-    for (int j = i; j > 0 && work(order[j]) > work(order[j - 1]); --j) { const int t = order[j]; order[j] = order[j - 1]; order[j - 1] = t; }
-  X6WgradBatch b{};
-  int rot = 0;
-  auto flush = [&]() -> int {
-    if (b.n == 0) return 0;
-    int rc = x6_wgrad_set_attr(true);
-    if (rc) return rc;
-    hipLaunchKernelGGL(wgrad_x6_batch_kernel, dim3(b.begin[b.n]), dim3(256), X6W_SH_WIDE, st, b);
-    hipError_t e = hipGetLastError();
-    b.n = 0;
-    return e == hipSuccess ? 0 : gkg_fail_hip(e, "wgrad_x6_batch_kernel");
-  };
-  for (int oi = 0; oi < n; ++oi) {
-    const GkgWgradProblem& q = p[order[oi]];
-    X6WgradPlan pl;
-    int rc = x6_wgrad_plan(q.dy, q.ldg, q.g_bstride, q.x, q.ldx, q.x_bstride, q.dw, q.R, q.cin, q.cout, q.nb, units_per_slab, pl, q.kperm);
-    if (rc) return rc;
-    if (pl.main.K > 0) {
-      const int i = b.n;
-      pl.main.rot = rot;
-      rot = (rot + (pl.main.share > 1 ? 0 : pl.main.splits)) & 7;
-      b.p[i] = pl.main; b.wide[i] = pl.wide ? 1 : 0; b.gridx[i] = pl.grid_x;
-      b.begin[i + 1] = b.begin[i] + pl.grid_x * q.nb;
-      b.n = i + 1;
-      if (b.n == X6W_BATCH && (rc = flush())) return rc;
+    const dim3 grid(pl.main.grid_x, q.nb);
+    hipError_t e;
+    if constexpr (DET) {
+      e = pl.wide ? x6_kernel_once<wgrad_x6_wide_det_kernel>(sh) : x6_kernel_once<wgrad_x6_dma_det_kernel>(sh);
+      if (e != hipSuccess) return gkg_fail_hip(e, "wgrad_x6 deterministic kernel (attribute)");
+      if (pl.wide) hipLaunchKernelGGL(wgrad_x6_wide_det_kernel, grid, dim3(256), sh, st, m, E);
+      else hipLaunchKernelGGL(wgrad_x6_dma_det_kernel, grid, dim3(256), sh, st, m, E);
+    } else {
+      e = pl.wide ? x6_kernel_once<wgrad_x6_wide_kernel>(sh) : x6_kernel_once<wgrad_x6_dma_kernel>(sh);
+      if (e != hipSuccess) return gkg_fail_hip(e, "wgrad_x6 DMA kernel (attribute)");
+      if (pl.wide) hipLaunchKernelGGL(wgrad_x6_wide_kernel, grid, dim3(256), sh, st, m);
+      else hipLaunchKernelGGL(wgrad_x6_dma_kernel, grid, dim3(256), sh, st, m);
     }
-    if (pl.rest.K > 0) {
-      hipLaunchKernelGGL(wgrad_x6_kernel, dim3(pl.rest_grid_x, q.nb), dim3(256), 0, st, pl.rest);
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return gkg_fail_hip(e, "wgrad_x6_kernel");
-    }
+    e = hipGetLastError();
+    if (e != hipSuccess) return gkg_fail_hip(e, DET ? "wgrad_x6 deterministic DMA kernel" : "wgrad_x6 DMA kernel");
   }
-  return flush();
-}
-
-// ---- deterministic weight gradients (gkg_linear_wgrad_x6_det, _batch_det; include/gkg_hip.h has the definition) ---------------
-// The launches of the entry points above with the DET instantiations of their bodies — slab s of the plan stores its tiles into
-// image s of the caller's workspace (main launch's slabs first, then the ragged remainder's, both in ascending row order) —
-// and ONE small launch behind them that adds the images in that order and writes dW.  No atomics, no memset, no counters: the
-// kernel boundary orders the partial stores before the reduction's loads.
-namespace gkg {
-static int x6_wdet_set_attr(int kind) {          // 0: 64 x 64 DMA body, 1: wide body, 2: batch
-  static bool once[3][64] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !once[kind][dev]) {
-    const void* f = kind == 0 ? (const void*)wgrad_x6_dma_det_kernel
-                              : kind == 1 ? (const void*)wgrad_x6_wide_det_kernel : (const void*)wgrad_x6_batch_det_kernel;
-    hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kind == 0 ? X6W_SH_DMA : X6W_SH_WIDE));
-    if (e != hipSuccess) return gkg_fail_hip(e, "wgrad_x6 deterministic kernel (attribute)");
-    if (dev >= 0 && dev < 64) once[kind][dev] = true;
-  }
+  if (pl.rest.rows > 0)
+    return x6w_launch_rest<DET>(x6w_bind(q, pl, pl.rest, dy, x, C + (DET ? (size_t)pl.main_slabs() * E : 0)), pl.rest.grid_x, q.nb, E, st);
   return 0;
 }
-
-inline int x6_wdet_main_slabs(const X6WgradPlan& pl) { return pl.main.K > 0 ? pl.main.splits : 0; }
-inline int x6_wdet_slabs(const X6WgradPlan& pl) { return x6_wdet_main_slabs(pl) + (pl.rest.K > 0 ? pl.rest.splits : 0); }
-// elements of dw = floats of one slab image; the reduction's grid is counted in ints
-inline bool x6_wdet_elems_ok(int cin, int cout, int nb) {
-  return cin > 0 && cout > 0 && nb > 0 && (unsigned long long)nb * (unsigned long long)cout * (unsigned long long)cin <= (1ull << 31);
-}
-static const float* const X6W_ANY = reinterpret_cast<const float*>(16);      // the queries plan without operands
 
 // the reduction launches of up to X6W_BATCH problems each
 struct X6WdetReducer {
@@ -1738,17 +1406,88 @@ struct X6WdetReducer {
     return 0;
   }
 };
+
+// The weight gradients of n layers in ONE launch per 16 problems (wgrad_x6_batch_kernel): problem i is what
+// gkg_linear_wgrad_x6(p[i].dy, ..., p[i].nb) would compute — every dw ZERO on entry.  Problems whose rows are not whole
+// 128-row units / 16-byte aligned fall back to their own launches, in the plan's order between the group launches.
+// DET: every problem's slab images in the workspace, then every dw in slab order (X6WdetReducer).
+template <bool DET>
+static int x6w_batch_run(const GkgWgradProblem* p, int n, int units_per_slab, void* workspace, size_t workspace_bytes, hipStream_t st) {
+  X6WgradBatchPlan bp;
+  const char* msg = nullptr;
+  int rc = x6_wgrad_batch_plan(p, n, units_per_slab, DET, &bp, &msg);
+  if (rc) return gkg_fail(rc, msg);
+  if (DET && (!workspace || ((size_t)workspace & 15) || workspace_bytes < ((bp.det_floats * 4 + 15) & ~(size_t)15)))
+    return gkg_fail(GKG_ERR_WORKSPACE, "gkg_linear_wgrad_x6_batch_det: workspace NULL, not 16-byte aligned or below gkg_linear_wgrad_x6_batch_det_workspace_bytes()");
+  X6WgradBatchDet b{};
+  auto flush = [&]() -> int {
+    if (b.b.n == 0) return 0;
+    hipError_t e = DET ? x6_kernel_once<wgrad_x6_batch_det_kernel>(X6W_SH_WIDE) : x6_kernel_once<wgrad_x6_batch_kernel>(X6W_SH_WIDE);
+    if (e != hipSuccess) return gkg_fail_hip(e, DET ? "wgrad_x6 deterministic kernel (attribute)" : "wgrad_x6 batch kernel (attribute)");
+    if constexpr (DET) hipLaunchKernelGGL(wgrad_x6_batch_det_kernel, dim3(b.b.begin[b.b.n]), dim3(256), X6W_SH_WIDE, st, b);
+    else hipLaunchKernelGGL(wgrad_x6_batch_kernel, dim3(b.b.begin[b.b.n]), dim3(256), X6W_SH_WIDE, st, b.b);
+    e = hipGetLastError();
+    b.b.n = 0;
+    return e == hipSuccess ? 0 : gkg_fail_hip(e, DET ? "wgrad_x6_batch_det_kernel" : "wgrad_x6_batch_kernel");
+  };
+  float* cur = (float*)workspace;
+  for (int oi = 0; oi < n; ++oi) {
+    const GkgWgradProblem& q = p[bp.order[oi]];
+    const X6WgradPlan& pl = bp.pl[oi];
+    const X6WgradCall qc = x6w_call(q);
+    const size_t E = (size_t)q.nb * q.cout * q.cin;
+    float* C = DET ? cur : q.dw;
+    if (const int i = bp.slot[oi]; i >= 0) {
+      b.b.p[i] = x6w_bind(qc, pl, pl.main, q.dy, q.x, C);
+      b.b.p[i].rot = bp.rot[oi];
+      b.b.wide[i] = pl.wide ? 1 : 0; b.b.gridx[i] = pl.main.grid_x; b.sstride[i] = E;
+      b.b.begin[i + 1] = bp.end[oi];
+      b.b.n = i + 1;
+      if (b.b.n == X6W_BATCH && (rc = flush())) return rc;
+    }
+    if (pl.rest.rows > 0 &&
+        (rc = x6w_launch_rest<DET>(x6w_bind(qc, pl, pl.rest, q.dy, q.x, C + (DET ? (size_t)pl.main_slabs() * E : 0)), pl.rest.grid_x, q.nb, E, st)))
+      return rc;
+    if (DET) cur += (size_t)pl.slabs() * E;
+  }
+  if ((rc = flush())) return rc;
+  if constexpr (DET) {
+    X6WdetReducer red;
+    red.st = st;
+    cur = (float*)workspace;
+    for (int oi = 0; oi < n; ++oi) {
+      const GkgWgradProblem& q = p[bp.order[oi]];
+      const size_t E = (size_t)q.nb * q.cout * q.cin;
+      const int S = bp.pl[oi].slabs();
+      if ((rc = red.add(q.dw, cur, E, S))) return rc;
+      cur += (size_t)S * E;
+    }
+    return red.flush();
+  }
+  return 0;
+}
 }  // namespace gkg
+
+extern "C" int gkg_linear_wgrad_x6(const float* dy, int ldg, size_t g_bstride, const float* x, int ldx, size_t x_bstride,
+                                   float* dw, int R, int cin, int cout, int nb, int kperm, void* stream) {
+  if (!dy || !x || !dw) return gkg_fail(GKG_ERR_NULL, "gkg_linear_wgrad_x6: null pointer");
+  const X6WgradCall q = x6w_call(dy, ldg, g_bstride, x, ldx, x_bstride, R, cin, cout, nb, kperm, 0);
+  X6WgradPlan pl;
+  const char* msg = nullptr;
+  if (const int rc = x6_wgrad_plan(q, &pl, &msg)) return gkg_fail(rc, msg);
+  return x6w_run<false>(q, pl, dy, x, dw, 0, (hipStream_t)stream);
+}
+
+extern "C" int gkg_linear_wgrad_x6_batch(const GkgWgradProblem* p, int n, int units_per_slab, void* stream) {
+  return x6w_batch_run<false>(p, n, units_per_slab, nullptr, 0, (hipStream_t)stream);
+}
 
 extern "C" size_t gkg_linear_wgrad_x6_det_workspace_bytes(int R, int cin, int cout, int nb, int ldg, int ldx, int slabs) {
   if (slabs < 0 || slabs > 4096 || !x6_wdet_elems_ok(cin, cout, nb)) return 0;
-  int S = 0;
-  for (int al = 0; al < 2; ++al) {               // the larger of the aligned and the unaligned plan
-    X6WgradPlan pl;
-    if (x6_wgrad_plan(X6W_ANY, ldg, 0, X6W_ANY, ldx, 0, const_cast<float*>(X6W_ANY), R, cin, cout, nb, 0, pl, 0, slabs, al)) return 0;
-    const int s = x6_wdet_slabs(pl);
-    if (s > S) S = s;
-  }
+  int rc = 0;
+  const char* msg = nullptr;
+  const int S = x6_wdet_max_slabs(R, cin, cout, nb, ldg, ldx, slabs, &rc, &msg);
+  if (rc) gkg_fail(rc, msg);
   return ((size_t)S * nb * cout * cin * 4 + 15) & ~(size_t)15;
 }
 
@@ -1760,25 +1499,12 @@ extern "C" int gkg_linear_wgrad_x6_det_slabs(int R, int cin, int cout, int nb, i
   if (!x6_wdet_elems_ok(cin, cout, nb) && cin > 0 && cout > 0 && nb > 0)
     return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_wgrad_x6_det: more than 2^31 elements of dw");
   X6WgradPlan pl;
-  int rc = x6_wgrad_plan(X6W_ANY, ldg, 0, X6W_ANY, ldx, 0, const_cast<float*>(X6W_ANY), R, cin, cout, nb, units_per_slab, pl, 0,
-                         units_per_slab > 0 ? 0 : slabs, aligned ? 1 : 0);
-  if (rc) return rc;
-  int n = 0;
-  const X6WgradArgs& m = pl.main;
-  for (int s = 0; s < x6_wdet_main_slabs(pl); ++s, ++n)
-    if (n < cap) {
-      first_row[n] = 128 * (s * m.ubase + (s < m.urem ? s : m.urem));
-      rows[n] = 128 * (m.ubase + (s < m.urem ? 1 : 0));
-    }
-  if (pl.rest.K > 0) {
-    const int done = R - pl.rest.K;
-    for (int s = 0; s < pl.rest.splits; ++s, ++n)
-      if (n < cap) {
-        first_row[n] = done + s * pl.rest.rows_per_split;
-        rows[n] = pl.rest.K - s * pl.rest.rows_per_split < pl.rest.rows_per_split ? pl.rest.K - s * pl.rest.rows_per_split
-                                                                                  : pl.rest.rows_per_split;
-      }
-  }
+  const char* msg = nullptr;
+  if (const int rc = x6_wgrad_plan(X6WgradCall{R, cin, cout, nb, ldg, ldx, 0, 0, aligned != 0, units_per_slab, 0,
+                                               units_per_slab > 0 ? 0 : slabs}, &pl, &msg))
+    return gkg_fail(rc, msg);
+  const int n = pl.slabs();
+  for (int s = 0; s < n && s < cap; ++s) pl.slab_rows(s, first_row + s, rows + s);
   return n;
 }
 
@@ -1786,125 +1512,34 @@ extern "C" int gkg_linear_wgrad_x6_det(const float* dy, int ldg, size_t g_bstrid
                                        float* dw, int R, int cin, int cout, int nb, int kperm, int slabs, void* workspace,
                                        size_t workspace_bytes, void* stream) {
   if (slabs < 0 || slabs > 4096) return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_wgrad_x6_det: slabs out of range (0 .. 4096)");
+  if (!dy || !x || !dw) return gkg_fail(GKG_ERR_NULL, "gkg_linear_wgrad_x6: null pointer");
+  const X6WgradCall q = x6w_call(dy, ldg, g_bstride, x, ldx, x_bstride, R, cin, cout, nb, kperm, slabs);
   X6WgradPlan pl;
-  int rc = x6_wgrad_plan(dy, ldg, g_bstride, x, ldx, x_bstride, dw, R, cin, cout, nb, 0, pl, kperm, slabs);
-  if (rc) return rc;
+  const char* msg = nullptr;
+  int rc = x6_wgrad_plan(q, &pl, &msg);
+  if (rc) return gkg_fail(rc, msg);
   if (!x6_wdet_elems_ok(cin, cout, nb)) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_wgrad_x6_det: more than 2^31 elements of dw");
   const size_t need = gkg_linear_wgrad_x6_det_workspace_bytes(R, cin, cout, nb, ldg, ldx, slabs);
   if (!workspace || ((size_t)workspace & 15) || workspace_bytes < need || need == 0)
     return gkg_fail(GKG_ERR_WORKSPACE, "gkg_linear_wgrad_x6_det: workspace NULL, not 16-byte aligned or below gkg_linear_wgrad_x6_det_workspace_bytes()");
   hipStream_t st = (hipStream_t)stream;
-  float* ws = (float*)workspace;
   const size_t E = (size_t)nb * cout * cin;
-  const int Sm = x6_wdet_main_slabs(pl), S = x6_wdet_slabs(pl);
-  if (pl.main.K > 0) {
-    if ((rc = x6_wdet_set_attr(pl.wide ? 1 : 0))) return rc;
-    pl.main.C = ws;
-    const dim3 grid(pl.grid_x, nb);
-    if (pl.wide) hipLaunchKernelGGL(wgrad_x6_wide_det_kernel, grid, dim3(256), X6W_SH_WIDE, st, pl.main, E);
-    else hipLaunchKernelGGL(wgrad_x6_dma_det_kernel, grid, dim3(256), X6W_SH_DMA, st, pl.main, E);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return gkg_fail_hip(e, "wgrad_x6 deterministic DMA kernel");
-  }
-  if (pl.rest.K > 0) {
-    pl.rest.C = ws + (size_t)Sm * E;
-    hipLaunchKernelGGL(wgrad_x6_det_kernel, dim3(pl.rest_grid_x, nb), dim3(256), 0, st, pl.rest, E);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return gkg_fail_hip(e, "wgrad_x6_det_kernel");
-  }
+  if ((rc = x6w_run<true>(q, pl, dy, x, (float*)workspace, E, st))) return rc;
   X6WdetReducer red;
   red.st = st;
-  if ((rc = red.add(dw, ws, E, S))) return rc;
+  if ((rc = red.add(dw, (const float*)workspace, E, pl.slabs()))) return rc;
   return red.flush();
 }
 
-namespace gkg {
-// validation and plans of a deterministic batch, in launch order (largest problems first); `floats`: the workspace they need
-static int x6_wdet_batch_plan(const GkgWgradProblem* p, int n, int units_per_slab, int* order, std::vector<X6WgradPlan>& pls,
-                              size_t& floats) {
-  if (!p || n <= 0) return gkg_fail(GKG_ERR_NULL, "gkg_linear_wgrad_x6_batch_det: no problems");
-  if (units_per_slab < 0 || units_per_slab > 4096) return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_wgrad_x6_batch_det: units_per_slab out of range");
-  if (n > 256) return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_wgrad_x6_batch_det: at most 256 problems per call");
-  if (units_per_slab == 0) units_per_slab = 20;
-  for (int i = 0; i < n; ++i) order[i] = i;
-  auto work = [&](int i) { return (double)p[i].R * p[i].cin * p[i].cout * p[i].nb; };
-  for (int i = 1; i < n; ++i)                     // insertion sort, descending work
-    for (int j = i; j > 0 && work(order[j]) > work(order[j - 1]); --j) { const int t = order[j]; order[j] = order[j - 1]; order[j - 1] = t; }
-  pls.resize(n);
-  floats = 0;
-  for (int oi = 0; oi < n; ++oi) {
-    const GkgWgradProblem& q = p[order[oi]];
-    int rc = x6_wgrad_plan(q.dy, q.ldg, q.g_bstride, q.x, q.ldx, q.x_bstride, q.dw, q.R, q.cin, q.cout, q.nb, units_per_slab, pls[oi], q.kperm);
-    if (rc) return rc;
-    if (!x6_wdet_elems_ok(q.cin, q.cout, q.nb)) return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_wgrad_x6_batch_det: more than 2^31 elements of a dw");
-    floats += (size_t)x6_wdet_slabs(pls[oi]) * q.nb * q.cout * q.cin;
-  }
-  return 0;
-}
-}  // namespace gkg
-
 extern "C" size_t gkg_linear_wgrad_x6_batch_det_workspace_bytes(const GkgWgradProblem* p, int n, int units_per_slab) {
-  int order[256];
-  std::vector<X6WgradPlan> pls;
-  size_t floats = 0;
-  if (x6_wdet_batch_plan(p, n, units_per_slab, order, pls, floats)) return 0;
-  return (floats * 4 + 15) & ~(size_t)15;
+  X6WgradBatchPlan bp;
+  const char* msg = nullptr;
+  if (const int rc = x6_wgrad_batch_plan(p, n, units_per_slab, true, &bp, &msg)) { gkg_fail(rc, msg); return 0; }
+  return (bp.det_floats * 4 + 15) & ~(size_t)15;
 }
 
 extern "C" int gkg_linear_wgrad_x6_batch_det(const GkgWgradProblem* p, int n, int units_per_slab, void* workspace,
                                              size_t workspace_bytes, void* stream) {
-  int order[256];
-  std::vector<X6WgradPlan> pls;
-  size_t floats = 0;
-  int rc = x6_wdet_batch_plan(p, n, units_per_slab, order, pls, floats);
-  if (rc) return rc;
-  if (!workspace || ((size_t)workspace & 15) || workspace_bytes < ((floats * 4 + 15) & ~(size_t)15))
-    return gkg_fail(GKG_ERR_WORKSPACE, "gkg_linear_wgrad_x6_batch_det: workspace NULL, not 16-byte aligned or below gkg_linear_wgrad_x6_batch_det_workspace_bytes()");
-  hipStream_t st = (hipStream_t)stream;
-  X6WgradBatchDet b{};
-  int rot = 0;
-  auto flush = [&]() -> int {
-    if (b.b.n == 0) return 0;
-    int rc2 = x6_wdet_set_attr(2);
-    if (rc2) return rc2;
-    hipLaunchKernelGGL(wgrad_x6_batch_det_kernel, dim3(b.b.begin[b.b.n]), dim3(256), X6W_SH_WIDE, st, b);
-    hipError_t e = hipGetLastError();
-    b.b.n = 0;
-    return e == hipSuccess ? 0 : gkg_fail_hip(e, "wgrad_x6_batch_det_kernel");
-  };
-  float* cur = (float*)workspace;
-  for (int oi = 0; oi < n; ++oi) {                // every problem's slab images: one launch per 16 problems + the ragged remainders
-    const GkgWgradProblem& q = p[order[oi]];
-    X6WgradPlan& pl = pls[oi];
-    const size_t E = (size_t)q.nb * q.cout * q.cin;
-    if (pl.main.K > 0) {
-      const int i = b.b.n;
-      pl.main.rot = rot;
-      rot = (rot + (pl.main.share > 1 ? 0 : pl.main.splits)) & 7;
-      pl.main.C = cur;
-      b.b.p[i] = pl.main; b.b.wide[i] = pl.wide ? 1 : 0; b.b.gridx[i] = pl.grid_x; b.sstride[i] = E;
-      b.b.begin[i + 1] = b.b.begin[i] + pl.grid_x * q.nb;
-      b.b.n = i + 1;
-      if (b.b.n == X6W_BATCH && (rc = flush())) return rc;
-    }
-    if (pl.rest.K > 0) {
-      pl.rest.C = cur + (size_t)x6_wdet_main_slabs(pl) * E;
-      hipLaunchKernelGGL(wgrad_x6_det_kernel, dim3(pl.rest_grid_x, q.nb), dim3(256), 0, st, pl.rest, E);
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return gkg_fail_hip(e, "wgrad_x6_det_kernel");
-    }
-    cur += (size_t)x6_wdet_slabs(pl) * E;
-  }
-  if ((rc = flush())) return rc;
-  X6WdetReducer red;                              // then every dw, in slab order
-  red.st = st;
-  cur = (float*)workspace;
-  for (int oi = 0; oi < n; ++oi) {
-    const GkgWgradProblem& q = p[order[oi]];
-    const size_t E = (size_t)q.nb * q.cout * q.cin;
-    const int S = x6_wdet_slabs(pls[oi]);
-    if ((rc = red.add(q.dw, cur, E, S))) return rc;
-    cur += (size_t)S * E;
-  }
-  return red.flush();
+  return x6w_batch_run<true>(p, n, units_per_slab, workspace, workspace_bytes, (hipStream_t)stream);
 }
+

@@ -226,8 +226,11 @@ def _wgrad_defer(dY, x, out, R, cin, cout, nb, ldg, g_bs, ldx, x_bs, kperm=0) ->
             and R % 128 == 0 and cin % 4 == 0 and cout % 4 == 0 and ldg % 4 == 0 and ldx % 4 == 0 and g_bs % 4 == 0 and x_bs % 4 == 0
             and dY.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0 and R * max(ldg, ldx) * 4 < 0xffffffff and nb <= 64):
         return False
-    # a problem that fills the chip on its own (GKGNet-576's stage-1 / stage-2 layers: thousands of 128-row units) keeps its
-    # stand-alone slabs inside a batch anyway (csrc x6_wgrad_plan): launching it from the node costs nothing and frees its operands
+    # a problem that fills the chip on its own (GKGNet-576's stage-1 / stage-2 layers: thousands of 128-row units) is launched from
+    # the node: that costs nothing and frees its operands.  This is a SEPARATE, coarser rule than the library's: inside a batch the
+    # library keeps a problem's stand-alone slabs when tiles * stand-alone slab count >= 512 (csrc/gkg_x6_plan.h x6_wgrad_fills_chip,
+    # over the tile shape x6_wgrad_plan picks); the test below only decides which problems are queued at all, and the two are not
+    # the same predicate.
     tiles = nb * ((cout + 63) // 64) * ((cin + 63) // 64)
     if tiles * min(R // 128, 64) >= 2048 and R >= 32768:
         return False
