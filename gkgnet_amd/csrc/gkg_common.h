@@ -23,6 +23,15 @@ __device__ __forceinline__ void stf(uint16_t* p, float v) {
 __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
   return (uint32_t)__builtin_bit_cast(uint16_t, (__bf16)lo) | ((uint32_t)__builtin_bit_cast(uint16_t, (__bf16)hi) << 16);
 }
+// Two floats as IEEE fp16 (lo in the low half): round-to-nearest-even, overflow to +-inf, NaN stays NaN, SUBNORMAL results kept (one
+// v_cvt_pk_f16_f32 in the default rounding / denormal modes).  Training operands under a loss scale: small gradients must survive
+// (the k-NN's pack_f16x2_flush, gkg_knn_prep.h, zeroes them on purpose — not that one).
+typedef float gkg_f32x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 gkg_f16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t pack_f16x2(float lo, float hi) {
+  const gkg_f32x2 v = {lo, hi};
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, gkg_f16x2));
+}
 __device__ __forceinline__ void stf4(float* p, const float4& v) { *reinterpret_cast<float4*>(p) = v; }
 __device__ __forceinline__ void stf4(uint16_t* p, const float4& v) {
   *reinterpret_cast<uint2*>(p) = make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));

@@ -54,8 +54,16 @@
 // bit: an output element's contraction runs in the same order in both), look-ahead unchanged.
 //   linear_bf16_kernel<2, false, true>   186 VGPRs, 0 AGPRs, 62 SGPRs   LDS 53 248 B (dynamic), no scratch   2 waves / SIMD by registers
 // The other four instantiations keep their figures (234 / 66, 152 / 62, 237 / 106, 155 / 106).
+//
+// E = LbElem::F16 (gkg_linear_f16_f32a: training under fp16 autocast, GKG_ENABLE=train_f16): the fp32-A 64-column form with IEEE fp16
+// in the places where the element kind shows — the stash packs with pack_f16x2 (round to nearest even, overflow to inf, subnormals
+// kept), the fragments are _Float16 x 8 for v_mfma_f32_32x32x16_f16 (the bf16 instruction's rate and lane maps), the 16-bit output
+// is fp16.  Fragment layout, LDS pitches, look-ahead, barriers, zero-fill, tile map, epilogue and refusals are the shared code.
+//   linear_bf16_kernel<2, false, true, LbElem::F16>   184 VGPRs, 0 AGPRs, 62 SGPRs   LDS 53 248 B (dynamic), no scratch   2 waves / SIMD
+// The five bf16 instantiations keep their figures with the parameter (234 / 66, 152 / 62, 237 / 106, 155 / 106, 186 / 62).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include <type_traits>
 
@@ -66,6 +74,7 @@ namespace gkg {
 
 typedef float lb_f32x16 __attribute__((ext_vector_type(16)));
 typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 lb_bf16x8;
+typedef __attribute__((__vector_size__(8 * sizeof(_Float16)))) _Float16 lb_f16x8;
 
 constexpr int LB_BM = 128;                       // rows per workgroup: 4 waves x 32
 constexpr int LB_KC = 64;                        // contraction elements per LDS stage (4 MFMA steps of 16)
@@ -130,9 +139,26 @@ __device__ __forceinline__ void lb_prep_rows(const LinBf16PrepArgs& g, float* co
   }
 }
 
-template <int NB, bool PREP = false, bool F32A = false>
+// The 16-bit element kind of the operands in LDS, of the weight fragments and of the 16-bit output: one packing helper, one
+// fragment type, one MFMA per kind; everything else of the kernel is shared.
+enum class LbElem { BF16, F16 };
+template <LbElem E>
+__device__ __forceinline__ uint32_t lb_pack2(float lo, float hi) {
+  if constexpr (E == LbElem::F16) return pack_f16x2(lo, hi);
+  else return pack_bf16x2(lo, hi);
+}
+template <LbElem E>
+__device__ __forceinline__ lb_f32x16 lb_mfma(const uint4& a, const uint4& b, lb_f32x16 c) {
+  if constexpr (E == LbElem::F16)
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(lb_f16x8, a), __builtin_bit_cast(lb_f16x8, b), c, 0, 0, 0);
+  else
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(lb_bf16x8, a), __builtin_bit_cast(lb_bf16x8, b), c, 0, 0, 0);
+}
+
+template <int NB, bool PREP = false, bool F32A = false, LbElem E = LbElem::BF16>
 __global__ __launch_bounds__(LB_NT, 2) void linear_bf16_kernel(std::conditional_t<PREP, LinBf16PrepArgs, LinBf16Args> g) {
   static_assert(!(PREP && F32A), "the fp32-A form has no token preparation");
+  static_assert(E == LbElem::BF16 || (F32A && NB == 2), "fp16 operands: the fp32-A 64-column form only");
   extern __shared__ __align__(16) unsigned char lb_lds[];
   constexpr int BN = 32 * NB;
   constexpr int BBYTES = (LB_KC / 8) * BN * 16;
@@ -189,9 +215,9 @@ __global__ __launch_bounds__(LB_NT, 2) void linear_bf16_kernel(std::conditional_
     for (int i = 0; i < NA; ++i) {
       const int gi = tid + LB_NT * i;
       uint4 v;
-      if constexpr (F32A) {                                // round to nearest even here: the LDS image is the bf16 kernel's
+      if constexpr (F32A) {                                // round to nearest even here: the LDS image is the 16-bit kernel's
         const float4 f0 = __builtin_bit_cast(float4, qa[2 * i]), f1 = __builtin_bit_cast(float4, qa[2 * i + 1]);
-        v = make_uint4(pack_bf16x2(f0.x, f0.y), pack_bf16x2(f0.z, f0.w), pack_bf16x2(f1.x, f1.y), pack_bf16x2(f1.z, f1.w));
+        v = make_uint4(lb_pack2<E>(f0.x, f0.y), lb_pack2<E>(f0.z, f0.w), lb_pack2<E>(f1.x, f1.y), lb_pack2<E>(f1.z, f1.w));
       } else {
         v = qa[i];
       }
@@ -216,12 +242,12 @@ __global__ __launch_bounds__(LB_NT, 2) void linear_bf16_kernel(std::conditional_
     const unsigned char* bp = bbuf + buf * BBYTES + (kg * BN + l31) * 16;
     const int steps = min(LB_KC / 16, S - c * (LB_KC / 16));
     auto step = [&](int s, bool all) __attribute__((always_inline)) {
-      const lb_bf16x8 av = __builtin_bit_cast(lb_bf16x8, *reinterpret_cast<const uint4*>(ap + 32 * s));
+      const uint4 av = *reinterpret_cast<const uint4*>(ap + 32 * s);
 #pragma unroll
       for (int u = 0; u < NB; ++u)
         if (all || has[u]) {
-          const lb_bf16x8 bv = __builtin_bit_cast(lb_bf16x8, *reinterpret_cast<const uint4*>(bp + (2 * s * BN + 32 * u) * 16));
-          acc[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc[u], 0, 0, 0);
+          const uint4 bv = *reinterpret_cast<const uint4*>(bp + (2 * s * BN + 32 * u) * 16);
+          acc[u] = lb_mfma<E>(av, bv, acc[u]);
         }
     };
     if (steps == LB_KC / 16 && has[NB - 1]) {
@@ -305,7 +331,7 @@ __global__ __launch_bounds__(LB_NT, 2) void linear_bf16_kernel(std::conditional_
       }
       if (g.o16)
         *reinterpret_cast<uint4*>(g.o16 + (size_t)row * g.ldo16 + col) =
-            make_uint4(pack_bf16x2(z0.x, z0.y), pack_bf16x2(z0.z, z0.w), pack_bf16x2(z1.x, z1.y), pack_bf16x2(z1.z, z1.w));
+            make_uint4(lb_pack2<E>(z0.x, z0.y), lb_pack2<E>(z0.z, z0.w), lb_pack2<E>(z1.x, z1.y), lb_pack2<E>(z1.z, z1.w));
     }
   }
   if constexpr (PREP) {
@@ -351,15 +377,15 @@ __global__ __launch_bounds__(LB_NT, 2) void linear_bf16_kernel(std::conditional_
   }
 }
 
-template <int NB, bool PREP = false, bool F32A = false, typename Args>
+template <int NB, bool PREP = false, bool F32A = false, LbElem E = LbElem::BF16, typename Args>
 static hipError_t lb_launch(const Args& g, hipStream_t st) {
   constexpr size_t lds = lb_lds_bytes(NB);
   if (lds > 64 * 1024) {
-    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_bf16_kernel<NB, PREP, F32A>),
+    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_bf16_kernel<NB, PREP, F32A, E>),
                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (ea != hipSuccess) return ea;
   }
-  hipLaunchKernelGGL((linear_bf16_kernel<NB, PREP, F32A>), dim3((unsigned)(g.tiles_per_xcd * 8)), dim3(LB_NT), lds, st, g);
+  hipLaunchKernelGGL((linear_bf16_kernel<NB, PREP, F32A, E>), dim3((unsigned)(g.tiles_per_xcd * 8)), dim3(LB_NT), lds, st, g);
   return hipGetLastError();
 }
 
@@ -439,24 +465,49 @@ extern "C" int gkg_linear_bf16_f32a_supported(int R, int cin, int cout, int has_
   return lb_tiles(R, lb_co_pad(cout), 2, &ct) <= 0x3fffffffLL ? 1 : 0;              // the 64-column form at every shape
 }
 
+// One body for the two element kinds: `fn` names the entry point in the messages
+template <LbElem E>
+static int lb_f32a_call(const char* fn, const float* x, int ldx, const void* wplanes, const float* a, const float* cshift, const float* res,
+                        int ldr, float* out_f32, int ldo32, void* out16, int ldo16, int R, int cin, int cout, int act, void* stream) {
+  char msg[160];
+  auto fail = [&](int code, const char* what) { snprintf(msg, sizeof msg, "%s: %s", fn, what); return gkg_fail(code, msg); };
+  if (!x || !wplanes || (!out_f32 && !out16)) return fail(GKG_ERR_NULL, "null pointer");
+  if (R < 1 || cin <= 0 || cout <= 0 || act < 0 || act > 1)
+    return fail(GKG_ERR_SHAPE, "bad sizes (need R >= 1, cin, cout > 0, act in 0..1)");
+  if (!gkg_linear_bf16_f32a_supported(R, cin, cout, res != nullptr, out_f32 != nullptr, out16 != nullptr, act))
+    return fail(GKG_ERR_UNSUPPORTED, "need cin % 8 == 0, cout % 8 == 0 and a grid that fits");
+  if ((ldx & 3) || (out16 && (ldo16 & 7)) || (out_f32 && (ldo32 & 3)) || (res && (ldr & 3)))
+    return fail(GKG_ERR_UNSUPPORTED, "need ldx % 4 == 0, ldo16 % 8 == 0, ldo32 % 4 == 0, ldr % 4 == 0");
+  if (((uintptr_t)x | (uintptr_t)wplanes | (uintptr_t)res | (uintptr_t)out_f32 | (uintptr_t)out16) & 15)
+    return fail(GKG_ERR_UNSUPPORTED, "x, wplanes, res and the outputs must be 16-byte aligned");
+  if (ldx < cin || (out16 && ldo16 < cout) || (out_f32 && ldo32 < cout) || (res && ldr < cout))
+    return fail(GKG_ERR_SHAPE, "a row pitch is below the row's width");
+  LinBf16Args g;
+  lb_fill(g, x, ldx, wplanes, a, cshift, res, ldr, out_f32, ldo32, out16, ldo16, R, cin, cout, act, 2);
+  const hipError_t e = lb_launch<2, false, true, E>(g, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : gkg_fail_hip(e, E == LbElem::F16 ? "linear_bf16_kernel (fp32 A, fp16 operands)" : "linear_bf16_kernel (fp32 A)");
+}
+
 extern "C" int gkg_linear_bf16_f32a(const float* x, int ldx, const void* wplanes, const float* a, const float* cshift, const float* res,
                                     int ldr, float* out_f32, int ldo32, void* out_bf16, int ldo16, int R, int cin, int cout, int act,
                                     void* stream) {
-  if (!x || !wplanes || (!out_f32 && !out_bf16)) return gkg_fail(GKG_ERR_NULL, "gkg_linear_bf16_f32a: null pointer");
-  if (R < 1 || cin <= 0 || cout <= 0 || act < 0 || act > 1)
-    return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_bf16_f32a: bad sizes (need R >= 1, cin, cout > 0, act in 0..1)");
-  if (!gkg_linear_bf16_f32a_supported(R, cin, cout, res != nullptr, out_f32 != nullptr, out_bf16 != nullptr, act))
-    return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_bf16_f32a: need cin % 8 == 0, cout % 8 == 0 and a grid that fits");
-  if ((ldx & 3) || (out_bf16 && (ldo16 & 7)) || (out_f32 && (ldo32 & 3)) || (res && (ldr & 3)))
-    return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_bf16_f32a: need ldx % 4 == 0, ldo16 % 8 == 0, ldo32 % 4 == 0, ldr % 4 == 0");
-  if (((uintptr_t)x | (uintptr_t)wplanes | (uintptr_t)res | (uintptr_t)out_f32 | (uintptr_t)out_bf16) & 15)
-    return gkg_fail(GKG_ERR_UNSUPPORTED, "gkg_linear_bf16_f32a: x, wplanes, res and the outputs must be 16-byte aligned");
-  if (ldx < cin || (out_bf16 && ldo16 < cout) || (out_f32 && ldo32 < cout) || (res && ldr < cout))
-    return gkg_fail(GKG_ERR_SHAPE, "gkg_linear_bf16_f32a: a row pitch is below the row's width");
-  LinBf16Args g;
-  lb_fill(g, x, ldx, wplanes, a, cshift, res, ldr, out_f32, ldo32, out_bf16, ldo16, R, cin, cout, act, 2);
-  const hipError_t e = lb_launch<2, false, true>(g, (hipStream_t)stream);
-  return e == hipSuccess ? 0 : gkg_fail_hip(e, "linear_bf16_kernel (fp32 A)");
+  return lb_f32a_call<LbElem::BF16>("gkg_linear_bf16_f32a", x, ldx, wplanes, a, cshift, res, ldr, out_f32, ldo32, out_bf16, ldo16, R, cin,
+                                    cout, act, stream);
+}
+
+// ---------------------------------------------------------------------------------------------- fp32 A operand, fp16 operands (training)
+// The fragment array's paddings, the tile form and the size limits are the element kind's business nowhere: the bf16 answers.
+extern "C" size_t gkg_linear_f16_planes_bytes(int cin, int cout) { return gkg_linear_bf16_planes_bytes(cin, cout); }
+
+extern "C" int gkg_linear_f16_f32a_supported(int R, int cin, int cout, int has_res, int want_f32, int want_f16, int act) {
+  return gkg_linear_bf16_f32a_supported(R, cin, cout, has_res, want_f32, want_f16, act);
+}
+
+extern "C" int gkg_linear_f16_f32a(const float* x, int ldx, const void* wplanes_f16, const float* a, const float* cshift, const float* res,
+                                   int ldr, float* out_f32, int ldo32, void* out_f16, int ldo16, int R, int cin, int cout, int act,
+                                   void* stream) {
+  return lb_f32a_call<LbElem::F16>("gkg_linear_f16_f32a", x, ldx, wplanes_f16, a, cshift, res, ldr, out_f32, ldo32, out_f16, ldo16, R, cin,
+                                   cout, act, stream);
 }
 
 // ---------------------------------------------------------------------------------------------- fc1 + the k-NN's token preparation

@@ -13,6 +13,7 @@ from . import _lib
 from .planes import param_version
 
 _BF16 = torch.bfloat16
+_F16 = torch.float16
 _STORE = weakref.WeakKeyDictionary()            # owner module -> {slot: ([(weak reference, address, token) per source], (extra, epoch), value)}
 
 
@@ -71,12 +72,20 @@ def bf16_fragments(w, k_pad, n_pad) -> torch.Tensor:
     return W.view(w.shape[:-2] + (n_pad, k_pad // 8, 8)).transpose(-3, -2).contiguous()
 
 
-def _fragments_slot(conv, slot, mat, nbytes):
+def f16_fragments(w, k_pad, n_pad) -> torch.Tensor:
+    """bf16_fragments' layout in IEEE fp16: the weight rounded by ``.to(torch.float16)``, autocast's own cast."""
+    n, k = w.shape[-2:]
+    W = torch.zeros(w.shape[:-2] + (n_pad, k_pad), dtype=_F16, device=w.device)
+    W[..., :n, :k] = w.detach().to(_F16)
+    return W.view(w.shape[:-2] + (n_pad, k_pad // 8, 8)).transpose(-3, -2).contiguous()
+
+
+def _fragments_slot(conv, slot, mat, nbytes, fragments=bf16_fragments):
     """``mat(w)`` -> the matrix (or stack) to lay out, ``nbytes(lib, n, k)`` -> the library's size of that array."""
     def build():
         m = mat(conv.weight.detach())
         n, k = m.shape[-2:]
-        planes = bf16_fragments(m, _up(k, K_ALIGN), _up(n, N_ALIGN))
+        planes = fragments(m, _up(k, K_ALIGN), _up(n, N_ALIGN))
         assert planes.numel() * 2 == int(nbytes(_lib.load(), n, k)), (slot, tuple(m.shape))      # the library owns the paddings
         return planes
     return get(conv, slot, (conv.weight,), build)
@@ -93,6 +102,18 @@ def lin_planes_t(conv) -> torch.Tensor:
     cout and output columns cin): [co_pad'/8][ci_pad'][8], fragment (f, n) = w[8f .. 8f+7][n]."""
     return _fragments_slot(conv, "lin_planes_t", lambda w: w.reshape(w.shape[0], -1).t(),
                            lambda lib, ci, co: lib.gkg_linear_bf16_planes_bytes(co, ci))
+
+
+def lin_planes_f16(conv) -> torch.Tensor:
+    """lin_planes in fp16, what gkg_linear_f16_f32a streams for the forward (GKG_ENABLE=train_f16)."""
+    return _fragments_slot(conv, "lin_planes_f16", lambda w: w.reshape(w.shape[0], -1),
+                           lambda lib, co, ci: lib.gkg_linear_f16_planes_bytes(ci, co), f16_fragments)
+
+
+def lin_planes_t_f16(conv) -> torch.Tensor:
+    """lin_planes_t in fp16, what gkg_linear_f16_f32a streams for the input gradient."""
+    return _fragments_slot(conv, "lin_planes_t_f16", lambda w: w.reshape(w.shape[0], -1).t(),
+                           lambda lib, ci, co: lib.gkg_linear_f16_planes_bytes(co, ci), f16_fragments)
 
 
 def mr_planes(conv) -> torch.Tensor:

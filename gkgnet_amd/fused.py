@@ -97,7 +97,15 @@ DETERMINISTIC = os.environ.get("GKG_DETERMINISTIC", "0") != "0"
 #                  and the six-product x6 weight gradient.  bf16 autocast with gradients only; not under GKG_DETERMINISTIC (the
 #                  weight gradient adds its row slabs atomically); the grouped projection, fp16 autocast and the BN passes keep
 #                  their paths.  Opt-in: per-layer measurements in EXPERIMENTS.md.
-#   wgrad_det      with GKG_DETERMINISTIC=1 and GKG_GEMM_MATH=x6 only: the projections' weight gradients stay on the library's x6
+#   train_f16      training under fp16 autocast (the reference's recipe: fp16 AMP with a dynamic loss scale): the forward Y = x W^T and
+#                  the input gradient dx = dY W (+ the skip gradient) of the same layers run on the fp16 form of the own kernel —
+#                  IEEE fp16 operands rounded from the fp32 tensors on their way into LDS (subnormals kept), fp32 accumulation
+#                  (gkg_linear_f16_f32a; linear_bf16.py) — instead of the autocast vendor GEMM with its casts and the fp32 vendor
+#                  GEMM.  The weight gradient stays where it is (_wgrad), so the switch adds nothing atomically and also holds
+#                  under GKG_DETERMINISTIC.  fp16 autocast with gradients only; bf16 autocast, fp32, fp16 inference, the grouped
+#                  projection and the BN passes keep their paths.  May be on together with train_bf16: each acts under its own
+#                  autocast dtype.  Opt-in: per-layer measurements in EXPERIMENTS.md.
+#   wgrad_det     with GKG_DETERMINISTIC=1 and GKG_GEMM_MATH=x6 only: the projections' weight gradients stay on the library's x6
 #                  kernels in their run-independent form (gkg_linear_wgrad_x6_det / _batch_det: the row slabs' partial tiles go to
 #                  a workspace and are added in slab order; no atomics, no cleared slot) instead of the vendor batched GEMM + sum —
 #                  the XM operand view with its column permutation included, and batched into one launch per backward pass like
@@ -128,6 +136,7 @@ FFN_BF16 = "ffn_bf16" in _ENABLED          # likewise; acts only together with L
 # likewise (False | True: the measured shapes | "all": every supported shape); acts only together with LIN_BF16 and MR_GEMM
 MR_FC2_BF16 = "all" if "mr_fc2_bf16_all" in _ENABLED else ("mr_fc2_bf16" in _ENABLED)
 TRAIN_BF16 = "train_bf16" in _ENABLED      # likewise a module constant the tests flip
+TRAIN_F16 = "train_f16" in _ENABLED        # likewise
 WGRAD_DET = "wgrad_det" in _ENABLED        # likewise; acts only together with DETERMINISTIC and GEMM_MATH == "x6"
 
 
@@ -450,6 +459,7 @@ from .linear_bf16 import ffn_bf16_ok, ffn_bf16_eval      # noqa: E402,F401  (GKG
 from .linear_bf16 import mr_fc2_bf16_ok, mr_fc2_bf16_eval      # noqa: E402,F401  (GKG_ENABLE=lin_bf16,mr_fc2_bf16)
 from .linear_bf16 import (train_bf16_ok, linear_bf16_train_fwd,      # noqa: E402,F401  (GKG_ENABLE=train_bf16)
                           linear_bf16_dgrad, linear_bf16_wgrad)
+from .linear_bf16 import train_f16_ok, linear_f16_train_fwd, linear_f16_dgrad      # noqa: E402,F401  (GKG_ENABLE=train_f16)
 from .layout import _tm_dtype, _TokenMajorToCL, _ToTokenMajor, _BlockEntry, _AvgPoolTM      # noqa: E402  (layout Functions: layout.py)
 
 
@@ -681,10 +691,11 @@ class _LinearBNAct(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, gamma, beta, residual, bn, act, nchw, out_lowp=False, w16=None, scale=None,
-                rows_per_scale=0, want16=False, alias=False, dual=False, xm=None, knn=None, conv=None):
-        """``conv``: the projection's module (travels like ``w16``), handed over by ``_lin`` only where GKG_ENABLE=train_bf16 takes
-        the layer (train_bf16_ok, asked there: in here gradients are switched off): its two cached fragment arrays are what the
-        own bf16 products of this node's forward and backward stream.
+                rows_per_scale=0, want16=False, alias=False, dual=False, xm=None, knn=None, t16=None):
+        """``t16`` = (kind, conv) — "bf16" | "f16" and the projection's module (travels like ``w16``) —, handed over by ``_lin`` only
+        where GKG_ENABLE=train_bf16 / train_f16 takes the layer (_train_16bit, asked there: in here gradients are switched off and
+        the backward runs outside autocast): the module's cached fragment arrays of that kind are what the own 16-bit products of
+        this node's forward and backward stream.
         ``alias``: also return ``x`` itself as a second output (a view).  A caller that uses the layer's input again
         as the residual of a later layer takes the alias for that: both gradient contributions then arrive at THIS node
         and the input-gradient GEMM adds the residual one in its epilogue (``addmm``), instead of autograd summing two
@@ -705,7 +716,7 @@ class _LinearBNAct(torch.autograd.Function):
         group = _sync_group(bn)
         x6f, x6d = _x6(x, weight, bn, 1, "fwd", group), _x6(x, weight, bn, 1, "dgrad", group)
         own = x6f
-        tb16 = None
+        taken = None
         pf, pd = _planes(lib, weight, 1, cout, cin, x6f, x6d) if x6f or x6d else (None, None)
         pf, pd = (pf if x6f else None), (pd if x6d else None)
         res = None if residual is None else residual.contiguous()
@@ -742,10 +753,15 @@ class _LinearBNAct(torch.autograd.Function):
         elif own:                                     # projection kernel with the BN statistics in its epilogue
             Y, a, c, mean, invstd = _linear_fwd_own(lib, x, pf, (R, cin, cout, 1), bias, bn)
         else:
-            # bf16 autocast with gradients, opt-in: the product on the own bf16 kernel (fp32 A operand rounded on its way into LDS).
-            # The backward runs outside autocast: the decision is recorded here
-            tb16 = conv
-            Y = linear_bf16_train_fwd(x, conv) if tb16 is not None else _mm_t(x, weight.view(cout, cin), w16)
+            # bf16 / fp16 autocast with gradients, opt-in: the product on the own kernel of that kind (fp32 A operand rounded on its
+            # way into LDS).  The backward runs outside autocast: the decision is recorded here
+            taken = t16
+            if taken is None:
+                Y = _mm_t(x, weight.view(cout, cin), w16)
+            elif taken[0] == "f16":
+                Y = linear_f16_train_fwd(x, taken[1])
+            else:
+                Y = linear_bf16_train_fwd(x, taken[1])
             a, c, mean, invstd, sync = bn_passes.forward_params(lib, Y, bn, bias, R, cout, 1, group)
         if not fused_apply and not (own and mean is None and code == _lib.F32 and not want16):
             prep = None      # besides the train-mode pass only a frozen layer's affine behind the x6 projection, fp32 out, prepares
@@ -778,7 +794,7 @@ class _LinearBNAct(torch.autograd.Function):
         ctx.scale = (scale, rows_per_scale)
         ctx.gparams = (weight, gamma, beta)
         ctx.pd = pd
-        ctx.tb16 = tb16
+        ctx.t16 = taken
         ctx.prev = prev if (prev is not None and pd is not None and prev.nb * prev.co == cin and prev.R == R) else None
         ctx.link = _bn_link(out, state, ctx.bn, scale) if (nchw is None and xm is None) else None
         if xm is not None:
@@ -880,9 +896,9 @@ class _LinearBNAct(torch.autograd.Function):
             _dgrad_x6(lib, dY, cout, R * cout, ctx.pd, dx, R, cin, cout, 1, res)
             if res is not None:
                 dalias = None
-        elif ctx.tb16 is not None:                         # GKG_ENABLE=train_bf16: the own bf16 product, the skip gradient in its epilogue
+        elif ctx.t16 is not None:                          # GKG_ENABLE=train_bf16 / train_f16: the own product, the skip gradient in its epilogue
             res = dalias if (dalias is not None and dalias.dtype == _F32 and dalias.shape == (R, cin)) else None
-            dx = linear_bf16_dgrad(dY, ctx.tb16, residual=res)
+            dx = (linear_f16_dgrad if ctx.t16[0] == "f16" else linear_bf16_dgrad)(dY, ctx.t16[1], residual=res)
             if res is not None:
                 dalias = None
         elif dalias is not None and dalias.dtype == dY.dtype:
@@ -894,10 +910,10 @@ class _LinearBNAct(torch.autograd.Function):
             dx = dx + dalias
         elif dalias is not None:
             dx = dalias
-        if ctx.tb16 is not None:
+        if ctx.t16 is not None and ctx.t16[0] == "bf16":
             # launched from the node: the deferred weight-gradient queue's problem records are x6 problems
             dW = linear_bf16_wgrad(dY, x, dWv).view_as(weight)
-        else:
+        else:                                              # (train_f16 has no weight-gradient kernel of its own: the path of the switch-off run)
             dW = _wgrad(dY, x, dWv).view_as(weight)
         return dx, dW, dbias, dgamma, dbeta, dres, None, None, None, None, None, None, None, None, None, None, None, None, None
 
@@ -1466,10 +1482,16 @@ def fused_supported(mod, x, groups: int) -> bool:
     return ENABLED
 
 
-def _train_bf16_conv(x, conv, bn):
-    """The module _LinearBNAct takes its own bf16 products' fragment arrays from, or None: GKG_ENABLE=train_bf16 and the layer is
-    in its scope (linear_bf16.train_bf16_ok — asked here, where the caller's gradient mode is still visible)."""
-    return conv if train_bf16_ok(TRAIN_BF16, x, conv, bn) else None
+def _train_16bit(x, conv, bn):
+    """Which own 16-bit products _LinearBNAct takes for this layer, as (kind, conv) — "bf16": GKG_ENABLE=train_bf16 under bf16
+    autocast (linear_bf16.train_bf16_ok), "f16": GKG_ENABLE=train_f16 under fp16 autocast (linear_bf16.train_f16_ok) — with the module
+    its fragment arrays are cached on, or None.  Asked here, where the caller's gradient mode and autocast state are still
+    visible.  The two predicates exclude each other by the autocast dtype, so both switches may be on."""
+    if train_bf16_ok(TRAIN_BF16, x, conv, bn):
+        return "bf16", conv
+    if train_f16_ok(TRAIN_F16, x, conv, bn):
+        return "f16", conv
+    return None
 
 
 def _lin(x, seq, act=0, residual=None, nchw=None, out_lowp=False, scale=None, rows_per_scale=0, want16=False, alias=False,
@@ -1485,7 +1507,7 @@ def _lin(x, seq, act=0, residual=None, nchw=None, out_lowp=False, scale=None, ro
         conv, bn = seq[0], seq[1]
         w16 = derived.w16(conv) if x.dtype == torch.bfloat16 else None
         return _LinearBNAct.apply(x, conv.weight, conv.bias, bn.weight, bn.bias, residual, bn, act, nchw, out_lowp, w16, scale,
-                                  rows_per_scale, want16, True, False, xm, knn, _train_bf16_conv(x, conv, bn))
+                                  rows_per_scale, want16, True, False, xm, knn, _train_16bit(x, conv, bn))
     conv, bn = seq[0], seq[1]
     if knn is not None and lowp_inference():
         # only grapher_forward's bf16-inference branch hands a problem over here (both switches on): fc1 + the k-NN's token
@@ -1517,7 +1539,7 @@ def _lin(x, seq, act=0, residual=None, nchw=None, out_lowp=False, scale=None, ro
         return torch.addmm(cf32, x, wf.t(), out_dtype=_F32)
     w16 = derived.w16(conv) if x.dtype == torch.bfloat16 else None
     return _LinearBNAct.apply(x, conv.weight, conv.bias, bn.weight, bn.bias, residual, bn, act, nchw, out_lowp, w16, scale,
-                              rows_per_scale, want16, False, dual, xm, knn, _train_bf16_conv(x, conv, bn))
+                              rows_per_scale, want16, False, dual, xm, knn, _train_16bit(x, conv, bn))
 
 
 # ---- a block output in both layouts (round 5) ---------------------------------------------------------------------------

@@ -3,8 +3,9 @@
 it dispatches here — and the same launch with the k-NN's token preparation riding on it (gkg_linear_bf16_knn_prep: a Grapher's
 fc1) — and an FFN's two projections as one launch with the hidden matrix kept on chip (gkg_ffn_bf16, csrc/gkg_ffn_bf16.hip) — and a Grapher's aggregation, grouped projection and fc2 as one launch
 (gkg_mr_fc2_bf16, csrc/gkg_mr_fc2_bf16.hip).  Also the training side (GKG_ENABLE=train_bf16): the same kernel reading an fp32 A operand for a layer's forward and input
-gradient (gkg_linear_bf16_f32a), the bf16 weight-gradient kernel (gkg_linear_wgrad_bf16) and their predicate.  Mechanism only: the
-switches (``fused.LIN_BF16``, ``fused.LIN_BF16_PREP``, ``fused.FFN_BF16``, ``fused.MR_FC2_BF16``, ``fused.TRAIN_BF16``) and the mode test (``fused.lowp_inference``) stay in
+gradient (gkg_linear_bf16_f32a), the bf16 weight-gradient kernel (gkg_linear_wgrad_bf16) and their predicate; and under fp16 autocast
+(GKG_ENABLE=train_f16) the forward and input gradient on the fp16 form of that kernel (gkg_linear_f16_f32a).  Mechanism only: the
+switches (``fused.LIN_BF16``, ``fused.LIN_BF16_PREP``, ``fused.FFN_BF16``, ``fused.MR_FC2_BF16``, ``fused.TRAIN_BF16``, ``fused.TRAIN_F16``) and the mode test (``fused.lowp_inference``) stay in
 ``fused.py`` and arrive as arguments."""
 from __future__ import annotations
 
@@ -369,3 +370,63 @@ def linear_bf16_wgrad(dY, x, out=None):
     _lib.check(_lib.load().gkg_linear_wgrad_bf16(_ptr(dY), dY.stride(0), _ptr(x), x.stride(0), _ptr(out), R, cin, cout, _stream()),
                "gkg_linear_wgrad_bf16")
     return out
+
+
+# ---- training under fp16 autocast (GKG_ENABLE=train_f16): the forward and the input gradient on the fp16 form of the same kernel ----
+# Y = x W^T and dx = dY W (+ the skip gradient) are gkg_linear_f16_f32a: fp32 operands rounded to IEEE fp16 on their way into LDS
+# (subnormals kept: a loss-scaled gradient's small values survive), fp32 accumulation, no vendor GEMM, no cast launch.  The weight
+# gradient is NOT here: it stays where ``fused._wgrad`` puts it (the x6 kernels measured faster than a one-product 16-bit weight
+# gradient at every cfg4 shape), so this path adds nothing atomically and holds under GKG_DETERMINISTIC as well.  Mechanism only:
+# ``fused.TRAIN_F16`` arrives as ``on``.
+def train_f16_ok(on, x, conv, bn, supported=None) -> bool:
+    """Whether ``fused._LinearBNAct.forward`` takes its product from linear_f16_train_fwd (and the backward its input gradient from
+    linear_f16_dgrad): the switch, gradients on, fp16 autocast, an fp32 CUDA matrix with unit column stride and a pitch that is a
+    multiple of 4, a dense 1x1 weight over exactly its columns, and the library's answers for both products (``supported(R, cin,
+    cout)`` stands in for them in tests).  ``fused.DETERMINISTIC`` takes no part (the weight gradient keeps its own path), nor does
+    ``bn``: the BN passes behind the product are the caller's, unchanged."""
+    if not on or not torch.is_grad_enabled():
+        return False
+    if not torch.is_autocast_enabled() or torch.get_autocast_dtype("cuda") != torch.float16:
+        return False
+    if x.dtype != _F32 or not x.is_cuda or len(x.shape) != 2 or x.stride(1) != 1 or x.stride(0) % 4:
+        return False
+    wshape = tuple(conv.weight.shape)
+    if conv.groups != 1 or len(wshape) != 4 or wshape[2:] != (1, 1) or wshape[1] != x.shape[1]:
+        return False
+    R, cin, cout = x.shape[0], wshape[1], wshape[0]
+    if supported is not None:
+        return bool(supported(R, cin, cout))
+    lib = _lib.load()
+    return bool(lib.gkg_linear_f16_f32a_supported(R, cin, cout, 0, 1, 0, 0) and lib.gkg_linear_f16_f32a_supported(R, cout, cin, 1, 1, 0, 0))
+
+
+def _f16_f32a(lib, x, planes, res, R, cin, cout, what):
+    """out (R, cout) fp32 = f16(x) (R, cin) . planes (+ res) on gkg_linear_f16_f32a."""
+    x = _rows(x, 4)
+    if res is not None:
+        res = _rows(res, 4)
+    out = torch.empty((R, cout), dtype=_F32, device=x.device)
+    _lib.check(lib.gkg_linear_f16_f32a(_ptr(x), x.stride(0), _ptr(planes), None, None, _ptr(res), 0 if res is None else res.stride(0),
+                                       _ptr(out), cout, None, 0, R, cin, cout, 0, _stream()), what)
+    return out
+
+
+@torch.no_grad()
+def linear_f16_train_fwd(x, conv):
+    """x (R, cin) fp32 -> Y = f16(x) f16(W)^T (R, cout) fp32: the pre-BN matrix (the conv bias stays in the BN passes)."""
+    assert x.dtype == _F32 and x.dim() == 2
+    cout = conv.weight.shape[0]
+    return _f16_f32a(_lib.load(), x, derived.lin_planes_f16(conv), None, x.shape[0], x.shape[1], cout, "gkg_linear_f16_f32a (forward)")
+
+
+@torch.no_grad()
+def linear_f16_dgrad(dY, conv, residual=None):
+    """dY (R, cout) fp32 -> dx = f16(dY) f16(W) (+ residual (R, cin) fp32: the skip gradient, added in the epilogue) (R, cin)."""
+    assert dY.dtype == _F32 and dY.dim() == 2
+    w = conv.weight
+    cout, cin = w.shape[0], w.numel() // w.shape[0]
+    assert dY.shape[1] == cout
+    if residual is not None:
+        assert residual.dtype == _F32 and tuple(residual.shape) == (dY.shape[0], cin)
+    return _f16_f32a(_lib.load(), dY, derived.lin_planes_t_f16(conv), residual, dY.shape[0], cout, cin,
+                     "gkg_linear_f16_f32a (input gradient)")

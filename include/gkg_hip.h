@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define GKG_ABI_VERSION 20
+#define GKG_ABI_VERSION 21
 
 /* dtype codes */
 #define GKG_F32 0
@@ -548,6 +548,36 @@ int gkg_linear_bf16_f32a(const float* x /* fp32 (R, ldx) */, int ldx, const void
 int gkg_linear_wgrad_bf16_supported(int R, int cin, int cout);
 int gkg_linear_wgrad_bf16(const float* dy /* (R, ldg) */, int ldg, const float* x /* (R, ldx) */, int ldx,
                           float* dw /* (cout, cin), += */, int R, int cin, int cout, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Training under fp16 autocast (opt-in GKG_ENABLE=train_f16; the reference's own recipe, configs/gkgnet/gkgnet_coco_576.py:146
+ * fp16 = dict(loss_scale='dynamic')): the forward and the input gradient of a dense 1x1 projection on IEEE fp16 operands with
+ * fp32 accumulation — the fp16 instantiation of the kernel above (csrc/gkg_linear_bf16.hip).  The weight gradient has no fp16
+ * form: it stays on gkg_linear_wgrad_x6.
+ *
+ * gkg_linear_f16_f32a: gkg_linear_bf16_f32a's arguments and meaning (NULL a = 1, NULL cshift = 0, the same forward / input-gradient
+ * uses), with
+ *   x (R, ldx) fp32, each element rounded to fp16 on its way into LDS: round-to-nearest-even, overflow to +-inf, NaN stays NaN,
+ *     subnormal results KEPT (under a loss scale small gradients are what must survive)
+ *   wplanes_f16: fp16 weight fragments in gkg_linear_bf16's layout, [ci_pad/8][co_pad][8], fragment (f, n) = w[n][8f .. 8f+7], zero
+ *     outside cin / cout; gkg_linear_f16_planes_bytes(cin, cout) bytes — the same paddings as the bf16 array, and like
+ *     gkg_linear_bf16_planes_bytes the only place that encodes them
+ *   acc[r][n] = sum_k f16(x[r][k]) * w[n][k]: the exact products of f16(x) and the fp16 fragments (an fp16 x fp16 product is exact
+ *     in fp32; subnormal operands are not flushed), accumulated in fp32 on v_mfma_f32_32x32x16_f16 in the bf16 kernel's contraction
+ *     order (ascending steps of 16, no K-split; the 64-column tile form at every shape)
+ *   the a / cshift / act / res epilogue of gkg_linear_bf16, out_f32 as there, out_f16[r][n] = IEEE fp16 of the fp32 result
+ *     (round-to-nearest-even; with both outputs the fp16 one is the rounding of the fp32 one).
+ * Consequently the call on x and the call on the fp32 widening of x.to(fp16) give equal bits.  Preconditions, bounds and error
+ * codes: gkg_linear_bf16_f32a's (cin % 8, cout % 8, ldx % 4, ldo16 % 8, ldo32 % 4, ldr % 4, 16-byte alignment).
+ * gkg_linear_f16_f32a_supported: 1 when the sizes pass (pure host code; gkg_linear_bf16_f32a_supported's answer). */
+size_t gkg_linear_f16_planes_bytes(int cin, int cout);
+int gkg_linear_f16_f32a_supported(int R, int cin, int cout, int has_res, int want_f32, int want_f16, int act);
+int gkg_linear_f16_f32a(const float* x /* fp32 (R, ldx) */, int ldx, const void* wplanes_f16,
+                        const float* a /* [cout] or NULL = 1 */, const float* cshift /* [cout] or NULL = 0 */,
+                        const float* res /* fp32 (R, ldr) or NULL */, int ldr,
+                        float* out_f32 /* (R, ldo32) or NULL */, int ldo32,
+                        void* out_f16 /* (R, ldo16) or NULL */, int ldo16,
+                        int R, int cin, int cout, int act /* 0 none, 1 GELU */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Bandwidth kernels between the dense 1x1 projections (Conv2d 1x1 + SyncBN [+ GELU], reference

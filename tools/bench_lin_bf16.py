@@ -47,7 +47,14 @@ the four stage shapes of the cfg4 training step (GKGNet-576, B 32), each against
     dgrad   gkg_linear_bf16_f32a (fp32 dY, fragments of W^T)  vs  torch.mm(dY, W) in fp32 (autograd runs the backward outside autocast)
     wgrad   gkg_linear_wgrad_bf16 (+ clearing dW)             vs  gkg_linear_wgrad_x6 (+ clearing dW)
 
-Same alternation, hipGraph replays and cache sweep."""
+Same alternation, hipGraph replays and cache sweep.
+
+--train --amp f16: the two products GKG_ENABLE=train_f16 moves under fp16 autocast, at the same 16 shapes, four legs alternating:
+
+    fwd     gkg_linear_f16_f32a (fp32 x, fp32 Y)             vs  fused._mm_t under fp16 autocast (two casts + vendor GEMM + cast back)
+    dgrad   gkg_linear_f16_f32a (fp32 dY, fragments of W^T)   vs  torch.mm(dY, W) in fp32
+
+(the weight gradient keeps its path with that switch).  --amp bf16 is the default: --train alone prints what it always did."""
 import argparse
 import json
 import os
@@ -374,8 +381,69 @@ def train_leg(args, lib, flush):
     return rows
 
 
+def train_f16_leg(args, lib, flush):
+    """--train --amp f16: the forward and the input gradient on gkg_linear_f16_f32a against the two paths GKG_ENABLE=train_f16
+    replaces (the weight gradient keeps its path with the switch: nothing to compare)."""
+    from gkgnet_amd import derived, fused
+    B = args.batch or 32
+    widths = {int(t) for t in args.widths.split(",")}
+    rows = []
+    for C, side in ((80, 144), (160, 72), (400, 36), (640, 18)):
+        if C not in widths:
+            continue
+        R = B * side * side
+        for name, cin, cout in (("fc1", C, C), ("fc2", 2 * C, C), ("ffn_fc1", C, 4 * C), ("ffn_fc2", 4 * C, C)):
+            gen = torch.Generator(device="cuda").manual_seed(cin * 7 + cout)
+            conv = torch.nn.Conv2d(cin, cout, 1).cuda()
+            x = torch.randn(R, cin, device="cuda", generator=gen)
+            dY = torch.randn(R, cout, device="cuda", generator=gen)
+            W = conv.weight.detach().view(cout, cin)
+            pf, pt = derived.lin_planes_f16(conv), derived.lin_planes_t_f16(conv)
+            Y, dx = torch.empty(R, cout, device="cuda"), torch.empty(R, cin, device="cuda")
+            V = {}
+
+            def fwd_own():
+                _lib.check(lib.gkg_linear_f16_f32a(_ptr(x), cin, _ptr(pf), None, None, None, 0, _ptr(Y), cout, None, 0, R, cin, cout, 0,
+                                                   _stream()), "gkg_linear_f16_f32a")
+
+            def fwd_old():
+                with torch.autocast("cuda", dtype=torch.float16):
+                    V["Y"] = fused._mm_t(x, W)
+
+            def dgrad_own():
+                _lib.check(lib.gkg_linear_f16_f32a(_ptr(dY), cout, _ptr(pt), None, None, None, 0, _ptr(dx), cin, None, 0, R, cout, cin, 0,
+                                                   _stream()), "gkg_linear_f16_f32a")
+
+            def dgrad_old():
+                V["dx"] = torch.mm(dY, W)
+            legs = (("fwd", fwd_own, fwd_old), ("dgrad", dgrad_own, dgrad_old))
+            graphs = [(capture(a), capture(b)) for _, a, b in legs]
+            t = [([], []) for _ in legs]
+            for _ in range(args.reps):                                           # alternate all four
+                for i, (ga, gb) in enumerate(graphs):
+                    t[i][0].append(1e3 * replay_ms(ga, flush))
+                    t[i][1].append(1e3 * replay_ms(gb, flush))
+            # the two sides agree to fp16 resolution: a sanity check of the comparison, not a test
+            diffs = [(((a - b).abs().max() / b.abs().max()).item()) for a, b in ((Y, V["Y"]), (dx, V["dx"]))]
+            row = dict(layer=name, C=C, R=R, cin=cin, cout=cout)
+            msg = f"C={C:4d} {name:8s} R={R:6d} {cin:4d}->{cout:4d}:"
+            for (leg, _, _), (to, tv), d in zip(legs, t, diffs):
+                uo, uv = statistics.median(to), statistics.median(tv)
+                row.update({f"{leg}_own_us": round(uo, 1), f"{leg}_old_us": round(uv, 1), f"{leg}_own_us_min": round(min(to), 1),
+                            f"{leg}_own_us_max": round(max(to), 1), f"{leg}_old_us_min": round(min(tv), 1),
+                            f"{leg}_old_us_max": round(max(tv), 1), f"{leg}_own_tflops": round(2.0 * R * cin * cout / uo * 1e-6, 1),
+                            f"{leg}_max_rel_diff": float(f"{d:.3e}"), f"{leg}_winner": "own" if uo < uv else "old"})
+                msg += f"  {leg} own {uo:7.1f} [{min(to):.1f}, {max(to):.1f}] old {uv:7.1f} [{min(tv):.1f}, {max(tv):.1f}] us"
+            rows.append(row)
+            print(msg + "  (max rel diff " + " ".join(f"{d:.1e}" for d in diffs) + ")", flush=True)
+            del x, dY, Y, dx, V, graphs
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--amp", default="bf16", choices=("bf16", "f16"),
+                    help="with --train: the autocast dtype — bf16 (GKG_ENABLE=train_bf16, three products) or f16 (GKG_ENABLE=train_f16: forward and input gradient)")
     ap.add_argument("--train", action="store_true", help="run the three training products (GKG_ENABLE=train_bf16) at the cfg4 shapes")
     ap.add_argument("--prep", default=None, choices=sorted(PREP_CONFIGS), help="run the fc1 + k-NN preparation leg at this config's shapes")
     ap.add_argument("--ffn", default=None, choices=sorted(PREP_CONFIGS), help="run the fused FFN launch against the two-launch pair at this config's shapes")
@@ -390,11 +458,11 @@ def main():
     lib = _lib.load()
     flush = torch.empty(128 << 20, dtype=torch.float32, device="cuda")
     if args.train:
-        rows = train_leg(args, lib, flush)
+        rows = train_f16_leg(args, lib, flush) if args.amp == "f16" else train_leg(args, lib, flush)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             with open(args.out, "w") as fh:
-                json.dump(dict(tool="bench_lin_bf16 --train", batch=args.batch or 32, reps=args.reps,
+                json.dump(dict(tool="bench_lin_bf16 --train" + (" --amp f16" if args.amp == "f16" else ""), batch=args.batch or 32, reps=args.reps,
                                device=torch.cuda.get_device_name(0), rows=rows), fh, indent=1)
         return
     if args.ffn:
