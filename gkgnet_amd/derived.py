@@ -1,8 +1,9 @@
 """Tensors derived from a layer's parameters and kept between calls — the bf16 weight copy, the BN-folded weight and shifts, the
-fragment arrays of the own bf16 kernels, an eval-mode BN's (a, c) — under ONE staleness protocol (``get``), and the builders of
-those values.  Mechanism only: which layer takes which of them is decided in ``fused.py``.  The store lives here, keyed weakly on
-the owning module: nothing is attached to the module, so deepcopy and pickling do not carry it.  (The x6 weight planes are not
-here: planes._WeightPlanes is per device, refreshes in batches and has its own capture rules.)"""
+fragment arrays of the own 16-bit kernels (one builder, ``_fragments``; a projection's four slots behind one ``lin_planes(conv, kind,
+transposed)``, the kind a row of linear_bf16.KINDS), an eval-mode BN's (a, c) — under ONE staleness protocol (``get``), and the
+builders of those values.  Mechanism only: which layer takes which of them is decided in ``fused.py``.  The store lives here,
+keyed weakly on the owning module: nothing is attached to the module, so deepcopy and pickling do not carry it.  (The x6 weight
+planes are not here: planes._WeightPlanes is per device, refreshes in batches and has its own capture rules.)"""
 from __future__ import annotations
 
 import weakref
@@ -55,7 +56,7 @@ def clear(owner=None):
         _STORE.pop(owner, None)
 
 
-# ---- the fragment arrays of the own bf16 kernels (include/gkg_hip.h): contraction padded to K_ALIGN, columns to N_ALIGN
+# ---- the fragment arrays of the own 16-bit kernels (include/gkg_hip.h): contraction padded to K_ALIGN, columns to N_ALIGN
 K_ALIGN, N_ALIGN = 16, 32
 
 
@@ -63,57 +64,47 @@ def _up(v, m):
     return (v + m - 1) // m * m
 
 
-def bf16_fragments(w, k_pad, n_pad) -> torch.Tensor:
-    """w (n, k), or a stack (g, n, k), as bf16 [k_pad/8][n_pad][8] (a leading g for a stack): fragment (f, n) = w[n][8f .. 8f+7],
-    zero outside the matrix."""
+def _fragments(w, k_pad, n_pad, dtype) -> torch.Tensor:
+    """w (n, k), or a stack (g, n, k), rounded by ``.to(dtype)`` (autocast's own cast) as [k_pad/8][n_pad][8] (a leading g for a
+    stack): fragment (f, n) = w[n][8f .. 8f+7], zero outside the matrix."""
     n, k = w.shape[-2:]
-    W = torch.zeros(w.shape[:-2] + (n_pad, k_pad), dtype=_BF16, device=w.device)
-    W[..., :n, :k] = w.detach().to(_BF16)
+    W = torch.zeros(w.shape[:-2] + (n_pad, k_pad), dtype=dtype, device=w.device)
+    W[..., :n, :k] = w.detach().to(dtype)
     return W.view(w.shape[:-2] + (n_pad, k_pad // 8, 8)).transpose(-3, -2).contiguous()
+
+
+def bf16_fragments(w, k_pad, n_pad) -> torch.Tensor:
+    """_fragments in bf16."""
+    return _fragments(w, k_pad, n_pad, _BF16)
 
 
 def f16_fragments(w, k_pad, n_pad) -> torch.Tensor:
-    """bf16_fragments' layout in IEEE fp16: the weight rounded by ``.to(torch.float16)``, autocast's own cast."""
-    n, k = w.shape[-2:]
-    W = torch.zeros(w.shape[:-2] + (n_pad, k_pad), dtype=_F16, device=w.device)
-    W[..., :n, :k] = w.detach().to(_F16)
-    return W.view(w.shape[:-2] + (n_pad, k_pad // 8, 8)).transpose(-3, -2).contiguous()
+    """_fragments in IEEE fp16."""
+    return _fragments(w, k_pad, n_pad, _F16)
 
 
-def _fragments_slot(conv, slot, mat, nbytes, fragments=bf16_fragments):
+def _fragments_slot(conv, slot, mat, nbytes, dtype=_BF16):
     """``mat(w)`` -> the matrix (or stack) to lay out, ``nbytes(lib, n, k)`` -> the library's size of that array."""
     def build():
         m = mat(conv.weight.detach())
         n, k = m.shape[-2:]
-        planes = fragments(m, _up(k, K_ALIGN), _up(n, N_ALIGN))
+        planes = _fragments(m, _up(k, K_ALIGN), _up(n, N_ALIGN), dtype)
         assert planes.numel() * 2 == int(nbytes(_lib.load(), n, k)), (slot, tuple(m.shape))      # the library owns the paddings
         return planes
     return get(conv, slot, (conv.weight,), build)
 
 
-def lin_planes(conv) -> torch.Tensor:
-    """The projection's UNFOLDED weight (cout, cin) as the fragment array gkg_linear_bf16 streams: [ci_pad/8][co_pad][8]."""
-    return _fragments_slot(conv, "lin_planes", lambda w: w.reshape(w.shape[0], -1),
-                           lambda lib, co, ci: lib.gkg_linear_bf16_planes_bytes(ci, co))
-
-
-def lin_planes_t(conv) -> torch.Tensor:
-    """The fragment array of the TRANSPOSED weight, what the input gradient dx = dY W streams (gkg_linear_bf16_f32a with contraction
-    cout and output columns cin): [co_pad'/8][ci_pad'][8], fragment (f, n) = w[8f .. 8f+7][n]."""
-    return _fragments_slot(conv, "lin_planes_t", lambda w: w.reshape(w.shape[0], -1).t(),
-                           lambda lib, ci, co: lib.gkg_linear_bf16_planes_bytes(co, ci))
-
-
-def lin_planes_f16(conv) -> torch.Tensor:
-    """lin_planes in fp16, what gkg_linear_f16_f32a streams for the forward (GKG_ENABLE=train_f16)."""
-    return _fragments_slot(conv, "lin_planes_f16", lambda w: w.reshape(w.shape[0], -1),
-                           lambda lib, co, ci: lib.gkg_linear_f16_planes_bytes(ci, co), f16_fragments)
-
-
-def lin_planes_t_f16(conv) -> torch.Tensor:
-    """lin_planes_t in fp16, what gkg_linear_f16_f32a streams for the input gradient."""
-    return _fragments_slot(conv, "lin_planes_t_f16", lambda w: w.reshape(w.shape[0], -1).t(),
-                           lambda lib, ci, co: lib.gkg_linear_f16_planes_bytes(co, ci), f16_fragments)
+def lin_planes(conv, kind="bf16", transposed=False) -> torch.Tensor:
+    """The projection's UNFOLDED weight (cout, cin) as the fragment array the own projection kernels stream, [ci_pad/8][co_pad][8]:
+    gkg_linear_bf16 and its kin, and a training layer's forward.  ``kind``: a row of linear_bf16.KINDS or its name — the element
+    type, the library's size question and the two slots are the row's.  ``transposed``: the array of W^T instead, what the input
+    gradient dx = dY W streams (the ``*_f32a`` entry point with contraction cout and output columns cin): [co_pad'/8][ci_pad'][8],
+    fragment (f, n) = w[8f .. 8f+7][n]."""
+    if isinstance(kind, str):
+        kind = linear_bf16.KINDS[kind]
+    return _fragments_slot(conv, kind.slots[transposed],
+                           lambda w: w.reshape(w.shape[0], -1).t() if transposed else w.reshape(w.shape[0], -1),
+                           lambda lib, n, k: getattr(lib, kind.planes_bytes)(k, n), kind.fragment)
 
 
 def mr_planes(conv) -> torch.Tensor:
@@ -142,3 +133,6 @@ def folded(conv, bn):
             return wf, shift.to(_BF16).contiguous(), shift.contiguous()
     srcs = (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var) + (() if conv.bias is None else (conv.bias,))
     return get(conv, "folded", srcs, build, extra=(bn.eps,), stats_of=bn)
+
+
+from . import linear_bf16      # noqa: E402  (last: linear_bf16 imports this module; only its KINDS is read, when lin_planes is called)

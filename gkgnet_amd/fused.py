@@ -457,9 +457,8 @@ from .linear_bf16 import (lin_bf16_ok, linear_bf16_eval,      # noqa: E402,F401 
                           lin_bf16_prep_ok, linear_bf16_knn_prep_eval)
 from .linear_bf16 import ffn_bf16_ok, ffn_bf16_eval      # noqa: E402,F401  (GKG_ENABLE=lin_bf16,ffn_bf16)
 from .linear_bf16 import mr_fc2_bf16_ok, mr_fc2_bf16_eval      # noqa: E402,F401  (GKG_ENABLE=lin_bf16,mr_fc2_bf16)
-from .linear_bf16 import (train_bf16_ok, linear_bf16_train_fwd,      # noqa: E402,F401  (GKG_ENABLE=train_bf16)
-                          linear_bf16_dgrad, linear_bf16_wgrad)
-from .linear_bf16 import train_f16_ok, linear_f16_train_fwd, linear_f16_dgrad      # noqa: E402,F401  (GKG_ENABLE=train_f16)
+from .linear_bf16 import (BF16, F16, train16_ok, train16_fwd,      # noqa: E402,F401  (GKG_ENABLE=train_bf16 / train_f16)
+                          train16_dgrad, linear_bf16_wgrad)
 from .layout import _tm_dtype, _TokenMajorToCL, _ToTokenMajor, _BlockEntry, _AvgPoolTM      # noqa: E402  (layout Functions: layout.py)
 
 
@@ -692,7 +691,7 @@ class _LinearBNAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, gamma, beta, residual, bn, act, nchw, out_lowp=False, w16=None, scale=None,
                 rows_per_scale=0, want16=False, alias=False, dual=False, xm=None, knn=None, t16=None):
-        """``t16`` = (kind, conv) — "bf16" | "f16" and the projection's module (travels like ``w16``) —, handed over by ``_lin`` only
+        """``t16`` = (kind, conv) — a row of linear_bf16.KINDS and the projection's module (travels like ``w16``) —, handed over by ``_lin`` only
         where GKG_ENABLE=train_bf16 / train_f16 takes the layer (_train_16bit, asked there: in here gradients are switched off and
         the backward runs outside autocast): the module's cached fragment arrays of that kind are what the own 16-bit products of
         this node's forward and backward stream.
@@ -756,12 +755,7 @@ class _LinearBNAct(torch.autograd.Function):
             # bf16 / fp16 autocast with gradients, opt-in: the product on the own kernel of that kind (fp32 A operand rounded on its
             # way into LDS).  The backward runs outside autocast: the decision is recorded here
             taken = t16
-            if taken is None:
-                Y = _mm_t(x, weight.view(cout, cin), w16)
-            elif taken[0] == "f16":
-                Y = linear_f16_train_fwd(x, taken[1])
-            else:
-                Y = linear_bf16_train_fwd(x, taken[1])
+            Y = _mm_t(x, weight.view(cout, cin), w16) if taken is None else train16_fwd(taken[0], x, taken[1])
             a, c, mean, invstd, sync = bn_passes.forward_params(lib, Y, bn, bias, R, cout, 1, group)
         if not fused_apply and not (own and mean is None and code == _lib.F32 and not want16):
             prep = None      # besides the train-mode pass only a frozen layer's affine behind the x6 projection, fp32 out, prepares
@@ -878,6 +872,11 @@ class _LinearBNAct(torch.autograd.Function):
         dbias, dgamma, dbeta = bn_passes.backward(lib, layer, g, cout, 0, dY, (dgamma, dbeta), ctx.needs_input_grad[2:5], row_scale,
                                                   atomic)
         W = weight.view(cout, cin)
+
+        def rides(dalias, shape):
+            """The alias gradient as the residual of an own input-gradient epilogue (fp32, exactly the product's shape), or None."""
+            return dalias if (dalias is not None and dalias.dtype == _F32 and dalias.shape == shape) else None
+
         if not ctx.needs_input_grad[0]:
             dx = None
         elif ctx.prev is not None and dalias is None:
@@ -886,19 +885,19 @@ class _LinearBNAct(torch.autograd.Function):
         # statistics epilogue takes no residual.  Above that this branch is EXPECTED to miss: the plain input gradient below adds
         # the residual, the link stays empty and the producer runs its own statistics pass — as the block driver's
         # dgrad_stats_ok does for the same shapes)
-        elif (ctx.prev is not None and dalias.dtype == _F32 and dalias.shape == (R, cin)
-              and _dgrad_with_link_ok(lib, R, cin, True)):
+        elif ctx.prev is not None and rides(dalias, (R, cin)) is not None and _dgrad_with_link_ok(lib, R, cin, True):
             dx = _dgrad_x6_with_link(lib, dY, ctx.pd, R, cin, cout, ctx.prev, dalias.contiguous())      # + the skip gradient in front
             dalias = None
         elif ctx.pd is not None:
             dx = torch.empty((R, cin), dtype=_F32, device=dY.device)
-            res = dalias.contiguous() if (dalias is not None and dalias.dtype == _F32 and dalias.shape == dx.shape) else None
+            res = rides(dalias, dx.shape)
+            res = None if res is None else res.contiguous()
             _dgrad_x6(lib, dY, cout, R * cout, ctx.pd, dx, R, cin, cout, 1, res)
             if res is not None:
                 dalias = None
         elif ctx.t16 is not None:                          # GKG_ENABLE=train_bf16 / train_f16: the own product, the skip gradient in its epilogue
-            res = dalias if (dalias is not None and dalias.dtype == _F32 and dalias.shape == (R, cin)) else None
-            dx = (linear_f16_dgrad if ctx.t16[0] == "f16" else linear_bf16_dgrad)(dY, ctx.t16[1], residual=res)
+            res = rides(dalias, (R, cin))
+            dx = train16_dgrad(ctx.t16[0], dY, ctx.t16[1], residual=res)
             if res is not None:
                 dalias = None
         elif dalias is not None and dalias.dtype == dY.dtype:
@@ -910,10 +909,10 @@ class _LinearBNAct(torch.autograd.Function):
             dx = dx + dalias
         elif dalias is not None:
             dx = dalias
-        if ctx.t16 is not None and ctx.t16[0] == "bf16":
+        if ctx.t16 is not None and ctx.t16[0].own_wgrad:
             # launched from the node: the deferred weight-gradient queue's problem records are x6 problems
             dW = linear_bf16_wgrad(dY, x, dWv).view_as(weight)
-        else:                                              # (train_f16 has no weight-gradient kernel of its own: the path of the switch-off run)
+        else:                                              # (a kind without a weight-gradient kernel of its own: the path of the switch-off run)
             dW = _wgrad(dY, x, dWv).view_as(weight)
         return dx, dW, dbias, dgamma, dbeta, dres, None, None, None, None, None, None, None, None, None, None, None, None, None
 
@@ -1483,14 +1482,13 @@ def fused_supported(mod, x, groups: int) -> bool:
 
 
 def _train_16bit(x, conv, bn):
-    """Which own 16-bit products _LinearBNAct takes for this layer, as (kind, conv) — "bf16": GKG_ENABLE=train_bf16 under bf16
-    autocast (linear_bf16.train_bf16_ok), "f16": GKG_ENABLE=train_f16 under fp16 autocast (linear_bf16.train_f16_ok) — with the module
-    its fragment arrays are cached on, or None.  Asked here, where the caller's gradient mode and autocast state are still
-    visible.  The two predicates exclude each other by the autocast dtype, so both switches may be on."""
-    if train_bf16_ok(TRAIN_BF16, x, conv, bn):
-        return "bf16", conv
-    if train_f16_ok(TRAIN_F16, x, conv, bn):
-        return "f16", conv
+    """Which own 16-bit products _LinearBNAct takes for this layer, as (kind, conv) — the row of linear_bf16.KINDS whose switch is on
+    (GKG_ENABLE=train_bf16 / train_f16) and whose predicate holds (linear_bf16.train16_ok: its autocast dtype among the rest), with the
+    module its fragment arrays are cached on — or None.  Asked here, where the caller's gradient mode and autocast state are still
+    visible.  The kinds exclude each other by the autocast dtype, so both switches may be on; bf16 is asked first."""
+    for kind, on in ((BF16, TRAIN_BF16), (F16, TRAIN_F16)):
+        if train16_ok(kind, on, x, conv, bn):
+            return kind, conv
     return None
 
 

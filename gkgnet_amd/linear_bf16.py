@@ -2,12 +2,16 @@
 (gkg_linear_bf16, csrc/gkg_linear_bf16.hip) — the call (the weight's fragment array: derived.lin_planes) and the predicate ``fused._lin`` asks before
 it dispatches here — and the same launch with the k-NN's token preparation riding on it (gkg_linear_bf16_knn_prep: a Grapher's
 fc1) — and an FFN's two projections as one launch with the hidden matrix kept on chip (gkg_ffn_bf16, csrc/gkg_ffn_bf16.hip) — and a Grapher's aggregation, grouped projection and fc2 as one launch
-(gkg_mr_fc2_bf16, csrc/gkg_mr_fc2_bf16.hip).  Also the training side (GKG_ENABLE=train_bf16): the same kernel reading an fp32 A operand for a layer's forward and input
-gradient (gkg_linear_bf16_f32a), the bf16 weight-gradient kernel (gkg_linear_wgrad_bf16) and their predicate; and under fp16 autocast
-(GKG_ENABLE=train_f16) the forward and input gradient on the fp16 form of that kernel (gkg_linear_f16_f32a).  Mechanism only: the
+(gkg_mr_fc2_bf16, csrc/gkg_mr_fc2_bf16.hip).  Also the training side (GKG_ENABLE=train_bf16 / train_f16): the same kernel reading an fp32 A
+operand for a layer's forward and input gradient, in bf16 (gkg_linear_bf16_f32a) or IEEE fp16 (gkg_linear_f16_f32a).  What differs
+between the two element kinds is one row each of ``KINDS`` (autocast dtype, entry-point names, fragment dtype, derived's two slots,
+``own_wgrad``); the predicate and the two products (train16_ok, train16_fwd, train16_dgrad) are written once against it, and the bf16
+weight-gradient kernel (gkg_linear_wgrad_bf16, linear_bf16_wgrad) is the one thing only bf16 has.  Mechanism only: the
 switches (``fused.LIN_BF16``, ``fused.LIN_BF16_PREP``, ``fused.FFN_BF16``, ``fused.MR_FC2_BF16``, ``fused.TRAIN_BF16``, ``fused.TRAIN_F16``) and the mode test (``fused.lowp_inference``) stay in
 ``fused.py`` and arrive as arguments."""
 from __future__ import annotations
+
+from typing import NamedTuple
 
 import torch
 
@@ -292,22 +296,47 @@ def linear_bf16_knn_prep_eval(x16, conv, bn, knn):
     return out
 
 
-# ---- training under bf16 autocast (GKG_ENABLE=train_bf16): the layer's three products on the own bf16 kernels ------------------
-# Y = x W^T and dx = dY W (+ the skip gradient) are gkg_linear_bf16_f32a (the projection kernel reading its A operand as fp32 and
-# rounding it on the way into LDS), dW = dY^T x is gkg_linear_wgrad_bf16 (csrc/gkg_linear_bf16_train.hip): one bf16 matrix
-# product with fp32 accumulation each, no vendor GEMM, no cast launch.  Mechanism only: ``fused.TRAIN_BF16`` arrives as ``on``.
-def train_bf16_ok(on, x, conv, bn, supported=None) -> bool:
-    """Whether ``fused._LinearBNAct.forward`` takes its product from linear_bf16_train_fwd (and the backward its two from
-    linear_bf16_dgrad / linear_bf16_wgrad): the switch, gradients on, bf16 autocast, not GKG_DETERMINISTIC (the weight gradient adds
-    with atomics), an fp32 CUDA matrix with unit column stride and a pitch that is a multiple of 4, a dense 1x1 weight over
-    exactly its columns, and the library's answers for all three products (``supported(R, cin, cout)`` stands in for them in
-    tests).  ``bn`` takes no part: the BN passes behind the product are the caller's, unchanged."""
+# ---- training under 16-bit autocast (GKG_ENABLE=train_bf16 / train_f16): a dense layer's products on the own kernel of that kind ----
+# Y = x W^T and dx = dY W (+ the skip gradient) are the kind's ``*_f32a`` entry point: the projection kernel reading fp32 operands and
+# rounding them on their way into LDS (bf16; or IEEE fp16, subnormals kept: a loss-scaled gradient's small values survive), fp32
+# accumulation, no vendor GEMM, no cast launch.  What differs between the two kinds is a row of KINDS; everything below is written
+# once against it.  bf16 alone has a weight-gradient kernel of its own (dW = dY^T x, gkg_linear_wgrad_bf16,
+# csrc/gkg_linear_bf16_train.hip: atomically added slabs, hence refused under GKG_DETERMINISTIC); fp16's weight gradient stays where
+# ``fused._wgrad`` puts it (the x6 kernels measured faster than a one-product 16-bit weight gradient at every cfg4 shape), so that kind
+# adds nothing atomically and holds under GKG_DETERMINISTIC as well.  Mechanism only: ``fused.TRAIN_BF16`` / ``fused.TRAIN_F16``
+# arrive as ``on``.
+class Kind16(NamedTuple):
+    """One element kind of the own 16-bit training products: exactly what differs between the kinds."""
+    name: str
+    autocast: torch.dtype            # the autocast dtype under which the kind is taken
+    f32a: str                        # entry points (include/gkg_hip.h): the product on fp32 operands,
+    f32a_supported: str              # its envelope,
+    planes_bytes: str                # the size of a fragment array
+    fragment: torch.dtype            # element type of the fragment arrays
+    slots: tuple                     # derived's cache slots of the weight's fragments: (as it is, transposed)
+    own_wgrad: bool                  # a weight-gradient kernel of its own (linear_bf16_wgrad): atomics, not under GKG_DETERMINISTIC
+
+
+BF16 = Kind16("bf16", torch.bfloat16, "gkg_linear_bf16_f32a", "gkg_linear_bf16_f32a_supported", "gkg_linear_bf16_planes_bytes",
+              torch.bfloat16, ("lin_planes", "lin_planes_t"), True)
+F16 = Kind16("f16", torch.float16, "gkg_linear_f16_f32a", "gkg_linear_f16_f32a_supported", "gkg_linear_f16_planes_bytes",
+             torch.float16, ("lin_planes_f16", "lin_planes_t_f16"), False)
+KINDS = {k.name: k for k in (BF16, F16)}
+
+
+def train16_ok(kind, on, x, conv, bn, supported=None) -> bool:
+    """Whether ``fused._LinearBNAct.forward`` takes its product from train16_fwd (and the backward its input gradient from
+    train16_dgrad and, for a kind with ``own_wgrad``, its weight gradient from linear_bf16_wgrad): the switch, gradients on, not
+    GKG_DETERMINISTIC where the kind's own weight gradient adds with atomics, the kind's autocast dtype, an fp32 CUDA matrix with
+    unit column stride and a pitch that is a multiple of 4, a dense 1x1 weight over exactly its columns, and the library's answers
+    for every product of the kind (``supported(R, cin, cout)`` stands in for them in tests).  ``bn`` takes no part: the BN passes
+    behind the product are the caller's, unchanged."""
     if not on:
         return False
     from . import fused
-    if not torch.is_grad_enabled() or fused.DETERMINISTIC:
+    if not torch.is_grad_enabled() or (kind.own_wgrad and fused.DETERMINISTIC):
         return False
-    if not torch.is_autocast_enabled() or torch.get_autocast_dtype("cuda") != torch.bfloat16:
+    if not torch.is_autocast_enabled() or torch.get_autocast_dtype("cuda") != kind.autocast:
         return False
     if x.dtype != _F32 or not x.is_cuda or len(x.shape) != 2 or x.stride(1) != 1 or x.stride(0) % 4:
         return False
@@ -318,39 +347,41 @@ def train_bf16_ok(on, x, conv, bn, supported=None) -> bool:
     if supported is not None:
         return bool(supported(R, cin, cout))
     lib = _lib.load()
-    return bool(lib.gkg_linear_bf16_f32a_supported(R, cin, cout, 0, 1, 0, 0) and lib.gkg_linear_bf16_f32a_supported(R, cout, cin, 1, 1, 0, 0)
-                and lib.gkg_linear_wgrad_bf16_supported(R, cin, cout))
+    f32a_supported = getattr(lib, kind.f32a_supported)
+    return bool(f32a_supported(R, cin, cout, 0, 1, 0, 0) and f32a_supported(R, cout, cin, 1, 1, 0, 0)
+                and (not kind.own_wgrad or lib.gkg_linear_wgrad_bf16_supported(R, cin, cout)))
 
 
-def _f32a(lib, x, planes, res, R, cin, cout, what):
-    """out (R, cout) fp32 = bf16(x) (R, cin) . planes (+ res) on gkg_linear_bf16_f32a."""
+def _f32a(kind, x, planes, res, R, cin, cout, what):
+    """out (R, cout) fp32 = kind(x) (R, cin) . planes (+ res) on the kind's ``*_f32a`` entry point."""
     x = _rows(x, 4)
     if res is not None:
         res = _rows(res, 4)
     out = torch.empty((R, cout), dtype=_F32, device=x.device)
-    _lib.check(lib.gkg_linear_bf16_f32a(_ptr(x), x.stride(0), _ptr(planes), None, None, _ptr(res), 0 if res is None else res.stride(0),
-                                        _ptr(out), cout, None, 0, R, cin, cout, 0, _stream()), what)
+    _lib.check(getattr(_lib.load(), kind.f32a)(_ptr(x), x.stride(0), _ptr(planes), None, None, _ptr(res),
+                                               0 if res is None else res.stride(0), _ptr(out), cout, None, 0, R, cin, cout, 0,
+                                               _stream()), "%s (%s)" % (kind.f32a, what))
     return out
 
 
 @torch.no_grad()
-def linear_bf16_train_fwd(x, conv):
-    """x (R, cin) fp32 -> Y = bf16(x) bf16(W)^T (R, cout) fp32: the pre-BN matrix (the conv bias stays in the BN passes)."""
+def train16_fwd(kind, x, conv):
+    """x (R, cin) fp32 -> Y = kind(x) kind(W)^T (R, cout) fp32: the pre-BN matrix (the conv bias stays in the BN passes)."""
     assert x.dtype == _F32 and x.dim() == 2
     cout = conv.weight.shape[0]
-    return _f32a(_lib.load(), x, derived.lin_planes(conv), None, x.shape[0], x.shape[1], cout, "gkg_linear_bf16_f32a (forward)")
+    return _f32a(kind, x, derived.lin_planes(conv, kind), None, x.shape[0], x.shape[1], cout, "forward")
 
 
 @torch.no_grad()
-def linear_bf16_dgrad(dY, conv, residual=None):
-    """dY (R, cout) fp32 -> dx = bf16(dY) bf16(W) (+ residual (R, cin) fp32: the skip gradient, added in the epilogue) (R, cin)."""
+def train16_dgrad(kind, dY, conv, residual=None):
+    """dY (R, cout) fp32 -> dx = kind(dY) kind(W) (+ residual (R, cin) fp32: the skip gradient, added in the epilogue) (R, cin)."""
     assert dY.dtype == _F32 and dY.dim() == 2
     w = conv.weight
     cout, cin = w.shape[0], w.numel() // w.shape[0]
     assert dY.shape[1] == cout
     if residual is not None:
         assert residual.dtype == _F32 and tuple(residual.shape) == (dY.shape[0], cin)
-    return _f32a(_lib.load(), dY, derived.lin_planes_t(conv), residual, dY.shape[0], cout, cin, "gkg_linear_bf16_f32a (input gradient)")
+    return _f32a(kind, dY, derived.lin_planes(conv, kind, transposed=True), residual, dY.shape[0], cout, cin, "input gradient")
 
 
 @torch.no_grad()
@@ -370,63 +401,3 @@ def linear_bf16_wgrad(dY, x, out=None):
     _lib.check(_lib.load().gkg_linear_wgrad_bf16(_ptr(dY), dY.stride(0), _ptr(x), x.stride(0), _ptr(out), R, cin, cout, _stream()),
                "gkg_linear_wgrad_bf16")
     return out
-
-
-# ---- training under fp16 autocast (GKG_ENABLE=train_f16): the forward and the input gradient on the fp16 form of the same kernel ----
-# Y = x W^T and dx = dY W (+ the skip gradient) are gkg_linear_f16_f32a: fp32 operands rounded to IEEE fp16 on their way into LDS
-# (subnormals kept: a loss-scaled gradient's small values survive), fp32 accumulation, no vendor GEMM, no cast launch.  The weight
-# gradient is NOT here: it stays where ``fused._wgrad`` puts it (the x6 kernels measured faster than a one-product 16-bit weight
-# gradient at every cfg4 shape), so this path adds nothing atomically and holds under GKG_DETERMINISTIC as well.  Mechanism only:
-# ``fused.TRAIN_F16`` arrives as ``on``.
-def train_f16_ok(on, x, conv, bn, supported=None) -> bool:
-    """Whether ``fused._LinearBNAct.forward`` takes its product from linear_f16_train_fwd (and the backward its input gradient from
-    linear_f16_dgrad): the switch, gradients on, fp16 autocast, an fp32 CUDA matrix with unit column stride and a pitch that is a
-    multiple of 4, a dense 1x1 weight over exactly its columns, and the library's answers for both products (``supported(R, cin,
-    cout)`` stands in for them in tests).  ``fused.DETERMINISTIC`` takes no part (the weight gradient keeps its own path), nor does
-    ``bn``: the BN passes behind the product are the caller's, unchanged."""
-    if not on or not torch.is_grad_enabled():
-        return False
-    if not torch.is_autocast_enabled() or torch.get_autocast_dtype("cuda") != torch.float16:
-        return False
-    if x.dtype != _F32 or not x.is_cuda or len(x.shape) != 2 or x.stride(1) != 1 or x.stride(0) % 4:
-        return False
-    wshape = tuple(conv.weight.shape)
-    if conv.groups != 1 or len(wshape) != 4 or wshape[2:] != (1, 1) or wshape[1] != x.shape[1]:
-        return False
-    R, cin, cout = x.shape[0], wshape[1], wshape[0]
-    if supported is not None:
-        return bool(supported(R, cin, cout))
-    lib = _lib.load()
-    return bool(lib.gkg_linear_f16_f32a_supported(R, cin, cout, 0, 1, 0, 0) and lib.gkg_linear_f16_f32a_supported(R, cout, cin, 1, 1, 0, 0))
-
-
-def _f16_f32a(lib, x, planes, res, R, cin, cout, what):
-    """out (R, cout) fp32 = f16(x) (R, cin) . planes (+ res) on gkg_linear_f16_f32a."""
-    x = _rows(x, 4)
-    if res is not None:
-        res = _rows(res, 4)
-    out = torch.empty((R, cout), dtype=_F32, device=x.device)
-    _lib.check(lib.gkg_linear_f16_f32a(_ptr(x), x.stride(0), _ptr(planes), None, None, _ptr(res), 0 if res is None else res.stride(0),
-                                       _ptr(out), cout, None, 0, R, cin, cout, 0, _stream()), what)
-    return out
-
-
-@torch.no_grad()
-def linear_f16_train_fwd(x, conv):
-    """x (R, cin) fp32 -> Y = f16(x) f16(W)^T (R, cout) fp32: the pre-BN matrix (the conv bias stays in the BN passes)."""
-    assert x.dtype == _F32 and x.dim() == 2
-    cout = conv.weight.shape[0]
-    return _f16_f32a(_lib.load(), x, derived.lin_planes_f16(conv), None, x.shape[0], x.shape[1], cout, "gkg_linear_f16_f32a (forward)")
-
-
-@torch.no_grad()
-def linear_f16_dgrad(dY, conv, residual=None):
-    """dY (R, cout) fp32 -> dx = f16(dY) f16(W) (+ residual (R, cin) fp32: the skip gradient, added in the epilogue) (R, cin)."""
-    assert dY.dtype == _F32 and dY.dim() == 2
-    w = conv.weight
-    cout, cin = w.shape[0], w.numel() // w.shape[0]
-    assert dY.shape[1] == cout
-    if residual is not None:
-        assert residual.dtype == _F32 and tuple(residual.shape) == (dY.shape[0], cin)
-    return _f16_f32a(_lib.load(), dY, derived.lin_planes_t_f16(conv), residual, dY.shape[0], cout, cin,
-                     "gkg_linear_f16_f32a (input gradient)")

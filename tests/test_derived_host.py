@@ -70,6 +70,8 @@ def _call(slot, conv, bn, lib):
             return bn_passes.eval_ac(lib, bn, conv.bias, conv.out_channels)
         if slot == "folded":
             return derived.folded(conv, bn)
+        if slot == "lin_planes_t":
+            return derived.lin_planes(conv, transposed=True)
         return getattr(derived, slot)(conv)
 
 
@@ -313,7 +315,7 @@ def test_bf16_fragments_of_the_transposed_weight():
     assert tuple(pt.shape) == (4, 64, 8)
     assert torch.equal(pt.view(torch.int16), _ref_fragments(w.t(), k_pad, n_pad).view(torch.int16))
     assert pt.numel() * 2 == _lib.load().gkg_linear_bf16_planes_bytes(co, ci)
-    assert torch.equal(derived.lin_planes_t(conv).view(torch.int16), pt.view(torch.int16))
+    assert torch.equal(derived.lin_planes(conv, transposed=True).view(torch.int16), pt.view(torch.int16))
 
 
 @pytest.mark.parametrize("ci,co", [(8, 8), (24, 24), (24, 40)])

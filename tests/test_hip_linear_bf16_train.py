@@ -2,7 +2,7 @@
 
   gkg_linear_bf16_f32a    the projection kernel with an fp32 A operand: BIT-identical to gkg_linear_bf16 on x.to(bfloat16), in every
                           form (csrc/gkg_linear_bf16.hip: the same LDS image, contraction order and epilogue)
-  linear_bf16_dgrad       dx = bf16(dY) bf16(W) (+ residual) against the fp64 product of the rounded operands, the bound of
+  train16_dgrad (bf16)    dx = bf16(dY) bf16(W) (+ residual) against the fp64 product of the rounded operands, the bound of
                           test_hip_linear_bf16._definition with the contraction length cout
   gkg_linear_wgrad_bf16   dw += bf16(dy)^T bf16(x) against fp64: |got - want| <= R 2^-24 mag + 8 2^-24 |want|, mag = |bf16(dy)|^T
                           |bf16(x)| — the first-order bound of ANY fp32 summation order over R exact products (the slabs are added
@@ -138,7 +138,7 @@ def test_dgrad_matches_the_fp64_product_of_the_rounded_operands(shape, with_res)
     conv.cuda()
     dY = torch.randn(R, cout, generator=g).cuda()
     res = torch.randn(R, cin, generator=g).cuda() if with_res else None
-    dx = linear_bf16.linear_bf16_dgrad(dY, conv, residual=res)
+    dx = linear_bf16.train16_dgrad(linear_bf16.BF16, dY, conv, residual=res)
     torch.cuda.synchronize()
     assert dx.dtype == torch.float32 and tuple(dx.shape) == (R, cin)
     d = dY.to(BF16).double().cpu()

@@ -11,7 +11,7 @@
                         within fp32's range — the derivation holds as it stands):
                           |got - want| <= cin 2^-24 |a| mag + 8 2^-24 (|want| + |res|) + 3e-7 |z| [GELU].
                         An all-subnormal x must meet the same bound (a flushing operand path would return zeros).
-  linear_f16_dgrad      dx = f16(dY) f16(W) (+ residual) against fp64 of the rounded operands, contraction length cout.
+  train16_dgrad (f16)   dx = f16(dY) f16(W) (+ residual) against fp64 of the rounded operands, contraction length cout.
 Reference layers: Conv2d(1x1) of Grapher.fc1 / fc2 (torch_vertex.py:290-306) and FFN.fc1 / fc2 (gkgnet.py:46-72) under fp16 AMP
 (configs/gkgnet/gkgnet_coco_576.py:146)."""
 import functools
@@ -211,7 +211,7 @@ def test_dgrad_matches_the_fp64_product_of_the_rounded_operands(shape, with_res)
     conv.cuda()
     dY = torch.randn(R, cout, generator=g).cuda()
     res = torch.randn(R, cin, generator=g).cuda() if with_res else None
-    dx = linear_bf16.linear_f16_dgrad(dY, conv, residual=res)
+    dx = linear_bf16.train16_dgrad(linear_bf16.F16, dY, conv, residual=res)
     torch.cuda.synchronize()
     assert dx.dtype == torch.float32 and tuple(dx.shape) == (R, cin)
     d = dY.to(F16).double().cpu()
@@ -228,9 +228,9 @@ def test_train_fwd_is_the_c_call_on_the_cached_fragments():
     g = torch.Generator().manual_seed(3)
     conv = torch.nn.Conv2d(cin, cout, 1).cuda()
     x = torch.randn(R, cin, generator=g).cuda()
-    Y = linear_bf16.linear_f16_train_fwd(x, conv)
+    Y = linear_bf16.train16_fwd(linear_bf16.F16, x, conv)
     torch.cuda.synchronize()
-    assert torch.equal(derived.lin_planes_f16(conv), _planes(conv.weight.detach().reshape(cout, cin).to(F16)))
+    assert torch.equal(derived.lin_planes(conv, "f16"), _planes(conv.weight.detach().reshape(cout, cin).to(F16)))
     xd, wd = x.to(F16).double().cpu(), conv.weight.detach().reshape(cout, cin).to(F16).double().cpu()
     want, bound = _definition(xd @ wd.t(), xd.abs() @ wd.abs().t(), cin, None, torch.zeros(cout), None, 0)
     assert bool(((Y.double().cpu() - want).abs() <= bound).all())

@@ -67,14 +67,17 @@ def _same_bits(a, b):
 
 
 def _instrument(monkeypatch):
-    """Counting wrappers around the three own callers of ``fused`` (recording operands and results), the library GEMMs of ``fused``
-    and gkg_linear_wgrad_x6 (recording nb)."""
+    """Counting wrappers around the three own callers of ``fused`` (recording operands and results of the bf16 kind, without the kind
+    argument), the library GEMMs of ``fused`` and gkg_linear_wgrad_x6 (recording nb)."""
     from gkgnet_amd import _lib, fused
     rec, counts, x6 = {"fwd": [], "dgrad": [], "wgrad": []}, {}, []
-    for kind, name in (("fwd", "linear_bf16_train_fwd"), ("dgrad", "linear_bf16_dgrad"), ("wgrad", "linear_bf16_wgrad")):
-        def recording(*a, _real=getattr(fused, name), _kind=kind, **k):
+    for key, name in (("fwd", "train16_fwd"), ("dgrad", "train16_dgrad"), ("wgrad", "linear_bf16_wgrad")):
+        def recording(*a, _real=getattr(fused, name), _key=key, **k):
             out = _real(*a, **k)
-            rec[_kind].append((a, k, out))
+            if _key == "wgrad":
+                rec[_key].append((a, k, out))
+            elif a[0].name == "bf16":
+                rec[_key].append((a[1:], k, out))
             return out
         monkeypatch.setattr(fused, name, recording)
     lib = _lib.load()

@@ -16,19 +16,22 @@ from tests.test_hip_train_bf16_modules import DENSE, _inputs, _pair, _same_bits,
 pytestmark = pytest.mark.gpu
 
 F16, BF16 = torch.float16, torch.bfloat16
-OWN = (("f16_fwd", "linear_f16_train_fwd"), ("f16_dgrad", "linear_f16_dgrad"),
-       ("bf16_fwd", "linear_bf16_train_fwd"), ("bf16_dgrad", "linear_bf16_dgrad"), ("bf16_wgrad", "linear_bf16_wgrad"))
+OWN = (("fwd", "train16_fwd"), ("dgrad", "train16_dgrad"), ("wgrad", "linear_bf16_wgrad"))
+KEYS = ("f16_fwd", "f16_dgrad", "bf16_fwd", "bf16_dgrad", "bf16_wgrad")
 
 
 def _instrument(monkeypatch):
-    """Recording wrappers around the own callers of ``fused`` (both kinds), the library GEMMs of ``fused`` counted, and
-    gkg_linear_wgrad_x6's nb recorded."""
+    """Recording wrappers around the own callers of ``fused``, sorted by their kind argument (both kinds; recorded without it), the
+    library GEMMs of ``fused`` counted, and gkg_linear_wgrad_x6's nb recorded."""
     from gkgnet_amd import _lib, fused
-    rec, counts, x6 = {kind: [] for kind, _ in OWN}, {}, []
-    for kind, name in OWN:
-        def recording(*a, _real=getattr(fused, name), _kind=kind, **k):
+    rec, counts, x6 = {key: [] for key in KEYS}, {}, []
+    for what, name in OWN:
+        def recording(*a, _real=getattr(fused, name), _what=what, **k):
             out = _real(*a, **k)
-            rec[_kind].append((a, k, out))
+            if _what == "wgrad":
+                rec["bf16_wgrad"].append((a, k, out))
+            else:
+                rec[f"{a[0].name}_{_what}"].append((a[1:], k, out))
             return out
         monkeypatch.setattr(fused, name, recording)
     lib = _lib.load()

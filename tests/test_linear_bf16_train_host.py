@@ -2,6 +2,7 @@
 version and the four entry points in the derived binding, the pure host functions, the dispatch predicate and the fragment
 array of the transposed weight."""
 import ctypes as C
+import functools
 import types
 
 import torch
@@ -69,7 +70,7 @@ def test_train_predicate_truth_table(monkeypatch):
     monkeypatch.setattr(torch, "get_autocast_dtype", lambda *a: auto["dtype"])
     monkeypatch.setattr(fused, "DETERMINISTIC", False)
     sup = lambda R, cin, cout: (R, cin, cout) == (324, 80, 160)                   # noqa: E731
-    ok = fused.train_bf16_ok
+    ok = functools.partial(fused.train16_ok, fused.BF16)
     bn = types.SimpleNamespace(training=True, track_running_stats=True)
     x, conv = _x(), _conv()
     with torch.enable_grad():
@@ -119,7 +120,7 @@ def test_transposed_planes_are_the_fragments_of_w_t_and_cached():
     from gkgnet_amd import _lib, derived
     torch.manual_seed(5)
     conv = torch.nn.Conv2d(24, 40, 1)                                            # cout 40 -> contraction pad 48, cin 24 -> 32 columns
-    pt = derived.lin_planes_t(conv)
+    pt = derived.lin_planes(conv, transposed=True)
     assert pt.dtype == torch.bfloat16 and pt.is_contiguous() and tuple(pt.shape) == (6, 32, 8)
     assert pt.numel() * 2 == _lib.load().gkg_linear_bf16_planes_bytes(40, 24)
     w = conv.weight.detach().reshape(40, 24)
@@ -127,9 +128,9 @@ def test_transposed_planes_are_the_fragments_of_w_t_and_cached():
     # the forward array is the same layout of w itself: the two are one construction
     assert torch.equal(derived.lin_planes(conv).view(torch.int16), _fragments(w).view(torch.int16))
     assert bool((pt[5] == 0).all()) and bool((pt[:, 24:] == 0).all())            # the pad region
-    assert derived.lin_planes_t(conv) is pt                                    # cached
+    assert derived.lin_planes(conv, transposed=True) is pt                                    # cached
     with torch.no_grad():
         conv.weight.mul_(2.0)                                                    # an in-place parameter update
-    pt2 = derived.lin_planes_t(conv)
+    pt2 = derived.lin_planes(conv, transposed=True)
     assert pt2 is not pt and torch.equal(pt2.float(), 2.0 * pt.float())
     assert torch.equal(pt2.view(torch.int16), _fragments(conv.weight.detach().reshape(40, 24).t()).view(torch.int16))

@@ -1,6 +1,7 @@
 """GKG_ENABLE=train_f16 (gkg_linear_f16_f32a; linear_bf16.py, derived.py), the parts that need no device: the ABI version and the
 three entry points in the derived binding, the pure host functions, the fp16 fragment layout and the dispatch predicate."""
 import ctypes as C
+import functools
 import itertools
 import re
 import types
@@ -95,18 +96,18 @@ def test_f16_plane_slots_are_cached_and_follow_updates():
     from gkgnet_amd import _lib, derived
     torch.manual_seed(5)
     conv = torch.nn.Conv2d(24, 40, 1)
-    p, pt = derived.lin_planes_f16(conv), derived.lin_planes_t_f16(conv)
+    p, pt = derived.lin_planes(conv, "f16"), derived.lin_planes(conv, "f16", transposed=True)
     assert p.dtype == pt.dtype == torch.float16 and tuple(p.shape) == (4, 64, 8) and tuple(pt.shape) == (6, 32, 8)
     lib = _lib.load()
     assert p.numel() * 2 == lib.gkg_linear_f16_planes_bytes(24, 40) and pt.numel() * 2 == lib.gkg_linear_f16_planes_bytes(40, 24)
     w = conv.weight.detach().reshape(40, 24)
     assert torch.equal(p.view(torch.int16), _fragments(w).view(torch.int16))
     assert torch.equal(pt.view(torch.int16), _fragments(w.t()).view(torch.int16))
-    assert derived.lin_planes_f16(conv) is p and derived.lin_planes_t_f16(conv) is pt
+    assert derived.lin_planes(conv, "f16") is p and derived.lin_planes(conv, "f16", transposed=True) is pt
     assert derived.lin_planes(conv).dtype == torch.bfloat16                      # the bf16 slots are their own
     with torch.no_grad():
         conv.weight.mul_(2.0)
-    p2, pt2 = derived.lin_planes_f16(conv), derived.lin_planes_t_f16(conv)
+    p2, pt2 = derived.lin_planes(conv, "f16"), derived.lin_planes(conv, "f16", transposed=True)
     assert p2 is not p and pt2 is not pt
     w2 = conv.weight.detach().reshape(40, 24)
     assert not torch.equal(p2, p) and not torch.equal(pt2, pt)
@@ -130,7 +131,7 @@ def test_train_f16_predicate_truth_table(monkeypatch):
     monkeypatch.setattr(torch, "get_autocast_dtype", lambda *a: auto["dtype"])
     monkeypatch.setattr(fused, "DETERMINISTIC", False)
     sup = lambda R, cin, cout: (R, cin, cout) == (324, 80, 160)                   # noqa: E731
-    ok = fused.train_f16_ok
+    ok = functools.partial(fused.train16_ok, fused.F16)
     bn = types.SimpleNamespace(training=True, track_running_stats=True)
     x, conv = _x(), _conv()
     with torch.enable_grad():
@@ -163,7 +164,7 @@ def test_train_f16_predicate_truth_table(monkeypatch):
 
 
 def test_the_two_switches_do_not_see_each_other(monkeypatch):
-    """train_bf16_ok's answers are what they were, whatever TRAIN_F16 is; the one decision of ``fused`` returns the kind that
+    """train16_ok's bf16 answers are what they were, whatever TRAIN_F16 is; the one decision of ``fused`` returns the kind that
     belongs to the autocast dtype, with both switches on too."""
     from gkgnet_amd import fused
     auto = {"on": True, "dtype": torch.bfloat16}
@@ -172,13 +173,14 @@ def test_the_two_switches_do_not_see_each_other(monkeypatch):
     monkeypatch.setattr(fused, "DETERMINISTIC", False)
     bn = types.SimpleNamespace(training=True, track_running_stats=True)
     x, conv = _x(), _conv()
+    bf16_ok = functools.partial(fused.train16_ok, fused.BF16)
     with torch.enable_grad():
         for f16 in (False, True):
             monkeypatch.setattr(fused, "TRAIN_F16", f16)
             auto["dtype"] = torch.bfloat16
-            assert fused.train_bf16_ok(True, x, conv, bn) is True and fused.train_bf16_ok(False, x, conv, bn) is False
+            assert bf16_ok(True, x, conv, bn) is True and bf16_ok(False, x, conv, bn) is False
             auto["dtype"] = torch.float16
-            assert fused.train_bf16_ok(True, x, conv, bn) is False
+            assert bf16_ok(True, x, conv, bn) is False
         want = {(False, False): (None, None), (True, False): ("bf16", None), (False, True): (None, "f16"), (True, True): ("bf16", "f16")}
         for (b16, f16), (under_bf16, under_f16) in want.items():
             monkeypatch.setattr(fused, "TRAIN_BF16", b16)
@@ -186,7 +188,7 @@ def test_the_two_switches_do_not_see_each_other(monkeypatch):
             for dtype, kind in ((torch.bfloat16, under_bf16), (torch.float16, under_f16)):
                 auto["dtype"] = dtype
                 got = fused._train_16bit(x, conv, bn)
-                assert (got is None and kind is None) or (got[0] == kind and got[1] is conv), (b16, f16, dtype, got)
+                assert (got is None and kind is None) or (got[0].name == kind and got[1] is conv), (b16, f16, dtype, got)
             auto["on"] = False
             assert fused._train_16bit(x, conv, bn) is None                       # fp32
             auto["on"] = True

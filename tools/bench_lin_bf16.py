@@ -64,7 +64,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
-from gkgnet_amd import _lib  # noqa: E402
+from gkgnet_amd import _lib, linear_bf16  # noqa: E402
 from gkgnet_amd.ops import _ptr, _stream  # noqa: E402
 
 BF16 = torch.bfloat16
@@ -313,10 +313,14 @@ def tail_leg(args, lib, flush):
     return rows
 
 
-def train_leg(args, lib, flush):
+def train_leg(args, lib, flush, kind):
+    """--train: the own training products of ``kind`` (a row of linear_bf16.KINDS; --amp) against the paths its switch replaces — the
+    forward and the input gradient on the kind's ``*_f32a`` entry point, and the weight gradient where the kind has a kernel of its
+    own (bf16; fp16's keeps its path with the switch: nothing to compare)."""
     from gkgnet_amd import derived, fused
     B = args.batch or 32
     widths = {int(t) for t in args.widths.split(",")}
+    f32a = getattr(lib, kind.f32a)
     rows = []
     for C, side in ((80, 144), (160, 72), (400, 36), (640, 18)):
         if C not in widths:
@@ -328,22 +332,20 @@ def train_leg(args, lib, flush):
             x = torch.randn(R, cin, device="cuda", generator=gen)
             dY = torch.randn(R, cout, device="cuda", generator=gen)
             W = conv.weight.detach().view(cout, cin)
-            pf, pt = derived.lin_planes(conv), derived.lin_planes_t(conv)
+            pf, pt = derived.lin_planes(conv, kind), derived.lin_planes(conv, kind, transposed=True)
             Y, dx = torch.empty(R, cout, device="cuda"), torch.empty(R, cin, device="cuda")
             dw_own, dw_x6 = torch.empty(cout, cin, device="cuda"), torch.empty(cout, cin, device="cuda")
             V = {}
 
             def fwd_own():
-                _lib.check(lib.gkg_linear_bf16_f32a(_ptr(x), cin, _ptr(pf), None, None, None, 0, _ptr(Y), cout, None, 0, R, cin, cout, 0,
-                                                    _stream()), "gkg_linear_bf16_f32a")
+                _lib.check(f32a(_ptr(x), cin, _ptr(pf), None, None, None, 0, _ptr(Y), cout, None, 0, R, cin, cout, 0, _stream()), kind.f32a)
 
             def fwd_old():
-                with torch.autocast("cuda", dtype=BF16):
+                with torch.autocast("cuda", dtype=kind.autocast):
                     V["Y"] = fused._mm_t(x, W)
 
             def dgrad_own():
-                _lib.check(lib.gkg_linear_bf16_f32a(_ptr(dY), cout, _ptr(pt), None, None, None, 0, _ptr(dx), cin, None, 0, R, cout, cin, 0,
-                                                    _stream()), "gkg_linear_bf16_f32a")
+                _lib.check(f32a(_ptr(dY), cout, _ptr(pt), None, None, None, 0, _ptr(dx), cin, None, 0, R, cout, cin, 0, _stream()), kind.f32a)
 
             def dgrad_old():
                 V["dx"] = torch.mm(dY, W)
@@ -357,74 +359,15 @@ def train_leg(args, lib, flush):
                 dw_x6.zero_()
                 _lib.check(lib.gkg_linear_wgrad_x6(_ptr(dY), cout, 0, _ptr(x), cin, 0, _ptr(dw_x6), R, cin, cout, 1, 0, _stream()),
                            "gkg_linear_wgrad_x6")
-            legs = (("fwd", fwd_own, fwd_old), ("dgrad", dgrad_own, dgrad_old), ("wgrad", wgrad_own, wgrad_old))
+            legs = (("fwd", fwd_own, fwd_old), ("dgrad", dgrad_own, dgrad_old), ("wgrad", wgrad_own, wgrad_old))[:3 if kind.own_wgrad else 2]
             graphs = [(capture(a), capture(b)) for _, a, b in legs]
             t = [([], []) for _ in legs]
-            for _ in range(args.reps):                                           # alternate all six
+            for _ in range(args.reps):                                           # alternate all of them
                 for i, (ga, gb) in enumerate(graphs):
                     t[i][0].append(1e3 * replay_ms(ga, flush))
                     t[i][1].append(1e3 * replay_ms(gb, flush))
-            # the two sides agree to bf16 resolution: a sanity check of the comparison, not a test
-            diffs = [(((a - b).abs().max() / b.abs().max()).item()) for a, b in ((Y, V["Y"]), (dx, V["dx"]), (dw_own, dw_x6))]
-            row = dict(layer=name, C=C, R=R, cin=cin, cout=cout)
-            msg = f"C={C:4d} {name:8s} R={R:6d} {cin:4d}->{cout:4d}:"
-            for (leg, _, _), (to, tv), d in zip(legs, t, diffs):
-                uo, uv = statistics.median(to), statistics.median(tv)
-                row.update({f"{leg}_own_us": round(uo, 1), f"{leg}_old_us": round(uv, 1), f"{leg}_own_us_min": round(min(to), 1),
-                            f"{leg}_own_us_max": round(max(to), 1), f"{leg}_old_us_min": round(min(tv), 1),
-                            f"{leg}_old_us_max": round(max(tv), 1), f"{leg}_own_tflops": round(2.0 * R * cin * cout / uo * 1e-6, 1),
-                            f"{leg}_max_rel_diff": float(f"{d:.3e}"), f"{leg}_winner": "own" if uo < uv else "old"})
-                msg += f"  {leg} own {uo:7.1f} [{min(to):.1f}, {max(to):.1f}] old {uv:7.1f} [{min(tv):.1f}, {max(tv):.1f}] us"
-            rows.append(row)
-            print(msg + "  (max rel diff " + " ".join(f"{d:.1e}" for d in diffs) + ")", flush=True)
-            del x, dY, Y, dx, V, graphs
-    return rows
-
-
-def train_f16_leg(args, lib, flush):
-    """--train --amp f16: the forward and the input gradient on gkg_linear_f16_f32a against the two paths GKG_ENABLE=train_f16
-    replaces (the weight gradient keeps its path with the switch: nothing to compare)."""
-    from gkgnet_amd import derived, fused
-    B = args.batch or 32
-    widths = {int(t) for t in args.widths.split(",")}
-    rows = []
-    for C, side in ((80, 144), (160, 72), (400, 36), (640, 18)):
-        if C not in widths:
-            continue
-        R = B * side * side
-        for name, cin, cout in (("fc1", C, C), ("fc2", 2 * C, C), ("ffn_fc1", C, 4 * C), ("ffn_fc2", 4 * C, C)):
-            gen = torch.Generator(device="cuda").manual_seed(cin * 7 + cout)
-            conv = torch.nn.Conv2d(cin, cout, 1).cuda()
-            x = torch.randn(R, cin, device="cuda", generator=gen)
-            dY = torch.randn(R, cout, device="cuda", generator=gen)
-            W = conv.weight.detach().view(cout, cin)
-            pf, pt = derived.lin_planes_f16(conv), derived.lin_planes_t_f16(conv)
-            Y, dx = torch.empty(R, cout, device="cuda"), torch.empty(R, cin, device="cuda")
-            V = {}
-
-            def fwd_own():
-                _lib.check(lib.gkg_linear_f16_f32a(_ptr(x), cin, _ptr(pf), None, None, None, 0, _ptr(Y), cout, None, 0, R, cin, cout, 0,
-                                                   _stream()), "gkg_linear_f16_f32a")
-
-            def fwd_old():
-                with torch.autocast("cuda", dtype=torch.float16):
-                    V["Y"] = fused._mm_t(x, W)
-
-            def dgrad_own():
-                _lib.check(lib.gkg_linear_f16_f32a(_ptr(dY), cout, _ptr(pt), None, None, None, 0, _ptr(dx), cin, None, 0, R, cout, cin, 0,
-                                                   _stream()), "gkg_linear_f16_f32a")
-
-            def dgrad_old():
-                V["dx"] = torch.mm(dY, W)
-            legs = (("fwd", fwd_own, fwd_old), ("dgrad", dgrad_own, dgrad_old))
-            graphs = [(capture(a), capture(b)) for _, a, b in legs]
-            t = [([], []) for _ in legs]
-            for _ in range(args.reps):                                           # alternate all four
-                for i, (ga, gb) in enumerate(graphs):
-                    t[i][0].append(1e3 * replay_ms(ga, flush))
-                    t[i][1].append(1e3 * replay_ms(gb, flush))
-            # the two sides agree to fp16 resolution: a sanity check of the comparison, not a test
-            diffs = [(((a - b).abs().max() / b.abs().max()).item()) for a, b in ((Y, V["Y"]), (dx, V["dx"]))]
+            # the two sides agree to the kind's resolution: a sanity check of the comparison, not a test
+            diffs = [(((a - b).abs().max() / b.abs().max()).item()) for a, b in ((Y, V["Y"]), (dx, V["dx"]), (dw_own, dw_x6))[:len(legs)]]
             row = dict(layer=name, C=C, R=R, cin=cin, cout=cout)
             msg = f"C={C:4d} {name:8s} R={R:6d} {cin:4d}->{cout:4d}:"
             for (leg, _, _), (to, tv), d in zip(legs, t, diffs):
@@ -458,7 +401,7 @@ def main():
     lib = _lib.load()
     flush = torch.empty(128 << 20, dtype=torch.float32, device="cuda")
     if args.train:
-        rows = train_f16_leg(args, lib, flush) if args.amp == "f16" else train_leg(args, lib, flush)
+        rows = train_leg(args, lib, flush, linear_bf16.KINDS[args.amp])
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             with open(args.out, "w") as fh:
