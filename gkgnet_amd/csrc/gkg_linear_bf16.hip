@@ -61,6 +61,24 @@
 // is fp16.  Fragment layout, LDS pitches, look-ahead, barriers, zero-fill, tile map, epilogue and refusals are the shared code.
 //   linear_bf16_kernel<2, false, true, LbElem::F16>   184 VGPRs, 0 AGPRs, 62 SGPRs   LDS 53 248 B (dynamic), no scratch   2 waves / SIMD
 // The five bf16 instantiations keep their figures with the parameter (234 / 66, 152 / 62, 237 / 106, 155 / 106, 186 / 62).
+//
+// GROUPED = true (gkg_linear_bf16_f32a_grouped / gkg_linear_f16_f32a_grouped: BasicConv's Conv2d(1x1, groups = 4) behind the
+// max-relative aggregation, torch_nn.py:57-69 behind torch_vertex.py:57-61, under 16-bit autocast with gradients, opt-in
+// GKG_ENABLE=train_grouped): the fp32-A 64-column form with a group dimension.  One launch computes nb independent products; group
+// q's x, fragment array and output are the launch's base pointers plus q times a per-operand stride (LinBf16GroupedArgs).  The only
+// thing that differs from the single-matrix form is the origin of a tile's pointers: the workgroup derives q from its tile index
+// (workgroup-uniform: scalar registers, 64-bit offsets) and from there on runs the shared code — element rounding, LDS image,
+// contraction order, zero-fill of partial tiles, store path — on its group's own (R, cin) x (cout, cin) problem, so group q's bits
+// are those of gkg_linear_{bf16,f16}_f32a on group q's views.  A pure product: scale, shift, activation, residual and the 16-bit
+// output are compiled out (what remains is the single-matrix form's acc + 0 of a NULL shift vector).
+// Tile map: tiles = row tiles x nb x col_tiles inside the per-XCD contiguous ranges, column tile fastest, then the group, then the
+// row tile: the nb groups of one 128-row tile are adjacent on one XCD.  In the forward a row of XM holds all four groups' chunks in
+// 4 ci contiguous floats, so its cache lines come from memory once per L2; in the input gradient the same holds for the rows of dXM
+// being written.
+//   linear_bf16_kernel<2, false, true, LbElem::BF16, true>   191 VGPRs, 0 AGPRs, 64 SGPRs   LDS 53 248 B (dynamic), no scratch   2 waves / SIMD
+//   linear_bf16_kernel<2, false, true, LbElem::F16, true>    189 VGPRs, 0 AGPRs, 64 SGPRs   LDS 53 248 B (dynamic), no scratch   2 waves / SIMD
+// The six instantiations above keep their figures AND their instructions with the parameter (234 / 66, 152 / 62, 237 / 106,
+// 155 / 106, 186 / 62, 184 / 62): without it the kernel's text is what it was.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -98,6 +116,14 @@ struct LinBf16Args {
 // call behind it.  q: the queries' set of that call's own plan (knn_query_prep_plan; q.s.t == o32, token-major rows of B images x
 // N tokens, G groups of c channels); cnt: one arrival counter per row tile, zero between launches.
 struct LinBf16PrepArgs : LinBf16Args { KnnQueryPrep q; unsigned* cnt; int B, G, c, N; };
+
+// GROUPED (gkg_linear_bf16_f32a_grouped / gkg_linear_f16_f32a_grouped): nb independent products in one launch.  Group q's operands
+// are the base pointers plus q times a stride: x + q x_gs and o32 + q out_gs in floats, wp + q wp_gs in fragments (the nb fragment
+// arrays lie back to back).  tiles = row tiles x nb x col_tiles.
+struct LinBf16GroupedArgs : LinBf16Args { long long x_gs, out_gs, wp_gs; int nb; };
+
+template <bool PREP, bool GROUPED>
+using lb_args_t = std::conditional_t<PREP, LinBf16PrepArgs, std::conditional_t<GROUPED, LinBf16GroupedArgs, LinBf16Args>>;
 
 constexpr size_t lb_lds_bytes(int NB) { return 2 * (size_t)(LB_ABYTES + (LB_KC / 8) * 32 * NB * 16); }
 // tokens per cooperative preparation tile: c (TK + 1) floats fit the operand buffers of either tile form (53 248 B)
@@ -155,9 +181,10 @@ __device__ __forceinline__ lb_f32x16 lb_mfma(const uint4& a, const uint4& b, lb_
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(lb_bf16x8, a), __builtin_bit_cast(lb_bf16x8, b), c, 0, 0, 0);
 }
 
-template <int NB, bool PREP = false, bool F32A = false, LbElem E = LbElem::BF16>
-__global__ __launch_bounds__(LB_NT, 2) void linear_bf16_kernel(std::conditional_t<PREP, LinBf16PrepArgs, LinBf16Args> g) {
+template <int NB, bool PREP = false, bool F32A = false, LbElem E = LbElem::BF16, bool GROUPED = false>
+__global__ __launch_bounds__(LB_NT, 2) void linear_bf16_kernel(lb_args_t<PREP, GROUPED> g) {
   static_assert(!(PREP && F32A), "the fp32-A form has no token preparation");
+  static_assert(!GROUPED || (F32A && NB == 2), "the grouped form: the fp32-A 64-column form only");
   static_assert(E == LbElem::BF16 || (F32A && NB == 2), "fp16 operands: the fp32-A 64-column form only");
   extern __shared__ __align__(16) unsigned char lb_lds[];
   constexpr int BN = 32 * NB;
@@ -174,7 +201,21 @@ __global__ __launch_bounds__(LB_NT, 2) void linear_bf16_kernel(std::conditional_
   const int lin = blockIdx.x;
   const int tl = lin >> 3, tile = (lin & 7) * g.tiles_per_xcd + tl;
   if (tl >= g.tiles_per_xcd || tile >= g.tiles) return;
-  const int rt = tile / g.col_tiles, ct = tile - rt * g.col_tiles;
+  // the origin of the tile's operands: the launch's own pointers, or (GROUPED) those of the tile's group — column tile fastest, then
+  // the group, then the row tile: the nb groups of one 128-row tile are adjacent on one XCD, so where they share their rows' cache
+  // lines (the forward: a row of XM holds every group's chunk) the lines come from memory once per L2.  The group index is a
+  // function of blockIdx alone: the three pointers are scalar registers, their offsets 64-bit.
+  int gtile = tile;
+  if constexpr (GROUPED) {
+    const int per = g.nb * g.col_tiles;
+    const int grt = tile / per, rem = tile - grt * per;
+    const int q = rem / g.col_tiles;
+    gtile = grt * g.col_tiles + (rem - q * g.col_tiles);               // the tile's index within its group's own matrix
+    g.x = reinterpret_cast<const uint16_t*>(reinterpret_cast<const float*>(g.x) + (long long)q * g.x_gs);
+    g.wp += (long long)q * g.wp_gs;
+    g.o32 += (long long)q * g.out_gs;
+  }
+  const int rt = gtile / g.col_tiles, ct = gtile - rt * g.col_tiles;
   const long long r0 = (long long)rt * LB_BM;
   const int n0 = ct * BN;
   unsigned char* abuf = lb_lds;                          // [2][128][144 B]
@@ -285,7 +326,8 @@ __global__ __launch_bounds__(LB_NT, 2) void linear_bf16_kernel(std::conditional_
       const int col = n0 + 32 * u + l31;
       if (has[u] && col < g.cout) {
         float cv;
-        if constexpr (F32A) cv = g.cs ? g.cs[col] : 0.f;               // (the fp32-A entry point only: no shift vector = zeros)
+        if constexpr (GROUPED) cv = 0.f;
+        else if constexpr (F32A) cv = g.cs ? g.cs[col] : 0.f;          // (the fp32-A entry point only: no shift vector = zeros)
         else cv = g.cs[col];
         const float av = scaled ? g.a[col] : 1.f;
 #pragma unroll
@@ -298,7 +340,9 @@ __global__ __launch_bounds__(LB_NT, 2) void linear_bf16_kernel(std::conditional_
       }
     }
   };
-  if (g.a) {                                                         // the mode tests once, not per element
+  if constexpr (GROUPED) {                                           // a pure product: no scale, no shift vector (acc + 0), no activation
+    affine(false, false);
+  } else if (g.a) {                                                  // the mode tests once, not per element
     if (g.act == 1) affine(true, true); else affine(true, false);
   } else {
     if (g.act == 1) affine(false, true); else affine(false, false);
@@ -313,13 +357,13 @@ __global__ __launch_bounds__(LB_NT, 2) void linear_bf16_kernel(std::conditional_
     if (row < g.R && col < g.cout) {
       float4 z0 = *reinterpret_cast<const float4*>(st + rl * SP + 8 * (it % NG));
       float4 z1 = *reinterpret_cast<const float4*>(st + rl * SP + 8 * (it % NG) + 4);
-      if (g.res) {
+      if (!GROUPED && g.res) {
         const float* rp = g.res + (size_t)row * g.ldr + col;
         const float4 q0 = *reinterpret_cast<const float4*>(rp), q1 = *reinterpret_cast<const float4*>(rp + 4);
         z0.x += q0.x; z0.y += q0.y; z0.z += q0.z; z0.w += q0.w;
         z1.x += q1.x; z1.y += q1.y; z1.z += q1.z; z1.w += q1.w;
       }
-      if (g.o32) {
+      if (GROUPED || g.o32) {
         float* op = g.o32 + (size_t)row * g.ldo32 + col;
         if (PREP && g.col_tiles > 1) {                               // another workgroup prepares these rows: write-through stores
           lb_store_wt(op, z0);
@@ -329,7 +373,7 @@ __global__ __launch_bounds__(LB_NT, 2) void linear_bf16_kernel(std::conditional_
           *reinterpret_cast<float4*>(op + 4) = z1;
         }
       }
-      if (g.o16)
+      if (!GROUPED && g.o16)
         *reinterpret_cast<uint4*>(g.o16 + (size_t)row * g.ldo16 + col) =
             make_uint4(lb_pack2<E>(z0.x, z0.y), lb_pack2<E>(z0.z, z0.w), lb_pack2<E>(z1.x, z1.y), lb_pack2<E>(z1.z, z1.w));
     }
@@ -377,15 +421,16 @@ __global__ __launch_bounds__(LB_NT, 2) void linear_bf16_kernel(std::conditional_
   }
 }
 
-template <int NB, bool PREP = false, bool F32A = false, LbElem E = LbElem::BF16, typename Args>
+template <int NB, bool PREP = false, bool F32A = false, LbElem E = LbElem::BF16, bool GROUPED = false, typename Args>
 static hipError_t lb_launch(const Args& g, hipStream_t st) {
+  static_assert(std::is_same_v<Args, lb_args_t<PREP, GROUPED>>, "the form's own argument struct");
   constexpr size_t lds = lb_lds_bytes(NB);
   if (lds > 64 * 1024) {
-    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_bf16_kernel<NB, PREP, F32A, E>),
+    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_bf16_kernel<NB, PREP, F32A, E, GROUPED>),
                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (ea != hipSuccess) return ea;
   }
-  hipLaunchKernelGGL((linear_bf16_kernel<NB, PREP, F32A, E>), dim3((unsigned)(g.tiles_per_xcd * 8)), dim3(LB_NT), lds, st, g);
+  hipLaunchKernelGGL((linear_bf16_kernel<NB, PREP, F32A, E, GROUPED>), dim3((unsigned)(g.tiles_per_xcd * 8)), dim3(LB_NT), lds, st, g);
   return hipGetLastError();
 }
 
@@ -508,6 +553,53 @@ extern "C" int gkg_linear_f16_f32a(const float* x, int ldx, const void* wplanes_
                                    void* stream) {
   return lb_f32a_call<LbElem::F16>("gkg_linear_f16_f32a", x, ldx, wplanes_f16, a, cshift, res, ldr, out_f32, ldo32, out_f16, ldo16, R, cin,
                                    cout, act, stream);
+}
+
+// ---------------------------------------------------------------------------------------------- fp32 A operand, nb groups (training)
+extern "C" int gkg_linear_bf16_f32a_grouped_supported(int R, int cin, int cout, int nb) {
+  if (nb < 1 || nb > 64 || !gkg_linear_bf16_f32a_supported(R, cin, cout, 0, 1, 0, 0)) return 0;
+  int ct;
+  return (long long)nb * lb_tiles(R, lb_co_pad(cout), 2, &ct) <= 0x3fffffffLL ? 1 : 0;
+}
+
+// One body for the two element kinds: `fn` names the entry point in the messages
+template <LbElem E>
+static int lb_grouped_call(const char* fn, const float* x, int ldx, long long x_gs, const void* wplanes, float* out, int ldo,
+                           long long out_gs, int R, int cin, int cout, int nb, void* stream) {
+  char msg[160];
+  auto fail = [&](int code, const char* what) { snprintf(msg, sizeof msg, "%s: %s", fn, what); return gkg_fail(code, msg); };
+  if (!x || !wplanes || !out) return fail(GKG_ERR_NULL, "null pointer");
+  if (R < 1 || cin <= 0 || cout <= 0 || x_gs < 0 || out_gs < 0)
+    return fail(GKG_ERR_SHAPE, "bad sizes (need R >= 1, cin, cout > 0, group strides >= 0)");
+  if (!gkg_linear_bf16_f32a_grouped_supported(R, cin, cout, nb))
+    return fail(GKG_ERR_UNSUPPORTED, "need cin % 8 == 0, cout % 8 == 0, 1 <= nb <= 64 and a grid that fits");
+  if ((ldx & 3) || (ldo & 3) || (x_gs & 3) || (out_gs & 3))
+    return fail(GKG_ERR_UNSUPPORTED, "need ldx % 4 == 0, ldo % 4 == 0, x_gs % 4 == 0, out_gs % 4 == 0");
+  if (((uintptr_t)x | (uintptr_t)wplanes | (uintptr_t)out) & 15) return fail(GKG_ERR_UNSUPPORTED, "x, wplanes and out must be 16-byte aligned");
+  if (ldx < cin || ldo < cout) return fail(GKG_ERR_SHAPE, "a row pitch is below the row's width");
+  LinBf16GroupedArgs g;
+  lb_fill(g, x, ldx, wplanes, nullptr, nullptr, nullptr, 0, out, ldo, nullptr, 0, R, cin, cout, 0, 2);
+  g.x_gs = x_gs; g.out_gs = out_gs; g.nb = nb;
+  g.wp_gs = (long long)(gkg_linear_bf16_planes_bytes(cin, cout) / sizeof(uint4));
+  const long long tiles = (long long)g.tiles * nb;                      // row tiles x nb x column tiles
+  g.tiles = (int)tiles;
+  g.tiles_per_xcd = (int)((tiles + 7) / 8);
+  const hipError_t e = lb_launch<2, false, true, E, true>(g, (hipStream_t)stream);
+  return e == hipSuccess ? 0 : gkg_fail_hip(e, E == LbElem::F16 ? "linear_bf16_kernel (grouped, fp16 operands)" : "linear_bf16_kernel (grouped)");
+}
+
+extern "C" int gkg_linear_bf16_f32a_grouped(const float* x, int ldx, long long x_gs, const void* wplanes, float* out, int ldo,
+                                            long long out_gs, int R, int cin, int cout, int nb, void* stream) {
+  return lb_grouped_call<LbElem::BF16>("gkg_linear_bf16_f32a_grouped", x, ldx, x_gs, wplanes, out, ldo, out_gs, R, cin, cout, nb, stream);
+}
+
+extern "C" int gkg_linear_f16_f32a_grouped_supported(int R, int cin, int cout, int nb) {
+  return gkg_linear_bf16_f32a_grouped_supported(R, cin, cout, nb);
+}
+
+extern "C" int gkg_linear_f16_f32a_grouped(const float* x, int ldx, long long x_gs, const void* wplanes, float* out, int ldo,
+                                           long long out_gs, int R, int cin, int cout, int nb, void* stream) {
+  return lb_grouped_call<LbElem::F16>("gkg_linear_f16_f32a_grouped", x, ldx, x_gs, wplanes, out, ldo, out_gs, R, cin, cout, nb, stream);
 }
 
 // ---------------------------------------------------------------------------------------------- fc1 + the k-NN's token preparation

@@ -1,6 +1,6 @@
 """Tensors derived from a layer's parameters and kept between calls — the bf16 weight copy, the BN-folded weight and shifts, the
 fragment arrays of the own 16-bit kernels (one builder, ``_fragments``; a projection's four slots behind one ``lin_planes(conv, kind,
-transposed)``, the kind a row of linear_bf16.KINDS), an eval-mode BN's (a, c) — under ONE staleness protocol (``get``), and the
+transposed)``, the kind a row of linear_bf16.KINDS; a grouped projection's four behind ``glin_planes``), an eval-mode BN's (a, c) — under ONE staleness protocol (``get``), and the
 builders of those values.  Mechanism only: which layer takes which of them is decided in ``fused.py``.  The store lives here,
 keyed weakly on the owning module: nothing is attached to the module, so deepcopy and pickling do not carry it.  (The x6 weight
 planes are not here: planes._WeightPlanes is per device, refreshes in batches and has its own capture rules.)"""
@@ -105,6 +105,30 @@ def lin_planes(conv, kind="bf16", transposed=False) -> torch.Tensor:
     return _fragments_slot(conv, kind.slots[transposed],
                            lambda w: w.reshape(w.shape[0], -1).t() if transposed else w.reshape(w.shape[0], -1),
                            lambda lib, n, k: getattr(lib, kind.planes_bytes)(k, n), kind.fragment)
+
+
+def kperm_weight(Wg: torch.Tensor) -> torch.Tensor:
+    """(nb, co, ci) grouped weight with its input columns as [even | odd]: the order an XM operand buffer presents them in (the x
+    chunk, then the m chunk).  (``fused._kperm_weight`` is this function.)"""
+    nb, co, ci = Wg.shape
+    return Wg.view(nb, co, ci // 2, 2).permute(0, 1, 3, 2).reshape(nb, co, ci)
+
+
+def glin_planes(conv, kind="bf16", transposed=False) -> torch.Tensor:
+    """The GROUPED projection's weight (nb co, ci, 1, 1), nb = conv.groups, as the stacked fragment array the ``*_f32a_grouped`` entry
+    points stream: [nb][..] — nb arrays of lin_planes' layout back to back, of Wp[q] (co, ci) = kperm_weight(Wg)[q] for the forward
+    (contraction columns in XM order) or, ``transposed``, of Wp[q]^T (ci, co) for the input gradient (output columns in XM order).
+    ``kind`` as in lin_planes; the slots are the row's ``gslots``, the size the library's: nb x planes_bytes (asked for the widths
+    rounded up to the kernels' granule of 8, which pads the same: a width the kernels refuse still has its array)."""
+    if isinstance(kind, str):
+        kind = linear_bf16.KINDS[kind]
+    nb = conv.groups
+
+    def mat(w):
+        Wp = kperm_weight(w.reshape(nb, w.shape[0] // nb, -1))
+        return Wp.transpose(1, 2) if transposed else Wp
+    return _fragments_slot(conv, kind.gslots[transposed], mat,
+                           lambda lib, n, k: nb * getattr(lib, kind.planes_bytes)(_up(k, 8), _up(n, 8)), kind.fragment)
 
 
 def mr_planes(conv) -> torch.Tensor:

@@ -105,6 +105,14 @@ DETERMINISTIC = os.environ.get("GKG_DETERMINISTIC", "0") != "0"
 #                  under GKG_DETERMINISTIC.  fp16 autocast with gradients only; bf16 autocast, fp32, fp16 inference, the grouped
 #                  projection and the BN passes keep their paths.  May be on together with train_bf16: each acts under its own
 #                  autocast dtype.  Opt-in: per-layer measurements in EXPERIMENTS.md.
+#   train_grouped  an add-on to train_bf16 / train_f16 (alone it does nothing): the GROUPED projection between a Grapher's dense
+#                  layers (BasicConv's Conv2d 1x1, groups = 4, behind the max-relative aggregation) takes its forward Y_q = XM_q W_q^T
+#                  and its input gradient dXM_q = dY_q W_q from ONE launch each of the own kernel's grouped form
+#                  (gkg_linear_bf16_f32a_grouped / gkg_linear_f16_f32a_grouped; linear_bf16.py) under the kind's autocast dtype —
+#                  instead of the autocast vendor bmm on a gathered 16-bit copy of the strided operand view with its widening pass,
+#                  and the fp32 vendor bmm with its re-layout copy.  Nothing atomic: holds under GKG_DETERMINISTIC for both kinds.
+#                  The grouped weight gradient, the BN passes, the block driver and XM_DIRECT keep their paths.  With it off every
+#                  launch of every other switch combination is what it was.  Opt-in: per-layer measurements in EXPERIMENTS.md.
 #   wgrad_det     with GKG_DETERMINISTIC=1 and GKG_GEMM_MATH=x6 only: the projections' weight gradients stay on the library's x6
 #                  kernels in their run-independent form (gkg_linear_wgrad_x6_det / _batch_det: the row slabs' partial tiles go to
 #                  a workspace and are added in slab order; no atomics, no cleared slot) instead of the vendor batched GEMM + sum —
@@ -137,6 +145,7 @@ FFN_BF16 = "ffn_bf16" in _ENABLED          # likewise; acts only together with L
 MR_FC2_BF16 = "all" if "mr_fc2_bf16_all" in _ENABLED else ("mr_fc2_bf16" in _ENABLED)
 TRAIN_BF16 = "train_bf16" in _ENABLED      # likewise a module constant the tests flip
 TRAIN_F16 = "train_f16" in _ENABLED        # likewise
+TRAIN_GROUPED = "train_grouped" in _ENABLED    # likewise; acts only together with TRAIN_BF16 / TRAIN_F16, each under its own autocast dtype
 WGRAD_DET = "wgrad_det" in _ENABLED        # likewise; acts only together with DETERMINISTIC and GEMM_MATH == "x6"
 
 
@@ -299,9 +308,9 @@ def _wgrad(dY: torch.Tensor, x: torch.Tensor, out=None) -> torch.Tensor:
 
 def _kperm_weight(Wg: torch.Tensor) -> torch.Tensor:
     """(nb, co, ci) weight with its input columns as [even | odd]: the order an XM operand buffer presents them in (the x
-    chunk, then the m chunk) — for the GEMM paths that read the weight tensor itself rather than its x6 planes."""
-    nb, co, ci = Wg.shape
-    return Wg.view(nb, co, ci // 2, 2).permute(0, 1, 3, 2).reshape(nb, co, ci)
+    chunk, then the m chunk) — for the GEMM paths that read the weight tensor itself rather than its x6 planes (and, through
+    derived.glin_planes, for the fragment arrays of the own grouped 16-bit products)."""
+    return derived.kperm_weight(Wg)
 
 
 def _kperm_grad_back(dWp: torch.Tensor, out=None) -> torch.Tensor:
@@ -459,6 +468,8 @@ from .linear_bf16 import ffn_bf16_ok, ffn_bf16_eval      # noqa: E402,F401  (GKG
 from .linear_bf16 import mr_fc2_bf16_ok, mr_fc2_bf16_eval      # noqa: E402,F401  (GKG_ENABLE=lin_bf16,mr_fc2_bf16)
 from .linear_bf16 import (BF16, F16, train16_ok, train16_fwd,      # noqa: E402,F401  (GKG_ENABLE=train_bf16 / train_f16)
                           train16_dgrad, linear_bf16_wgrad)
+from .linear_bf16 import (train16_grouped_ok, train16_grouped_fwd,      # noqa: E402,F401  (GKG_ENABLE=train_grouped beside them)
+                          train16_grouped_dgrad)
 from .layout import _tm_dtype, _TokenMajorToCL, _ToTokenMajor, _BlockEntry, _AvgPoolTM      # noqa: E402  (layout Functions: layout.py)
 
 
@@ -921,10 +932,12 @@ class _GroupedLinearBNAct(torch.autograd.Function):
     """The reference's BasicConv: Conv2d(1x1, groups=4) + BN + act on the interleaved [x, m] channels (torch_nn.py:57-69 behind
     torch_vertex.py:57-61), reading the XM operand buffer (R, 4 ci) instead of an interleaved tensor: group q's ci inputs are
     the contiguous columns [q ci, (q+1) ci) = [x chunk | m chunk]; the weight's input columns are taken in that order (x6 planes
-    built with kperm, or _kperm_weight for the library paths).  -> out (R, 4 co) token-major (column q co + j)."""
+    built with kperm, or _kperm_weight for the library paths).  -> out (R, 4 co) token-major (column q co + j).  ``t16``: the
+    caller's _train_grouped_16bit decision, (kind, conv) or None — the product and the input gradient on the own grouped 16-bit kernel
+    (taken where the x6 kernels refuse: under autocast)."""
 
     @staticmethod
-    def forward(ctx, XM, weight, bias, gamma, beta, bn, act, out_lowp=False, w16=None):
+    def forward(ctx, XM, weight, bias, gamma, beta, bn, act, out_lowp=False, w16=None, t16=None):
         lib = _lib.load()
         nb = 4
         R, ci = XM.shape[0], XM.shape[1] // nb
@@ -950,7 +963,9 @@ class _GroupedLinearBNAct(torch.autograd.Function):
         elif own:
             Y, a, c, mean, invstd = _linear_fwd_own(lib, U, pf, (R, ci, co, nb), bias, bn)
         else:
-            if XM.dtype == torch.bfloat16:
+            if t16 is not None:                                     # GKG_ENABLE=train_grouped: one launch, no gathered copy, fp32 Y
+                Y = train16_grouped_fwd(t16[0], XM, t16[1])         # (nb, R, co)
+            elif XM.dtype == torch.bfloat16:
                 Wb = weight.to(torch.bfloat16) if w16 is None else w16
                 Y = torch.bmm(U, _kperm_weight(Wb.view(nb, co, ci)).transpose(1, 2), out_dtype=_F32)
             else:
@@ -966,6 +981,7 @@ class _GroupedLinearBNAct(torch.autograd.Function):
         ctx.bn = (act, nb, co, R, sync) + ((bn, bias) if mean is None else ())
         ctx.gparams = (weight, gamma, beta)
         ctx.pd = pd
+        ctx.t16 = t16                                               # (the backward runs outside autocast: the decision is the forward's)
         ctx.link = _bn_link(out, state, ctx.bn, None)
         return out
 
@@ -989,10 +1005,12 @@ class _GroupedLinearBNAct(torch.autograd.Function):
         elif ctx.pd is not None:                                    # dXM (R, 4 ci) written in place: [direct chunk | dm chunk] per group
             dXM = torch.empty((R, nb * ci), dtype=_F32, device=dY.device)
             _dgrad_x6(lib, dY, co, R * co, ctx.pd, dXM, R, ci, co, nb, ldx=nb * ci, x_bs=ci)
+        elif ctx.t16 is not None:                                   # dXM written in place by the own grouped kernel: no re-layout copy
+            dXM = train16_grouped_dgrad(ctx.t16[0], dY, ctx.t16[1])
         else:
             dXM = torch.bmm(dY, _kperm_weight(Wg)).permute(1, 0, 2).reshape(R, nb * ci)
         dW = _wgrad_grouped(dY, XM.view(R, nb, ci).permute(1, 0, 2), dWv, kperm=1).view_as(weight)
-        return dXM, dW, dbias, dgamma, dbeta, None, None, None, None
+        return dXM, dW, dbias, dgamma, dbeta, None, None, None, None, None
 
 
 # ----------------------------------------------------------------------------------------------- BN (+ act) behind a library conv
@@ -1415,7 +1433,7 @@ def _aggregate_project(x1b, yb, nn_idx, groups, nn_, C, lp):
         return mr_grouped_linear_eval(x1b, yb, nn_idx, groups, nn_[0], nn_[1])
     XM = _MaxRelativeTM.apply(x1b, yb, nn_idx, groups, 1, lp)       # (T, 2C) operand buffer [x | m]
     return _GroupedLinearBNAct.apply(XM, nn_[0].weight, nn_[0].bias, nn_[1].weight, nn_[1].bias, nn_[1], 1, lp,
-                                     derived.w16(nn_[0]) if lp else None)   # (T, 2C)
+                                     derived.w16(nn_[0]) if lp else None, _train_grouped_16bit(XM, nn_[0], nn_[1]))   # (T, 2C)
 
 
 # ----------------------------------------------------------------------------------------------- row g1 (inference)
@@ -1492,6 +1510,19 @@ def _train_16bit(x, conv, bn):
     return None
 
 
+def _train_grouped_16bit(XM, conv, bn):
+    """Which own GROUPED 16-bit products _GroupedLinearBNAct takes for this layer, as (kind, conv), or None: GKG_ENABLE=train_grouped
+    acts only beside the kind's own switch (train_bf16 under bf16 autocast, train_f16 under fp16 autocast), and the predicate
+    (linear_bf16.train16_grouped_ok) holds.  Asked by the callers (_graph_and_project, _aggregate_project), where the gradient mode
+    and the autocast state are still visible.  GKG_DETERMINISTIC is not asked: these two products add nothing atomically."""
+    if not TRAIN_GROUPED:
+        return None
+    for kind, on in ((BF16, TRAIN_BF16), (F16, TRAIN_F16)):
+        if train16_grouped_ok(kind, on, XM, conv, bn):
+            return kind, conv
+    return None
+
+
 def _lin(x, seq, act=0, residual=None, nchw=None, out_lowp=False, scale=None, rows_per_scale=0, want16=False, alias=False,
          dual=False, xm=None, knn=None, chain=False):
     """``scale`` (one factor per image; token-major outputs: per ``rows_per_scale`` consecutive rows) multiplies the BN
@@ -1563,7 +1594,8 @@ def _graph_and_project(x1b, yb, relative_pos, gc, groups, C, lp, want_edge):
     N = x1b.shape[1]
     if _knn_mr_ok(x1b, yb, relative_pos, gc.k, gc.d, groups, nn_, lp):      # row g2: graph + aggregation in one kernel
         XM, edge = _KnnMaxRelativeTM.apply(x1b, yb, relative_pos, gc.k, gc.d, groups, want_edge)
-        a2 = _GroupedLinearBNAct.apply(XM, nn_[0].weight, nn_[0].bias, nn_[1].weight, nn_[1].bias, nn_[1], 1, False, None)
+        a2 = _GroupedLinearBNAct.apply(XM, nn_[0].weight, nn_[0].bias, nn_[1].weight, nn_[1].bias, nn_[1], 1, False, None,
+                                       _train_grouped_16bit(XM, nn_[0], nn_[1]))
         return a2, (edge if want_edge else None)
     nn_idx, edge = _graph_lists(x1b, yb, relative_pos, gc, groups, want_edge)
     return _aggregate_project(x1b, yb, nn_idx, groups, nn_, C, lp), edge       # row g1: aggregation = the projection's operand producer

@@ -6,8 +6,10 @@ fc1) — and an FFN's two projections as one launch with the hidden matrix kept 
 operand for a layer's forward and input gradient, in bf16 (gkg_linear_bf16_f32a) or IEEE fp16 (gkg_linear_f16_f32a).  What differs
 between the two element kinds is one row each of ``KINDS`` (autocast dtype, entry-point names, fragment dtype, derived's two slots,
 ``own_wgrad``); the predicate and the two products (train16_ok, train16_fwd, train16_dgrad) are written once against it, and the bf16
-weight-gradient kernel (gkg_linear_wgrad_bf16, linear_bf16_wgrad) is the one thing only bf16 has.  Mechanism only: the
-switches (``fused.LIN_BF16``, ``fused.LIN_BF16_PREP``, ``fused.FFN_BF16``, ``fused.MR_FC2_BF16``, ``fused.TRAIN_BF16``, ``fused.TRAIN_F16``) and the mode test (``fused.lowp_inference``) stay in
+weight-gradient kernel (gkg_linear_wgrad_bf16, linear_bf16_wgrad) is the one thing only bf16 has.  With GKG_ENABLE=train_grouped beside
+either switch the GROUPED projection between a Grapher's dense layers takes its forward and input gradient from the kernel's grouped
+form, again written once against the row (train16_grouped_ok, train16_grouped_fwd, train16_grouped_dgrad).  Mechanism only: the
+switches (``fused.LIN_BF16``, ``fused.LIN_BF16_PREP``, ``fused.FFN_BF16``, ``fused.MR_FC2_BF16``, ``fused.TRAIN_BF16``, ``fused.TRAIN_F16``, ``fused.TRAIN_GROUPED``) and the mode test (``fused.lowp_inference``) stay in
 ``fused.py`` and arrive as arguments."""
 from __future__ import annotations
 
@@ -315,12 +317,17 @@ class Kind16(NamedTuple):
     fragment: torch.dtype            # element type of the fragment arrays
     slots: tuple                     # derived's cache slots of the weight's fragments: (as it is, transposed)
     own_wgrad: bool                  # a weight-gradient kernel of its own (linear_bf16_wgrad): atomics, not under GKG_DETERMINISTIC
+    f32a_grouped: str                # the grouped projection (GKG_ENABLE=train_grouped): nb products in one launch,
+    f32a_grouped_supported: str      # its envelope
+    gslots: tuple                    # derived's cache slots of the grouped weight's stacked fragments: (as it is, transposed)
 
 
 BF16 = Kind16("bf16", torch.bfloat16, "gkg_linear_bf16_f32a", "gkg_linear_bf16_f32a_supported", "gkg_linear_bf16_planes_bytes",
-              torch.bfloat16, ("lin_planes", "lin_planes_t"), True)
+              torch.bfloat16, ("lin_planes", "lin_planes_t"), True,
+              "gkg_linear_bf16_f32a_grouped", "gkg_linear_bf16_f32a_grouped_supported", ("glin_planes", "glin_planes_t"))
 F16 = Kind16("f16", torch.float16, "gkg_linear_f16_f32a", "gkg_linear_f16_f32a_supported", "gkg_linear_f16_planes_bytes",
-             torch.float16, ("lin_planes_f16", "lin_planes_t_f16"), False)
+             torch.float16, ("lin_planes_f16", "lin_planes_t_f16"), False,
+             "gkg_linear_f16_f32a_grouped", "gkg_linear_f16_f32a_grouped_supported", ("glin_planes_f16", "glin_planes_t_f16"))
 KINDS = {k.name: k for k in (BF16, F16)}
 
 
@@ -382,6 +389,65 @@ def train16_dgrad(kind, dY, conv, residual=None):
     if residual is not None:
         assert residual.dtype == _F32 and tuple(residual.shape) == (dY.shape[0], cin)
     return _f32a(kind, dY, derived.lin_planes(conv, kind, transposed=True), residual, dY.shape[0], cout, cin, "input gradient")
+
+
+# ---- the GROUPED projection of a Grapher under the same switches plus GKG_ENABLE=train_grouped (``fused.TRAIN_GROUPED``) --------------
+# BasicConv's Conv2d(2C -> 2C, 1x1, groups = 4) behind the max-relative aggregation (reference torch_nn.py:57-69 behind
+# torch_vertex.py:57-61), reading the XM operand buffer (R, 4 ci): forward and input gradient are ONE launch each of the kind's
+# ``*_f32a_grouped`` entry point — no strided gather into a 16-bit copy, no vendor GEMM, no widening pass, no re-layout of dXM.  The
+# column permutation (XM's [x chunk | m chunk] order) lives in the cached fragment arrays (derived.glin_planes).  Neither product adds
+# atomically, so neither ``own_wgrad`` nor GKG_DETERMINISTIC is asked; the grouped weight gradient stays where _wgrad_grouped puts it.
+GROUPS = 4
+
+
+def train16_grouped_ok(kind, on, XM, conv, bn, supported=None) -> bool:
+    """Whether ``fused._GroupedLinearBNAct`` takes its product from train16_grouped_fwd and its input gradient from
+    train16_grouped_dgrad: ``on`` (the kind's own switch AND ``fused.TRAIN_GROUPED``: the caller's conjunction), gradients on, the
+    kind's autocast dtype, an fp32 CUDA operand buffer XM (R, 4 ci) with unit column stride, a groups = 4 1x1 weight (4 co, ci, 1, 1)
+    over exactly those columns, and the library's answers for both products (``supported(R, cin, cout, nb)`` stands in for them in
+    tests).  ``bn`` takes no part: the BN passes behind the product are the caller's, unchanged."""
+    if not on or not torch.is_grad_enabled():
+        return False
+    if not torch.is_autocast_enabled() or torch.get_autocast_dtype("cuda") != kind.autocast:
+        return False
+    if XM.dtype != _F32 or not XM.is_cuda or len(XM.shape) != 2 or XM.stride(1) != 1:
+        return False
+    wshape = tuple(conv.weight.shape)
+    if conv.groups != GROUPS or len(wshape) != 4 or wshape[2:] != (1, 1) or wshape[0] % GROUPS or wshape[1] * GROUPS != XM.shape[1]:
+        return False
+    R, ci, co = XM.shape[0], wshape[1], wshape[0] // GROUPS
+    if supported is None:
+        supported = getattr(_lib.load(), kind.f32a_grouped_supported)
+    return bool(supported(R, ci, co, GROUPS) and supported(R, co, ci, GROUPS))
+
+
+def _f32a_grouped(kind, x, ldx, x_gs, planes, out, ldo, out_gs, R, cin, cout, what):
+    _lib.check(getattr(_lib.load(), kind.f32a_grouped)(_ptr(x), ldx, x_gs, _ptr(planes), _ptr(out), ldo, out_gs, R, cin, cout, GROUPS,
+                                                       _stream()), "%s (%s)" % (kind.f32a_grouped, what))
+    return out
+
+
+@torch.no_grad()
+def train16_grouped_fwd(kind, XM, conv):
+    """XM (R, 4 ci) fp32, group q's operand its columns [q ci, (q + 1) ci) = [x chunk | m chunk] -> Y (4, R, co) fp32 stacked,
+    Y_q = kind(XM_q) kind(Wp_q)^T with Wp = fused._kperm_weight(Wg): the pre-BN matrices (the conv bias stays in the BN passes)."""
+    assert XM.dtype == _F32 and XM.dim() == 2
+    XM = _rows(XM, 4)
+    R, ci, co = XM.shape[0], XM.shape[1] // GROUPS, conv.weight.shape[0] // GROUPS
+    Y = torch.empty((GROUPS, R, co), dtype=_F32, device=XM.device)
+    return _f32a_grouped(kind, XM, XM.stride(0), ci, derived.glin_planes(conv, kind), Y, co, R * co, R, ci, co, "forward")
+
+
+@torch.no_grad()
+def train16_grouped_dgrad(kind, dY, conv):
+    """dY (4, R, co) fp32 stacked -> dXM (R, 4 ci) fp32 written in place, dXM_q = kind(dY_q) kind(Wp_q): columns in XM order."""
+    assert dY.dtype == _F32 and dY.dim() == 3 and dY.shape[0] == GROUPS
+    dY = dY.contiguous()
+    R, co, ci = dY.shape[1], dY.shape[2], conv.weight.shape[1]
+    assert co * GROUPS == conv.weight.shape[0]
+    dXM = torch.empty((R, GROUPS * ci), dtype=_F32, device=dY.device)
+    return _f32a_grouped(kind, dY, co, R * co, derived.glin_planes(conv, kind, transposed=True), dXM, GROUPS * ci, ci, R, co, ci,
+                         "input gradient")
 
 
 @torch.no_grad()

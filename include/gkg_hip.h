@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define GKG_ABI_VERSION 21
+#define GKG_ABI_VERSION 22
 
 /* dtype codes */
 #define GKG_F32 0
@@ -578,6 +578,46 @@ int gkg_linear_f16_f32a(const float* x /* fp32 (R, ldx) */, int ldx, const void*
                         float* out_f32 /* (R, ldo32) or NULL */, int ldo32,
                         void* out_f16 /* (R, ldo16) or NULL */, int ldo16,
                         int R, int cin, int cout, int act /* 0 none, 1 GELU */, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Training under 16-bit autocast, the GROUPED projection (opt-in GKG_ENABLE=train_grouped beside train_bf16 / train_f16): the forward
+ * and the input gradient of BasicConv's Conv2d(2C -> 2C, 1x1, groups = 4) behind the max-relative aggregation (reference
+ * torch_nn.py:57-69 behind torch_vertex.py:57-61) as ONE launch of the kernel above with a group dimension.
+ *
+ * gkg_linear_bf16_f32a_grouped / gkg_linear_f16_f32a_grouped: nb independent products
+ *     out_q (R, cout) fp32 = kind(x_q) (R, cin) . kind(W_q)^T,   q = 0 .. nb - 1,   cin and cout PER GROUP,
+ * group q's operands being x + q x_gs (row pitch ldx) and out + q out_gs (row pitch ldo), strides and pitches in floats, and the
+ * q-th of nb fragment arrays that lie back to back in wplanes, each in gkg_linear_bf16's layout ([ci_pad/8][co_pad][8], fragment
+ * (f, n) = W_q[n][8f .. 8f+7], zero outside cin / cout) and gkg_linear_bf16_planes_bytes(cin, cout) bytes long (fp16 elements for the
+ * f16 entry point: gkg_linear_f16_planes_bytes, the same number).
+ * BIT CONTRACT: group q's output is bit for bit what gkg_linear_bf16_f32a / gkg_linear_f16_f32a writes when called on group q's
+ * views — x + q x_gs with ldx, wplanes + q planes_bytes, out + q out_gs with ldo, a = cshift = res = NULL, act = 0, the fp32 output
+ * only — i.e. the same rounding of x on its way into LDS, the same contraction order (ascending steps of 16, no K-split, the
+ * 64-column tile form) and store path.  Nothing outside rows [0, R) x columns [0, cin) of a group's x is read, nothing outside rows
+ * [0, R) x columns [0, cout) of a group's out is written (pitch slack and the other groups' columns stay untouched); the CALLER
+ * keeps the groups' output regions disjoint (they are written concurrently, in no order).  Workgroups are independent: no atomics,
+ * no counters, run-independent bits.  The two layouts the library's own caller uses (XM (R, nb ci) the [x | m] operand buffer, Wg
+ * (nb, co, ci) the grouped weight, Wp = its input columns in XM order [x chunk | m chunk]: fused._kperm_weight):
+ *     product                            x                  ldx, x_gs     planes of                 out                  ldo, out_gs
+ *     forward         Y_q = XM_q Wp_q^T    XM (R, nb ci)      nb ci, ci     Wp[q]   (co, ci)          Y (nb, R, co) stacked  co, R co
+ *     input gradient  dXM_q = dY_q Wp_q    dY (nb, R, co)     co, R co      Wp[q]^T (ci, co)          dXM (R, nb ci) in place nb ci, ci
+ * The column permutation lives in the fragment arrays, as it lives in the x6 planes (kperm): contraction columns in XM order for the
+ * forward, output columns in XM order for the input gradient; no interleave and no re-layout copy exists at run time.
+ * Preconditions, otherwise GKG_ERR_UNSUPPORTED with nothing launched: cin % 8 == 0, cout % 8 == 0 (each <= 2^24); ldx, ldo, x_gs,
+ * out_gs multiples of 4; x, wplanes, out 16-byte aligned; 1 <= nb <= 64; nb x (row tiles x column tiles) <= 0x3fffffff.  R, cin or
+ * cout <= 0, a negative group stride, ldx < cin or ldo < cout are GKG_ERR_SHAPE; a null pointer is GKG_ERR_NULL.
+ * gkg_linear_bf16_f32a_grouped_supported: 1 when the sizes pass (pure host code; pitches, strides and pointers are the call's to
+ * check); gkg_linear_f16_f32a_grouped_supported: the bf16 answer. */
+int gkg_linear_bf16_f32a_grouped_supported(int R, int cin, int cout, int nb);
+int gkg_linear_bf16_f32a_grouped(const float* x /* fp32, group q at x + q x_gs, (R, ldx) */, int ldx, long long x_gs,
+                                 const void* wplanes /* nb fragment arrays back to back */,
+                                 float* out /* fp32, group q at out + q out_gs, (R, ldo) */, int ldo, long long out_gs,
+                                 int R, int cin, int cout, int nb, void* stream);
+int gkg_linear_f16_f32a_grouped_supported(int R, int cin, int cout, int nb);
+int gkg_linear_f16_f32a_grouped(const float* x /* fp32, group q at x + q x_gs, (R, ldx) */, int ldx, long long x_gs,
+                                const void* wplanes /* nb fragment arrays back to back */,
+                                float* out /* fp32, group q at out + q out_gs, (R, ldo) */, int ldo, long long out_gs,
+                                int R, int cin, int cout, int nb, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Bandwidth kernels between the dense 1x1 projections (Conv2d 1x1 + SyncBN [+ GELU], reference

@@ -54,7 +54,16 @@ Same alternation, hipGraph replays and cache sweep.
     fwd     gkg_linear_f16_f32a (fp32 x, fp32 Y)             vs  fused._mm_t under fp16 autocast (two casts + vendor GEMM + cast back)
     dgrad   gkg_linear_f16_f32a (fp32 dY, fragments of W^T)   vs  torch.mm(dY, W) in fp32
 
-(the weight gradient keeps its path with that switch).  --amp bf16 is the default: --train alone prints what it always did."""
+(the weight gradient keeps its path with that switch).  --amp bf16 is the default: --train alone prints what it always did.
+
+--train --grouped [--amp bf16|f16]: the two products GKG_ENABLE=train_grouped moves beside the kind's own switch, at the GROUPED
+projection (Conv2d 2C -> 2C, groups = 4: nb = 4, per-group ci = co = C / 2, XM pitch 2C) of the same four stage shapes:
+
+    fwd     gkg_linear_{bf16,f16}_f32a_grouped (XM in place, Y (4, R, co) fp32)   vs  the autocast torch.bmm on the strided (4, R, ci)
+                                                                                     view of XM, its casts and .float() included
+    dgrad   gkg_linear_{bf16,f16}_f32a_grouped (dY stacked, dXM written in place)  vs  torch.bmm(dY, W) in fp32 + permute().reshape()
+
+Same alternation, hipGraph replays and cache sweep."""
 import argparse
 import json
 import os
@@ -383,8 +392,72 @@ def train_leg(args, lib, flush, kind):
     return rows
 
 
+def grouped_leg(args, lib, flush, kind):
+    """--train --grouped: the two products GKG_ENABLE=train_grouped moves (beside the kind's own switch) at the grouped projection of
+    the four cfg4 stage shapes (nb = 4, per-group ci = co = C / 2, XM pitch 2C), each against what it replaces in
+    ``fused._GroupedLinearBNAct`` on the parent: the autocast bmm on the strided (4, R, ci) view of XM with its casts and .float(), and
+    the fp32 bmm + permute().reshape()."""
+    from gkgnet_amd import derived, fused
+    B = args.batch or 32
+    widths = {int(t) for t in args.widths.split(",")}
+    rows = []
+    for C, side in ((80, 144), (160, 72), (400, 36), (640, 18)):
+        if C not in widths:
+            continue
+        R, nb, ci = B * side * side, 4, C // 2
+        co = ci
+        gen = torch.Generator(device="cuda").manual_seed(C * 7 + 1)
+        conv = torch.nn.Conv2d(2 * C, 2 * C, 1, groups=nb).cuda()
+        XM = torch.randn(R, nb * ci, device="cuda", generator=gen)
+        dY = torch.randn(nb, R, co, device="cuda", generator=gen)
+        Wg = conv.weight.detach().view(nb, co, ci)
+        U = XM.view(R, nb, ci).permute(1, 0, 2)
+        assert getattr(lib, kind.f32a_grouped_supported)(R, ci, co, nb)
+        derived.glin_planes(conv, kind), derived.glin_planes(conv, kind, transposed=True)      # built once, as in a training step
+        V = {}
+
+        def fwd_own():
+            V["Y_own"] = linear_bf16.train16_grouped_fwd(kind, XM, conv)
+
+        def fwd_old():
+            with torch.autocast("cuda", dtype=kind.autocast):
+                Y = torch.bmm(U, fused._kperm_weight(Wg).transpose(1, 2))
+            V["Y"] = Y.float()
+
+        def dgrad_own():
+            V["dXM_own"] = linear_bf16.train16_grouped_dgrad(kind, dY, conv)
+
+        def dgrad_old():
+            V["dXM"] = torch.bmm(dY, fused._kperm_weight(Wg)).permute(1, 0, 2).reshape(R, nb * ci)
+        legs = (("fwd", fwd_own, fwd_old), ("dgrad", dgrad_own, dgrad_old))
+        graphs = [(capture(a), capture(b)) for _, a, b in legs]
+        t = [([], []) for _ in legs]
+        for _ in range(args.reps):                                               # alternate all of them
+            for i, (ga, gb) in enumerate(graphs):
+                t[i][0].append(1e3 * replay_ms(ga, flush))
+                t[i][1].append(1e3 * replay_ms(gb, flush))
+        # the two sides agree to the kind's resolution: a sanity check of the comparison, not a test
+        diffs = [((a - b).abs().max() / b.abs().max()).item() for a, b in ((V["Y_own"], V["Y"]), (V["dXM_own"], V["dXM"]))]
+        row = dict(layer="grouped", C=C, R=R, nb=nb, ci=ci, co=co, ldxm=nb * ci)
+        msg = f"C={C:4d} grouped R={R:6d} {nb} x ({ci:3d}->{co:3d}):"
+        for (leg, _, _), (to, tv), d in zip(legs, t, diffs):
+            uo, uv = statistics.median(to), statistics.median(tv)
+            row.update({f"{leg}_own_us": round(uo, 1), f"{leg}_old_us": round(uv, 1), f"{leg}_own_us_min": round(min(to), 1),
+                        f"{leg}_own_us_max": round(max(to), 1), f"{leg}_old_us_min": round(min(tv), 1),
+                        f"{leg}_old_us_max": round(max(tv), 1), f"{leg}_own_tflops": round(2.0 * R * nb * ci * co / uo * 1e-6, 1),
+                        f"{leg}_own_GBps": round((R * nb * (ci + co) * 4) / uo * 1e-3, 0),
+                        f"{leg}_max_rel_diff": float(f"{d:.3e}"), f"{leg}_winner": "own" if uo < uv else "old"})
+            msg += f"  {leg} own {uo:7.1f} [{min(to):.1f}, {max(to):.1f}] old {uv:7.1f} [{min(tv):.1f}, {max(tv):.1f}] us -> {row[leg + '_winner']}"
+        rows.append(row)
+        print(msg + "  (max rel diff " + " ".join(f"{d:.1e}" for d in diffs) + ")", flush=True)
+        del XM, dY, V, graphs
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--grouped", action="store_true",
+                    help="with --train: the grouped projection's forward and input gradient (GKG_ENABLE=train_grouped beside train_bf16 / train_f16) at the cfg4 shapes")
     ap.add_argument("--amp", default="bf16", choices=("bf16", "f16"),
                     help="with --train: the autocast dtype — bf16 (GKG_ENABLE=train_bf16, three products) or f16 (GKG_ENABLE=train_f16: forward and input gradient)")
     ap.add_argument("--train", action="store_true", help="run the three training products (GKG_ENABLE=train_bf16) at the cfg4 shapes")
@@ -401,11 +474,12 @@ def main():
     lib = _lib.load()
     flush = torch.empty(128 << 20, dtype=torch.float32, device="cuda")
     if args.train:
-        rows = train_leg(args, lib, flush, linear_bf16.KINDS[args.amp])
+        rows = (grouped_leg if args.grouped else train_leg)(args, lib, flush, linear_bf16.KINDS[args.amp])
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             with open(args.out, "w") as fh:
-                json.dump(dict(tool="bench_lin_bf16 --train" + (" --amp f16" if args.amp == "f16" else ""), batch=args.batch or 32, reps=args.reps,
+                json.dump(dict(tool="bench_lin_bf16 --train" + (" --grouped --amp " + args.amp if args.grouped else "") +
+                               (" --amp f16" if args.amp == "f16" and not args.grouped else ""), batch=args.batch or 32, reps=args.reps,
                                device=torch.cuda.get_device_name(0), rows=rows), fh, indent=1)
         return
     if args.ffn:
